@@ -22,6 +22,8 @@ Extra objects on the JSON line: `roofline` (dominant kernel = whatever the dispa
 from HIP event pairs recorded on the launch stream inside this process), `roofline_hbm` (the HBM-bound
 decode kernel at M=1), `cpu_baseline` (the C oracle timed on the host cores, bounded sample) and
 `per_m` (per sweep point: us, TOPS, GB/s, speedup vs torch fp16 GEMM on the same GPU).
+
+--dump-outputs DIR writes the outputs of the last timed step (D_m<M>.npy, float32; see dump_outputs) for comparing two builds.
 """
 from __future__ import annotations
 
@@ -526,6 +528,33 @@ def write_detail(result):
     return None
 
 
+DUMP_MAX_ROWS = 512  # rows kept of a larger output: the five sweep outputs then take 37 MB as float32, under the 64 MB bound
+
+
+def dump_rows(M, max_rows=DUMP_MAX_ROWS, seed=0):
+    """the rows of an M-row output that --dump-outputs writes: all of them up to `max_rows`, else a fixed seeded sample (sorted)"""
+    if M <= max_rows:
+        return np.arange(M)
+    return np.sort(np.random.default_rng(seed + M).choice(M, size=max_rows, replace=False))
+
+
+def dump_outputs(dirname, outs):
+    """--dump-outputs: each output tensor {name: [M, N]} -> dirname/<name>.npy as float32 (a seeded row sample of a large one,
+    whose row indices go to dirname/<name>_rows.npy as float64); returns the bytes written"""
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in outs.items():
+        rows = dump_rows(t.shape[0])
+        if len(rows) < t.shape[0]:
+            t = t[torch.from_numpy(rows).to(t.device)]
+            np.save(os.path.join(dirname, f"{name}_rows.npy"), rows.astype(np.float64))
+            total += rows.size * 8
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        total += a.size * 4
+    return total
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -541,7 +570,12 @@ def main():
     ap.add_argument("--llama-budget", type=float, default=90.0, help="wall-clock bound of the configs[3] block, seconds")
     ap.add_argument("--check", action="store_true",
                     help="after the timed region verify the gathered outputs of the sharded points against a local full GEMM")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the fp16 output of every sweep point, as float32; a seeded row sample "
+                         f"of outputs above {DUMP_MAX_ROWS} rows) to DIR/D_m<M>.npy; the inputs are seeded, so runs with the same arguments compare")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -706,6 +740,8 @@ def main():
             run_step()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before anything below launches into the output buffers again
+        dump_outputs(args.dump_outputs, {f"D_m{M}": Dfull[M] for M in SWEEP_M})
     # per-step spread, measured AFTER the timed region with stream events (diagnostic only; `value` uses `dt`)
     step_us = []
     if not is_multi:

@@ -82,3 +82,33 @@ def test_printed_line_survives_pathological_blocks():
     assert len(line) < bench.LINE_LIMIT
     out = json.loads(line)
     assert "roofline" in out and "cpu_baseline" in out and out["llama7b"] == {"dropped": "see detail file"}
+
+
+def test_dump_outputs_is_seeded_and_bounded(tmp_path):
+    """--dump-outputs: the row sample of a large output is fixed run to run, the whole sweep stays under 64 MB, and what is
+    written is float32 holding exactly the fp16 values of the sampled rows"""
+    import numpy as np
+    import torch
+
+    import bench
+
+    r = bench.dump_rows(4096)
+    assert np.array_equal(r, bench.dump_rows(4096)) and len(r) == bench.DUMP_MAX_ROWS
+    assert np.all(np.diff(r) > 0) and r[0] >= 0 and r[-1] < 4096
+    assert np.array_equal(bench.dump_rows(16), np.arange(16))
+    total = sum(len(bench.dump_rows(M)) * bench.N_FULL * 4 + (8 * bench.DUMP_MAX_ROWS if M > bench.DUMP_MAX_ROWS else 0)
+                for M in bench.SWEEP_M)
+    assert total <= 64 * 2**20, total
+
+    g = torch.Generator().manual_seed(1)
+    big = torch.randn((bench.DUMP_MAX_ROWS + 88, 8), generator=g).half()
+    small = torch.randn((3, 8), generator=g).half()
+    n = bench.dump_outputs(str(tmp_path), {"D_big": big, "D_small": small})
+    got_big, got_small = np.load(tmp_path / "D_big.npy"), np.load(tmp_path / "D_small.npy")
+    rows = np.load(tmp_path / "D_big_rows.npy")
+    assert got_big.dtype == np.float32 and got_small.dtype == np.float32 and rows.dtype == np.float64
+    assert np.array_equal(rows, bench.dump_rows(big.shape[0]))
+    assert np.array_equal(got_big, big.float().numpy()[rows.astype(np.int64)])
+    assert np.array_equal(got_small, small.float().numpy())
+    assert n == got_big.nbytes + got_small.nbytes + rows.nbytes
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["D_big.npy", "D_big_rows.npy", "D_small.npy"]
