@@ -59,6 +59,11 @@ def lib():
     L.qqq_pack_int4.restype = ci
     L.qqq_unpack_int4.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp]
     L.qqq_unpack_int4.restype = ci
+    # include/qqq_amd_act.h
+    L.qqq_rmsnorm_quant.argtypes = [vp, vp, vp, ctypes.c_float, vp, vp, vp, ci, ci, ci, vp]
+    L.qqq_rmsnorm_quant.restype = ci
+    L.qqq_silu_mul_quant.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, vp]
+    L.qqq_silu_mul_quant.restype = ci
     L.qqq_amd_abi_version.restype = ci
     L.qqq_amd_last_error.restype = ctypes.c_char_p
     if L.qqq_amd_abi_version() != ABI_VERSION:

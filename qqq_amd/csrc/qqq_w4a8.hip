@@ -63,6 +63,8 @@
 #include "qqq_tiled.hip.h"
 #include "qqq_wide.hip.h"
 #include "qqq_small.hip.h"
+#include "qqq_act.hip.h"
+#include "../../include/qqq_amd_act.h"
 #include "qqq_rates.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1468,6 +1470,91 @@ extern "C" int qqq_dynamic_quant(const void* x, void* xq, void* s1, int m, int k
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_dynamic_quant_kernel launch");
   return QQQ_OK;
+}
+
+// ---- activation quantisers of a decoder block (include/qqq_amd_act.h; kernels in qqq_act.hip.h).  Same launch shapes as qqq_dynamic_quant:
+// 1024 threads per row for few rows (<= 2 per CU) or long rows, 256 otherwise; VPT 16-byte vectors per thread cover the row.
+template <template <int, int> class Launch, typename... Args>
+static int act_launch(const char* what, int m, int k, hipStream_t st, Args... args) {
+  const int nvec = k / 8;
+  const int vpt = (nvec + 255) / 256;
+  if ((m <= 512 || nvec > 2048) && vpt > 2) {
+    const int v4 = (nvec + 1023) / 1024;
+    if (v4 <= 2)
+      Launch<2, 1024>::run(m, st, args...);
+    else if (v4 <= 4)
+      Launch<4, 1024>::run(m, st, args...);
+    else
+      Launch<8, 1024>::run(m, st, args...);
+  } else if (vpt <= 2)
+    Launch<2, 256>::run(m, st, args...);
+  else if (vpt <= 4)
+    Launch<4, 256>::run(m, st, args...);
+  else
+    Launch<8, 256>::run(m, st, args...);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, what);
+  return QQQ_OK;
+}
+
+template <int VPT, int NT>
+struct RmsnormQuantLaunch {
+  static void run(int m, hipStream_t st, const _Float16* x, _Float16* r, const _Float16* w, float eps, _Float16* y, int8_t* xq, float* s1, int k) {
+    hipLaunchKernelGGL((qqq_rmsnorm_quant_kernel<VPT, NT>), dim3(m), dim3(NT), 0, st, x, r, w, eps, y, xq, s1, k);
+  }
+};
+
+template <int VPT, int NT>
+struct SiluMulQuantLaunch {
+  static void run(int m, hipStream_t st, const _Float16* g, int ldg, const _Float16* u, int ldu, _Float16* y, int8_t* xq, float* s1, int i) {
+    hipLaunchKernelGGL((qqq_silu_mul_quant_kernel<VPT, NT>), dim3(m), dim3(NT), 0, st, g, ldg, u, ldu, y, xq, s1, i);
+  }
+};
+
+static bool misaligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+extern "C" int qqq_rmsnorm_quant(const void* x, void* residual, const void* weight, float eps, void* y, void* xq, void* s1, int m, int k,
+                                 int dev, void* stream) {
+  g_err[0] = 0;
+  if (m >= 0 && k >= 0 && (m == 0 || k == 0)) return QQQ_OK;
+  if (m < 0 || k < 0 || (k % 8) != 0 || k > 65536) {
+    snprintf(g_err, sizeof(g_err), "qqq_rmsnorm_quant: bad shape m=%d k=%d (k must be a multiple of 8, at most 65536)", m, k);
+    return QQQ_ERR_ARG;
+  }
+  if (!x || !weight || !xq || !s1 || misaligned(x, 16) || misaligned(weight, 16) || (residual && misaligned(residual, 16)) ||
+      (y && misaligned(y, 16)) || misaligned(xq, 8) || misaligned(s1, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_rmsnorm_quant: bad argument (x / weight / xq / s1 must be non-NULL; x, weight, residual, y 16-byte, "
+             "xq 8-byte, s1 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  return act_launch<RmsnormQuantLaunch>("qqq_rmsnorm_quant_kernel launch", m, k, static_cast<hipStream_t>(stream),
+                                        static_cast<const _Float16*>(x), static_cast<_Float16*>(residual), static_cast<const _Float16*>(weight),
+                                        eps, static_cast<_Float16*>(y), static_cast<int8_t*>(xq), static_cast<float*>(s1), k);
+}
+
+extern "C" int qqq_silu_mul_quant(const void* gate, int ld_gate, const void* up, int ld_up, void* y, void* xq, void* s1, int m, int i,
+                                  int dev, void* stream) {
+  g_err[0] = 0;
+  if (m >= 0 && i >= 0 && (m == 0 || i == 0)) return QQQ_OK;
+  if (m < 0 || i < 0 || (i % 8) != 0 || i > 65536) {
+    snprintf(g_err, sizeof(g_err), "qqq_silu_mul_quant: bad shape m=%d i=%d (i must be a multiple of 8, at most 65536)", m, i);
+    return QQQ_ERR_ARG;
+  }
+  if (ld_gate < i || ld_up < i || (ld_gate % 8) != 0 || (ld_up % 8) != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_silu_mul_quant: bad row strides ld_gate=%d ld_up=%d (need >= i=%d and multiples of 8)", ld_gate, ld_up, i);
+    return QQQ_ERR_ARG;
+  }
+  if (!gate || !up || !xq || !s1 || misaligned(gate, 16) || misaligned(up, 16) || (y && misaligned(y, 16)) || misaligned(xq, 8) ||
+      misaligned(s1, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_silu_mul_quant: bad argument (gate / up / xq / s1 must be non-NULL; gate, up, y 16-byte, xq 8-byte, "
+             "s1 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  return act_launch<SiluMulQuantLaunch>("qqq_silu_mul_quant_kernel launch", m, i, static_cast<hipStream_t>(stream),
+                                        static_cast<const _Float16*>(gate), ld_gate, static_cast<const _Float16*>(up), ld_up,
+                                        static_cast<_Float16*>(y), static_cast<int8_t*>(xq), static_cast<float*>(s1), i);
 }
 
 extern "C" int qqq_quantlinear_forward(const void* x, void* xq, void* s1, const void* B, void* C, void* D,

@@ -379,3 +379,103 @@ def quantlinear_forward(x: torch.Tensor, B, C, s2, s3, workspace, bias=None, max
         _ptr(s3), m, n, k, workspace.data_ptr(), groupsize, x.device.index or 0, _stream_for(x), max_par, _ptr(bias), _ptr(W8))
     _raise_for(err, m, n, k, -1, -1, groupsize)
     return D
+
+
+# ---- activation quantisers of a decoder block (include/qqq_amd_act.h): the fp16 activation in front of a QuantLinear and its per-token
+# int8 quantisation in one launch; (xq, s1) are bit for bit dynamic_quant(y) of the activation y they compute.
+
+def _rmsnorm_quant_impl(x, weight, eps, residual, return_y):
+    if x.dtype != torch.float16 or not x.is_cuda or x.dim() < 1:
+        raise RuntimeError("rmsnorm_quant: expected an fp16 tensor on the GPU (there is no CPU path)")
+    k = x.shape[-1]
+    if weight.dtype != torch.float16 or weight.device != x.device or weight.numel() != k:
+        raise RuntimeError(f"rmsnorm_quant: weight must be an fp16 [{k}] tensor on x's device")
+    if residual is not None and (residual.dtype != torch.float16 or residual.device != x.device or residual.shape != x.shape
+                                 or not residual.is_contiguous()):
+        raise RuntimeError("rmsnorm_quant: residual must be a contiguous fp16 tensor of x's shape on x's device (it is updated in place)")
+    if x.numel() == 0:
+        return (x.new_empty(x.shape, dtype=torch.int8), x.new_empty(x.shape[:-1] + (1,), dtype=torch.float32),
+                x.new_empty(x.shape if return_y else (0,)))
+    x2 = x.reshape(-1, k).contiguous()
+    m = x2.shape[0]
+    xq = torch.empty((m, k), dtype=torch.int8, device=x.device)
+    s1 = torch.empty((m, 1), dtype=torch.float32, device=x.device)
+    y = torch.empty((m, k) if return_y else (0,), dtype=torch.float16, device=x.device)
+    err = _lib.lib().qqq_rmsnorm_quant(_ptr(x2), _ptr(residual), _ptr(weight.contiguous()), float(eps), _ptr(y), _ptr(xq), _ptr(s1), m, k,
+                                       x.device.index or 0, _stream_for(x))
+    if err:
+        raise RuntimeError(f"qqq_amd: rmsnorm_quant error {err}: {_lib.last_error()}")
+    return xq.reshape(x.shape), s1.reshape(x.shape[:-1] + (1,)), (y.reshape(x.shape) if return_y else y)
+
+
+@torch.library.custom_op("qqq_amd::rmsnorm_quant", mutates_args=("residual",))
+def _rmsnorm_quant_op(x: torch.Tensor, weight: torch.Tensor, eps: float, residual: Optional[torch.Tensor],
+                      return_y: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _rmsnorm_quant_impl(x, weight, eps, residual, return_y)
+
+
+@_rmsnorm_quant_op.register_fake
+def _(x, weight, eps, residual, return_y):
+    return (x.new_empty(x.shape, dtype=torch.int8), x.new_empty(x.shape[:-1] + (1,), dtype=torch.float32),
+            x.new_empty(x.shape if return_y else (0,), dtype=torch.float16))
+
+
+def rmsnorm_quant(x: torch.Tensor, weight: torch.Tensor, eps: float, residual: Optional[torch.Tensor] = None, return_y: bool = False):
+    """LlamaRMSNorm of an fp16 tensor (transformers' formula: fp32 norm, cast to fp16, times the fp16 weight) fused with the per-token int8
+    quantisation of its output: (int8 x.shape, f32 x.shape[:-1] + (1,)), plus the fp16 output y with `return_y`.  With `residual` the
+    input of the norm is fp16(residual + x), which is also written back into `residual` (the decoder's `residual = residual + h`)."""
+    if _compiling(x, weight, residual):
+        out = _rmsnorm_quant_op(x, weight, eps, residual, return_y)
+    else:
+        out = _rmsnorm_quant_impl(x, weight, eps, residual, return_y)
+    return out if return_y else out[:2]
+
+
+def _rows(t: torch.Tensor, i: int):
+    # (rows [m, i], row stride): a view where the kernel can read it in place (unit column stride, row stride >= i and a multiple of 8,
+    # 16-byte aligned base), a contiguous copy otherwise
+    r = t.reshape(-1, i)
+    ld = r.stride(0) if r.shape[0] > 1 else i
+    if r.stride(1) != 1 or ld < i or ld % 8 or r.data_ptr() % 16:
+        r, ld = r.contiguous(), i
+    return r, ld
+
+
+def _silu_mul_quant_impl(gate, up, return_y):
+    if gate.dtype != torch.float16 or up.dtype != torch.float16 or not gate.is_cuda or up.device != gate.device or gate.dim() < 1:
+        raise RuntimeError("silu_mul_quant: expected fp16 gate and up on the same GPU (there is no CPU path)")
+    if gate.shape != up.shape:
+        raise RuntimeError(f"silu_mul_quant: gate {tuple(gate.shape)} and up {tuple(up.shape)} must have the same shape")
+    i = gate.shape[-1]
+    if gate.numel() == 0:
+        return (gate.new_empty(gate.shape, dtype=torch.int8), gate.new_empty(gate.shape[:-1] + (1,), dtype=torch.float32),
+                gate.new_empty(gate.shape if return_y else (0,)))
+    (g2, ld_g), (u2, ld_u) = _rows(gate, i), _rows(up, i)
+    m = g2.shape[0]
+    xq = torch.empty((m, i), dtype=torch.int8, device=gate.device)
+    s1 = torch.empty((m, 1), dtype=torch.float32, device=gate.device)
+    y = torch.empty((m, i) if return_y else (0,), dtype=torch.float16, device=gate.device)
+    err = _lib.lib().qqq_silu_mul_quant(_ptr(g2), ld_g, _ptr(u2), ld_u, _ptr(y), _ptr(xq), _ptr(s1), m, i, gate.device.index or 0,
+                                        _stream_for(gate))
+    if err:
+        raise RuntimeError(f"qqq_amd: silu_mul_quant error {err}: {_lib.last_error()}")
+    return xq.reshape(gate.shape), s1.reshape(gate.shape[:-1] + (1,)), (y.reshape(gate.shape) if return_y else y)
+
+
+@torch.library.custom_op("qqq_amd::silu_mul_quant", mutates_args=())
+def _silu_mul_quant_op(gate: torch.Tensor, up: torch.Tensor, return_y: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _silu_mul_quant_impl(gate, up, return_y)
+
+
+@_silu_mul_quant_op.register_fake
+def _(gate, up, return_y):
+    return (gate.new_empty(gate.shape, dtype=torch.int8), gate.new_empty(gate.shape[:-1] + (1,), dtype=torch.float32),
+            gate.new_empty(gate.shape if return_y else (0,), dtype=torch.float16))
+
+
+def silu_mul_quant(gate: torch.Tensor, up: torch.Tensor, return_y: bool = False):
+    """F.silu(gate) * up on fp16 fused with the per-token int8 quantisation of the product: (int8 gate.shape, f32 gate.shape[:-1] + (1,)),
+    plus the fp16 product y with `return_y`.  gate / up may be strided views (e.g. the two halves of one fused gate|up output) as long as
+    their rows are contiguous; they are read in place."""
+    out = _silu_mul_quant_op(gate, up, return_y) if _compiling(gate, up) else _silu_mul_quant_impl(gate, up, return_y)
+    return out if return_y else out[:2]

@@ -162,6 +162,22 @@ class QuantLinear(nn.Module):
                                     self.bias, max_par=self.max_par, W8=self.W8)
         return D if out_shape is None else D.reshape(out_shape)
 
+    def forward_int8(self, xq: torch.Tensor, s1: torch.Tensor) -> torch.Tensor:
+        """forward() on an input that is already quantised per token -- (int8 [..., infeatures], f32 [..., 1]) as dynamic_quant,
+        rmsnorm_quant or silu_mul_quant return them: the same GEMM, bias and W8 handling, so forward_int8(*dynamic_quant(x)) is
+        bit-identical to forward(x).  Output fp16 [..., outfeatures]."""
+        if xq.dtype != torch.int8 or xq.shape[-1] != self.infeatures:
+            raise RuntimeError(f"forward_int8: xq must be int8 [..., {self.infeatures}]")
+        out_shape = xq.shape[:-1] + (self.outfeatures,)
+        A = xq.reshape(-1, self.infeatures).contiguous()
+        if s1.numel() != A.shape[0]:
+            raise RuntimeError(f"forward_int8: s1 must hold one scale per token ({A.shape[0]}), got {tuple(s1.shape)}")
+        D = torch.empty((A.shape[0], self.outfeatures), dtype=torch.float16, device=xq.device)
+        if A.shape[0]:
+            ops.qqq_gemm_w8(A, self.B, self.reduce_buffer, D, s1.reshape(-1, 1).contiguous(), self.s_channel, self.s_group, self.workspace,
+                            bias=self.bias, W8=self.W8, max_par=self.max_par)
+        return D.reshape(out_shape)
+
 
 def fuse_quant_linears(layers) -> QuantLinear:
     """Concatenate QuantLinear layers that share their input along the output dimension (q/k/v, gate/up:
