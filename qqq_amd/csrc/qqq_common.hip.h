@@ -43,14 +43,8 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 // that count (relaxed), barrier, and reads the deposits with agent-scope `sc1` loads -- no fences: an agent-scope acquire is a
 // `buffer_inv sc1` over the whole L2 (~3 us on the finisher's critical path, and it evicts every other workgroup's operand
 // lines on the XCD).  The formal variants are RUNTIME switches (tune.fused bits 2 / 3 -> `hflags`), so that the same library
-// runs both ways and the stress tests cover both (tests/test_gpu_parity.py); `-DQQQ_HANDOFF_ACQUIRE_FENCE` still forces bit 0.
-__device__ __forceinline__ bool qqq_formal_acquire(const int hflags) {
-#ifdef QQQ_HANDOFF_ACQUIRE_FENCE
-  return true;
-#else
-  return (hflags & 1) != 0;
-#endif
-}
+// runs both ways and the stress tests cover both (tests/test_gpu_parity.py).
+__device__ __forceinline__ bool qqq_formal_acquire(const int hflags) { return (hflags & 1) != 0; }
 __device__ __forceinline__ void qqq_publish_add(int* counter, const int hflags) {  // a depositor's "my deposit is complete"
   if (hflags & 2) __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
   else __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -405,10 +405,6 @@ __global__ __launch_bounds__(64 * WN * KG) void qqq_panel_kernel(
     // barrier (two workgroups sharing a CU) would otherwise read stage 2 rows for its first step.
     if constexpr (NBUF == 2 || RELAX) __syncthreads();
     QQQ_TR(1);
-#ifdef QQQ_PANEL_PRIO
-    // measurement: static priority for the later-dispatched half of the waves (the arbitration loser of every SIMD pair)
-    if (__builtin_amdgcn_readfirstlane(tid) >= NT / 2) __builtin_amdgcn_s_setprio(1);
-#endif
     // ---- steady state: PFS stages per iteration (ring slots are compile-time registers), branch-free ----
     int i0 = 0;
     for (; i0 + PFS <= nst; i0 += PFS) {

@@ -204,15 +204,11 @@ struct LaunchArgs {
 
 template <int MT, bool GROUPED, int WAVES, int PF>
 static hipError_t launch_stream_t(const LaunchArgs& a, int ksplit, int fused) {
-#ifdef QQQ_DEV_WIDE_ONLY  // measurement builds (tools/ab.py variants of the wide kernel): the other families are not compiled
-  return hipErrorNotSupported;
-#else
   dim3 grid((a.N + 127) / 128, ksplit & 0xffff, (a.M + 16 * MT - 1) / (16 * MT));
   hipLaunchKernelGGL((qqq_stream_kernel<MT, GROUPED, WAVES, PF>), grid, dim3(WAVES * 64), 0, a.stream,
                      a.A, a.B, a.C, a.D, a.s1, a.s2, a.s3, a.acc_out, a.tickets, a.bias, a.M, a.N, a.K,
                      ksplit, fused);
   return hipGetLastError();
-#endif
 }
 
 // prefetch depth PF (ring slots of 4 KiB weights per wave): deeper for the small-m bodies
@@ -252,14 +248,10 @@ static hipError_t launch_stream(const LaunchArgs& a, bool grouped, int mt, int w
 
 template <int MT, bool GROUPED, int WAVES, int PF>
 static hipError_t launch_column_t(const LaunchArgs& a, int ksplit) {
-#ifdef QQQ_DEV_WIDE_ONLY  // measurement builds (tools/ab.py variants of the wide kernel): the other families are not compiled
-  return hipErrorNotSupported;
-#else
   dim3 grid(a.N / 32, ksplit, (a.M + 16 * MT - 1) / (16 * MT));
   hipLaunchKernelGGL((qqq_column_kernel<MT, GROUPED, WAVES, PF>), grid, dim3(WAVES * 64), 0, a.stream, a.A,
                      a.B, a.C, a.D, a.s1, a.s2, a.s3, a.acc_out, a.bias, a.M, a.N, a.K, ksplit);
   return hipGetLastError();
-#endif
 }
 
 template <bool GROUPED>
@@ -283,9 +275,6 @@ static hipError_t launch_column(const LaunchArgs& a, bool grouped, int mt, int p
 
 template <int MT, bool GROUPED, int WN, int KG, int PFS, int XL, int HW = 1>
 static hipError_t launch_panel_t(const LaunchArgs& a, int ksplit) {
-#ifdef QQQ_DEV_WIDE_ONLY  // measurement builds (tools/ab.py variants of the wide kernel): the other families are not compiled
-  return hipErrorNotSupported;
-#else
   constexpr int ROWS = 16 * MT, BN = 32 * WN * HW;
   constexpr int XBUF = (qqq_panel_relaxed(KG, PFS, XL, HW) ? 4 : KG == 2 ? 2 : 3) * ROWS * 128;
   constexpr int EP = ROWS * (BN + 4) * 4;
@@ -305,7 +294,6 @@ static hipError_t launch_panel_t(const LaunchArgs& a, int ksplit) {
   hipLaunchKernelGGL(kern, grid, dim3(64 * WN * KG), LDS, a.stream, a.A, a.B, a.C, a.D, a.s1, a.s2, a.s3, a.acc_out,
                      a.tickets, a.bias, a.M, a.N, a.K, ksplit | ((a.hflags & 0xff) << 16) | ((ksplit > 1 ? a.skew & 0x3f : 0) << 24));
   return hipGetLastError();
-#endif
 }
 
 template <int MT, bool GROUPED, int PFS, int XL>
@@ -353,9 +341,6 @@ static hipError_t launch_panel(const LaunchArgs& a, bool grouped, int mt, int bn
 
 template <int BM, int MTW, int JW, int NB, bool GROUPED, int NS>
 static hipError_t launch_tiled_t(const LaunchArgs& a, int ksplit, int nslots, int pw) {
-#ifdef QQQ_DEV_WIDE_ONLY  // measurement builds (tools/ab.py variants of the wide kernel): the other families are not compiled
-  return hipErrorNotSupported;
-#else
   constexpr int WAVES = (BM / (32 * MTW)) * (4 / JW) * (2 / NB);
   constexpr int NT = WAVES * 64;
   constexpr int STAGE = 8 * 2048 + BM * 128 + ((NS > 0 && GROUPED) ? WAVES * 512 : 0);
@@ -377,7 +362,6 @@ static hipError_t launch_tiled_t(const LaunchArgs& a, int ksplit, int nslots, in
   hipLaunchKernelGGL(kern, grid, dim3(NT), LDS, a.stream, a.A, a.B, a.C, a.D, a.s1, a.s2, a.s3,
                      a.acc_out, a.bias, a.M, a.N, a.K, ksplit | (a.hflags << 16), tiles_m, tiles_n, a.tickets, nslots, pw);
   return hipGetLastError();
-#endif
 }
 
 // stages: 0 = register-staged; 2..4 = LDS-DMA ring depth (clamped to what fits in 160 KiB of LDS)
@@ -495,10 +479,9 @@ static hipError_t launch_wide_chain(const LaunchArgs& a, int mode, int mt, int b
   // (expanded weights: ring of 4 steps -- 64 registers; with 8 the walk's seam spills inside the stage loop: 32 registers, 75 scratch instructions)
   if (mode == 2) return launch_wide_t<2, 16, 4, 4, 2, true>(a, pw, 1);
   const bool grouped = mode == 1;
-  constexpr int GRS = QQQ_WIDE_DWORD != 0 ? 4 : 8;  // per-group ring depth of the walk (dword weight loads: 8 loads per step -- a ring of 8 steps would pass vmcnt's 63)
-  if (bn == 128) return grouped ? launch_wide_t<1, 16, 4, GRS, 1, true>(a, pw, 1) : launch_wide_t<0, 16, 4, 4, 1, true>(a, pw, 1);
-  if (mt == 8) return grouped ? launch_wide_t<1, 8, 4, GRS, 2, true>(a, pw, 1) : launch_wide_t<0, 8, 4, 4, 2, true>(a, pw, 1);
-  return grouped ? launch_wide_t<1, 16, 4, GRS, 2, true>(a, pw, 1) : launch_wide_t<0, 16, 4, 4, 2, true>(a, pw, 1);
+  if (bn == 128) return grouped ? launch_wide_t<1, 16, 4, 4, 1, true>(a, pw, 1) : launch_wide_t<0, 16, 4, 4, 1, true>(a, pw, 1);
+  if (mt == 8) return grouped ? launch_wide_t<1, 8, 4, 4, 2, true>(a, pw, 1) : launch_wide_t<0, 8, 4, 4, 2, true>(a, pw, 1);
+  return grouped ? launch_wide_t<1, 16, 4, 4, 2, true>(a, pw, 1) : launch_wide_t<0, 16, 4, 4, 2, true>(a, pw, 1);
 }
 // Automatic choice (profiles/r04_tile_walk_sweep.txt: plain vs walk over nine layer shapes x five token counts x both modes).
 // A seam costs 5.5 us (per-group 7) where the plain grid pays 9 us between two tiles of a CU (epilogue 6.3 + relaunch 0.2 +
@@ -951,15 +934,11 @@ static Plan make_plan(const int M, const int N, const int K, const bool grouped,
     // (128 x 128 tiles compile from the same template and were measured: 39 us at M=128 against the panel kernel's 36, 4 % ahead
     // of it only at 160-256 tokens in two K slices -- not instantiated; profiles/r03_wide_128x128.txt)
     pl.stages = 1;                                        // activation lead: the LDS-DMA of a stage is issued a full stage ahead
-    // weight ring in 64-k steps.  Round 3 had per-channel 4 / per-group 8 (8 measured 1.5 % ahead per-group THEN).  Round 5, same A/B with the variants repeated in the
-    // interleaved list (profiles/r05_wide_ring_depth.txt): for the 256 x 256 tiles it is now the other way round -- per-channel 8: 449.8 vs 456.2 us at 4096 tokens,
-    // per-group 4: 584.1 vs 594.4 -- and the compiled code says why: of the two instantiations of a mode the slower one carries the register spills (69 / 27 scratch
-    // instructions against 3, all in the epilogue, none in the loop: tools/code_object.py); the ring depth moves hipcc's allocation at the seam between loop and epilogue.
-    // The other shapes (no spills either way) measure level and keep their depths.
+    // weight ring: 4 steps of 64 k in every mode.  The packed modes load a step as 8 dwords per lane, and a ring of 8 steps would pass the 63 loads vmcnt
+    // counts (the depths measured before the dword loads, 4 against 8: profiles/r05_wide_ring_depth.txt).
     const bool big_tile = (pl.mt == 16 && pl.bm == 256);
     pl.w8 = have_w8 ? 1 : 0;
-    pl.pf = pl.w8 ? 4 : (t.pf == 8 || t.pf == 4) ? t.pf : (big_tile ? (grouped ? 4 : 8) : (grouped ? 8 : 4));
-    if (QQQ_WIDE_DWORD != 0 && !pl.w8) pl.pf = 4;  // (dword weight loads: 8 loads per step -- a ring of 8 steps would pass vmcnt's 63)
+    pl.pf = 4;
     pl.pw = (t.pw == 4 || t.pw == 8 || t.pw == 16 || t.pw == 32) ? t.pw : 8;
     const int rows = 16 * pl.mt;
     const long long tl = (long long)((M + rows - 1) / rows) * ((N + pl.bm - 1) / pl.bm);
@@ -987,7 +966,7 @@ static Plan make_plan(const int M, const int N, const int K, const bool grouped,
     // the persistent tile walk (t.glds: 1 = never, 2 = whenever it applies, 0 = automatic); its ring depth is the mode's default
     pl.chain = (t.glds != 1 && wide_chain_ok(M, N, K, rows, pl.bm, ksplit) && (t.glds == 2 || wide_chain_pays(tl, K, pl.mt, pl.bm))) ? 1 : 0;
     if (pl.chain && pl.w8 && !big_tile) pl.chain = 0;  // (the walk over expanded weights is instantiated for 256 x 256 tiles only)
-    if (pl.chain) pl.pf = pl.w8 ? 4 : (grouped && QQQ_WIDE_DWORD == 0) ? 8 : 4;
+    if (pl.chain) pl.pf = 4;
     return pl;
   }
 

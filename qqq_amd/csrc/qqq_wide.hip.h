@@ -18,13 +18,12 @@
 // The price: nothing hides a wave's own stalls (no partner on the SIMD) and an in-order wave issues one instruction per ~4
 // cycles, i.e. a 16-cycle MFMA leaves room for at most three others.  (Round 6 MEASURED it -- tools/mfma_issue_bench.hip: ~5.2 cycles
 // per instruction of any kind, TWO free behind an MFMA, nothing given back by an empty slot -- and rebuilt the loop against that: see
-// QQQ_WIDE_BALANCE / QQQ_WIDE_CURSORS / QQQ_WIDE_DWORD below; with DWORD the weights arrive as one-word loads and the quad transpose
-// described next is gone from the shipped loop.)  So:
+// the weight loads, the one-instruction items and the running cursors below.)  So:
 //   * the accumulators are updated IN PLACE by inline-asm MFMAs ("+a"): with the builtin hipcc selects the untied form in the
 //     accumulation registers and, all 256 of them live, bounces accumulators through VGPRs and scratch;
 //   * the issue order is pinned slot by slot (sched_barrier): slot k of a 64-k step = the MFMA of (m-tile k / 4, column set
-//     k % 4) + its share of everything else -- the NEXT step's weights (HBM -> VGPR ring, RS steps ahead) are transposed
-//     (4 x 4 quad transpose as four 3-instruction pieces) and unpacked into a second operand set over the whole step, every
+//     k % 4) + its share of everything else -- the NEXT step's weights (HBM -> VGPR ring, RS steps ahead) are unpacked into a
+//     second operand set over the whole step, every
 //     activation fragment is re-read from LDS for the next step right behind its fourth MFMA, and the activations are staged
 //     by LDS-DMA, one 16-byte chunk per lane every 16 slots (see "LDS-DMA staging" below; at first global -> VGPR -> ds_write).
 //     Everything is spread EVENLY: the four waves of a workgroup run in lock step (one barrier per stage), so anything issued
@@ -39,7 +38,7 @@
 // ------------------------------------------------------------------------------------------
 
 // Measurement only (tools/ablate_wide.sh): -DQQQ_WIDE_ABLATE=<bits> removes parts of the steady-state loop -- 1 stage-end
-// barrier, 2 activation staging, 4 transpose + unpack VALU, 8 weight-ring refill, 16 LDS fragment reads.  Results are wrong
+// barrier, 2 activation staging, 4 unpack VALU, 8 weight-ring refill, 16 LDS fragment reads.  Results are wrong
 // by construction; never defined in a shipped build.
 #ifndef QQQ_WIDE_ABLATE
 #define QQQ_WIDE_ABLATE 0
@@ -74,40 +73,20 @@ __device__ __forceinline__ v4u wide_load16(__amdgpu_buffer_rsrc_t view, const un
   return __builtin_amdgcn_raw_buffer_load_b128(view, voff, soff, 0);
 }
 
-// Measurement / tuning: QQQ_WIDE_SLOTMAP=1 keeps the unpack items of the per-channel 256-token shape out of the slots that
-// already carry a memory instruction (fragment re-read, staging write / reload, ring refill): a memory instruction takes
-// more than one issue slot, and with a VALU item behind it the slot overruns its MFMA's 16 cycles.
-#ifndef QQQ_WIDE_FLUSH_AUX
-#define QQQ_WIDE_FLUSH_AUX 0  // cache policy of the tile walk's D stores (buffer aux bits: 1 sc0, 2 nt, 16 sc1); measurement builds set it
-#endif
-// QQQ_WIDE_STAGGER = d > 0 (round 6): the four waves of a workgroup run d issue slots apart instead of in lock step.  Wave w takes the stage barrier d (3 - w)
-// slots INTO the next stage (wave 3 in front of its first MFMA, wave 0 behind its 3 d-th): all four meet at the same moment, so wave w runs d (3 - w) slots
-// ahead of wave 3 from then on -- and no two waves hand the LDS / the vector-memory unit the same instruction in the same cycle.  0: one common barrier.
-#ifndef QQQ_WIDE_STAGGER
-#define QQQ_WIDE_STAGGER 0
-#endif
-#ifndef QQQ_WIDE_SLOTMAP
-#define QQQ_WIDE_SLOTMAP 5  // bit 0: per-channel, bit 1: per-group, bit 2: the 128-token shape too
-#endif
 // The static roles of the NSLOT = 2 * HW * MT issue slots of a 64-k step (slot k: m-tile k / (2 HW), column set k % (2 HW)).
 // HW = 2 (64 columns per wave): fragment re-read behind every fourth MFMA, ring refill in slots 2 and 6, the LDS-DMA's M0 in
 // slot 8 and the DMA itself in slot 9 of every 16, group scales in slot 1 of a stage's second step; unpack items in the rest.
 // HW = 1 (32 columns per wave, 256 x 128 tiles): every ODD slot re-reads a fragment, so everything else sits in even ones.
 __host__ __device__ constexpr bool wide_frag_slot(int hw, int k) { return k % (2 * hw) == 2 * hw - 1; }
-__host__ __device__ constexpr bool wide_refill_slot(int hw, int k, int hf) { return hf < hw && k == 2 + 4 * hf; }
-// QQQ_WIDE_DWORD (round 6): the packed weights of a step come in as FOUR 4-byte loads per lane and 32-column half instead of one 16-byte load + a 4 x 4 quad transpose:
+// Weight loads (round 6): the packed weights of a step come in as FOUR 4-byte loads per lane and 32-column half instead of one 16-byte load + a 4 x 4 quad transpose:
 // MFMA lane (h, cq, jt) needs the words jt of the pieces kq = 0 .. 3 of its chunk, i.e. the dwords at chunk + 16 kq + 4 jt -- load kq fetches exactly that (a quad of lanes
 // takes 16 contiguous bytes; the four loads of a half touch the same lines, the first brings them into the L1).  13 issue slots' worth of transpose (4 VCC writes, 8 DPP
 // selects, in a loop that is issue-bound wherever it is not power-bound: per-group everywhere, per-channel in the 128-token / 128-column shapes) against 3 more loads.
 // The loads of a step sit one per slot (wide_dw_load_index); ring of 4 steps only (8 steps x 8 loads would pass vmcnt's 63).
 // Measured (profiles/r06b_wide_dword_loads.txt, interleaved A/B): 4096 tokens 427 - 435 -> 422 - 427 us, 1024 tokens (128 x 256 tiles) 123.5 - 124.5 -> 119.1, 320 ... 768 -1 ... -2 %,
 // per-group 4096 -2 %, 512 -2.5 %; Llama-2-7B layers level ... -2.5 %; no point slower.  Loop: 1.38 -> 1.09 extras per MFMA per-channel, 3.2 -> 2.9 per-group, 2.5 -> 1.8 in the
-// 128-token shape.  On.
-#ifndef QQQ_WIDE_DWORD
-#define QQQ_WIDE_DWORD 1
-#endif
-__host__ __device__ constexpr bool wide_dw(int mode) { return QQQ_WIDE_DWORD != 0 && mode != 2; }
-__host__ __device__ constexpr int wide_dw_load_index(int mt, int hw, int k) {  // DWORD: the load 4 hf + kq that slot k issues; -1: none
+// 128-token shape.  (The expanded int8 weights of mode 2 keep their 16-byte loads: they are the MFMA operands as loaded.)
+__host__ __device__ constexpr int wide_dw_load_index(int mt, int hw, int k) {  // packed modes: the load 4 hf + kq that slot k issues; -1: none
   if (hw == 2) {
     if (mt == 8) {  // (128-token tiles, 32 slots: slot 30 is the stage's wait + barrier, and the ring cursor needs a plain slot behind the last load)
       constexpr int at[8] = {2, 5, 6, 10, 14, 18, 22, 26};
@@ -119,14 +98,12 @@ __host__ __device__ constexpr int wide_dw_load_index(int mt, int hw, int k) {  /
   }
   return k == 2 ? 0 : k == 8 ? 1 : k == 10 ? 2 : k == 16 ? 3 : -1;
 }
-// the ring load(s) of slot k in any mode: >= 0 an index (packed: the half hf; DWORD: 4 hf + kq; expanded: the column set), -1 none
+// the ring load of slot k in any mode: >= 0 an index (packed: 4 hf + kq; expanded: the column set), -1 none
 __host__ __device__ constexpr int wide_ring_load(int mode, int mt, int hw, int k) {
   if (mode == 2) return k % ((2 * hw * mt) / (2 * hw)) == 2 ? k / ((2 * hw * mt) / (2 * hw)) : -1;
-  if (wide_dw(mode)) return wide_dw_load_index(mt, hw, k);
-  return wide_refill_slot(hw, k, 0) ? 0 : wide_refill_slot(hw, k, 1) ? 1 : -1;
+  return wide_dw_load_index(mt, hw, k);
 }
-__host__ __device__ constexpr int wide_ring_last_slot(int mode, int mt, int hw, int hf) {  // the slot that issues the LAST load of half hf of a step (packed modes)
-  if (!wide_dw(mode)) return 2 + 4 * hf;
+__host__ __device__ constexpr int wide_ring_last_slot(int mt, int hw, int hf) {  // the slot that issues the LAST load of half hf of a step (packed modes)
   int last = 0;
   for (int k = 0; k < 2 * hw * mt; ++k)
     if (wide_dw_load_index(mt, hw, k) == 4 * hf + 3) last = k;
@@ -136,35 +113,18 @@ __host__ __device__ constexpr int wide_dma_period(int mt, int hw) { return (2 * 
 __host__ __device__ constexpr bool wide_m0_slot(int mt, int hw, int k) { return k % wide_dma_period(mt, hw) == (hw == 2 ? 8 : 4); }
 __host__ __device__ constexpr bool wide_dma_slot(int mt, int hw, int k) { return k % wide_dma_period(mt, hw) == (hw == 2 ? 9 : 6); }
 __host__ __device__ constexpr int wide_scale_slot(int hw) { return hw == 2 ? 1 : 0; }
-__host__ __device__ constexpr bool wide_item_slot(int hw, int k) {  // slots of a step that take an unpack item
-  if (hw == 1) return k % 2 == 0 && k != 2 && k % 8 != 6;
-  return (k % 4 == 0) || (k % 4 == 2 && k != 2 && k != 6) || (k % 8 == 5);
-}
-__host__ __device__ constexpr int wide_item_slots_before(int hw, int k) {  // number of item slots in [0, k)
-  int n = 0;
-  for (int j = 0; j < k; ++j) n += wide_item_slot(hw, j) ? 1 : 0;
-  return n;
-}
 
-// QQQ_WIDE_BALANCE (round 6): the issue model of a wave that is alone on its SIMD, measured (tools/mfma_issue_bench.hip, profiles/r06_mfma_issue_model.txt): every
+// One-instruction items, dealt by capacity (round 6): the issue model of a wave that is alone on its SIMD, measured (tools/mfma_issue_bench.hip, profiles/r06_mfma_issue_model.txt): every
 // instruction -- VALU, SALU, s_nop, a wait that does not block -- takes the wave ~5.2 cycles of issue; behind a 16-cycle MFMA TWO of them are free, the third costs its
 // full 4 - 5 cycles, and an empty slot gives nothing back (3 VALU behind every other MFMA: 18.5 cycles per MFMA, 1.5 behind every one: 16.5).  A ds_read_b128 takes ~12
-// cycles (alone in a slot: free; with two VALU next to it: + 13), an LDS-DMA ~17 (+ 6 whatever shares its slot).  The quad transpose's pieces were 3-instruction blocks
-// (s_mov_b64 vcc + two DPP selects; with hipcc's hazard s_nop and the ring wait in front: 4 - 5 instructions in ONE slot, eight times per 64-k step).  So: every unpack
-// item is ONE instruction (the transpose's thirteen per half: the ring wait, then per piece the VCC write and its two selects, in order -- nothing else in the loop writes
-// VCC, tests/test_code_object_cpu.py checks the compiled code), and the items are dealt to the slots by CAPACITY: 0 where the slot already carries a fragment re-read, an
+// cycles (alone in a slot: free; with two VALU next to it: + 13), an LDS-DMA ~17 (+ 6 whatever shares its slot).  So: every unpack item is ONE instruction (per
+// half: the ring wait, then the unpack parts, in order), and the items are dealt to the slots by CAPACITY: 0 where the slot already carries a fragment re-read, an
 // LDS-DMA or a ring refill, 1 next to the DMA's M0 write, 2 elsewhere (scaled up together where a shape has more items than that: per-group, 128-token and 128-column tiles).
-#ifndef QQQ_WIDE_BALANCE
-#define QQQ_WIDE_BALANCE 1
-#endif
-// QQQ_WIDE_CURSORS (round 6): the plain kernel's loop loads read through running scalar offsets (one s_add per load kind and stage, as the tile walk's cursors) instead
+// Running cursors (round 6): the plain kernel's loop loads read through running scalar offsets (one s_add per load kind and stage, as the tile walk's cursors) instead
 // of offsets worked out per step from the stage index with a clamp (s_add, s_min, s_add, s_mul in ONE issue slot, three times per stage).  The clamp ("past the end of
 // the K slice: re-read its last stage") goes: the descriptors END where their tensors end, so a load past the end of K is either the next slice's / next row's data
 // (in range, never used) or out of range for the buffer unit (returns zeros, never used).
-#ifndef QQQ_WIDE_CURSORS
-#define QQQ_WIDE_CURSORS 1
-#endif
-// Fixed duties that sit in the slot schedule next to the loads (BALANCE): the stage-end wait + barrier (step parity 1) and, with running cursors (QQQ_WIDE_CURSORS),
+// Fixed duties that sit in the slot schedule next to the loads: the stage-end wait + barrier (step parity 1) and, with running cursors (the plain kernel),
 // one scalar add per load kind -- each in a slot of its own choosing, its capacity reduced accordingly.
 __host__ __device__ constexpr int wide_w8_refill_index_(int mt, int hw, int k) { return k % ((2 * hw * mt) / (2 * hw)) == 2 ? k / ((2 * hw * mt) / (2 * hw)) : -1; }
 __host__ __device__ constexpr bool wide_plain_slot(int mode, int mt, int hw, int k) {  // no load, no fragment re-read, no M0 write in this slot
@@ -198,72 +158,19 @@ __host__ __device__ constexpr int wide_ring_inc_slot(int mode, int mt, int hw) {
 }
 __host__ __device__ constexpr int wide_dma_inc_slot(int, int, int) { return 0; }  // (slot 0 carries no load, no fragment re-read and no M0 write in any shape)
 __host__ __device__ constexpr int wide_scale_inc_slot(int mode, int mt, int hw) { return wide_plain_after(mode, mt, hw, wide_scale_slot(hw), 2); }
-// QQQ_WIDE_XWAIT (round 6): the fragment re-reads are inline asm as well, their lgkmcnt waits hand-placed.  hipcc put a wait behind 8 of the 16 re-reads of a step --
-// INTO the slot that already carries the ds_read_b128 (~12 cycles of issue): MFMA + ds_read + wait = 22 cycles, 6 lost eight times per step.  Here: one wait per group of
-// four m-tiles, in the last plain slot in front of the group's first MFMA of the NEXT step (group 0: in the tail of the step that issued the reads).  LDS reads return in
-// issue order (nothing else in the loop counts in lgkmcnt), so "group j has landed" == "at most <reads issued since its last one> are outstanding"; tools/check_waits.py
-// replays the compiled loop (every instruction against the reads still in flight).
-// Built, replayed clean on every instantiation, GPU suite green -- and measured LEVEL (profiles/r06_wide_balanced_slots.txt: 4096 tokens 423.2 - 427.3 us without, 422.9 -
-// 425.9 with): once the slots are balanced the launch sits on the part's power limit again, and issue cycles saved come back as clock lost.  Off; the compiler's waits stay.
-#ifndef QQQ_WIDE_XWAIT
-#define QQQ_WIDE_XWAIT 0
-#endif
-__host__ __device__ constexpr int wide_frag_slot_of(int hw, int m) { return 2 * hw * m + 2 * hw - 1; }  // the slot whose extras re-read x[m]
-// the wait slot of group j (m-tiles 4 j .. 4 j + 3): as an ABSOLUTE slot on the two-step timeline (step 0 issues the reads, step 1 uses them); -1: no such group
-__host__ __device__ constexpr int wide_xw_abs(int mode, int mt, int hw, int j) {
-  const int nslot = 2 * hw * mt;
-  if (4 * j >= mt) return -1;
-  const int use = nslot + 2 * hw * 4 * j;  // first MFMA of the group in step 1
-  for (int a = use - 2; a > wide_frag_slot_of(hw, 4 * j + 3); --a) {
-    const int k = a % nslot;
-    if (wide_plain_slot(mode, mt, hw, k) && k != wide_barrier_slot(mode, mt, hw)) return a;
-  }
-  return -1;
-}
-__host__ __device__ constexpr int wide_xw_count(int mode, int mt, int hw, int j) {  // re-reads issued behind the group's last one and in front of its wait
-  const int nslot = 2 * hw * mt, a = wide_xw_abs(mode, mt, hw, j), last = wide_frag_slot_of(hw, 4 * j + 3);
-  int n = 0;
-  for (int step = 0; step < 2; ++step)
-    for (int m = 0; m < mt; ++m) {
-      const int at = step * nslot + wide_frag_slot_of(hw, m);
-      if (at > last && at < a) ++n;
-    }
-  return n;
-}
-__host__ __device__ constexpr int wide_xw_count_at(int mode, int mt, int hw, int k) {  // the wait of slot k of a step: lgkmcnt(n) (the strictest of the groups that wait here); -1: none
-  int n = -1;
-  for (int j = 0; 4 * j < mt; ++j)
-    if (wide_xw_abs(mode, mt, hw, j) >= 0 && wide_xw_abs(mode, mt, hw, j) % (2 * hw * mt) == k && (n < 0 || wide_xw_count(mode, mt, hw, j) < n)) n = wide_xw_count(mode, mt, hw, j);
-  return n;
-}
-// QQQ_WIDE_CHAINPREP (round 6, tile walk): the offsets of a stage's loads are prepared one stage AHEAD, in plain slots of the previous stage's second step (two register
-// sets, picked by the stage's compile-time parity), instead of at the stage's start -- where copies, cursor adds and the tile-end test stood in ONE slot: 13 instructions
-// between two MFMAs, once per stage (tools/slot_load.py).  What is left at the boundary: the countdown, the seam test, the "last P stages" test.
-// Measured (profiles/r06c_tile_walk_prepared_offsets.txt): level.  The walk kernels are out of SGPRs (106, two spilled), hipcc keeps the loop-carried set in VGPRs and the
-// v_readfirstlane read-backs -- which must stand at the stage head, five wait states ahead of the first load -- cost what the boundary bookkeeping did.  Parity-clean, off.
-#ifndef QQQ_WIDE_CHAINPREP
-#define QQQ_WIDE_CHAINPREP 0
-#endif
-__host__ __device__ constexpr int wide_prep_slot(int mode, int mt, int hw, int j) { return wide_plain_after(mode, mt, hw, -1, j); }  // the j-th plain slot of a step (j = 0 .. 3)
-__host__ __device__ constexpr int wide_bal_cap(int mode, int mt, int hw, int t, int k, int cursors) {  // cursors: 0 none, 1 the plain kernel's running cursors, 2 the tile walk's prepared offsets
+__host__ __device__ constexpr int wide_bal_cap(int mode, int mt, int hw, int t, int k, int cursors) {  // cursors: 1 the plain kernel's running cursors, 0 none (tile walk)
   if (!wide_plain_slot(mode, mt, hw, k)) return wide_m0_slot(mt, hw, k) && !wide_frag_slot(hw, k) && !wide_dma_slot(mt, hw, k) ? 1 : 0;
   int c = 2;
   if (t == 1 && k == wide_barrier_slot(mode, mt, hw)) c -= 2;
-  if (QQQ_WIDE_XWAIT != 0 && wide_xw_count_at(mode, mt, hw, k) >= 0) c -= 1;
   if (cursors == 1) {
     if (k == wide_ring_inc_slot(mode, mt, hw)) c -= 1;
     if (t == 0 && k == wide_dma_inc_slot(mode, mt, hw)) c -= 1;
     if (mode == 1 && t == 1 && k == wide_scale_inc_slot(mode, mt, hw)) c -= 1;
   }
-  if (cursors == 2 && t == 1) {
-    if (k == wide_prep_slot(mode, mt, hw, 0) || k == wide_prep_slot(mode, mt, hw, 1) || (mode == 1 && k == wide_prep_slot(mode, mt, hw, 3))) c -= 2;
-    if (k == wide_prep_slot(mode, mt, hw, 2)) c -= 1;
-  }
   return c < 0 ? 0 : c;
 }
-__host__ __device__ constexpr int wide_bal_head(int mode) { return wide_dw(mode) ? 1 : 13; }  // per 32-column half: the ring wait, then (unless DWORD) 4 x (VCC write, 2 selects)
-__host__ __device__ constexpr int wide_bal_items(int mode) { return wide_bal_head(mode) + (mode == 1 ? 32 : 12); }  // ... then the unpack parts
-__host__ __device__ constexpr int wide_bal_cost(int mode, int w) { return w < wide_bal_head(mode) ? 1 : (mode == 1 ? 2 : 1); }  // instructions of item w of a half
+__host__ __device__ constexpr int wide_bal_items(int mode) { return 1 + (mode == 1 ? 32 : 12); }  // per 32-column half (packed modes): the ring wait, then the unpack parts
+__host__ __device__ constexpr int wide_bal_cost(int mode, int w) { return w == 0 ? 1 : (mode == 1 ? 2 : 1); }  // instructions of item w of a half
 // number of items (of the hw * wide_bal_items(mode) of a step, in order) dealt to slots [0, k): item i goes to the first slot whose cumulative share of the capacity
 // reaches the item's cumulative share of the instructions
 __host__ __device__ constexpr int wide_bal_before(int mode, int mt, int hw, int t, int k, int cursors) {
@@ -313,7 +220,7 @@ struct WideBalTable {
 };
 
 static_assert(WideBalTable<0, 16, 2, 0, 1>::tab.before[17] == wide_bal_before(0, 16, 2, 0, 17, 1) && WideBalTable<0, 16, 2, 1, 1>::tab.before[63] == wide_bal_before(0, 16, 2, 1, 63, 1) &&
-                  WideBalTable<1, 8, 2, 1, 0>::tab.before[9] == wide_bal_before(1, 8, 2, 1, 9, 0) && WideBalTable<1, 16, 1, 0, 2>::tab.before[30] == wide_bal_before(1, 16, 1, 0, 30, 2),
+                  WideBalTable<1, 8, 2, 1, 0>::tab.before[9] == wide_bal_before(1, 8, 2, 1, 9, 0) && WideBalTable<1, 16, 1, 0, 0>::tab.before[30] == wide_bal_before(1, 16, 1, 0, 30, 0),
               "the table is the function");
 
 // LDS-DMA staging: the activations go global -> LDS directly (buffer_load_dwordx4 ... lds, one
@@ -501,7 +408,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   };
   // (CHAIN: one descriptor over the whole tensor, the tile's column group goes into the scalar offset -- ng * 512 / ng * 128 bytes)
   v4u wdesc = descriptor(CHAIN ? (const void*)B : (const void*)(B + (size_t)ng * (W8 ? 4096 : 512)));
-  constexpr bool CUR = !CHAIN && QQQ_WIDE_CURSORS != 0;
+  constexpr bool CUR = !CHAIN;  // the plain kernel's loop loads read through running cursors
   if constexpr (CUR) {  // the descriptor ends with the tensor (packed: K / 16 rows of 8 N bytes; expanded: K x N bytes -- below 4 GiB, the host sends larger ones elsewhere)
     const unsigned long long total = W8 ? (unsigned long long)K * (unsigned)N : ((unsigned long long)K * (unsigned)N) >> 1;
     wdesc[2] = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(total - (unsigned long long)ng * (W8 ? 4096u : 512u)));
@@ -652,9 +559,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int q = 0; q < NQ; ++q) acc[mt][q] = (v4i){0, 0, 0, 0};
 
   v4u wr[RS][WRN];
-  constexpr bool DW = wide_dw(MODE);
-  static_assert(!DW || QQQ_WIDE_BALANCE != 0, "the dword loads are scheduled by the balanced slot plan");
-  unsigned wq[DW ? RS : 1][HW][4];  // DWORD: the ring as words [step][half][kq] -- word jt (this lane's) of piece kq of the lane's chunk
+  constexpr bool DW = !W8;          // packed modes: the weights come in as dword loads
+  unsigned wq[DW ? RS : 1][HW][4];  // packed modes: the ring as words [step][half][kq] -- word jt (this lane's) of piece kq of the lane's chunk
   const unsigned woff_dw = (unsigned)h * rowbytes + (unsigned)(cq * 64 + q4 * 4 + 256 * whalf);  // + step * wstep (scalar) + 256 hf + 16 kq (immediate)
   auto asm_load_d = [&](unsigned& dst, auto ic, unsigned so, auto rawc) __attribute__((always_inline)) {  // load index 4 hf + kq; rawc: `so` is a cursor (no copy)
     constexpr int li = decltype(ic)::value;
@@ -678,72 +584,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   auto read_x = [&](const int buf, const int t, const int mt) {
     x[mt] = *reinterpret_cast<const v4i*>(smem + buf * XB + xrd_t[t] + mt * 2048);
   };
-  // the loop's re-reads as inline asm (QQQ_WIDE_XWAIT): LDS byte address (the dynamic LDS starts at 0, as the LDS-DMA's M0 presumes) = lane part + a 16-bit
-  // immediate; the stage buffers span more than 64 KiB, so there is a second lane part 64 KiB up
-  // (not in the tile walk: with asm-defined fragments in every stage's basic block hipcc's allocator gives up -- 167 - 227 spilled registers when tried)
-  constexpr bool XW = QQQ_WIDE_XWAIT != 0 && QQQ_WIDE_BALANCE != 0 && !(QQQ_WIDE_ABLATE & 16) && !CHAIN;
-  static_assert(!XW || (wide_xw_abs(MODE, MT, HW, 0) >= 0 && wide_xw_abs(MODE, MT, HW, MT / 4 - 1) >= 0), "every group of four m-tiles has a slot for its wait");
-  const unsigned xrd_hi[2] = {xrd_t[0] + 65536u, xrd_t[1] + 65536u};
-  auto read_x_asm = [&](auto bufc, auto tc, auto mtc) __attribute__((always_inline)) {
-    constexpr int imm = decltype(bufc)::value * XB + decltype(mtc)::value * 2048, tt = decltype(tc)::value;
-    (void)xrd_hi[0], (void)xrd_t[0], (void)x[0];
-    if constexpr (imm >= 65536) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x[decltype(mtc)::value]) : "v"(xrd_hi[tt]), "n"(imm - 65536));
-    else asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(x[decltype(mtc)::value]) : "v"(xrd_t[tt]), "n"(imm));
-  };
 
-  // ---- the unpack of one 32-column half (hf) of a step, cut into pieces that are placed one by one between the MFMAs ----
-  // transpose: the two butterfly stages of quad_transpose4 (qqq_common.hip.h) as four 3-instruction pieces (lane masks kept
-  // in SGPR pairs, one s_mov_b64 into VCC per piece); pieces sit in different issue slots, which also covers the two wait
-  // states a DPP source needs behind the VALU that wrote it
-  unsigned z[4], y[4];
-  const unsigned long long km5 = 0x5555555555555555ull, kma = 0xaaaaaaaaaaaaaaaaull, km3 = 0x3333333333333333ull, kmc = 0xccccccccccccccccull;
-  auto tr_piece = [&](auto pc, const v4u& w) {
-    constexpr int pi = decltype(pc)::value;
-    (void)y[0];  // (odr-use outside the discarded branches: clang does not capture from inside them)
-    (void)z[0];
-    if constexpr (pi == 0)       // z0 = even ? w0 : w1',  z2 = even ? w2 : w3'
-      asm volatile("s_mov_b64 vcc, %6\n\t"
-                   "v_cndmask_b32_dpp %0, %3, %2, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_cndmask_b32_dpp %1, %5, %4, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
-                   : "=&v"(z[0]), "=&v"(z[2]) : "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "s"(km5) : "vcc");
-    else if constexpr (pi == 1)  // z1 = odd ? w1 : w0',  z3 = odd ? w3 : w2'
-      asm volatile("s_mov_b64 vcc, %6\n\t"
-                   "v_cndmask_b32_dpp %0, %2, %3, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_cndmask_b32_dpp %1, %4, %5, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
-                   : "=&v"(z[1]), "=&v"(z[3]) : "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "s"(kma) : "vcc");
-    else if constexpr (pi == 2)  // y0 = lo ? z0 : z2'',  y1 = lo ? z1 : z3''
-      asm volatile("s_mov_b64 vcc, %6\n\t"
-                   "v_cndmask_b32_dpp %0, %4, %2, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_cndmask_b32_dpp %1, %5, %3, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
-                   : "=&v"(y[0]), "=&v"(y[1]) : "v"(z[0]), "v"(z[1]), "v"(z[2]), "v"(z[3]), "s"(km3) : "vcc");
-    else                         // y2 = hi ? z2 : z0'',  y3 = hi ? z3 : z1''
-      asm volatile("s_mov_b64 vcc, %6\n\t"
-                   "v_cndmask_b32_dpp %0, %2, %4, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n\t"
-                   "v_cndmask_b32_dpp %1, %3, %5, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf"
-                   : "=&v"(y[2]), "=&v"(y[3]) : "v"(z[0]), "v"(z[1]), "v"(z[2]), "v"(z[3]), "s"(kmc) : "vcc");
-  };
-  // the same four pieces one INSTRUCTION at a time (QQQ_WIDE_BALANCE): si = 0 the piece's VCC write, 1 / 2 its two selects.  VCC carries from one statement to the
-  // next: nothing else in the steady-state loop writes it (the asm statements keep their order; the compiled loop is checked by tests/test_code_object_cpu.py)
-  auto tr_single = [&](auto pc, auto sc, const v4u& w) {
-    constexpr int pi = decltype(pc)::value, si = decltype(sc)::value;
-    (void)y[0];
-    (void)z[0];
-    if constexpr (si == 0) {
-      asm volatile("s_mov_b64 vcc, %0" : : "s"(pi == 0 ? km5 : pi == 1 ? kma : pi == 2 ? km3 : kmc) : "vcc");
-    } else if constexpr (pi == 0) {
-      if constexpr (si == 1) asm volatile("v_cndmask_b32_dpp %0, %2, %1, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=&v"(z[0]) : "v"(w[0]), "v"(w[1]));
-      else asm volatile("v_cndmask_b32_dpp %0, %2, %1, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=&v"(z[2]) : "v"(w[2]), "v"(w[3]));
-    } else if constexpr (pi == 1) {
-      if constexpr (si == 1) asm volatile("v_cndmask_b32_dpp %0, %1, %2, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=&v"(z[1]) : "v"(w[0]), "v"(w[1]));
-      else asm volatile("v_cndmask_b32_dpp %0, %1, %2, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf" : "=&v"(z[3]) : "v"(w[2]), "v"(w[3]));
-    } else if constexpr (pi == 2) {
-      if constexpr (si == 1) asm volatile("v_cndmask_b32_dpp %0, %2, %1, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "=&v"(y[0]) : "v"(z[0]), "v"(z[2]));
-      else asm volatile("v_cndmask_b32_dpp %0, %2, %1, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "=&v"(y[1]) : "v"(z[1]), "v"(z[3]));
-    } else {
-      if constexpr (si == 1) asm volatile("v_cndmask_b32_dpp %0, %1, %2, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "=&v"(y[2]) : "v"(z[0]), "v"(z[2]));
-      else asm volatile("v_cndmask_b32_dpp %0, %1, %2, vcc quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf" : "=&v"(y[3]) : "v"(z[1]), "v"(z[3]));
-    }
-  };
+  // ---- the unpack of one 32-column half (hf) of a step, cut into one-instruction items that are placed one by one between the MFMAs ----
   // per-channel: 12 VALU (and | shift, and per packed word); per-group: 8 x dequant_group4 in 4 two-instruction parts
   const unsigned nmask = QQQ_NIB_MASK;
   h2 sb[2];                    // per-group: the half's two group scales, broadcast
@@ -756,7 +598,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       sb[1] = (h2){sc[1], sc[1]};
     }
   };
-  auto un_part = [&](auto pc, auto hfc, v4i (&a)[NQ], const unsigned (&y)[4]) {  // y: the half's four words (the transpose's output, or -- DWORD -- the ring registers themselves)
+  auto un_part = [&](auto pc, auto hfc, v4i (&a)[NQ], const unsigned (&y)[4]) {  // y: the half's four words (the ring registers themselves)
     constexpr int pi = decltype(pc)::value, hf = decltype(hfc)::value;
     if constexpr (GROUPED) {
       // the two re-quantisations of a packed word (b = 0, 1) run in lock step: part p of b = 0, then part p of b = 1 -- a
@@ -788,33 +630,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     } else {
       // (CHAIN: every stage is a basic block of its own -- a seam may follow -- and hipcc sinks an operand word that is only
       // used by the next stage's MFMAs into that block, in front of its first MFMA: 24 VALU instructions per stage with the
-      // matrix pipe idle.  The empty asm holds each word where its slot put it.)
+      // matrix pipe idle.  An empty asm that uses each word holds it where its slot put it -- a USE only: behind an asm that DEFINES
+      // a register hipcc puts an s_nop in front of its next reader.)
       constexpr int kq = pi / 3, part = pi % 3;
       if constexpr (part == 0) {
         int w = (int)(y[kq] & nmask);                                            // odd nibbles  -> 16*w4 of column n      (b = 0)
-        if constexpr (QQQ_WIDE_BALANCE != 0) asm volatile("" : : "v"(w));  // (a USE only: behind an asm that DEFINES a register hipcc puts an s_nop in front of its next reader)
-        else if constexpr (CHAIN) asm volatile("" : "+v"(w));
+        asm volatile("" : : "v"(w));
         a[2 * hf][kq] = w;
       } else if constexpr (part == 1) {
         gt0[0] = y[kq] << 4;
-        if constexpr (QQQ_WIDE_BALANCE != 0) asm volatile("" : : "v"(gt0[0]));
-        else if constexpr (CHAIN) asm volatile("" : "+v"(gt0[0]));
+        asm volatile("" : : "v"(gt0[0]));
       } else {
         int w = (int)(gt0[0] & nmask);                                           // even nibbles -> 16*w4 of column n + 8  (b = 1)
-        if constexpr (QQQ_WIDE_BALANCE != 0) asm volatile("" : : "v"(w));
-        else if constexpr (CHAIN) asm volatile("" : "+v"(w));
+        asm volatile("" : : "v"(w));
         a[2 * hf + 1][kq] = w;
       }
-    }
-  };
-  // behind the loop: the last step's re-reads are never used -- their registers must stay theirs until they have landed
-  auto drain_x = [&]() __attribute__((always_inline)) {
-    if constexpr (XW) {
-      qqq_static_for<MT / 4>([&](auto jc) {
-        constexpr int j = decltype(jc)::value;
-        (void)x[0];  // (odr-use: clang does not capture what only an asm operand of a generic lambda names)
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(x[4 * j]), "+v"(x[4 * j + 1]), "+v"(x[4 * j + 2]), "+v"(x[4 * j + 3]));
-      });
     }
   };
   auto mfma = [&](v4i& c, const auto& wa, const v4i& xb) {
@@ -824,63 +654,25 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   };
 
   // One 64-k step (stage i, half t of it; u = i % P and t compile-time).  Slot k of a step = MFMA (m-tile k / 4, column set k % 4) + its share of
-  // everything else.  Step s unpacks step s + 1 into the other operand set (2 x (4 transpose pieces + UPARTS parts), evenly
-  // over the 4 MT slots), re-reads fragment x[mt] for step s + 1 right behind its fourth MFMA, refills ring slot s % RS (read by
+  // everything else.  Step s unpacks step s + 1 into the other operand set (per half: the ring wait + UPARTS parts, dealt to the
+  // slots by capacity), re-reads fragment x[mt] for step s + 1 right behind its fourth MFMA, refills ring slot s % RS (read by
   // the unpack that ran during step s - 1) with step s + RS, and issues the LDS-DMA of one 16-byte chunk per lane of activation
   // stage i + LA every 16 slots.  The waits are hand-counted from the static schedule (wide_loads_between).
   unsigned st_xso = 0, st_swo[2] = {0, 0}, st_sco = 0;  // CHAIN: the scalar offsets of the current stage's loads (do_stage_chain)
-  constexpr bool PREP = CHAIN && QQQ_WIDE_CHAINPREP != 0 && QQQ_WIDE_BALANCE != 0;
-  unsigned pz_xso[2] = {0, 0}, pz_swo[2][2] = {{0, 0}, {0, 0}}, pz_sco[2] = {0, 0};  // PREP: two sets, [stage parity]: the stage reads one while the next one's is written
-  // one set from the running cursors (common case: the next stage's loads stay inside the tile), cursors advanced; in four pieces for four slots
-  auto prep_piece = [&](auto setc, auto jc) __attribute__((always_inline)) {
-    constexpr int ns = decltype(setc)::value, j = decltype(jc)::value;
-    (void)pz_xso[0], (void)pz_swo[0][0], (void)pz_sco[0], (void)cx_so, (void)cr_so, (void)cc_so;
-    // (sgpr(): a no-op on a value that is scalar already; it only tells hipcc so where it cannot see it -- the cursors themselves are not pinned: an "s" operand
-    // of a value hipcc believes to be in a VGPR does not compile)
-    if constexpr (j == 0) {
-      pz_xso[ns] = sgpr(cx_so);
-      cx_so += 128u;
-      asm volatile("" : "+s"(pz_xso[ns]));
-    } else if constexpr (j == 1) {
-      pz_swo[ns][0] = sgpr(cr_so);
-      pz_swo[ns][1] = sgpr(cr_so + wstep);
-      asm volatile("" : "+s"(pz_swo[ns][0]), "+s"(pz_swo[ns][1]));
-    } else if constexpr (j == 2) {
-      cr_so += 2u * wstep;
-    } else if constexpr (GROUPED) {
-      pz_sco[ns] = sgpr(cc_so);
-      cc_so += (unsigned)N * 2u;
-      asm volatile("" : "+s"(pz_sco[ns]));
-    }
-  };
-  auto prep_set = [&](auto setc) __attribute__((always_inline)) { qqq_static_for<4>([&](auto jc) { prep_piece(setc, jc); }); };
   auto step = [&](const int i, auto uc, auto tc) __attribute__((always_inline)) {
     constexpr int t = decltype(tc)::value, u = decltype(uc)::value;
     constexpr int cur = t, nxt = 1 - t;         // 2 P steps per trip: the step's parity is its t
     constexpr int sl = (2 * u + t) % RS, sn = (sl + 1) % RS;
-    const int step_abs = 2 * i + t;
     constexpr int su = GROUPED ? ((t == 1) ? (u + 1) % P : u) : 0;  // scales of the NEXT step's stage
-    const int st_x = i + LA < NST ? i + LA : NST - 1;
-    // (CHAIN: i is not used, do_stage_chain says where the loads read; plain kernel with cursors: the running offsets themselves, advanced in slots of their own below)
-    const unsigned cswo = PREP ? pz_swo[u & 1][t] : st_swo[t], csco = PREP ? pz_sco[u & 1] : st_sco;
+    // (CHAIN: i is not used, do_stage_chain says where the loads read; plain kernel: the running cursors themselves, advanced in slots of their own below)
+    const unsigned cswo = st_swo[t], csco = st_sco;
     constexpr int BSLOT = wide_barrier_slot(MODE, MT, HW);
     static_assert(!CUR || (wide_ring_inc_slot(MODE, MT, HW) > 0 && (!GROUPED || wide_scale_inc_slot(MODE, MT, HW) > wide_scale_slot(HW))), "every cursor has a slot behind its last use");
-    constexpr int NI = HW * (4 + UPARTS);
     auto slot = [&](auto kc) __attribute__((always_inline)) {
       constexpr int k = decltype(kc)::value, mt = k / NQ, q = k % NQ;
-      constexpr int SD = QQQ_WIDE_STAGGER <= 0 ? 1 : (HW == 2 ? QQQ_WIDE_STAGGER : 1);  // (128-column tiles: the first M0 slot is slot 4)
-      if constexpr (QQQ_WIDE_STAGGER > 0 && t == 0 && k % SD == 0 && k / SD < 4) {
-        // the barrier that ends the PREVIOUS stage, taken by wave 3 - k / d only (wave-uniform scalar branch around one s_barrier).  What it orders is a stage away
-        // on both sides: the buffer this stage's LDS-DMA overwrites (first chunk: slot wide_dma_slot > 3 d) was last read a step before the previous stage ended,
-        // the buffer it publishes is first read in this stage's second step; the wave's own share of that buffer has landed (vmcnt wait at the end of the
-        // previous stage).  No LDS drain in front of it: the fragment reads in flight belong to this step.
-        static_assert(3 * SD < (HW == 2 ? 8 : 4), "every wave passes the barrier before the stage's first LDS-DMA (M0 slot)");
-        (void)wn;
-        asm volatile("s_cmp_lg_u32 %0, %1\n\ts_cbranch_scc1 1f\n\ts_barrier\n1:" : : "s"(wn), "n"(3 - k / SD) : "scc");
-      }
       if constexpr (W8) mfma(acc[mt][q], wr[sl][q], x[mt]);
       else mfma(acc[mt][q], aop[cur][q], x[mt]);
-      if constexpr (QQQ_WIDE_BALANCE != 0) __builtin_amdgcn_sched_barrier(0);  // (the slot's other instructions BEHIND its MFMA: hipcc likes to hoist a free VALU instruction in front of it, i.e. into the previous slot)
+      __builtin_amdgcn_sched_barrier(0);  // (the slot's other instructions BEHIND its MFMA: hipcc likes to hoist a free VALU instruction in front of it, i.e. into the previous slot)
       if constexpr (W8) {
         // the operands of step s + 1 (ring slot sn): fetched during step s + 1 - RL, the last of them at that step's last refill slot; landed once at
         // most the loads issued since are outstanding.  One wait per step, behind the step's last MFMA.
@@ -890,64 +682,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           if constexpr (HW == 2) asm volatile("s_waitcnt vmcnt(%4)" : "+v"(wr[sn][0]), "+v"(wr[sn][1]), "+v"(wr[sn][2]), "+v"(wr[sn][3]) : "n"(younger));
           else asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wr[sn][0]), "+v"(wr[sn][1]) : "n"(younger));
         }
-      } else if constexpr (!(QQQ_WIDE_ABLATE & 4) && QQQ_WIDE_BALANCE != 0) {
-        // one-instruction items dealt by slot capacity (see QQQ_WIDE_BALANCE above)
+      } else if constexpr (!(QQQ_WIDE_ABLATE & 4)) {
+        // one-instruction items dealt by slot capacity (see "One-instruction items" above)
         constexpr int PER = wide_bal_items(MODE);
-        constexpr int FIX = CUR ? 1 : PREP ? 2 : 0;
+        constexpr int FIX = CUR ? 1 : 0;
         constexpr int lo = WideBalTable<MODE, MT, HW, t, FIX>::tab.before[k], hi = WideBalTable<MODE, MT, HW, t, FIX>::tab.before[k + 1];
         qqq_static_for<(hi - lo)>([&](auto jc) {
           constexpr int it = lo + decltype(jc)::value;
           constexpr int hf = it / PER, w_ = it % PER;
           if constexpr (w_ == 0) {
-            // ring slot sn, half hf: loaded RS - 1 steps ago, its last load at slot wide_ring_last_slot (2 + 4 hf; DWORD: the half's fourth word); everything older (the
+            // ring slot sn, half hf: loaded RS - 1 steps ago, its last load at slot wide_ring_last_slot (the half's fourth word); everything older (the
             // group scales of this stage among it) has landed once at most the loads issued since are outstanding (vmcnt is a 6-bit counter: more than 63 loads waits a little early, never late)
-            constexpr int younger_all = wide_loads_between(MODE, MT, HW, (t + RS - 1) & 1, wide_ring_last_slot(MODE, MT, HW, hf), RS - 1, k);
+            constexpr int younger_all = wide_loads_between(MODE, MT, HW, (t + RS - 1) & 1, wide_ring_last_slot(MT, HW, hf), RS - 1, k);
             constexpr int younger = younger_all < 63 ? younger_all : 63;
-            if constexpr (DW) {
-              (void)wq[0][0][0];
-              // (CHAIN, 32-column waves: the second scale word is fetched and never used; tied in here it stays allocated until it has landed -- see the packed branch below)
-              if constexpr (GROUPED && CHAIN && HW == 1) asm volatile("s_waitcnt vmcnt(%6)" : "+v"(wq[sn][hf][0]), "+v"(wq[sn][hf][1]), "+v"(wq[sn][hf][2]), "+v"(wq[sn][hf][3]), "+v"(scr[su][0]), "+v"(scr[su][1]) : "n"(younger));
-              else if constexpr (GROUPED) asm volatile("s_waitcnt vmcnt(%5)" : "+v"(wq[sn][hf][0]), "+v"(wq[sn][hf][1]), "+v"(wq[sn][hf][2]), "+v"(wq[sn][hf][3]), "+v"(scr[su][hf]) : "n"(younger));
-              else asm volatile("s_waitcnt vmcnt(%4)" : "+v"(wq[sn][hf][0]), "+v"(wq[sn][hf][1]), "+v"(wq[sn][hf][2]), "+v"(wq[sn][hf][3]) : "n"(younger));
-            } else if constexpr (GROUPED && CHAIN && HW == 1) asm volatile("s_waitcnt vmcnt(%3)" : "+v"(wr[sn][hf]), "+v"(scr[su][0]), "+v"(scr[su][1]) : "n"(younger));
-            else if constexpr (GROUPED) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wr[sn][hf]), "+v"(scr[su][hf]) : "n"(younger));
-            else asm volatile("s_waitcnt vmcnt(%1)" : "+v"(wr[sn][hf]) : "n"(younger));
+            (void)wq[0][0][0];
+            // (CHAIN, 32-column waves: the second scale word is fetched -- the load counts do not depend on HW -- and never used; tied in here it stays allocated
+            // until it has landed.  The plain kernel keeps it live by using it behind its loop.)
+            if constexpr (GROUPED && CHAIN && HW == 1) asm volatile("s_waitcnt vmcnt(%6)" : "+v"(wq[sn][hf][0]), "+v"(wq[sn][hf][1]), "+v"(wq[sn][hf][2]), "+v"(wq[sn][hf][3]), "+v"(scr[su][0]), "+v"(scr[su][1]) : "n"(younger));
+            else if constexpr (GROUPED) asm volatile("s_waitcnt vmcnt(%5)" : "+v"(wq[sn][hf][0]), "+v"(wq[sn][hf][1]), "+v"(wq[sn][hf][2]), "+v"(wq[sn][hf][3]), "+v"(scr[su][hf]) : "n"(younger));
+            else asm volatile("s_waitcnt vmcnt(%4)" : "+v"(wq[sn][hf][0]), "+v"(wq[sn][hf][1]), "+v"(wq[sn][hf][2]), "+v"(wq[sn][hf][3]) : "n"(younger));
             un_setup(__builtin_bit_cast(h2, scr[su][hf]));
-          } else if constexpr (DW) {
+          } else {
             un_part(std::integral_constant<int, w_ - 1>{}, std::integral_constant<int, hf>{}, aop[nxt], wq[sn][hf]);
-          } else if constexpr (w_ < 13) {
-            tr_single(std::integral_constant<int, (w_ - 1) / 3>{}, std::integral_constant<int, (w_ - 1) % 3>{}, wr[sn][hf]);
-          } else {
-            un_part(std::integral_constant<int, w_ - 13>{}, std::integral_constant<int, hf>{}, aop[nxt], y);
-          }
-        });
-      } else if constexpr (!(QQQ_WIDE_ABLATE & 4)) {
-        // MT == 16: the NI items go to the NE = 34 memory-free slots of the step (per-channel one each, per-group 2-3 each)
-        constexpr bool MAPPED = HW == 1 || ((QQQ_WIDE_SLOTMAP & (GROUPED ? 2 : 1)) != 0 && (MT == 16 || (QQQ_WIDE_SLOTMAP & 4) != 0));
-        constexpr int NE = wide_item_slots_before(HW, NSLOT), e = wide_item_slots_before(HW, k);
-        constexpr bool here = wide_item_slot(HW, k);
-        constexpr int lo = MAPPED ? (here ? (e * NI) / NE : 0) : (k * NI) / NSLOT;
-        constexpr int hi = MAPPED ? (here ? ((e + 1) * NI) / NE : 0) : ((k + 1) * NI) / NSLOT;
-        qqq_static_for<(hi - lo)>([&](auto jc) {
-          constexpr int it = lo + decltype(jc)::value;
-          constexpr int hf = it / (4 + UPARTS), w_ = it % (4 + UPARTS);
-          if constexpr (w_ < 4) {
-            if constexpr (w_ == 0) {
-              // ring slot sn, half hf: loaded RS - 1 steps ago at slot 2 + 4 hf; everything older (the group scales of this
-              // stage among it) has landed once at most the loads issued since are outstanding
-              // (vmcnt is a 6-bit counter: a deeper ring than 63 loads waits a little early, never late)
-              constexpr int younger_all = wide_loads_between(MODE, MT, HW, (t + RS - 1) & 1, 2 + 4 * hf, RS - 1, k);
-              constexpr int younger = younger_all < 63 ? younger_all : 63;
-              // (CHAIN, 32-column waves: the second scale word is fetched -- the load counts do not depend on HW -- and never
-              // used; tied in here it stays allocated until it has landed.  The plain kernel keeps it live by using it behind its loop.)
-              if constexpr (GROUPED && CHAIN && HW == 1) asm volatile("s_waitcnt vmcnt(%3)" : "+v"(wr[sn][hf]), "+v"(scr[su][0]), "+v"(scr[su][1]) : "n"(younger));
-              else if constexpr (GROUPED) asm volatile("s_waitcnt vmcnt(%2)" : "+v"(wr[sn][hf]), "+v"(scr[su][hf]) : "n"(younger));
-              else asm volatile("s_waitcnt vmcnt(%1)" : "+v"(wr[sn][hf]) : "n"(younger));
-              un_setup(__builtin_bit_cast(h2, scr[su][hf]));
-            }
-            tr_piece(std::integral_constant<int, w_>{}, wr[sn][hf]);
-          } else {
-            un_part(std::integral_constant<int, w_ - 4>{}, std::integral_constant<int, hf>{}, aop[nxt], y);
           }
         });
       } else if constexpr (k == 0) {
@@ -956,27 +712,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
           aop[nxt][qq] = (v4i){(int)wr[sn][qq / 2][0], (int)wr[sn][qq / 2][1], (int)wr[sn][qq / 2][2], (int)wr[sn][qq / 2][3]};
         });
       }
-      if constexpr (XW) {
-        if constexpr (wide_frag_slot(HW, k)) read_x_asm(std::integral_constant<int, (t == 0 ? (u % P) : ((u + 1) % P))>{}, std::integral_constant<int, (t == 0 ? 1 : 0)>{}, std::integral_constant<int, mt>{});
-        constexpr int n = wide_xw_count_at(MODE, MT, HW, k);
-        if constexpr (n >= 0) {  // the re-reads of the group(s) that wait here (issued a step ago; group 0: in this step) have landed
-          // (not tied to the registers: their only readers are the MFMA statements, which keep their place behind this one -- and behind an asm that DEFINES a
-          // register hipcc puts an s_nop in front of the next statement that reads it)
-          asm volatile("s_waitcnt lgkmcnt(%0)" : : "n"(n));
-        }
-      } else if constexpr (wide_frag_slot(HW, k) && !(QQQ_WIDE_ABLATE & 16)) {
+      if constexpr (wide_frag_slot(HW, k) && !(QQQ_WIDE_ABLATE & 16)) {
         read_x(t == 0 ? (u % P) : ((u + 1) % P), t == 0 ? 1 : 0, mt);
       }
       // (the order of the loads inside a slot is the order wide_loads_in_slot counts them in)
       if constexpr (GROUPED && t == 1 && k == wide_scale_slot(HW) && !(QQQ_WIDE_ABLATE & 8)) {
         if constexpr (CUR) load_sc_cur(scr[u]);
-        else if constexpr (CHAIN) load_sc_so(csco, scr[u]);
-        else load_sc(i + P, scr[u]);
-      }
-      if constexpr (PREP && t == 1) {  // the NEXT stage's offsets (the other set), piece by piece (wide_bal_cap leaves room for them)
-        qqq_static_for<4>([&](auto jc) {
-          if constexpr (k == wide_prep_slot(MODE, MT, HW, decltype(jc)::value)) prep_piece(std::integral_constant<int, (u + 1) & 1>{}, jc);
-        });
+        else load_sc_so(csco, scr[u]);
       }
       if constexpr (CUR) {  // the cursors' scalar adds, one per slot (wide_bal_cap leaves room for them)
         (void)cx_so, (void)cr_so, (void)cc_so;
@@ -994,24 +736,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         }
       }
       if constexpr (!(QQQ_WIDE_ABLATE & 8)) {  // ring refill, one 16-byte load per slot
-        const int sw = step_abs + RL < KS ? step_abs + RL : KS - 1;
-        const unsigned swo = CUR ? cr_so : CHAIN ? cswo : (unsigned)(2 * st0 + sw) * wstep;
+        const unsigned swo = CUR ? cr_so : cswo;
         if constexpr (W8) {  // column set j of the slot the PREVIOUS step consumed
           constexpr int j = wide_w8_refill_index(MT, HW, k);
           if constexpr (j >= 0 && CUR) asm_load_w_cur(wr[(sl + RS - 1) % RS][j], std::integral_constant<int, j>{});
           else if constexpr (j >= 0) asm_load_w(wr[(sl + RS - 1) % RS][j], std::integral_constant<int, j>{}, swo);
-        } else if constexpr (DW) {  // one word per slot: load 4 hf + kq of the step this ring slot holds next
+        } else {  // one word per slot: load 4 hf + kq of the step this ring slot holds next
           constexpr int li = wide_dw_load_index(MT, HW, k);
           if constexpr (li >= 0) {
             if constexpr (CUR) asm_load_d(wq[sl][li / 4][li % 4], std::integral_constant<int, li>{}, cr_so, std::true_type{});
             else asm_load_d(wq[sl][li / 4][li % 4], std::integral_constant<int, li>{}, swo, std::false_type{});
           }
-        } else if constexpr (CUR) {
-          if constexpr (wide_refill_slot(HW, k, 0)) asm_load_w_cur(wr[sl][0], std::integral_constant<int, 0>{});
-          if constexpr (wide_refill_slot(HW, k, 1)) asm_load_w_cur(wr[sl][HW - 1], std::integral_constant<int, 1>{});
-        } else {
-          if constexpr (wide_refill_slot(HW, k, 0)) asm_load_w(wr[sl][0], std::integral_constant<int, 0>{}, swo);
-          if constexpr (wide_refill_slot(HW, k, 1)) asm_load_w(wr[sl][HW - 1], std::integral_constant<int, 1>{}, swo);
         }
       }
       constexpr int DP = wide_dma_period(MT, HW);  // chunk (XPT / 2) t + k / DP of stage i + LA: M0, then the DMA
@@ -1019,10 +754,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         dma_m0(std::integral_constant<int, (u + LA) % P>{}, std::integral_constant<int, (XPT / 2) * t + k / DP>{});
       if constexpr (wide_dma_slot(MT, HW, k) && !(QQQ_WIDE_ABLATE & 2)) {
         if constexpr (CUR) dma_go_cur(std::integral_constant<int, (XPT / 2) * t + k / DP>{});
-        else dma_go(std::integral_constant<int, (XPT / 2) * t + k / DP>{}, PREP ? pz_xso[u & 1] : CHAIN ? st_xso : (unsigned)(st0 + st_x) * 128u);
+        else dma_go(std::integral_constant<int, (XPT / 2) * t + k / DP>{}, st_xso);
       }
-      if constexpr (QQQ_WIDE_BALANCE != 0 && QQQ_WIDE_STAGGER == 0 && t == 1 && k == BSLOT) {
-        // the stage's end, in a slot of its own (BALANCE): the LDS-DMA of stage i + 2, issued during stage i + 3 - P, is done when at most the loads issued since
+      if constexpr (t == 1 && k == BSLOT) {
+        // the stage's end, in a slot of its own: the LDS-DMA of stage i + 2, issued during stage i + 3 - P, is done when at most the loads issued since
         // its last chunk are outstanding; then the barrier.  A bare s_barrier: what it orders is this wave's share of that DMA (waited for here) and the fragment reads of
         // the buffer the next stage's DMA overwrites -- consumed by MFMAs a step ago; the reads in flight belong to the next stage and need no drain.
         constexpr int since = wide_loads_between(MODE, MT, HW, 1, wide_last_dma_slot(MT, HW), 2 * (P - 3), k + 1);
@@ -1133,12 +868,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         if constexpr (HW == 2) {  // column sets in column order: q = 0, 2, 1, 3
           const h8 lo8 = {o[0][0], o[0][1], o[0][2], o[0][3], o[2][0], o[2][1], o[2][2], o[2][3]};
           const h8 hi8 = {o[1][0], o[1][1], o[1][2], o[1][3], o[3][0], o[3][1], o[3][2], o[3][3]};
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, lo8), dview, dr + (unsigned)cl * 2u, 0, QQQ_WIDE_FLUSH_AUX);
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, hi8), dview, dr + (unsigned)cl * 2u + 16u, 0, QQQ_WIDE_FLUSH_AUX);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, lo8), dview, dr + (unsigned)cl * 2u, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, hi8), dview, dr + (unsigned)cl * 2u + 16u, 0, 0);
         } else {
           typedef unsigned v2u __attribute__((ext_vector_type(2)));
 #pragma unroll
-          for (int q = 0; q < NQ; ++q) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o[q]), dview, dr + (unsigned)dl[q] * 2u, 0, QQQ_WIDE_FLUSH_AUX);
+          for (int q = 0; q < NQ; ++q) __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(v2u, o[q]), dview, dr + (unsigned)dl[q] * 2u, 0, 0);
         }
       }
       __builtin_amdgcn_sched_barrier(0);  // m-tile by m-tile: the seam must not ask for more registers than the loop leaves free
@@ -1213,11 +948,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         (void)wq[0][0][0];
         asm volatile("s_waitcnt vmcnt(0)" : "+v"(wq[j][hf][0]), "+v"(wq[j][hf][1]), "+v"(wq[j][hf][2]), "+v"(wq[j][hf][3]));
       });
-    } else
-    // (HW = 1: ONE operand -- the same variable tied twice gets two registers and a copy in front of the wait)
-    if constexpr (W8 && HW == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(wr[j][0]), "+v"(wr[j][1]), "+v"(wr[j][2]), "+v"(wr[j][3]));
-    else if constexpr (W8 || HW == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(wr[j][0]), "+v"(wr[j][1]));
-    else asm volatile("s_waitcnt vmcnt(0)" : "+v"(wr[j][0]));
+    } else if constexpr (HW == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(wr[j][0]), "+v"(wr[j][1]), "+v"(wr[j][2]), "+v"(wr[j][3]));
+    else asm volatile("s_waitcnt vmcnt(0)" : "+v"(wr[j][0]), "+v"(wr[j][1]));
   });
   if constexpr (GROUPED) {
     qqq_static_for<P>([&](auto jc) {
@@ -1226,26 +958,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     });
   }
   __syncthreads();
-  if constexpr (XW) {
-    // (asm as well, and drained here: a compiler-visible LDS read pending at the loop's entry makes hipcc wait for it INSIDE the loop body -- lgkmcnt(14) ... (0) in
-    // front of the first step's MFMAs of EVERY trip, each of which also drains the asm re-reads in flight)
-    qqq_static_for<MT>([&](auto mc) { read_x_asm(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, mc); });
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  } else {
 #pragma unroll
-    for (int mt = 0; mt < MT; ++mt) read_x(0, 0, mt);
-  }
+  for (int mt = 0; mt < MT; ++mt) read_x(0, 0, mt);
   if constexpr (!W8) {
     qqq_static_for<HW>([&](auto hfc) {  // both halves of step 0 into operand set 0
       constexpr int hf = decltype(hfc)::value;
       un_setup(__builtin_bit_cast(h2, scr[0][hf]));
-      if constexpr (DW) {
-        (void)wq[0][0][0];
-        qqq_static_for<UPARTS>([&](auto pc) { un_part(pc, hfc, aop[0], wq[0][hf]); });
-      } else {
-        qqq_static_for<4>([&](auto pc) { tr_piece(pc, wr[0][hf]); __builtin_amdgcn_sched_barrier(0); });
-        qqq_static_for<UPARTS>([&](auto pc) { un_part(pc, hfc, aop[0], y); });
-      }
+      (void)wq[0][0][0];
+      qqq_static_for<UPARTS>([&](auto pc) { un_part(pc, hfc, aop[0], wq[0][hf]); });
     });
   }
   __builtin_amdgcn_sched_barrier(0);
@@ -1255,16 +975,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     cr_so = sgpr((unsigned)(2 * st0 + RL) * wstep);
     cc_so = sgpr((unsigned)(st0 + P) * (unsigned)N * 2u);
   }
-  auto do_stage = [&](const int i, auto uc) __attribute__((always_inline)) {  // one 128-k stage: two steps and the barrier that publishes stage i + LA
+  auto do_stage = [&](const int i, auto uc) __attribute__((always_inline)) {  // one 128-k stage: two steps (the second ends with the barrier that publishes stage i + LA)
     step(i, uc, std::integral_constant<int, 0>{});
     step(i, uc, std::integral_constant<int, 1>{});
-    if constexpr (QQQ_WIDE_BALANCE != 0 && QQQ_WIDE_STAGGER == 0) return;  // (the stage-end wait and barrier sit in slot BSLOT of the second step)
-    // the LDS-DMA of stage i + 2, issued during stage i + 3 - P: done when at most the loads issued since its last chunk
-    // (the last DMA slot of that stage's second step) are outstanding, i.e. those of the P - 3 stages since
-    constexpr int since = wide_loads_between(MODE, MT, HW, 1, wide_last_dma_slot(MT, HW), 2 * (P - 3), NSLOT);
-    static_assert(since < 64, "vmcnt is a 6-bit counter");
-    asm volatile("s_waitcnt vmcnt(%0)" : : "n"(since) : "memory");
-    if constexpr (!(QQQ_WIDE_ABLATE & 1) && QQQ_WIDE_STAGGER == 0) __syncthreads();  // stage i + 2 is in LDS for everybody; buffer (i % P) is free
   };
   QQQ_WTR(1);
   if constexpr (CHAIN) {
@@ -1274,26 +987,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     int left = NST;
     auto do_stage_chain = [&](auto uc) __attribute__((always_inline)) {
       const unsigned sstep = (unsigned)N * 2u;
-      constexpr int sset = decltype(uc)::value & 1;
-      if constexpr (PREP) {
-        if (__builtin_expect(left <= P, 0)) {  // the last P stages: the prepared set is overwritten -- the loads cross into the next tile one kind after the other
-          const int done = NST - left;
-          const bool xn = left <= LA;
-          pz_xso[sset] = sgpr(xn ? (unsigned)(LA - left) * 128u : (unsigned)(done + LA) * 128u);
-          xdesc[0] = sgpr(xn ? nx_a_lo : cu_a_lo), xdesc[1] = sgpr(xn ? nx_a_hi : cu_a_hi), xdesc[2] = sgpr(xn ? nx_a_rec : cu_a_rec);
-#pragma unroll
-          for (int t = 0; t < 2; ++t) {
-            const int sn_ = 2 * done + t + RL;
-            pz_swo[sset][t] = sgpr(sn_ < KS ? cu_w_so + (unsigned)sn_ * wstep : nx_w_so + (unsigned)(sn_ - KS) * wstep);
-          }
-          pz_sco[sset] = sgpr(nx_s_so + (unsigned)(P - left) * sstep);
-          asm volatile("s_nop 4" : "+s"(pz_xso[sset]), "+s"(pz_swo[sset][0]), "+s"(pz_swo[sset][1]), "+s"(pz_sco[sset]), "+s"(xdesc));  // (settled here: see below)
-        }
-        // in SGPRs HERE, three MFMAs ahead of the first load that reads one: a set that reaches its stage through a loop-carried copy (hipcc keeps those in
-        // VGPRs when SGPRs run short) would otherwise be read back by a v_readfirstlane right in front of the load, inside the 5 wait states (see below)
-        pz_xso[sset] = sgpr(pz_xso[sset]), pz_swo[sset][0] = sgpr(pz_swo[sset][0]), pz_swo[sset][1] = sgpr(pz_swo[sset][1]), pz_sco[sset] = sgpr(pz_sco[sset]);
-        asm volatile("" : "+s"(pz_xso[sset]), "+s"(pz_swo[sset][0]), "+s"(pz_swo[sset][1]), "+s"(pz_sco[sset]));
-      } else
       if (__builtin_expect(left > P, 1)) {  // every load of this stage stays inside the tile
         // (sgpr(): a no-op on a value that is scalar already; it only tells hipcc so where it cannot see it)
         st_xso = sgpr(cx_so), st_swo[0] = sgpr(cr_so), st_swo[1] = sgpr(cr_so + wstep), st_sco = sgpr(cc_so);
@@ -1317,13 +1010,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
       }
       step(0, uc, std::integral_constant<int, 0>{});
       step(0, uc, std::integral_constant<int, 1>{});
-      if constexpr (QQQ_WIDE_BALANCE != 0 && QQQ_WIDE_STAGGER == 0) return;  // (the stage-end wait and barrier sit in slot BSLOT of the second step)
-      constexpr int since = wide_loads_between(MODE, MT, HW, 1, wide_last_dma_slot(MT, HW), 2 * (P - 3), NSLOT);
-      static_assert(since < 64, "vmcnt is a 6-bit counter");
-      asm volatile("s_waitcnt vmcnt(%0)" : : "n"(since) : "memory");
-      if constexpr (QQQ_WIDE_STAGGER == 0) __syncthreads();
     };
-    if constexpr (PREP) prep_set(std::integral_constant<int, 0>{});  // the first stage's set (the cursors stand at the run's stage 0)
     bool more = true;
     // (the expectations put the seams and the tile-end offset code out of line: the common stage falls through from one MFMA
     // run into the next -- a taken branch is a fetch bubble nothing hides when the wave is alone on its SIMD)
@@ -1332,11 +1019,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     do_stage_chain(std::integral_constant<int, U>{});         \
     if (__builtin_expect(--left == 0, 0)) {                   \
       seam();                                                 \
-      if constexpr (PREP) prep_set(std::integral_constant<int, (U + 1) & 1>{}); /* the next tile's stage 0, from the cursors the seam restarted */ \
       left = NST;                                             \
       if (ch_pos == ch_tiles) {                               \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      \
-        drain_x();                                            \
         more = false;                                         \
       }                                                       \
     }                                                         \
@@ -1367,7 +1052,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
   // destination of a dead asm load to the next value -- which the load then overwrites when it lands (seen: the transposed words of
   // column half 0 in the ragged tail).
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  drain_x();
   if constexpr (DW) {
     qqq_static_for<RS * HW>([&](auto jc) {
       constexpr int j = decltype(jc)::value / HW, hf = decltype(jc)::value % HW;
