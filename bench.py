@@ -18,10 +18,14 @@ N > 1 (BASELINE configs[4]): same sweep, rows of every point with M >= 64*N shar
 (qqq_amd/parallel.py); smaller points are computed redundantly on every rank (no collective).  Strong
 scaling: the total work is fixed.
 
-Extra objects on the JSON line: `roofline` (dominant kernel = whatever the dispatcher runs at M=4096, durations
-from HIP event pairs recorded on the launch stream inside this process), `roofline_hbm` (the HBM-bound
-decode kernel at M=1), `cpu_baseline` (the C oracle timed on the host cores, bounded sample) and
-`per_m` (per sweep point: us, TOPS, GB/s, speedup vs torch fp16 GEMM on the same GPU).
+A plain run does only what the headline needs: set up, warm up, time the K steps, write the outputs if --dump-outputs
+is given, print the line.  Everything else the benchmark measures runs only with --full, after the timed region:
+`step_us` (event-timed replays), `eager` (the K steps launched from Python), `per_m` (per sweep point: us, TOPS, GB/s,
+speedup vs torch fp16 GEMM on the same GPU), `roofline` (dominant kernel = whatever the dispatcher runs at M=4096,
+durations from HIP event pairs recorded on the launch stream inside this process, traffic from rocprofv3 PMC passes),
+`roofline_hbm` (the HBM-bound decode kernel at M=1), `per_m_g128` / `per_m_g128_expanded`, `clocks`, `llama7b`
+(BASELINE configs[3]), `cpu_baseline` (the C oracle timed on the host cores, bounded sample), at N > 1 the GEMM-only /
+all-gather-only / overlapped times of the sharded points, and the side file with the full result (`detail`).
 
 --dump-outputs DIR writes the outputs of the last timed step (D_m<M>.npy, float32; see dump_outputs) for comparing two builds.
 """
@@ -555,27 +559,35 @@ def dump_outputs(dirname, outs):
     return total
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-fp16", action="store_true", help="skip the torch fp16 GPU GEMM comparison")
-    ap.add_argument("--detail-iters", type=int, default=100)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure everything beyond the headline (per-point timings, rooflines, per-group "
+                         "mode, clocks, Llama-2-7B block, CPU baseline, N > 1 breakdown) and write the detail file")
+    ap.add_argument("--no-cpu", action="store_true", help="(--full) skip the cpu_baseline leg")
+    ap.add_argument("--no-fp16", action="store_true", help="(--full) skip the torch fp16 GPU GEMM comparison")
+    ap.add_argument("--detail-iters", type=int, default=100, help="(--full) event-timed launches per sweep point")
     ap.add_argument("--steps-per-graph", type=int, default=0,
                     help="steps captured per hipGraph of the timed region (0 = 10; a shorter graph takes the remainder of --steps)")
-    ap.add_argument("--no-pmc", action="store_true", help="do not run the rocprofv3 PMC traffic passes; quote the committed ones")
-    ap.add_argument("--no-llama", action="store_true", help="skip the BASELINE configs[3] block (Llama-2-7B linears)")
-    ap.add_argument("--llama-budget", type=float, default=90.0, help="wall-clock bound of the configs[3] block, seconds")
+    ap.add_argument("--no-pmc", action="store_true", help="(--full) do not run the rocprofv3 PMC traffic passes; quote the committed ones")
+    ap.add_argument("--no-llama", action="store_true", help="(--full) skip the BASELINE configs[3] block (Llama-2-7B linears)")
+    ap.add_argument("--llama-budget", type=float, default=90.0, help="(--full) wall-clock bound of the configs[3] block, seconds")
     ap.add_argument("--check", action="store_true",
                     help="after the timed region verify the gathered outputs of the sharded points against a local full GEMM")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (the fp16 output of every sweep point, as float32; a seeded row sample "
                          f"of outputs above {DUMP_MAX_ROWS} rows) to DIR/D_m<M>.npy; the inputs are seeded, so runs with the same arguments compare")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    return args
+
+
+def main():
+    args = parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -742,9 +754,9 @@ def main():
     dt = time.perf_counter() - t0
     if args.dump_outputs and rank == 0:  # before anything below launches into the output buffers again
         dump_outputs(args.dump_outputs, {f"D_m{M}": Dfull[M] for M in SWEEP_M})
-    # per-step spread, measured AFTER the timed region with stream events (diagnostic only; `value` uses `dt`)
+    # --full: per-step spread, measured AFTER the timed region with stream events (diagnostic only; `value` uses `dt`)
     step_us = []
-    if not is_multi:
+    if args.full and not is_multi:
         evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(min(args.steps, 50))]
         for a, b in evs:
             a.record()
@@ -753,7 +765,7 @@ def main():
         torch.cuda.synchronize()
         step_us = [a.elapsed_time(b) * 1e3 for a, b in evs]
     eager = None
-    if not is_multi and graph is not None:
+    if args.full and not is_multi and graph is not None:
         # the same K steps launched eagerly (Python loop, compiled binding): what an N > 1 run, whose step is eager, should be
         # compared with -- the graph figure above removes ~5 host calls per step that the N > 1 loop still pays
         for _ in range(3):
@@ -770,11 +782,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    # N > 1: where the step's time goes at the sharded points: GEMM-only, all-gather-only, overlapped total;
+    # N > 1, --full: where the step's time goes at the sharded points: GEMM-only, all-gather-only, overlapped total;
     # event-timed on the launch stream after the timed region, max over ranks
-    multi = None
-    if is_multi:
-        multi = {}
+    multi = {} if is_multi else None
+    if args.full and is_multi:
         for j, M in enumerate(SWEEP_M):
             if M not in sharded:
                 continue
@@ -853,6 +864,8 @@ def main():
         result["step_us"] = {"min": float(np.min(step_us)), "median": float(np.median(step_us)), "max": float(np.max(step_us)),
                              "n": len(step_us), "note": "event-timed replays after the timed region"}
     if rank == 0 and not is_multi:
+        result["device"] = torch.cuda.get_device_name(dev)
+    if args.full and rank == 0 and not is_multi:
         # ---- per-point detail, HIP event pairs around every launch (cold = rotating weights) ----
         per_m = {}
         it = args.detail_iters
@@ -997,10 +1010,10 @@ def main():
         if not args.no_cpu:
             result["cpu_baseline"] = cpu_baseline()
             result["cpu_baseline"]["cpu_model"] = cpu_model_name()
-        result["device"] = torch.cuda.get_device_name(dev)
 
     if rank == 0:
-        result["detail"] = write_detail(result)
+        if args.full:
+            result["detail"] = write_detail(result)
         sys.stdout.flush()
         print(compact_line(result), flush=True)
     if dist is not None:

@@ -112,3 +112,29 @@ def test_dump_outputs_is_seeded_and_bounded(tmp_path):
     assert np.array_equal(got_small, small.float().numpy())
     assert n == got_big.nbytes + got_small.nbytes + rows.nbytes
     assert sorted(p.name for p in tmp_path.iterdir()) == ["D_big.npy", "D_big_rows.npy", "D_small.npy"]
+
+
+def test_full_is_opt_in():
+    """a plain run measures the headline only; everything else waits for --full"""
+    import bench
+
+    assert bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full is False
+    assert bench.parse_args(["--full"]).full is True
+
+
+def test_plain_line_carries_the_contract():
+    """the line of a plain run (no --full blocks in the result) still holds every contract key and nothing it did not measure"""
+    import json
+
+    import bench
+
+    full = _worst_case_result()
+    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "timed_region_ms", "higher_is_better", "scaling",
+            "vs_baseline", "dtype", "data", "config", "device")
+    plain = {k: full[k] for k in keep}
+    out = json.loads(bench.compact_line(plain))
+    for k in keep:
+        assert k in out, k
+    for k in ("roofline", "roofline_hbm", "per_m", "per_m_g128", "llama7b", "cpu_baseline", "eager_ms_per_step", "step_us_median", "detail"):
+        assert k not in out, k
+    assert out["value"] == bench._r(full["value"]) and out["ms_per_step"] == bench._r(full["ms_per_step"])

@@ -21,7 +21,7 @@ def test_bench_two_ranks_one_gpu_gloo(dev):
     env = dict(os.environ, QQQ_BENCH_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--no-cpu", "--no-fp16", "--check"]
+           "--full", "--no-cpu", "--no-fp16", "--check"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     assert "identical to local full GEMMs" in p.stderr
@@ -72,7 +72,8 @@ def test_bench_one_rank_rccl_through_the_sharded_path(dev, extra):
     env = dict(os.environ, QQQ_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", **extra)
     env.pop("QQQ_BENCH_BACKEND", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-fp16", "--check"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu", "--no-fp16",
+           "--check"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     assert "identical to local full GEMMs" in p.stderr
