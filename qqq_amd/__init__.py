@@ -10,6 +10,8 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     expand_int8(B, s_group) / QuantLinear.expand_for_prefill()                     # opt-in load-time int8 expansion
     rmsnorm_quant(x, weight, eps, residual) / silu_mul_quant(gate, up)              # decoder activations, produced already int8-quantised
     QuantLinear.forward_int8(xq, s1), QuantRMSNorm, QuantLlamaMLP                     # the layer on pre-quantised input; qqq_amd/blocks.py
+    rope_qkv(q, k, v, cos, sin, pos, k_cache, v_cache)                              # RoPE on q/k + static KV-cache write, one launch
+    KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer                            # attention and the whole layer; qqq_amd/attention.py
 """
 from .ops import (  # noqa: F401
     dynamic_quant,
@@ -22,10 +24,13 @@ from .ops import (  # noqa: F401
     qqq_gemm_w8,
     quantlinear_forward,
     rmsnorm_quant,
+    rope_qkv,
     silu_mul_quant,
 )
 from .qlinear import QuantLinear, fuse_quant_linears  # noqa: F401
 from .blocks import QuantLlamaMLP, QuantRMSNorm  # noqa: F401
+from .attention import KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer  # noqa: F401
 
 __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_int8", "mul", "marlin_qqq_gemm", "dynamic_quant", "quantlinear_forward",
-           "rmsnorm_quant", "silu_mul_quant", "QuantLinear", "fuse_quant_linears", "QuantRMSNorm", "QuantLlamaMLP"]
+           "rmsnorm_quant", "silu_mul_quant", "QuantLinear", "fuse_quant_linears", "QuantRMSNorm", "QuantLlamaMLP",
+           "rope_qkv", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer"]

@@ -64,6 +64,9 @@ def lib():
     L.qqq_rmsnorm_quant.restype = ci
     L.qqq_silu_mul_quant.argtypes = [vp, ci, vp, ci, vp, vp, vp, ci, ci, ci, vp]
     L.qqq_silu_mul_quant.restype = ci
+    # include/qqq_amd_attn.h
+    L.qqq_rope_qkv.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+    L.qqq_rope_qkv.restype = ci
     L.qqq_amd_abi_version.restype = ci
     L.qqq_amd_last_error.restype = ctypes.c_char_p
     if L.qqq_amd_abi_version() != ABI_VERSION:

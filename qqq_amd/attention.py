@@ -1,0 +1,247 @@
+"""The attention half of a Llama / Qwen2 decoder layer around QuantLinear, and the layer itself: the reference's
+QuantizedLlamaAttention / QuantizedQwen2Attention and Quantized{Llama,Qwen2}DecoderLayer (QQQ/gptq/models/llama.py, qwen2.py).
+
+    rope_tables       cos / sin tables [length, head_dim] as transformers' rotary embedding computes them (rope_type "default", "llama3")
+    KVCache           static fp16 K / V per layer, [b, kvh, capacity, head_dim], allocated once: no history copy per step
+    QuantLlamaAttention      q/k/v GEMMs on the int8 input of QuantRMSNorm -> rope_qkv (RoPE on q and k, k / v into the cache, one launch)
+                             -> scaled_dot_product_attention -> dynamic_quant -> o_proj
+    QuantLlamaDecoderLayer   input_layernorm, self_attn, post_attention_layernorm (residual add fused), mlp, final residual add
+
+The attention core is torch's scaled_dot_product_attention, as in the reference.  Parameter and buffer names are the reference's, so the
+layers' state-dicts load unchanged; the rope tables and the fused q|k|v copy of fuse_qkv() are not part of them.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+from .blocks import QuantLlamaMLP, QuantRMSNorm
+from .qlinear import QuantLinear, fuse_quant_linears
+
+
+def rope_inv_freq(head_dim: int, rope_theta: float = 10000.0, rope_scaling: Optional[dict] = None):
+    """(inv_freq fp32 [head_dim / 2] on the CPU, attention_scaling) of transformers' rope initialisers for rope_type "default" (Llama-2,
+    Llama-3, Qwen2) and "llama3" (Llama-3.1 / 3.2).  `rope_scaling` is a transformers rope dict ("rope_type" or the older "type" key) or
+    None; every other rope type, and a partial rotary factor, raises NotImplementedError."""
+    sc = dict(rope_scaling or {})
+    rope_type = sc.get("rope_type", sc.get("type", "default")) or "default"
+    if rope_type not in ("default", "llama3"):
+        raise NotImplementedError(f"rope_type {rope_type!r} is not supported (only 'default' and 'llama3')")
+    if float(sc.get("partial_rotary_factor", 1.0)) != 1.0:
+        raise NotImplementedError("a partial rotary factor is not supported")
+    base, dim = float(sc.get("rope_theta", rope_theta)), int(head_dim)
+    inv_freq = 1.0 / (base ** (torch.arange(0, dim, 2, dtype=torch.int64).to(dtype=torch.float) / dim))
+    if rope_type == "llama3":
+        factor, low, high = sc["factor"], sc["low_freq_factor"], sc["high_freq_factor"]
+        old_len = sc["original_max_position_embeddings"]
+        low_wavelen, high_wavelen = old_len / low, old_len / high
+        wavelen = 2 * math.pi / inv_freq
+        inv_freq_llama = torch.where(wavelen > low_wavelen, inv_freq / factor, inv_freq)
+        smooth = (old_len / wavelen - low) / (high - low)
+        smoothed = (1 - smooth) * inv_freq_llama / factor + smooth * inv_freq_llama
+        is_medium = ~(wavelen < high_wavelen) * ~(wavelen > low_wavelen)
+        inv_freq = torch.where(is_medium, smoothed, inv_freq_llama)
+    return inv_freq, 1.0
+
+
+@torch.no_grad()
+def rope_tables(inv_freq: torch.Tensor, attention_scaling: float, length: int, device, dtype=torch.float16):
+    """(cos, sin) [length, 2 * inv_freq.numel()] for positions 0 ... length-1: transformers' rotary forward on `device` (fp32 freqs =
+    inv_freq @ positions, emb = cat(freqs, freqs), cos = emb.cos() * attention_scaling, then cast to `dtype`)."""
+    inv = inv_freq.to(device=device, dtype=torch.float)[None, :, None]
+    positions = torch.arange(length, device=device)[None, None, :].float()
+    freqs = (inv @ positions).transpose(1, 2)
+    emb = torch.cat((freqs, freqs), dim=-1)
+    return (emb.cos() * attention_scaling).to(dtype)[0], (emb.sin() * attention_scaling).to(dtype)[0]
+
+
+class KVCache:
+    """Static fp16 key / value cache of `num_layers` layers: k[layer], v[layer] of shape [batch, num_kv_heads, capacity, head_dim],
+    allocated (zeroed) once, written in place by rope_qkv at each token's position.  Memory: 4 * num_layers * batch * num_kv_heads *
+    capacity * head_dim bytes (K and V, 2 bytes an element).  Every batch row is at the same position (no per-row lengths, no paging)."""
+
+    def __init__(self, num_layers: int, batch: int, num_kv_heads: int, head_dim: int, capacity: int, device=None):
+        self.num_layers, self.batch, self.num_kv_heads, self.head_dim, self.capacity = num_layers, batch, num_kv_heads, head_dim, capacity
+        shape = (batch, num_kv_heads, capacity, head_dim)
+        self.k = [torch.zeros(shape, dtype=torch.float16, device=device) for _ in range(num_layers)]
+        self.v = [torch.zeros(shape, dtype=torch.float16, device=device) for _ in range(num_layers)]
+        # positions p of every batch row, [capacity, batch]: the s = 1 (decode) and b = 1 position vectors are views of it, no launch
+        self._rep = torch.arange(capacity, device=device)[:, None].expand(capacity, batch).contiguous()
+
+    @property
+    def nbytes(self) -> int:
+        return 4 * self.num_layers * self.batch * self.num_kv_heads * self.capacity * self.head_dim
+
+    def positions(self, start: int, s: int) -> torch.Tensor:
+        """int64 [batch * s] device positions start ... start+s-1 of every batch row (token bi * s + si)."""
+        if s == 1 or self.batch == 1:
+            return self._rep[start:start + s].reshape(-1)
+        return self._rep[start:start + s, 0].repeat(self.batch)
+
+
+def _drop_fused_qkv_on_load(module, *args, **kwargs):
+    module._qkv = None  # a state-dict is being loaded: the fused q|k|v copy would be stale
+
+
+class QuantLlamaAttention(nn.Module):
+    """QuantizedLlamaAttention / QuantizedQwen2Attention (SDPA) with W4A8 QuantLinears and a static KV cache.
+
+    forward_int8(xq, s1, cache, start): (xq int8 [b*s, hidden], s1 f32 [b*s, 1]) as QuantRMSNorm returns them, tokens at positions
+    start ... start+s-1 (the same for every batch row) -> fp16 [b*s, hidden].  forward(x, cache, start) quantises its fp16 input first.
+    Llama: qkv_bias = o_bias = config.attention_bias;  Qwen2: qkv_bias=True, o_bias=False."""
+
+    def __init__(self, hidden: int, num_heads: int, num_kv_heads: int, group_size: int, head_dim: Optional[int] = None,
+                 qkv_bias: bool = False, o_bias: bool = False, rope_theta: float = 10000.0, rope_scaling: Optional[dict] = None,
+                 layer_idx: int = 0):
+        super().__init__()
+        head_dim = head_dim or hidden // num_heads
+        if num_heads % num_kv_heads:
+            raise ValueError(f"num_heads {num_heads} must be a multiple of num_kv_heads {num_kv_heads}")
+        if head_dim % 16 or head_dim > 256:
+            raise ValueError(f"head_dim {head_dim} must be a multiple of 16, at most 256")
+        self.hidden_size, self.num_heads, self.num_key_value_heads, self.head_dim = hidden, num_heads, num_kv_heads, head_dim
+        self.layer_idx = layer_idx
+        self.scaling = head_dim ** -0.5
+        self.q_proj = QuantLinear(4, group_size, hidden, num_heads * head_dim, bias=qkv_bias)
+        self.k_proj = QuantLinear(4, group_size, hidden, num_kv_heads * head_dim, bias=qkv_bias)
+        self.v_proj = QuantLinear(4, group_size, hidden, num_kv_heads * head_dim, bias=qkv_bias)
+        self.o_proj = QuantLinear(4, group_size, num_heads * head_dim, hidden, bias=o_bias)
+        self.inv_freq, self.attention_scaling = rope_inv_freq(head_dim, rope_theta, rope_scaling)  # plain attributes: not in the state-dict
+        self._cos = self._sin = None  # rope tables, built lazily up to the cache capacity on the module's device
+        self._qkv = None  # fuse_qkv(): the fused q|k|v layer, kept outside the module tree (not in the state-dict)
+        # a plain function: a bound method would make module -> hook -> module a reference cycle (see QuantLlamaMLP)
+        self._register_load_state_dict_pre_hook(_drop_fused_qkv_on_load, with_module=True)
+
+    def rope_tables(self, length: int):
+        """(cos, sin) fp16 [>= length, head_dim] on the module's device, built on first need and regrown when a longer cache arrives."""
+        dev = self.q_proj.B.device
+        if self._cos is None or self._cos.shape[0] < length or self._cos.device != dev:
+            self._cos, self._sin = rope_tables(self.inv_freq, self.attention_scaling, length, dev)
+        return self._cos, self._sin
+
+    @torch.no_grad()
+    def fuse_qkv(self):
+        """Opt-in: ONE GEMM for q, k and v (fuse_quant_linears: N = (h + 2 kvh) * head_dim), whose three column ranges feed rope_qkv in
+        place.  Memory: a second copy of the three layers' weights, scales and bias.  state_dict(): unchanged.  Loading a state-dict drops
+        the fused copy (the module then runs the three GEMMs until fuse_qkv() is called again); unfuse_qkv() releases it.  The fused layer
+        follows later .to() / .cuda() moves of the module.  Returns self."""
+        fused = fuse_quant_linears([self.q_proj, self.k_proj, self.v_proj])
+        if all(p.W8 is not None for p in (self.q_proj, self.k_proj, self.v_proj)):
+            fused.expand_for_prefill(per_channel=True)
+        object.__setattr__(self, "_qkv", fused)  # a plain attribute: nn.Module would register it as a submodule
+        return self
+
+    def unfuse_qkv(self):
+        """Release the fused q|k|v layer of fuse_qkv()."""
+        self._qkv = None
+        return self
+
+    @property
+    def qkv_fused(self) -> bool:
+        return self._qkv is not None
+
+    def _apply(self, fn, recurse=True):
+        super()._apply(fn, recurse=recurse)
+        if self._qkv is not None:
+            self._qkv._apply(fn, recurse=recurse)
+        return self
+
+    def project_qkv(self, xq: torch.Tensor, s1: torch.Tensor):
+        """(q, k, v) fp16 token rows [b*s, h*d], [b*s, kvh*d], [b*s, kvh*d]: three views into one output after fuse_qkv()."""
+        if self._qkv is not None:
+            qkv = self._qkv.forward_int8(xq, s1)
+            nq, nk = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
+            return qkv[:, :nq], qkv[:, nq:nq + nk], qkv[:, nq + nk:]
+        return self.q_proj.forward_int8(xq, s1), self.k_proj.forward_int8(xq, s1), self.v_proj.forward_int8(xq, s1)
+
+    def attend(self, q_out: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
+        """scaled_dot_product_attention of q_out [b, h, s, d] over the cache slice [:, :, :start+s] -> fp16 [b, s, h*d]: causal for a
+        prefill from 0, a bottom-right causal mask for a chunk at start > 0, no mask for one token."""
+        b, h, s, d = q_out.shape
+        kc = cache.k[self.layer_idx][:, :, :start + s]
+        vc = cache.v[self.layer_idx][:, :, :start + s]
+        mask = None
+        if s > 1 and start > 0:
+            mask = torch.ones((s, start + s), dtype=torch.bool, device=q_out.device).tril(diagonal=start)
+        o = F.scaled_dot_product_attention(q_out, kc, vc, attn_mask=mask, is_causal=(s > 1 and start == 0), scale=self.scaling,
+                                           enable_gqa=h != self.num_key_value_heads)
+        return o.transpose(1, 2).reshape(b, s, h * d)
+
+    def forward_int8(self, xq: torch.Tensor, s1: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
+        m = xq.shape[0]
+        b = cache.batch
+        if xq.dim() != 2 or m % b:
+            raise RuntimeError(f"forward_int8: xq must be [batch * s, hidden] with batch = {b} (the cache's)")
+        s = m // b
+        if start < 0 or start + s > cache.capacity:
+            raise RuntimeError(f"forward_int8: tokens {start} ... {start + s - 1} do not fit the cache capacity {cache.capacity}")
+        cos, sin = self.rope_tables(cache.capacity)
+        q, k, v = self.project_qkv(xq, s1)
+        q_out = ops.rope_qkv(q, k, v, cos, sin, cache.positions(start, s), cache.k[self.layer_idx], cache.v[self.layer_idx])
+        aq, a1 = ops.dynamic_quant(self.attend(q_out, cache, start))
+        return self.o_proj.forward_int8(aq.reshape(m, -1), a1.reshape(m, 1))
+
+    def forward(self, x: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
+        """x fp16 [b, s, hidden] or [b*s, hidden] -> the attention output of the same shape."""
+        xq, s1 = ops.dynamic_quant(x.reshape(-1, x.shape[-1]).half())
+        return self.forward_int8(xq, s1, cache, start).reshape(x.shape)
+
+
+def _config_rope(config):
+    """(rope_theta, rope dict or None) of a transformers config, 5.x (`rope_parameters`) or 4.x (`rope_theta`, `rope_scaling`) style."""
+    rp = getattr(config, "rope_parameters", None)
+    if isinstance(rp, dict) and rp:
+        return float(rp.get("rope_theta", getattr(config, "rope_theta", 10000.0))), rp
+    return float(getattr(config, "rope_theta", 10000.0)), getattr(config, "rope_scaling", None)
+
+
+class QuantLlamaDecoderLayer(nn.Module):
+    """Quantized{Llama,Qwen2}DecoderLayer: transformers' layer output
+        h = hidden + self_attn(input_layernorm(hidden));  out = h + mlp(post_attention_layernorm(h))
+    with every GEMM input produced already int8-quantised (QuantRMSNorm, silu_mul_quant) and the residual add of the second norm fused
+    into it.  forward(hidden, cache, start): hidden fp16 [b, s, hidden] or [b*s, hidden], tokens at positions start ... start+s-1."""
+
+    def __init__(self, hidden: int, num_heads: int, num_kv_heads: int, intermediate: int, group_size: int, head_dim: Optional[int] = None,
+                 qkv_bias: bool = False, o_bias: bool = False, rms_norm_eps: float = 1e-6, rope_theta: float = 10000.0,
+                 rope_scaling: Optional[dict] = None, layer_idx: int = 0):
+        super().__init__()
+        self.hidden_size = hidden
+        self.self_attn = QuantLlamaAttention(hidden, num_heads, num_kv_heads, group_size, head_dim=head_dim, qkv_bias=qkv_bias,
+                                             o_bias=o_bias, rope_theta=rope_theta, rope_scaling=rope_scaling, layer_idx=layer_idx)
+        self.mlp = QuantLlamaMLP(hidden, intermediate, group_size)
+        self.input_layernorm = QuantRMSNorm(hidden, eps=rms_norm_eps)
+        self.post_attention_layernorm = QuantRMSNorm(hidden, eps=rms_norm_eps)
+
+    @classmethod
+    def from_config(cls, config, group_size: int, layer_idx: int = 0):
+        """The layer of a transformers LlamaConfig or Qwen2Config (duck-typed, 4.x or 5.x attribute style).  Qwen2: q/k/v with bias, o
+        without; Llama: all four follow `attention_bias`.  Sliding-window Qwen2 and rope types other than "default" / "llama3" raise
+        NotImplementedError."""
+        if getattr(config, "hidden_act", "silu") != "silu":
+            raise NotImplementedError(f"hidden_act {config.hidden_act!r}: only SiLU MLPs are supported")
+        qwen2 = getattr(config, "model_type", "") == "qwen2"
+        if qwen2 and getattr(config, "use_sliding_window", False):
+            raise NotImplementedError("sliding-window attention is not supported")
+        theta, rope = _config_rope(config)
+        heads = config.num_attention_heads
+        kv = getattr(config, "num_key_value_heads", None) or heads
+        bias = bool(getattr(config, "attention_bias", False))
+        return cls(config.hidden_size, heads, kv, config.intermediate_size, group_size,
+                   head_dim=getattr(config, "head_dim", None) or config.hidden_size // heads,
+                   qkv_bias=True if qwen2 else bias, o_bias=False if qwen2 else bias, rms_norm_eps=config.rms_norm_eps,
+                   rope_theta=theta, rope_scaling=rope, layer_idx=layer_idx)
+
+    def forward(self, hidden: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
+        x = hidden.reshape(-1, self.hidden_size)
+        a = self.self_attn.forward_int8(*self.input_layernorm(x), cache, start)
+        # a becomes h = fp16(a + x), torch's `residual + attn_out` (fp16 addition commutes), in the launch that quantises its norm
+        mq, ms = self.post_attention_layernorm(x, a)
+        return (a + self.mlp.forward_int8(mq, ms)).reshape(hidden.shape)
+
+
+__all__ = ["KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer", "rope_inv_freq", "rope_tables"]

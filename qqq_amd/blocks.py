@@ -5,7 +5,7 @@
     QuantLlamaMLP     down(silu(gate(x)) * up(x)): the product is quantised in the same launch that computes it (silu_mul_quant)
 
 Parameter and buffer names are the reference's, so `input_layernorm.*`, `post_attention_layernorm.*` and `mlp.*` state-dicts load unchanged.
-Attention, RoPE and the KV cache are not here.
+Attention, RoPE, the KV cache and the whole decoder layer are in qqq_amd/attention.py (QuantLlamaAttention, QuantLlamaDecoderLayer).
 """
 from __future__ import annotations
 

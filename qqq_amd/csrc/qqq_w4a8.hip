@@ -65,6 +65,8 @@
 #include "qqq_small.hip.h"
 #include "qqq_act.hip.h"
 #include "../../include/qqq_amd_act.h"
+#include "qqq_attn.hip.h"
+#include "../../include/qqq_amd_attn.h"
 #include "qqq_rates.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1534,6 +1536,50 @@ extern "C" int qqq_silu_mul_quant(const void* gate, int ld_gate, const void* up,
   return act_launch<SiluMulQuantLaunch>("qqq_silu_mul_quant_kernel launch", m, i, static_cast<hipStream_t>(stream),
                                         static_cast<const _Float16*>(gate), ld_gate, static_cast<const _Float16*>(up), ld_up,
                                         static_cast<_Float16*>(y), static_cast<int8_t*>(xq), static_cast<float*>(s1), i);
+}
+
+// ---- RoPE + KV-cache write of an attention block (include/qqq_amd_attn.h; kernel in qqq_attn.hip.h).  Grid x = token, grid y = blocks of
+// ROPE_NT (head, 16-byte pair) items: at decode a Llama-2-7B layer (96 heads of 128) spreads over 6 workgroups instead of one.
+static constexpr int ROPE_NT = 128;
+
+extern "C" int qqq_rope_qkv(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, const void* cos, const void* sin,
+                            int table_len, const void* pos, void* q_out, void* k_cache, void* v_cache, int b, int s, int h, int kvh, int d,
+                            int cap, int dev, void* stream) {
+  g_err[0] = 0;
+  if (b < 0 || s < 0 || h < 0 || kvh < 0 || d < 0 || cap < 0 || table_len < 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_rope_qkv: negative size (b=%d s=%d h=%d kvh=%d d=%d cap=%d table_len=%d)", b, s, h, kvh, d, cap,
+             table_len);
+    return QQQ_ERR_ARG;
+  }
+  if (b == 0 || s == 0) return QQQ_OK;
+  if ((long long)b * s > 0x7fffffffLL || h < 1 || kvh < 1 || h % kvh != 0 || d < 16 || d > 256 || d % 16 != 0 ||
+      (long long)(h + 2LL * kvh) * d > (1LL << 20)) {
+    snprintf(g_err, sizeof(g_err), "qqq_rope_qkv: bad shape b=%d s=%d h=%d kvh=%d d=%d (need b*s < 2^31, h %% kvh == 0, d a multiple of 16 "
+             "in [16, 256], (h + 2 kvh) d <= 2^20)", b, s, h, kvh, d);
+    return QQQ_ERR_ARG;
+  }
+  if (ld_q < h * d || ld_k < kvh * d || ld_v < kvh * d || ld_q % 8 || ld_k % 8 || ld_v % 8) {
+    snprintf(g_err, sizeof(g_err), "qqq_rope_qkv: bad row strides ld_q=%d ld_k=%d ld_v=%d (need multiples of 8, >= h*d=%d / kvh*d=%d)", ld_q,
+             ld_k, ld_v, h * d, kvh * d);
+    return QQQ_ERR_ARG;
+  }
+  if (!q || !k || !v || !cos || !sin || !pos || !q_out || !k_cache || !v_cache || misaligned(q, 16) || misaligned(k, 16) ||
+      misaligned(v, 16) || misaligned(cos, 16) || misaligned(sin, 16) || misaligned(pos, 8) || misaligned(q_out, 16) ||
+      misaligned(k_cache, 16) || misaligned(v_cache, 16)) {
+    snprintf(g_err, sizeof(g_err), "qqq_rope_qkv: bad argument (every pointer must be non-NULL; fp16 tensors 16-byte, pos 8-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  const int items = (h + 2 * kvh) * (d / 16);
+  const long long limit = cap < table_len ? cap : table_len;
+  hipLaunchKernelGGL((qqq_rope_qkv_kernel<ROPE_NT>), dim3(b * s, (items + ROPE_NT - 1) / ROPE_NT), dim3(ROPE_NT), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const _Float16*>(q), ld_q, static_cast<const _Float16*>(k), ld_k,
+                     static_cast<const _Float16*>(v), ld_v, static_cast<const _Float16*>(cos), static_cast<const _Float16*>(sin),
+                     static_cast<const long long*>(pos), limit, static_cast<_Float16*>(q_out), static_cast<_Float16*>(k_cache),
+                     static_cast<_Float16*>(v_cache), s, h, kvh, d, cap);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_rope_qkv_kernel launch");
+  return QQQ_OK;
 }
 
 extern "C" int qqq_quantlinear_forward(const void* x, void* xq, void* s1, const void* B, void* C, void* D,

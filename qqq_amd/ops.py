@@ -479,3 +479,78 @@ def silu_mul_quant(gate: torch.Tensor, up: torch.Tensor, return_y: bool = False)
     their rows are contiguous; they are read in place."""
     out = _silu_mul_quant_op(gate, up, return_y) if _compiling(gate, up) else _silu_mul_quant_impl(gate, up, return_y)
     return out if return_y else out[:2]
+
+
+# ---- RoPE + KV-cache write of an attention block (include/qqq_amd_attn.h): q/k/v rows straight from the projection output, rotated q in
+# scaled_dot_product_attention's layout, rotated k and plain v into a static cache, in one launch.
+
+def _rope_qkv_shapes(q, k, v, cos, pos, k_cache):
+    # (b, s, h, kvh, d, cap) from the tensors' shapes; raises for anything the kernel could not take
+    if k_cache.dim() != 4:
+        raise RuntimeError("rope_qkv: k_cache must be fp16 [b, kvh, cap, d]")
+    b, kvh, cap, d = k_cache.shape
+    m = pos.numel()
+    if b == 0 or m % b:
+        raise RuntimeError(f"rope_qkv: pos holds {m} positions, not a multiple of the cache's batch {b}")
+    s = m // b
+    if m == 0 or d == 0:
+        return b, s, 0, kvh, d, cap
+    if q.numel() % (m * d) or k.numel() != m * kvh * d or v.numel() != m * kvh * d:
+        raise RuntimeError(f"rope_qkv: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must hold {m} token rows of h*{d}, "
+                           f"{kvh}*{d}, {kvh}*{d} elements")
+    if cos.dim() != 2 or cos.shape[1] != d:
+        raise RuntimeError(f"rope_qkv: cos / sin must be fp16 [table_len, {d}]")
+    return b, s, q.numel() // (m * d), kvh, d, cap
+
+
+def _rope_qkv_impl(q, k, v, cos, sin, pos, k_cache, v_cache):
+    ts = (q, k, v, cos, sin, pos, k_cache, v_cache)
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError("rope_qkv: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != q.device for t in ts):
+        raise RuntimeError("rope_qkv: every tensor must be on the same GPU")
+    if any(t.dtype != torch.float16 for t in (q, k, v, cos, sin, k_cache, v_cache)) or pos.dtype != torch.int64:
+        raise RuntimeError("rope_qkv: q, k, v, cos, sin and the caches must be fp16, pos int64")
+    b, s, h, kvh, d, cap = _rope_qkv_shapes(q, k, v, cos, pos, k_cache)
+    if v_cache.shape != k_cache.shape or sin.shape != cos.shape:
+        raise RuntimeError("rope_qkv: v_cache must have k_cache's shape and sin cos's shape")
+    for name, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+        if not t.is_contiguous():
+            raise RuntimeError(f"rope_qkv: {name} must be contiguous (it is written in place)")
+    q_out = torch.empty((b, h, s, d), dtype=torch.float16, device=q.device)
+    if q_out.numel() == 0:
+        return q_out
+    (q2, ld_q), (k2, ld_k), (v2, ld_v) = _rows(q, h * d), _rows(k, kvh * d), _rows(v, kvh * d)
+    cos, sin, pos = cos.contiguous(), sin.contiguous(), pos.contiguous()
+    err = _lib.lib().qqq_rope_qkv(_ptr(q2), ld_q, _ptr(k2), ld_k, _ptr(v2), ld_v, _ptr(cos), _ptr(sin), cos.shape[0], _ptr(pos),
+                                  _ptr(q_out), _ptr(k_cache), _ptr(v_cache), b, s, h, kvh, d, cap, q.device.index or 0, _stream_for(q))
+    if err:
+        raise RuntimeError(f"qqq_amd: rope_qkv error {err}: {_lib.last_error()}")
+    return q_out
+
+
+@torch.library.custom_op("qqq_amd::rope_qkv", mutates_args=("k_cache", "v_cache"))
+def _rope_qkv_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
+                 k_cache: torch.Tensor, v_cache: torch.Tensor) -> torch.Tensor:
+    return _rope_qkv_impl(q, k, v, cos, sin, pos, k_cache, v_cache)
+
+
+@_rope_qkv_op.register_fake
+def _(q, k, v, cos, sin, pos, k_cache, v_cache):
+    b, s, h, _, d, _ = _rope_qkv_shapes(q, k, v, cos, pos, k_cache)
+    return q.new_empty((b, h, s, d), dtype=torch.float16)
+
+
+def rope_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
+             k_cache: torch.Tensor, v_cache: torch.Tensor) -> torch.Tensor:
+    """transformers' apply_rotary_pos_emb on fp16 q and k, bit for bit, plus the cache update, in one launch.
+
+    q, k, v    fp16 token rows ([b*s, h*d] / [b*s, kvh*d], or [b, s, ...]); strided views such as the column ranges of one fused q|k|v
+               output are read in place when their rows are contiguous, copied otherwise
+    cos, sin   fp16 [table_len, d], indexed by position;  pos  int64 [b*s] positions in device memory (token bi*s + si)
+    k_cache, v_cache  fp16 [b, kvh, cap, d], updated in place: rotated k and plain v of token (bi, si) go to slot pos[bi*s + si] of row bi
+    Returns q_out fp16 [b, h, s, d], the rotated q in scaled_dot_product_attention's layout.  A token whose position is outside
+    [0, min(cap, table_len)) writes nothing (its q_out rows are left uninitialised)."""
+    if _compiling(q, k, v, cos, sin, pos, k_cache, v_cache):
+        return _rope_qkv_op(q, k, v, cos, sin, pos, k_cache, v_cache)
+    return _rope_qkv_impl(q, k, v, cos, sin, pos, k_cache, v_cache)

@@ -1,0 +1,152 @@
+#!/usr/bin/env python3
+"""What the launches around the attention core cost per decoder layer: the transformers-style eager path against rope_qkv with the static
+KV cache.  Both paths start from the fp16 output of input_layernorm and end with o_proj's output; every step is replayed from a hipGraph
+(tools/bench_llama.time_fn).  Shapes: Llama-2-7B (hidden 4096, 32 / 32 heads of 128) and Llama-3-8B (32 / 8), per-channel and g128.
+
+    unfused     q/k/v_proj.forward(y) (each quantises its own input); view + transpose; torch RoPE on q and k (apply_rotary_pos_emb with
+                cos / sin gathered at the positions); DynamicCache-style torch.cat of the history and the new k / v; SDPA; transpose +
+                contiguous; o_proj.forward
+    fused       QuantLlamaAttention.forward(y): dynamic_quant once, q/k/v forward_int8, rope_qkv into the static cache, SDPA,
+                dynamic_quant, o_proj.forward_int8
+    fused_qkv   the same after fuse_qkv(): one q|k|v GEMM whose column ranges rope_qkv reads in place
+
+Points: decode (s = 1) at b in {1, 16} with a context of {1024, 4096} tokens (the new token included); prefill of s in {128, 1024, 4096}
+tokens at b = 1 from position 0.
+
+    python tools/bench_attn.py [--points decode,prefill] [--out FILE]   -> one JSON object on stdout
+    python tools/bench_attn.py --summarize TRACE_DIR                    -> qqq_rope_qkv_kernel times and HBM fractions from a rocprofv3
+                                                                          --kernel-trace run of the above
+"""
+import argparse
+import collections
+import csv
+import glob
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+HIDDEN, D = 4096, 128
+SHAPES = {"llama2_7b": (32, 32), "llama3_8b": (32, 8)}
+DECODE = [(b, ctx) for b in (1, 16) for ctx in (1024, 4096)]
+PREFILL = (128, 1024, 4096)
+HBM_BYTES_PER_S = 8e12
+ROPE_NT = 128  # qqq_w4a8.hip: ROPE_NT
+
+
+def _rotate_half(x):
+    import torch
+
+    return torch.cat((-x[..., x.shape[-1] // 2:], x[..., : x.shape[-1] // 2]), dim=-1)
+
+
+def run(points, group_sizes):
+    import torch
+    import torch.nn.functional as F
+
+    from bench_llama import make_ql, time_fn
+    from qqq_amd import KVCache, QuantLlamaAttention
+
+    dev = torch.device("cuda:0")
+    out = {"hidden": HIDDEN, "head_dim": D, "unit": "us per call, hipGraph replay (median)", "points": []}
+    for shape, (h, kvh) in SHAPES.items():
+        for gs in group_sizes:
+            attn = QuantLlamaAttention(HIDDEN, h, kvh, gs).to(dev)
+            attn.q_proj, attn.k_proj = make_ql(dev, h * D, HIDDEN, gs, 1), make_ql(dev, kvh * D, HIDDEN, gs, 2)
+            attn.v_proj, attn.o_proj = make_ql(dev, kvh * D, HIDDEN, gs, 3), make_ql(dev, HIDDEN, h * D, gs, 4)
+            runs = [("decode", b, ctx - 1, 1) for b, ctx in DECODE] if "decode" in points else []
+            runs += [("prefill", 1, 0, s) for s in PREFILL] if "prefill" in points else []
+            for kind, b, start, s in runs:
+                cap = start + s
+                cache = KVCache(1, b, kvh, D, cap, dev)
+                cos, sin = attn.rope_tables(cap)
+                y = (torch.randn((b * s, HIDDEN), device=dev) * 0.5).half()
+                k_past = torch.randn((b, kvh, start, D), device=dev).half()
+                v_past = torch.randn((b, kvh, start, D), device=dev).half()
+                pos = torch.arange(start, start + s, device=dev)[None].expand(b, s)
+
+                def unfused():
+                    q = attn.q_proj.forward(y).view(b, s, h, D).transpose(1, 2)
+                    k = attn.k_proj.forward(y).view(b, s, kvh, D).transpose(1, 2)
+                    v = attn.v_proj.forward(y).view(b, s, kvh, D).transpose(1, 2)
+                    c, sn = cos[pos].unsqueeze(1), sin[pos].unsqueeze(1)
+                    q = (q * c) + (_rotate_half(q) * sn)
+                    k = (k * c) + (_rotate_half(k) * sn)
+                    kk, vv = torch.cat((k_past, k), dim=-2), torch.cat((v_past, v), dim=-2)
+                    o = F.scaled_dot_product_attention(q, kk, vv, is_causal=s > 1, scale=D ** -0.5, enable_gqa=h != kvh)
+                    return attn.o_proj.forward(o.transpose(1, 2).contiguous().reshape(b * s, h * D))
+
+                def fused():
+                    return attn.forward(y, cache, start)
+
+                pt = {"shape": shape, "heads": h, "kv_heads": kvh, "group_size": gs, "kind": kind, "batch": b, "tokens": s,
+                      "context": start + s}
+                attn.unfuse_qkv()
+                pt["unfused"] = round(time_fn(unfused), 2)
+                pt["fused"] = round(time_fn(fused), 2)
+                attn.fuse_qkv()
+                pt["fused_qkv"] = round(time_fn(fused), 2)
+                attn.unfuse_qkv()
+                pt["saved"] = round(pt["unfused"] - pt["fused"], 2)
+                pt["saved_qkv"] = round(pt["unfused"] - pt["fused_qkv"], 2)
+                out["points"].append(pt)
+                print(json.dumps(pt), file=sys.stderr, flush=True)
+                del cache, k_past, v_past
+                torch.cuda.empty_cache()
+    return out
+
+
+def summarize(trace_dir):
+    from code_object import _demangle
+
+    times = collections.defaultdict(list)
+    for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
+        for r in csv.DictReader(open(f)):
+            name = r["Kernel_Name"]
+            name = name[5:] if name.startswith("void ") else name
+            name = name.split("(")[0]
+            name = _demangle(name) if name.startswith("_Z") else name
+            if not name.startswith("qqq_rope_qkv_kernel"):
+                continue
+            m = int(r["Grid_Size_X"]) // int(r["Workgroup_Size_X"])
+            gy = int(r.get("Grid_Size_Y", 1)) // max(1, int(r.get("Workgroup_Size_Y", 1)))
+            times[(m, gy)].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    # the shape behind a launch: grid y = ceil((h + 2 kvh) * D / 16 / ROPE_NT) blocks
+    by_gy = {-(-(h + 2 * kvh) * (D // 16) // ROPE_NT): (name, h, kvh) for name, (h, kvh) in SHAPES.items()}
+    rows = []
+    for (m, gy), v in sorted(times.items()):
+        if gy not in by_gy:
+            continue
+        name, h, kvh = by_gy[gy]
+        v = sorted(v)
+        med = v[len(v) // 2]
+        width = (h + 2 * kvh) * D
+        nbytes = m * width * 2 * 2 + m * D * 2 * 2  # q|k|v read + q, k, v written; one cos and one sin row per token
+        rows.append({"kernel": "qqq_rope_qkv_kernel", "shape": name, "tokens": m, "calls": len(v), "median_us": round(med, 2),
+                     "min_us": round(v[0], 2), "bytes": nbytes, "hbm_fraction_of_8TBps": round(nbytes / (med * 1e-6) / HBM_BYTES_PER_S, 4)})
+    return {"unit": "kernel time from rocprofv3 --kernel-trace (median over calls)", "kernels": rows}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", default="decode,prefill")
+    ap.add_argument("--group-sizes", default="-1,128")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--summarize", default=None, metavar="TRACE_DIR")
+    a = ap.parse_args()
+    if a.summarize:
+        res = summarize(a.summarize)
+    else:
+        res = run(a.points.split(","), [int(v) for v in a.group_sizes.split(",")])
+    s = json.dumps(res)
+    print(s)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(s + "\n")
+
+
+if __name__ == "__main__":
+    main()
