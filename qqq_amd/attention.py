@@ -4,11 +4,13 @@ QuantizedLlamaAttention / QuantizedQwen2Attention and Quantized{Llama,Qwen2}Deco
     rope_tables       cos / sin tables [length, head_dim] as transformers' rotary embedding computes them (rope_type "default", "llama3")
     KVCache           static fp16 K / V per layer, [b, kvh, capacity, head_dim], allocated once: no history copy per step
     QuantLlamaAttention      q/k/v GEMMs on the int8 input of QuantRMSNorm -> rope_qkv (RoPE on q and k, k / v into the cache, one launch)
-                             -> scaled_dot_product_attention -> dynamic_quant -> o_proj
+                             -> scaled_dot_product_attention -> dynamic_quant -> o_proj;  opt-in fuse_decode(): one-token steps take
+                             decode_attention (split-K over the cache, output int8-quantised) in place of the last two
     QuantLlamaDecoderLayer   input_layernorm, self_attn, post_attention_layernorm (residual add fused), mlp, final residual add
 
-The attention core is torch's scaled_dot_product_attention, as in the reference.  Parameter and buffer names are the reference's, so the
-layers' state-dicts load unchanged; the rope tables and the fused q|k|v copy of fuse_qkv() are not part of them.
+The attention core is torch's scaled_dot_product_attention, as in the reference, unless fuse_decode() is on and the step has one token.
+Parameter and buffer names are the reference's, so the layers' state-dicts load unchanged; the rope tables, the fused q|k|v copy of
+fuse_qkv() and the fuse_decode() flag are not part of them.
 """
 from __future__ import annotations
 
@@ -114,6 +116,7 @@ class QuantLlamaAttention(nn.Module):
         self.inv_freq, self.attention_scaling = rope_inv_freq(head_dim, rope_theta, rope_scaling)  # plain attributes: not in the state-dict
         self._cos = self._sin = None  # rope tables, built lazily up to the cache capacity on the module's device
         self._qkv = None  # fuse_qkv(): the fused q|k|v layer, kept outside the module tree (not in the state-dict)
+        self._decode = False  # fuse_decode(): a plain flag (not in the state-dict; kept by load_state_dict and .to())
         # a plain function: a bound method would make module -> hook -> module a reference cycle (see QuantLlamaMLP)
         self._register_load_state_dict_pre_hook(_drop_fused_qkv_on_load, with_module=True)
 
@@ -144,6 +147,27 @@ class QuantLlamaAttention(nn.Module):
     @property
     def qkv_fused(self) -> bool:
         return self._qkv is not None
+
+    def fuse_decode(self):
+        """Opt-in: a step of one token (s = 1) runs the split-K decode attention kernel over the cache (decode_attention), which writes
+        o_proj's input already int8-quantised: two launches in place of scaled_dot_product_attention and dynamic_quant.  Prefill, chunks
+        (s > 1) and head shapes the kernel does not take (head_dim other than 64 / 128, more than 8 query heads per KV head, h * head_dim
+        above 16384) keep the SDPA path.  state_dict(): unchanged.  Returns self."""
+        self._decode = True
+        return self
+
+    def unfuse_decode(self):
+        """Back to scaled_dot_product_attention + dynamic_quant for every step."""
+        self._decode = False
+        return self
+
+    @property
+    def decode_fused(self) -> bool:
+        return self._decode
+
+    def _decode_supported(self) -> bool:
+        h, kvh, d = self.num_heads, self.num_key_value_heads, self.head_dim
+        return d in (64, 128) and h // kvh <= 8 and h * d <= 16384
 
     def _apply(self, fn, recurse=True):
         super()._apply(fn, recurse=recurse)
@@ -182,7 +206,12 @@ class QuantLlamaAttention(nn.Module):
             raise RuntimeError(f"forward_int8: tokens {start} ... {start + s - 1} do not fit the cache capacity {cache.capacity}")
         cos, sin = self.rope_tables(cache.capacity)
         q, k, v = self.project_qkv(xq, s1)
-        q_out = ops.rope_qkv(q, k, v, cos, sin, cache.positions(start, s), cache.k[self.layer_idx], cache.v[self.layer_idx])
+        pos = cache.positions(start, s)
+        kc, vc = cache.k[self.layer_idx], cache.v[self.layer_idx]
+        q_out = ops.rope_qkv(q, k, v, cos, sin, pos, kc, vc)
+        if self._decode and s == 1 and self._decode_supported():
+            aq, a1 = ops.decode_attention(q_out, kc, vc, pos, self.scaling, max_len=start + 1)
+            return self.o_proj.forward_int8(aq, a1)
         aq, a1 = ops.dynamic_quant(self.attend(q_out, cache, start))
         return self.o_proj.forward_int8(aq.reshape(m, -1), a1.reshape(m, 1))
 
@@ -235,6 +264,19 @@ class QuantLlamaDecoderLayer(nn.Module):
                    head_dim=getattr(config, "head_dim", None) or config.hidden_size // heads,
                    qkv_bias=True if qwen2 else bias, o_bias=False if qwen2 else bias, rms_norm_eps=config.rms_norm_eps,
                    rope_theta=theta, rope_scaling=rope, layer_idx=layer_idx)
+
+    def fuse_decode(self):
+        """self_attn.fuse_decode(): one-token steps take the split-K decode attention kernel.  Returns self."""
+        self.self_attn.fuse_decode()
+        return self
+
+    def unfuse_decode(self):
+        self.self_attn.unfuse_decode()
+        return self
+
+    @property
+    def decode_fused(self) -> bool:
+        return self.self_attn.decode_fused
 
     def forward(self, hidden: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
         x = hidden.reshape(-1, self.hidden_size)

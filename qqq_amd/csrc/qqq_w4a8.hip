@@ -67,6 +67,8 @@
 #include "../../include/qqq_amd_act.h"
 #include "qqq_attn.hip.h"
 #include "../../include/qqq_amd_attn.h"
+#include "qqq_decode.hip.h"
+#include "../../include/qqq_amd_decode.h"
 #include "qqq_rates.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1579,6 +1581,106 @@ extern "C" int qqq_rope_qkv(const void* q, int ld_q, const void* k, int ld_k, co
                      static_cast<_Float16*>(v_cache), s, h, kvh, d, cap);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_rope_qkv_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- split-K decode attention (include/qqq_amd_decode.h; kernels in qqq_decode.hip.h).  Split count: about four 4-wave workgroups per
+// CU over all (row, KV head) pairs -- the 16 waves a CU holds at the split kernel's 4 waves per SIMD, each with one 16 KB K/V block in
+// flight -- at most DEC_MAX_SPLITS and one per DEC_ROUND keys of max_len; the workspace is sized for the bound alone, so it does not
+// depend on the device.
+static constexpr int DEC_MAX_SPLITS = 32;
+
+static int decode_split_bound(int max_len) {
+  const int by_len = (max_len + DEC_ROUND - 1) / DEC_ROUND;
+  return by_len < DEC_MAX_SPLITS ? by_len : DEC_MAX_SPLITS;
+}
+
+static const char* decode_shape_error(int b, int h, int kvh, int d, int max_len) {
+  if (b < 0 || h < 1 || kvh < 1 || h % kvh != 0 || h / kvh > DEC_GMAX || (d != 64 && d != 128) || (long long)h * d > 16384 ||
+      b > 65535 || max_len < 1)
+    return "bad shape";
+  return nullptr;
+}
+
+extern "C" size_t qqq_decode_attn_workspace_bytes(int b, int h, int kvh, int d, int max_len) {
+  if (b == 0 || decode_shape_error(b, h, kvh, d, max_len)) return 0;
+  return (size_t)b * h * decode_split_bound(max_len) * (size_t)(d + 2) * sizeof(float);
+}
+
+template <int VPT>
+static void decode_combine(int b, hipStream_t st, const float* wo, const float* wml, const long long* pos, long long limit, _Float16* o16,
+                           int8_t* xq, float* s1, int h, int d, int chunk, int splits) {
+  hipLaunchKernelGGL((qqq_decode_combine_kernel<VPT, DEC_COMBINE_NT>), dim3(b), dim3(DEC_COMBINE_NT), 0, st, wo, wml, pos, limit, o16, xq,
+                     s1, h, d, chunk, splits);
+}
+
+extern "C" int qqq_decode_attn(const void* q, const void* k_cache, const void* v_cache, const void* pos, float scale, void* o_fp16, void* xq,
+                               void* s1, void* workspace, size_t workspace_bytes, int b, int h, int kvh, int d, int cap, int max_len, int dev,
+                               void* stream) {
+  g_err[0] = 0;
+  if (b < 0 || h < 0 || kvh < 0 || d < 0 || cap < 0 || max_len < 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn: negative size (b=%d h=%d kvh=%d d=%d cap=%d max_len=%d)", b, h, kvh, d, cap, max_len);
+    return QQQ_ERR_ARG;
+  }
+  if (b == 0) return QQQ_OK;
+  if (decode_shape_error(b, h, kvh, d, max_len) || max_len > cap) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn: bad shape b=%d h=%d kvh=%d d=%d cap=%d max_len=%d (need h %% kvh == 0, h / kvh <= %d, "
+             "d 64 or 128, h*d <= 16384, b <= 65535, 1 <= max_len <= cap)", b, h, kvh, d, cap, max_len, DEC_GMAX);
+    return QQQ_ERR_ARG;
+  }
+  if (!o_fp16 && !xq && !s1) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn: no output (o_fp16 and xq / s1 are all NULL)");
+    return QQQ_ERR_ARG;
+  }
+  if (!q || !k_cache || !v_cache || !pos || !workspace || (!xq) != (!s1) || misaligned(q, 16) || misaligned(k_cache, 16) ||
+      misaligned(v_cache, 16) || misaligned(pos, 8) || misaligned(workspace, 16) || (o_fp16 && misaligned(o_fp16, 16)) ||
+      (xq && misaligned(xq, 8)) || (s1 && misaligned(s1, 4))) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn: bad argument (q / caches / pos / workspace must be non-NULL, xq and s1 both given or "
+             "both NULL; q, caches, o_fp16, workspace 16-byte, pos / xq 8-byte, s1 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  const size_t need = qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len);
+  if (workspace_bytes < need) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn: workspace of %zu bytes, need %zu", workspace_bytes, need);
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int bk = b * kvh;
+  int splits = (4 * device_cus_of(dev) + bk - 1) / bk;
+  const int bound = decode_split_bound(max_len);
+  splits = splits < 1 ? 1 : (splits > bound ? bound : splits);
+  const int per = (max_len + splits - 1) / splits;
+  const int chunk = (per + DEC_ROUND - 1) / DEC_ROUND * DEC_ROUND;
+  splits = (max_len + chunk - 1) / chunk;
+  float* wo = static_cast<float*>(workspace);
+  float* wml = wo + (size_t)b * h * splits * d;
+  const long long* pp = static_cast<const long long*>(pos);
+  const long long limit = max_len;  // <= cap
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const _Float16* qp = static_cast<const _Float16*>(q);
+  const _Float16* kp = static_cast<const _Float16*>(k_cache);
+  const _Float16* vp = static_cast<const _Float16*>(v_cache);
+  if (d == 64)
+    hipLaunchKernelGGL((qqq_decode_split_kernel<64>), dim3(splits, kvh, b), dim3(DEC_WAVES * 64), 0, st, qp, kp, vp, pp, limit, scale_log2,
+                       wo, wml, h, kvh, cap, chunk, splits);
+  else
+    hipLaunchKernelGGL((qqq_decode_split_kernel<128>), dim3(splits, kvh, b), dim3(DEC_WAVES * 64), 0, st, qp, kp, vp, pp, limit, scale_log2,
+                       wo, wml, h, kvh, cap, chunk, splits);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_decode_split_kernel launch");
+  _Float16* o16 = static_cast<_Float16*>(o_fp16);
+  int8_t* xqp = static_cast<int8_t*>(xq);
+  float* s1p = static_cast<float*>(s1);
+  const int nvec = h * d / 8;
+  if (nvec <= DEC_COMBINE_NT)
+    decode_combine<1>(b, st, wo, wml, pp, limit, o16, xqp, s1p, h, d, chunk, splits);
+  else if (nvec <= 2 * DEC_COMBINE_NT)
+    decode_combine<2>(b, st, wo, wml, pp, limit, o16, xqp, s1p, h, d, chunk, splits);
+  else
+    decode_combine<4>(b, st, wo, wml, pp, limit, o16, xqp, s1p, h, d, chunk, splits);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_decode_combine_kernel launch");
   return QQQ_OK;
 }
 

@@ -554,3 +554,81 @@ def rope_qkv(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tenso
     if _compiling(q, k, v, cos, sin, pos, k_cache, v_cache):
         return _rope_qkv_op(q, k, v, cos, sin, pos, k_cache, v_cache)
     return _rope_qkv_impl(q, k, v, cos, sin, pos, k_cache, v_cache)
+
+
+# ---- split-K decode attention (include/qqq_amd_decode.h): one query token per batch row over the static KV cache, written as o_proj's
+# int8-quantised input; two launches (splits, then the combine that quantises).
+
+def _decode_attention_shapes(q_out, k_cache, pos, max_len):
+    # (b, h, kvh, d, cap, max_len) from the tensors' shapes; raises for anything the kernels could not take
+    if k_cache.dim() != 4:
+        raise RuntimeError("decode_attention: k_cache must be fp16 [b, kvh, cap, d]")
+    b, kvh, cap, d = k_cache.shape
+    if q_out.dim() != 4 or q_out.shape[0] != b or q_out.shape[2] != 1 or q_out.shape[3] != d:
+        raise RuntimeError(f"decode_attention: q_out {tuple(q_out.shape)} must be [{b}, h, 1, {d}] (rope_qkv's output at s = 1)")
+    if pos.numel() != b:
+        raise RuntimeError(f"decode_attention: pos holds {pos.numel()} positions, the cache's batch is {b}")
+    max_len = cap if max_len is None else int(max_len)
+    return b, q_out.shape[1], kvh, d, cap, max_len
+
+
+def _decode_attention_impl(q_out, k_cache, v_cache, pos, scale, max_len, return_fp16):
+    ts = (q_out, k_cache, v_cache, pos)
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError("decode_attention: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != q_out.device for t in ts):
+        raise RuntimeError("decode_attention: every tensor must be on the same GPU")
+    if any(t.dtype != torch.float16 for t in (q_out, k_cache, v_cache)) or pos.dtype != torch.int64:
+        raise RuntimeError("decode_attention: q_out and the caches must be fp16, pos int64")
+    b, h, kvh, d, cap, max_len = _decode_attention_shapes(q_out, k_cache, pos, max_len)
+    if v_cache.shape != k_cache.shape:
+        raise RuntimeError("decode_attention: v_cache must have k_cache's shape")
+    if not (k_cache.is_contiguous() and v_cache.is_contiguous()):
+        raise RuntimeError("decode_attention: the caches must be contiguous")
+    dev = q_out.device
+    xq = torch.empty((b, h * d), dtype=torch.int8, device=dev)
+    s1 = torch.empty((b, 1), dtype=torch.float32, device=dev)
+    o16 = torch.empty((b, h * d) if return_fp16 else (0,), dtype=torch.float16, device=dev)
+    if b == 0:
+        return xq, s1, o16
+    L = _lib.lib()
+    nbytes = L.qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)  # torch's allocator: also under stream / graph capture
+    q2, pos = q_out.contiguous(), pos.contiguous()
+    err = L.qqq_decode_attn(_ptr(q2), _ptr(k_cache), _ptr(v_cache), _ptr(pos), float(scale), _ptr(o16), _ptr(xq), _ptr(s1), _ptr(ws),
+                            ws.numel(), b, h, kvh, d, cap, max_len, dev.index or 0, _stream_for(q_out))
+    if err:
+        raise RuntimeError(f"qqq_amd: decode_attention error {err}: {_lib.last_error()}")
+    return xq, s1, o16
+
+
+@torch.library.custom_op("qqq_amd::decode_attn", mutates_args=())
+def _decode_attn_op(q_out: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, scale: float,
+                    max_len: Optional[int], return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _decode_attention_impl(q_out, k_cache, v_cache, pos, scale, max_len, return_fp16)
+
+
+@_decode_attn_op.register_fake
+def _(q_out, k_cache, v_cache, pos, scale, max_len, return_fp16):
+    b, h, _, d, _, _ = _decode_attention_shapes(q_out, k_cache, pos, max_len)
+    return (q_out.new_empty((b, h * d), dtype=torch.int8), q_out.new_empty((b, 1), dtype=torch.float32),
+            q_out.new_empty((b, h * d) if return_fp16 else (0,), dtype=torch.float16))
+
+
+def decode_attention(q_out: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, scale: float,
+                     max_len: Optional[int] = None, return_fp16: bool = False):
+    """Attention of one query token per batch row over the static KV cache, quantised for o_proj: (xq int8 [b, h*d], s1 f32 [b, 1]) --
+    dynamic_quant of the fp16 attention output, bit for bit -- plus that fp16 output [b, h*d] with `return_fp16`.
+
+    q_out      fp16 [b, h, 1, d], rope_qkv's output at s = 1;  k_cache, v_cache  fp16 [b, kvh, cap, d] (h % kvh == 0, h / kvh <= 8,
+               d 64 or 128, h*d <= 16384)
+    pos        int64 [b] positions in device memory: row bi attends keys 0 ... pos[bi] (the new token already in the cache)
+    scale      the score scale (head_dim ** -0.5);  max_len  the launch is sized for positions below it (default: cap), so a captured graph
+               replays at any position below max_len
+    Split-K over the keys with all query heads of a KV head in one workgroup; fp32 softmax and accumulation, probabilities rounded to fp16
+    for the P.V product.  A row whose position is outside [0, min(cap, max_len)) writes nothing (its outputs are left uninitialised)."""
+    if _compiling(q_out, k_cache, v_cache, pos):
+        out = _decode_attn_op(q_out, k_cache, v_cache, pos, scale, max_len, return_fp16)
+    else:
+        out = _decode_attention_impl(q_out, k_cache, v_cache, pos, scale, max_len, return_fp16)
+    return out if return_fp16 else out[:2]

@@ -9,13 +9,19 @@ KV cache.  Both paths start from the fp16 output of input_layernorm and end with
     fused       QuantLlamaAttention.forward(y): dynamic_quant once, q/k/v forward_int8, rope_qkv into the static cache, SDPA,
                 dynamic_quant, o_proj.forward_int8
     fused_qkv   the same after fuse_qkv(): one q|k|v GEMM whose column ranges rope_qkv reads in place
+    fused_decode  (decode points) fuse_qkv() + fuse_decode(): decode_attention (split-K over the cache, output int8-quantised) in place of
+                SDPA and the dynamic_quant in front of o_proj
 
-Points: decode (s = 1) at b in {1, 16} with a context of {1024, 4096} tokens (the new token included); prefill of s in {128, 1024, 4096}
-tokens at b = 1 from position 0.
+Points: decode (s = 1) at b in {1, 16} with a context of {1024, 4096} tokens (the new token included), and b = 1 at 16384; prefill of s in
+{128, 1024, 4096} tokens at b = 1 from position 0.  Before each point one dynamic_quant of POINT_MARK + i rows is launched: its grid marks
+where point i starts in a kernel trace.
 
     python tools/bench_attn.py [--points decode,prefill] [--out FILE]   -> one JSON object on stdout
-    python tools/bench_attn.py --summarize TRACE_DIR                    -> qqq_rope_qkv_kernel times and HBM fractions from a rocprofv3
-                                                                          --kernel-trace run of the above
+    python tools/bench_attn.py --summarize TRACE_DIR [--bench FILE]     -> from a rocprofv3 --kernel-trace run of the above: the
+                                                                          qqq_rope_qkv_kernel times and HBM fractions, and per decode point
+                                                                          (labelled from the run's JSON output FILE) the median times of
+                                                                          the two decode-attention kernels, their K/V bytes as a fraction
+                                                                          of 8 TB/s, and SDPA's attn_fwd
 """
 import argparse
 import collections
@@ -31,7 +37,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 HIDDEN, D = 4096, 128
 SHAPES = {"llama2_7b": (32, 32), "llama3_8b": (32, 8)}
-DECODE = [(b, ctx) for b in (1, 16) for ctx in (1024, 4096)]
+DECODE = [(b, ctx) for b in (1, 16) for ctx in (1024, 4096)] + [(1, 16384)]
+POINT_MARK = 100000  # rows of the marker dynamic_quant launched before point i: POINT_MARK + i (no other call here has that many)
 PREFILL = (128, 1024, 4096)
 HBM_BYTES_PER_S = 8e12
 ROPE_NT = 128  # qqq_w4a8.hip: ROPE_NT
@@ -48,7 +55,7 @@ def run(points, group_sizes):
     import torch.nn.functional as F
 
     from bench_llama import make_ql, time_fn
-    from qqq_amd import KVCache, QuantLlamaAttention
+    from qqq_amd import KVCache, QuantLlamaAttention, dynamic_quant
 
     dev = torch.device("cuda:0")
     out = {"hidden": HIDDEN, "head_dim": D, "unit": "us per call, hipGraph replay (median)", "points": []}
@@ -82,6 +89,7 @@ def run(points, group_sizes):
                 def fused():
                     return attn.forward(y, cache, start)
 
+                dynamic_quant(torch.zeros((POINT_MARK + len(out["points"]), 8), dtype=torch.float16, device=dev))
                 pt = {"shape": shape, "heads": h, "kv_heads": kvh, "group_size": gs, "kind": kind, "batch": b, "tokens": s,
                       "context": start + s}
                 attn.unfuse_qkv()
@@ -89,6 +97,10 @@ def run(points, group_sizes):
                 pt["fused"] = round(time_fn(fused), 2)
                 attn.fuse_qkv()
                 pt["fused_qkv"] = round(time_fn(fused), 2)
+                if kind == "decode":
+                    attn.fuse_decode()
+                    pt["fused_decode"] = round(time_fn(fused), 2)
+                    attn.unfuse_decode()
                 attn.unfuse_qkv()
                 pt["saved"] = round(pt["unfused"] - pt["fused"], 2)
                 pt["saved_qkv"] = round(pt["unfused"] - pt["fused_qkv"], 2)
@@ -99,21 +111,37 @@ def run(points, group_sizes):
     return out
 
 
-def summarize(trace_dir):
+def _median(v):
+    v = sorted(v)
+    return round(v[len(v) // 2], 2)
+
+
+def summarize(trace_dir, bench=None):
     from code_object import _demangle
 
     times = collections.defaultdict(list)
+    per_point = collections.defaultdict(lambda: collections.defaultdict(list))  # point -> kernel -> [us]
+    rows_all = []
     for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
-        for r in csv.DictReader(open(f)):
-            name = r["Kernel_Name"]
-            name = name[5:] if name.startswith("void ") else name
-            name = name.split("(")[0]
-            name = _demangle(name) if name.startswith("_Z") else name
-            if not name.startswith("qqq_rope_qkv_kernel"):
-                continue
-            m = int(r["Grid_Size_X"]) // int(r["Workgroup_Size_X"])
+        rows_all += list(csv.DictReader(open(f)))
+    point = None
+    for r in sorted(rows_all, key=lambda r: int(r["Start_Timestamp"])):
+        name = r["Kernel_Name"]
+        name = name[5:] if name.startswith("void ") else name
+        name = name.split("(")[0]
+        name = _demangle(name) if name.startswith("_Z") else name
+        us = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+        grid = int(r["Grid_Size_X"]) // int(r["Workgroup_Size_X"])
+        if name.startswith("qqq_dynamic_quant_kernel") and grid >= POINT_MARK:
+            point = grid - POINT_MARK
+            continue
+        if point is not None:
+            for key in ("qqq_decode_split_kernel", "qqq_decode_combine_kernel", "attn_fwd"):
+                if name.startswith(key) or (key == "attn_fwd" and "attn_fwd" in name):
+                    per_point[point][key].append(us)
+        if name.startswith("qqq_rope_qkv_kernel"):
             gy = int(r.get("Grid_Size_Y", 1)) // max(1, int(r.get("Workgroup_Size_Y", 1)))
-            times[(m, gy)].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+            times[(grid, gy)].append(us)
     # the shape behind a launch: grid y = ceil((h + 2 kvh) * D / 16 / ROPE_NT) blocks
     by_gy = {-(-(h + 2 * kvh) * (D // 16) // ROPE_NT): (name, h, kvh) for name, (h, kvh) in SHAPES.items()}
     rows = []
@@ -127,7 +155,20 @@ def summarize(trace_dir):
         nbytes = m * width * 2 * 2 + m * D * 2 * 2  # q|k|v read + q, k, v written; one cos and one sin row per token
         rows.append({"kernel": "qqq_rope_qkv_kernel", "shape": name, "tokens": m, "calls": len(v), "median_us": round(med, 2),
                      "min_us": round(v[0], 2), "bytes": nbytes, "hbm_fraction_of_8TBps": round(nbytes / (med * 1e-6) / HBM_BYTES_PER_S, 4)})
-    return {"unit": "kernel time from rocprofv3 --kernel-trace (median over calls)", "kernels": rows}
+    points = json.load(open(bench))["points"] if bench else []
+    decode = []
+    for i, ks in sorted(per_point.items()):
+        pt = points[i] if i < len(points) else {}
+        row = {"point": i}
+        row.update({k: pt[k] for k in ("shape", "group_size", "kind", "batch", "context", "fused_qkv", "fused_decode") if k in pt})
+        for key, v in ks.items():
+            row[key + "_median_us"], row[key + "_calls"] = _median(v), len(v)
+        if "qqq_decode_split_kernel" in ks and "context" in pt:
+            both = row["qqq_decode_split_kernel_median_us"] + row.get("qqq_decode_combine_kernel_median_us", 0.0)
+            kv = 2 * pt["batch"] * pt["kv_heads"] * pt["context"] * D * 2  # K and V, fp16
+            row.update({"decode_kernels_us": round(both, 2), "kv_bytes": kv, "kv_fraction_of_8TBps": round(kv / (both * 1e-6) / HBM_BYTES_PER_S, 4)})
+        decode.append(row)
+    return {"unit": "kernel time from rocprofv3 --kernel-trace (median over calls)", "kernels": rows, "points": decode}
 
 
 def main():
@@ -136,9 +177,10 @@ def main():
     ap.add_argument("--group-sizes", default="-1,128")
     ap.add_argument("--out", default=None)
     ap.add_argument("--summarize", default=None, metavar="TRACE_DIR")
+    ap.add_argument("--bench", default=None, metavar="FILE", help="--summarize: the JSON output of the traced run, to label the points")
     a = ap.parse_args()
     if a.summarize:
-        res = summarize(a.summarize)
+        res = summarize(a.summarize, a.bench)
     else:
         res = run(a.points.split(","), [int(v) for v in a.group_sizes.split(",")])
     s = json.dumps(res)
