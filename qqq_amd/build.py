@@ -1,6 +1,8 @@
 """Builds the gfx950 HIP libraries with hipcc, in-tree:
 
-    qqq_amd/libqqq_amd.so      the operator (include/qqq_amd.h)      <- csrc/qqq_w4a8.hip (+ csrc/*.hip.h)
+    qqq_amd/libqqq_amd.so      the operator (include/qqq_amd.h)      <- csrc/qqq_w4a8.hip: ONE translation unit -- the C-ABI entry points -- that includes
+                               the kernels with their launch tables (csrc/qqq_*.hip.h) and the dispatch planner (csrc/qqq_plan.h + the generated
+                               csrc/qqq_rates.h: pure host C++, compiles alone with the host compiler)
     qqq_amd/libqqq_amd_dev.so  test / tuning companion (include/qqq_amd_dev.h) <- csrc/qqq_dev.hip
     qqq_amd/_torch_ext*.so     compiled torch binding (pybind + TORCH_LIBRARY) of the operator library <- csrc/qqq_torch.cpp
 
@@ -13,7 +15,7 @@ import shutil
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(_HERE, "csrc", "qqq_w4a8.hip")  # the one translation unit of the operator; it includes csrc/*.hip.h
+SRC = os.path.join(_HERE, "csrc", "qqq_w4a8.hip")  # the one translation unit of the operator; it includes csrc/*.hip.h and csrc/qqq_plan.h
 DEV_SRC = os.path.join(_HERE, "csrc", "qqq_dev.hip")
 HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd.h")
 ACT_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_act.h")

@@ -172,4 +172,32 @@ __global__ __launch_bounds__(WAVES * 64) void qqq_column_kernel(
 }
 
 
+// ---- host side: the launch table (every instantiation of the kernel above) ----
+template <int MT, bool GROUPED, int WAVES, int PF>
+static hipError_t launch_column_t(const LaunchArgs& a, int ksplit) {
+  dim3 grid(a.N / 32, ksplit, (a.M + 16 * MT - 1) / (16 * MT));
+  hipLaunchKernelGGL((qqq_column_kernel<MT, GROUPED, WAVES, PF>), grid, dim3(WAVES * 64), 0, a.stream, a.A,
+                     a.B, a.C, a.D, a.s1, a.s2, a.s3, a.acc_out, a.bias, a.M, a.N, a.K, ksplit);
+  return hipGetLastError();
+}
+
+template <bool GROUPED>
+static hipError_t launch_column_g(const LaunchArgs& a, int mt, int pf, int ksplit, int waves) {
+  if (waves == 16 && mt == 1) return launch_column_t<1, GROUPED, 16, 3>(a, ksplit);  // (tune.waves = 16: sixteen waves split K inside the workgroup)
+  if (mt >= 2) {
+    if (pf <= 4) return launch_column_t<2, GROUPED, 8, 4>(a, ksplit);
+    return launch_column_t<2, GROUPED, 8, 8>(a, ksplit);
+  }
+  if (pf <= 2) return launch_column_t<1, GROUPED, 8, 2>(a, ksplit);
+  if (pf <= 3) return launch_column_t<1, GROUPED, 8, 3>(a, ksplit);
+  if (pf <= 4) return launch_column_t<1, GROUPED, 8, 4>(a, ksplit);
+  if (pf <= 6) return launch_column_t<1, GROUPED, 8, 6>(a, ksplit);
+  if (pf <= 8) return launch_column_t<1, GROUPED, 8, 8>(a, ksplit);
+  return launch_column_t<1, GROUPED, 8, 12>(a, ksplit);
+}
+
+static hipError_t launch_column(const LaunchArgs& a, bool grouped, int mt, int pf, int ksplit, int waves = 8) {
+  return grouped ? launch_column_g<true>(a, mt, pf, ksplit, waves) : launch_column_g<false>(a, mt, pf, ksplit, waves);
+}
+
 #endif  // QQQ_AMD_QQQ_COLUMN_HIP_H_

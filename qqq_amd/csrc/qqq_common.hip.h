@@ -198,4 +198,37 @@ __device__ __forceinline__ v4i load16_agent(__amdgpu_buffer_rsrc_t view, const u
   return (v4i){(int)v.x, (int)v.y, (int)v.z, (int)v.w};
 }
 
+// ---- host side: what every family's launch table is handed ----
+struct LaunchArgs {
+  const int8_t* A;
+  const unsigned char* B;
+  int32_t* C;
+  _Float16* D;
+  const float* s1;
+  const float* s2;
+  const _Float16* s3;
+  int32_t* acc_out;
+  int* tickets;
+  const _Float16* bias;
+  int M, N, K;
+  int skew;    // panel: 128-k stages the last K slice gets on top of an even share (0 = even slices)
+  int hflags;  // in-launch split-K hand-off switches (tune.fused bits 2 / 3 / 4): 1 = formal acquire fence, 2 = release on publish, 4 = never L2-local deposits
+  int cus;     // the CUs this call plans and launches with (the wide kernel's tile walk: one workgroup each)
+  hipStream_t stream;
+};
+
+// A kernel that asks for more dynamic LDS than the default limit has to be allowed to, once per instantiation and device: `done` is the launcher's own
+// static flag array (one per instantiation), indexed by the current device.
+template <typename Kernel>
+static hipError_t allow_dynamic_lds(Kernel kern, int lds_bytes, bool (&done)[64]) {
+  int cur = 0;
+  (void)hipGetDevice(&cur);
+  if (cur < 0 || cur >= 64 || !done[cur]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+    if (e != hipSuccess) return e;
+    if (cur >= 0 && cur < 64) done[cur] = true;
+  }
+  return hipSuccess;
+}
+
 #endif  // QQQ_AMD_QQQ_COMMON_HIP_H_

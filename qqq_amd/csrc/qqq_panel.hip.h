@@ -641,4 +641,65 @@ __global__ __launch_bounds__(64 * WN * KG) void qqq_panel_kernel(
 #endif
 }
 
+// ---- host side: the launch table (every instantiation of the kernel above) ----
+template <int MT, bool GROUPED, int WN, int KG, int PFS, int XL, int HW = 1>
+static hipError_t launch_panel_t(const LaunchArgs& a, int ksplit) {
+  constexpr int ROWS = 16 * MT, BN = 32 * WN * HW;
+  constexpr int XBUF = (qqq_panel_relaxed(KG, PFS, XL, HW) ? 4 : KG == 2 ? 2 : 3) * ROWS * 128;
+  constexpr int EP = ROWS * (BN + 4) * 4;
+  constexpr int RED = (KG == 2) ? WN * MT * HW * 2048 : 0;
+  constexpr int LDS = XBUF > EP ? (XBUF > RED ? XBUF : RED) : (EP > RED ? EP : RED);
+  static_assert(LDS <= 160 * 1024, "LDS budget");
+  static bool attr_set[64] = {};  // per instantiation, per device
+  auto kern = qqq_panel_kernel<MT, GROUPED, WN, KG, PFS, XL, HW>;
+  if (hipError_t e = allow_dynamic_lds(kern, LDS, attr_set); e != hipSuccess) return e;
+  dim3 grid((a.N + BN - 1) / BN, ksplit, (a.M + ROWS - 1) / ROWS);
+  hipLaunchKernelGGL(kern, grid, dim3(64 * WN * KG), LDS, a.stream, a.A, a.B, a.C, a.D, a.s1, a.s2, a.s3, a.acc_out,
+                     a.tickets, a.bias, a.M, a.N, a.K, ksplit | ((a.hflags & 0xff) << 16) | ((ksplit > 1 ? a.skew & 0x3f : 0) << 24));
+  return hipGetLastError();
+}
+
+template <int MT, bool GROUPED, int PFS, int XL>
+static hipError_t launch_panel_shape(const LaunchArgs& a, int bn, int waves, int cw, int ksplit) {
+  if constexpr (MT == 8 && PFS >= 3 && (PFS == XL || (PFS == 4 && XL == 2))) {  // 64 columns per wave (two k-groups of 4 waves)
+    if (bn == 256 && cw == 2) return launch_panel_t<MT, GROUPED, 4, 2, PFS, XL, 2>(a, ksplit);
+    // (128-column strips as four waves x 64 columns x two k-groups -- one wave per SIMD, half the fragment reads and unpack work per MFMA --
+    //  were instantiated and measured in round 5: 46.1 vs 37.3 us at 128 tokens, 21.7 vs 16.5 on 4096 x 4096: nobody hides a lone
+    //  wave's stalls.  Not kept; profiles/r05_uneven_k_slices.txt has the lines.)
+  }
+  if (bn == 256) return launch_panel_t<MT, GROUPED, 8, 1, PFS, XL>(a, ksplit);
+  if (waves == 4) return launch_panel_t<MT, GROUPED, 4, 1, PFS, XL>(a, ksplit);
+  // (a NINTH wave feeding the activations by LDS-DMA -- so that they do not queue behind the weight loads in the compute waves' in-order
+  //  return queues -- was built and measured in round 5: bit-exact, 150 cases, and level with this kernel everywhere, 35.4 vs 35.4 us at 128
+  //  tokens: it is the L2 <-> CU traffic of the activations that costs, not how it is issued.  Not kept; profiles/r05_panel_feeder.txt)
+  return launch_panel_t<MT, GROUPED, 4, 2, PFS, XL>(a, ksplit);
+}
+
+template <int MT, bool GROUPED>
+static hipError_t launch_panel_pf(const LaunchArgs& a, int bn, int waves, int cw, int pfs, int xl, int ksplit) {
+  // XL (activation lead) = PFS (weight lead) unless asked otherwise: loads return in order, so a shorter activation
+  // lead would force the weight loads issued before it to land early and cut their effective lead to XL + 1
+  if (pfs <= 2) return launch_panel_shape<MT, GROUPED, 2, 2>(a, bn, waves, cw, ksplit);
+  if constexpr (MT <= 4) {
+    if (pfs >= 8) return launch_panel_shape<MT, GROUPED, 8, 8>(a, bn, waves, cw, ksplit);
+  }
+  if (pfs >= 6 || pfs == 3) return launch_panel_shape<MT, GROUPED, 3, 3>(a, bn, waves, cw, ksplit);
+  if (xl == 2) return launch_panel_shape<MT, GROUPED, 4, 2>(a, bn, waves, cw, ksplit);
+  return launch_panel_shape<MT, GROUPED, 4, 4>(a, bn, waves, cw, ksplit);
+}
+
+template <bool GROUPED>
+static hipError_t launch_panel_g(const LaunchArgs& a, int mt, int bn, int waves, int cw, int pfs, int xl, int ksplit) {
+  switch (mt) {
+    case 1: return launch_panel_pf<1, GROUPED>(a, bn, waves, cw, pfs, xl, ksplit);
+    case 2: return launch_panel_pf<2, GROUPED>(a, bn, waves, cw, pfs, xl, ksplit);
+    case 4: return launch_panel_pf<4, GROUPED>(a, bn, waves, cw, pfs, xl, ksplit);
+    default: return launch_panel_pf<8, GROUPED>(a, bn, waves, cw, pfs, xl, ksplit);
+  }
+}
+
+static hipError_t launch_panel(const LaunchArgs& a, bool grouped, int mt, int bn, int waves, int cw, int pfs, int xl, int ksplit) {
+  return grouped ? launch_panel_g<true>(a, mt, bn, waves, cw, pfs, xl, ksplit) : launch_panel_g<false>(a, mt, bn, waves, cw, pfs, xl, ksplit);
+}
+
 #endif  // QQQ_AMD_QQQ_PANEL_HIP_H_

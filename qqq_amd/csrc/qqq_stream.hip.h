@@ -310,4 +310,49 @@ __global__ __launch_bounds__(WAVES * 64) void qqq_stream_kernel(
 }
 
 
+// ---- host side: the launch table (every instantiation of the kernel above) ----
+template <int MT, bool GROUPED, int WAVES, int PF>
+static hipError_t launch_stream_t(const LaunchArgs& a, int ksplit, int fused) {
+  dim3 grid((a.N + 127) / 128, ksplit & 0xffff, (a.M + 16 * MT - 1) / (16 * MT));
+  hipLaunchKernelGGL((qqq_stream_kernel<MT, GROUPED, WAVES, PF>), grid, dim3(WAVES * 64), 0, a.stream,
+                     a.A, a.B, a.C, a.D, a.s1, a.s2, a.s3, a.acc_out, a.tickets, a.bias, a.M, a.N, a.K,
+                     ksplit, fused);
+  return hipGetLastError();
+}
+
+// prefetch depth PF (ring slots of 4 KiB weights per wave): deeper for the small-m bodies
+template <bool GROUPED, int WAVES>
+static hipError_t launch_stream_mt(const LaunchArgs& a, int mt, int pf, int ksplit, int fused) {
+  if constexpr (WAVES == 16) {
+    // 1024-thread blocks cap VGPRs at 128: only the MT=1 / PF=3 body fits (host never asks otherwise)
+    return launch_stream_t<1, GROUPED, 16, 3>(a, ksplit, fused);
+  } else {
+    switch (mt) {
+      case 1:
+        if (pf >= 7) return launch_stream_t<1, GROUPED, WAVES, 7>(a, ksplit, fused);
+        if (pf >= 5) return launch_stream_t<1, GROUPED, WAVES, 5>(a, ksplit, fused);
+        return launch_stream_t<1, GROUPED, WAVES, 3>(a, ksplit, fused);
+      case 2:
+        if (pf >= 5) return launch_stream_t<2, GROUPED, WAVES, 5>(a, ksplit, fused);
+        return launch_stream_t<2, GROUPED, WAVES, 3>(a, ksplit, fused);
+      case 3:
+        return launch_stream_t<3, GROUPED, WAVES, 2>(a, ksplit, fused);
+      default:
+        return launch_stream_t<4, GROUPED, WAVES, 2>(a, ksplit, fused);
+    }
+  }
+}
+
+static hipError_t launch_stream(const LaunchArgs& a, bool grouped, int mt, int waves, int pf, int ksplit,
+                                int fused) {
+  if (grouped) {
+    if (waves == 4) return launch_stream_mt<true, 4>(a, mt, pf, ksplit, fused);
+    if (waves == 16) return launch_stream_mt<true, 16>(a, mt, pf, ksplit, fused);
+    return launch_stream_mt<true, 8>(a, mt, pf, ksplit, fused);
+  }
+  if (waves == 4) return launch_stream_mt<false, 4>(a, mt, pf, ksplit, fused);
+  if (waves == 16) return launch_stream_mt<false, 16>(a, mt, pf, ksplit, fused);
+  return launch_stream_mt<false, 8>(a, mt, pf, ksplit, fused);
+}
+
 #endif  // QQQ_AMD_QQQ_STREAM_HIP_H_

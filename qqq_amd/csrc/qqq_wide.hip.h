@@ -1296,4 +1296,57 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 #endif
 }
 
+// ---- host side: the launch table (every instantiation of the kernel above) ----
+// MODE: 0 per-channel, 1 per-group (re-quantised in the loop), 2 = expanded int8 weights (a.B is the W8 tensor of qqq_expand_int8)
+template <int MODE, int MT, int P, int RS, int HW, bool CHAIN = false>
+static hipError_t launch_wide_t(const LaunchArgs& a, int pw, int ksplit) {
+  constexpr int ROWS = 16 * MT, BN = 128 * HW;
+  constexpr int XBUF = P * ROWS * 128, EP = (HW == 2 ? 8 * MT : 16 * MT) * (BN + 4) * 4 + 16;  // + the ticket exchange word
+  constexpr int CH = XBUF + 2 * (ROWS * 4 + BN * 6);  // CHAIN: stage buffers + two scale regions, no epilogue image
+  constexpr int LDS = CHAIN ? CH : (XBUF > EP ? XBUF : EP);
+  static_assert(LDS <= 160 * 1024, "LDS budget");
+  static bool attr_set[64] = {};  // per instantiation, per device
+  auto kern = qqq_wide_kernel<MODE, MT, P, RS, HW, CHAIN>;
+  if (hipError_t e = allow_dynamic_lds(kern, LDS, attr_set); e != hipSuccess) return e;
+  const int tiles_m = (a.M + ROWS - 1) / ROWS, tiles_n = (a.N + BN - 1) / BN;
+  const int grid = CHAIN ? (a.cus & ~7) : tiles_m * tiles_n * ksplit;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), LDS, a.stream, a.A, a.B, a.C, a.D, a.s1, a.s2, a.s3,
+                     a.acc_out, a.tickets, a.bias, a.M, a.N, a.K, tiles_m, tiles_n, pw,
+                     ksplit | ((a.hflags & 0xff) << 16) | ((!CHAIN && ksplit > 1 ? a.skew & 0x3f : 0) << 24));
+  return hipGetLastError();
+}
+
+// mt: 16 (256-token tiles) or 8 (128-token tiles); pf: weight ring in 64-k steps (4 or 8); four LDS stage buffers;
+// bn: 256 columns per workgroup, or (mt = 16 only) 128: 32 columns per wave
+template <int MODE, int MT>
+static hipError_t launch_wide_m(const LaunchArgs& a, int pf, int pw, int ksplit) {
+  return pf == 4 ? launch_wide_t<MODE, MT, 4, 4, 2>(a, pw, ksplit) : launch_wide_t<MODE, MT, 4, 8, 2>(a, pw, ksplit);
+}
+// the persistent tile walk: the ring depth each mode runs by default (per-channel 4 steps, per-group 8; expanded weights: 256 x 256 tiles only)
+static hipError_t launch_wide_chain(const LaunchArgs& a, int mode, int mt, int bn, int pw) {
+  // (expanded weights: ring of 4 steps -- 64 registers; with 8 the walk's seam spills inside the stage loop: 32 registers, 75 scratch instructions)
+  if (mode == 2) return launch_wide_t<2, 16, 4, 4, 2, true>(a, pw, 1);
+  const bool grouped = mode == 1;
+  if (bn == 128) return grouped ? launch_wide_t<1, 16, 4, 4, 1, true>(a, pw, 1) : launch_wide_t<0, 16, 4, 4, 1, true>(a, pw, 1);
+  if (mt == 8) return grouped ? launch_wide_t<1, 8, 4, 4, 2, true>(a, pw, 1) : launch_wide_t<0, 8, 4, 4, 2, true>(a, pw, 1);
+  return grouped ? launch_wide_t<1, 16, 4, 4, 2, true>(a, pw, 1) : launch_wide_t<0, 16, 4, 4, 2, true>(a, pw, 1);
+}
+static hipError_t launch_wide(const LaunchArgs& a, int mode, int mt, int bn, int pf, int pw, int ksplit, bool chain = false) {
+  if (chain) return launch_wide_chain(a, mode, mt, bn, pw);
+  if (mode == 2) {
+    // expanded weights: ring of 4 steps in every shape (the ring holds ready operands -- 16 registers per step, not 8; 4 measured 1 - 1.5 % ahead of 8 on the
+    // 256 x 256 tiles, profiles/r06_w8_first_numbers.txt; with 8 the 128-token shape parks ring registers in accumulation registers)
+    if (bn == 128) return launch_wide_t<2, 16, 4, 4, 1>(a, pw, ksplit);
+    if (mt == 8) return launch_wide_t<2, 8, 4, 4, 2>(a, pw, ksplit);
+    return launch_wide_t<2, 16, 4, 4, 2>(a, pw, ksplit);
+  }
+  const bool grouped = mode == 1;
+  if (bn == 128) {
+    if (grouped) return pf == 4 ? launch_wide_t<1, 16, 4, 4, 1>(a, pw, ksplit) : launch_wide_t<1, 16, 4, 8, 1>(a, pw, ksplit);
+    return pf == 4 ? launch_wide_t<0, 16, 4, 4, 1>(a, pw, ksplit) : launch_wide_t<0, 16, 4, 8, 1>(a, pw, ksplit);
+  }
+  if (mt == 8) return grouped ? launch_wide_m<1, 8>(a, pf, pw, ksplit) : launch_wide_m<0, 8>(a, pf, pw, ksplit);
+  return grouped ? launch_wide_m<1, 16>(a, pf, pw, ksplit) : launch_wide_m<0, 16>(a, pf, pw, ksplit);
+}
+
 #endif  // QQQ_AMD_QQQ_WIDE_HIP_H_

@@ -459,3 +459,21 @@ def test_plan_is_pure_host_logic_with_the_mi355x_cu_count():
     assert p["kernel"] == 5 and p["glds"] == 2, p
     p = _lib.plan(2048, 4096, 4096, -1, 16)   # 128 tiles: fewer than one per CU -> one tile per workgroup
     assert p["kernel"] == 5 and p["glds"] == 1, p
+
+
+def test_planner_header_is_pure_host_code(tmp_path):
+    """csrc/qqq_plan.h -- make_plan, the cost models, the M split -- compiles ALONE with the host compiler: no HIP header, no __global__, nothing of the
+    kernels' translation unit.  That is what lets a planner change be compiled and compared (tools/plan_dump.py) without building a kernel; a HIP
+    dependency that creeps in fails here."""
+    import shutil
+    import subprocess
+
+    gxx = shutil.which("g++")
+    assert gxx, "g++ not found: the planner header's host-purity check needs the host compiler"
+    hdr = os.path.join(ROOT, "qqq_amd", "csrc", "qqq_plan.h")
+    src = open(hdr).read() + open(os.path.join(ROOT, "qqq_amd", "csrc", "qqq_rates.h")).read()
+    assert not re.search(r"\bhip[A-Z_]\w*|__global__|__device__|#include\s*<hip", src)
+    includes = set(re.findall(r'#include\s*([<"][^>"]+[>"])', open(hdr).read()))
+    assert {i for i in includes if i.startswith('"')} == {'"../../include/qqq_amd.h"', '"qqq_rates.h"'}, includes
+    r = subprocess.run([gxx, "-std=c++17", "-fsyntax-only", "-Wall", "-Wno-unused-function", "-x", "c++", hdr], capture_output=True, text=True, cwd=tmp_path)
+    assert r.returncode == 0 and not r.stderr.strip(), r.stderr

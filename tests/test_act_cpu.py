@@ -84,7 +84,7 @@ def test_kernels_in_the_code_object_without_scratch_or_spills():
     build.build()
     ks = {k["demangled"]: k for k in code_object.kernels(build.LIB)}
     for fam in ("qqq_rmsnorm_quant_kernel", "qqq_silu_mul_quant_kernel"):
-        # the launch shapes of the host dispatch (qqq_w4a8.hip: act_launch)
+        # the launch shapes of the host dispatch (qqq_w4a8.hip: act_launch, the one ladder of the three per-row quantisers)
         for vpt, nt in ((2, 256), (4, 256), (8, 256), (2, 1024), (4, 1024), (8, 1024)):
             k = ks[f"{fam}<{vpt},{nt}>"]
             assert k["private_segment_fixed_size"] == 0 and k["vgpr_spill_count"] == 0 and k["sgpr_spill_count"] == 0, k

@@ -1,4 +1,4 @@
-"""The kernels' lane-level address arithmetic (tests/lane_model.py mirrors qqq_w4a8.hip) reproduces the
+"""The kernels' lane-level address arithmetic (tests/lane_model.py mirrors the kernels of qqq_amd/csrc/qqq_*.hip.h) reproduces the
 oracle's int32 accumulators: packed-layout decode, LDS swizzles, MFMA operand/accumulator maps, split-K,
 m/n edge handling and the XCD-aware tile order.  CPU only."""
 import numpy as np

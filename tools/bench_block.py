@@ -100,7 +100,7 @@ def run(ms, group_sizes):
 
 def _k_of(name):
     # the row length behind a kernel instance in THIS tool's runs: the <VPT, NT> instances that cover k = 4096 (VPT * NT * 8 == 4096) are only
-    # launched for the hidden size, every other instance for the intermediate size (include/qqq_amd_act.h dispatch: qqq_w4a8.hip act_launch)
+    # launched for the hidden size, every other instance for the intermediate size (include/qqq_amd_act.h dispatch: act_launch in qqq_w4a8.hip, shared with qqq_dynamic_quant)
     vpt, nt = (int(v) for v in name.split("<")[1].rstrip(">").split(","))
     return HIDDEN if vpt * nt * 8 == HIDDEN else INTER
 

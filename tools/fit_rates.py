@@ -13,7 +13,7 @@ these rates is followed by: re-measure (tools/visits/r5_v07.sh), re-run this too
 
 The wide kernel's three tile shapes (256 x 256, 256 x 128, 128 x 256; columns wide / w16x2 / w128 / w128x2 / w8 of the checks run with WIDE_SHAPES=1) get the
 three rates of wide_estimate's form -- us = 3.7 + rounds * (fixed + handoff * [ksplit > 1] * tile KiB / 256 + stages per workgroup * t_stage * load) with the
-rounds / load rules of qqq_w4a8.hip -- fitted the same way per (shape, mode).
+rounds / load rules of qqq_plan.h -- fitted the same way per (shape, mode).
 
 Up to 64 tokens the column kernel (1 ... 32 tokens) and the stream kernel get one linear form per token range and mode (small_features below; columns column /
 stream of the checks), fitted the same way.
@@ -67,7 +67,7 @@ WIDE_LAUNCH, WIDE_LO = 3.7, (0.80, 0.85)  # the part of wide_estimate's form tha
 
 
 def wide_features(tl, ks, rows, bn, nst, grouped):
-    """(rounds, rounds * [split] * tile KiB / 256, rounds * stages per workgroup * load) -- wide_estimate's rounds / load rules (qqq_w4a8.hip)"""
+    """(rounds, rounds * [split] * tile KiB / 256, rounds * stages per workgroup * load) -- wide_estimate's rounds / load rules (qqq_plan.h)"""
     x = tl * ks / 256.0
     cx = math.ceil(x)
     rounds = 1.0 if x <= 1.0 else cx - 0.3 * (cx - x)
@@ -162,7 +162,7 @@ def collect_small(files):
 
 
 def small_features(fam, grouped, M, N, K):
-    """the linear forms of column_small_estimate / stream_small_estimate / the 33 ... 64-token branch of stream_estimate (qqq_w4a8.hip); None outside a form's range"""
+    """the linear forms of column_small_estimate / stream_small_estimate / the 33 ... 64-token branch of stream_estimate (qqq_plan.h); None outside a form's range"""
     if fam == "column":
         wgs = N // 32
         rounds = (wgs + 255) // 256
@@ -284,7 +284,7 @@ def main():
     lines += ["};", ""]
     wide = collect_wide(files)
     wnames = ("256 x 256 tiles", "256 x 128 tiles (32 columns per wave)", "128 x 256 tiles")
-    lines += ["// wide kernel: us = 3.7 + rounds * (fixed + handoff * [ksplit > 1] * tile KiB / 256 + stages per workgroup * t_stage * load); rounds / load: wide_estimate (qqq_w4a8.hip)",
+    lines += ["// wide kernel: us = 3.7 + rounds * (fixed + handoff * [ksplit > 1] * tile KiB / 256 + stages per workgroup * t_stage * load); rounds / load: wide_estimate (qqq_plan.h)",
               "struct QqqWideRate { double fixed, handoff, t_stage; };", "// [shape][per-channel, per-group, expanded int8 weights (profiles/r06_w8_dispatch_check_main.txt)]",
               "static const QqqWideRate kQqqWideRates[3][3] = {"]
     fitted = {}
@@ -315,7 +315,7 @@ def main():
         return "{" + ", ".join("%.5g" % c for c in coef) + "}  /* %d points, %.1f %%, %.0f %% */" % (n, 100 * mae, 100 * worst)
 
     lines += ["// up to 64 tokens: the column kernel (1 ... 32 tokens) and the stream kernel, one linear form per kernel, token range and mode (column_small_estimate, stream_small_estimate,",
-              "// stream_estimate in qqq_w4a8.hip say what the terms are); MB = N K / 2e6, pb = a pass over the weights at 5 TB/s in us, r = rounds of 256 workgroups (x 0.92 from the second)",
+              "// stream_estimate in qqq_plan.h say what the terms are); MB = N K / 2e6, pb = a pass over the weights at 5 TB/s in us, r = rounds of 256 workgroups (x 0.92 from the second)",
               "struct QqqSmallRates {",
               "  double col_pc[4];   // c0 + c1 MB + c2 K m rounds / 1e6 + c3 K / 1000 max(0, 1 - workgroups / 256)",
               "  double col_g[4];    // g0 + g1 K r / 1000 + g2 (K r / 1000) ((m - 16) / 16)^0.75 [m > 16] + g3 MB",
