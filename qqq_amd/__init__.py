@@ -12,10 +12,12 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     QuantLinear.forward_int8(xq, s1), QuantRMSNorm, QuantLlamaMLP                     # the layer on pre-quantised input; qqq_amd/blocks.py
     rope_qkv(q, k, v, cos, sin, pos, k_cache, v_cache)                              # RoPE on q/k + static KV-cache write, one launch
     decode_attention(q_out, k_cache, v_cache, pos, scale)                           # split-K decode attention over the cache, output int8-quantised
+    rope_qkv_kv8(..., k_cache, v_cache, k_scale, v_scale) / decode_attention_kv8(...)  # the same two over an int8 KV cache (KVCache(dtype=torch.int8))
     KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer                            # attention and the whole layer; qqq_amd/attention.py
 """
 from .ops import (  # noqa: F401
     decode_attention,
+    decode_attention_kv8,
     dynamic_quant,
     expand_int8,
     marlin_qqq_gemm,
@@ -27,6 +29,7 @@ from .ops import (  # noqa: F401
     quantlinear_forward,
     rmsnorm_quant,
     rope_qkv,
+    rope_qkv_kv8,
     silu_mul_quant,
 )
 from .qlinear import QuantLinear, fuse_quant_linears  # noqa: F401
@@ -35,4 +38,4 @@ from .attention import KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer  # n
 
 __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_int8", "mul", "marlin_qqq_gemm", "dynamic_quant", "quantlinear_forward",
            "rmsnorm_quant", "silu_mul_quant", "QuantLinear", "fuse_quant_linears", "QuantRMSNorm", "QuantLlamaMLP",
-           "rope_qkv", "decode_attention", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer"]
+           "rope_qkv", "decode_attention", "rope_qkv_kv8", "decode_attention_kv8", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer"]

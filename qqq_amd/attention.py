@@ -2,7 +2,8 @@
 QuantizedLlamaAttention / QuantizedQwen2Attention and Quantized{Llama,Qwen2}DecoderLayer (QQQ/gptq/models/llama.py, qwen2.py).
 
     rope_tables       cos / sin tables [length, head_dim] as transformers' rotary embedding computes them (rope_type "default", "llama3")
-    KVCache           static fp16 K / V per layer, [b, kvh, capacity, head_dim], allocated once: no history copy per step
+    KVCache           static fp16 K / V per layer, [b, kvh, capacity, head_dim], allocated once: no history copy per step; opt-in
+                      dtype=torch.int8: every head row as int8 codes and one f32 scale (rope_qkv_kv8 / decode_attention_kv8)
     QuantLlamaAttention      q/k/v GEMMs on the int8 input of QuantRMSNorm -> rope_qkv (RoPE on q and k, k / v into the cache, one launch)
                              -> scaled_dot_product_attention -> dynamic_quant -> o_proj;  opt-in fuse_decode(): one-token steps take
                              decode_attention (split-K over the cache, output int8-quantised) in place of the last two
@@ -63,27 +64,51 @@ def rope_tables(inv_freq: torch.Tensor, attention_scaling: float, length: int, d
 
 
 class KVCache:
-    """Static fp16 key / value cache of `num_layers` layers: k[layer], v[layer] of shape [batch, num_kv_heads, capacity, head_dim],
-    allocated (zeroed) once, written in place by rope_qkv at each token's position.  Memory: 4 * num_layers * batch * num_kv_heads *
-    capacity * head_dim bytes (K and V, 2 bytes an element).  Every batch row is at the same position (no per-row lengths, no paging)."""
+    """Static key / value cache of `num_layers` layers: k[layer], v[layer] of shape [batch, num_kv_heads, capacity, head_dim], allocated
+    (zeroed) once, written in place by rope_qkv at each token's position.  Every batch row is at the same position (no per-row lengths, no
+    paging).
 
-    def __init__(self, num_layers: int, batch: int, num_kv_heads: int, head_dim: int, capacity: int, device=None):
+    dtype=torch.float16 (default): fp16 K and V, 4 * num_layers * batch * num_kv_heads * capacity * head_dim bytes.
+    dtype=torch.int8: every head row is dynamic_quant of that fp16 row -- int8 codes in k / v plus one f32 scale per row in k_scale[layer],
+    v_scale[layer] of shape [batch, num_kv_heads, capacity] -- written by rope_qkv_kv8 and read by decode_attention_kv8:
+    2 * num_layers * batch * num_kv_heads * capacity * (head_dim + 4) bytes.  Any other dtype raises."""
+
+    def __init__(self, num_layers: int, batch: int, num_kv_heads: int, head_dim: int, capacity: int, device=None, dtype=torch.float16):
+        if dtype not in (torch.float16, torch.int8):
+            raise ValueError(f"KVCache: dtype must be torch.float16 or torch.int8, not {dtype}")
         self.num_layers, self.batch, self.num_kv_heads, self.head_dim, self.capacity = num_layers, batch, num_kv_heads, head_dim, capacity
+        self.dtype = dtype
         shape = (batch, num_kv_heads, capacity, head_dim)
-        self.k = [torch.zeros(shape, dtype=torch.float16, device=device) for _ in range(num_layers)]
-        self.v = [torch.zeros(shape, dtype=torch.float16, device=device) for _ in range(num_layers)]
+        self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(num_layers)]
+        self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(num_layers)]
+        if dtype == torch.int8:
+            self.k_scale = [torch.zeros(shape[:3], dtype=torch.float32, device=device) for _ in range(num_layers)]
+            self.v_scale = [torch.zeros(shape[:3], dtype=torch.float32, device=device) for _ in range(num_layers)]
         # positions p of every batch row, [capacity, batch]: the s = 1 (decode) and b = 1 position vectors are views of it, no launch
         self._rep = torch.arange(capacity, device=device)[:, None].expand(capacity, batch).contiguous()
 
     @property
+    def quantized(self) -> bool:
+        return self.dtype == torch.int8
+
+    @property
     def nbytes(self) -> int:
-        return 4 * self.num_layers * self.batch * self.num_kv_heads * self.capacity * self.head_dim
+        rows = self.num_layers * self.batch * self.num_kv_heads * self.capacity
+        return 2 * rows * (self.head_dim + 4) if self.quantized else 4 * rows * self.head_dim
 
     def positions(self, start: int, s: int) -> torch.Tensor:
         """int64 [batch * s] device positions start ... start+s-1 of every batch row (token bi * s + si)."""
         if s == 1 or self.batch == 1:
             return self._rep[start:start + s].reshape(-1)
         return self._rep[start:start + s, 0].repeat(self.batch)
+
+    def dequant(self, layer: int, length: int):
+        """(k, v) fp16 [batch, num_kv_heads, length, head_dim] of an int8 cache's first `length` slots: fp16(float(code) * scale), plain
+        torch on the cache's device (CPU tensors too)."""
+        if not self.quantized:
+            raise RuntimeError("KVCache.dequant: the cache is not int8")
+        return tuple((c[:, :, :length].float() * sc[:, :, :length, None]).half()
+                     for c, sc in ((self.k[layer], self.k_scale[layer]), (self.v[layer], self.v_scale[layer])))
 
 
 def _drop_fused_qkv_on_load(module, *args, **kwargs):
@@ -185,10 +210,14 @@ class QuantLlamaAttention(nn.Module):
 
     def attend(self, q_out: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
         """scaled_dot_product_attention of q_out [b, h, s, d] over the cache slice [:, :, :start+s] -> fp16 [b, s, h*d]: causal for a
-        prefill from 0, a bottom-right causal mask for a chunk at start > 0, no mask for one token."""
+        prefill from 0, a bottom-right causal mask for a chunk at start > 0, no mask for one token.  An int8 cache is dequantised first
+        (KVCache.dequant), so prefill attends to the quantised K / V that decode reads later."""
         b, h, s, d = q_out.shape
-        kc = cache.k[self.layer_idx][:, :, :start + s]
-        vc = cache.v[self.layer_idx][:, :, :start + s]
+        if cache.quantized:
+            kc, vc = cache.dequant(self.layer_idx, start + s)
+        else:
+            kc = cache.k[self.layer_idx][:, :, :start + s]
+            vc = cache.v[self.layer_idx][:, :, :start + s]
         mask = None
         if s > 1 and start > 0:
             mask = torch.ones((s, start + s), dtype=torch.bool, device=q_out.device).tril(diagonal=start)
@@ -204,14 +233,24 @@ class QuantLlamaAttention(nn.Module):
         s = m // b
         if start < 0 or start + s > cache.capacity:
             raise RuntimeError(f"forward_int8: tokens {start} ... {start + s - 1} do not fit the cache capacity {cache.capacity}")
+        if cache.quantized and not self._decode_supported():
+            raise NotImplementedError(f"an int8 KV cache needs head_dim 64 or 128, at most 8 query heads per KV head and h * head_dim <= "
+                                      f"16384 (h={self.num_heads}, kvh={self.num_key_value_heads}, head_dim={self.head_dim})")
         cos, sin = self.rope_tables(cache.capacity)
         q, k, v = self.project_qkv(xq, s1)
         pos = cache.positions(start, s)
         kc, vc = cache.k[self.layer_idx], cache.v[self.layer_idx]
-        q_out = ops.rope_qkv(q, k, v, cos, sin, pos, kc, vc)
-        if self._decode and s == 1 and self._decode_supported():
-            aq, a1 = ops.decode_attention(q_out, kc, vc, pos, self.scaling, max_len=start + 1)
-            return self.o_proj.forward_int8(aq, a1)
+        if cache.quantized:  # the int8 cache is the opt-in: one-token steps take its decode kernel whatever fuse_decode() says
+            ksc, vsc = cache.k_scale[self.layer_idx], cache.v_scale[self.layer_idx]
+            q_out = ops.rope_qkv_kv8(q, k, v, cos, sin, pos, kc, vc, ksc, vsc)
+            if s == 1:
+                aq, a1 = ops.decode_attention_kv8(q_out, kc, vc, ksc, vsc, pos, self.scaling, max_len=start + 1)
+                return self.o_proj.forward_int8(aq, a1)
+        else:
+            q_out = ops.rope_qkv(q, k, v, cos, sin, pos, kc, vc)
+            if self._decode and s == 1 and self._decode_supported():
+                aq, a1 = ops.decode_attention(q_out, kc, vc, pos, self.scaling, max_len=start + 1)
+                return self.o_proj.forward_int8(aq, a1)
         aq, a1 = ops.dynamic_quant(self.attend(q_out, cache, start))
         return self.o_proj.forward_int8(aq.reshape(m, -1), a1.reshape(m, 1))
 

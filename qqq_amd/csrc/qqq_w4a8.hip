@@ -30,6 +30,7 @@
 //   qqq_tiled.hip.h    "tiled" kernel: tune.kernel = 2 only -- the fuzzers' independent reference, the fallback beyond 4 GB of packed weights
 //   qqq_small.hip.h    split-K reduce, dynamic quantiser, int4 packer / unpacker, int8 expander
 //   qqq_act.hip.h, qqq_attn.hip.h, qqq_decode.hip.h   the decoder block's fused quantisers, RoPE + KV-cache write, split-K decode attention
+//   qqq_kv8.hip.h      the int8 KV cache: the quantising RoPE / cache write and the decode split kernel that reads it
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -60,6 +61,8 @@
 #include "../../include/qqq_amd_attn.h"
 #include "qqq_decode.hip.h"
 #include "../../include/qqq_amd_decode.h"
+#include "qqq_kv8.hip.h"
+#include "../../include/qqq_amd_kv8.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -559,6 +562,35 @@ static void decode_combine(int b, hipStream_t st, const float* wo, const float* 
                      s1, h, d, chunk, splits);
 }
 
+// splits and keys per split of a call: the same for the fp16 and the int8 cache
+static void decode_split_plan(int dev, int b, int kvh, int max_len, int* splits_out, int* chunk_out) {
+  const int bk = b * kvh;
+  int splits = (4 * device_cus_of(dev) + bk - 1) / bk;
+  const int bound = decode_split_bound(max_len);
+  splits = splits < 1 ? 1 : (splits > bound ? bound : splits);
+  const int per = (max_len + splits - 1) / splits;
+  const int chunk = (per + DEC_ROUND - 1) / DEC_ROUND * DEC_ROUND;
+  *splits_out = (max_len + chunk - 1) / chunk;
+  *chunk_out = chunk;
+}
+
+static int decode_combine_launch(int b, hipStream_t st, const float* wo, const float* wml, const long long* pp, long long limit, void* o_fp16,
+                                 void* xq, void* s1, int h, int d, int chunk, int splits) {
+  _Float16* o16 = static_cast<_Float16*>(o_fp16);
+  int8_t* xqp = static_cast<int8_t*>(xq);
+  float* s1p = static_cast<float*>(s1);
+  const int nvec = h * d / 8;
+  if (nvec <= DEC_COMBINE_NT)
+    decode_combine<1>(b, st, wo, wml, pp, limit, o16, xqp, s1p, h, d, chunk, splits);
+  else if (nvec <= 2 * DEC_COMBINE_NT)
+    decode_combine<2>(b, st, wo, wml, pp, limit, o16, xqp, s1p, h, d, chunk, splits);
+  else
+    decode_combine<4>(b, st, wo, wml, pp, limit, o16, xqp, s1p, h, d, chunk, splits);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_decode_combine_kernel launch");
+  return QQQ_OK;
+}
+
 extern "C" int qqq_decode_attn(const void* q, const void* k_cache, const void* v_cache, const void* pos, float scale, void* o_fp16, void* xq,
                                void* s1, void* workspace, size_t workspace_bytes, int b, int h, int kvh, int d, int cap, int max_len, int dev,
                                void* stream) {
@@ -591,13 +623,8 @@ extern "C" int qqq_decode_attn(const void* q, const void* k_cache, const void* v
   }
   DeviceGuard guard(dev);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int bk = b * kvh;
-  int splits = (4 * device_cus_of(dev) + bk - 1) / bk;
-  const int bound = decode_split_bound(max_len);
-  splits = splits < 1 ? 1 : (splits > bound ? bound : splits);
-  const int per = (max_len + splits - 1) / splits;
-  const int chunk = (per + DEC_ROUND - 1) / DEC_ROUND * DEC_ROUND;
-  splits = (max_len + chunk - 1) / chunk;
+  int splits, chunk;
+  decode_split_plan(dev, b, kvh, max_len, &splits, &chunk);
   float* wo = static_cast<float*>(workspace);
   float* wml = wo + (size_t)b * h * splits * d;
   const long long* pp = static_cast<const long long*>(pos);
@@ -614,19 +641,106 @@ extern "C" int qqq_decode_attn(const void* q, const void* k_cache, const void* v
                        wo, wml, h, kvh, cap, chunk, splits);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_decode_split_kernel launch");
-  _Float16* o16 = static_cast<_Float16*>(o_fp16);
-  int8_t* xqp = static_cast<int8_t*>(xq);
-  float* s1p = static_cast<float*>(s1);
-  const int nvec = h * d / 8;
-  if (nvec <= DEC_COMBINE_NT)
-    decode_combine<1>(b, st, wo, wml, pp, limit, o16, xqp, s1p, h, d, chunk, splits);
-  else if (nvec <= 2 * DEC_COMBINE_NT)
-    decode_combine<2>(b, st, wo, wml, pp, limit, o16, xqp, s1p, h, d, chunk, splits);
-  else
-    decode_combine<4>(b, st, wo, wml, pp, limit, o16, xqp, s1p, h, d, chunk, splits);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip(e, "qqq_decode_combine_kernel launch");
+  return decode_combine_launch(b, st, wo, wml, pp, limit, o_fp16, xq, s1, h, d, chunk, splits);
+}
+
+// ---- the int8 KV cache (include/qqq_amd_kv8.h; kernels in qqq_kv8.hip.h): qqq_rope_qkv's and qqq_decode_attn's launches with the
+// quantising / int8-reading kernels; the decode call ends in the same combine kernel.
+extern "C" int qqq_rope_qkv_kv8(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, const void* cos, const void* sin,
+                                int table_len, const void* pos, void* q_out, void* k_cache, void* v_cache, void* k_scale, void* v_scale,
+                                int b, int s, int h, int kvh, int d, int cap, int dev, void* stream) {
+  g_err[0] = 0;
+  if (b < 0 || s < 0 || h < 0 || kvh < 0 || d < 0 || cap < 0 || table_len < 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_rope_qkv_kv8: negative size (b=%d s=%d h=%d kvh=%d d=%d cap=%d table_len=%d)", b, s, h, kvh, d, cap,
+             table_len);
+    return QQQ_ERR_ARG;
+  }
+  if (b == 0 || s == 0) return QQQ_OK;
+  if ((long long)b * s > 0x7fffffffLL || h < 1 || kvh < 1 || h % kvh != 0 || (d != 64 && d != 128) ||
+      (long long)(h + 2LL * kvh) * d > (1LL << 20)) {
+    snprintf(g_err, sizeof(g_err), "qqq_rope_qkv_kv8: bad shape b=%d s=%d h=%d kvh=%d d=%d (need b*s < 2^31, h %% kvh == 0, d 64 or 128, "
+             "(h + 2 kvh) d <= 2^20)", b, s, h, kvh, d);
+    return QQQ_ERR_ARG;
+  }
+  if (ld_q < h * d || ld_k < kvh * d || ld_v < kvh * d || ld_q % 8 || ld_k % 8 || ld_v % 8) {
+    snprintf(g_err, sizeof(g_err), "qqq_rope_qkv_kv8: bad row strides ld_q=%d ld_k=%d ld_v=%d (need multiples of 8, >= h*d=%d / kvh*d=%d)",
+             ld_q, ld_k, ld_v, h * d, kvh * d);
+    return QQQ_ERR_ARG;
+  }
+  if (!q || !k || !v || !cos || !sin || !pos || !q_out || !k_cache || !v_cache || !k_scale || !v_scale || misaligned(q, 16) ||
+      misaligned(k, 16) || misaligned(v, 16) || misaligned(cos, 16) || misaligned(sin, 16) || misaligned(pos, 8) || misaligned(q_out, 16) ||
+      misaligned(k_cache, 16) || misaligned(v_cache, 16) || misaligned(k_scale, 4) || misaligned(v_scale, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_rope_qkv_kv8: bad argument (every pointer must be non-NULL; fp16 tensors and the caches 16-byte, pos "
+             "8-byte, the scales 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  const int items = (h + 2 * kvh) * (d / 16);
+  const long long limit = cap < table_len ? cap : table_len;
+  hipLaunchKernelGGL((qqq_kv8_rope_qkv_kernel<ROPE_NT>), dim3(b * s, (items + ROPE_NT - 1) / ROPE_NT), dim3(ROPE_NT), 0,
+                     static_cast<hipStream_t>(stream), static_cast<const _Float16*>(q), ld_q, static_cast<const _Float16*>(k), ld_k,
+                     static_cast<const _Float16*>(v), ld_v, static_cast<const _Float16*>(cos), static_cast<const _Float16*>(sin),
+                     static_cast<const long long*>(pos), limit, static_cast<_Float16*>(q_out), static_cast<int8_t*>(k_cache),
+                     static_cast<int8_t*>(v_cache), static_cast<float*>(k_scale), static_cast<float*>(v_scale), s, h, kvh, d, cap);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_kv8_rope_qkv_kernel launch");
   return QQQ_OK;
+}
+
+extern "C" int qqq_decode_attn_kv8(const void* q, const void* k_cache, const void* v_cache, const void* k_scale, const void* v_scale,
+                                   const void* pos, float scale, void* o_fp16, void* xq, void* s1, void* workspace, size_t workspace_bytes,
+                                   int b, int h, int kvh, int d, int cap, int max_len, int dev, void* stream) {
+  g_err[0] = 0;
+  if (b < 0 || h < 0 || kvh < 0 || d < 0 || cap < 0 || max_len < 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn_kv8: negative size (b=%d h=%d kvh=%d d=%d cap=%d max_len=%d)", b, h, kvh, d, cap,
+             max_len);
+    return QQQ_ERR_ARG;
+  }
+  if (b == 0) return QQQ_OK;
+  if (decode_shape_error(b, h, kvh, d, max_len) || max_len > cap) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn_kv8: bad shape b=%d h=%d kvh=%d d=%d cap=%d max_len=%d (need h %% kvh == 0, h / kvh <= "
+             "%d, d 64 or 128, h*d <= 16384, b <= 65535, 1 <= max_len <= cap)", b, h, kvh, d, cap, max_len, DEC_GMAX);
+    return QQQ_ERR_ARG;
+  }
+  if (!o_fp16 && !xq && !s1) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn_kv8: no output (o_fp16 and xq / s1 are all NULL)");
+    return QQQ_ERR_ARG;
+  }
+  if (!q || !k_cache || !v_cache || !k_scale || !v_scale || !pos || !workspace || (!xq) != (!s1) || misaligned(q, 16) ||
+      misaligned(k_cache, 16) || misaligned(v_cache, 16) || misaligned(k_scale, 4) || misaligned(v_scale, 4) || misaligned(pos, 8) ||
+      misaligned(workspace, 16) || (o_fp16 && misaligned(o_fp16, 16)) || (xq && misaligned(xq, 8)) || (s1 && misaligned(s1, 4))) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn_kv8: bad argument (q / caches / scales / pos / workspace must be non-NULL, xq and s1 both "
+             "given or both NULL; q, caches, o_fp16, workspace 16-byte, pos / xq 8-byte, s1 and the scales 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  const size_t need = qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len);
+  if (workspace_bytes < need) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn_kv8: workspace of %zu bytes, need %zu", workspace_bytes, need);
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int splits, chunk;
+  decode_split_plan(dev, b, kvh, max_len, &splits, &chunk);
+  float* wo = static_cast<float*>(workspace);
+  float* wml = wo + (size_t)b * h * splits * d;
+  const long long* pp = static_cast<const long long*>(pos);
+  const long long limit = max_len;  // <= cap
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const _Float16* qp = static_cast<const _Float16*>(q);
+  const int8_t* kp = static_cast<const int8_t*>(k_cache);
+  const int8_t* vp = static_cast<const int8_t*>(v_cache);
+  const float* ksp = static_cast<const float*>(k_scale);
+  const float* vsp = static_cast<const float*>(v_scale);
+  if (d == 64)
+    hipLaunchKernelGGL((qqq_kv8_decode_split_kernel<64>), dim3(splits, kvh, b), dim3(DEC_WAVES * 64), 0, st, qp, kp, vp, ksp, vsp, pp, limit,
+                       scale_log2, wo, wml, h, kvh, cap, chunk, splits);
+  else
+    hipLaunchKernelGGL((qqq_kv8_decode_split_kernel<128>), dim3(splits, kvh, b), dim3(DEC_WAVES * 64), 0, st, qp, kp, vp, ksp, vsp, pp, limit,
+                       scale_log2, wo, wml, h, kvh, cap, chunk, splits);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_kv8_decode_split_kernel launch");
+  return decode_combine_launch(b, st, wo, wml, pp, limit, o_fp16, xq, s1, h, d, chunk, splits);
 }
 
 extern "C" int qqq_quantlinear_forward(const void* x, void* xq, void* s1, const void* B, void* C, void* D,

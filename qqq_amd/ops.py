@@ -632,3 +632,126 @@ def decode_attention(q_out: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.
     else:
         out = _decode_attention_impl(q_out, k_cache, v_cache, pos, scale, max_len, return_fp16)
     return out if return_fp16 else out[:2]
+
+
+# ---- the int8 KV cache (include/qqq_amd_kv8.h): rope_qkv and decode_attention over caches that hold every head row as dynamic_quant of
+# the fp16 row -- int8 codes [b, kvh, cap, d] and one f32 scale per row [b, kvh, cap].
+
+def _kv8_check_caches(name, k_cache, v_cache, k_scale, v_scale):
+    if any(t.dtype != torch.int8 for t in (k_cache, v_cache)) or any(t.dtype != torch.float32 for t in (k_scale, v_scale)):
+        raise RuntimeError(f"{name}: the caches must be int8 and their scales f32")
+    if k_cache.dim() != 4:
+        raise RuntimeError(f"{name}: k_cache must be int8 [b, kvh, cap, d]")
+    if v_cache.shape != k_cache.shape or k_scale.shape != k_cache.shape[:3] or v_scale.shape != k_cache.shape[:3]:
+        raise RuntimeError(f"{name}: v_cache must have k_cache's shape [b, kvh, cap, d] and the scales its first three dimensions")
+    for nm, t in (("k_cache", k_cache), ("v_cache", v_cache), ("k_scale", k_scale), ("v_scale", v_scale)):
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name}: {nm} must be contiguous")
+
+
+def _rope_qkv_kv8_impl(q, k, v, cos, sin, pos, k_cache, v_cache, k_scale, v_scale):
+    ts = (q, k, v, cos, sin, pos, k_cache, v_cache, k_scale, v_scale)
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError("rope_qkv_kv8: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != q.device for t in ts):
+        raise RuntimeError("rope_qkv_kv8: every tensor must be on the same GPU")
+    if any(t.dtype != torch.float16 for t in (q, k, v, cos, sin)) or pos.dtype != torch.int64:
+        raise RuntimeError("rope_qkv_kv8: q, k, v, cos and sin must be fp16, pos int64")
+    _kv8_check_caches("rope_qkv_kv8", k_cache, v_cache, k_scale, v_scale)
+    b, s, h, kvh, d, cap = _rope_qkv_shapes(q, k, v, cos, pos, k_cache)
+    if sin.shape != cos.shape:
+        raise RuntimeError("rope_qkv_kv8: sin must have cos's shape")
+    q_out = torch.empty((b, h, s, d), dtype=torch.float16, device=q.device)
+    if q_out.numel() == 0:
+        return q_out
+    (q2, ld_q), (k2, ld_k), (v2, ld_v) = _rows(q, h * d), _rows(k, kvh * d), _rows(v, kvh * d)
+    cos, sin, pos = cos.contiguous(), sin.contiguous(), pos.contiguous()
+    err = _lib.lib().qqq_rope_qkv_kv8(_ptr(q2), ld_q, _ptr(k2), ld_k, _ptr(v2), ld_v, _ptr(cos), _ptr(sin), cos.shape[0], _ptr(pos),
+                                      _ptr(q_out), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), b, s, h, kvh, d, cap,
+                                      q.device.index or 0, _stream_for(q))
+    if err:
+        raise RuntimeError(f"qqq_amd: rope_qkv_kv8 error {err}: {_lib.last_error()}")
+    return q_out
+
+
+@torch.library.custom_op("qqq_amd::rope_qkv_kv8", mutates_args=("k_cache", "v_cache", "k_scale", "v_scale"))
+def _rope_qkv_kv8_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
+                     k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor) -> torch.Tensor:
+    return _rope_qkv_kv8_impl(q, k, v, cos, sin, pos, k_cache, v_cache, k_scale, v_scale)
+
+
+@_rope_qkv_kv8_op.register_fake
+def _(q, k, v, cos, sin, pos, k_cache, v_cache, k_scale, v_scale):
+    b, s, h, _, d, _ = _rope_qkv_shapes(q, k, v, cos, pos, k_cache)
+    return q.new_empty((b, h, s, d), dtype=torch.float16)
+
+
+def rope_qkv_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
+                 k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor) -> torch.Tensor:
+    """rope_qkv into an int8 cache, one launch: q_out is rope_qkv's, bit for bit; the rotated k row and the plain v row of every (token,
+    KV head) are stored as dynamic_quant of the fp16 row rope_qkv would have cached, bit for bit.
+
+    q, k, v, cos, sin, pos   as for rope_qkv (head_dim 64 or 128)
+    k_cache, v_cache  int8 [b, kvh, cap, d];  k_scale, v_scale  f32 [b, kvh, cap]; all four updated in place at each token's position
+    Returns q_out fp16 [b, h, s, d].  A token whose position is outside [0, min(cap, table_len)) writes nothing."""
+    ts = (q, k, v, cos, sin, pos, k_cache, v_cache, k_scale, v_scale)
+    if _compiling(*ts):
+        return _rope_qkv_kv8_op(*ts)
+    return _rope_qkv_kv8_impl(*ts)
+
+
+def _decode_attention_kv8_impl(q_out, k_cache, v_cache, k_scale, v_scale, pos, scale, max_len, return_fp16):
+    ts = (q_out, k_cache, v_cache, k_scale, v_scale, pos)
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError("decode_attention_kv8: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != q_out.device for t in ts):
+        raise RuntimeError("decode_attention_kv8: every tensor must be on the same GPU")
+    if q_out.dtype != torch.float16 or pos.dtype != torch.int64:
+        raise RuntimeError("decode_attention_kv8: q_out must be fp16, pos int64")
+    _kv8_check_caches("decode_attention_kv8", k_cache, v_cache, k_scale, v_scale)
+    b, h, kvh, d, cap, max_len = _decode_attention_shapes(q_out, k_cache, pos, max_len)
+    dev = q_out.device
+    xq = torch.empty((b, h * d), dtype=torch.int8, device=dev)
+    s1 = torch.empty((b, 1), dtype=torch.float32, device=dev)
+    o16 = torch.empty((b, h * d) if return_fp16 else (0,), dtype=torch.float16, device=dev)
+    if b == 0:
+        return xq, s1, o16
+    L = _lib.lib()
+    nbytes = L.qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)  # torch's allocator: also under stream / graph capture
+    q2, pos = q_out.contiguous(), pos.contiguous()
+    err = L.qqq_decode_attn_kv8(_ptr(q2), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(pos), float(scale), _ptr(o16),
+                                _ptr(xq), _ptr(s1), _ptr(ws), ws.numel(), b, h, kvh, d, cap, max_len, dev.index or 0, _stream_for(q_out))
+    if err:
+        raise RuntimeError(f"qqq_amd: decode_attention_kv8 error {err}: {_lib.last_error()}")
+    return xq, s1, o16
+
+
+@torch.library.custom_op("qqq_amd::decode_attn_kv8", mutates_args=())
+def _decode_attn_kv8_op(q_out: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                        pos: torch.Tensor, scale: float, max_len: Optional[int],
+                        return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _decode_attention_kv8_impl(q_out, k_cache, v_cache, k_scale, v_scale, pos, scale, max_len, return_fp16)
+
+
+@_decode_attn_kv8_op.register_fake
+def _(q_out, k_cache, v_cache, k_scale, v_scale, pos, scale, max_len, return_fp16):
+    b, h, _, d, _, _ = _decode_attention_shapes(q_out, k_cache, pos, max_len)
+    return (q_out.new_empty((b, h * d), dtype=torch.int8), q_out.new_empty((b, 1), dtype=torch.float32),
+            q_out.new_empty((b, h * d) if return_fp16 else (0,), dtype=torch.float16))
+
+
+def decode_attention_kv8(q_out: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                         pos: torch.Tensor, scale: float, max_len: Optional[int] = None, return_fp16: bool = False):
+    """decode_attention over an int8 cache: (xq int8 [b, h*d], s1 f32 [b, 1]), plus the fp16 output [b, h*d] with `return_fp16`.
+
+    q_out      fp16 [b, h, 1, d], rope_qkv_kv8's output at s = 1 (q is not quantised)
+    k_cache, v_cache  int8 [b, kvh, cap, d];  k_scale, v_scale  f32 [b, kvh, cap]: the cache rope_qkv_kv8 fills, only read here
+    pos, scale, max_len   as for decode_attention; so are the shape limits and the out-of-range rule
+    Scores are (q . codes) in fp32 times k_scale[key] * scale; fp32 softmax; the probabilities are rounded to fp16 and a value enters P.V
+    as fp16(code * v_scale[key]); fp32 accumulation."""
+    if _compiling(q_out, k_cache, v_cache, k_scale, v_scale, pos):
+        out = _decode_attn_kv8_op(q_out, k_cache, v_cache, k_scale, v_scale, pos, scale, max_len, return_fp16)
+    else:
+        out = _decode_attention_kv8_impl(q_out, k_cache, v_cache, k_scale, v_scale, pos, scale, max_len, return_fp16)
+    return out if return_fp16 else out[:2]

@@ -11,12 +11,15 @@ KV cache.  Both paths start from the fp16 output of input_layernorm and end with
     fused_qkv   the same after fuse_qkv(): one q|k|v GEMM whose column ranges rope_qkv reads in place
     fused_decode  (decode points) fuse_qkv() + fuse_decode(): decode_attention (split-K over the cache, output int8-quantised) in place of
                 SDPA and the dynamic_quant in front of o_proj
+    fused_decode_kv8  (--kv8, decode points) the same with KVCache(dtype=torch.int8): rope_qkv_kv8 + decode_attention_kv8.  It is timed
+                alternately with fused_decode, KV8_ROUNDS times each in the same process; both lists are kept (`*_runs`) and the medians
+                reported (`fused_decode_alt`, `fused_decode_kv8`).  Prefill points get `fused_qkv_kv8` (SDPA over the dequantised cache).
 
 Points: decode (s = 1) at b in {1, 16} with a context of {1024, 4096} tokens (the new token included), and b = 1 at 16384; prefill of s in
 {128, 1024, 4096} tokens at b = 1 from position 0.  Before each point one dynamic_quant of POINT_MARK + i rows is launched: its grid marks
 where point i starts in a kernel trace.
 
-    python tools/bench_attn.py [--points decode,prefill] [--out FILE]   -> one JSON object on stdout
+    python tools/bench_attn.py [--points decode,prefill] [--kv8] [--out FILE]   -> one JSON object on stdout
     python tools/bench_attn.py --summarize TRACE_DIR [--bench FILE]     -> from a rocprofv3 --kernel-trace run of the above: the
                                                                           qqq_rope_qkv_kernel times and HBM fractions, and per decode point
                                                                           (labelled from the run's JSON output FILE) the median times of
@@ -42,6 +45,7 @@ POINT_MARK = 100000  # rows of the marker dynamic_quant launched before point i:
 PREFILL = (128, 1024, 4096)
 HBM_BYTES_PER_S = 8e12
 ROPE_NT = 128  # qqq_w4a8.hip: ROPE_NT
+KV8_ROUNDS = 3  # --kv8: alternations of fused_decode / fused_decode_kv8 at a decode point
 
 
 def _rotate_half(x):
@@ -50,7 +54,7 @@ def _rotate_half(x):
     return torch.cat((-x[..., x.shape[-1] // 2:], x[..., : x.shape[-1] // 2]), dim=-1)
 
 
-def run(points, group_sizes):
+def run(points, group_sizes, kv8=False):
     import torch
     import torch.nn.functional as F
 
@@ -101,6 +105,24 @@ def run(points, group_sizes):
                     attn.fuse_decode()
                     pt["fused_decode"] = round(time_fn(fused), 2)
                     attn.unfuse_decode()
+                if kv8:
+                    cache8 = KVCache(1, b, kvh, D, cap, dev, dtype=torch.int8)
+
+                    def fused8():
+                        return attn.forward(y, cache8, start)
+
+                    if kind == "decode":
+                        attn.fuse_decode()
+                        alt, alt8 = [], []
+                        for _ in range(KV8_ROUNDS):
+                            alt.append(round(time_fn(fused), 2))
+                            alt8.append(round(time_fn(fused8), 2))
+                        attn.unfuse_decode()
+                        pt.update({"fused_decode_alt": _median(alt), "fused_decode_kv8": _median(alt8), "fused_decode_alt_runs": alt,
+                                   "fused_decode_kv8_runs": alt8})
+                    else:
+                        pt["fused_qkv_kv8"] = round(time_fn(fused8), 2)
+                    del cache8
                 attn.unfuse_qkv()
                 pt["saved"] = round(pt["unfused"] - pt["fused"], 2)
                 pt["saved_qkv"] = round(pt["unfused"] - pt["fused_qkv"], 2)
@@ -136,7 +158,7 @@ def summarize(trace_dir, bench=None):
             point = grid - POINT_MARK
             continue
         if point is not None:
-            for key in ("qqq_decode_split_kernel", "qqq_decode_combine_kernel", "attn_fwd"):
+            for key in ("qqq_decode_split_kernel", "qqq_kv8_decode_split_kernel", "qqq_decode_combine_kernel", "attn_fwd"):
                 if name.startswith(key) or (key == "attn_fwd" and "attn_fwd" in name):
                     per_point[point][key].append(us)
         if name.startswith("qqq_rope_qkv_kernel"):
@@ -160,13 +182,24 @@ def summarize(trace_dir, bench=None):
     for i, ks in sorted(per_point.items()):
         pt = points[i] if i < len(points) else {}
         row = {"point": i}
-        row.update({k: pt[k] for k in ("shape", "group_size", "kind", "batch", "context", "fused_qkv", "fused_decode") if k in pt})
+        row.update({k: pt[k] for k in ("shape", "group_size", "kind", "batch", "context", "fused_qkv", "fused_decode", "fused_decode_alt",
+                                       "fused_decode_kv8") if k in pt})
         for key, v in ks.items():
             row[key + "_median_us"], row[key + "_calls"] = _median(v), len(v)
         if "qqq_decode_split_kernel" in ks and "context" in pt:
             both = row["qqq_decode_split_kernel_median_us"] + row.get("qqq_decode_combine_kernel_median_us", 0.0)
             kv = 2 * pt["batch"] * pt["kv_heads"] * pt["context"] * D * 2  # K and V, fp16
             row.update({"decode_kernels_us": round(both, 2), "kv_bytes": kv, "kv_fraction_of_8TBps": round(kv / (both * 1e-6) / HBM_BYTES_PER_S, 4)})
+        if "qqq_kv8_decode_split_kernel" in ks and "context" in pt:
+            # the int8 cache: d codes and one f32 scale per (token, KV head), K and V; the combine kernel's calls are both modes' together
+            both = row["qqq_kv8_decode_split_kernel_median_us"] + row.get("qqq_decode_combine_kernel_median_us", 0.0)
+            kv = 2 * pt["batch"] * pt["kv_heads"] * pt["context"] * (D + 4)
+            row.update({"kv8_decode_kernels_us": round(both, 2), "kv8_bytes": kv,
+                        "kv8_fraction_of_8TBps": round(kv / (both * 1e-6) / HBM_BYTES_PER_S, 4)})
+            for key in ("qqq_decode_split_kernel", "qqq_kv8_decode_split_kernel"):  # the spread the two medians are compared against
+                v = sorted(ks.get(key, []))
+                if v:
+                    row[key + "_p10_us"], row[key + "_p90_us"] = round(v[len(v) // 10], 2), round(v[(9 * len(v)) // 10], 2)
         decode.append(row)
     return {"unit": "kernel time from rocprofv3 --kernel-trace (median over calls)", "kernels": rows, "points": decode}
 
@@ -175,6 +208,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", default="decode,prefill")
     ap.add_argument("--group-sizes", default="-1,128")
+    ap.add_argument("--kv8", action="store_true", help="also time the int8 KV cache (fused_decode_kv8 / fused_qkv_kv8)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--summarize", default=None, metavar="TRACE_DIR")
     ap.add_argument("--bench", default=None, metavar="FILE", help="--summarize: the JSON output of the traced run, to label the points")
@@ -182,7 +216,7 @@ def main():
     if a.summarize:
         res = summarize(a.summarize, a.bench)
     else:
-        res = run(a.points.split(","), [int(v) for v in a.group_sizes.split(",")])
+        res = run(a.points.split(","), [int(v) for v in a.group_sizes.split(",")], kv8=a.kv8)
     s = json.dumps(res)
     print(s)
     if a.out:
