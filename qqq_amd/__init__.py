@@ -13,11 +13,16 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     rope_qkv(q, k, v, cos, sin, pos, k_cache, v_cache)                              # RoPE on q/k + static KV-cache write, one launch
     decode_attention(q_out, k_cache, v_cache, pos, scale)                           # split-K decode attention over the cache, output int8-quantised
     rope_qkv_kv8(..., k_cache, v_cache, k_scale, v_scale) / decode_attention_kv8(...)  # the same two over an int8 KV cache (KVCache(dtype=torch.int8))
+    rope_qkv_paged(..., pos, slots, k_pool, v_pool) / decode_attention_paged(q_out, k_pool, v_pool, block_table, pos, scale)  # the same two
+    rope_qkv_paged_kv8(...) / decode_attention_paged_kv8(...)                       # over block pools (fp16 / int8) through slots and a block table
     KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer                            # attention and the whole layer; qqq_amd/attention.py
+    PagedKVCache, PagedStep                                                        # block pools + host-side allocator; qqq_amd/paged.py
 """
 from .ops import (  # noqa: F401
     decode_attention,
     decode_attention_kv8,
+    decode_attention_paged,
+    decode_attention_paged_kv8,
     dynamic_quant,
     expand_int8,
     marlin_qqq_gemm,
@@ -30,12 +35,16 @@ from .ops import (  # noqa: F401
     rmsnorm_quant,
     rope_qkv,
     rope_qkv_kv8,
+    rope_qkv_paged,
+    rope_qkv_paged_kv8,
     silu_mul_quant,
 )
 from .qlinear import QuantLinear, fuse_quant_linears  # noqa: F401
 from .blocks import QuantLlamaMLP, QuantRMSNorm  # noqa: F401
 from .attention import KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer  # noqa: F401
+from .paged import PagedKVCache, PagedStep  # noqa: F401
 
 __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_int8", "mul", "marlin_qqq_gemm", "dynamic_quant", "quantlinear_forward",
            "rmsnorm_quant", "silu_mul_quant", "QuantLinear", "fuse_quant_linears", "QuantRMSNorm", "QuantLlamaMLP",
-           "rope_qkv", "decode_attention", "rope_qkv_kv8", "decode_attention_kv8", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer"]
+           "rope_qkv", "decode_attention", "rope_qkv_kv8", "decode_attention_kv8", "rope_qkv_paged",
+           "decode_attention_paged", "rope_qkv_paged_kv8", "decode_attention_paged_kv8", "PagedKVCache", "PagedStep", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer"]

@@ -77,6 +77,17 @@ def lib():
     L.qqq_rope_qkv_kv8.restype = ci
     L.qqq_decode_attn_kv8.argtypes = [vp, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, ci, ci, ci, ci, ci, ci, ci, vp]
     L.qqq_decode_attn_kv8.restype = ci
+    # include/qqq_amd_paged.h
+    L.qqq_rope_qkv_paged.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+    L.qqq_rope_qkv_paged.restype = ci
+    L.qqq_rope_qkv_paged_kv8.argtypes = [vp, ci, vp, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp]
+    L.qqq_rope_qkv_paged_kv8.restype = ci
+    L.qqq_decode_attn_paged.argtypes = [vp, vp, vp, vp, ci, vp, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, ci, ci, ci, ci, ci, ci, ci,
+                                        ci, vp]
+    L.qqq_decode_attn_paged.restype = ci
+    L.qqq_decode_attn_paged_kv8.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, ci, ci, ci, ci,
+                                            ci, ci, ci, ci, vp]
+    L.qqq_decode_attn_paged_kv8.restype = ci
     L.qqq_amd_abi_version.restype = ci
     L.qqq_amd_last_error.restype = ctypes.c_char_p
     if L.qqq_amd_abi_version() != ABI_VERSION:

@@ -4,12 +4,19 @@ QuantizedLlamaAttention / QuantizedQwen2Attention and Quantized{Llama,Qwen2}Deco
     rope_tables       cos / sin tables [length, head_dim] as transformers' rotary embedding computes them (rope_type "default", "llama3")
     KVCache           static fp16 K / V per layer, [b, kvh, capacity, head_dim], allocated once: no history copy per step; opt-in
                       dtype=torch.int8: every head row as int8 codes and one f32 scale (rope_qkv_kv8 / decode_attention_kv8)
+    PagedKVCache      (qqq_amd/paged.py) block pools [num_blocks, kvh, block_size, head_dim] with a host-side block allocator, fp16 or
+                      int8: sequences of different lengths in one packed batch, blocks reused when a sequence finishes
     QuantLlamaAttention      q/k/v GEMMs on the int8 input of QuantRMSNorm -> rope_qkv (RoPE on q and k, k / v into the cache, one launch)
                              -> scaled_dot_product_attention -> dynamic_quant -> o_proj;  opt-in fuse_decode(): one-token steps take
                              decode_attention (split-K over the cache, output int8-quantised) in place of the last two
     QuantLlamaDecoderLayer   input_layernorm, self_attn, post_attention_layernorm (residual add fused), mlp, final residual add
 
 The attention core is torch's scaled_dot_product_attention, as in the reference, unless fuse_decode() is on and the step has one token.
+
+Paged cache: forward_int8(xq, s1, cache, step) with a PagedKVCache takes a PagedStep (cache.step(seq_ids, counts)) in place of the start
+position and xq [m, hidden] with the sequences' tokens packed in order.  rope_qkv_paged(_kv8) writes all m tokens in one launch; a step of
+one token per sequence runs decode_attention_paged(_kv8) through the step's block table, whatever fuse_decode() says; any other step runs
+scaled_dot_product_attention per sequence over PagedKVCache.gather (a contiguous copy; there is no paged prefill kernel).
 Parameter and buffer names are the reference's, so the layers' state-dicts load unchanged; the rope tables, the fused q|k|v copy of
 fuse_qkv() and the fuse_decode() flag are not part of them.
 """
@@ -24,6 +31,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .blocks import QuantLlamaMLP, QuantRMSNorm
+from .paged import PagedKVCache, PagedStep
 from .qlinear import QuantLinear, fuse_quant_linears
 
 
@@ -65,8 +73,8 @@ def rope_tables(inv_freq: torch.Tensor, attention_scaling: float, length: int, d
 
 class KVCache:
     """Static key / value cache of `num_layers` layers: k[layer], v[layer] of shape [batch, num_kv_heads, capacity, head_dim], allocated
-    (zeroed) once, written in place by rope_qkv at each token's position.  Every batch row is at the same position (no per-row lengths, no
-    paging).
+    (zeroed) once, written in place by rope_qkv at each token's position.  In a KVCache every batch row is at the same position (no
+    per-row lengths, no paging: that is PagedKVCache, qqq_amd/paged.py).
 
     dtype=torch.float16 (default): fp16 K and V, 4 * num_layers * batch * num_kv_heads * capacity * head_dim bytes.
     dtype=torch.int8: every head row is dynamic_quant of that fp16 row -- int8 codes in k / v plus one f32 scale per row in k_scale[layer],
@@ -120,6 +128,7 @@ class QuantLlamaAttention(nn.Module):
 
     forward_int8(xq, s1, cache, start): (xq int8 [b*s, hidden], s1 f32 [b*s, 1]) as QuantRMSNorm returns them, tokens at positions
     start ... start+s-1 (the same for every batch row) -> fp16 [b*s, hidden].  forward(x, cache, start) quantises its fp16 input first.
+    With a PagedKVCache `start` is a PagedStep and xq [m, hidden] holds the sequences' tokens packed in order (see the module docstring).
     Llama: qkv_bias = o_bias = config.attention_bias;  Qwen2: qkv_bias=True, o_bias=False."""
 
     def __init__(self, hidden: int, num_heads: int, num_kv_heads: int, group_size: int, head_dim: Optional[int] = None,
@@ -218,6 +227,11 @@ class QuantLlamaAttention(nn.Module):
         else:
             kc = cache.k[self.layer_idx][:, :, :start + s]
             vc = cache.v[self.layer_idx][:, :, :start + s]
+        return self._sdpa(q_out, kc, vc, start)
+
+    def _sdpa(self, q_out: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor, start: int) -> torch.Tensor:
+        """q_out [b, h, s, d] at positions start ... start+s-1 over keys 0 ... start+s-1 (kc, vc [b, kvh, start+s, d]) -> [b, s, h*d]"""
+        b, h, s, d = q_out.shape
         mask = None
         if s > 1 and start > 0:
             mask = torch.ones((s, start + s), dtype=torch.bool, device=q_out.device).tril(diagonal=start)
@@ -225,7 +239,36 @@ class QuantLlamaAttention(nn.Module):
                                            enable_gqa=h != self.num_key_value_heads)
         return o.transpose(1, 2).reshape(b, s, h * d)
 
+    def _forward_paged(self, xq: torch.Tensor, s1: torch.Tensor, cache: PagedKVCache, step: PagedStep) -> torch.Tensor:
+        if not isinstance(step, PagedStep):
+            raise RuntimeError("forward_int8: a PagedKVCache takes the PagedStep of cache.step(seq_ids, counts) in place of a start position")
+        m = xq.shape[0]
+        if xq.dim() != 2 or m != sum(step.counts):
+            raise RuntimeError(f"forward_int8: xq must be [m, hidden] with the step's m = {sum(step.counts)} tokens packed in order")
+        if not self._decode_supported():
+            raise NotImplementedError(f"a paged KV cache needs head_dim 64 or 128, at most 8 query heads per KV head and h * head_dim <= "
+                                      f"16384 (h={self.num_heads}, kvh={self.num_key_value_heads}, head_dim={self.head_dim})")
+        # the tables grow in powers of two with the longest sequence, not with the pool (which may hold millions of keys)
+        cos, sin = self.rope_tables(min(cache.capacity, max(1024, 1 << (step.max_len - 1).bit_length())))
+        q, k, v = self.project_qkv(xq, s1)
+        li = self.layer_idx
+        pools = (cache.k[li], cache.v[li]) + ((cache.k_scale[li], cache.v_scale[li]) if cache.quantized else ())
+        q_out = (ops.rope_qkv_paged_kv8 if cache.quantized else ops.rope_qkv_paged)(q, k, v, cos, sin, step.pos, step.slots, *pools)
+        if step.decode:  # one token per sequence: the decode kernel through the block table, whatever fuse_decode() says
+            decode = ops.decode_attention_paged_kv8 if cache.quantized else ops.decode_attention_paged
+            aq, a1 = decode(q_out, *pools, step.block_table, step.last_pos, self.scaling, max_len=step.max_len)
+            return self.o_proj.forward_int8(aq, a1)
+        outs, t = [], 0
+        for sid, c, start in zip(step.seq_ids, step.counts, step.starts):  # prefill / chunks: SDPA over a gathered copy, per sequence
+            kc, vc = cache.gather(li, sid, start + c)
+            outs.append(self._sdpa(q_out[t:t + c].transpose(0, 1)[None], kc, vc, start)[0])
+            t += c
+        aq, a1 = ops.dynamic_quant(torch.cat(outs) if len(outs) > 1 else outs[0])
+        return self.o_proj.forward_int8(aq.reshape(m, -1), a1.reshape(m, 1))
+
     def forward_int8(self, xq: torch.Tensor, s1: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
+        if isinstance(cache, PagedKVCache):  # `start` is the PagedStep of this forward pass
+            return self._forward_paged(xq, s1, cache, start)
         m = xq.shape[0]
         b = cache.batch
         if xq.dim() != 2 or m % b:
@@ -272,7 +315,8 @@ class QuantLlamaDecoderLayer(nn.Module):
     """Quantized{Llama,Qwen2}DecoderLayer: transformers' layer output
         h = hidden + self_attn(input_layernorm(hidden));  out = h + mlp(post_attention_layernorm(h))
     with every GEMM input produced already int8-quantised (QuantRMSNorm, silu_mul_quant) and the residual add of the second norm fused
-    into it.  forward(hidden, cache, start): hidden fp16 [b, s, hidden] or [b*s, hidden], tokens at positions start ... start+s-1."""
+    into it.  forward(hidden, cache, start): hidden fp16 [b, s, hidden] or [b*s, hidden], tokens at positions start ... start+s-1; with a
+    PagedKVCache, forward(hidden, cache, step): hidden [m, hidden] packed as the PagedStep says."""
 
     def __init__(self, hidden: int, num_heads: int, num_kv_heads: int, intermediate: int, group_size: int, head_dim: Optional[int] = None,
                  qkv_bias: bool = False, o_bias: bool = False, rms_norm_eps: float = 1e-6, rope_theta: float = 10000.0,
@@ -325,4 +369,4 @@ class QuantLlamaDecoderLayer(nn.Module):
         return (a + self.mlp.forward_int8(mq, ms)).reshape(hidden.shape)
 
 
-__all__ = ["KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer", "rope_inv_freq", "rope_tables"]
+__all__ = ["KVCache", "PagedKVCache", "PagedStep", "QuantLlamaAttention", "QuantLlamaDecoderLayer", "rope_inv_freq", "rope_tables"]

@@ -31,6 +31,7 @@
 //   qqq_small.hip.h    split-K reduce, dynamic quantiser, int4 packer / unpacker, int8 expander
 //   qqq_act.hip.h, qqq_attn.hip.h, qqq_decode.hip.h   the decoder block's fused quantisers, RoPE + KV-cache write, split-K decode attention
 //   qqq_kv8.hip.h      the int8 KV cache: the quantising RoPE / cache write and the decode split kernel that reads it
+//   qqq_paged.hip.h    the block-table (paged) KV cache, fp16 and int8: the cache writes by slot and the decode split kernels through a block table
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -63,6 +64,8 @@
 #include "../../include/qqq_amd_decode.h"
 #include "qqq_kv8.hip.h"
 #include "../../include/qqq_amd_kv8.h"
+#include "qqq_paged.hip.h"
+#include "../../include/qqq_amd_paged.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -741,6 +744,169 @@ extern "C" int qqq_decode_attn_kv8(const void* q, const void* k_cache, const voi
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_kv8_decode_split_kernel launch");
   return decode_combine_launch(b, st, wo, wml, pp, limit, o_fp16, xq, s1, h, d, chunk, splits);
+}
+
+// ---- the block-table (paged) KV cache (include/qqq_amd_paged.h; kernels in qqq_paged.hip.h): the four launches above with a slot per
+// token / a block table per row in place of the contiguous caches' (row, position) addresses.  One body per pair; `name` is the entry
+// point's, kv8 selects the int8 pool with its scales.
+static int paged_log2_block(int block_size) {  // log2 of a power of two in [16, 256], -1 otherwise
+  for (int l = 4; l <= 8; ++l)
+    if (block_size == (1 << l)) return l;
+  return -1;
+}
+
+static int rope_qkv_paged(const char* name, bool kv8, const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v,
+                          const void* cos, const void* sin, int table_len, const void* pos, const void* slots, void* q_out, void* k_pool,
+                          void* v_pool, void* k_scale, void* v_scale, int m, int h, int kvh, int d, int num_blocks, int block_size, int dev,
+                          void* stream) {
+  g_err[0] = 0;
+  if (m < 0 || h < 0 || kvh < 0 || d < 0 || num_blocks < 0 || block_size < 0 || table_len < 0) {
+    snprintf(g_err, sizeof(g_err), "%s: negative size (m=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_len=%d)", name, m, h, kvh, d,
+             num_blocks, block_size, table_len);
+    return QQQ_ERR_ARG;
+  }
+  if (m == 0) return QQQ_OK;
+  const int lbs = paged_log2_block(block_size);
+  if (h < 1 || kvh < 1 || h % kvh != 0 || (d != 64 && d != 128) || (long long)(h + 2LL * kvh) * d > (1LL << 20) || lbs < 0 ||
+      num_blocks < 1 || (long long)num_blocks * block_size > 0x7fffffffLL) {
+    snprintf(g_err, sizeof(g_err), "%s: bad shape m=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d (need h %% kvh == 0, d 64 or 128, "
+             "(h + 2 kvh) d <= 2^20, block_size a power of two in [16, 256], num_blocks >= 1, num_blocks * block_size < 2^31)", name, m, h,
+             kvh, d, num_blocks, block_size);
+    return QQQ_ERR_ARG;
+  }
+  if (ld_q < h * d || ld_k < kvh * d || ld_v < kvh * d || ld_q % 8 || ld_k % 8 || ld_v % 8) {
+    snprintf(g_err, sizeof(g_err), "%s: bad row strides ld_q=%d ld_k=%d ld_v=%d (need multiples of 8, >= h*d=%d / kvh*d=%d)", name, ld_q,
+             ld_k, ld_v, h * d, kvh * d);
+    return QQQ_ERR_ARG;
+  }
+  if (!q || !k || !v || !cos || !sin || !pos || !slots || !q_out || !k_pool || !v_pool || misaligned(q, 16) || misaligned(k, 16) ||
+      misaligned(v, 16) || misaligned(cos, 16) || misaligned(sin, 16) || misaligned(pos, 8) || misaligned(slots, 8) ||
+      misaligned(q_out, 16) || misaligned(k_pool, 16) || misaligned(v_pool, 16) ||
+      (kv8 && (!k_scale || !v_scale || misaligned(k_scale, 4) || misaligned(v_scale, 4)))) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (every pointer must be non-NULL; fp16 tensors and the pools 16-byte, pos / slots "
+             "8-byte, the scales 4-byte aligned)", name);
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  const int items = (h + 2 * kvh) * (d / 16);
+  const dim3 grid(m, (items + ROPE_NT - 1) / ROPE_NT);
+  const long long limit = table_len, nslots = (long long)num_blocks * block_size;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const _Float16 *qp = static_cast<const _Float16*>(q), *kp = static_cast<const _Float16*>(k), *vp = static_cast<const _Float16*>(v);
+  const _Float16 *cp = static_cast<const _Float16*>(cos), *sp = static_cast<const _Float16*>(sin);
+  const long long *pp = static_cast<const long long*>(pos), *slp = static_cast<const long long*>(slots);
+  if (kv8)
+    hipLaunchKernelGGL((qqq_paged_kv8_rope_qkv_kernel<ROPE_NT>), grid, dim3(ROPE_NT), 0, st, qp, ld_q, kp, ld_k, vp, ld_v, cp, sp, pp, limit,
+                       slp, nslots, static_cast<_Float16*>(q_out), static_cast<int8_t*>(k_pool), static_cast<int8_t*>(v_pool),
+                       static_cast<float*>(k_scale), static_cast<float*>(v_scale), h, kvh, d, lbs);
+  else
+    hipLaunchKernelGGL((qqq_paged_rope_qkv_kernel<ROPE_NT>), grid, dim3(ROPE_NT), 0, st, qp, ld_q, kp, ld_k, vp, ld_v, cp, sp, pp, limit, slp,
+                       nslots, static_cast<_Float16*>(q_out), static_cast<_Float16*>(k_pool), static_cast<_Float16*>(v_pool), h, kvh, d, lbs);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, kv8 ? "qqq_paged_kv8_rope_qkv_kernel launch" : "qqq_paged_rope_qkv_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_rope_qkv_paged(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, const void* cos, const void* sin,
+                                  int table_len, const void* pos, const void* slots, void* q_out, void* k_pool, void* v_pool, int m, int h,
+                                  int kvh, int d, int num_blocks, int block_size, int dev, void* stream) {
+  return rope_qkv_paged("qqq_rope_qkv_paged", false, q, ld_q, k, ld_k, v, ld_v, cos, sin, table_len, pos, slots, q_out, k_pool, v_pool,
+                        nullptr, nullptr, m, h, kvh, d, num_blocks, block_size, dev, stream);
+}
+
+extern "C" int qqq_rope_qkv_paged_kv8(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, const void* cos,
+                                      const void* sin, int table_len, const void* pos, const void* slots, void* q_out, void* k_pool,
+                                      void* v_pool, void* k_scale, void* v_scale, int m, int h, int kvh, int d, int num_blocks,
+                                      int block_size, int dev, void* stream) {
+  return rope_qkv_paged("qqq_rope_qkv_paged_kv8", true, q, ld_q, k, ld_k, v, ld_v, cos, sin, table_len, pos, slots, q_out, k_pool, v_pool,
+                        k_scale, v_scale, m, h, kvh, d, num_blocks, block_size, dev, stream);
+}
+
+static int decode_attn_paged(const char* name, bool kv8, const void* q, const void* k_pool, const void* v_pool, const void* k_scale,
+                             const void* v_scale, const void* block_table, int table_stride, const void* pos, float scale, void* o_fp16,
+                             void* xq, void* s1, void* workspace, size_t workspace_bytes, int b, int h, int kvh, int d, int num_blocks,
+                             int block_size, int max_len, int dev, void* stream) {
+  g_err[0] = 0;
+  if (b < 0 || h < 0 || kvh < 0 || d < 0 || num_blocks < 0 || block_size < 0 || table_stride < 0 || max_len < 0) {
+    snprintf(g_err, sizeof(g_err), "%s: negative size (b=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_stride=%d max_len=%d)", name,
+             b, h, kvh, d, num_blocks, block_size, table_stride, max_len);
+    return QQQ_ERR_ARG;
+  }
+  if (b == 0) return QQQ_OK;
+  const int lbs = paged_log2_block(block_size);
+  if (decode_shape_error(b, h, kvh, d, max_len) || lbs < 0 || num_blocks < 1 || (long long)num_blocks * block_size > 0x7fffffffLL ||
+      table_stride < 1 || max_len > (long long)table_stride * block_size) {
+    snprintf(g_err, sizeof(g_err), "%s: bad shape b=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_stride=%d max_len=%d (need "
+             "h %% kvh == 0, h / kvh <= %d, d 64 or 128, h*d <= 16384, b <= 65535, block_size a power of two in [16, 256], num_blocks >= 1, "
+             "num_blocks * block_size < 2^31, 1 <= max_len <= table_stride * block_size)", name, b, h, kvh, d, num_blocks, block_size,
+             table_stride, max_len, DEC_GMAX);
+    return QQQ_ERR_ARG;
+  }
+  if (!o_fp16 && !xq && !s1) {
+    snprintf(g_err, sizeof(g_err), "%s: no output (o_fp16 and xq / s1 are all NULL)", name);
+    return QQQ_ERR_ARG;
+  }
+  if (!q || !k_pool || !v_pool || !block_table || !pos || !workspace || (!xq) != (!s1) || misaligned(q, 16) || misaligned(k_pool, 16) ||
+      misaligned(v_pool, 16) || misaligned(block_table, 4) || misaligned(pos, 8) || misaligned(workspace, 16) ||
+      (o_fp16 && misaligned(o_fp16, 16)) || (xq && misaligned(xq, 8)) || (s1 && misaligned(s1, 4)) ||
+      (kv8 && (!k_scale || !v_scale || misaligned(k_scale, 4) || misaligned(v_scale, 4)))) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (q / pools / scales / block_table / pos / workspace must be non-NULL, xq and s1 both "
+             "given or both NULL; q, pools, o_fp16, workspace 16-byte, pos / xq 8-byte, block_table, s1 and the scales 4-byte aligned)", name);
+    return QQQ_ERR_ARG;
+  }
+  const size_t need = qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len);
+  if (workspace_bytes < need) {
+    snprintf(g_err, sizeof(g_err), "%s: workspace of %zu bytes, need %zu", name, workspace_bytes, need);
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int splits, chunk;
+  decode_split_plan(dev, b, kvh, max_len, &splits, &chunk);
+  float* wo = static_cast<float*>(workspace);
+  float* wml = wo + (size_t)b * h * splits * d;
+  const long long* pp = static_cast<const long long*>(pos);
+  const long long limit = max_len;  // <= table_stride * block_size
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const _Float16* qp = static_cast<const _Float16*>(q);
+  const int* tp = static_cast<const int*>(block_table);
+  const dim3 grid(splits, kvh, b), block(DEC_WAVES * 64);
+  if (kv8) {
+    const int8_t *kp = static_cast<const int8_t*>(k_pool), *vp = static_cast<const int8_t*>(v_pool);
+    const float *ksp = static_cast<const float*>(k_scale), *vsp = static_cast<const float*>(v_scale);
+    if (d == 64)
+      hipLaunchKernelGGL((qqq_paged_kv8_decode_split_kernel<64>), grid, block, 0, st, qp, kp, vp, ksp, vsp, tp, table_stride, pp, limit,
+                         scale_log2, wo, wml, h, kvh, num_blocks, lbs, chunk, splits);
+    else
+      hipLaunchKernelGGL((qqq_paged_kv8_decode_split_kernel<128>), grid, block, 0, st, qp, kp, vp, ksp, vsp, tp, table_stride, pp, limit,
+                         scale_log2, wo, wml, h, kvh, num_blocks, lbs, chunk, splits);
+  } else {
+    const _Float16 *kp = static_cast<const _Float16*>(k_pool), *vp = static_cast<const _Float16*>(v_pool);
+    if (d == 64)
+      hipLaunchKernelGGL((qqq_paged_decode_split_kernel<64>), grid, block, 0, st, qp, kp, vp, tp, table_stride, pp, limit, scale_log2, wo,
+                         wml, h, kvh, num_blocks, lbs, chunk, splits);
+    else
+      hipLaunchKernelGGL((qqq_paged_decode_split_kernel<128>), grid, block, 0, st, qp, kp, vp, tp, table_stride, pp, limit, scale_log2, wo,
+                         wml, h, kvh, num_blocks, lbs, chunk, splits);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, kv8 ? "qqq_paged_kv8_decode_split_kernel launch" : "qqq_paged_decode_split_kernel launch");
+  return decode_combine_launch(b, st, wo, wml, pp, limit, o_fp16, xq, s1, h, d, chunk, splits);
+}
+
+extern "C" int qqq_decode_attn_paged(const void* q, const void* k_pool, const void* v_pool, const void* block_table, int table_stride,
+                                     const void* pos, float scale, void* o_fp16, void* xq, void* s1, void* workspace, size_t workspace_bytes,
+                                     int b, int h, int kvh, int d, int num_blocks, int block_size, int max_len, int dev, void* stream) {
+  return decode_attn_paged("qqq_decode_attn_paged", false, q, k_pool, v_pool, nullptr, nullptr, block_table, table_stride, pos, scale, o_fp16,
+                           xq, s1, workspace, workspace_bytes, b, h, kvh, d, num_blocks, block_size, max_len, dev, stream);
+}
+
+extern "C" int qqq_decode_attn_paged_kv8(const void* q, const void* k_pool, const void* v_pool, const void* k_scale, const void* v_scale,
+                                         const void* block_table, int table_stride, const void* pos, float scale, void* o_fp16, void* xq,
+                                         void* s1, void* workspace, size_t workspace_bytes, int b, int h, int kvh, int d, int num_blocks,
+                                         int block_size, int max_len, int dev, void* stream) {
+  return decode_attn_paged("qqq_decode_attn_paged_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, pos, scale,
+                           o_fp16, xq, s1, workspace, workspace_bytes, b, h, kvh, d, num_blocks, block_size, max_len, dev, stream);
 }
 
 extern "C" int qqq_quantlinear_forward(const void* x, void* xq, void* s1, const void* B, void* C, void* D,

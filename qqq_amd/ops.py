@@ -755,3 +755,239 @@ def decode_attention_kv8(q_out: torch.Tensor, k_cache: torch.Tensor, v_cache: to
     else:
         out = _decode_attention_kv8_impl(q_out, k_cache, v_cache, k_scale, v_scale, pos, scale, max_len, return_fp16)
     return out if return_fp16 else out[:2]
+
+
+# ---- the block-table (paged) KV cache (include/qqq_amd_paged.h): the four ops above over pools of blocks [num_blocks, kvh, block_size, d]
+# that any sequence may own -- a slot per token for the write, a block table per row for the decode attention.
+
+def _paged_check_pools(name, k_pool, v_pool, k_scale=None, v_scale=None):
+    # (num_blocks, kvh, block_size, d); an int8 pool comes with its scales
+    kv8 = k_scale is not None
+    want = torch.int8 if kv8 else torch.float16
+    if k_pool.dtype != want or v_pool.dtype != want or (kv8 and any(t.dtype != torch.float32 for t in (k_scale, v_scale))):
+        raise RuntimeError(f"{name}: the pools must be {'int8 and their scales f32' if kv8 else 'fp16'}")
+    if k_pool.dim() != 4:
+        raise RuntimeError(f"{name}: k_pool must be [num_blocks, kvh, block_size, d]")
+    if v_pool.shape != k_pool.shape or (kv8 and (k_scale.shape != k_pool.shape[:3] or v_scale.shape != k_pool.shape[:3])):
+        raise RuntimeError(f"{name}: v_pool must have k_pool's shape [num_blocks, kvh, block_size, d]" +
+                           (" and the scales its first three dimensions" if kv8 else ""))
+    for nm, t in (("k_pool", k_pool), ("v_pool", v_pool)) + ((("k_scale", k_scale), ("v_scale", v_scale)) if kv8 else ()):
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name}: {nm} must be contiguous")
+    return tuple(k_pool.shape)
+
+
+def _rope_qkv_paged_shapes(name, q, k, v, cos, pos, slots, k_pool):
+    # (m, h, kvh, d, num_blocks, block_size) from the tensors' shapes; raises for anything the kernel could not take
+    if k_pool.dim() != 4:
+        raise RuntimeError(f"{name}: k_pool must be [num_blocks, kvh, block_size, d]")
+    nb, kvh, bs, d = k_pool.shape
+    m = pos.numel()
+    if slots.numel() != m:
+        raise RuntimeError(f"{name}: pos holds {m} positions and slots {slots.numel()} slots")
+    if m == 0 or d == 0:
+        return m, 0, kvh, d, nb, bs
+    if q.numel() % (m * d) or k.numel() != m * kvh * d or v.numel() != m * kvh * d:
+        raise RuntimeError(f"{name}: q {tuple(q.shape)}, k {tuple(k.shape)}, v {tuple(v.shape)} must hold {m} token rows of h*{d}, "
+                           f"{kvh}*{d}, {kvh}*{d} elements")
+    if cos.dim() != 2 or cos.shape[1] != d:
+        raise RuntimeError(f"{name}: cos / sin must be fp16 [table_len, {d}]")
+    return m, q.numel() // (m * d), kvh, d, nb, bs
+
+
+def _rope_qkv_paged_impl(q, k, v, cos, sin, pos, slots, k_pool, v_pool, k_scale=None, v_scale=None):
+    kv8 = k_scale is not None
+    name = "rope_qkv_paged_kv8" if kv8 else "rope_qkv_paged"
+    ts = (q, k, v, cos, sin, pos, slots, k_pool, v_pool) + ((k_scale, v_scale) if kv8 else ())
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError(f"{name}: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != q.device for t in ts):
+        raise RuntimeError(f"{name}: every tensor must be on the same GPU")
+    if any(t.dtype != torch.float16 for t in (q, k, v, cos, sin)) or pos.dtype != torch.int64 or slots.dtype != torch.int64:
+        raise RuntimeError(f"{name}: q, k, v, cos and sin must be fp16, pos and slots int64")
+    _paged_check_pools(name, k_pool, v_pool, k_scale, v_scale)
+    m, h, kvh, d, nb, bs = _rope_qkv_paged_shapes(name, q, k, v, cos, pos, slots, k_pool)
+    if sin.shape != cos.shape:
+        raise RuntimeError(f"{name}: sin must have cos's shape")
+    q_out = torch.empty((m, h, d), dtype=torch.float16, device=q.device)
+    if q_out.numel() == 0:
+        return q_out
+    (q2, ld_q), (k2, ld_k), (v2, ld_v) = _rows(q, h * d), _rows(k, kvh * d), _rows(v, kvh * d)
+    cos, sin, pos, slots = cos.contiguous(), sin.contiguous(), pos.contiguous(), slots.contiguous()
+    L = _lib.lib()
+    head = (_ptr(q2), ld_q, _ptr(k2), ld_k, _ptr(v2), ld_v, _ptr(cos), _ptr(sin), cos.shape[0], _ptr(pos), _ptr(slots), _ptr(q_out),
+            _ptr(k_pool), _ptr(v_pool))
+    tail = (m, h, kvh, d, nb, bs, q.device.index or 0, _stream_for(q))
+    if kv8:
+        err = L.qqq_rope_qkv_paged_kv8(*head, _ptr(k_scale), _ptr(v_scale), *tail)
+    else:
+        err = L.qqq_rope_qkv_paged(*head, *tail)
+    if err:
+        raise RuntimeError(f"qqq_amd: {name} error {err}: {_lib.last_error()}")
+    return q_out
+
+
+@torch.library.custom_op("qqq_amd::rope_qkv_paged", mutates_args=("k_pool", "v_pool"))
+def _rope_qkv_paged_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
+                       slots: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor) -> torch.Tensor:
+    return _rope_qkv_paged_impl(q, k, v, cos, sin, pos, slots, k_pool, v_pool)
+
+
+@_rope_qkv_paged_op.register_fake
+def _(q, k, v, cos, sin, pos, slots, k_pool, v_pool):
+    m, h, _, d, _, _ = _rope_qkv_paged_shapes("rope_qkv_paged", q, k, v, cos, pos, slots, k_pool)
+    return q.new_empty((m, h, d), dtype=torch.float16)
+
+
+def rope_qkv_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
+                   slots: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor) -> torch.Tensor:
+    """rope_qkv into a block pool, one launch for all m tokens of the call (any mix of sequences): q_out and the cached rows are rope_qkv's
+    for the same token and position, bit for bit.
+
+    q, k, v, cos, sin   as for rope_qkv (head_dim 64 or 128);  pos  int64 [m], a position per token
+    slots      int64 [m]: token t's k / v rows go to block slots[t] // block_size at offset slots[t] % block_size
+    k_pool, v_pool   fp16 [num_blocks, kvh, block_size, d] (block_size a power of two in [16, 256]), updated in place
+    Returns q_out fp16 [m, h, d], token-major (for a decode batch the memory of [b, h, 1, d]).  A token whose position is outside
+    [0, table_len) writes nothing; a token whose slot is outside the pool (a padding slot, -1) writes its q_out row only."""
+    ts = (q, k, v, cos, sin, pos, slots, k_pool, v_pool)
+    if _compiling(*ts):
+        return _rope_qkv_paged_op(*ts)
+    return _rope_qkv_paged_impl(*ts)
+
+
+@torch.library.custom_op("qqq_amd::rope_qkv_paged_kv8", mutates_args=("k_pool", "v_pool", "k_scale", "v_scale"))
+def _rope_qkv_paged_kv8_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
+                           slots: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor,
+                           v_scale: torch.Tensor) -> torch.Tensor:
+    return _rope_qkv_paged_impl(q, k, v, cos, sin, pos, slots, k_pool, v_pool, k_scale, v_scale)
+
+
+@_rope_qkv_paged_kv8_op.register_fake
+def _(q, k, v, cos, sin, pos, slots, k_pool, v_pool, k_scale, v_scale):
+    m, h, _, d, _, _ = _rope_qkv_paged_shapes("rope_qkv_paged_kv8", q, k, v, cos, pos, slots, k_pool)
+    return q.new_empty((m, h, d), dtype=torch.float16)
+
+
+def rope_qkv_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor,
+                       slots: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor,
+                       v_scale: torch.Tensor) -> torch.Tensor:
+    """rope_qkv_paged into an int8 pool: every cached row is stored as rope_qkv_kv8 stores it (codes and one f32 scale), bit for bit.
+
+    k_pool, v_pool  int8 [num_blocks, kvh, block_size, d];  k_scale, v_scale  f32 [num_blocks, kvh, block_size]; all four updated in place
+    Everything else, the return value and the padding / out-of-range rules are rope_qkv_paged's."""
+    ts = (q, k, v, cos, sin, pos, slots, k_pool, v_pool, k_scale, v_scale)
+    if _compiling(*ts):
+        return _rope_qkv_paged_kv8_op(*ts)
+    return _rope_qkv_paged_impl(*ts)
+
+
+def _decode_attention_paged_shapes(name, q_out, k_pool, block_table, pos, max_len):
+    # (b, h, kvh, d, num_blocks, block_size, table_stride, max_len) from the tensors' shapes
+    if k_pool.dim() != 4:
+        raise RuntimeError(f"{name}: k_pool must be [num_blocks, kvh, block_size, d]")
+    nb, kvh, bs, d = k_pool.shape
+    if block_table.dim() != 2:
+        raise RuntimeError(f"{name}: block_table must be int32 [b, blocks per row]")
+    b, width = block_table.shape
+    if q_out.dim() == 4 and q_out.shape[2] == 1:
+        q_out = q_out[:, :, 0]
+    if q_out.dim() != 3 or q_out.shape[0] != b or q_out.shape[2] != d:
+        raise RuntimeError(f"{name}: q_out {tuple(q_out.shape)} must be [{b}, h, {d}] or [{b}, h, 1, {d}] (rope_qkv_paged's output of a "
+                           f"decode batch)")
+    if pos.numel() != b:
+        raise RuntimeError(f"{name}: pos holds {pos.numel()} positions, the block table has {b} rows")
+    max_len = width * bs if max_len is None else int(max_len)
+    return b, q_out.shape[1], kvh, d, nb, bs, width, max_len
+
+
+def _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, k_scale=None, v_scale=None):
+    kv8 = k_scale is not None
+    name = "decode_attention_paged_kv8" if kv8 else "decode_attention_paged"
+    ts = (q_out, k_pool, v_pool, block_table, pos) + ((k_scale, v_scale) if kv8 else ())
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError(f"{name}: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != q_out.device for t in ts):
+        raise RuntimeError(f"{name}: every tensor must be on the same GPU")
+    if q_out.dtype != torch.float16 or pos.dtype != torch.int64 or block_table.dtype != torch.int32:
+        raise RuntimeError(f"{name}: q_out must be fp16, pos int64 and block_table int32")
+    _paged_check_pools(name, k_pool, v_pool, k_scale, v_scale)
+    b, h, kvh, d, nb, bs, width, max_len = _decode_attention_paged_shapes(name, q_out, k_pool, block_table, pos, max_len)
+    dev = q_out.device
+    xq = torch.empty((b, h * d), dtype=torch.int8, device=dev)
+    s1 = torch.empty((b, 1), dtype=torch.float32, device=dev)
+    o16 = torch.empty((b, h * d) if return_fp16 else (0,), dtype=torch.float16, device=dev)
+    if b == 0:
+        return xq, s1, o16
+    L = _lib.lib()
+    nbytes = L.qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)  # torch's allocator: also under stream / graph capture
+    q2, pos, table = q_out.contiguous(), pos.contiguous(), block_table.contiguous()
+    tail = (_ptr(table), width, _ptr(pos), float(scale), _ptr(o16), _ptr(xq), _ptr(s1), _ptr(ws), ws.numel(), b, h, kvh, d, nb, bs, max_len,
+            dev.index or 0, _stream_for(q_out))
+    if kv8:
+        err = L.qqq_decode_attn_paged_kv8(_ptr(q2), _ptr(k_pool), _ptr(v_pool), _ptr(k_scale), _ptr(v_scale), *tail)
+    else:
+        err = L.qqq_decode_attn_paged(_ptr(q2), _ptr(k_pool), _ptr(v_pool), *tail)
+    if err:
+        raise RuntimeError(f"qqq_amd: {name} error {err}: {_lib.last_error()}")
+    return xq, s1, o16
+
+
+def _decode_paged_fake(name, q_out, k_pool, block_table, pos, max_len, return_fp16):
+    b, h, _, d = _decode_attention_paged_shapes(name, q_out, k_pool, block_table, pos, max_len)[:4]
+    return (q_out.new_empty((b, h * d), dtype=torch.int8), q_out.new_empty((b, 1), dtype=torch.float32),
+            q_out.new_empty((b, h * d) if return_fp16 else (0,), dtype=torch.float16))
+
+
+@torch.library.custom_op("qqq_amd::decode_attn_paged", mutates_args=())
+def _decode_attn_paged_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, pos: torch.Tensor,
+                          scale: float, max_len: Optional[int], return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16)
+
+
+@_decode_attn_paged_op.register_fake
+def _(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16):
+    return _decode_paged_fake("decode_attention_paged", q_out, k_pool, block_table, pos, max_len, return_fp16)
+
+
+def decode_attention_paged(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, pos: torch.Tensor,
+                           scale: float, max_len: Optional[int] = None, return_fp16: bool = False):
+    """decode_attention over a block pool: (xq int8 [b, h*d], s1 f32 [b, 1]), plus the fp16 output [b, h*d] with `return_fp16` -- bit for bit
+    decode_attention's over a contiguous cache that holds the same rows, for equal b and max_len.
+
+    q_out      fp16 [b, h, d] or [b, h, 1, d]: rope_qkv_paged's output of a decode batch
+    k_pool, v_pool   fp16 [num_blocks, kvh, block_size, d], only read
+    block_table      int32 [b, W] in device memory: key j of row bi lives in block block_table[bi, j // block_size]; only the entries up to
+                     pos[bi] // block_size are read, several rows may name the same blocks, ids are clamped into the pool
+    pos        int64 [b]: row bi attends keys 0 ... pos[bi];  scale  the score scale
+    max_len    the launch is sized for positions below it (default and upper bound: W * block_size); a row whose position is outside
+               [0, max_len) writes nothing"""
+    if _compiling(q_out, k_pool, v_pool, block_table, pos):
+        out = _decode_attn_paged_op(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16)
+    else:
+        out = _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16)
+    return out if return_fp16 else out[:2]
+
+
+@torch.library.custom_op("qqq_amd::decode_attn_paged_kv8", mutates_args=())
+def _decode_attn_paged_kv8_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                              block_table: torch.Tensor, pos: torch.Tensor, scale: float, max_len: Optional[int],
+                              return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, k_scale, v_scale)
+
+
+@_decode_attn_paged_kv8_op.register_fake
+def _(q_out, k_pool, v_pool, k_scale, v_scale, block_table, pos, scale, max_len, return_fp16):
+    return _decode_paged_fake("decode_attention_paged_kv8", q_out, k_pool, block_table, pos, max_len, return_fp16)
+
+
+def decode_attention_paged_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                               block_table: torch.Tensor, pos: torch.Tensor, scale: float, max_len: Optional[int] = None,
+                               return_fp16: bool = False):
+    """decode_attention_paged over an int8 pool (k_pool, v_pool int8 [num_blocks, kvh, block_size, d]; k_scale, v_scale f32 [num_blocks, kvh,
+    block_size]) with decode_attention_kv8's arithmetic, bit for bit."""
+    if _compiling(q_out, k_pool, v_pool, k_scale, v_scale, block_table, pos):
+        out = _decode_attn_paged_kv8_op(q_out, k_pool, v_pool, k_scale, v_scale, block_table, pos, scale, max_len, return_fp16)
+    else:
+        out = _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, k_scale, v_scale)
+    return out if return_fp16 else out[:2]

@@ -1,0 +1,161 @@
+"""The block-table (paged) KV cache: per layer a pool of blocks of `block_size` keys that any sequence may own, a host-side block allocator
+with per-sequence lengths, and the per-step metadata the paged ops read (ops.rope_qkv_paged / decode_attention_paged and their _kv8 forms).
+
+    PagedKVCache   k[layer], v[layer] of shape [num_blocks, num_kv_heads, block_size, head_dim] (fp16 or int8; an int8 pool with
+                   k_scale[layer], v_scale[layer] [num_blocks, num_kv_heads, block_size]); add / free / step / gather
+    PagedStep      what one forward pass over a packed batch of sequences needs, built once on the host and shared by all layers
+
+Sequences arrive and finish at different times, have different lengths, and a finished sequence's blocks serve the next one.  The allocator
+keeps no reference counts: sharing the blocks of a common prompt between rows is a property of the ops (a block table may name any
+block), not of this class.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence
+
+import torch
+
+
+@dataclass
+class PagedStep:
+    """One step of a packed batch: sequence i contributes counts[i] tokens at positions starts[i] ... starts[i] + counts[i] - 1, in order.
+
+    Host fields: seq_ids, counts, starts, max_len (the longest sequence after the step), decode (every count is 1).
+    Device tensors: pos int64 [m] and slots int64 [m] per token (m = sum(counts)); block_table int32 [b, W] (row i: the blocks of
+    sequence i, padded with 0) and last_pos int64 [b] (the position of each sequence's last token) per sequence."""
+    seq_ids: List
+    counts: List[int]
+    starts: List[int]
+    max_len: int
+    decode: bool
+    pos: torch.Tensor
+    slots: torch.Tensor
+    block_table: torch.Tensor
+    last_pos: torch.Tensor
+
+
+class PagedKVCache:
+    """Key / value block pools of `num_layers` layers and the allocator of their blocks (one block id covers all layers).
+
+    dtype=torch.float16 (default): fp16 K and V, 4 * num_layers * num_blocks * num_kv_heads * block_size * head_dim bytes.
+    dtype=torch.int8: every head row is dynamic_quant of that fp16 row, as in KVCache(dtype=torch.int8):
+    2 * num_layers * num_blocks * num_kv_heads * block_size * (head_dim + 4) bytes.  Any other dtype raises.
+    block_size is a power of two in [16, 256]."""
+
+    def __init__(self, num_layers: int, num_blocks: int, num_kv_heads: int, head_dim: int, block_size: int, device=None,
+                 dtype=torch.float16):
+        if dtype not in (torch.float16, torch.int8):
+            raise ValueError(f"PagedKVCache: dtype must be torch.float16 or torch.int8, not {dtype}")
+        if block_size not in (16, 32, 64, 128, 256):
+            raise ValueError(f"PagedKVCache: block_size must be a power of two in [16, 256], not {block_size}")
+        if num_blocks < 1:
+            raise ValueError(f"PagedKVCache: num_blocks must be at least 1, not {num_blocks}")
+        self.num_layers, self.num_blocks, self.num_kv_heads, self.head_dim, self.block_size = (num_layers, num_blocks, num_kv_heads,
+                                                                                               head_dim, block_size)
+        self.dtype, self.device = dtype, device
+        shape = (num_blocks, num_kv_heads, block_size, head_dim)
+        self.k = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(num_layers)]
+        self.v = [torch.zeros(shape, dtype=dtype, device=device) for _ in range(num_layers)]
+        if dtype == torch.int8:
+            self.k_scale = [torch.zeros(shape[:3], dtype=torch.float32, device=device) for _ in range(num_layers)]
+            self.v_scale = [torch.zeros(shape[:3], dtype=torch.float32, device=device) for _ in range(num_layers)]
+        self._free: List[int] = list(range(num_blocks - 1, -1, -1))  # a stack: block 0 goes out first, a freed block is the next one out
+        self._blocks: Dict[object, List[int]] = {}
+        self._len: Dict[object, int] = {}
+
+    @property
+    def quantized(self) -> bool:
+        return self.dtype == torch.int8
+
+    @property
+    def nbytes(self) -> int:
+        rows = self.num_layers * self.num_blocks * self.num_kv_heads * self.block_size
+        return 2 * rows * (self.head_dim + 4) if self.quantized else 4 * rows * self.head_dim
+
+    @property
+    def capacity(self) -> int:
+        """The longest sequence the pool could hold (all blocks to one sequence): what the rope tables are sized for."""
+        return self.num_blocks * self.block_size
+
+    # ---- the allocator (host only)
+
+    @property
+    def free_blocks(self) -> int:
+        return len(self._free)
+
+    def add(self, seq_id) -> None:
+        """Admit an empty sequence; it owns no block until its first step()."""
+        if seq_id in self._blocks:
+            raise KeyError(f"PagedKVCache.add: sequence {seq_id!r} exists")
+        self._blocks[seq_id], self._len[seq_id] = [], 0
+
+    def free(self, seq_id) -> None:
+        """Drop a sequence; its blocks go back to the free list (the last one it took is the first to go out again)."""
+        if seq_id not in self._blocks:
+            raise KeyError(f"PagedKVCache.free: no sequence {seq_id!r}")
+        self._free.extend(self._blocks.pop(seq_id))
+        del self._len[seq_id]
+
+    def length(self, seq_id) -> int:
+        return self._len[seq_id]
+
+    def blocks(self, seq_id) -> List[int]:
+        return list(self._blocks[seq_id])
+
+    def step(self, seq_ids: Sequence, counts: Sequence[int]) -> PagedStep:
+        """Reserve blocks for counts[i] new tokens of sequence seq_ids[i], advance the lengths and return the step's metadata (device
+        tensors built on the host, one copy each).  Raises, and changes nothing, when the pool cannot hold the step."""
+        seq_ids, counts = list(seq_ids), [int(c) for c in counts]
+        if len(seq_ids) != len(counts) or not seq_ids or len(set(seq_ids)) != len(seq_ids):
+            raise ValueError("PagedKVCache.step: seq_ids and counts must be non-empty, of one length, without repeated sequences")
+        if any(c < 1 for c in counts):
+            raise ValueError("PagedKVCache.step: every sequence of a step brings at least one token")
+        for sid in seq_ids:
+            if sid not in self._blocks:
+                raise KeyError(f"PagedKVCache.step: no sequence {sid!r}")
+        bs = self.block_size
+        need = [-(-(self._len[sid] + c) // bs) - len(self._blocks[sid]) for sid, c in zip(seq_ids, counts)]
+        if sum(need) > len(self._free):
+            raise RuntimeError(f"PagedKVCache.step: the pool is exhausted ({sum(need)} blocks needed, {len(self._free)} free)")
+        starts, pos, slots = [], [], []
+        for sid, c, n in zip(seq_ids, counts, need):
+            mine = self._blocks[sid]
+            for _ in range(n):
+                mine.append(self._free.pop())
+            start = self._len[sid]
+            starts.append(start)
+            for p in range(start, start + c):
+                pos.append(p)
+                slots.append(mine[p // bs] * bs + p % bs)
+            self._len[sid] = start + c
+        width = max(len(self._blocks[sid]) for sid in seq_ids)
+        table = [self._blocks[sid] + [0] * (width - len(self._blocks[sid])) for sid in seq_ids]
+        last = [self._len[sid] - 1 for sid in seq_ids]
+        dev = self.device
+        return PagedStep(seq_ids=seq_ids, counts=counts, starts=starts, max_len=max(last) + 1, decode=all(c == 1 for c in counts),
+                         pos=torch.tensor(pos, dtype=torch.int64).to(dev), slots=torch.tensor(slots, dtype=torch.int64).to(dev),
+                         block_table=torch.tensor(table, dtype=torch.int32).to(dev), last_pos=torch.tensor(last, dtype=torch.int64).to(dev))
+
+    # ---- reading a sequence back (plain torch; CPU tensors too)
+
+    def gather(self, layer: int, seq_id, length: Optional[int] = None):
+        """Contiguous fp16 (k, v) [1, num_kv_heads, length, head_dim] of a sequence's first `length` keys (default: all of them).  An int8
+        pool is dequantised as KVCache.dequant does: fp16(float(code) * scale)."""
+        n = self._len[seq_id] if length is None else int(length)
+        if n < 0 or n > self._len[seq_id]:
+            raise ValueError(f"PagedKVCache.gather: length {n} outside the sequence's {self._len[seq_id]} keys")
+        nblk = -(-n // self.block_size)
+        idx = torch.tensor(self._blocks[seq_id][:nblk], dtype=torch.int64, device=self.k[layer].device)
+        out = []
+        for pool, scales in ((self.k[layer], self.k_scale[layer] if self.quantized else None),
+                             (self.v[layer], self.v_scale[layer] if self.quantized else None)):
+            rows = pool.index_select(0, idx).transpose(0, 1).reshape(self.num_kv_heads, nblk * self.block_size, self.head_dim)[:, :n]
+            if scales is not None:
+                sc = scales.index_select(0, idx).transpose(0, 1).reshape(self.num_kv_heads, nblk * self.block_size)[:, :n]
+                rows = (rows.float() * sc[:, :, None]).half()
+            out.append(rows[None].contiguous())
+        return tuple(out)
+
+
+__all__ = ["PagedKVCache", "PagedStep"]

@@ -14,6 +14,10 @@ KV cache.  Both paths start from the fp16 output of input_layernorm and end with
     fused_decode_kv8  (--kv8, decode points) the same with KVCache(dtype=torch.int8): rope_qkv_kv8 + decode_attention_kv8.  It is timed
                 alternately with fused_decode, KV8_ROUNDS times each in the same process; both lists are kept (`*_runs`) and the medians
                 reported (`fused_decode_alt`, `fused_decode_kv8`).  Prefill points get `fused_qkv_kv8` (SDPA over the dequantised cache).
+    paged       (--paged [--block-size N], decode points) the same module over a PagedKVCache whose block tables are a random permutation of
+                the pool: rope_qkv_paged + decode_attention_paged.  Contiguous (fused_decode) and paged are timed alternately, PAGED_ROUNDS
+                times each in one process -- with --kv8 the two int8 paths join the rotation -- and every list is kept under `paged_runs`,
+                the medians under `paged`.
 
 Points: decode (s = 1) at b in {1, 16} with a context of {1024, 4096} tokens (the new token included), and b = 1 at 16384; prefill of s in
 {128, 1024, 4096} tokens at b = 1 from position 0.  Before each point one dynamic_quant of POINT_MARK + i rows is launched: its grid marks
@@ -24,7 +28,9 @@ where point i starts in a kernel trace.
                                                                           qqq_rope_qkv_kernel times and HBM fractions, and per decode point
                                                                           (labelled from the run's JSON output FILE) the median times of
                                                                           the two decode-attention kernels, their K/V bytes as a fraction
-                                                                          of 8 TB/s, and SDPA's attn_fwd
+                                                                          of 8 TB/s, and SDPA's attn_fwd; for a --paged run each split
+                                                                          kernel's median per alternation and the paged kernels' excess
+                                                                          over the contiguous ones against the latter's spread
 """
 import argparse
 import collections
@@ -46,6 +52,9 @@ PREFILL = (128, 1024, 4096)
 HBM_BYTES_PER_S = 8e12
 ROPE_NT = 128  # qqq_w4a8.hip: ROPE_NT
 KV8_ROUNDS = 3  # --kv8: alternations of fused_decode / fused_decode_kv8 at a decode point
+PAGED_ROUNDS = 5  # --paged: alternations of the contiguous and the paged paths at a decode point
+SPLIT_KERNELS = ("qqq_decode_split_kernel", "qqq_kv8_decode_split_kernel", "qqq_paged_decode_split_kernel",
+                 "qqq_paged_kv8_decode_split_kernel")
 
 
 def _rotate_half(x):
@@ -54,7 +63,27 @@ def _rotate_half(x):
     return torch.cat((-x[..., x.shape[-1] // 2:], x[..., : x.shape[-1] // 2]), dim=-1)
 
 
-def run(points, group_sizes, kv8=False):
+def _paged_decode_step(torch, dev, b, kvh, ctx, block_size, dtype):
+    """(PagedKVCache, PagedStep): b sequences of ctx - 1 keys and the decode step that brings each to ctx, with the block ids replaced by
+    a random permutation of the pool (the allocator hands blocks out in order; a serving pool after a while does not)"""
+    import dataclasses
+
+    from qqq_amd import PagedKVCache
+
+    per = -(-ctx // block_size)
+    cache = PagedKVCache(1, b * per, kvh, D, block_size, dev, dtype=dtype)
+    for i in range(b):
+        cache.add(i)
+    if ctx > 1:
+        cache.step(range(b), [ctx - 1] * b)
+    step = cache.step(range(b), [1] * b)
+    perm = torch.randperm(b * per, generator=torch.Generator().manual_seed(ctx + b)).to(dev)
+    table = perm[step.block_table.long()].to(torch.int32)
+    slots = perm[step.slots // block_size] * block_size + step.slots % block_size
+    return cache, dataclasses.replace(step, block_table=table, slots=slots)
+
+
+def run(points, group_sizes, kv8=False, paged=False, block_size=128):
     import torch
     import torch.nn.functional as F
 
@@ -63,6 +92,8 @@ def run(points, group_sizes, kv8=False):
 
     dev = torch.device("cuda:0")
     out = {"hidden": HIDDEN, "head_dim": D, "unit": "us per call, hipGraph replay (median)", "points": []}
+    if paged:
+        out["block_size"] = block_size
     for shape, (h, kvh) in SHAPES.items():
         for gs in group_sizes:
             attn = QuantLlamaAttention(HIDDEN, h, kvh, gs).to(dev)
@@ -123,6 +154,21 @@ def run(points, group_sizes, kv8=False):
                     else:
                         pt["fused_qkv_kv8"] = round(time_fn(fused8), 2)
                     del cache8
+                if paged and kind == "decode":
+                    # contiguous and paged module paths in rotation, fuse_qkv() and fuse_decode() on: name -> (cache, start or PagedStep)
+                    variants = {"fused_decode": (cache, start), "paged": _paged_decode_step(torch, dev, b, kvh, cap, block_size, torch.float16)}
+                    if kv8:
+                        variants["fused_decode_kv8"] = (KVCache(1, b, kvh, D, cap, dev, dtype=torch.int8), start)
+                        variants["paged_kv8"] = _paged_decode_step(torch, dev, b, kvh, cap, block_size, torch.int8)
+                    attn.fuse_decode()
+                    lists = {name: [] for name in variants}
+                    for _ in range(PAGED_ROUNDS):
+                        for name, (c_, st_) in variants.items():
+                            lists[name].append(round(time_fn(lambda: attn.forward(y, c_, st_)), 2))
+                    attn.unfuse_decode()
+                    pt["paged"] = {name: _median(v) for name, v in lists.items()}
+                    pt["paged_runs"] = lists
+                    del variants
                 attn.unfuse_qkv()
                 pt["saved"] = round(pt["unfused"] - pt["fused"], 2)
                 pt["saved_qkv"] = round(pt["unfused"] - pt["fused_qkv"], 2)
@@ -147,6 +193,8 @@ def summarize(trace_dir, bench=None):
     for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
         rows_all += list(csv.DictReader(open(f)))
     point = None
+    alternations = collections.defaultdict(lambda: collections.defaultdict(list))  # point -> split kernel -> [[us] per alternation]
+    last_split = {}
     for r in sorted(rows_all, key=lambda r: int(r["Start_Timestamp"])):
         name = r["Kernel_Name"]
         name = name[5:] if name.startswith("void ") else name
@@ -158,9 +206,14 @@ def summarize(trace_dir, bench=None):
             point = grid - POINT_MARK
             continue
         if point is not None:
-            for key in ("qqq_decode_split_kernel", "qqq_kv8_decode_split_kernel", "qqq_decode_combine_kernel", "attn_fwd"):
+            for key in SPLIT_KERNELS + ("qqq_decode_combine_kernel", "attn_fwd"):
                 if name.startswith(key) or (key == "attn_fwd" and "attn_fwd" in name):
                     per_point[point][key].append(us)
+                    if key in SPLIT_KERNELS:  # an alternation: a run of launches of one split kernel that another one ends
+                        if last_split.get(point) != key:
+                            alternations[point][key].append([])
+                            last_split[point] = key
+                        alternations[point][key][-1].append(us)
         if name.startswith("qqq_rope_qkv_kernel"):
             gy = int(r.get("Grid_Size_Y", 1)) // max(1, int(r.get("Workgroup_Size_Y", 1)))
             times[(grid, gy)].append(us)
@@ -183,7 +236,7 @@ def summarize(trace_dir, bench=None):
         pt = points[i] if i < len(points) else {}
         row = {"point": i}
         row.update({k: pt[k] for k in ("shape", "group_size", "kind", "batch", "context", "fused_qkv", "fused_decode", "fused_decode_alt",
-                                       "fused_decode_kv8") if k in pt})
+                                       "fused_decode_kv8", "paged") if k in pt})
         for key, v in ks.items():
             row[key + "_median_us"], row[key + "_calls"] = _median(v), len(v)
         if "qqq_decode_split_kernel" in ks and "context" in pt:
@@ -200,6 +253,17 @@ def summarize(trace_dir, bench=None):
                 v = sorted(ks.get(key, []))
                 if v:
                     row[key + "_p10_us"], row[key + "_p90_us"] = round(v[len(v) // 10], 2), round(v[(9 * len(v)) // 10], 2)
+        # a --paged run: the paged split kernel against the contiguous one of the same point.  The yardstick is the contiguous kernel's own
+        # run-to-run spread: the range of its per-alternation medians
+        for cont, pg in (("qqq_decode_split_kernel", "qqq_paged_decode_split_kernel"),
+                         ("qqq_kv8_decode_split_kernel", "qqq_paged_kv8_decode_split_kernel")):
+            if cont in ks and pg in ks:
+                meds = {k: [_median(a) for a in alternations[i][k]] for k in (cont, pg)}
+                spread = round(max(meds[cont]) - min(meds[cont]), 2)
+                excess = round(_median(ks[pg]) - _median(ks[cont]), 2)
+                row[pg + "_vs_contiguous"] = {"contiguous_median_us": _median(ks[cont]), "paged_median_us": _median(ks[pg]),
+                                              "excess_us": excess, "contiguous_spread_us": spread, "within_spread": excess <= spread,
+                                              "contiguous_alternation_medians_us": meds[cont], "paged_alternation_medians_us": meds[pg]}
         decode.append(row)
     return {"unit": "kernel time from rocprofv3 --kernel-trace (median over calls)", "kernels": rows, "points": decode}
 
@@ -209,6 +273,8 @@ def main():
     ap.add_argument("--points", default="decode,prefill")
     ap.add_argument("--group-sizes", default="-1,128")
     ap.add_argument("--kv8", action="store_true", help="also time the int8 KV cache (fused_decode_kv8 / fused_qkv_kv8)")
+    ap.add_argument("--paged", action="store_true", help="decode points: time the contiguous and the paged module path alternately")
+    ap.add_argument("--block-size", type=int, default=128, help="--paged: keys per block (a power of two in [16, 256])")
     ap.add_argument("--out", default=None)
     ap.add_argument("--summarize", default=None, metavar="TRACE_DIR")
     ap.add_argument("--bench", default=None, metavar="FILE", help="--summarize: the JSON output of the traced run, to label the points")
@@ -216,7 +282,7 @@ def main():
     if a.summarize:
         res = summarize(a.summarize, a.bench)
     else:
-        res = run(a.points.split(","), [int(v) for v in a.group_sizes.split(",")], kv8=a.kv8)
+        res = run(a.points.split(","), [int(v) for v in a.group_sizes.split(",")], kv8=a.kv8, paged=a.paged, block_size=a.block_size)
     s = json.dumps(res)
     print(s)
     if a.out:
