@@ -15,6 +15,8 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     rope_qkv_kv8(..., k_cache, v_cache, k_scale, v_scale) / decode_attention_kv8(...)  # the same two over an int8 KV cache (KVCache(dtype=torch.int8))
     rope_qkv_paged(..., pos, slots, k_pool, v_pool) / decode_attention_paged(q_out, k_pool, v_pool, block_table, pos, scale)  # the same two
     rope_qkv_paged_kv8(...) / decode_attention_paged_kv8(...)                       # over block pools (fp16 / int8) through slots and a block table
+    prefill_attention_paged(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale) / prefill_attention_paged_kv8(...)  # ragged causal
+                                                                                    # prefill attention over the block pools, output int8-quantised
     KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer                            # attention and the whole layer; qqq_amd/attention.py
     PagedKVCache, PagedStep                                                        # block pools + host-side allocator; qqq_amd/paged.py
 """
@@ -27,6 +29,8 @@ from .ops import (  # noqa: F401
     expand_int8,
     marlin_qqq_gemm,
     mul,
+    prefill_attention_paged,
+    prefill_attention_paged_kv8,
     qqq_gemm,
     qqq_gemm_bias,
     qqq_gemm_ex,
@@ -47,4 +51,5 @@ from .paged import PagedKVCache, PagedStep  # noqa: F401
 __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_int8", "mul", "marlin_qqq_gemm", "dynamic_quant", "quantlinear_forward",
            "rmsnorm_quant", "silu_mul_quant", "QuantLinear", "fuse_quant_linears", "QuantRMSNorm", "QuantLlamaMLP",
            "rope_qkv", "decode_attention", "rope_qkv_kv8", "decode_attention_kv8", "rope_qkv_paged",
-           "decode_attention_paged", "rope_qkv_paged_kv8", "decode_attention_paged_kv8", "PagedKVCache", "PagedStep", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer"]
+           "decode_attention_paged", "rope_qkv_paged_kv8", "decode_attention_paged_kv8", "prefill_attention_paged",
+           "prefill_attention_paged_kv8", "PagedKVCache", "PagedStep", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer"]

@@ -88,6 +88,15 @@ def lib():
     L.qqq_decode_attn_paged_kv8.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, ci, ci, ci, ci,
                                             ci, ci, ci, ci, vp]
     L.qqq_decode_attn_paged_kv8.restype = ci
+    # include/qqq_amd_prefill.h
+    L.qqq_prefill_attn_paged.argtypes = [vp, vp, vp, vp, ci, vp, vp, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, ci, ci, ci, ci, ci, ci,
+                                         ci, ci, ci, vp]
+    L.qqq_prefill_attn_paged.restype = ci
+    L.qqq_prefill_attn_paged_kv8.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, ci, ci, ci,
+                                             ci, ci, ci, ci, ci, ci, vp]
+    L.qqq_prefill_attn_paged_kv8.restype = ci
+    L.qqq_prefill_attn_workspace_bytes.argtypes = [ci, ci, ci]
+    L.qqq_prefill_attn_workspace_bytes.restype = ctypes.c_size_t
     L.qqq_amd_abi_version.restype = ci
     L.qqq_amd_last_error.restype = ctypes.c_char_p
     if L.qqq_amd_abi_version() != ABI_VERSION:

@@ -16,9 +16,11 @@ The attention core is torch's scaled_dot_product_attention, as in the reference,
 Paged cache: forward_int8(xq, s1, cache, step) with a PagedKVCache takes a PagedStep (cache.step(seq_ids, counts)) in place of the start
 position and xq [m, hidden] with the sequences' tokens packed in order.  rope_qkv_paged(_kv8) writes all m tokens in one launch; a step of
 one token per sequence runs decode_attention_paged(_kv8) through the step's block table, whatever fuse_decode() says; any other step runs
-scaled_dot_product_attention per sequence over PagedKVCache.gather (a contiguous copy; there is no paged prefill kernel).
+scaled_dot_product_attention per sequence over PagedKVCache.gather (a contiguous copy), or, after the opt-in fuse_prefill(),
+prefill_attention_paged(_kv8): one ragged causal attention over the whole packed batch that reads the pool in place and writes o_proj's
+input already int8-quantised.
 Parameter and buffer names are the reference's, so the layers' state-dicts load unchanged; the rope tables, the fused q|k|v copy of
-fuse_qkv() and the fuse_decode() flag are not part of them.
+fuse_qkv() and the fuse_decode() / fuse_prefill() flags are not part of them.
 """
 from __future__ import annotations
 
@@ -151,6 +153,7 @@ class QuantLlamaAttention(nn.Module):
         self._cos = self._sin = None  # rope tables, built lazily up to the cache capacity on the module's device
         self._qkv = None  # fuse_qkv(): the fused q|k|v layer, kept outside the module tree (not in the state-dict)
         self._decode = False  # fuse_decode(): a plain flag (not in the state-dict; kept by load_state_dict and .to())
+        self._prefill = False  # fuse_prefill(): the same kind of flag
         # a plain function: a bound method would make module -> hook -> module a reference cycle (see QuantLlamaMLP)
         self._register_load_state_dict_pre_hook(_drop_fused_qkv_on_load, with_module=True)
 
@@ -198,6 +201,23 @@ class QuantLlamaAttention(nn.Module):
     @property
     def decode_fused(self) -> bool:
         return self._decode
+
+    def fuse_prefill(self):
+        """Opt-in: a step over a PagedKVCache that is not a decode step (a prompt, a chunk, chunks batched with decoding rows) runs
+        prefill_attention_paged(_kv8) -- one ragged causal attention launch over the whole packed batch that reads K and V through the
+        block table in place, and one that quantises its rows for o_proj -- in place of the per-sequence gather, scaled_dot_product_attention
+        and dynamic_quant.  Decode steps and KVCache paths are unchanged.  state_dict(): unchanged.  Returns self."""
+        self._prefill = True
+        return self
+
+    def unfuse_prefill(self):
+        """Back to scaled_dot_product_attention over PagedKVCache.gather for paged steps of more than one token."""
+        self._prefill = False
+        return self
+
+    @property
+    def prefill_fused(self) -> bool:
+        return self._prefill
 
     def _decode_supported(self) -> bool:
         h, kvh, d = self.num_heads, self.num_key_value_heads, self.head_dim
@@ -257,6 +277,10 @@ class QuantLlamaAttention(nn.Module):
         if step.decode:  # one token per sequence: the decode kernel through the block table, whatever fuse_decode() says
             decode = ops.decode_attention_paged_kv8 if cache.quantized else ops.decode_attention_paged
             aq, a1 = decode(q_out, *pools, step.block_table, step.last_pos, self.scaling, max_len=step.max_len)
+            return self.o_proj.forward_int8(aq, a1)
+        if self._prefill:  # fuse_prefill(): the whole packed batch in one ragged causal attention over the pool, quantised for o_proj
+            prefill = ops.prefill_attention_paged_kv8 if cache.quantized else ops.prefill_attention_paged
+            aq, a1 = prefill(q_out, *pools, step.block_table, step.cu_tokens, step.start_pos, self.scaling, max_len=step.max_len)
             return self.o_proj.forward_int8(aq, a1)
         outs, t = [], 0
         for sid, c, start in zip(step.seq_ids, step.counts, step.starts):  # prefill / chunks: SDPA over a gathered copy, per sequence
@@ -360,6 +384,19 @@ class QuantLlamaDecoderLayer(nn.Module):
     @property
     def decode_fused(self) -> bool:
         return self.self_attn.decode_fused
+
+    def fuse_prefill(self):
+        """self_attn.fuse_prefill(): paged steps of more than one token take the paged prefill attention kernel.  Returns self."""
+        self.self_attn.fuse_prefill()
+        return self
+
+    def unfuse_prefill(self):
+        self.self_attn.unfuse_prefill()
+        return self
+
+    @property
+    def prefill_fused(self) -> bool:
+        return self.self_attn.prefill_fused
 
     def forward(self, hidden: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
         x = hidden.reshape(-1, self.hidden_size)

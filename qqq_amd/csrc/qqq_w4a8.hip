@@ -32,6 +32,7 @@
 //   qqq_act.hip.h, qqq_attn.hip.h, qqq_decode.hip.h   the decoder block's fused quantisers, RoPE + KV-cache write, split-K decode attention
 //   qqq_kv8.hip.h      the int8 KV cache: the quantising RoPE / cache write and the decode split kernel that reads it
 //   qqq_paged.hip.h    the block-table (paged) KV cache, fp16 and int8: the cache writes by slot and the decode split kernels through a block table
+//   qqq_prefill.hip.h  paged, ragged, causal prefill attention over the block pools (fp16 and int8) and the quantisation of its rows
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -66,6 +67,8 @@
 #include "../../include/qqq_amd_kv8.h"
 #include "qqq_paged.hip.h"
 #include "../../include/qqq_amd_paged.h"
+#include "qqq_prefill.hip.h"
+#include "../../include/qqq_amd_prefill.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -907,6 +910,125 @@ extern "C" int qqq_decode_attn_paged_kv8(const void* q, const void* k_pool, cons
                                          int block_size, int max_len, int dev, void* stream) {
   return decode_attn_paged("qqq_decode_attn_paged_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, pos, scale,
                            o_fp16, xq, s1, workspace, workspace_bytes, b, h, kvh, d, num_blocks, block_size, max_len, dev, stream);
+}
+
+// ---- the paged prefill attention (include/qqq_amd_prefill.h; kernels in qqq_prefill.hip.h): one attention launch over the packed batch's
+// query tiles and one launch that quantises the rows it wrote.  One body for the pair; `name` is the entry point's.
+static bool prefill_shape_error(int h, int kvh, int d) {
+  return h < 1 || kvh < 1 || h % kvh != 0 || h / kvh > DEC_GMAX || (d != 64 && d != 128) || (long long)h * d > 16384;
+}
+
+extern "C" size_t qqq_prefill_attn_workspace_bytes(int m, int h, int d) {
+  if (m <= 0 || h < 1 || (d != 64 && d != 128) || (long long)h * d > 16384) return 0;
+  return (size_t)m * h * d * sizeof(_Float16);
+}
+
+template <int VPT>
+static void prefill_quant(int m, hipStream_t st, const _Float16* o16, const int* cu, const long long* sp, long long limit, int8_t* xq,
+                          float* s1, int b, int hd) {
+  hipLaunchKernelGGL((qqq_prefill_quant_kernel<VPT, PF_QUANT_NT>), dim3(m), dim3(PF_QUANT_NT), 0, st, o16, cu, sp, limit, xq, s1, m, b, hd);
+}
+
+static int prefill_attn_paged(const char* name, bool kv8, const void* q, const void* k_pool, const void* v_pool, const void* k_scale,
+                              const void* v_scale, const void* block_table, int table_stride, const void* cu_tokens, const void* start_pos,
+                              float scale, void* o_fp16, void* xq, void* s1, void* workspace, size_t workspace_bytes, int m, int b, int h,
+                              int kvh, int d, int num_blocks, int block_size, int max_len, int dev, void* stream) {
+  g_err[0] = 0;
+  if (m < 0 || b < 0 || h < 0 || kvh < 0 || d < 0 || num_blocks < 0 || block_size < 0 || table_stride < 0 || max_len < 0) {
+    snprintf(g_err, sizeof(g_err), "%s: negative size (m=%d b=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_stride=%d max_len=%d)",
+             name, m, b, h, kvh, d, num_blocks, block_size, table_stride, max_len);
+    return QQQ_ERR_ARG;
+  }
+  if (m == 0 || b == 0) return QQQ_OK;
+  const int lbs = paged_log2_block(block_size);
+  if (prefill_shape_error(h, kvh, d) || b > 65535 || lbs < 0 || num_blocks < 1 || (long long)num_blocks * block_size > 0x7fffffffLL ||
+      table_stride < 1 || max_len < 1 || max_len > (long long)table_stride * block_size) {
+    snprintf(g_err, sizeof(g_err), "%s: bad shape m=%d b=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_stride=%d max_len=%d (need "
+             "h %% kvh == 0, h / kvh <= %d, d 64 or 128, h*d <= 16384, b <= 65535, block_size a power of two in [16, 256], num_blocks >= 1, "
+             "num_blocks * block_size < 2^31, 1 <= max_len <= table_stride * block_size)", name, m, b, h, kvh, d, num_blocks, block_size,
+             table_stride, max_len, DEC_GMAX);
+    return QQQ_ERR_ARG;
+  }
+  if (!o_fp16 && !xq && !s1) {
+    snprintf(g_err, sizeof(g_err), "%s: no output (o_fp16 and xq / s1 are all NULL)", name);
+    return QQQ_ERR_ARG;
+  }
+  if (!q || !k_pool || !v_pool || !block_table || !cu_tokens || !start_pos || (!xq) != (!s1) || (!o_fp16 && !workspace) ||
+      misaligned(q, 16) || misaligned(k_pool, 16) || misaligned(v_pool, 16) || misaligned(block_table, 4) || misaligned(cu_tokens, 4) ||
+      misaligned(start_pos, 8) || (workspace && misaligned(workspace, 16)) || (o_fp16 && misaligned(o_fp16, 16)) ||
+      (xq && misaligned(xq, 8)) || (s1 && misaligned(s1, 4)) ||
+      (kv8 && (!k_scale || !v_scale || misaligned(k_scale, 4) || misaligned(v_scale, 4)))) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (q / pools / scales / block_table / cu_tokens / start_pos must be non-NULL, workspace "
+             "too where o_fp16 is NULL, xq and s1 both given or both NULL; q, pools, o_fp16, workspace 16-byte, start_pos / xq 8-byte, "
+             "cu_tokens, block_table, s1 and the scales 4-byte aligned)", name);
+    return QQQ_ERR_ARG;
+  }
+  const size_t need = qqq_prefill_attn_workspace_bytes(m, h, d);
+  if (!o_fp16 && workspace_bytes < need) {
+    snprintf(g_err, sizeof(g_err), "%s: workspace of %zu bytes, need %zu", name, workspace_bytes, need);
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int tq = PF_ROWS / (h / kvh);  // tokens of a query tile
+  const int nslots = m / tq + b;      // sequence i owns the slots from cu_tokens[i] / tq + i on: an upper bound of the tiles of any split of m
+  const dim3 grid(nslots, kvh), block(PF_NT);
+  const long long limit = max_len;
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const _Float16* qp = static_cast<const _Float16*>(q);
+  const float *ksp = static_cast<const float*>(k_scale), *vsp = static_cast<const float*>(v_scale);
+  const int* tp = static_cast<const int*>(block_table);
+  const int* cup = static_cast<const int*>(cu_tokens);
+  const long long* spp = static_cast<const long long*>(start_pos);
+  _Float16* o16 = static_cast<_Float16*>(o_fp16 ? o_fp16 : workspace);
+  if (kv8) {
+    if (d == 64)
+      hipLaunchKernelGGL((qqq_prefill_attn_kernel<64, true>), grid, block, 0, st, qp, k_pool, v_pool, ksp, vsp, tp, table_stride, cup, spp,
+                         limit, scale_log2, o16, m, b, h, kvh, num_blocks, lbs, nslots);
+    else
+      hipLaunchKernelGGL((qqq_prefill_attn_kernel<128, true>), grid, block, 0, st, qp, k_pool, v_pool, ksp, vsp, tp, table_stride, cup, spp,
+                         limit, scale_log2, o16, m, b, h, kvh, num_blocks, lbs, nslots);
+  } else {
+    if (d == 64)
+      hipLaunchKernelGGL((qqq_prefill_attn_kernel<64, false>), grid, block, 0, st, qp, k_pool, v_pool, ksp, vsp, tp, table_stride, cup, spp,
+                         limit, scale_log2, o16, m, b, h, kvh, num_blocks, lbs, nslots);
+    else
+      hipLaunchKernelGGL((qqq_prefill_attn_kernel<128, false>), grid, block, 0, st, qp, k_pool, v_pool, ksp, vsp, tp, table_stride, cup, spp,
+                         limit, scale_log2, o16, m, b, h, kvh, num_blocks, lbs, nslots);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_prefill_attn_kernel launch");
+  if (!xq) return QQQ_OK;
+  int8_t* xqp = static_cast<int8_t*>(xq);
+  float* s1p = static_cast<float*>(s1);
+  const int hd = h * d, nvec = hd / 8;
+  if (nvec <= PF_QUANT_NT)
+    prefill_quant<1>(m, st, o16, cup, spp, limit, xqp, s1p, b, hd);
+  else if (nvec <= 2 * PF_QUANT_NT)
+    prefill_quant<2>(m, st, o16, cup, spp, limit, xqp, s1p, b, hd);
+  else
+    prefill_quant<4>(m, st, o16, cup, spp, limit, xqp, s1p, b, hd);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_prefill_quant_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_prefill_attn_paged(const void* q, const void* k_pool, const void* v_pool, const void* block_table, int table_stride,
+                                      const void* cu_tokens, const void* start_pos, float scale, void* o_fp16, void* xq, void* s1,
+                                      void* workspace, size_t workspace_bytes, int m, int b, int h, int kvh, int d, int num_blocks,
+                                      int block_size, int max_len, int dev, void* stream) {
+  return prefill_attn_paged("qqq_prefill_attn_paged", false, q, k_pool, v_pool, nullptr, nullptr, block_table, table_stride, cu_tokens,
+                            start_pos, scale, o_fp16, xq, s1, workspace, workspace_bytes, m, b, h, kvh, d, num_blocks, block_size, max_len,
+                            dev, stream);
+}
+
+extern "C" int qqq_prefill_attn_paged_kv8(const void* q, const void* k_pool, const void* v_pool, const void* k_scale, const void* v_scale,
+                                          const void* block_table, int table_stride, const void* cu_tokens, const void* start_pos,
+                                          float scale, void* o_fp16, void* xq, void* s1, void* workspace, size_t workspace_bytes, int m,
+                                          int b, int h, int kvh, int d, int num_blocks, int block_size, int max_len, int dev, void* stream) {
+  return prefill_attn_paged("qqq_prefill_attn_paged_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, cu_tokens,
+                            start_pos, scale, o_fp16, xq, s1, workspace, workspace_bytes, m, b, h, kvh, d, num_blocks, block_size, max_len,
+                            dev, stream);
 }
 
 extern "C" int qqq_quantlinear_forward(const void* x, void* xq, void* s1, const void* B, void* C, void* D,

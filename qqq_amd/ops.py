@@ -991,3 +991,124 @@ def decode_attention_paged_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool
     else:
         out = _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, k_scale, v_scale)
     return out if return_fp16 else out[:2]
+
+
+# ---- the paged prefill attention (include/qqq_amd_prefill.h): any mix of prompts, chunks and decoding rows of a packed batch in one call,
+# K and V read in place through the block table.
+
+def _prefill_attention_paged_shapes(name, q_out, k_pool, block_table, cu_tokens, start_pos, max_len):
+    # (m, b, h, kvh, d, num_blocks, block_size, table_stride, max_len) from the tensors' shapes
+    if k_pool.dim() != 4:
+        raise RuntimeError(f"{name}: k_pool must be [num_blocks, kvh, block_size, d]")
+    nb, kvh, bs, d = k_pool.shape
+    if block_table.dim() != 2:
+        raise RuntimeError(f"{name}: block_table must be int32 [b, blocks per row]")
+    b, width = block_table.shape
+    if q_out.dim() != 3 or q_out.shape[2] != d:
+        raise RuntimeError(f"{name}: q_out {tuple(q_out.shape)} must be [m, h, {d}] (rope_qkv_paged's output)")
+    if cu_tokens.numel() != b + 1 or start_pos.numel() != b:
+        raise RuntimeError(f"{name}: cu_tokens holds {cu_tokens.numel()} entries and start_pos {start_pos.numel()}, the block table has {b} "
+                           f"rows (need b + 1 and b)")
+    max_len = width * bs if max_len is None else int(max_len)
+    return q_out.shape[0], b, q_out.shape[1], kvh, d, nb, bs, width, max_len
+
+
+def _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16, k_scale=None,
+                                  v_scale=None):
+    kv8 = k_scale is not None
+    name = "prefill_attention_paged_kv8" if kv8 else "prefill_attention_paged"
+    ts = (q_out, k_pool, v_pool, block_table, cu_tokens, start_pos) + ((k_scale, v_scale) if kv8 else ())
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError(f"{name}: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != q_out.device for t in ts):
+        raise RuntimeError(f"{name}: every tensor must be on the same GPU")
+    if q_out.dtype != torch.float16 or start_pos.dtype != torch.int64 or block_table.dtype != torch.int32 or cu_tokens.dtype != torch.int32:
+        raise RuntimeError(f"{name}: q_out must be fp16, start_pos int64, block_table and cu_tokens int32")
+    _paged_check_pools(name, k_pool, v_pool, k_scale, v_scale)
+    m, b, h, kvh, d, nb, bs, width, max_len = _prefill_attention_paged_shapes(name, q_out, k_pool, block_table, cu_tokens, start_pos, max_len)
+    dev = q_out.device
+    xq = torch.empty((m, h * d), dtype=torch.int8, device=dev)
+    s1 = torch.empty((m, 1), dtype=torch.float32, device=dev)
+    o16 = torch.empty((m, h * d) if return_fp16 else (0,), dtype=torch.float16, device=dev)
+    if m == 0 or b == 0:
+        return xq, s1, o16
+    L = _lib.lib()
+    nbytes = 0 if return_fp16 else L.qqq_prefill_attn_workspace_bytes(m, h, d)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)  # torch's allocator: also under stream / graph capture
+    q2, table, cu, sp = q_out.contiguous(), block_table.contiguous(), cu_tokens.contiguous(), start_pos.contiguous()
+    tail = (_ptr(table), width, _ptr(cu), _ptr(sp), float(scale), _ptr(o16), _ptr(xq), _ptr(s1), _ptr(ws), ws.numel(), m, b, h, kvh, d, nb,
+            bs, max_len, dev.index or 0, _stream_for(q_out))
+    if kv8:
+        err = L.qqq_prefill_attn_paged_kv8(_ptr(q2), _ptr(k_pool), _ptr(v_pool), _ptr(k_scale), _ptr(v_scale), *tail)
+    else:
+        err = L.qqq_prefill_attn_paged(_ptr(q2), _ptr(k_pool), _ptr(v_pool), *tail)
+    if err:
+        raise RuntimeError(f"qqq_amd: {name} error {err}: {_lib.last_error()}")
+    return xq, s1, o16
+
+
+def _prefill_paged_fake(name, q_out, k_pool, block_table, cu_tokens, start_pos, max_len, return_fp16):
+    m, _, h, _, d = _prefill_attention_paged_shapes(name, q_out, k_pool, block_table, cu_tokens, start_pos, max_len)[:5]
+    return (q_out.new_empty((m, h * d), dtype=torch.int8), q_out.new_empty((m, 1), dtype=torch.float32),
+            q_out.new_empty((m, h * d) if return_fp16 else (0,), dtype=torch.float16))
+
+
+@torch.library.custom_op("qqq_amd::prefill_attn_paged", mutates_args=())
+def _prefill_attn_paged_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                           cu_tokens: torch.Tensor, start_pos: torch.Tensor, scale: float, max_len: Optional[int],
+                           return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16)
+
+
+@_prefill_attn_paged_op.register_fake
+def _(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16):
+    return _prefill_paged_fake("prefill_attention_paged", q_out, k_pool, block_table, cu_tokens, start_pos, max_len, return_fp16)
+
+
+def prefill_attention_paged(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                            cu_tokens: torch.Tensor, start_pos: torch.Tensor, scale: float, max_len: Optional[int] = None,
+                            return_fp16: bool = False):
+    """Causal attention of a packed batch of chunks over a block pool, read in place: (xq int8 [m, h*d], s1 f32 [m, 1]) -- o_proj's input,
+    bit for bit dynamic_quant of the fp16 output -- plus that output fp16 [m, h*d] with `return_fp16`.  Two launches for the whole batch.
+
+    q_out      fp16 [m, h, d]: rope_qkv_paged's output (the step's new tokens are in the pool already)
+    k_pool, v_pool   fp16 [num_blocks, kvh, block_size, d], only read
+    block_table      int32 [b, W] in device memory, as for decode_attention_paged
+    cu_tokens  int32 [b + 1]: sequence i owns tokens cu_tokens[i] ... cu_tokens[i + 1] - 1 (cu_tokens[0] = 0, non-decreasing); tokens from
+               cu_tokens[b] on are padding
+    start_pos  int64 [b]: the position of sequence i's first token of the call; token t of it attends keys 0 ... its own position
+    max_len    default and upper bound W * block_size; a sequence that starts below 0 or ends beyond max_len writes nothing
+    Rows of padding tokens and of such sequences are left as torch.empty made them.  The launch sizes depend on the shapes alone, so a
+    captured graph replays with other contents of cu_tokens, start_pos and block_table."""
+    if _compiling(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos):
+        out = _prefill_attn_paged_op(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16)
+    else:
+        out = _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16)
+    return out if return_fp16 else out[:2]
+
+
+@torch.library.custom_op("qqq_amd::prefill_attn_paged_kv8", mutates_args=())
+def _prefill_attn_paged_kv8_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                               block_table: torch.Tensor, cu_tokens: torch.Tensor, start_pos: torch.Tensor, scale: float,
+                               max_len: Optional[int], return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16, k_scale,
+                                         v_scale)
+
+
+@_prefill_attn_paged_kv8_op.register_fake
+def _(q_out, k_pool, v_pool, k_scale, v_scale, block_table, cu_tokens, start_pos, scale, max_len, return_fp16):
+    return _prefill_paged_fake("prefill_attention_paged_kv8", q_out, k_pool, block_table, cu_tokens, start_pos, max_len, return_fp16)
+
+
+def prefill_attention_paged_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                                block_table: torch.Tensor, cu_tokens: torch.Tensor, start_pos: torch.Tensor, scale: float,
+                                max_len: Optional[int] = None, return_fp16: bool = False):
+    """prefill_attention_paged over an int8 pool (k_pool, v_pool int8 [num_blocks, kvh, block_size, d]; k_scale, v_scale f32 [num_blocks,
+    kvh, block_size]) with decode_attention_kv8's arithmetic: scores from the codes times the key's scale, V as fp16(code * scale)."""
+    if _compiling(q_out, k_pool, v_pool, k_scale, v_scale, block_table, cu_tokens, start_pos):
+        out = _prefill_attn_paged_kv8_op(q_out, k_pool, v_pool, k_scale, v_scale, block_table, cu_tokens, start_pos, scale, max_len,
+                                         return_fp16)
+    else:
+        out = _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16, k_scale,
+                                            v_scale)
+    return out if return_fp16 else out[:2]

@@ -1,5 +1,6 @@
 """The block-table (paged) KV cache: per layer a pool of blocks of `block_size` keys that any sequence may own, a host-side block allocator
-with per-sequence lengths, and the per-step metadata the paged ops read (ops.rope_qkv_paged / decode_attention_paged and their _kv8 forms).
+with per-sequence lengths, and the per-step metadata the paged ops read (ops.rope_qkv_paged / decode_attention_paged /
+prefill_attention_paged and their _kv8 forms).
 
     PagedKVCache   k[layer], v[layer] of shape [num_blocks, num_kv_heads, block_size, head_dim] (fp16 or int8; an int8 pool with
                    k_scale[layer], v_scale[layer] [num_blocks, num_kv_heads, block_size]); add / free / step / gather
@@ -23,7 +24,9 @@ class PagedStep:
 
     Host fields: seq_ids, counts, starts, max_len (the longest sequence after the step), decode (every count is 1).
     Device tensors: pos int64 [m] and slots int64 [m] per token (m = sum(counts)); block_table int32 [b, W] (row i: the blocks of
-    sequence i, padded with 0) and last_pos int64 [b] (the position of each sequence's last token) per sequence."""
+    sequence i, padded with 0) and last_pos int64 [b] (the position of each sequence's last token) per sequence; cu_tokens int32 [b + 1]
+    (sequence i owns tokens cu_tokens[i] ... cu_tokens[i + 1] - 1 of the packed batch) and start_pos int64 [b] (= starts), which
+    ops.prefill_attention_paged reads."""
     seq_ids: List
     counts: List[int]
     starts: List[int]
@@ -33,6 +36,8 @@ class PagedStep:
     slots: torch.Tensor
     block_table: torch.Tensor
     last_pos: torch.Tensor
+    cu_tokens: Optional[torch.Tensor] = None
+    start_pos: Optional[torch.Tensor] = None
 
 
 class PagedKVCache:
@@ -133,9 +138,13 @@ class PagedKVCache:
         table = [self._blocks[sid] + [0] * (width - len(self._blocks[sid])) for sid in seq_ids]
         last = [self._len[sid] - 1 for sid in seq_ids]
         dev = self.device
+        cu = [0]
+        for c in counts:
+            cu.append(cu[-1] + c)
         return PagedStep(seq_ids=seq_ids, counts=counts, starts=starts, max_len=max(last) + 1, decode=all(c == 1 for c in counts),
                          pos=torch.tensor(pos, dtype=torch.int64).to(dev), slots=torch.tensor(slots, dtype=torch.int64).to(dev),
-                         block_table=torch.tensor(table, dtype=torch.int32).to(dev), last_pos=torch.tensor(last, dtype=torch.int64).to(dev))
+                         block_table=torch.tensor(table, dtype=torch.int32).to(dev), last_pos=torch.tensor(last, dtype=torch.int64).to(dev),
+                         cu_tokens=torch.tensor(cu, dtype=torch.int32).to(dev), start_pos=torch.tensor(starts, dtype=torch.int64).to(dev))
 
     # ---- reading a sequence back (plain torch; CPU tensors too)
 

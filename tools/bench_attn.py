@@ -19,11 +19,20 @@ KV cache.  Both paths start from the fp16 output of input_layernorm and end with
                 times each in one process -- with --kv8 the two int8 paths join the rotation -- and every list is kept under `paged_runs`,
                 the medians under `paged`.
 
+    prefill_paged  (--points prefill --paged [--kv8] [--block-size N]: this mode alone) the module over a PagedKVCache at the packed steps of
+                PAGED_PREFILL, with fuse_prefill() off -- per sequence PagedKVCache.gather, a mask, SDPA; then torch.cat and dynamic_quant:
+                the baseline -- and on -- prefill_attention_paged, one ragged causal attention over the pool in place.  The off path builds
+                index tensors on the host, so it cannot be captured: both are timed eagerly with events around each call, alternately,
+                PREFILL_ROUNDS times in one process; every list is kept.  `faster` says whether the fused median is below the unfused one by
+                more than the unfused path's spread over the rounds.  The attention op alone is timed from a hipGraph as well and its rate
+                given against the nominal fp16 MFMA peak (FP16_PEAK_TFLOPS).
+
 Points: decode (s = 1) at b in {1, 16} with a context of {1024, 4096} tokens (the new token included), and b = 1 at 16384; prefill of s in
 {128, 1024, 4096} tokens at b = 1 from position 0.  Before each point one dynamic_quant of POINT_MARK + i rows is launched: its grid marks
 where point i starts in a kernel trace.
 
     python tools/bench_attn.py [--points decode,prefill] [--kv8] [--out FILE]   -> one JSON object on stdout
+    python tools/bench_attn.py --points prefill --paged [--kv8] [--block-size N] [--out FILE]   -> the paged prefill points alone
     python tools/bench_attn.py --summarize TRACE_DIR [--bench FILE]     -> from a rocprofv3 --kernel-trace run of the above: the
                                                                           qqq_rope_qkv_kernel times and HBM fractions, and per decode point
                                                                           (labelled from the run's JSON output FILE) the median times of
@@ -53,6 +62,14 @@ HBM_BYTES_PER_S = 8e12
 ROPE_NT = 128  # qqq_w4a8.hip: ROPE_NT
 KV8_ROUNDS = 3  # --kv8: alternations of fused_decode / fused_decode_kv8 at a decode point
 PAGED_ROUNDS = 5  # --paged: alternations of the contiguous and the paged paths at a decode point
+PREFILL_ROUNDS = 5  # --points prefill --paged: alternations of fuse_prefill() off and on at a point
+PREFILL_CALLS = 7   # ... and event-timed calls per alternation (their median is the alternation's value)
+FP16_PEAK_TFLOPS = 2500.0  # MI355X, dense fp16 MFMA (nominal)
+# (name, [(start, count) per sequence]): a prompt, a batch of prompts, a late chunk, and that chunk batched with 15 decoding rows
+PAGED_PREFILL = [("1x2048", [(0, 2048)]), ("8x512", [(0, 512)] * 8), ("chunk512@3584", [(3584, 512)]),
+                 ("chunk512@3584+15dec@2048", [(3584, 512)] + [(2047, 1)] * 15)]
+PREFILL_KERNELS = ("qqq_prefill_attn_kernel", "qqq_prefill_quant_kernel", "qqq_paged_rope_qkv_kernel", "qqq_paged_kv8_rope_qkv_kernel",
+                   "qqq_dynamic_quant_kernel")
 SPLIT_KERNELS = ("qqq_decode_split_kernel", "qqq_kv8_decode_split_kernel", "qqq_paged_decode_split_kernel",
                  "qqq_paged_kv8_decode_split_kernel")
 
@@ -184,6 +201,139 @@ def _median(v):
     return round(v[len(v) // 2], 2)
 
 
+def _paged_prefill_step(torch, dev, seqs, kvh, block_size, dtype):
+    """(PagedKVCache, PagedStep) of a packed step of (start, count) sequences whose histories are in the pool; the allocator's free list is
+    shuffled first, so block tables, slots and gather() all see a random permutation of the pool"""
+    import random
+
+    from qqq_amd import PagedKVCache
+
+    nb = sum(-(-(s + c) // block_size) for s, c in seqs)
+    cache = PagedKVCache(1, nb, kvh, D, block_size, dev, dtype=dtype)
+    random.Random(nb).shuffle(cache._free)
+    for i, (s, _) in enumerate(seqs):
+        cache.add(i)
+        if s:
+            cache.step([i], [s])
+    g = torch.Generator(device=dev).manual_seed(nb)
+    for t in cache.k + cache.v:  # a history: random rows (random codes and scales for an int8 pool)
+        if dtype == torch.int8:
+            t.copy_(torch.randint(-127, 128, t.shape, generator=g, device=dev, dtype=torch.int8))
+        else:
+            t.copy_(torch.randn(t.shape, generator=g, device=dev).half())
+    if dtype == torch.int8:
+        for t in cache.k_scale + cache.v_scale:
+            t.copy_(torch.rand(t.shape, generator=g, device=dev) * 0.02 + 0.005)
+    return cache, cache.step(range(len(seqs)), [c for _, c in seqs])
+
+
+def _time_eager(torch, fn, calls):
+    """median GPU time of one eager call in us, events around each call (launch gaps of the call included, as a serving loop sees them)"""
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    v = []
+    for _ in range(calls):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        v.append(a.elapsed_time(b) * 1e3)
+    return _median(v)
+
+
+def run_paged_prefill(group_sizes, kv8=False, block_size=128):
+    import torch
+
+    from bench_llama import make_ql, time_fn
+    from qqq_amd import QuantLlamaAttention, dynamic_quant, ops
+
+    dev = torch.device("cuda:0")
+    out = {"hidden": HIDDEN, "head_dim": D, "block_size": block_size, "rounds": PREFILL_ROUNDS, "calls_per_round": PREFILL_CALLS,
+           "unit": "us per module call (fp16 norm output -> o_proj output), eager, events around each call; median of the rounds' medians",
+           "fp16_peak_tflops_nominal": FP16_PEAK_TFLOPS, "points": []}
+    for shape, (h, kvh) in SHAPES.items():
+        for gs in group_sizes:
+            attn = QuantLlamaAttention(HIDDEN, h, kvh, gs).to(dev)
+            attn.q_proj, attn.k_proj = make_ql(dev, h * D, HIDDEN, gs, 1), make_ql(dev, kvh * D, HIDDEN, gs, 2)
+            attn.v_proj, attn.o_proj = make_ql(dev, kvh * D, HIDDEN, gs, 3), make_ql(dev, HIDDEN, h * D, gs, 4)
+            attn.fuse_qkv()
+            for name, seqs in PAGED_PREFILL:
+                for dtype in (torch.float16,) + ((torch.int8,) if kv8 else ()):
+                    cache, step = _paged_prefill_step(torch, dev, seqs, kvh, block_size, dtype)
+                    m = sum(step.counts)
+                    y = (torch.randn((m, HIDDEN), device=dev) * 0.5).half()
+                    dynamic_quant(torch.zeros((POINT_MARK + len(out["points"]), 8), dtype=torch.float16, device=dev))
+                    lists = {"unfused": [], "fused": []}
+                    for _ in range(PREFILL_ROUNDS):
+                        attn.unfuse_prefill()
+                        lists["unfused"].append(_time_eager(torch, lambda: attn.forward(y, cache, step), PREFILL_CALLS))
+                        attn.fuse_prefill()
+                        lists["fused"].append(_time_eager(torch, lambda: attn.forward(y, cache, step), PREFILL_CALLS))
+                    attn.unfuse_prefill()
+                    # the attention op alone, from a hipGraph: its launches are shape-only
+                    q_out = torch.randn((m, h, D), device=dev).half()
+                    pools = (cache.k[0], cache.v[0]) + ((cache.k_scale[0], cache.v_scale[0]) if cache.quantized else ())
+                    op = ops.prefill_attention_paged_kv8 if cache.quantized else ops.prefill_attention_paged
+                    op_us = time_fn(lambda: op(q_out, *pools, step.block_table, step.cu_tokens, step.start_pos, D ** -0.5,
+                                               max_len=step.max_len))
+                    flops = sum(4 * D * h * (2 * s + c + 1) * c // 2 for s, c in seqs)  # 2 * 2 d per (token, head, attended key)
+                    mu, mf = _median(lists["unfused"]), _median(lists["fused"])
+                    spread = round(max(lists["unfused"]) - min(lists["unfused"]), 2)
+                    pt = {"shape": shape, "heads": h, "kv_heads": kvh, "group_size": gs, "kind": "prefill_paged", "step": name,
+                          "kv_dtype": "int8" if cache.quantized else "fp16", "tokens": m, "sequences": len(seqs), "unfused": mu, "fused": mf,
+                          "unfused_spread": spread, "ratio": round(mu / mf, 3), "faster": bool(mu - mf > spread),
+                          "gated": "dec@" not in name, "runs": lists, "attention_op_us": round(op_us, 2), "attention_flops": flops,
+                          "attention_tflops": round(flops / op_us * 1e-6, 1),
+                          "fraction_of_fp16_peak": round(flops / op_us * 1e-6 / FP16_PEAK_TFLOPS, 4)}
+                    out["points"].append(pt)
+                    print(json.dumps(pt), file=sys.stderr, flush=True)
+                    del cache, step, pools
+                    torch.cuda.empty_cache()
+    return out
+
+
+def summarize_prefill(trace_dir, bench=None):
+    """kernel medians of a rocprofv3 --kernel-trace run of --points prefill --paged, per point (between the marker launches)"""
+    from code_object import _demangle
+
+    rows_all = []
+    for f in glob.glob(os.path.join(trace_dir, "**", "*kernel_trace.csv"), recursive=True):
+        rows_all += list(csv.DictReader(open(f)))
+    per_point = collections.defaultdict(lambda: collections.defaultdict(list))
+    point = None
+    for r in sorted(rows_all, key=lambda r: int(r["Start_Timestamp"])):
+        name = r["Kernel_Name"]
+        name = name[5:] if name.startswith("void ") else name
+        name = name.split("(")[0]
+        name = _demangle(name) if name.startswith("_Z") else name
+        us = (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3
+        grid = int(r["Grid_Size_X"]) // int(r["Workgroup_Size_X"])
+        if name.startswith("qqq_dynamic_quant_kernel") and grid >= POINT_MARK:
+            point = grid - POINT_MARK
+            continue
+        if point is None:
+            continue
+        key = next((k for k in PREFILL_KERNELS if name.startswith(k)), "attn_fwd" if "attn_fwd" in name or "fmha" in name.lower() else None)
+        if key:
+            per_point[point][key].append(us)
+    points = json.load(open(bench))["points"] if bench else []
+    rows = []
+    for i, ks in sorted(per_point.items()):
+        pt = points[i] if i < len(points) else {}
+        row = {"point": i}
+        row.update({k: pt[k] for k in ("shape", "group_size", "step", "kv_dtype", "tokens", "attention_flops") if k in pt})
+        for key, v in ks.items():
+            row[key + "_median_us"], row[key + "_calls"] = _median(v), len(v)
+        if "qqq_prefill_attn_kernel" in ks and "attention_flops" in pt:
+            tf = pt["attention_flops"] / row["qqq_prefill_attn_kernel_median_us"] * 1e-6
+            row.update({"prefill_attn_kernel_tflops": round(tf, 1), "fraction_of_fp16_peak": round(tf / FP16_PEAK_TFLOPS, 4)})
+        rows.append(row)
+    return {"unit": "kernel time from rocprofv3 --kernel-trace (median over calls), us", "fp16_peak_tflops_nominal": FP16_PEAK_TFLOPS,
+            "points": rows}
+
+
 def summarize(trace_dir, bench=None):
     from code_object import _demangle
 
@@ -273,14 +423,17 @@ def main():
     ap.add_argument("--points", default="decode,prefill")
     ap.add_argument("--group-sizes", default="-1,128")
     ap.add_argument("--kv8", action="store_true", help="also time the int8 KV cache (fused_decode_kv8 / fused_qkv_kv8)")
-    ap.add_argument("--paged", action="store_true", help="decode points: time the contiguous and the paged module path alternately")
+    ap.add_argument("--paged", action="store_true", help="decode points: time the contiguous and the paged module path alternately; "
+                    "with --points prefill alone: the paged prefill points, fuse_prefill() off against on")
     ap.add_argument("--block-size", type=int, default=128, help="--paged: keys per block (a power of two in [16, 256])")
     ap.add_argument("--out", default=None)
     ap.add_argument("--summarize", default=None, metavar="TRACE_DIR")
     ap.add_argument("--bench", default=None, metavar="FILE", help="--summarize: the JSON output of the traced run, to label the points")
     a = ap.parse_args()
     if a.summarize:
-        res = summarize(a.summarize, a.bench)
+        res = summarize_prefill(a.summarize, a.bench) if a.paged and a.points == "prefill" else summarize(a.summarize, a.bench)
+    elif a.paged and a.points == "prefill":
+        res = run_paged_prefill([int(v) for v in a.group_sizes.split(",")], kv8=a.kv8, block_size=a.block_size)
     else:
         res = run(a.points.split(","), [int(v) for v in a.group_sizes.split(",")], kv8=a.kv8, paged=a.paged, block_size=a.block_size)
     s = json.dumps(res)
