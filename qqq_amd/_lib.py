@@ -97,6 +97,9 @@ def lib():
     L.qqq_prefill_attn_paged_kv8.restype = ci
     L.qqq_prefill_attn_workspace_bytes.argtypes = [ci, ci, ci]
     L.qqq_prefill_attn_workspace_bytes.restype = ctypes.c_size_t
+    # include/qqq_amd_sample.h
+    L.qqq_sample_tokens.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp]
+    L.qqq_sample_tokens.restype = ci
     L.qqq_amd_abi_version.restype = ci
     L.qqq_amd_last_error.restype = ctypes.c_char_p
     if L.qqq_amd_abi_version() != ABI_VERSION:

@@ -9,7 +9,8 @@ QuantizedLlamaAttention / QuantizedQwen2Attention and Quantized{Llama,Qwen2}Deco
     QuantLlamaAttention      q/k/v GEMMs on the int8 input of QuantRMSNorm -> rope_qkv (RoPE on q and k, k / v into the cache, one launch)
                              -> scaled_dot_product_attention -> dynamic_quant -> o_proj;  opt-in fuse_decode(): one-token steps take
                              decode_attention (split-K over the cache, output int8-quantised) in place of the last two
-    QuantLlamaDecoderLayer   input_layernorm, self_attn, post_attention_layernorm (residual add fused), mlp, final residual add
+    QuantLlamaDecoderLayer   input_layernorm, self_attn, post_attention_layernorm (residual add fused), mlp, final residual add;
+                             forward_chained() leaves that last add to the next layer's norm (qqq_amd/model.py)
 
 The attention core is torch's scaled_dot_product_attention, as in the reference, unless fuse_decode() is on and the step has one token.
 
@@ -404,6 +405,21 @@ class QuantLlamaDecoderLayer(nn.Module):
         # a becomes h = fp16(a + x), torch's `residual + attn_out` (fp16 addition commutes), in the launch that quantises its norm
         mq, ms = self.post_attention_layernorm(x, a)
         return (a + self.mlp.forward_int8(mq, ms)).reshape(hidden.shape)
+
+    def forward_chained(self, delta: torch.Tensor, residual: Optional[torch.Tensor], cache: KVCache, start: int):
+        """The layer on a hidden state handed over as an unformed sum, hidden = residual + delta, returned the same way: (delta, residual)
+        [tokens, hidden] -> (delta', residual') with forward(hidden) = fp16(residual' + delta').  The add that ends forward() is left to
+        the next layer's input_layernorm (or the model's final norm), whose launch forms fp16(residual + delta) anyway: one launch per
+        layer less, and bit for bit the chain of forward() calls, fp16 addition being correctly rounded and commutative.  `residual` is
+        None for the first layer (delta is the hidden state itself) and is otherwise updated in place."""
+        if residual is None:
+            residual = delta.reshape(-1, self.hidden_size)
+            xq, s1 = self.input_layernorm(residual)
+        else:
+            xq, s1 = self.input_layernorm(delta, residual)  # residual becomes the hidden state
+        a = self.self_attn.forward_int8(xq, s1, cache, start)
+        mq, ms = self.post_attention_layernorm(residual, a)  # a becomes h = hidden + attention
+        return self.mlp.forward_int8(mq, ms), a
 
 
 __all__ = ["KVCache", "PagedKVCache", "PagedStep", "QuantLlamaAttention", "QuantLlamaDecoderLayer", "rope_inv_freq", "rope_tables"]

@@ -33,6 +33,7 @@
 //   qqq_kv8.hip.h      the int8 KV cache: the quantising RoPE / cache write and the decode split kernel that reads it
 //   qqq_paged.hip.h    the block-table (paged) KV cache, fp16 and int8: the cache writes by slot and the decode split kernels through a block table
 //   qqq_prefill.hip.h  paged, ragged, causal prefill attention over the block pools (fp16 and int8) and the quantisation of its rows
+//   qqq_sample.hip.h   the fused token sampler: temperature, top-k, top-p and the draw over a batch of fp16 logit rows, one launch
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -69,6 +70,8 @@
 #include "../../include/qqq_amd_paged.h"
 #include "qqq_prefill.hip.h"
 #include "../../include/qqq_amd_prefill.h"
+#include "qqq_sample.hip.h"
+#include "../../include/qqq_amd_sample.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1029,6 +1032,35 @@ extern "C" int qqq_prefill_attn_paged_kv8(const void* q, const void* k_pool, con
   return prefill_attn_paged("qqq_prefill_attn_paged_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, cu_tokens,
                             start_pos, scale, o_fp16, xq, s1, workspace, workspace_bytes, m, b, h, kvh, d, num_blocks, block_size, max_len,
                             dev, stream);
+}
+
+// ---- the fused token sampler (include/qqq_amd_sample.h; kernel in qqq_sample.hip.h): one launch, one workgroup per row, no workspace.
+extern "C" int qqq_sample_tokens(const void* logits, int ld, const void* temperature, const void* top_k, const void* top_p, const void* u,
+                                 void* tokens, int rows, int vocab, int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 0 || rows > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_sample_tokens: rows=%d outside [0, 65535]", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  if (vocab < 1 || vocab > SMP_MAX_VOCAB || ld < vocab || ld % 8 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_sample_tokens: bad shape vocab=%d ld=%d (need 1 <= vocab <= %d, ld >= vocab, ld %% 8 == 0)", vocab, ld,
+             SMP_MAX_VOCAB);
+    return QQQ_ERR_ARG;
+  }
+  if (!logits || !temperature || !top_k || !top_p || !u || !tokens || misaligned(logits, 16) || misaligned(temperature, 4) ||
+      misaligned(top_k, 4) || misaligned(top_p, 4) || misaligned(u, 4) || misaligned(tokens, 8)) {
+    snprintf(g_err, sizeof(g_err), "qqq_sample_tokens: bad argument (every pointer must be non-NULL; logits 16-byte, tokens 8-byte, "
+             "temperature / top_k / top_p / u 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_sample_tokens_kernel, dim3(rows), dim3(SMP_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(logits), ld, static_cast<const float*>(temperature), static_cast<const int*>(top_k),
+                     static_cast<const float*>(top_p), static_cast<const float*>(u), static_cast<long long*>(tokens), vocab);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_sample_tokens_kernel launch");
+  return QQQ_OK;
 }
 
 extern "C" int qqq_quantlinear_forward(const void* x, void* xq, void* s1, const void* B, void* C, void* D,

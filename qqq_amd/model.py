@@ -1,0 +1,232 @@
+"""The whole model around the quantised decoder layers: the reference's QuantizedLlamaModel / QuantizedLlamaForCausalLM and their Qwen2
+twins (QQQ/gptq/models/llama.py, qwen2.py), and the generation loop of its examples/test_model.py over the paged KV cache.
+
+    QuantLlamaModel        embed_tokens (fp16 nn.Embedding) -> layers (QuantLlamaDecoderLayer, chained through forward_chained: the add
+                           that ends a layer is formed by the next layer's norm launch) -> norm (QuantRMSNorm): the normed fp16 rows
+    QuantLlamaForCausalLM  model + lm_head (fp16 nn.Linear, not quantised, as in the reference): logits; generate()
+
+Parameter and buffer names are the reference's (model.embed_tokens.weight, model.layers.N. ..., model.norm.weight, lm_head.weight), so a
+state-dict saved by it loads with load_state_dict(strict=True).
+
+generate() serves prompts of different lengths in one batch over a PagedKVCache: the prompts are prefilled as one packed step, every later
+step feeds each running sequence's last token, tokens come from ops.sample_tokens and stay on the device for the next embedding lookup, a
+sequence that ends frees its blocks at once, and prompts the pool could not hold yet are admitted as blocks come free.
+"""
+from __future__ import annotations
+
+from collections import deque
+from typing import List, Optional, Sequence
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+from .attention import KVCache, QuantLlamaDecoderLayer
+from .blocks import QuantRMSNorm
+from .paged import PagedKVCache, PagedStep
+
+
+class QuantLlamaModel(nn.Module):
+    """Quantized{Llama,Qwen2}Model: embedding, decoder layers, final norm.
+
+    forward(input_ids, cache, step_or_start, all_rows=False) -> the normed fp16 hidden rows.
+      PagedKVCache + PagedStep: input_ids int64 [m], packed as the step says -> [b, hidden], the last token of each sequence (rows
+                                cu_tokens[1:] - 1, selected on the device); all_rows=True -> [m, hidden]
+      KVCache + start position: input_ids int64 [b, s] -> [b, hidden]; all_rows=True -> [b, s, hidden]"""
+
+    def __init__(self, vocab_size: int, num_layers: int, hidden: int, num_heads: int, num_kv_heads: int, intermediate: int, group_size: int,
+                 rms_norm_eps: float = 1e-6, padding_idx: Optional[int] = None, layers: Optional[Sequence[nn.Module]] = None, **layer_kw):
+        super().__init__()
+        self.vocab_size, self.hidden_size = vocab_size, hidden
+        self.embed_tokens = nn.Embedding(vocab_size, hidden, padding_idx, dtype=torch.float16)
+        self.embed_tokens.weight.requires_grad_(False)
+        if layers is None:
+            layers = [QuantLlamaDecoderLayer(hidden, num_heads, num_kv_heads, intermediate, group_size, rms_norm_eps=rms_norm_eps,
+                                             layer_idx=i, **layer_kw) for i in range(num_layers)]
+        self.layers = nn.ModuleList(layers)
+        self.norm = QuantRMSNorm(hidden, eps=rms_norm_eps)
+
+    @classmethod
+    def from_config(cls, config, group_size: int):
+        """The model of a transformers LlamaConfig or Qwen2Config (duck-typed, as QuantLlamaDecoderLayer.from_config, whose refusals
+        propagate)."""
+        layers = [QuantLlamaDecoderLayer.from_config(config, group_size, layer_idx=i) for i in range(config.num_hidden_layers)]
+        heads = config.num_attention_heads
+        return cls(config.vocab_size, config.num_hidden_layers, config.hidden_size, heads, getattr(config, "num_key_value_heads", None) or heads,
+                   config.intermediate_size, group_size, rms_norm_eps=config.rms_norm_eps, padding_idx=getattr(config, "pad_token_id", None),
+                   layers=layers)
+
+    def _each_layer(self, name: str):
+        for layer in self.layers:
+            getattr(layer, name)()
+        return self
+
+    def fuse_decode(self):
+        """fuse_decode() on every layer.  Returns self."""
+        return self._each_layer("fuse_decode")
+
+    def unfuse_decode(self):
+        return self._each_layer("unfuse_decode")
+
+    def fuse_prefill(self):
+        """fuse_prefill() on every layer.  Returns self."""
+        return self._each_layer("fuse_prefill")
+
+    def unfuse_prefill(self):
+        return self._each_layer("unfuse_prefill")
+
+    def fuse_qkv(self):
+        """self_attn.fuse_qkv() on every layer (a second copy of the q / k / v weights).  Returns self."""
+        for layer in self.layers:
+            layer.self_attn.fuse_qkv()
+        return self
+
+    def unfuse_qkv(self):
+        for layer in self.layers:
+            layer.self_attn.unfuse_qkv()
+        return self
+
+    def forward(self, input_ids: torch.Tensor, cache, step_or_start, all_rows: bool = False) -> torch.Tensor:
+        paged = isinstance(cache, PagedKVCache)
+        if paged:
+            if not isinstance(step_or_start, PagedStep):
+                raise RuntimeError("QuantLlamaModel: a PagedKVCache takes the PagedStep of cache.step(seq_ids, counts)")
+            if input_ids.dim() != 1 or input_ids.shape[0] != sum(step_or_start.counts):
+                raise RuntimeError(f"QuantLlamaModel: input_ids must be [m] with the step's m = {sum(step_or_start.counts)} tokens packed in order")
+        elif input_ids.dim() != 2 or input_ids.shape[0] != cache.batch:
+            raise RuntimeError(f"QuantLlamaModel: input_ids must be [batch, s] with batch = {cache.batch} (the cache's)")
+        delta, residual = self.embed_tokens(input_ids).reshape(-1, self.hidden_size), None
+        for layer in self.layers:
+            delta, residual = layer.forward_chained(delta, residual, cache, step_or_start)
+        if not all_rows:  # the last token of every sequence, before the (row-wise) final norm
+            if paged and not step_or_start.decode:
+                rows = step_or_start.cu_tokens[1:].long() - 1
+                delta = delta.index_select(0, rows)
+                residual = residual.index_select(0, rows) if residual is not None else None
+            elif not paged and input_ids.shape[1] > 1:
+                b, s = input_ids.shape
+                delta = delta.reshape(b, s, -1)[:, -1].contiguous()
+                residual = residual.reshape(b, s, -1)[:, -1].contiguous() if residual is not None else None
+        w = self.norm.weight if self.norm.weight.dtype == torch.float16 else self.norm.weight.half()
+        y = ops.rmsnorm_quant(delta, w, self.norm.variance_epsilon, residual=residual, return_y=True)[2]
+        if not paged and all_rows:
+            return y.reshape(input_ids.shape + (self.hidden_size,))
+        return y
+
+
+class QuantLlamaForCausalLM(nn.Module):
+    """Quantized{Llama,Qwen2}ForCausalLM: QuantLlamaModel and an fp16 lm_head.  forward(...) takes QuantLlamaModel.forward's arguments and
+    returns the fp16 logits of the rows it returns."""
+
+    def __init__(self, model: QuantLlamaModel, tie_word_embeddings: bool = False):
+        super().__init__()
+        self.model = model
+        self.vocab_size = model.vocab_size
+        self.lm_head = nn.Linear(model.hidden_size, model.vocab_size, bias=False, dtype=torch.float16)
+        self.lm_head.weight.requires_grad_(False)
+        if tie_word_embeddings:
+            self.lm_head.weight = self.model.embed_tokens.weight
+
+    @classmethod
+    def from_config(cls, config, group_size: int):
+        return cls(QuantLlamaModel.from_config(config, group_size), tie_word_embeddings=bool(getattr(config, "tie_word_embeddings", False)))
+
+    def fuse_decode(self):
+        self.model.fuse_decode()
+        return self
+
+    def fuse_prefill(self):
+        self.model.fuse_prefill()
+        return self
+
+    def fuse_qkv(self):
+        self.model.fuse_qkv()
+        return self
+
+    def forward(self, input_ids: torch.Tensor, cache, step_or_start, all_rows: bool = False) -> torch.Tensor:
+        return F.linear(self.model(input_ids, cache, step_or_start, all_rows), self.lm_head.weight)
+
+    def new_cache(self, num_blocks: int, block_size: int = 16, dtype=torch.float16) -> PagedKVCache:
+        """A PagedKVCache of this model's layer count and head shape on its device."""
+        attn = self.model.layers[0].self_attn
+        return PagedKVCache(len(self.model.layers), num_blocks, attn.num_key_value_heads, attn.head_dim, block_size,
+                            device=self.lm_head.weight.device, dtype=dtype)
+
+    @torch.no_grad()
+    def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                 generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, cache: Optional[PagedKVCache] = None,
+                 block_size: int = 16, dtype=torch.float16) -> List[List[int]]:
+        """Generate up to `max_new_tokens` tokens for every prompt (token lists of any lengths) -> the generated ids per prompt, the
+        eos_token_id that ends a sequence included.
+
+        Every forward pass is followed by ops.sample_tokens with u = torch.rand(rows, generator=generator) -- temperature 0 is greedy --
+        and the sampled ids feed the next step's embedding without leaving the device; they are read back once per pass for the
+        bookkeeping (PagedKVCache.step is host-side anyway).  A sequence that emits eos_token_id or reaches its budget leaves the batch
+        and its blocks are freed at once.  `cache`: a PagedKVCache to run in (it may hold other sequences); default: a new one with room
+        for everything (`block_size`, `dtype`).  A prompt is admitted once the free blocks cover its whole budget on top of what the
+        running sequences may still take, so the pool never runs out mid-sequence; when it cannot hold all prompts at once the rest wait,
+        in order, for blocks to come free.  Newly admitted prompts are prefilled in one packed step of their own and the running rows
+        decode in another: a sequence's tokens do not depend on what else was in the batch.  The random draws do: one torch.rand per pass."""
+        prompts = [list(p) for p in prompts]
+        if any(not p for p in prompts):
+            raise ValueError("generate: every prompt needs at least one token")
+        out: List[List[int]] = [[] for _ in prompts]
+        if max_new_tokens < 1 or not prompts:
+            return out
+        dev = self.lm_head.weight.device
+        need = [-(-(len(p) + max_new_tokens - 1) // (cache.block_size if cache is not None else block_size)) for p in prompts]
+        if cache is None:
+            cache = self.new_cache(sum(need), block_size, dtype)
+        tag = object()  # sequence ids no other user of the cache can hold
+        sid = lambda i: (tag, i)  # noqa: E731
+        waiting, running = deque(range(len(prompts))), []
+        cur = None  # int64 [len(running)] on the device: the running sequences' last tokens
+
+        def sample(ids, step):
+            logits = self(ids, cache, step)
+            u = torch.rand(logits.shape[0], generator=generator, device=logits.device)
+            return ops.sample_tokens(logits, temperature, top_k, top_p, u)
+
+        def settle(seqs, toks):
+            """record a pass's tokens; -> (the sequences that go on, their rows of the pass)"""
+            alive, rows = [], []
+            for row, (i, t) in enumerate(zip(seqs, toks.tolist())):
+                out[i].append(t)
+                if len(out[i]) >= max_new_tokens or (eos_token_id is not None and t == eos_token_id):
+                    cache.free(sid(i))
+                else:
+                    alive.append(i)
+                    rows.append(row)
+            return alive, rows
+
+        def take(toks, rows):
+            return toks if len(rows) == toks.shape[0] else toks[torch.tensor(rows, dtype=torch.int64, device=toks.device)]
+
+        while waiting or running:
+            if running:
+                toks = sample(cur, cache.step([sid(i) for i in running], [1] * len(running)))
+                running, rows = settle(running, toks)
+                cur = take(toks, rows)
+            new = []
+            owed = sum(need[i] - len(cache.blocks(sid(i))) for i in running)  # what the running sequences may still take
+            while waiting and need[waiting[0]] <= cache.free_blocks - owed:
+                i = waiting.popleft()
+                cache.add(sid(i))
+                owed += need[i]
+                new.append(i)
+            if not new:
+                if not running and waiting:
+                    raise RuntimeError(f"generate: the pool's {cache.free_blocks} free blocks cannot hold a prompt that needs "
+                                       f"{need[waiting[0]]} (prompt and budget)")
+                continue
+            ids = torch.tensor([t for i in new for t in prompts[i]], dtype=torch.int64, device=dev)
+            toks = sample(ids, cache.step([sid(i) for i in new], [len(prompts[i]) for i in new]))
+            alive, rows = settle(new, toks)
+            first = take(toks, rows)
+            cur = first if not running else torch.cat([cur, first])
+            running = running + alive
+        return out
+
+
+__all__ = ["QuantLlamaModel", "QuantLlamaForCausalLM"]

@@ -1112,3 +1112,80 @@ def prefill_attention_paged_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_poo
         out = _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16, k_scale,
                                             v_scale)
     return out if return_fp16 else out[:2]
+
+
+# ---- the fused token sampler (include/qqq_amd_sample.h): logits -> next-token ids, one launch for the whole batch
+
+def _sample_param(name, v, rows, dtype, device):
+    # a per-row parameter: a tensor of `rows` entries on the logits' device, or a Python scalar that is broadcast
+    if isinstance(v, torch.Tensor):
+        if v.numel() != rows and v.numel() != 1:
+            raise RuntimeError(f"sample_tokens: {name} holds {v.numel()} entries, the logits have {rows} rows")
+        if v.device != device:
+            raise RuntimeError(f"sample_tokens: {name} must be on the logits' device")
+        v = v.reshape(-1).to(dtype)
+        return (v.expand(rows) if v.numel() != rows else v).contiguous()
+    return torch.full((rows,), v, dtype=dtype, device=device)
+
+
+def _sample_tokens_impl(logits, temperature, top_k, top_p, u):
+    ts = (logits, temperature, top_k, top_p, u)
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError("sample_tokens: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != logits.device for t in ts):
+        raise RuntimeError("sample_tokens: every tensor must be on the same GPU")
+    if logits.dtype != torch.float16 or logits.dim() != 2:
+        raise RuntimeError("sample_tokens: logits must be fp16 [rows, vocab]")
+    rows, vocab = logits.shape
+    if temperature.dtype != torch.float32 or top_p.dtype != torch.float32 or u.dtype != torch.float32 or top_k.dtype != torch.int32:
+        raise RuntimeError("sample_tokens: temperature, top_p and u must be f32, top_k int32")
+    if any(t.numel() != rows for t in ts[1:]):
+        raise RuntimeError(f"sample_tokens: temperature, top_k, top_p and u must hold one entry per row ({rows})")
+    if vocab < 1 or vocab > 262144 or rows > 65535:
+        raise RuntimeError(f"sample_tokens: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows <= 65535")
+    tokens = torch.empty((rows,), dtype=torch.int64, device=logits.device)
+    if rows == 0:
+        return tokens
+    # a row-strided view (the first vocab columns of a padded head output) is taken in place; anything else is copied into such rows
+    if logits.stride(1) != 1 or logits.stride(0) < vocab or logits.stride(0) % 8 or logits.data_ptr() % 16:
+        rows8 = torch.empty((rows, vocab + (-vocab) % 8), dtype=torch.float16, device=logits.device)
+        rows8[:, :vocab] = logits
+        logits = rows8[:, :vocab]
+    err = _lib.lib().qqq_sample_tokens(_ptr(logits), logits.stride(0), _ptr(temperature.contiguous()), _ptr(top_k.contiguous()),
+                                       _ptr(top_p.contiguous()), _ptr(u.contiguous()), _ptr(tokens), rows, vocab,
+                                       logits.device.index or 0, _stream_for(logits))
+    if err:
+        raise RuntimeError(f"qqq_amd: sample_tokens error {err}: {_lib.last_error()}")
+    return tokens
+
+
+@torch.library.custom_op("qqq_amd::sample_tokens", mutates_args=())
+def _sample_tokens_op(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+                      u: torch.Tensor) -> torch.Tensor:
+    return _sample_tokens_impl(logits, temperature, top_k, top_p, u)
+
+
+@_sample_tokens_op.register_fake
+def _(logits, temperature, top_k, top_p, u):
+    return logits.new_empty((logits.shape[0],), dtype=torch.int64)
+
+
+def sample_tokens(logits: torch.Tensor, temperature, top_k, top_p, u: torch.Tensor) -> torch.Tensor:
+    """The next token of every row of fp16 logits [rows, vocab]: temperature, top-k, top-p and the draw in one launch -> int64 [rows].
+
+    temperature  f32 [rows] or a float: <= 0 (or NaN) is greedy, the lowest index of the maximum
+    top_k        int32 [rows] or an int: <= 0 or >= vocab keeps every token, 1 is greedy; ties at the k-th largest value all stay
+    top_p        f32 [rows] or a float: >= 1 keeps the top-k set; equal logits at the cut stay or go together
+    u            f32 [rows]: one uniform variate in [0, 1) per row (torch.rand); the op holds no random state of its own
+    The exact semantics of a row are stated in include/qqq_amd_sample.h.  Nothing is read on the host and the launch size depends on the
+    shape alone, so a captured graph replays with other contents.  A view whose rows are `vocab` columns of a wider, 16-byte aligned
+    fp16 matrix (row stride a multiple of 8) is read in place; its other columns are never touched."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(u, torch.Tensor) or logits.dim() != 2:
+        raise RuntimeError("sample_tokens: logits must be an fp16 [rows, vocab] tensor and u an f32 [rows] tensor")
+    rows, dev = logits.shape[0], logits.device
+    temperature = _sample_param("temperature", temperature, rows, torch.float32, dev)
+    top_k = _sample_param("top_k", top_k, rows, torch.int32, dev)
+    top_p = _sample_param("top_p", top_p, rows, torch.float32, dev)
+    if _compiling(logits, temperature, top_k, top_p, u):
+        return _sample_tokens_op(logits, temperature, top_k, top_p, u)
+    return _sample_tokens_impl(logits, temperature, top_k, top_p, u)

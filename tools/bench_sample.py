@@ -1,0 +1,135 @@
+#!/usr/bin/env python3
+"""ops.sample_tokens against a torch composition of the same semantics, on the same GPU.
+
+    fused   ops.sample_tokens(logits, T, k, p, u): one launch
+    torch   logits.float() / T; torch.topk's k-th value as a threshold (ties kept); softmax; a full sort for top-p, cumsum, the cut as a
+            threshold on the probability (ties together), renormalise; cumsum in token order and the first index above u * total.  The
+            parameters are the same for every row, which is the cheap case for torch (one k for torch.topk, no per-row gather).
+Both read one fp16 [rows, vocab] tensor and write int64 [rows].  The two are timed alternately in one process, ROUNDS times: CALLS calls each
+per round, every call between two device events on an otherwise idle stream (eager), then the same replayed from a hipGraph each (graph).
+A round's value is the median of its calls; the JSON keeps every round and reports the median of rounds, their min / max as the spread, and
+torch / fused.  Logits are fp16(4 N(0, 1)), T = 0.8, k = 50, p = 0.9; `--mode` picks which cuts are on.
+
+    python tools/bench_sample.py [--out profiles/sample_bench.json] [--rows 1,16,64] [--vocab 32000,128256,151936]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+ROUNDS, CALLS, WARMUP = 5, 20, 5
+MODES = {"sample": (0.8, 0, 1.0), "top_k": (0.8, 50, 1.0), "top_p": (0.8, 0, 0.9), "top_k_top_p": (0.8, 50, 0.9)}
+
+
+def torch_sample(logits, T, k, p, u):
+    import torch
+
+    x = logits.float() / T
+    if k > 0:
+        kth = torch.topk(x, k, dim=-1).values[:, -1:]
+        x = x.masked_fill(x < kth, float("-inf"))
+    probs = torch.softmax(x, dim=-1)
+    if p < 1.0:
+        srt, _ = torch.sort(probs, dim=-1)  # ascending: the mass of everything no more probable
+        cum = srt.cumsum(dim=-1)
+        first = (cum > (1.0 - p)).int().argmax(dim=-1, keepdim=True)  # the least probable value that stays
+        probs = probs.masked_fill(probs < srt.gather(1, first), 0.0)
+    c = probs.cumsum(dim=-1)
+    return (c > u[:, None] * c[:, -1:]).int().argmax(dim=-1)
+
+
+def time_calls(fn, n):
+    import torch
+
+    out = []
+    for _ in range(n):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) * 1e3)
+    return out
+
+
+def capture(fn):
+    import torch
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    return graph
+
+
+def point(rows, vocab, mode, dev):
+    import torch
+
+    from qqq_amd import ops
+
+    T, k, p = MODES[mode]
+    g = torch.Generator(device=dev).manual_seed(vocab + rows)
+    logits = (4.0 * torch.randn((rows, vocab), generator=g, device=dev)).half()
+    u = torch.rand(rows, generator=g, device=dev)
+    Tt, kt, pt = (torch.full((rows,), v, dtype=dt, device=dev) for v, dt in ((T, torch.float32), (k, torch.int32), (p, torch.float32)))
+    fns = {"fused": lambda: ops.sample_tokens(logits, Tt, kt, pt, u), "torch": lambda: torch_sample(logits, T, k, p, u)}
+    same = float((fns["fused"]() == fns["torch"]()).float().mean())  # f32 against exact sums: a row may differ at a cut or an edge
+    res = {"rows": rows, "vocab": vocab, "mode": mode, "rows_equal_fraction": same}
+    for how in ("eager", "graph"):
+        run = fns if how == "eager" else {n: capture(f).replay for n, f in fns.items()}
+        for f in run.values():
+            for _ in range(WARMUP):
+                f()
+        torch.cuda.synchronize()
+        rounds = {n: [] for n in run}
+        for _ in range(ROUNDS):
+            for n, f in run.items():
+                rounds[n].append(statistics.median(time_calls(f, CALLS)))
+        r = {}
+        for n, v in rounds.items():
+            r[n] = {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
+                    "rounds_us": [round(x, 2) for x in v]}
+        r["torch_over_fused"] = round(r["torch"]["median_us"] / r["fused"]["median_us"], 2)
+        r["torch_over_fused_range"] = [round(r["torch"]["min_us"] / r["fused"]["max_us"], 2), round(r["torch"]["max_us"] / r["fused"]["min_us"], 2)]
+        res[how] = r
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sample_bench.json"))
+    ap.add_argument("--rows", default="1,16,64")
+    ap.add_argument("--vocab", default="32000,128256,151936")
+    ap.add_argument("--modes", default="sample,top_k_top_p")
+    args = ap.parse_args()
+    import torch
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_sample.py needs a GPU: a timing taken elsewhere says nothing")
+    dev = torch.device("cuda:0")
+    points = [point(r, v, m, dev) for m in args.modes.split(",") for v in map(int, args.vocab.split(",")) for r in map(int, args.rows.split(","))]
+    notes = [f"{p['mode']} rows={p['rows']} vocab={p['vocab']} {how}: the fused op does not win ({p[how]['torch_over_fused']}x)"
+             for p in points for how in ("eager", "graph") if p[how]["torch_over_fused_range"][0] <= 1.0]
+    out = {"tool": "tools/bench_sample.py", "device": torch.cuda.get_device_name(0), "rounds": ROUNDS, "calls_per_round": CALLS,
+           "modes": {m: dict(zip(("temperature", "top_k", "top_p"), MODES[m])) for m in args.modes.split(",")}, "points": points,
+           "notes": notes or ["the fused op wins at every point, also at the unfavourable ends of both spreads"]}
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"{p['mode']:12s} rows {p['rows']:3d} vocab {p['vocab']:6d}: " + "  ".join(
+            f"{how} fused {p[how]['fused']['median_us']:8.1f} us torch {p[how]['torch']['median_us']:8.1f} us ({p[how]['torch_over_fused']}x)"
+            for how in ("eager", "graph")))
+
+
+if __name__ == "__main__":
+    main()
