@@ -21,6 +21,9 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     PagedKVCache, PagedStep                                                        # block pools + host-side allocator; qqq_amd/paged.py
     sample_tokens(logits, temperature, top_k, top_p, u)                             # temperature / top-k / top-p / draw for a batch, one launch
     QuantLlamaModel, QuantLlamaForCausalLM                                         # the whole model and generate(); qqq_amd/model.py
+    sample_advance(logits, ..., u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out, block_size)  # sample_tokens + the decode
+                                                                                    # loop's per-row bookkeeping on the device, one launch
+    DecodeLoop(lm, cache, rows, max_len)                                            # device-resident decode loop, one graph per step; qqq_amd/serve.py
 """
 from .ops import (  # noqa: F401
     decode_attention,
@@ -43,6 +46,7 @@ from .ops import (  # noqa: F401
     rope_qkv_kv8,
     rope_qkv_paged,
     rope_qkv_paged_kv8,
+    sample_advance,
     sample_tokens,
     silu_mul_quant,
 )
@@ -51,10 +55,11 @@ from .blocks import QuantLlamaMLP, QuantRMSNorm  # noqa: F401
 from .attention import KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer  # noqa: F401
 from .paged import PagedKVCache, PagedStep  # noqa: F401
 from .model import QuantLlamaForCausalLM, QuantLlamaModel  # noqa: F401
+from .serve import DecodeLoop  # noqa: F401
 
 __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_int8", "mul", "marlin_qqq_gemm", "dynamic_quant", "quantlinear_forward",
            "rmsnorm_quant", "silu_mul_quant", "QuantLinear", "fuse_quant_linears", "QuantRMSNorm", "QuantLlamaMLP",
            "rope_qkv", "decode_attention", "rope_qkv_kv8", "decode_attention_kv8", "rope_qkv_paged",
            "decode_attention_paged", "rope_qkv_paged_kv8", "decode_attention_paged_kv8", "prefill_attention_paged",
            "prefill_attention_paged_kv8", "PagedKVCache", "PagedStep", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer",
-           "sample_tokens", "QuantLlamaModel", "QuantLlamaForCausalLM"]
+           "sample_tokens", "QuantLlamaModel", "QuantLlamaForCausalLM", "sample_advance", "DecodeLoop"]

@@ -145,16 +145,26 @@ __device__ __forceinline__ void qqq_sample_hist(const unsigned short* __restrict
   }
 }
 
-__global__ __launch_bounds__(SMP_NT) void qqq_sample_tokens_kernel(const unsigned short* __restrict__ logits, const int ld,
-                                                                   const float* __restrict__ temperature, const int* __restrict__ top_k,
-                                                                   const float* __restrict__ top_p, const float* __restrict__ uu,
-                                                                   long long* __restrict__ tokens, const int vocab) {
+// Where a row's variate comes from and what the one lane that ends up holding the row's token does with it: qqq_sample_tokens reads u[r]
+// and stores the token; the decode loop's step kernel (qqq_step.hip.h) indexes u by the row's tick and advances the row's state.
+struct qqq_sample_store {
+  const float* __restrict__ uu;
+  long long* __restrict__ tokens;
+  __device__ __forceinline__ float variate(const int r) const { return uu[r]; }
+  __device__ __forceinline__ void operator()(const int r, const long long tok) const { tokens[r] = tok; }
+};
+
+// The sampler of one row by one workgroup, shared by every kernel that draws a token: every lane calls emit.variate(r) in front of the
+// first barrier, and `emit(r, token)` is called exactly once, by one lane, behind it.
+template <class Emit>
+__device__ __forceinline__ void qqq_sample_row(const unsigned short* __restrict__ logits, const int ld, const float* __restrict__ temperature,
+                                               const int* __restrict__ top_k, const float* __restrict__ top_p, const int vocab, const int r,
+                                               const Emit emit) {
   __shared__ unsigned hc[256 * SMP_COPIES];
   __shared__ qqq_u64 hm[256 * SMP_COPIES];
   __shared__ qqq_u64 cnt[256], m1[256], m2[256];
   __shared__ qqq_u64 red[SMP_WAVES];
 
-  const int r = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -163,7 +173,7 @@ __global__ __launch_bounds__(SMP_NT) void qqq_sample_tokens_kernel(const unsigne
   const float T = temperature[r];
   const int k = top_k[r];
   const float p = top_p[r];
-  const float u = uu[r];
+  const float u = emit.variate(r);
 
   // ---- walk 0: the maximum, its lowest index, and whether anything is finite
   qqq_u64 best = 0ull;
@@ -190,11 +200,11 @@ __global__ __launch_bounds__(SMP_NT) void qqq_sample_tokens_kernel(const unsigne
   const unsigned kmax = (unsigned)(best >> 32);
   const long long imax = (long long)(0xffffffffu - (unsigned)(best & 0xffffffffull));
   if (!finite) {
-    if (tid == 0) tokens[r] = 0;
+    if (tid == 0) emit(r, 0ll);
     return;
   }
   if (!(T > 0.f) || k == 1) {
-    if (tid == 0) tokens[r] = imax;
+    if (tid == 0) emit(r, imax);
     return;
   }
   const bool topk = k > 1 && k < vocab;
@@ -359,13 +369,20 @@ __global__ __launch_bounds__(SMP_NT) void qqq_sample_tokens_kernel(const unsigne
           acc += f[e];
           if (tok < 0 && acc > target) tok = 8 * v + e;
         }
-        tokens[r] = (long long)tok;
+        emit(r, (long long)tok);
       }
       return;
     }
     run += tot;
   }
-  if (lane == 0) tokens[r] = imax;  // not reached: the sums are exact, so the owning wave finds its token
+  if (lane == 0) emit(r, imax);  // not reached: the sums are exact, so the owning wave finds its token
+}
+
+__global__ __launch_bounds__(SMP_NT) void qqq_sample_tokens_kernel(const unsigned short* __restrict__ logits, const int ld,
+                                                                   const float* __restrict__ temperature, const int* __restrict__ top_k,
+                                                                   const float* __restrict__ top_p, const float* __restrict__ uu,
+                                                                   long long* __restrict__ tokens, const int vocab) {
+  qqq_sample_row(logits, ld, temperature, top_k, top_p, vocab, blockIdx.x, qqq_sample_store{uu, tokens});
 }
 
 #endif  // QQQ_AMD_QQQ_SAMPLE_HIP_H_

@@ -34,6 +34,7 @@
 //   qqq_paged.hip.h    the block-table (paged) KV cache, fp16 and int8: the cache writes by slot and the decode split kernels through a block table
 //   qqq_prefill.hip.h  paged, ragged, causal prefill attention over the block pools (fp16 and int8) and the quantisation of its rows
 //   qqq_sample.hip.h   the fused token sampler: temperature, top-k, top-p and the draw over a batch of fp16 logit rows, one launch
+//   qqq_step.hip.h     the decode loop's step: that sampler with an epilogue that advances each row's decode state on the device
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -72,6 +73,8 @@
 #include "../../include/qqq_amd_prefill.h"
 #include "qqq_sample.hip.h"
 #include "../../include/qqq_amd_sample.h"
+#include "qqq_step.hip.h"
+#include "../../include/qqq_amd_step.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1060,6 +1063,59 @@ extern "C" int qqq_sample_tokens(const void* logits, int ld, const void* tempera
                      static_cast<const float*>(top_p), static_cast<const float*>(u), static_cast<long long*>(tokens), vocab);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_sample_tokens_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- the decode loop's sample-and-advance step (include/qqq_amd_step.h; kernel in qqq_step.hip.h): the sampler's launch with an epilogue.
+extern "C" int qqq_sample_advance(const void* logits, int ld, const void* temperature, const void* top_k, const void* top_p, const void* u,
+                                  int u_stride, void* tick, void* ids, void* pos, void* slots, const void* block_table, int table_stride,
+                                  void* remaining, const void* eos, void* out, int out_stride, void* n_out, int rows, int vocab,
+                                  int block_size, int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 0 || rows > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_sample_advance: rows=%d outside [0, 65535]", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  if (vocab < 1 || vocab > SMP_MAX_VOCAB || ld < vocab || ld % 8 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_sample_advance: bad shape vocab=%d ld=%d (need 1 <= vocab <= %d, ld >= vocab, ld %% 8 == 0)", vocab,
+             ld, SMP_MAX_VOCAB);
+    return QQQ_ERR_ARG;
+  }
+  if (block_size < 16 || block_size > 256 || (block_size & (block_size - 1)) || table_stride < 1 || out_stride < 1 || u_stride < 1) {
+    snprintf(g_err, sizeof(g_err), "qqq_sample_advance: bad shape block_size=%d table_stride=%d out_stride=%d u_stride=%d (need block_size a "
+             "power of two in [16, 256] and every stride >= 1)", block_size, table_stride, out_stride, u_stride);
+    return QQQ_ERR_ARG;
+  }
+  if (!logits || !temperature || !top_k || !top_p || !u || !tick || !ids || !pos || !slots || !block_table || !remaining || !eos || !out ||
+      !n_out || misaligned(logits, 16) || misaligned(temperature, 4) || misaligned(top_k, 4) || misaligned(top_p, 4) || misaligned(u, 4) ||
+      misaligned(tick, 4) || misaligned(ids, 8) || misaligned(pos, 8) || misaligned(slots, 8) || misaligned(block_table, 4) ||
+      misaligned(remaining, 4) || misaligned(eos, 4) || misaligned(out, 8) || misaligned(n_out, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_sample_advance: bad argument (every pointer must be non-NULL; logits 16-byte, ids / pos / slots / out "
+             "8-byte, everything else 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_step_emit st;
+  st.uu = static_cast<const float*>(u);
+  st.u_stride = u_stride;
+  st.tick = static_cast<int*>(tick);
+  st.ids = static_cast<long long*>(ids);
+  st.pos = static_cast<long long*>(pos);
+  st.slots = static_cast<long long*>(slots);
+  st.block_table = static_cast<const int*>(block_table);
+  st.remaining = static_cast<int*>(remaining);
+  st.eos = static_cast<const int*>(eos);
+  st.out = static_cast<long long*>(out);
+  st.n_out = static_cast<int*>(n_out);
+  st.table_stride = table_stride;
+  st.out_stride = out_stride;
+  st.block_shift = __builtin_ctz((unsigned)block_size);
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_step_advance_kernel, dim3(rows), dim3(SMP_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(logits), ld, static_cast<const float*>(temperature), static_cast<const int*>(top_k),
+                     static_cast<const float*>(top_p), st, vocab);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_step_advance_kernel launch");
   return QQQ_OK;
 }
 

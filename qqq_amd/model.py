@@ -156,7 +156,7 @@ class QuantLlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, cache: Optional[PagedKVCache] = None,
-                 block_size: int = 16, dtype=torch.float16) -> List[List[int]]:
+                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False) -> List[List[int]]:
         """Generate up to `max_new_tokens` tokens for every prompt (token lists of any lengths) -> the generated ids per prompt, the
         eos_token_id that ends a sequence included.
 
@@ -167,7 +167,11 @@ class QuantLlamaForCausalLM(nn.Module):
         for everything (`block_size`, `dtype`).  A prompt is admitted once the free blocks cover its whole budget on top of what the
         running sequences may still take, so the pool never runs out mid-sequence; when it cannot hold all prompts at once the rest wait,
         in order, for blocks to come free.  Newly admitted prompts are prefilled in one packed step of their own and the running rows
-        decode in another: a sequence's tokens do not depend on what else was in the batch.  The random draws do: one torch.rand per pass."""
+        decode in another: a sequence's tokens do not depend on what else was in the batch.  The random draws do: one torch.rand per pass.
+
+        device_loop=True hands the prompts to a DecodeLoop (qqq_amd/serve.py) of min(len(prompts), 64) rows, sized for the longest budget
+        rounded up to a block: the decode steps replay from one captured graph and the host syncs once per several tokens.  Greedy tokens
+        are the same; the random draws are the loop's (one torch.rand(rows, u_stride) per u_stride steps)."""
         prompts = [list(p) for p in prompts]
         if any(not p for p in prompts):
             raise ValueError("generate: every prompt needs at least one token")
@@ -178,6 +182,11 @@ class QuantLlamaForCausalLM(nn.Module):
         need = [-(-(len(p) + max_new_tokens - 1) // (cache.block_size if cache is not None else block_size)) for p in prompts]
         if cache is None:
             cache = self.new_cache(sum(need), block_size, dtype)
+        if device_loop:
+            from .serve import DecodeLoop
+
+            loop = DecodeLoop(self, cache, rows=min(len(prompts), 64), max_len=max(need) * cache.block_size)
+            return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id)
         tag = object()  # sequence ids no other user of the cache can hold
         sid = lambda i: (tag, i)  # noqa: E731
         waiting, running = deque(range(len(prompts))), []

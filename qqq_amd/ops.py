@@ -1116,13 +1116,13 @@ def prefill_attention_paged_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_poo
 
 # ---- the fused token sampler (include/qqq_amd_sample.h): logits -> next-token ids, one launch for the whole batch
 
-def _sample_param(name, v, rows, dtype, device):
+def _sample_param(name, v, rows, dtype, device, op="sample_tokens"):
     # a per-row parameter: a tensor of `rows` entries on the logits' device, or a Python scalar that is broadcast
     if isinstance(v, torch.Tensor):
         if v.numel() != rows and v.numel() != 1:
-            raise RuntimeError(f"sample_tokens: {name} holds {v.numel()} entries, the logits have {rows} rows")
+            raise RuntimeError(f"{op}: {name} holds {v.numel()} entries, the logits have {rows} rows")
         if v.device != device:
-            raise RuntimeError(f"sample_tokens: {name} must be on the logits' device")
+            raise RuntimeError(f"{op}: {name} must be on the logits' device")
         v = v.reshape(-1).to(dtype)
         return (v.expand(rows) if v.numel() != rows else v).contiguous()
     return torch.full((rows,), v, dtype=dtype, device=device)
@@ -1189,3 +1189,103 @@ def sample_tokens(logits: torch.Tensor, temperature, top_k, top_p, u: torch.Tens
     if _compiling(logits, temperature, top_k, top_p, u):
         return _sample_tokens_op(logits, temperature, top_k, top_p, u)
     return _sample_tokens_impl(logits, temperature, top_k, top_p, u)
+
+
+# ---- the decode loop's sample-and-advance step (include/qqq_amd_step.h): sample_tokens with an epilogue that advances every row's state
+
+_ADVANCE_STATE = (("tick", torch.int32), ("ids", torch.int64), ("pos", torch.int64), ("slots", torch.int64), ("remaining", torch.int32),
+                  ("eos", torch.int32), ("n_out", torch.int32))
+
+
+def _sample_advance_check(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out, block_size):
+    # the checks that need no device: dtypes and shapes (shared by the launch and the fake implementation)
+    if logits.dtype != torch.float16 or logits.dim() != 2:
+        raise RuntimeError("sample_advance: logits must be fp16 [rows, vocab]")
+    rows, vocab = logits.shape
+    if temperature.dtype != torch.float32 or top_p.dtype != torch.float32 or u.dtype != torch.float32 or top_k.dtype != torch.int32:
+        raise RuntimeError("sample_advance: temperature, top_p and u must be f32, top_k int32")
+    if any(t.numel() != rows for t in (temperature, top_k, top_p)):
+        raise RuntimeError(f"sample_advance: temperature, top_k and top_p must hold one entry per row ({rows})")
+    if u.dim() != 2 or u.shape[0] != rows or u.shape[1] < 1:
+        raise RuntimeError(f"sample_advance: u must be f32 [{rows}, u_stride] with u_stride >= 1, not {tuple(u.shape)}")
+    state = dict(tick=tick, ids=ids, pos=pos, slots=slots, remaining=remaining, eos=eos, n_out=n_out)
+    for name, dtype in _ADVANCE_STATE:
+        t = state[name]
+        if t.dtype != dtype or t.dim() != 1 or t.shape[0] != rows:
+            raise RuntimeError(f"sample_advance: {name} must be {str(dtype).replace('torch.', '')} [{rows}], not "
+                               f"{str(t.dtype).replace('torch.', '')} {tuple(t.shape)}")
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != rows or block_table.shape[1] < 1:
+        raise RuntimeError(f"sample_advance: block_table must be int32 [{rows}, blocks per row >= 1], not {tuple(block_table.shape)}")
+    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != rows or out.shape[1] < 1:
+        raise RuntimeError(f"sample_advance: out must be int64 [{rows}, out_stride >= 1], not {tuple(out.shape)}")
+    if block_size not in (16, 32, 64, 128, 256):
+        raise RuntimeError(f"sample_advance: block_size must be a power of two in [16, 256], not {block_size}")
+    if vocab < 1 or vocab > 262144 or rows > 65535:
+        raise RuntimeError(f"sample_advance: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows <= 65535")
+    return rows, vocab
+
+
+def _sample_advance_impl(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out, block_size):
+    ts = (logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out)
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError("sample_advance: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != logits.device for t in ts):
+        raise RuntimeError("sample_advance: every tensor must be on the same GPU")
+    rows, vocab = _sample_advance_check(*ts, block_size)
+    if rows == 0:
+        return
+    # everything written is written in place: no copy may stand in for a state array
+    for name, t in (("u", u), ("tick", tick), ("ids", ids), ("pos", pos), ("slots", slots), ("block_table", block_table),
+                    ("remaining", remaining), ("eos", eos), ("out", out), ("n_out", n_out)):
+        if not t.is_contiguous():
+            raise RuntimeError(f"sample_advance: {name} must be contiguous (the state is updated in place)")
+    if logits.stride(1) != 1 or logits.stride(0) < vocab or logits.stride(0) % 8 or logits.data_ptr() % 16:
+        rows8 = torch.empty((rows, vocab + (-vocab) % 8), dtype=torch.float16, device=logits.device)
+        rows8[:, :vocab] = logits
+        logits = rows8[:, :vocab]
+    err = _lib.lib().qqq_sample_advance(_ptr(logits), logits.stride(0), _ptr(temperature.contiguous()), _ptr(top_k.contiguous()),
+                                        _ptr(top_p.contiguous()), _ptr(u), u.shape[1], _ptr(tick), _ptr(ids), _ptr(pos), _ptr(slots),
+                                        _ptr(block_table), block_table.shape[1], _ptr(remaining), _ptr(eos), _ptr(out), out.shape[1],
+                                        _ptr(n_out), rows, vocab, block_size, logits.device.index or 0, _stream_for(logits))
+    if err:
+        raise RuntimeError(f"qqq_amd: sample_advance error {err}: {_lib.last_error()}")
+
+
+@torch.library.custom_op("qqq_amd::sample_advance", mutates_args=("tick", "ids", "pos", "slots", "remaining", "out", "n_out"))
+def _sample_advance_op(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, u: torch.Tensor,
+                       tick: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor, block_table: torch.Tensor,
+                       remaining: torch.Tensor, eos: torch.Tensor, out: torch.Tensor, n_out: torch.Tensor, block_size: int) -> None:
+    _sample_advance_impl(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out, block_size)
+
+
+@_sample_advance_op.register_fake
+def _(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out, block_size):
+    _sample_advance_check(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out, block_size)
+
+
+def sample_advance(logits: torch.Tensor, temperature, top_k, top_p, u: torch.Tensor, tick: torch.Tensor, ids: torch.Tensor,
+                   pos: torch.Tensor, slots: torch.Tensor, block_table: torch.Tensor, remaining: torch.Tensor, eos: torch.Tensor,
+                   out: torch.Tensor, n_out: torch.Tensor, block_size: int) -> None:
+    """One decode step's sampling and bookkeeping in one launch: sample_tokens on every row of fp16 logits [rows, vocab], then -- on the
+    device -- record the token, check eos and budget, and move the row to its next position and cache slot, or retire it.  Returns nothing;
+    tick, ids, pos, slots, remaining, out and n_out are updated in place.
+
+    temperature, top_k, top_p   as for sample_tokens (a tensor per row or a scalar)
+    u            f32 [rows, u_stride]: row r draws with u[r, tick[r] % u_stride];  tick  int32 [rows], + 1 per call for every row
+    ids, pos, slots   int64 [rows]: the next step's input token, its position (-1: an idle row) and its cache slot (-1 when idle)
+    block_table  int32 [rows, W], only read;  block_size  the pool's (a power of two in [16, 256])
+    remaining    int32 [rows]: tokens the row may still emit, 0 for an idle row;  eos  int32 [rows]: the row's eos id, -1 for none
+    out          int64 [rows, out_stride], n_out int32 [rows]: the emitted tokens and their number
+    A row that draws its eos, uses up its budget, or would leave its block table or out retires: ids 0, pos -1, slots -1, remaining 0.  The
+    exact semantics of a row are stated in include/qqq_amd_step.h.  Nothing is read on the host and the launch size depends on the shape
+    alone, so a decode step that ends in this call replays from a captured graph while rows finish and join."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(u, torch.Tensor) or logits.dim() != 2:
+        raise RuntimeError("sample_advance: logits must be an fp16 [rows, vocab] tensor and u an f32 [rows, u_stride] tensor")
+    rows, dev = logits.shape[0], logits.device
+    temperature = _sample_param("temperature", temperature, rows, torch.float32, dev, "sample_advance")
+    top_k = _sample_param("top_k", top_k, rows, torch.int32, dev, "sample_advance")
+    top_p = _sample_param("top_p", top_p, rows, torch.float32, dev, "sample_advance")
+    args = (logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out)
+    if _compiling(*args):
+        return _sample_advance_op(*args, int(block_size))
+    return _sample_advance_impl(*args, int(block_size))

@@ -3,7 +3,7 @@ with per-sequence lengths, and the per-step metadata the paged ops read (ops.rop
 prefill_attention_paged and their _kv8 forms).
 
     PagedKVCache   k[layer], v[layer] of shape [num_blocks, num_kv_heads, block_size, head_dim] (fp16 or int8; an int8 pool with
-                   k_scale[layer], v_scale[layer] [num_blocks, num_kv_heads, block_size]); add / free / step / gather
+                   k_scale[layer], v_scale[layer] [num_blocks, num_kv_heads, block_size]); add / free / reserve / step / advance / gather
     PagedStep      what one forward pass over a packed batch of sequences needs, built once on the host and shared by all layers
 
 Sequences arrive and finish at different times, have different lengths, and a finished sequence's blocks serve the next one.  The allocator
@@ -107,6 +107,30 @@ class PagedKVCache:
 
     def blocks(self, seq_id) -> List[int]:
         return list(self._blocks[seq_id])
+
+    def reserve(self, seq_id, length: int) -> None:
+        """Take blocks from the free list until the sequence owns the ceil(length / block_size) blocks that `length` keys need (nothing
+        if it owns them already).  The sequence's length does not change: step() takes new blocks only beyond what is owned, and free()
+        returns reserved blocks, used or not.  Raises, and changes nothing, when the pool cannot cover it."""
+        if seq_id not in self._blocks:
+            raise KeyError(f"PagedKVCache.reserve: no sequence {seq_id!r}")
+        need = -(-int(length) // self.block_size) - len(self._blocks[seq_id])
+        if need > len(self._free):
+            raise RuntimeError(f"PagedKVCache.reserve: the pool is exhausted ({need} blocks needed, {len(self._free)} free)")
+        for _ in range(need):
+            self._blocks[seq_id].append(self._free.pop())
+
+    def advance(self, seq_id, n: int) -> None:
+        """Add `n` keys that were written on the device (through the sequence's block table, by a loop the host did not follow token by
+        token) to the sequence's length, so that gather() and a later step() see them.  Raises, and changes nothing, if the blocks the
+        sequence owns do not hold them: reserve() first."""
+        if seq_id not in self._blocks:
+            raise KeyError(f"PagedKVCache.advance: no sequence {seq_id!r}")
+        n = int(n)
+        owned = len(self._blocks[seq_id]) * self.block_size
+        if n < 0 or self._len[seq_id] + n > owned:
+            raise ValueError(f"PagedKVCache.advance: {self._len[seq_id]} + {n} keys outside the {owned} the sequence's blocks hold")
+        self._len[seq_id] += n
 
     def step(self, seq_ids: Sequence, counts: Sequence[int]) -> PagedStep:
         """Reserve blocks for counts[i] new tokens of sequence seq_ids[i], advance the lengths and return the step's metadata (device

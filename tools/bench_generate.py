@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Generation end to end, decode time per token, three ways in one process: a Llama-2-7B-shaped model of four layers (hidden 4096, 32 heads
+of 128, intermediate 11008, vocab 32000, per-channel W4A8, fuse_qkv()) over a paged fp16 cache, prompts of 128 tokens, 128 new tokens, greedy.
+
+    generate        QuantLlamaForCausalLM.generate(device_loop=False): a host-built step, eager launches and a tolist() per token
+    loop eager      DecodeLoop(graph=False): the step's metadata on the device, eager launches, a host sync every `sync_every` tokens
+    loop graph      DecodeLoop(graph=True): the same, the step replayed from one captured graph
+
+A round times every variant once, alternately.  A variant's value in a round is (wall time of a run with NEW tokens - wall time of a run with
+1 token) / (NEW - 1): the prefill and the first token are in both runs, the NEW - 1 decode steps in one.  Both runs end in a device
+synchronise.  The capture happens in the warm-up, outside the timed runs.  Written: the per-round values, their median, min and max, the
+ratio generate / loop graph, and at batch 1 whether the captured loop's median lies below generate's by more than generate's own
+round-to-round spread (max - min).
+
+    python tools/bench_generate.py [--batch 1,16] [--rounds 5] [--baseline-only] [--out profiles/decode_loop_bench.json]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+PROMPT, NEW, BS, LAYERS, SYNC_EVERY = 128, 128, 16, 4, 8
+
+
+def point(lm, batch, rounds, baseline_only, dev):
+    import torch
+
+    from bench_model import VOCAB
+
+    g = torch.Generator().manual_seed(batch)
+    prompts = [torch.randint(0, VOCAB, (PROMPT,), generator=g).tolist() for _ in range(batch)]
+    blocks = batch * -(-(PROMPT + NEW - 1) // BS)
+    base_cache = lm.new_cache(blocks, BS)
+    variants = {"generate": lambda n: lm.generate(prompts, n, cache=base_cache)}
+    if not baseline_only:
+        from qqq_amd import DecodeLoop
+
+        max_len = -(-(PROMPT + NEW - 1) // BS) * BS
+        for name, graph in (("loop_eager", False), ("loop_graph", True)):
+            loop = DecodeLoop(lm, lm.new_cache(blocks, BS), rows=batch, max_len=max_len, sync_every=SYNC_EVERY, graph=graph)
+            variants[name] = lambda n, loop=loop: loop.generate(prompts, n)
+
+    def timed(f, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f(n)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    tokens = {}
+    for name, f in variants.items():  # warm-up: code objects, workspaces, rope tables, the capture
+        timed(f, 1)
+        tokens[name] = timed(f, NEW)[1]
+        assert all(len(o) == NEW for o in tokens[name]), name
+    values = {name: [] for name in variants}
+    for _ in range(rounds):
+        for name, f in variants.items():
+            short, full = timed(f, 1)[0], timed(f, NEW)[0]
+            values[name].append((full - short) / (NEW - 1) * 1e6)
+    res = {"batch": batch, "prompt_tokens": PROMPT, "new_tokens": NEW, "layers": LAYERS}
+    for name, v in values.items():
+        res[name] = {"median_us_per_token": round(statistics.median(v), 1), "min_us_per_token": round(min(v), 1),
+                     "max_us_per_token": round(max(v), 1), "rounds_us_per_token": [round(x, 1) for x in v]}
+    if not baseline_only:
+        assert tokens["loop_graph"] == tokens["loop_eager"], "the captured loop and the eager loop must emit the same tokens"
+        # generate's decode batch is sized for the running sequences' lengths, the loop's for max_len: another split plan, so the last
+        # bits of the attention output, and with them a greedy token, may differ
+        res["loop_tokens_equal_generate"] = tokens["loop_graph"] == tokens["generate"]
+        base, graph = res["generate"], res["loop_graph"]
+        res["generate_over_loop_graph"] = round(base["median_us_per_token"] / graph["median_us_per_token"], 2)
+        res["generate_round_spread_us"] = round(base["max_us_per_token"] - base["min_us_per_token"], 1)
+        res["loop_graph_below_generate_by_more_than_its_spread"] = bool(
+            graph["median_us_per_token"] < base["median_us_per_token"] - res["generate_round_spread_us"])
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", default="1,16")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--baseline-only", action="store_true", help="time generate() alone (runs on a tree without DecodeLoop)")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_loop_bench.json"))
+    args = ap.parse_args()
+    import torch
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_generate.py needs a GPU: a timing taken elsewhere says nothing")
+    from bench_model import build
+
+    dev = torch.device("cuda:0")
+    lm = build(LAYERS, dev)
+    with torch.no_grad():
+        points = [point(lm, b, args.rounds, args.baseline_only, dev) for b in map(int, args.batch.split(","))]
+    out = {"tool": "tools/bench_generate.py", "device": torch.cuda.get_device_name(0),
+           "shape": "Llama-2-7B layers, per-channel W4A8, fuse_qkv(), paged fp16 cache, block 16, greedy", "sync_every": SYNC_EVERY,
+           "rounds": args.rounds, "points": points}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"batch {p['batch']:3d}: " + "  ".join(f"{n} {p[n]['median_us_per_token']:.1f} us/token" for n in
+                                                     ("generate", "loop_eager", "loop_graph") if n in p)
+              + (f"  | generate / loop graph {p['generate_over_loop_graph']}x, generate's spread {p['generate_round_spread_us']} us"
+                 if "generate_over_loop_graph" in p else ""))
+    gate = [p for p in points if p["batch"] == 1 and "loop_graph_below_generate_by_more_than_its_spread" in p]
+    if gate and not gate[0]["loop_graph_below_generate_by_more_than_its_spread"]:
+        sys.exit("batch 1: the captured loop is not below generate() by more than generate()'s spread: the capture is not holding")
+
+
+if __name__ == "__main__":
+    main()
