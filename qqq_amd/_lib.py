@@ -103,6 +103,9 @@ def lib():
     # include/qqq_amd_step.h
     L.qqq_sample_advance.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, ci, ci, ci, ci, vp]
     L.qqq_sample_advance.restype = ci
+    # include/qqq_amd_score.h
+    L.qqq_token_logprobs.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, vp]
+    L.qqq_token_logprobs.restype = ci
     L.qqq_amd_abi_version.restype = ci
     L.qqq_amd_last_error.restype = ctypes.c_char_p
     if L.qqq_amd_abi_version() != ABI_VERSION:

@@ -26,6 +26,7 @@ PAGED_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_paged.h")
 PREFILL_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_prefill.h")
 SAMPLE_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_sample.h")
 STEP_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_step.h")
+SCORE_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_score.h")
 DEV_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_dev.h")
 LIB = os.environ.get("QQQ_AMD_LIB") or os.path.join(_HERE, "libqqq_amd.so")  # override: tuning builds only
 DEV_LIB = os.path.join(_HERE, "libqqq_amd_dev.so")
@@ -49,7 +50,7 @@ def _stale(lib: str, extra) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(LIB, [HDR, ACT_HDR, ATTN_HDR, DECODE_HDR, KV8_HDR, PAGED_HDR, PREFILL_HDR, SAMPLE_HDR, STEP_HDR])
+    return _stale(LIB, [HDR, ACT_HDR, ATTN_HDR, DECODE_HDR, KV8_HDR, PAGED_HDR, PREFILL_HDR, SAMPLE_HDR, STEP_HDR, SCORE_HDR])
 
 
 def _compile(src: str, out: str, verbose: bool, flags=()) -> str:
@@ -97,7 +98,7 @@ def build_torch_ext(force: bool = False, verbose: bool = False) -> str:
     default_lib = os.path.join(_HERE, "libqqq_amd.so")
     if not os.path.exists(default_lib):
         raise RuntimeError("build the operator library first (qqq_amd.build.build())")
-    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(TORCH_SRC), os.path.getmtime(HDR)):
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(TORCH_SRC), os.path.getmtime(HDR), os.path.getmtime(SCORE_HDR)):
         return out
     tdir = os.path.dirname(torch.__file__)
     cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",

@@ -6,12 +6,14 @@
 //     dispatcher round trip, no ctypes marshalling (tools/host_overhead.py: 7.5 us -> ~2 us of host time per call);
 //   * TORCH_LIBRARY ops `qqq_amd_native::{qqq_gemm, qqq_gemm_bias, qqq_gemm_w8, expand_int8, dynamic_quant}` for callers that want dispatcher-visible
 //     native ops (the Python custom ops of ops.py stay the torch.compile path: they carry the fake kernels).
+// The scoring kernel's op (`.token_logprobs`, include/qqq_amd_score.h) is bound the same way, with ops.py's checks and messages.
 // Errors: the reference's own checks and messages (csrc/qqq_gemm.cu:1062-1075, :1096-1105) plus the ones it leaves undefined.
 #include <c10/hip/HIPStream.h>
 #include <torch/extension.h>
 #include <torch/library.h>
 
 #include "../../include/qqq_amd.h"
+#include "../../include/qqq_amd_score.h"
 
 namespace {
 
@@ -161,6 +163,32 @@ at::Tensor quantlinear_forward(const at::Tensor& x, const at::Tensor& B, at::Ten
   return D;
 }
 
+// ops.token_logprobs (include/qqq_amd_score.h): (logprob f32 [rows], argmax int64 [rows]; int64 [0] without return_argmax)
+std::tuple<at::Tensor, at::Tensor> token_logprobs(const at::Tensor& logits, const at::Tensor& targets, bool return_argmax) {
+  TORCH_CHECK(logits.is_cuda() && targets.is_cuda(), "token_logprobs: logits and targets must be on the GPU (there is no CPU path)");
+  TORCH_CHECK(targets.device() == logits.device(), "token_logprobs: logits and targets must be on the same GPU");
+  TORCH_CHECK(logits.scalar_type() == at::kHalf && logits.dim() == 2, "token_logprobs: logits must be fp16 [rows, vocab]");
+  const int64_t rows = logits.size(0), vocab = logits.size(1);
+  TORCH_CHECK(targets.scalar_type() == at::kLong && targets.dim() == 1 && targets.size(0) == rows, "token_logprobs: targets must be int64 [",
+              rows, "], one entry per row, not ", targets.dtype(), " ", targets.sizes());
+  TORCH_CHECK(vocab >= 1 && vocab <= 262144 && rows <= 1048576, "token_logprobs: logits ", logits.sizes(),
+              " outside 1 <= vocab <= 262144, rows <= 1048576");
+  at::Tensor logprob = at::empty({rows}, logits.options().dtype(at::kFloat));
+  at::Tensor argmax = at::empty({return_argmax ? rows : 0}, logits.options().dtype(at::kLong));
+  if (rows == 0) return {logprob, argmax};
+  // a row-strided view (the first vocab columns of a padded head output) is taken in place; anything else is copied into such rows
+  at::Tensor x = logits;
+  if (x.stride(1) != 1 || x.stride(0) < vocab || x.stride(0) % 8 || reinterpret_cast<uintptr_t>(x.data_ptr()) % 16) {
+    x = at::empty({rows, vocab + (8 - vocab % 8) % 8}, logits.options()).narrow(1, 0, vocab);
+    x.copy_(logits);
+  }
+  const at::Tensor t = targets.contiguous();
+  const int err = qqq_token_logprobs(ptr(x), (int)x.stride(0), ptr(t), ptr(logprob), ptr(argmax), (int)rows, (int)vocab, logits.device().index(),
+                                     stream_of(logits));
+  TORCH_CHECK(err == QQQ_OK, "qqq_amd: token_logprobs error ", err, ": ", qqq_amd_last_error());
+  return {logprob, argmax};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(qqq_amd_native, m) {
@@ -191,5 +219,6 @@ PYBIND11_MODULE(_torch_ext, m) {
         pybind11::arg("workspace"), pybind11::arg("bias"), pybind11::arg("max_par"), pybind11::arg("W8") = c10::optional<at::Tensor>());
   m.def("qqq_gemm_w8", &qqq_gemm_w8);
   m.def("expand_int8", &expand_int8);
+  m.def("token_logprobs", &token_logprobs, pybind11::arg("logits"), pybind11::arg("targets"), pybind11::arg("return_argmax") = true);
   m.def("abi_version", []() { return qqq_amd_abi_version(); });
 }

@@ -34,6 +34,7 @@
 //   qqq_paged.hip.h    the block-table (paged) KV cache, fp16 and int8: the cache writes by slot and the decode split kernels through a block table
 //   qqq_prefill.hip.h  paged, ragged, causal prefill attention over the block pools (fp16 and int8) and the quantisation of its rows
 //   qqq_sample.hip.h   the fused token sampler: temperature, top-k, top-p and the draw over a batch of fp16 logit rows, one launch
+//   qqq_score.hip.h    the fused scoring kernel: a target token's log-probability and the argmax per fp16 logit row, one launch (the sampler's weights)
 //   qqq_step.hip.h     the decode loop's step: that sampler with an epilogue that advances each row's decode state on the device
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
@@ -73,6 +74,8 @@
 #include "../../include/qqq_amd_prefill.h"
 #include "qqq_sample.hip.h"
 #include "../../include/qqq_amd_sample.h"
+#include "qqq_score.hip.h"
+#include "../../include/qqq_amd_score.h"
 #include "qqq_step.hip.h"
 #include "../../include/qqq_amd_step.h"
 #include "qqq_plan.h"
@@ -1063,6 +1066,34 @@ extern "C" int qqq_sample_tokens(const void* logits, int ld, const void* tempera
                      static_cast<const float*>(top_p), static_cast<const float*>(u), static_cast<long long*>(tokens), vocab);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_sample_tokens_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- the fused scoring kernel (include/qqq_amd_score.h; kernel in qqq_score.hip.h): one launch, one workgroup per row, no workspace.
+extern "C" int qqq_token_logprobs(const void* logits, int ld, const void* targets, void* logprob, void* argmax, int rows, int vocab, int dev,
+                                  void* stream) {
+  g_err[0] = 0;
+  if (rows < 0 || rows > 1048576) {
+    snprintf(g_err, sizeof(g_err), "qqq_token_logprobs: rows=%d outside [0, 1048576]", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  if (vocab < 1 || vocab > SMP_MAX_VOCAB || ld < vocab || ld % 8 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_token_logprobs: bad shape vocab=%d ld=%d (need 1 <= vocab <= %d, ld >= vocab, ld %% 8 == 0)", vocab, ld,
+             SMP_MAX_VOCAB);
+    return QQQ_ERR_ARG;
+  }
+  if (!logits || !targets || !logprob || misaligned(logits, 16) || misaligned(targets, 8) || misaligned(logprob, 4) || misaligned(argmax, 8)) {
+    snprintf(g_err, sizeof(g_err), "qqq_token_logprobs: bad argument (logits, targets and logprob must be non-NULL; logits 16-byte, targets and "
+             "argmax 8-byte, logprob 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_token_logprobs_kernel, dim3(rows), dim3(SMP_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(logits), ld, static_cast<const long long*>(targets), static_cast<float*>(logprob),
+                     static_cast<long long*>(argmax), vocab);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_token_logprobs_kernel launch");
   return QQQ_OK;
 }
 

@@ -3,7 +3,8 @@ twins (QQQ/gptq/models/llama.py, qwen2.py), and the generation loop of its examp
 
     QuantLlamaModel        embed_tokens (fp16 nn.Embedding) -> layers (QuantLlamaDecoderLayer, chained through forward_chained: the add
                            that ends a layer is formed by the next layer's norm launch) -> norm (QuantRMSNorm): the normed fp16 rows
-    QuantLlamaForCausalLM  model + lm_head (fp16 nn.Linear, not quantised, as in the reference): logits; generate()
+    QuantLlamaForCausalLM  model + lm_head (fp16 nn.Linear, not quantised, as in the reference): logits; generate(); score(),
+                           loglikelihood() and perplexity() (qqq_amd/score.py), the reference's examples/eval_model.py
 
 Parameter and buffer names are the reference's (model.embed_tokens.weight, model.layers.N. ..., model.norm.weight, lm_head.weight), so a
 state-dict saved by it loads with load_state_dict(strict=True).
@@ -236,6 +237,29 @@ class QuantLlamaForCausalLM(nn.Module):
             cur = first if not running else torch.cat([cur, first])
             running = running + alive
         return out
+
+    def score(self, sequences: Sequence[Sequence[int]], cache: Optional[PagedKVCache] = None, chunk_tokens: int = 2048, block_size: int = 16,
+              dtype=torch.float16, return_greedy: bool = False):
+        """Per-token log-probabilities log p(seq[t + 1] | seq[:t + 1]) of every sequence, f32 [len - 1] each (with return_greedy also the
+        argmax ids), in chunks of `chunk_tokens` tokens over a paged cache through ops.token_logprobs: qqq_amd/score.py::score."""
+        from . import score as _score
+
+        return _score.score(self, sequences, cache=cache, chunk_tokens=chunk_tokens, block_size=block_size, dtype=dtype,
+                            return_greedy=return_greedy)
+
+    def loglikelihood(self, requests, **score_kw):
+        """[(sum of the continuation's log-probs, is_greedy)] for (context_ids, continuation_ids) requests, the shape of lm-eval's
+        loglikelihood: qqq_amd/score.py::loglikelihood."""
+        from . import score as _score
+
+        return _score.loglikelihood(self, requests, **score_kw)
+
+    def perplexity(self, token_ids, seqlen: int = 2048, **score_kw) -> float:
+        """Perplexity over numel // seqlen disjoint windows by the convention of the reference's examples/eval_model.py (per window the
+        mean NLL of its seqlen - 1 targets times seqlen; exp(sum / (nsamples * seqlen))): qqq_amd/score.py::perplexity."""
+        from . import score as _score
+
+        return _score.perplexity(self, token_ids, seqlen, **score_kw)
 
 
 __all__ = ["QuantLlamaModel", "QuantLlamaForCausalLM"]

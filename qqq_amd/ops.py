@@ -1191,6 +1191,75 @@ def sample_tokens(logits: torch.Tensor, temperature, top_k, top_p, u: torch.Tens
     return _sample_tokens_impl(logits, temperature, top_k, top_p, u)
 
 
+# ---- the fused scoring kernel (include/qqq_amd_score.h): logits + targets -> the targets' log-probabilities and the argmax, one launch
+
+def _token_logprobs_check(logits, targets):
+    if logits.dtype != torch.float16 or logits.dim() != 2:
+        raise RuntimeError("token_logprobs: logits must be fp16 [rows, vocab]")
+    rows, vocab = logits.shape
+    if targets.dtype != torch.int64 or targets.dim() != 1 or targets.shape[0] != rows:
+        raise RuntimeError(f"token_logprobs: targets must be int64 [{rows}], one entry per row, not "
+                           f"{str(targets.dtype).replace('torch.', '')} {tuple(targets.shape)}")
+    if vocab < 1 or vocab > 262144 or rows > 1048576:
+        raise RuntimeError(f"token_logprobs: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows <= 1048576")
+    return rows, vocab
+
+
+def _token_logprobs_impl(logits, targets, return_argmax):
+    if not (logits.is_cuda and targets.is_cuda):
+        raise RuntimeError("token_logprobs: logits and targets must be on the GPU (there is no CPU path)")
+    if targets.device != logits.device:
+        raise RuntimeError("token_logprobs: logits and targets must be on the same GPU")
+    rows, vocab = _token_logprobs_check(logits, targets)
+    logprob = torch.empty((rows,), dtype=torch.float32, device=logits.device)
+    argmax = torch.empty((rows if return_argmax else 0,), dtype=torch.int64, device=logits.device)
+    if rows == 0:
+        return logprob, argmax
+    # a row-strided view (the first vocab columns of a padded head output) is taken in place; anything else is copied into such rows
+    if logits.stride(1) != 1 or logits.stride(0) < vocab or logits.stride(0) % 8 or logits.data_ptr() % 16:
+        rows8 = torch.empty((rows, vocab + (-vocab) % 8), dtype=torch.float16, device=logits.device)
+        rows8[:, :vocab] = logits
+        logits = rows8[:, :vocab]
+    err = _lib.lib().qqq_token_logprobs(_ptr(logits), logits.stride(0), _ptr(targets.contiguous()), _ptr(logprob), _ptr(argmax), rows, vocab,
+                                        logits.device.index or 0, _stream_for(logits))
+    if err:
+        raise RuntimeError(f"qqq_amd: token_logprobs error {err}: {_lib.last_error()}")
+    return logprob, argmax
+
+
+@torch.library.custom_op("qqq_amd::token_logprobs", mutates_args=())
+def _token_logprobs_op(logits: torch.Tensor, targets: torch.Tensor, return_argmax: bool) -> tuple[torch.Tensor, torch.Tensor]:
+    return _token_logprobs_impl(logits, targets, return_argmax)
+
+
+@_token_logprobs_op.register_fake
+def _(logits, targets, return_argmax):
+    rows, _ = _token_logprobs_check(logits, targets)
+    return logits.new_empty((rows,), dtype=torch.float32), logits.new_empty((rows if return_argmax else 0,), dtype=torch.int64)
+
+
+def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, return_argmax: bool = True):
+    """log softmax(logits[r])[targets[r]] for every row of fp16 logits [rows, vocab] and int64 targets [rows], in one launch and without an
+    fp32 copy of the logits -> (logprob f32 [rows], argmax int64 [rows]; None with return_argmax=False).
+
+    The exact semantics of a row are stated in include/qqq_amd_score.h: the weights are the sampler's at temperature 1 (fixed point, summed
+    as integers, so a row's result is reproducible to the bit wherever the row sits), the logarithm is taken in f64 and rounded once;
+    argmax is the token sample_tokens returns at temperature 0.  targets < 0 are ignored (logprob 0.0, as ignore_index), targets >= vocab
+    give NaN, a target whose logit is NaN or -inf gives -inf.  Nothing is read on the host and the launch size depends on the shape alone,
+    so a captured graph replays with other contents.  A view whose rows are `vocab` columns of a wider, 16-byte aligned fp16 matrix (row
+    stride a multiple of 8) is read in place; its other columns are never touched."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(targets, torch.Tensor) or logits.dim() != 2:
+        raise RuntimeError("token_logprobs: logits must be an fp16 [rows, vocab] tensor and targets an int64 [rows] tensor")
+    return_argmax = bool(return_argmax)
+    if _compiling(logits, targets):
+        logprob, argmax = _token_logprobs_op(logits, targets, return_argmax)
+    elif _ext() is not None:
+        logprob, argmax = _EXT.token_logprobs(logits, targets, return_argmax)
+    else:
+        logprob, argmax = _token_logprobs_impl(logits, targets, return_argmax)
+    return logprob, (argmax if return_argmax else None)
+
+
 # ---- the decode loop's sample-and-advance step (include/qqq_amd_step.h): sample_tokens with an epilogue that advances every row's state
 
 _ADVANCE_STATE = (("tick", torch.int32), ("ids", torch.int64), ("pos", torch.int64), ("slots", torch.int64), ("remaining", torch.int32),
