@@ -168,6 +168,7 @@ int qqq_w4a8_model_us(int prob_m, int prob_n, int prob_k, int groupsize, int max
  *   s1[i]  = f32( f16_rn( max_k|x[i,k]| * (1.0f/127.0f) ) )     (torch-GPU lowering of .div(127.0))
  *   xq[i,k]= int8( clamp( rint( f32(x[i,k]) / s1[i] ), -128, 127 ) )
  * x fp16 [m,k] row-major, xq int8 [m,k], s1 f32 [m].  k must be a multiple of 8.
+ * A row whose scale is 0 (all zero, or max|x| <= 63 * 2^-24) gets codes 0 and s1 0; the reference divides by zero there.
  */
 int qqq_dynamic_quant(const void* x, void* xq, void* s1, int m, int k, int dev, void* stream);
 

@@ -173,7 +173,8 @@ def _layer_composition(layer, x, cache, start):
     return h + layer.mlp.forward_int8(mq, ms)
 
 
-SHAPES = {"llama": (1024, 8, 8, 2048, False), "llama_gqa": (1024, 8, 2, 2048, False), "qwen2": (896, 14, 2, 1024, True)}
+SHAPES = {"llama": (1024, 8, 8, 2048, False), "llama_gqa": (1024, 8, 2, 2048, False), "qwen2": (896, 14, 2, 1024, True),
+          "llama3_g8": (1024, 8, 1, 2048, False)}
 
 
 @pytest.mark.parametrize("kind", list(SHAPES))

@@ -187,7 +187,8 @@ def _decode_composition(attn, xq, s1, cache, start):
     return attn.o_proj.forward_int8(aq, a1)
 
 
-MODULE_SHAPES = {"llama": (1024, 8, 8, 2048, False), "llama_gqa": (1024, 8, 2, 2048, False), "qwen2": (896, 14, 2, 1024, True)}
+MODULE_SHAPES = {"llama": (1024, 8, 8, 2048, False), "llama_gqa": (1024, 8, 2, 2048, False), "qwen2": (896, 14, 2, 1024, True),
+                 "llama3_g8": (1024, 8, 1, 2048, False)}
 
 
 @pytest.mark.parametrize("kind", list(MODULE_SHAPES))
