@@ -24,6 +24,9 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     sample_advance(logits, ..., u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out, block_size)  # sample_tokens + the decode
                                                                                     # loop's per-row bookkeeping on the device, one launch
     DecodeLoop(lm, cache, rows, max_len)                                            # device-resident decode loop, one graph per step; qqq_amd/serve.py
+    spec_advance(logits, ..., u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len, n_out, n_acc, block_size, ngram_max)
+                                                                                    # draft_len + 1 draws per row, accept rule, n-gram drafter
+    SpecDecodeLoop(lm, cache, rows, max_len, draft_len=4), ngram_draft              # speculative decode loop, 1 ... draft_len + 1 tokens per replay
     token_logprobs(logits, targets, return_argmax=True)                             # a target's log-probability and the argmax per logit row, one launch
     QuantLlamaForCausalLM.score / loglikelihood / perplexity, pack_steps            # scoring text over the paged cache; qqq_amd/score.py
 """
@@ -51,6 +54,7 @@ from .ops import (  # noqa: F401
     sample_advance,
     sample_tokens,
     silu_mul_quant,
+    spec_advance,
     token_logprobs,
 )
 from .qlinear import QuantLinear, fuse_quant_linears  # noqa: F401
@@ -58,7 +62,7 @@ from .blocks import QuantLlamaMLP, QuantRMSNorm  # noqa: F401
 from .attention import KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer  # noqa: F401
 from .paged import PagedKVCache, PagedStep  # noqa: F401
 from .model import QuantLlamaForCausalLM, QuantLlamaModel  # noqa: F401
-from .serve import DecodeLoop  # noqa: F401
+from .serve import DecodeLoop, SpecDecodeLoop, ngram_draft  # noqa: F401
 from .score import pack_steps  # noqa: F401
 
 __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_int8", "mul", "marlin_qqq_gemm", "dynamic_quant", "quantlinear_forward",
@@ -66,4 +70,5 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "rope_qkv", "decode_attention", "rope_qkv_kv8", "decode_attention_kv8", "rope_qkv_paged",
            "decode_attention_paged", "rope_qkv_paged_kv8", "decode_attention_paged_kv8", "prefill_attention_paged",
            "prefill_attention_paged_kv8", "PagedKVCache", "PagedStep", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer",
-           "sample_tokens", "QuantLlamaModel", "QuantLlamaForCausalLM", "sample_advance", "DecodeLoop", "token_logprobs", "pack_steps"]
+           "sample_tokens", "QuantLlamaModel", "QuantLlamaForCausalLM", "sample_advance", "DecodeLoop", "token_logprobs", "pack_steps",
+           "spec_advance", "SpecDecodeLoop", "ngram_draft"]

@@ -106,6 +106,12 @@ def lib():
     # include/qqq_amd_score.h
     L.qqq_token_logprobs.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, vp]
     L.qqq_token_logprobs.restype = ci
+    # include/qqq_amd_spec.h
+    L.qqq_spec_advance.argtypes = [vp, ci, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, ctypes.c_size_t, ci,
+                                   ci, ci, ci, ci, ci, vp]
+    L.qqq_spec_advance.restype = ci
+    L.qqq_spec_advance_workspace_bytes.argtypes = [ci, ci]
+    L.qqq_spec_advance_workspace_bytes.restype = ctypes.c_size_t
     L.qqq_amd_abi_version.restype = ci
     L.qqq_amd_last_error.restype = ctypes.c_char_p
     if L.qqq_amd_abi_version() != ABI_VERSION:

@@ -36,6 +36,7 @@
 //   qqq_sample.hip.h   the fused token sampler: temperature, top-k, top-p and the draw over a batch of fp16 logit rows, one launch
 //   qqq_score.hip.h    the fused scoring kernel: a target token's log-probability and the argmax per fp16 logit row, one launch (the sampler's weights)
 //   qqq_step.hip.h     the decode loop's step: that sampler with an epilogue that advances each row's decode state on the device
+//   qqq_spec.hip.h     the speculative decode loop's step: draft_len + 1 draws per row by that sampler, the accept rule and the n-gram drafter
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -78,6 +79,8 @@
 #include "../../include/qqq_amd_score.h"
 #include "qqq_step.hip.h"
 #include "../../include/qqq_amd_step.h"
+#include "qqq_spec.hip.h"
+#include "../../include/qqq_amd_spec.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1147,6 +1150,97 @@ extern "C" int qqq_sample_advance(const void* logits, int ld, const void* temper
                      static_cast<const float*>(top_p), st, vocab);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_step_advance_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- the speculative decode loop's verify-and-advance step (include/qqq_amd_spec.h; kernels in qqq_spec.hip.h): the sampler's launch over
+// rows * (draft_len + 1) logits rows into the workspace, then one workgroup per row for the accept rule, the drafter and the next positions.
+extern "C" size_t qqq_spec_advance_workspace_bytes(int rows, int draft_len) {
+  if (rows < 1 || draft_len < 1 || draft_len > SPEC_MAX_DRAFT || (long long)rows * (draft_len + 1) > 65535) return 0;
+  return (size_t)rows * (size_t)(draft_len + 1) * sizeof(long long);
+}
+
+extern "C" int qqq_spec_advance(const void* logits, int ld, const void* temperature, const void* top_k, const void* top_p, const void* u,
+                                int u_stride, void* tick, void* ids, void* pos, void* slots, void* start, const void* block_table,
+                                int table_stride, void* remaining, const void* eos, void* hist, int hist_stride, void* hist_len,
+                                void* n_out, void* n_acc, void* workspace, size_t workspace_bytes, int rows, int draft_len, int ngram_max,
+                                int vocab, int block_size, int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_spec_advance: rows=%d is negative", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  if (draft_len < 1 || draft_len > SPEC_MAX_DRAFT || ngram_max < 1 || ngram_max > SPEC_MAX_NGRAM) {
+    snprintf(g_err, sizeof(g_err), "qqq_spec_advance: draft_len=%d outside [1, %d] or ngram_max=%d outside [1, %d]", draft_len,
+             SPEC_MAX_DRAFT, ngram_max, SPEC_MAX_NGRAM);
+    return QQQ_ERR_ARG;
+  }
+  const int group = draft_len + 1;
+  if ((long long)rows * group > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_spec_advance: rows=%d times draft_len + 1 = %d exceeds 65535 logits rows", rows, group);
+    return QQQ_ERR_ARG;
+  }
+  if (vocab < 1 || vocab > SMP_MAX_VOCAB || ld < vocab || ld % 8 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_spec_advance: bad shape vocab=%d ld=%d (need 1 <= vocab <= %d, ld >= vocab, ld %% 8 == 0)", vocab, ld,
+             SMP_MAX_VOCAB);
+    return QQQ_ERR_ARG;
+  }
+  if (block_size < 16 || block_size > 256 || (block_size & (block_size - 1)) || table_stride < 1 || hist_stride < 1 || u_stride < group) {
+    snprintf(g_err, sizeof(g_err), "qqq_spec_advance: bad shape block_size=%d table_stride=%d hist_stride=%d u_stride=%d (need block_size a "
+             "power of two in [16, 256], table_stride and hist_stride >= 1, u_stride >= draft_len + 1 = %d)", block_size, table_stride,
+             hist_stride, u_stride, group);
+    return QQQ_ERR_ARG;
+  }
+  if (!logits || !temperature || !top_k || !top_p || !u || !tick || !ids || !pos || !slots || !start || !block_table || !remaining || !eos ||
+      !hist || !hist_len || !n_out || !n_acc || !workspace || misaligned(logits, 16) || misaligned(temperature, 4) || misaligned(top_k, 4) ||
+      misaligned(top_p, 4) || misaligned(u, 4) || misaligned(tick, 4) || misaligned(ids, 8) || misaligned(pos, 8) || misaligned(slots, 8) ||
+      misaligned(start, 8) || misaligned(block_table, 4) || misaligned(remaining, 4) || misaligned(eos, 4) || misaligned(hist, 4) ||
+      misaligned(hist_len, 4) || misaligned(n_out, 4) || misaligned(n_acc, 4) || misaligned(workspace, 8)) {
+    snprintf(g_err, sizeof(g_err), "qqq_spec_advance: bad argument (every pointer must be non-NULL; logits 16-byte, ids / pos / slots / "
+             "start / workspace 8-byte, everything else 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  const size_t need = qqq_spec_advance_workspace_bytes(rows, draft_len);
+  if (workspace_bytes < need) {
+    snprintf(g_err, sizeof(g_err), "qqq_spec_advance: workspace of %zu bytes, %zu needed (qqq_spec_advance_workspace_bytes)", workspace_bytes,
+             need);
+    return QQQ_ERR_ARG;
+  }
+  qqq_spec_draw dr;
+  dr.uu = static_cast<const float*>(u);
+  dr.tick = static_cast<const int*>(tick);
+  dr.tokens = static_cast<long long*>(workspace);
+  dr.u_stride = u_stride;
+  dr.group = group;
+  qqq_spec_state st;
+  st.tokens = static_cast<const long long*>(workspace);
+  st.tick = static_cast<int*>(tick);
+  st.ids = static_cast<long long*>(ids);
+  st.pos = static_cast<long long*>(pos);
+  st.slots = static_cast<long long*>(slots);
+  st.start = static_cast<long long*>(start);
+  st.block_table = static_cast<const int*>(block_table);
+  st.remaining = static_cast<int*>(remaining);
+  st.eos = static_cast<const int*>(eos);
+  st.hist = static_cast<int*>(hist);
+  st.hist_len = static_cast<int*>(hist_len);
+  st.n_out = static_cast<int*>(n_out);
+  st.n_acc = static_cast<int*>(n_acc);
+  st.table_stride = table_stride;
+  st.hist_stride = hist_stride;
+  st.block_shift = __builtin_ctz((unsigned)block_size);
+  st.draft_len = draft_len;
+  st.ngram_max = ngram_max;
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_spec_draw_kernel, dim3(rows * group), dim3(SMP_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(logits), ld, static_cast<const float*>(temperature), static_cast<const int*>(top_k),
+                     static_cast<const float*>(top_p), dr, vocab);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_spec_draw_kernel launch");
+  hipLaunchKernelGGL(qqq_spec_advance_kernel, dim3(rows), dim3(SPEC_NT), 0, static_cast<hipStream_t>(stream), st);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_spec_advance_kernel launch");
   return QQQ_OK;
 }
 

@@ -157,7 +157,7 @@ class QuantLlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, cache: Optional[PagedKVCache] = None,
-                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False) -> List[List[int]]:
+                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False, draft_len: int = 0) -> List[List[int]]:
         """Generate up to `max_new_tokens` tokens for every prompt (token lists of any lengths) -> the generated ids per prompt, the
         eos_token_id that ends a sequence included.
 
@@ -172,7 +172,15 @@ class QuantLlamaForCausalLM(nn.Module):
 
         device_loop=True hands the prompts to a DecodeLoop (qqq_amd/serve.py) of min(len(prompts), 64) rows, sized for the longest budget
         rounded up to a block: the decode steps replay from one captured graph and the host syncs once per several tokens.  Greedy tokens
-        are the same; the random draws are the loop's (one torch.rand(rows, u_stride) per u_stride steps)."""
+        are the same; the random draws are the loop's (one torch.rand(rows, u_stride) per u_stride steps).
+
+        draft_len=K > 0 (with device_loop=True, on a model with fuse_prefill()) makes that loop a SpecDecodeLoop: K tokens drafted by
+        n-gram lookup ride behind every row's last token and a replay emits 1 ... K + 1 tokens per row.  The output distribution is
+        unchanged; the tokens under a seed differ (K + 1 variates per row and step), greedy tokens are the same up to near-ties of the
+        logits.  Every sequence needs K more keys of the pool."""
+        draft_len = int(draft_len)
+        if draft_len < 0 or (draft_len > 0 and not device_loop):
+            raise ValueError(f"generate: draft_len={draft_len} must be 0, or positive together with device_loop=True")
         prompts = [list(p) for p in prompts]
         if any(not p for p in prompts):
             raise ValueError("generate: every prompt needs at least one token")
@@ -180,9 +188,14 @@ class QuantLlamaForCausalLM(nn.Module):
         if max_new_tokens < 1 or not prompts:
             return out
         dev = self.lm_head.weight.device
-        need = [-(-(len(p) + max_new_tokens - 1) // (cache.block_size if cache is not None else block_size)) for p in prompts]
+        need = [-(-(len(p) + max_new_tokens - 1 + draft_len) // (cache.block_size if cache is not None else block_size)) for p in prompts]
         if cache is None:
             cache = self.new_cache(sum(need), block_size, dtype)
+        if draft_len:
+            from .serve import SpecDecodeLoop
+
+            loop = SpecDecodeLoop(self, cache, rows=min(len(prompts), 64), max_len=max(need) * cache.block_size, draft_len=draft_len)
+            return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id)
         if device_loop:
             from .serve import DecodeLoop
 

@@ -1358,3 +1358,134 @@ def sample_advance(logits: torch.Tensor, temperature, top_k, top_p, u: torch.Ten
     if _compiling(*args):
         return _sample_advance_op(*args, int(block_size))
     return _sample_advance_impl(*args, int(block_size))
+
+
+# ---- the speculative decode loop's verify-and-advance step (include/qqq_amd_spec.h): draft_len + 1 draws per row, the accept rule, the
+# n-gram drafter and the next step's positions, on the device
+
+_SPEC_ROW_STATE = (("tick", torch.int32), ("start", torch.int64), ("remaining", torch.int32), ("eos", torch.int32), ("hist_len", torch.int32),
+                   ("n_out", torch.int32), ("n_acc", torch.int32))
+
+
+def _spec_advance_check(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len,
+                        n_out, n_acc, block_size, ngram_max):
+    # the checks that need no device: dtypes and shapes (shared by the launch and the fake implementation)
+    if logits.dtype != torch.float16 or logits.dim() != 2:
+        raise RuntimeError("spec_advance: logits must be fp16 [rows * (draft_len + 1), vocab]")
+    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[1] < 2 or ids.shape[1] > 16:
+        raise RuntimeError(f"spec_advance: ids must be int64 [rows, draft_len + 1] with 1 <= draft_len <= 15, not "
+                           f"{str(ids.dtype).replace('torch.', '')} {tuple(ids.shape)}")
+    rows, group = ids.shape
+    m, vocab = logits.shape
+    if m != rows * group:
+        raise RuntimeError(f"spec_advance: logits hold {m} rows, ids {tuple(ids.shape)} asks for {rows * group}")
+    if temperature.dtype != torch.float32 or top_p.dtype != torch.float32 or u.dtype != torch.float32 or top_k.dtype != torch.int32:
+        raise RuntimeError("spec_advance: temperature, top_p and u must be f32, top_k int32")
+    if any(t.numel() != m for t in (temperature, top_k, top_p)):
+        raise RuntimeError(f"spec_advance: temperature, top_k and top_p must hold one entry per logits row ({m})")
+    if u.dim() != 2 or u.shape[0] != rows or u.shape[1] < group:
+        raise RuntimeError(f"spec_advance: u must be f32 [{rows}, u_stride] with u_stride >= draft_len + 1 = {group}, not {tuple(u.shape)}")
+    for name, t in (("pos", pos), ("slots", slots)):
+        if t.dtype != torch.int64 or tuple(t.shape) != (rows, group):
+            raise RuntimeError(f"spec_advance: {name} must be int64 [{rows}, {group}], not {str(t.dtype).replace('torch.', '')} "
+                               f"{tuple(t.shape)}")
+    state = dict(tick=tick, start=start, remaining=remaining, eos=eos, hist_len=hist_len, n_out=n_out, n_acc=n_acc)
+    for name, dtype in _SPEC_ROW_STATE:
+        t = state[name]
+        if t.dtype != dtype or t.dim() != 1 or t.shape[0] != rows:
+            raise RuntimeError(f"spec_advance: {name} must be {str(dtype).replace('torch.', '')} [{rows}], not "
+                               f"{str(t.dtype).replace('torch.', '')} {tuple(t.shape)}")
+    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != rows or block_table.shape[1] < 1:
+        raise RuntimeError(f"spec_advance: block_table must be int32 [{rows}, blocks per row >= 1], not {tuple(block_table.shape)}")
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] != rows or hist.shape[1] < 1:
+        raise RuntimeError(f"spec_advance: hist must be int32 [{rows}, hist_stride >= 1], not {str(hist.dtype).replace('torch.', '')} "
+                           f"{tuple(hist.shape)}")
+    if block_size not in (16, 32, 64, 128, 256):
+        raise RuntimeError(f"spec_advance: block_size must be a power of two in [16, 256], not {block_size}")
+    if ngram_max < 1 or ngram_max > 4:
+        raise RuntimeError(f"spec_advance: ngram_max must be in [1, 4], not {ngram_max}")
+    if vocab < 1 or vocab > 262144 or m > 65535:
+        raise RuntimeError(f"spec_advance: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows * (draft_len + 1) <= 65535")
+    return rows, group, vocab
+
+
+def _spec_advance_impl(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len,
+                       n_out, n_acc, block_size, ngram_max):
+    ts = (logits, temperature, top_k, top_p, u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len, n_out, n_acc)
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError("spec_advance: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != logits.device for t in ts):
+        raise RuntimeError("spec_advance: every tensor must be on the same GPU")
+    rows, group, vocab = _spec_advance_check(*ts, block_size, ngram_max)
+    if rows == 0:
+        return
+    # everything written is written in place: no copy may stand in for a state array
+    for name, t in (("u", u), ("tick", tick), ("ids", ids), ("pos", pos), ("slots", slots), ("start", start), ("block_table", block_table),
+                    ("remaining", remaining), ("eos", eos), ("hist", hist), ("hist_len", hist_len), ("n_out", n_out), ("n_acc", n_acc)):
+        if not t.is_contiguous():
+            raise RuntimeError(f"spec_advance: {name} must be contiguous (the state is updated in place)")
+    if logits.stride(1) != 1 or logits.stride(0) < vocab or logits.stride(0) % 8 or logits.data_ptr() % 16:
+        rows8 = torch.empty((rows * group, vocab + (-vocab) % 8), dtype=torch.float16, device=logits.device)
+        rows8[:, :vocab] = logits
+        logits = rows8[:, :vocab]
+    L = _lib.lib()
+    ws = torch.empty((max(L.qqq_spec_advance_workspace_bytes(rows, group - 1), 16),), dtype=torch.uint8, device=logits.device)
+    err = L.qqq_spec_advance(_ptr(logits), logits.stride(0), _ptr(temperature.contiguous()), _ptr(top_k.contiguous()),
+                             _ptr(top_p.contiguous()), _ptr(u), u.shape[1], _ptr(tick), _ptr(ids), _ptr(pos), _ptr(slots), _ptr(start),
+                             _ptr(block_table), block_table.shape[1], _ptr(remaining), _ptr(eos), _ptr(hist), hist.shape[1], _ptr(hist_len),
+                             _ptr(n_out), _ptr(n_acc), _ptr(ws), ws.numel(), rows, group - 1, ngram_max, vocab, block_size,
+                             logits.device.index or 0, _stream_for(logits))
+    if err:
+        raise RuntimeError(f"qqq_amd: spec_advance error {err}: {_lib.last_error()}")
+
+
+@torch.library.custom_op("qqq_amd::spec_advance",
+                         mutates_args=("tick", "ids", "pos", "slots", "start", "remaining", "hist", "hist_len", "n_out", "n_acc"))
+def _spec_advance_op(logits: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor, u: torch.Tensor,
+                     tick: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor, start: torch.Tensor,
+                     block_table: torch.Tensor, remaining: torch.Tensor, eos: torch.Tensor, hist: torch.Tensor, hist_len: torch.Tensor,
+                     n_out: torch.Tensor, n_acc: torch.Tensor, block_size: int, ngram_max: int) -> None:
+    _spec_advance_impl(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len, n_out,
+                       n_acc, block_size, ngram_max)
+
+
+@_spec_advance_op.register_fake
+def _(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len, n_out, n_acc,
+      block_size, ngram_max):
+    _spec_advance_check(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len,
+                        n_out, n_acc, block_size, ngram_max)
+
+
+def spec_advance(logits: torch.Tensor, temperature, top_k, top_p, u: torch.Tensor, tick: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor,
+                 slots: torch.Tensor, start: torch.Tensor, block_table: torch.Tensor, remaining: torch.Tensor, eos: torch.Tensor,
+                 hist: torch.Tensor, hist_len: torch.Tensor, n_out: torch.Tensor, n_acc: torch.Tensor, block_size: int,
+                 ngram_max: int = 3) -> None:
+    """One speculative decode step's sampling, verification, drafting and bookkeeping: a row fed its last token and K = draft_len drafts
+    through one forward; here each of its G = K + 1 logits rows is sampled as by sample_tokens, the draws behind a rightly guessed prefix
+    are emitted (1 ... G tokens), the next K drafts come from an n-gram lookup in the row's history, and the row moves to its next
+    positions and cache slots or retires -- all on the device, in two launches.  Returns nothing; tick, ids, pos, slots, start, remaining,
+    hist, hist_len, n_out and n_acc are updated in place.
+
+    logits       fp16 [rows * G, vocab]: draw j of row r reads row r * G + j
+    temperature, top_k, top_p   as for sample_tokens, per logits row (a tensor of rows * G entries or a scalar)
+    u            f32 [rows, u_stride >= G]: draw j of row r uses u[r, (tick[r] * G + j) % u_stride];  tick  int32 [rows], + 1 per call
+    ids, pos, slots   int64 [rows, G]: flattened, the next forward's input_ids, PagedStep.pos and PagedStep.slots (idle: 0, -1, -1)
+    start        int64 [rows]: PagedStep.start_pos, = pos[:, 0];  block_table  int32 [rows, W], only read;  block_size  the pool's
+    remaining    int32 [rows]: tokens the row may still emit, 0 for an idle row;  eos  int32 [rows]: the row's eos id, -1 for none
+    hist         int32 [rows, hist_stride], hist_len int32 [rows]: the sequence so far, prompt and emitted tokens
+    n_out, n_acc int32 [rows]: tokens emitted (they are hist[r, hist_len - n_out : hist_len]) and drafts accepted since last cleared
+    ngram_max    the longest n-gram the drafter looks up, 1 ... 4
+    Every emitted token is a plain sampler draw from logits computed on the true prefix, so the output distribution is the sampler's at any
+    temperature, top_k and top_p.  The exact semantics of a row are stated in include/qqq_amd_spec.h.  Nothing is read on the host and the
+    launch sizes depend on the shapes alone, so a step that ends in this call replays from a captured graph while rows finish and join."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(u, torch.Tensor) or not isinstance(ids, torch.Tensor) or logits.dim() != 2:
+        raise RuntimeError("spec_advance: logits must be an fp16 [rows * (draft_len + 1), vocab] tensor, u an f32 [rows, u_stride] tensor "
+                           "and ids an int64 [rows, draft_len + 1] tensor")
+    m, dev = logits.shape[0], logits.device
+    temperature = _sample_param("temperature", temperature, m, torch.float32, dev, "spec_advance")
+    top_k = _sample_param("top_k", top_k, m, torch.int32, dev, "spec_advance")
+    top_p = _sample_param("top_p", top_p, m, torch.float32, dev, "spec_advance")
+    args = (logits, temperature, top_k, top_p, u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len, n_out, n_acc)
+    if _compiling(*args):
+        return _spec_advance_op(*args, int(block_size), int(ngram_max))
+    return _spec_advance_impl(*args, int(block_size), int(ngram_max))

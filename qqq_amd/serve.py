@@ -2,7 +2,10 @@
 ops.sample_advance, so that one decode step -- model forward + sample_advance -- reads nothing on the host and is ONE captured graph,
 replayed `sync_every` times between host syncs while rows finish and join without re-capture.
 
-    DecodeLoop   the rows' state arrays (include/qqq_amd_step.h), the one PagedStep built over them, the captured step, and generate()
+    DecodeLoop      the rows' state arrays (include/qqq_amd_step.h), the one PagedStep built over them, the captured step, and generate()
+    SpecDecodeLoop  the same loop with draft_len guessed tokens behind every row's last one, verified on the device by ops.spec_advance
+                    (include/qqq_amd_spec.h): a replay emits 1 ... draft_len + 1 tokens per row.  Opt-in.
+    ngram_draft     the drafter's rule in plain Python: what the device computes from a row's history, and what the host writes at admission
 
 QuantLlamaForCausalLM.generate (qqq_amd/model.py) builds its batch anew on the host for every token: a PagedKVCache.step, an eager launch
 of every kernel, a tolist() before the next step.  Here the host only admits prompts (an eager packed prefill, the first token from
@@ -20,6 +23,25 @@ from . import ops
 from .paged import PagedKVCache, PagedStep
 
 
+def _check_loop(name, lm, cache, rows, max_len, sync_every, graph, u_stride_error=None):
+    """The checks every loop makes on its construction arguments, in this order -> the model's device.  `u_stride_error`: what the
+    loop's own check of u_stride found, or None."""
+    if not isinstance(cache, PagedKVCache):
+        raise TypeError(f"{name}: cache must be a PagedKVCache")
+    if rows < 1 or rows > 65535 or max_len < 1 or sync_every < 1:
+        raise ValueError(f"{name}: rows={rows}, max_len={max_len} and sync_every={sync_every} must be at least 1 (rows <= 65535)")
+    if u_stride_error:
+        raise ValueError(f"{name}: {u_stride_error}")
+    if max_len > cache.capacity:
+        raise ValueError(f"{name}: max_len={max_len} exceeds what the pool could hold ({cache.capacity} keys)")
+    dev = lm.lm_head.weight.device
+    if cache.k[0].device != dev:
+        raise RuntimeError(f"{name}: the model and the cache must be on the same device")
+    if graph and dev.type != "cuda":
+        raise RuntimeError(f"{name}: graph=True needs the model on the GPU (and the ops of a step have no CPU path)")
+    return dev
+
+
 class DecodeLoop:
     """`rows` decode rows over `cache` for sequences of at most `max_len` keys (prompt and generated tokens but the last).
 
@@ -32,21 +54,13 @@ class DecodeLoop:
     `captures` counts the captures: 1 for the life of the loop with graph=True.  The graph holds addresses: a model that is changed after
     the first generate() (fuse_*(), load_state_dict, .to()) needs a new loop."""
 
+    _name = "DecodeLoop"
+    _draws = 1  # variates a row uses per step
+
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, sync_every: int = 8, u_stride: int = 64, graph: bool = True):
-        if not isinstance(cache, PagedKVCache):
-            raise TypeError("DecodeLoop: cache must be a PagedKVCache")
         rows, max_len, sync_every, u_stride = int(rows), int(max_len), int(sync_every), int(u_stride)
-        if rows < 1 or rows > 65535 or max_len < 1 or sync_every < 1:
-            raise ValueError(f"DecodeLoop: rows={rows}, max_len={max_len} and sync_every={sync_every} must be at least 1 (rows <= 65535)")
-        if u_stride < sync_every:
-            raise ValueError(f"DecodeLoop: u_stride={u_stride} must cover the sync_every={sync_every} steps between two refills")
-        if max_len > cache.capacity:
-            raise ValueError(f"DecodeLoop: max_len={max_len} exceeds what the pool could hold ({cache.capacity} keys)")
-        dev = lm.lm_head.weight.device
-        if cache.k[0].device != dev:
-            raise RuntimeError("DecodeLoop: the model and the cache must be on the same device")
-        if graph and dev.type != "cuda":
-            raise RuntimeError("DecodeLoop: graph=True needs the model on the GPU (and the ops of a step have no CPU path)")
+        short = u_stride < sync_every and f"u_stride={u_stride} must cover the sync_every={sync_every} steps between two refills"
+        dev = _check_loop("DecodeLoop", lm, cache, rows, max_len, sync_every, graph, short)
         self.lm, self.cache, self.rows, self.max_len, self.sync_every, self.u_stride = lm, cache, rows, max_len, sync_every, u_stride
         self.graph, self.device, self.captures = bool(graph), dev, 0
         bs = cache.block_size
@@ -82,7 +96,7 @@ class DecodeLoop:
     def _capture(self) -> None:
         """Warm up and capture the step with every row idle (nothing but `tick` changes), on a side stream."""
         if bool((self.remaining != 0).any()):
-            raise RuntimeError("DecodeLoop: the step is captured with every row idle")
+            raise RuntimeError(f"{self._name}: the step is captured with every row idle")
         side = torch.cuda.Stream(self.device)
         side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(side):
@@ -98,11 +112,11 @@ class DecodeLoop:
         self.captures += 1
 
     def _run(self, steps: int, generator) -> None:
-        if self._used + steps > self.u_stride:  # tick is about to wrap: new variates, and the rows start over at the first
+        if self._used + steps * self._draws > self.u_stride:  # tick is about to wrap: new variates, and the rows start over at the first
             self.u.copy_(torch.rand((self.rows, self.u_stride), generator=generator, device=self.device))
             self.tick.zero_()
             self._used = 0
-        self._used += steps
+        self._used += steps * self._draws
         for _ in range(steps):
             if self._graph is not None:
                 self._graph.replay()
@@ -229,4 +243,229 @@ class DecodeLoop:
         return outs
 
 
-__all__ = ["DecodeLoop"]
+
+def ngram_draft(history: Sequence[int], draft_len: int, ngram_max: int = 3) -> List[int]:
+    """The `draft_len` tokens guessed to follow `history` by prompt lookup, the rule of include/qqq_amd_spec.h: for n = ngram_max down to 1
+    (only while n < len(history)) the latest earlier occurrence of the last n tokens; the first n that has one wins and the draft is what
+    followed it, copied with overlap (a match that runs into the end of the history continues its period).  With no match at all the
+    last token repeats.  Deterministic; ops.spec_advance computes the same tokens on the device."""
+    h = [int(t) for t in history]
+    draft_len, ngram_max, n_h = int(draft_len), int(ngram_max), len(h)
+    if not h or draft_len < 1 or ngram_max < 1:
+        raise ValueError("ngram_draft: history must hold a token, draft_len and ngram_max must be at least 1")
+    src = None
+    for n in range(min(ngram_max, n_h - 1), 0, -1):
+        tail = h[n_h - n:]
+        src = next((i + n for i in range(n_h - n - 1, -1, -1) if h[i:i + n] == tail), None)
+        if src is not None:
+            break
+    if src is None:
+        return [h[-1]] * draft_len
+    out: List[int] = []
+    for j in range(draft_len):
+        out.append(h[src + j] if src + j < n_h else out[src + j - n_h])
+    return out
+
+
+class SpecDecodeLoop(DecodeLoop):
+    """DecodeLoop with speculation: every row feeds its last token and `draft_len` drafted tokens through one forward pass (a chunk of
+    G = draft_len + 1 tokens per row through the paged prefill attention kernel, every token's logits), and ops.spec_advance draws a token
+    from each logits row, emits the draws behind a rightly guessed prefix -- 1 ... G tokens per row and step -- drafts the next chunk by
+    n-gram lookup in the row's history (ngram_draft) and advances or retires the row, all on the device.  The step is one captured graph
+    as in DecodeLoop.  Every emitted token is a plain sampler draw from logits computed on the true prefix: the output distribution is
+    DecodeLoop's at any temperature, top_k and top_p.  The tokens under a seed are not: a step uses G variates per row.  Greedy tokens
+    are DecodeLoop's up to near-ties of the logits (the head GEMM runs at another row count).
+
+    The model must have fuse_prefill() set: the per-sequence SDPA path reads lengths on the host.  A sequence needs
+    len(prompt) + max_new_tokens - 1 + draft_len keys of the pool and of max_len: the drafts behind its last token are written too.
+    ngram_max   the longest n-gram the drafter looks up (1 ... 4);  u_stride  default sync_every * G, a multiple of G
+    After a generate(): `accepted` drafts were accepted in `row_steps` steps of single rows, over `steps` steps of the loop; a row-step
+    emits 1 + its accepted drafts tokens."""
+
+    _name = "SpecDecodeLoop"
+
+    def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, draft_len: int = 4, ngram_max: int = 3, sync_every: int = 8,
+                 u_stride: Optional[int] = None, graph: bool = True):
+        rows, max_len, sync_every, draft_len, ngram_max = int(rows), int(max_len), int(sync_every), int(draft_len), int(ngram_max)
+        if draft_len < 1 or draft_len > 15 or ngram_max < 1 or ngram_max > 4:
+            raise ValueError(f"SpecDecodeLoop: draft_len={draft_len} must be in [1, 15] and ngram_max={ngram_max} in [1, 4]")
+        group = draft_len + 1
+        if u_stride is None:
+            u_stride = max(sync_every, 1) * group
+        u_stride = int(u_stride)
+        short = u_stride < sync_every * group and (f"u_stride={u_stride} must cover the sync_every={sync_every} steps between two refills, "
+                                                   f"draft_len + 1 = {group} variates each")
+        dev = _check_loop("SpecDecodeLoop", lm, cache, rows, max_len, sync_every, graph, short)
+        if rows * group > 65535:
+            raise ValueError(f"SpecDecodeLoop: rows={rows} times draft_len + 1 = {group} exceeds the sampler's 65535 logits rows")
+        if max_len <= draft_len:
+            raise ValueError(f"SpecDecodeLoop: max_len={max_len} must exceed draft_len={draft_len}")
+        if not all(getattr(layer.self_attn, "_prefill", False) for layer in lm.model.layers):
+            raise RuntimeError("SpecDecodeLoop: the model needs fuse_prefill(): a step is a chunk of draft_len + 1 tokens per row, and only "
+                               "the paged prefill attention kernel serves chunks without reading lengths on the host")
+        self.lm, self.cache, self.rows, self.max_len, self.sync_every, self.u_stride = lm, cache, rows, max_len, sync_every, u_stride
+        self.draft_len, self.ngram_max, self.group, self._draws = draft_len, ngram_max, group, group
+        self.graph, self.device, self.captures = bool(graph), dev, 0
+        self.accepted = self.row_steps = self.steps = 0
+        bs = cache.block_size
+        i32 = dict(dtype=torch.int32, device=dev)
+        i64 = dict(dtype=torch.int64, device=dev)
+        self.ids = torch.zeros((rows, group), **i64)
+        self.pos = torch.full((rows, group), -1, **i64)
+        self.slots = torch.full((rows, group), -1, **i64)
+        self.start = torch.full((rows,), -1, **i64)
+        self.block_table = torch.zeros((rows, -(-max_len // bs)), **i32)
+        self.remaining = torch.zeros(rows, **i32)
+        self.eos = torch.full((rows,), -1, **i32)
+        self.hist = torch.zeros((rows, max_len), **i32)
+        self.hist_len = torch.zeros(rows, **i32)
+        self.n_out = torch.zeros(rows, **i32)
+        self.n_acc = torch.zeros(rows, **i32)
+        self.tick = torch.zeros(rows, **i32)
+        self.u = torch.zeros((rows, u_stride), dtype=torch.float32, device=dev)
+        self.temperature = torch.zeros(rows * group, dtype=torch.float32, device=dev)
+        self.top_k = torch.zeros(rows * group, **i32)
+        self.top_p = torch.ones(rows * group, dtype=torch.float32, device=dev)
+        # the one step of every pass: a chunk of G tokens per row whose device tensors ARE the state arrays
+        self.step = PagedStep(seq_ids=[None] * rows, counts=[group] * rows, starts=[0] * rows, max_len=max_len, decode=False,
+                              pos=self.pos.view(-1), slots=self.slots.view(-1), block_table=self.block_table, last_pos=self.start,
+                              cu_tokens=torch.arange(rows + 1, **i32) * group, start_pos=self.start)
+        self._graph = None
+        self._used = u_stride
+
+    def _decode_step(self) -> None:
+        logits = self.lm(self.ids.view(-1), self.cache, self.step, all_rows=True)
+        ops.spec_advance(logits, self.temperature, self.top_k, self.top_p, self.u, self.tick, self.ids, self.pos, self.slots, self.start,
+                         self.block_table, self.remaining, self.eos, self.hist, self.hist_len, self.n_out, self.n_acc,
+                         self.cache.block_size, self.ngram_max)
+
+    @torch.no_grad()
+    def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
+                 generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None) -> List[List[int]]:
+        """DecodeLoop.generate's contract, admission and cleanup, with a budget of len(prompt) + max_new_tokens - 1 + draft_len keys per
+        sequence (reserved at once; the same sum must not exceed max_len).  The host writes an admitted row's history (the prompt and
+        its first token) and first drafts (ngram_draft); everything after that happens on the device.  The random draws: one torch.rand
+        per prefill pass, one torch.rand(rows, u_stride) at the first step of the call and then whenever u is used up; a step uses
+        draft_len + 1 variates per row, so sampled tokens differ from DecodeLoop's under the same seed."""
+        prompts = [list(p) for p in prompts]
+        if any(not p for p in prompts):
+            raise ValueError("SpecDecodeLoop.generate: every prompt needs at least one token")
+        outs: List[List[int]] = [[] for _ in prompts]
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens < 1 or not prompts:
+            return outs
+        K, G = self.draft_len, self.group
+        for p in prompts:
+            if len(p) + max_new_tokens - 1 + K > self.max_len:
+                raise ValueError(f"SpecDecodeLoop.generate: a prompt of {len(p)} tokens, {max_new_tokens} new ones and {K} drafts need "
+                                 f"{len(p) + max_new_tokens - 1 + K} keys, the loop was built for max_len={self.max_len}")
+        if self.graph and self._graph is None:
+            self._capture()
+        self._used = self.u_stride  # this call draws with its own generator alone
+        self.accepted = self.row_steps = self.steps = 0
+        cache, dev, bs = self.cache, self.device, self.cache.block_size
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        tag = object()
+        sid = lambda i: (tag, i)  # noqa: E731
+        waiting = deque(range(len(prompts)))
+        owner: List[Optional[int]] = [None] * self.rows
+        budget = [0] * self.rows  # an upper bound of the row's `remaining`, and so of the steps it still takes
+
+        def admit():
+            new = []
+            idle = [r for r in range(self.rows) if owner[r] is None]
+            while waiting and idle:
+                i = waiting[0]
+                keys = len(prompts[i]) + max_new_tokens - 1 + K
+                if -(-keys // bs) > cache.free_blocks:
+                    break
+                waiting.popleft()
+                cache.add(sid(i))
+                cache.reserve(sid(i), keys)
+                owner[idle[0]] = i
+                new.append((idle.pop(0), i))
+            if not new:
+                if waiting and all(o is None for o in owner):
+                    need = -(-(len(prompts[waiting[0]]) + max_new_tokens - 1 + K) // bs)
+                    raise RuntimeError(f"SpecDecodeLoop.generate: the pool's {cache.free_blocks} free blocks cannot hold a prompt that "
+                                       f"needs {need} (prompt, budget and drafts)")
+                return
+            seqs = [sid(i) for _, i in new]
+            ids = torch.tensor([t for _, i in new for t in prompts[i]], dtype=torch.int64, device=dev)
+            logits = self.lm(ids, cache, cache.step(seqs, [len(prompts[i]) for _, i in new]))
+            u = torch.rand(len(new), generator=generator, device=dev)
+            first = ops.sample_tokens(logits, temperature, top_k, top_p, u).tolist()
+            rows, tok, pos, slots, start, rem, tables, hist, hlen = [], [], [], [], [], [], [], [], []
+            for (r, i), t in zip(new, first):
+                outs[i].append(t)
+                if max_new_tokens == 1 or t == eos:
+                    cache.free(sid(i))
+                    owner[r] = None
+                    continue
+                blocks, p = cache.blocks(sid(i)), len(prompts[i])
+                h = prompts[i] + [t]
+                rows.append(r)
+                tok.append([t] + ngram_draft(h, K, self.ngram_max))
+                pos.append(list(range(p, p + G)))
+                slots.append([blocks[q // bs] * bs + q % bs for q in range(p, p + G)])
+                start.append(p)
+                rem.append(max_new_tokens - 1)
+                tables.append(blocks + [0] * (self.block_table.shape[1] - len(blocks)))
+                hist.append(h + [0] * (self.hist.shape[1] - len(h)))
+                hlen.append(len(h))
+                budget[r] = max_new_tokens - 1
+            if not rows:
+                return
+            at = torch.tensor(rows, dtype=torch.int64, device=dev)
+            n = len(rows)
+            per_draw = lambda t: t.view(self.rows, G)  # noqa: E731
+            for dst, src, dtype in ((self.ids, tok, torch.int64), (self.pos, pos, torch.int64), (self.slots, slots, torch.int64),
+                                    (self.start, start, torch.int64), (self.remaining, rem, torch.int32),
+                                    (self.eos, [eos] * n, torch.int32), (self.n_out, [0] * n, torch.int32),
+                                    (self.n_acc, [0] * n, torch.int32), (self.block_table, tables, torch.int32),
+                                    (self.hist, hist, torch.int32), (self.hist_len, hlen, torch.int32),
+                                    (per_draw(self.temperature), [[float(temperature)] * G] * n, torch.float32),
+                                    (per_draw(self.top_k), [[int(top_k)] * G] * n, torch.int32),
+                                    (per_draw(self.top_p), [[float(top_p)] * G] * n, torch.float32)):
+                dst[at] = torch.tensor(src, dtype=dtype).to(dev)
+
+        try:
+            while True:
+                admit()
+                active = [r for r in range(self.rows) if owner[r] is not None]
+                if not active:
+                    if waiting:
+                        continue
+                    break
+                steps = min(self.sync_every, max(budget[r] for r in active))
+                self._run(steps, generator)
+                self.steps += steps
+                n_out, remaining, n_acc = torch.stack((self.n_out, self.remaining, self.n_acc)).tolist()  # the sync: one transfer
+                done = [r for r in active if remaining[r] == 0]
+                for r in active:
+                    budget[r] = remaining[r]
+                if done:
+                    toks = self.hist[torch.tensor(done, dtype=torch.int64, device=dev)].tolist()
+                    for r, row in zip(done, toks):
+                        i = owner[r]
+                        first = len(prompts[i]) + 1  # the prompt and the prefill's token
+                        outs[i].extend(row[first:first + n_out[r]])
+                        self.accepted += n_acc[r]
+                        self.row_steps += n_out[r] - n_acc[r]  # a row-step emits one token more than it accepts drafts
+                        cache.free(sid(i))
+                        owner[r] = None
+        except BaseException:
+            # leave the loop idle and the caller's pool as it was found
+            for r, i in enumerate(owner):
+                if i is not None:
+                    cache.free(sid(i))
+            self.remaining.zero_()
+            self.pos.fill_(-1)
+            self.slots.fill_(-1)
+            self.start.fill_(-1)
+            self.ids.zero_()
+            raise
+        return outs
+
+
+__all__ = ["DecodeLoop", "SpecDecodeLoop", "ngram_draft"]

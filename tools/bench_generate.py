@@ -13,6 +13,16 @@ ratio generate / loop graph, and at batch 1 whether the captured loop's median l
 round-to-round spread (max - min).
 
     python tools/bench_generate.py [--batch 1,16] [--rounds 5] [--baseline-only] [--out profiles/decode_loop_bench.json]
+
+With --draft-len 0,2,4,7 the tool measures the speculative loop instead (SpecDecodeLoop, qqq_amd/serve.py) and writes
+profiles/spec_decode_bench.json: per batch and draft length K the time of one replayed step ((wall time with NEW tokens - wall time with 1
+token) / the steps the loop replayed, the same cold protocol; K = 0 is DecodeLoop), r(K) = step time at K over step time at 0, the
+break-even mean number of accepted drafts per row-step r(K) - 1, and tokens/s in two regimes: the random model, where next to no draft
+comes true (the cost of the wider step, the worst case), and the same model rigged to emit a period of 16 tokens (embeddings scaled up,
+lm_head row (t + 1) % 16 set to the embedding of t), where nearly every draft does (the upper bound).  The acceptance itself is measured
+and written, not assumed.  Acceptance on real text is not measured: that needs a checkpoint and a tokenizer.
+
+    python tools/bench_generate.py --draft-len 0,2,4,7 [--batch 1,16] [--rounds 5] [--out profiles/spec_decode_bench.json]
 """
 import argparse
 import json
@@ -80,17 +90,117 @@ def point(lm, batch, rounds, baseline_only, dev):
     return res
 
 
+PERIOD, RIG_SCALE = 16, 8.0
+
+
+def rig(lm):
+    """Make the model emit the period 0, 1, ... PERIOD - 1: the embeddings dominate the residual stream, and the head's row (t + 1) % PERIOD
+    is the embedding of t (every other row 0).  In place: captured graphs keep their addresses."""
+    emb = lm.model.embed_tokens.weight.data
+    emb.mul_(RIG_SCALE)
+    head = lm.lm_head.weight.data
+    head.zero_()
+    for t in range(PERIOD):
+        head[(t + 1) % PERIOD].copy_(emb[t] / RIG_SCALE)
+
+
+def spec_point(lm, batch, drafts, rounds, rigged, dev):
+    import torch
+
+    from bench_model import VOCAB
+    from qqq_amd import DecodeLoop, SpecDecodeLoop
+
+    g = torch.Generator().manual_seed(batch)
+    if rigged:
+        prompts = [[(s + i) % PERIOD for i in range(PROMPT)] for s in range(batch)]
+    else:
+        prompts = [torch.randint(0, VOCAB, (PROMPT,), generator=g).tolist() for _ in range(batch)]
+    loops = {}
+    for k in drafts:
+        max_len = -(-(PROMPT + NEW - 1 + k) // BS) * BS
+        cache = lm.new_cache(batch * (max_len // BS), BS)
+        loops[k] = (SpecDecodeLoop(lm, cache, rows=batch, max_len=max_len, draft_len=k, sync_every=SYNC_EVERY) if k else
+                    DecodeLoop(lm, cache, rows=batch, max_len=max_len, sync_every=SYNC_EVERY))
+
+    def timed(loop, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = loop.generate(prompts, n)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    stats = {}
+    for k, loop in loops.items():  # warm-up: code objects, workspaces, rope tables, the capture
+        timed(loop, 1)
+        out = timed(loop, NEW)[1]
+        assert all(len(o) == NEW for o in out), k
+        steps = loop.steps if k else NEW - 1
+        stats[k] = {"steps": steps, "row_steps": loop.row_steps if k else batch * (NEW - 1), "accepted": loop.accepted if k else 0}
+    values = {k: [] for k in loops}
+    for _ in range(rounds):
+        for k, loop in loops.items():
+            short, full = timed(loop, 1)[0], timed(loop, NEW)[0]
+            values[k].append(full - short)
+    res = {"batch": batch, "model": "rigged to a period" if rigged else "random", "prompt_tokens": PROMPT, "new_tokens": NEW, "layers": LAYERS,
+           "draft_len": {}}
+    for k, v in values.items():
+        sec, st = statistics.median(v), stats[k]
+        res["draft_len"][str(k)] = {
+            "steps": st["steps"], "accepted_per_row_step": round(st["accepted"] / max(st["row_steps"], 1), 3),
+            "step_us": round(sec / st["steps"] * 1e6, 1), "tokens_per_s": round(batch * (NEW - 1) / sec, 1),
+            "rounds_ms": [round(x * 1e3, 2) for x in v]}
+    base = res["draft_len"].get("0")
+    if base:
+        for k, e in res["draft_len"].items():
+            e["r"] = round(e["step_us"] / base["step_us"], 3)
+            e["break_even_accepted_per_row_step"] = round(e["r"] - 1, 3)
+            e["tokens_per_s_over_draft_len_0"] = round(e["tokens_per_s"] / base["tokens_per_s"], 3)
+    return res
+
+
+def spec_main(args):
+    import torch
+
+    from bench_model import build
+
+    drafts = sorted({int(k) for k in args.draft_len.split(",")})
+    dev = torch.device("cuda:0")
+    lm = build(LAYERS, dev).fuse_prefill()
+    batches = list(map(int, args.batch.split(",")))
+    with torch.no_grad():
+        points = [spec_point(lm, b, drafts, args.rounds, False, dev) for b in batches]
+        rig(lm)
+        points += [spec_point(lm, b, drafts, args.rounds, True, dev) for b in batches]
+    out = {"tool": "tools/bench_generate.py --draft-len " + args.draft_len, "device": torch.cuda.get_device_name(0),
+           "shape": "Llama-2-7B layers, per-channel W4A8, fuse_qkv(), fuse_prefill(), paged fp16 cache, block 16, greedy, ngram_max 3",
+           "sync_every": SYNC_EVERY, "rounds": args.rounds,
+           "not_measured": "acceptance on real text: no checkpoint or tokenizer was available; the two models bracket it", "points": points}
+    path = args.out or os.path.join(ROOT, "profiles", "spec_decode_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"batch {p['batch']:3d} {p['model']}: " + "  ".join(
+            f"K={k} {e['step_us']:.0f} us/step r={e.get('r')} acc={e['accepted_per_row_step']} {e['tokens_per_s']:.0f} tok/s"
+            for k, e in p["draft_len"].items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", default="1,16")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--baseline-only", action="store_true", help="time generate() alone (runs on a tree without DecodeLoop)")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "decode_loop_bench.json"))
+    ap.add_argument("--draft-len", default=None, help="e.g. 0,2,4,7: measure the speculative loop instead (profiles/spec_decode_bench.json)")
+    ap.add_argument("--out", default=None, help="default profiles/decode_loop_bench.json, or profiles/spec_decode_bench.json with --draft-len")
     args = ap.parse_args()
     import torch
 
     if not torch.cuda.is_available():
         sys.exit("bench_generate.py needs a GPU: a timing taken elsewhere says nothing")
+    if args.draft_len:
+        return spec_main(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "decode_loop_bench.json")
     from bench_model import build
 
     dev = torch.device("cuda:0")
