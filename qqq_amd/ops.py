@@ -65,6 +65,24 @@ def _stream_for(t: torch.Tensor):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def _dt(dtype) -> str:
+    return str(dtype).replace("torch.", "")
+
+
+def _same_gpu(name, ts):
+    # every tensor of `ts` on the GPU, and on the GPU of the first
+    if not all(t.is_cuda for t in ts):
+        raise RuntimeError(f"{name}: every tensor must be on the GPU (there is no CPU path)")
+    if any(t.device != ts[0].device for t in ts):
+        raise RuntimeError(f"{name}: every tensor must be on the same GPU")
+
+
+def _raise_lib(name, err):
+    # the library's own refusal of a call: its error code and message, under the op's name (None: the GEMM entry points, _raise_for)
+    if err:
+        raise RuntimeError(f"qqq_amd: {name + ' ' if name else ''}error {err}: {_lib.last_error()}")
+
+
 def _check_common(A, B, C, D, s1, s2, s3, workspace, max_par):
     # the reference's own checks (csrc/qqq_gemm.cu:1062-1075) ...
     prob_m, prob_n, prob_k = A.size(0), C.size(1), A.size(1)
@@ -111,7 +129,7 @@ def _raise_for(err, prob_m, prob_n, prob_k, thread_k, thread_n, groupsize):
         raise RuntimeError(
             f"No kernel implementation for thread_k={thread_k}, thread_n={thread_n}, groupsize={groupsize}."
         )
-    raise RuntimeError(f"qqq_amd: error {err}: {_lib.last_error()}")
+    _raise_lib(None, err)
 
 
 def _check_w8(W8, prob_k, prob_n, groupsize, device):
@@ -194,8 +212,7 @@ def _expand_int8_impl(B: torch.Tensor, s_group: torch.Tensor) -> torch.Tensor:
         raise RuntimeError("expand_int8: s_group must be the contiguous fp16 [k/128, n] tensor of a per-group layer on B's device (or empty: per-channel)")
     W8 = torch.empty(k * n, dtype=torch.int8, device=B.device)
     err = _lib.lib().qqq_expand_int8(_ptr(B), _ptr(s_group), _ptr(W8), k, n, 128 if grouped else -1, B.device.index or 0, _stream_for(B))
-    if err:
-        raise RuntimeError(f"qqq_amd: expand_int8 error {err}: {_lib.last_error()}")
+    _raise_lib("expand_int8", err)
     return W8
 
 
@@ -302,8 +319,7 @@ def _dynamic_quant_impl(x: torch.Tensor):
     xq = torch.empty((m, k), dtype=torch.int8, device=x.device)
     s1 = torch.empty((m, 1), dtype=torch.float32, device=x.device)
     err = L.qqq_dynamic_quant(_ptr(x2), _ptr(xq), _ptr(s1), m, k, x.device.index or 0, _stream_for(x))
-    if err:
-        raise RuntimeError(f"qqq_amd: dynamic_quant error {err}: {_lib.last_error()}")
+    _raise_lib("dynamic_quant", err)
     return xq.reshape(x.shape), s1.reshape(x.shape[:-1] + (1,))
 
 
@@ -403,8 +419,7 @@ def _rmsnorm_quant_impl(x, weight, eps, residual, return_y):
     y = torch.empty((m, k) if return_y else (0,), dtype=torch.float16, device=x.device)
     err = _lib.lib().qqq_rmsnorm_quant(_ptr(x2), _ptr(residual), _ptr(weight.contiguous()), float(eps), _ptr(y), _ptr(xq), _ptr(s1), m, k,
                                        x.device.index or 0, _stream_for(x))
-    if err:
-        raise RuntimeError(f"qqq_amd: rmsnorm_quant error {err}: {_lib.last_error()}")
+    _raise_lib("rmsnorm_quant", err)
     return xq.reshape(x.shape), s1.reshape(x.shape[:-1] + (1,)), (y.reshape(x.shape) if return_y else y)
 
 
@@ -457,8 +472,7 @@ def _silu_mul_quant_impl(gate, up, return_y):
     y = torch.empty((m, i) if return_y else (0,), dtype=torch.float16, device=gate.device)
     err = _lib.lib().qqq_silu_mul_quant(_ptr(g2), ld_g, _ptr(u2), ld_u, _ptr(y), _ptr(xq), _ptr(s1), m, i, gate.device.index or 0,
                                         _stream_for(gate))
-    if err:
-        raise RuntimeError(f"qqq_amd: silu_mul_quant error {err}: {_lib.last_error()}")
+    _raise_lib("silu_mul_quant", err)
     return xq.reshape(gate.shape), s1.reshape(gate.shape[:-1] + (1,)), (y.reshape(gate.shape) if return_y else y)
 
 
@@ -505,10 +519,7 @@ def _rope_qkv_shapes(q, k, v, cos, pos, k_cache):
 
 def _rope_qkv_impl(q, k, v, cos, sin, pos, k_cache, v_cache):
     ts = (q, k, v, cos, sin, pos, k_cache, v_cache)
-    if not all(t.is_cuda for t in ts):
-        raise RuntimeError("rope_qkv: every tensor must be on the GPU (there is no CPU path)")
-    if any(t.device != q.device for t in ts):
-        raise RuntimeError("rope_qkv: every tensor must be on the same GPU")
+    _same_gpu("rope_qkv", ts)
     if any(t.dtype != torch.float16 for t in (q, k, v, cos, sin, k_cache, v_cache)) or pos.dtype != torch.int64:
         raise RuntimeError("rope_qkv: q, k, v, cos, sin and the caches must be fp16, pos int64")
     b, s, h, kvh, d, cap = _rope_qkv_shapes(q, k, v, cos, pos, k_cache)
@@ -524,8 +535,7 @@ def _rope_qkv_impl(q, k, v, cos, sin, pos, k_cache, v_cache):
     cos, sin, pos = cos.contiguous(), sin.contiguous(), pos.contiguous()
     err = _lib.lib().qqq_rope_qkv(_ptr(q2), ld_q, _ptr(k2), ld_k, _ptr(v2), ld_v, _ptr(cos), _ptr(sin), cos.shape[0], _ptr(pos),
                                   _ptr(q_out), _ptr(k_cache), _ptr(v_cache), b, s, h, kvh, d, cap, q.device.index or 0, _stream_for(q))
-    if err:
-        raise RuntimeError(f"qqq_amd: rope_qkv error {err}: {_lib.last_error()}")
+    _raise_lib("rope_qkv", err)
     return q_out
 
 
@@ -574,10 +584,7 @@ def _decode_attention_shapes(q_out, k_cache, pos, max_len):
 
 def _decode_attention_impl(q_out, k_cache, v_cache, pos, scale, max_len, return_fp16):
     ts = (q_out, k_cache, v_cache, pos)
-    if not all(t.is_cuda for t in ts):
-        raise RuntimeError("decode_attention: every tensor must be on the GPU (there is no CPU path)")
-    if any(t.device != q_out.device for t in ts):
-        raise RuntimeError("decode_attention: every tensor must be on the same GPU")
+    _same_gpu("decode_attention", ts)
     if any(t.dtype != torch.float16 for t in (q_out, k_cache, v_cache)) or pos.dtype != torch.int64:
         raise RuntimeError("decode_attention: q_out and the caches must be fp16, pos int64")
     b, h, kvh, d, cap, max_len = _decode_attention_shapes(q_out, k_cache, pos, max_len)
@@ -597,8 +604,7 @@ def _decode_attention_impl(q_out, k_cache, v_cache, pos, scale, max_len, return_
     q2, pos = q_out.contiguous(), pos.contiguous()
     err = L.qqq_decode_attn(_ptr(q2), _ptr(k_cache), _ptr(v_cache), _ptr(pos), float(scale), _ptr(o16), _ptr(xq), _ptr(s1), _ptr(ws),
                             ws.numel(), b, h, kvh, d, cap, max_len, dev.index or 0, _stream_for(q_out))
-    if err:
-        raise RuntimeError(f"qqq_amd: decode_attention error {err}: {_lib.last_error()}")
+    _raise_lib("decode_attention", err)
     return xq, s1, o16
 
 
@@ -651,10 +657,7 @@ def _kv8_check_caches(name, k_cache, v_cache, k_scale, v_scale):
 
 def _rope_qkv_kv8_impl(q, k, v, cos, sin, pos, k_cache, v_cache, k_scale, v_scale):
     ts = (q, k, v, cos, sin, pos, k_cache, v_cache, k_scale, v_scale)
-    if not all(t.is_cuda for t in ts):
-        raise RuntimeError("rope_qkv_kv8: every tensor must be on the GPU (there is no CPU path)")
-    if any(t.device != q.device for t in ts):
-        raise RuntimeError("rope_qkv_kv8: every tensor must be on the same GPU")
+    _same_gpu("rope_qkv_kv8", ts)
     if any(t.dtype != torch.float16 for t in (q, k, v, cos, sin)) or pos.dtype != torch.int64:
         raise RuntimeError("rope_qkv_kv8: q, k, v, cos and sin must be fp16, pos int64")
     _kv8_check_caches("rope_qkv_kv8", k_cache, v_cache, k_scale, v_scale)
@@ -669,8 +672,7 @@ def _rope_qkv_kv8_impl(q, k, v, cos, sin, pos, k_cache, v_cache, k_scale, v_scal
     err = _lib.lib().qqq_rope_qkv_kv8(_ptr(q2), ld_q, _ptr(k2), ld_k, _ptr(v2), ld_v, _ptr(cos), _ptr(sin), cos.shape[0], _ptr(pos),
                                       _ptr(q_out), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), b, s, h, kvh, d, cap,
                                       q.device.index or 0, _stream_for(q))
-    if err:
-        raise RuntimeError(f"qqq_amd: rope_qkv_kv8 error {err}: {_lib.last_error()}")
+    _raise_lib("rope_qkv_kv8", err)
     return q_out
 
 
@@ -702,10 +704,7 @@ def rope_qkv_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: torch.T
 
 def _decode_attention_kv8_impl(q_out, k_cache, v_cache, k_scale, v_scale, pos, scale, max_len, return_fp16):
     ts = (q_out, k_cache, v_cache, k_scale, v_scale, pos)
-    if not all(t.is_cuda for t in ts):
-        raise RuntimeError("decode_attention_kv8: every tensor must be on the GPU (there is no CPU path)")
-    if any(t.device != q_out.device for t in ts):
-        raise RuntimeError("decode_attention_kv8: every tensor must be on the same GPU")
+    _same_gpu("decode_attention_kv8", ts)
     if q_out.dtype != torch.float16 or pos.dtype != torch.int64:
         raise RuntimeError("decode_attention_kv8: q_out must be fp16, pos int64")
     _kv8_check_caches("decode_attention_kv8", k_cache, v_cache, k_scale, v_scale)
@@ -722,8 +721,7 @@ def _decode_attention_kv8_impl(q_out, k_cache, v_cache, k_scale, v_scale, pos, s
     q2, pos = q_out.contiguous(), pos.contiguous()
     err = L.qqq_decode_attn_kv8(_ptr(q2), _ptr(k_cache), _ptr(v_cache), _ptr(k_scale), _ptr(v_scale), _ptr(pos), float(scale), _ptr(o16),
                                 _ptr(xq), _ptr(s1), _ptr(ws), ws.numel(), b, h, kvh, d, cap, max_len, dev.index or 0, _stream_for(q_out))
-    if err:
-        raise RuntimeError(f"qqq_amd: decode_attention_kv8 error {err}: {_lib.last_error()}")
+    _raise_lib("decode_attention_kv8", err)
     return xq, s1, o16
 
 
@@ -799,10 +797,7 @@ def _rope_qkv_paged_impl(q, k, v, cos, sin, pos, slots, k_pool, v_pool, k_scale=
     kv8 = k_scale is not None
     name = "rope_qkv_paged_kv8" if kv8 else "rope_qkv_paged"
     ts = (q, k, v, cos, sin, pos, slots, k_pool, v_pool) + ((k_scale, v_scale) if kv8 else ())
-    if not all(t.is_cuda for t in ts):
-        raise RuntimeError(f"{name}: every tensor must be on the GPU (there is no CPU path)")
-    if any(t.device != q.device for t in ts):
-        raise RuntimeError(f"{name}: every tensor must be on the same GPU")
+    _same_gpu(name, ts)
     if any(t.dtype != torch.float16 for t in (q, k, v, cos, sin)) or pos.dtype != torch.int64 or slots.dtype != torch.int64:
         raise RuntimeError(f"{name}: q, k, v, cos and sin must be fp16, pos and slots int64")
     _paged_check_pools(name, k_pool, v_pool, k_scale, v_scale)
@@ -822,8 +817,7 @@ def _rope_qkv_paged_impl(q, k, v, cos, sin, pos, slots, k_pool, v_pool, k_scale=
         err = L.qqq_rope_qkv_paged_kv8(*head, _ptr(k_scale), _ptr(v_scale), *tail)
     else:
         err = L.qqq_rope_qkv_paged(*head, *tail)
-    if err:
-        raise RuntimeError(f"qqq_amd: {name} error {err}: {_lib.last_error()}")
+    _raise_lib(name, err)
     return q_out
 
 
@@ -904,10 +898,7 @@ def _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale,
     kv8 = k_scale is not None
     name = "decode_attention_paged_kv8" if kv8 else "decode_attention_paged"
     ts = (q_out, k_pool, v_pool, block_table, pos) + ((k_scale, v_scale) if kv8 else ())
-    if not all(t.is_cuda for t in ts):
-        raise RuntimeError(f"{name}: every tensor must be on the GPU (there is no CPU path)")
-    if any(t.device != q_out.device for t in ts):
-        raise RuntimeError(f"{name}: every tensor must be on the same GPU")
+    _same_gpu(name, ts)
     if q_out.dtype != torch.float16 or pos.dtype != torch.int64 or block_table.dtype != torch.int32:
         raise RuntimeError(f"{name}: q_out must be fp16, pos int64 and block_table int32")
     _paged_check_pools(name, k_pool, v_pool, k_scale, v_scale)
@@ -928,8 +919,7 @@ def _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale,
         err = L.qqq_decode_attn_paged_kv8(_ptr(q2), _ptr(k_pool), _ptr(v_pool), _ptr(k_scale), _ptr(v_scale), *tail)
     else:
         err = L.qqq_decode_attn_paged(_ptr(q2), _ptr(k_pool), _ptr(v_pool), *tail)
-    if err:
-        raise RuntimeError(f"qqq_amd: {name} error {err}: {_lib.last_error()}")
+    _raise_lib(name, err)
     return xq, s1, o16
 
 
@@ -1018,10 +1008,7 @@ def _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens,
     kv8 = k_scale is not None
     name = "prefill_attention_paged_kv8" if kv8 else "prefill_attention_paged"
     ts = (q_out, k_pool, v_pool, block_table, cu_tokens, start_pos) + ((k_scale, v_scale) if kv8 else ())
-    if not all(t.is_cuda for t in ts):
-        raise RuntimeError(f"{name}: every tensor must be on the GPU (there is no CPU path)")
-    if any(t.device != q_out.device for t in ts):
-        raise RuntimeError(f"{name}: every tensor must be on the same GPU")
+    _same_gpu(name, ts)
     if q_out.dtype != torch.float16 or start_pos.dtype != torch.int64 or block_table.dtype != torch.int32 or cu_tokens.dtype != torch.int32:
         raise RuntimeError(f"{name}: q_out must be fp16, start_pos int64, block_table and cu_tokens int32")
     _paged_check_pools(name, k_pool, v_pool, k_scale, v_scale)
@@ -1042,8 +1029,7 @@ def _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens,
         err = L.qqq_prefill_attn_paged_kv8(_ptr(q2), _ptr(k_pool), _ptr(v_pool), _ptr(k_scale), _ptr(v_scale), *tail)
     else:
         err = L.qqq_prefill_attn_paged(_ptr(q2), _ptr(k_pool), _ptr(v_pool), *tail)
-    if err:
-        raise RuntimeError(f"qqq_amd: {name} error {err}: {_lib.last_error()}")
+    _raise_lib(name, err)
     return xq, s1, o16
 
 
@@ -1128,12 +1114,18 @@ def _sample_param(name, v, rows, dtype, device, op="sample_tokens"):
     return torch.full((rows,), v, dtype=dtype, device=device)
 
 
+def _logits_rows(logits, vocab):
+    # a row-strided view (the first vocab columns of a padded head output) is taken in place; anything else is copied into such rows
+    if logits.stride(1) != 1 or logits.stride(0) < vocab or logits.stride(0) % 8 or logits.data_ptr() % 16:
+        rows8 = torch.empty((logits.shape[0], vocab + (-vocab) % 8), dtype=torch.float16, device=logits.device)
+        rows8[:, :vocab] = logits
+        logits = rows8[:, :vocab]
+    return logits
+
+
 def _sample_tokens_impl(logits, temperature, top_k, top_p, u):
     ts = (logits, temperature, top_k, top_p, u)
-    if not all(t.is_cuda for t in ts):
-        raise RuntimeError("sample_tokens: every tensor must be on the GPU (there is no CPU path)")
-    if any(t.device != logits.device for t in ts):
-        raise RuntimeError("sample_tokens: every tensor must be on the same GPU")
+    _same_gpu("sample_tokens", ts)
     if logits.dtype != torch.float16 or logits.dim() != 2:
         raise RuntimeError("sample_tokens: logits must be fp16 [rows, vocab]")
     rows, vocab = logits.shape
@@ -1146,16 +1138,11 @@ def _sample_tokens_impl(logits, temperature, top_k, top_p, u):
     tokens = torch.empty((rows,), dtype=torch.int64, device=logits.device)
     if rows == 0:
         return tokens
-    # a row-strided view (the first vocab columns of a padded head output) is taken in place; anything else is copied into such rows
-    if logits.stride(1) != 1 or logits.stride(0) < vocab or logits.stride(0) % 8 or logits.data_ptr() % 16:
-        rows8 = torch.empty((rows, vocab + (-vocab) % 8), dtype=torch.float16, device=logits.device)
-        rows8[:, :vocab] = logits
-        logits = rows8[:, :vocab]
+    logits = _logits_rows(logits, vocab)
     err = _lib.lib().qqq_sample_tokens(_ptr(logits), logits.stride(0), _ptr(temperature.contiguous()), _ptr(top_k.contiguous()),
                                        _ptr(top_p.contiguous()), _ptr(u.contiguous()), _ptr(tokens), rows, vocab,
                                        logits.device.index or 0, _stream_for(logits))
-    if err:
-        raise RuntimeError(f"qqq_amd: sample_tokens error {err}: {_lib.last_error()}")
+    _raise_lib("sample_tokens", err)
     return tokens
 
 
@@ -1198,8 +1185,7 @@ def _token_logprobs_check(logits, targets):
         raise RuntimeError("token_logprobs: logits must be fp16 [rows, vocab]")
     rows, vocab = logits.shape
     if targets.dtype != torch.int64 or targets.dim() != 1 or targets.shape[0] != rows:
-        raise RuntimeError(f"token_logprobs: targets must be int64 [{rows}], one entry per row, not "
-                           f"{str(targets.dtype).replace('torch.', '')} {tuple(targets.shape)}")
+        raise RuntimeError(f"token_logprobs: targets must be int64 [{rows}], one entry per row, not {_dt(targets.dtype)} {tuple(targets.shape)}")
     if vocab < 1 or vocab > 262144 or rows > 1048576:
         raise RuntimeError(f"token_logprobs: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows <= 1048576")
     return rows, vocab
@@ -1215,15 +1201,10 @@ def _token_logprobs_impl(logits, targets, return_argmax):
     argmax = torch.empty((rows if return_argmax else 0,), dtype=torch.int64, device=logits.device)
     if rows == 0:
         return logprob, argmax
-    # a row-strided view (the first vocab columns of a padded head output) is taken in place; anything else is copied into such rows
-    if logits.stride(1) != 1 or logits.stride(0) < vocab or logits.stride(0) % 8 or logits.data_ptr() % 16:
-        rows8 = torch.empty((rows, vocab + (-vocab) % 8), dtype=torch.float16, device=logits.device)
-        rows8[:, :vocab] = logits
-        logits = rows8[:, :vocab]
+    logits = _logits_rows(logits, vocab)
     err = _lib.lib().qqq_token_logprobs(_ptr(logits), logits.stride(0), _ptr(targets.contiguous()), _ptr(logprob), _ptr(argmax), rows, vocab,
                                         logits.device.index or 0, _stream_for(logits))
-    if err:
-        raise RuntimeError(f"qqq_amd: token_logprobs error {err}: {_lib.last_error()}")
+    _raise_lib("token_logprobs", err)
     return logprob, argmax
 
 
@@ -1266,58 +1247,86 @@ _ADVANCE_STATE = (("tick", torch.int32), ("ids", torch.int64), ("pos", torch.int
                   ("eos", torch.int32), ("n_out", torch.int32))
 
 
-def _sample_advance_check(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out, block_size):
-    # the checks that need no device: dtypes and shapes (shared by the launch and the fake implementation)
+# The checks of sample_advance and spec_advance that need no device -- dtypes and shapes, shared by the launch and the fake implementation
+# -- are three helpers, called in the order the checks have always run in (an input with several faults reports the first): between them
+# each op checks what it alone has.
+
+def _sampler_inputs_check(op, logits, temperature, top_k, top_p, u, ids=None):
+    # logits, the sampler's parameters and u -> (rows, group, vocab); `ids`: spec_advance's [rows, group], None: a logits row per row
+    spec = ids is not None
     if logits.dtype != torch.float16 or logits.dim() != 2:
-        raise RuntimeError("sample_advance: logits must be fp16 [rows, vocab]")
-    rows, vocab = logits.shape
+        raise RuntimeError(f"{op}: logits must be fp16 [{'rows * (draft_len + 1)' if spec else 'rows'}, vocab]")
+    m, vocab = logits.shape
+    rows, group = m, 1
+    if spec:
+        if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[1] < 2 or ids.shape[1] > 16:
+            raise RuntimeError(f"{op}: ids must be int64 [rows, draft_len + 1] with 1 <= draft_len <= 15, not {_dt(ids.dtype)} "
+                               f"{tuple(ids.shape)}")
+        rows, group = ids.shape
+        if m != rows * group:
+            raise RuntimeError(f"{op}: logits hold {m} rows, ids {tuple(ids.shape)} asks for {rows * group}")
     if temperature.dtype != torch.float32 or top_p.dtype != torch.float32 or u.dtype != torch.float32 or top_k.dtype != torch.int32:
-        raise RuntimeError("sample_advance: temperature, top_p and u must be f32, top_k int32")
-    if any(t.numel() != rows for t in (temperature, top_k, top_p)):
-        raise RuntimeError(f"sample_advance: temperature, top_k and top_p must hold one entry per row ({rows})")
-    if u.dim() != 2 or u.shape[0] != rows or u.shape[1] < 1:
-        raise RuntimeError(f"sample_advance: u must be f32 [{rows}, u_stride] with u_stride >= 1, not {tuple(u.shape)}")
-    state = dict(tick=tick, ids=ids, pos=pos, slots=slots, remaining=remaining, eos=eos, n_out=n_out)
-    for name, dtype in _ADVANCE_STATE:
+        raise RuntimeError(f"{op}: temperature, top_p and u must be f32, top_k int32")
+    if any(t.numel() != m for t in (temperature, top_k, top_p)):
+        raise RuntimeError(f"{op}: temperature, top_k and top_p must hold one entry per {'logits row' if spec else 'row'} ({m})")
+    if u.dim() != 2 or u.shape[0] != rows or u.shape[1] < group:
+        raise RuntimeError(f"{op}: u must be f32 [{rows}, u_stride] with u_stride >= {f'draft_len + 1 = {group}' if spec else 1}, not "
+                           f"{tuple(u.shape)}")
+    return rows, group, vocab
+
+
+def _row_state_check(op, rows, table, state, block_table):
+    # the arrays that hold one entry per row, as `table` (_ADVANCE_STATE, _SPEC_ROW_STATE) lists them, and the block table
+    for name, dtype in table:
         t = state[name]
         if t.dtype != dtype or t.dim() != 1 or t.shape[0] != rows:
-            raise RuntimeError(f"sample_advance: {name} must be {str(dtype).replace('torch.', '')} [{rows}], not "
-                               f"{str(t.dtype).replace('torch.', '')} {tuple(t.shape)}")
+            raise RuntimeError(f"{op}: {name} must be {_dt(dtype)} [{rows}], not {_dt(t.dtype)} {tuple(t.shape)}")
     if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != rows or block_table.shape[1] < 1:
-        raise RuntimeError(f"sample_advance: block_table must be int32 [{rows}, blocks per row >= 1], not {tuple(block_table.shape)}")
+        raise RuntimeError(f"{op}: block_table must be int32 [{rows}, blocks per row >= 1], not {tuple(block_table.shape)}")
+
+
+def _sampler_limits_check(op, logits, block_size, ngram_max=None):
+    # `ngram_max`: spec_advance's, whose logits hold draft_len + 1 rows per row
+    if block_size not in (16, 32, 64, 128, 256):
+        raise RuntimeError(f"{op}: block_size must be a power of two in [16, 256], not {block_size}")
+    if ngram_max is not None and (ngram_max < 1 or ngram_max > 4):
+        raise RuntimeError(f"{op}: ngram_max must be in [1, 4], not {ngram_max}")
+    if logits.shape[1] < 1 or logits.shape[1] > 262144 or logits.shape[0] > 65535:
+        raise RuntimeError(f"{op}: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, "
+                           f"{'rows' if ngram_max is None else 'rows * (draft_len + 1)'} <= 65535")
+
+
+def _in_place_check(op, named):
+    # everything written is written in place: no copy may stand in for a state array
+    for name, t in named:
+        if not t.is_contiguous():
+            raise RuntimeError(f"{op}: {name} must be contiguous (the state is updated in place)")
+
+
+def _sample_advance_check(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out, block_size):
+    rows, _, vocab = _sampler_inputs_check("sample_advance", logits, temperature, top_k, top_p, u)
+    _row_state_check("sample_advance", rows, _ADVANCE_STATE,
+                     dict(tick=tick, ids=ids, pos=pos, slots=slots, remaining=remaining, eos=eos, n_out=n_out), block_table)
     if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != rows or out.shape[1] < 1:
         raise RuntimeError(f"sample_advance: out must be int64 [{rows}, out_stride >= 1], not {tuple(out.shape)}")
-    if block_size not in (16, 32, 64, 128, 256):
-        raise RuntimeError(f"sample_advance: block_size must be a power of two in [16, 256], not {block_size}")
-    if vocab < 1 or vocab > 262144 or rows > 65535:
-        raise RuntimeError(f"sample_advance: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows <= 65535")
+    _sampler_limits_check("sample_advance", logits, block_size)
     return rows, vocab
 
 
 def _sample_advance_impl(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out, block_size):
     ts = (logits, temperature, top_k, top_p, u, tick, ids, pos, slots, block_table, remaining, eos, out, n_out)
-    if not all(t.is_cuda for t in ts):
-        raise RuntimeError("sample_advance: every tensor must be on the GPU (there is no CPU path)")
-    if any(t.device != logits.device for t in ts):
-        raise RuntimeError("sample_advance: every tensor must be on the same GPU")
+    _same_gpu("sample_advance", ts)
     rows, vocab = _sample_advance_check(*ts, block_size)
     if rows == 0:
         return
-    # everything written is written in place: no copy may stand in for a state array
-    for name, t in (("u", u), ("tick", tick), ("ids", ids), ("pos", pos), ("slots", slots), ("block_table", block_table),
-                    ("remaining", remaining), ("eos", eos), ("out", out), ("n_out", n_out)):
-        if not t.is_contiguous():
-            raise RuntimeError(f"sample_advance: {name} must be contiguous (the state is updated in place)")
-    if logits.stride(1) != 1 or logits.stride(0) < vocab or logits.stride(0) % 8 or logits.data_ptr() % 16:
-        rows8 = torch.empty((rows, vocab + (-vocab) % 8), dtype=torch.float16, device=logits.device)
-        rows8[:, :vocab] = logits
-        logits = rows8[:, :vocab]
+    _in_place_check("sample_advance", (("u", u), ("tick", tick), ("ids", ids), ("pos", pos), ("slots", slots), ("block_table", block_table),
+                                       ("remaining", remaining), ("eos", eos), ("out", out), ("n_out", n_out)))
+    logits = _logits_rows(logits, vocab)
     err = _lib.lib().qqq_sample_advance(_ptr(logits), logits.stride(0), _ptr(temperature.contiguous()), _ptr(top_k.contiguous()),
                                         _ptr(top_p.contiguous()), _ptr(u), u.shape[1], _ptr(tick), _ptr(ids), _ptr(pos), _ptr(slots),
                                         _ptr(block_table), block_table.shape[1], _ptr(remaining), _ptr(eos), _ptr(out), out.shape[1],
                                         _ptr(n_out), rows, vocab, block_size, logits.device.index or 0, _stream_for(logits))
-    if err:
-        raise RuntimeError(f"qqq_amd: sample_advance error {err}: {_lib.last_error()}")
+    _raise_lib("sample_advance", err)
 
 
 @torch.library.custom_op("qqq_amd::sample_advance", mutates_args=("tick", "ids", "pos", "slots", "remaining", "out", "n_out"))
@@ -1369,65 +1378,29 @@ _SPEC_ROW_STATE = (("tick", torch.int32), ("start", torch.int64), ("remaining", 
 
 def _spec_advance_check(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len,
                         n_out, n_acc, block_size, ngram_max):
-    # the checks that need no device: dtypes and shapes (shared by the launch and the fake implementation)
-    if logits.dtype != torch.float16 or logits.dim() != 2:
-        raise RuntimeError("spec_advance: logits must be fp16 [rows * (draft_len + 1), vocab]")
-    if ids.dtype != torch.int64 or ids.dim() != 2 or ids.shape[1] < 2 or ids.shape[1] > 16:
-        raise RuntimeError(f"spec_advance: ids must be int64 [rows, draft_len + 1] with 1 <= draft_len <= 15, not "
-                           f"{str(ids.dtype).replace('torch.', '')} {tuple(ids.shape)}")
-    rows, group = ids.shape
-    m, vocab = logits.shape
-    if m != rows * group:
-        raise RuntimeError(f"spec_advance: logits hold {m} rows, ids {tuple(ids.shape)} asks for {rows * group}")
-    if temperature.dtype != torch.float32 or top_p.dtype != torch.float32 or u.dtype != torch.float32 or top_k.dtype != torch.int32:
-        raise RuntimeError("spec_advance: temperature, top_p and u must be f32, top_k int32")
-    if any(t.numel() != m for t in (temperature, top_k, top_p)):
-        raise RuntimeError(f"spec_advance: temperature, top_k and top_p must hold one entry per logits row ({m})")
-    if u.dim() != 2 or u.shape[0] != rows or u.shape[1] < group:
-        raise RuntimeError(f"spec_advance: u must be f32 [{rows}, u_stride] with u_stride >= draft_len + 1 = {group}, not {tuple(u.shape)}")
+    rows, group, vocab = _sampler_inputs_check("spec_advance", logits, temperature, top_k, top_p, u, ids)
     for name, t in (("pos", pos), ("slots", slots)):
         if t.dtype != torch.int64 or tuple(t.shape) != (rows, group):
-            raise RuntimeError(f"spec_advance: {name} must be int64 [{rows}, {group}], not {str(t.dtype).replace('torch.', '')} "
-                               f"{tuple(t.shape)}")
-    state = dict(tick=tick, start=start, remaining=remaining, eos=eos, hist_len=hist_len, n_out=n_out, n_acc=n_acc)
-    for name, dtype in _SPEC_ROW_STATE:
-        t = state[name]
-        if t.dtype != dtype or t.dim() != 1 or t.shape[0] != rows:
-            raise RuntimeError(f"spec_advance: {name} must be {str(dtype).replace('torch.', '')} [{rows}], not "
-                               f"{str(t.dtype).replace('torch.', '')} {tuple(t.shape)}")
-    if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.shape[0] != rows or block_table.shape[1] < 1:
-        raise RuntimeError(f"spec_advance: block_table must be int32 [{rows}, blocks per row >= 1], not {tuple(block_table.shape)}")
+            raise RuntimeError(f"spec_advance: {name} must be int64 [{rows}, {group}], not {_dt(t.dtype)} {tuple(t.shape)}")
+    _row_state_check("spec_advance", rows, _SPEC_ROW_STATE,
+                     dict(tick=tick, start=start, remaining=remaining, eos=eos, hist_len=hist_len, n_out=n_out, n_acc=n_acc), block_table)
     if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] != rows or hist.shape[1] < 1:
-        raise RuntimeError(f"spec_advance: hist must be int32 [{rows}, hist_stride >= 1], not {str(hist.dtype).replace('torch.', '')} "
-                           f"{tuple(hist.shape)}")
-    if block_size not in (16, 32, 64, 128, 256):
-        raise RuntimeError(f"spec_advance: block_size must be a power of two in [16, 256], not {block_size}")
-    if ngram_max < 1 or ngram_max > 4:
-        raise RuntimeError(f"spec_advance: ngram_max must be in [1, 4], not {ngram_max}")
-    if vocab < 1 or vocab > 262144 or m > 65535:
-        raise RuntimeError(f"spec_advance: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows * (draft_len + 1) <= 65535")
+        raise RuntimeError(f"spec_advance: hist must be int32 [{rows}, hist_stride >= 1], not {_dt(hist.dtype)} {tuple(hist.shape)}")
+    _sampler_limits_check("spec_advance", logits, block_size, ngram_max)
     return rows, group, vocab
 
 
 def _spec_advance_impl(logits, temperature, top_k, top_p, u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len,
                        n_out, n_acc, block_size, ngram_max):
     ts = (logits, temperature, top_k, top_p, u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len, n_out, n_acc)
-    if not all(t.is_cuda for t in ts):
-        raise RuntimeError("spec_advance: every tensor must be on the GPU (there is no CPU path)")
-    if any(t.device != logits.device for t in ts):
-        raise RuntimeError("spec_advance: every tensor must be on the same GPU")
+    _same_gpu("spec_advance", ts)
     rows, group, vocab = _spec_advance_check(*ts, block_size, ngram_max)
     if rows == 0:
         return
-    # everything written is written in place: no copy may stand in for a state array
-    for name, t in (("u", u), ("tick", tick), ("ids", ids), ("pos", pos), ("slots", slots), ("start", start), ("block_table", block_table),
-                    ("remaining", remaining), ("eos", eos), ("hist", hist), ("hist_len", hist_len), ("n_out", n_out), ("n_acc", n_acc)):
-        if not t.is_contiguous():
-            raise RuntimeError(f"spec_advance: {name} must be contiguous (the state is updated in place)")
-    if logits.stride(1) != 1 or logits.stride(0) < vocab or logits.stride(0) % 8 or logits.data_ptr() % 16:
-        rows8 = torch.empty((rows * group, vocab + (-vocab) % 8), dtype=torch.float16, device=logits.device)
-        rows8[:, :vocab] = logits
-        logits = rows8[:, :vocab]
+    _in_place_check("spec_advance", (("u", u), ("tick", tick), ("ids", ids), ("pos", pos), ("slots", slots), ("start", start),
+                                     ("block_table", block_table), ("remaining", remaining), ("eos", eos), ("hist", hist),
+                                     ("hist_len", hist_len), ("n_out", n_out), ("n_acc", n_acc)))
+    logits = _logits_rows(logits, vocab)
     L = _lib.lib()
     ws = torch.empty((max(L.qqq_spec_advance_workspace_bytes(rows, group - 1), 16),), dtype=torch.uint8, device=logits.device)
     err = L.qqq_spec_advance(_ptr(logits), logits.stride(0), _ptr(temperature.contiguous()), _ptr(top_k.contiguous()),
@@ -1435,8 +1408,7 @@ def _spec_advance_impl(logits, temperature, top_k, top_p, u, tick, ids, pos, slo
                              _ptr(block_table), block_table.shape[1], _ptr(remaining), _ptr(eos), _ptr(hist), hist.shape[1], _ptr(hist_len),
                              _ptr(n_out), _ptr(n_acc), _ptr(ws), ws.numel(), rows, group - 1, ngram_max, vocab, block_size,
                              logits.device.index or 0, _stream_for(logits))
-    if err:
-        raise RuntimeError(f"qqq_amd: spec_advance error {err}: {_lib.last_error()}")
+    _raise_lib("spec_advance", err)
 
 
 @torch.library.custom_op("qqq_amd::spec_advance",

@@ -11,6 +11,9 @@ QuantLlamaForCausalLM.generate (qqq_amd/model.py) builds its batch anew on the h
 of every kernel, a tolist() before the next step.  Here the host only admits prompts (an eager packed prefill, the first token from
 ops.sample_tokens), writes the admitted rows' state with indexed copies, replays, and reads (n_out, remaining) back once per `sync_every`
 steps.  A row that is idle (pos -1, slot -1, remaining 0) rides along in every step and is inert: see include/qqq_amd_step.h.
+
+generate() -- admission, prefill, the run / sync / retire loop and the cleanup -- exists once, on DecodeLoop.  SpecDecodeLoop inherits it
+and overrides _decode_step, _run, _start_call, _budget_words, _row_state and _collect, and the attributes _tokens, _synced and _idle.
 """
 from __future__ import annotations
 
@@ -55,34 +58,42 @@ class DecodeLoop:
     the first generate() (fuse_*(), load_state_dict, .to()) needs a new loop."""
 
     _name = "DecodeLoop"
-    _draws = 1  # variates a row uses per step
+    group = 1                        # tokens a row feeds through a step, and variates it uses
+    _tokens = "out"                  # the array a finished row's tokens are read from
+    _synced = ("n_out", "remaining")  # what a sync transfers
+    _idle = (("remaining", 0), ("pos", -1), ("slots", -1), ("ids", 0))  # what the cleanup resets
 
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, sync_every: int = 8, u_stride: int = 64, graph: bool = True):
         rows, max_len, sync_every, u_stride = int(rows), int(max_len), int(sync_every), int(u_stride)
         short = u_stride < sync_every and f"u_stride={u_stride} must cover the sync_every={sync_every} steps between two refills"
         dev = _check_loop("DecodeLoop", lm, cache, rows, max_len, sync_every, graph, short)
-        self.lm, self.cache, self.rows, self.max_len, self.sync_every, self.u_stride = lm, cache, rows, max_len, sync_every, u_stride
-        self.graph, self.device, self.captures = bool(graph), dev, 0
-        bs = cache.block_size
-        i32 = dict(dtype=torch.int32, device=dev)
-        i64 = dict(dtype=torch.int64, device=dev)
-        self.ids = torch.zeros(rows, **i64)
-        self.pos = torch.full((rows,), -1, **i64)
-        self.slots = torch.full((rows,), -1, **i64)
-        self.block_table = torch.zeros((rows, -(-max_len // bs)), **i32)
-        self.remaining = torch.zeros(rows, **i32)
-        self.eos = torch.full((rows,), -1, **i32)
-        self.out = torch.zeros((rows, max_len), **i64)
-        self.n_out = torch.zeros(rows, **i32)
-        self.tick = torch.zeros(rows, **i32)
-        self.u = torch.zeros((rows, u_stride), dtype=torch.float32, device=dev)
-        self.temperature = torch.zeros(rows, dtype=torch.float32, device=dev)
-        self.top_k = torch.zeros(rows, **i32)
-        self.top_p = torch.ones(rows, dtype=torch.float32, device=dev)
+        self._allocate(lm, cache, rows, max_len, sync_every, u_stride, graph, dev)
+        self.out = torch.zeros((rows, max_len), dtype=torch.int64, device=dev)
         # the one step of every decode pass: its device tensors ARE the state arrays (a row's position is its last position)
         self.step = PagedStep(seq_ids=[None] * rows, counts=[1] * rows, starts=[0] * rows, max_len=max_len, decode=True, pos=self.pos,
                               slots=self.slots, block_table=self.block_table, last_pos=self.pos,
-                              cu_tokens=torch.arange(rows + 1, **i32), start_pos=self.pos)
+                              cu_tokens=torch.arange(rows + 1, dtype=torch.int32, device=dev), start_pos=self.pos)
+
+    def _allocate(self, lm, cache, rows, max_len, sync_every, u_stride, graph, dev):
+        """The attributes and state arrays every loop has, for rows of `self.group` tokens: [rows] at 1, [rows, group] beyond."""
+        self.lm, self.cache, self.rows, self.max_len, self.sync_every, self.u_stride = lm, cache, rows, max_len, sync_every, u_stride
+        self.graph, self.device, self.captures = bool(graph), dev, 0
+        per_token = (rows,) if self.group == 1 else (rows, self.group)
+        i32 = dict(dtype=torch.int32, device=dev)
+        i64 = dict(dtype=torch.int64, device=dev)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.ids = torch.zeros(per_token, **i64)
+        self.pos = torch.full(per_token, -1, **i64)
+        self.slots = torch.full(per_token, -1, **i64)
+        self.block_table = torch.zeros((rows, -(-max_len // cache.block_size)), **i32)
+        self.remaining = torch.zeros(rows, **i32)
+        self.eos = torch.full((rows,), -1, **i32)
+        self.n_out = torch.zeros(rows, **i32)
+        self.tick = torch.zeros(rows, **i32)
+        self.u = torch.zeros((rows, u_stride), **f32)
+        self.temperature = torch.zeros(rows * self.group, **f32)  # the sampler's parameters: one per logits row
+        self.top_k = torch.zeros(rows * self.group, **i32)
+        self.top_p = torch.ones(rows * self.group, **f32)
         self._graph = None
         self._used = u_stride  # variates of u consumed since its last refill: none are left
 
@@ -112,16 +123,36 @@ class DecodeLoop:
         self.captures += 1
 
     def _run(self, steps: int, generator) -> None:
-        if self._used + steps * self._draws > self.u_stride:  # tick is about to wrap: new variates, and the rows start over at the first
+        if self._used + steps * self.group > self.u_stride:  # tick is about to wrap: new variates, and the rows start over at the first
             self.u.copy_(torch.rand((self.rows, self.u_stride), generator=generator, device=self.device))
             self.tick.zero_()
             self._used = 0
-        self._used += steps * self._draws
+        self._used += steps * self.group
         for _ in range(steps):
             if self._graph is not None:
                 self._graph.replay()
             else:
                 self._decode_step()
+
+    # ---- what differs between the loops
+
+    def _start_call(self) -> None:
+        self._used = self.u_stride  # this call draws with its own generator alone: nothing an earlier call left in u is used
+
+    def _budget_words(self, new: int):
+        """(the keys a sequence needs beyond its prompt and its new tokens but the last, how the two budget messages name the parts)"""
+        return 0, f" and {new} new ones", "prompt and budget"
+
+    def _row_state(self, prompt: List[int], first: int, blocks: List[int]) -> dict:
+        """What an admitted row writes, per state array: `prompt` is in the cache, `first` the token the prefill drew."""
+        p, bs = len(prompt), self.cache.block_size
+        table = blocks + [0] * (self.block_table.shape[1] - len(blocks))
+        return dict(ids=first, pos=p, slots=blocks[p // bs] * bs + p % bs, block_table=table)
+
+    def _collect(self, row: List[int], n_prompt: int, seq, n: dict) -> List[int]:
+        """The tokens a finished row emitted, from its line `row` of the `_tokens` array and its synced counts `n`."""
+        self.cache.advance(seq, n["n_out"])  # the keys the device wrote: one per decode step the row took
+        return row[:n["n_out"]]
 
     # ---- the loop
 
@@ -134,47 +165,53 @@ class DecodeLoop:
         ops.sample_tokens, and decoded by the captured step.  A prompt whose len + max_new_tokens - 1 exceeds max_len raises before
         anything runs.  The random draws: one torch.rand per prefill pass, one torch.rand(rows, u_stride) at the
         first decode step of the call and then per u_stride decode steps, so equally seeded generators give equal tokens whatever the
-        loop served before."""
+        loop served before.
+
+        SpecDecodeLoop: the budget is len(prompt) + max_new_tokens - 1 + draft_len keys per sequence (reserved at once; the same sum must
+        not exceed max_len).  The host writes an admitted row's history (the prompt and its first token) and first drafts (ngram_draft);
+        everything after that happens on the device.  u is refilled whenever it is used up; a step uses draft_len + 1 variates per row,
+        so sampled tokens differ from DecodeLoop's under the same seed."""
+        name = f"{self._name}.generate"
         prompts = [list(p) for p in prompts]
         if any(not p for p in prompts):
-            raise ValueError("DecodeLoop.generate: every prompt needs at least one token")
+            raise ValueError(f"{name}: every prompt needs at least one token")
         outs: List[List[int]] = [[] for _ in prompts]
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1 or not prompts:
             return outs
-        for p in prompts:
-            if len(p) + max_new_tokens - 1 > self.max_len:
-                raise ValueError(f"DecodeLoop.generate: a prompt of {len(p)} tokens and {max_new_tokens} new ones need "
-                                 f"{len(p) + max_new_tokens - 1} keys, the loop was built for max_len={self.max_len}")
+        extra, new_words, parts = self._budget_words(max_new_tokens)
+        keys = [len(p) + max_new_tokens - 1 + extra for p in prompts]
+        for p, k in zip(prompts, keys):
+            if k > self.max_len:
+                raise ValueError(f"{name}: a prompt of {len(p)} tokens{new_words} need {k} keys, the loop was built for max_len={self.max_len}")
         if self.graph and self._graph is None:
             self._capture()
-        self._used = self.u_stride  # this call draws with its own generator alone: nothing an earlier call left in u is used
+        self._start_call()
         cache, dev, bs = self.cache, self.device, self.cache.block_size
         eos = -1 if eos_token_id is None else int(eos_token_id)
         tag = object()  # sequence ids no other user of the cache can hold
         sid = lambda i: (tag, i)  # noqa: E731
         waiting = deque(range(len(prompts)))
         owner: List[Optional[int]] = [None] * self.rows  # the prompt each row serves
-        budget = [0] * self.rows                         # an upper bound of the row's `remaining`
+        budget = [0] * self.rows                         # an upper bound of the row's `remaining`, and so of the steps it still takes
+        per_row = dict(remaining=max_new_tokens - 1, eos=eos, n_out=0, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p))
 
         def admit():
             new = []
             idle = [r for r in range(self.rows) if owner[r] is None]
             while waiting and idle:
                 i = waiting[0]
-                keys = len(prompts[i]) + max_new_tokens - 1
-                if -(-keys // bs) > cache.free_blocks:
+                if -(-keys[i] // bs) > cache.free_blocks:
                     break
                 waiting.popleft()
                 cache.add(sid(i))
-                cache.reserve(sid(i), keys)
+                cache.reserve(sid(i), keys[i])
                 owner[idle[0]] = i
                 new.append((idle.pop(0), i))
             if not new:
                 if waiting and all(o is None for o in owner):
-                    need = -(-(len(prompts[waiting[0]]) + max_new_tokens - 1) // bs)
-                    raise RuntimeError(f"DecodeLoop.generate: the pool's {cache.free_blocks} free blocks cannot hold a prompt that needs "
-                                       f"{need} (prompt and budget)")
+                    raise RuntimeError(f"{name}: the pool's {cache.free_blocks} free blocks cannot hold a prompt that needs "
+                                       f"{-(-keys[waiting[0]] // bs)} ({parts})")
                 return
             # the packed prefill of the admitted prompts (eager, the existing step) and their first tokens
             seqs = [sid(i) for _, i in new]
@@ -182,31 +219,25 @@ class DecodeLoop:
             logits = self.lm(ids, cache, cache.step(seqs, [len(prompts[i]) for _, i in new]))
             u = torch.rand(len(new), generator=generator, device=dev)
             first = ops.sample_tokens(logits, temperature, top_k, top_p, u).tolist()
-            rows, tok, pos, slots, rem, tables = [], [], [], [], [], []
+            rows, state = [], {}
             for (r, i), t in zip(new, first):
                 outs[i].append(t)
                 if max_new_tokens == 1 or t == eos:
                     cache.free(sid(i))
                     owner[r] = None
                     continue
-                blocks, p = cache.blocks(sid(i)), len(prompts[i])
                 rows.append(r)
-                tok.append(t)
-                pos.append(p)
-                slots.append(blocks[p // bs] * bs + p % bs)
-                rem.append(max_new_tokens - 1)
-                tables.append(blocks + [0] * (self.block_table.shape[1] - len(blocks)))
+                for array, value in self._row_state(prompts[i], t, cache.blocks(sid(i))).items():
+                    state.setdefault(array, []).append(value)
                 budget[r] = max_new_tokens - 1
             if not rows:
                 return
             at = torch.tensor(rows, dtype=torch.int64, device=dev)
-            n = len(rows)
-            for dst, src, dtype in ((self.ids, tok, torch.int64), (self.pos, pos, torch.int64), (self.slots, slots, torch.int64),
-                                    (self.remaining, rem, torch.int32), (self.eos, [eos] * n, torch.int32),
-                                    (self.n_out, [0] * n, torch.int32), (self.block_table, tables, torch.int32),
-                                    (self.temperature, [float(temperature)] * n, torch.float32), (self.top_k, [int(top_k)] * n, torch.int32),
-                                    (self.top_p, [float(top_p)] * n, torch.float32)):
-                dst[at] = torch.tensor(src, dtype=dtype).to(dev)
+            for array, values in state.items():
+                dst = getattr(self, array)
+                dst[at] = torch.tensor(values, dtype=dst.dtype).to(dev)
+            for array, value in per_row.items():  # the same for every row of the call, and for each of a row's logits rows
+                getattr(self, array).view(self.rows, -1)[at] = value
 
         try:
             while True:
@@ -216,32 +247,28 @@ class DecodeLoop:
                     if waiting:
                         continue
                     break
-                steps = min(self.sync_every, max(budget[r] for r in active))
-                self._run(steps, generator)
-                n_out, remaining = torch.stack((self.n_out, self.remaining)).tolist()  # the sync: one transfer
+                self._run(min(self.sync_every, max(budget[r] for r in active)), generator)
+                synced = dict(zip(self._synced, torch.stack([getattr(self, a) for a in self._synced]).tolist()))  # the sync: one transfer
+                remaining = synced["remaining"]
                 done = [r for r in active if remaining[r] == 0]
                 for r in active:
                     budget[r] = remaining[r]
                 if done:
-                    toks = self.out[torch.tensor(done, dtype=torch.int64, device=dev)].tolist()
+                    toks = getattr(self, self._tokens)[torch.tensor(done, dtype=torch.int64, device=dev)].tolist()
                     for r, row in zip(done, toks):
                         i = owner[r]
-                        outs[i].extend(row[:n_out[r]])
-                        cache.advance(sid(i), n_out[r])  # the keys the device wrote: one per decode step the row took
+                        outs[i].extend(self._collect(row, len(prompts[i]), sid(i), {a: v[r] for a, v in synced.items()}))
                         cache.free(sid(i))
                         owner[r] = None
         except BaseException:
             # leave the loop idle and the caller's pool as it was found
-            for r, i in enumerate(owner):
+            for i in owner:
                 if i is not None:
                     cache.free(sid(i))
-            self.remaining.zero_()
-            self.pos.fill_(-1)
-            self.slots.fill_(-1)
-            self.ids.zero_()
+            for array, value in self._idle:
+                getattr(self, array).fill_(value)
             raise
         return outs
-
 
 
 def ngram_draft(history: Sequence[int], draft_len: int, ngram_max: int = 3) -> List[int]:
@@ -283,6 +310,9 @@ class SpecDecodeLoop(DecodeLoop):
     emits 1 + its accepted drafts tokens."""
 
     _name = "SpecDecodeLoop"
+    _tokens = "hist"
+    _synced = ("n_out", "remaining", "n_acc")
+    _idle = DecodeLoop._idle + (("start", -1),)
 
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, draft_len: int = 4, ngram_max: int = 3, sync_every: int = 8,
                  u_stride: Optional[int] = None, graph: bool = True):
@@ -303,35 +333,18 @@ class SpecDecodeLoop(DecodeLoop):
         if not all(getattr(layer.self_attn, "_prefill", False) for layer in lm.model.layers):
             raise RuntimeError("SpecDecodeLoop: the model needs fuse_prefill(): a step is a chunk of draft_len + 1 tokens per row, and only "
                                "the paged prefill attention kernel serves chunks without reading lengths on the host")
-        self.lm, self.cache, self.rows, self.max_len, self.sync_every, self.u_stride = lm, cache, rows, max_len, sync_every, u_stride
-        self.draft_len, self.ngram_max, self.group, self._draws = draft_len, ngram_max, group, group
-        self.graph, self.device, self.captures = bool(graph), dev, 0
+        self.draft_len, self.ngram_max, self.group = draft_len, ngram_max, group
         self.accepted = self.row_steps = self.steps = 0
-        bs = cache.block_size
+        self._allocate(lm, cache, rows, max_len, sync_every, u_stride, graph, dev)
         i32 = dict(dtype=torch.int32, device=dev)
-        i64 = dict(dtype=torch.int64, device=dev)
-        self.ids = torch.zeros((rows, group), **i64)
-        self.pos = torch.full((rows, group), -1, **i64)
-        self.slots = torch.full((rows, group), -1, **i64)
-        self.start = torch.full((rows,), -1, **i64)
-        self.block_table = torch.zeros((rows, -(-max_len // bs)), **i32)
-        self.remaining = torch.zeros(rows, **i32)
-        self.eos = torch.full((rows,), -1, **i32)
+        self.start = torch.full((rows,), -1, dtype=torch.int64, device=dev)
         self.hist = torch.zeros((rows, max_len), **i32)
         self.hist_len = torch.zeros(rows, **i32)
-        self.n_out = torch.zeros(rows, **i32)
         self.n_acc = torch.zeros(rows, **i32)
-        self.tick = torch.zeros(rows, **i32)
-        self.u = torch.zeros((rows, u_stride), dtype=torch.float32, device=dev)
-        self.temperature = torch.zeros(rows * group, dtype=torch.float32, device=dev)
-        self.top_k = torch.zeros(rows * group, **i32)
-        self.top_p = torch.ones(rows * group, dtype=torch.float32, device=dev)
         # the one step of every pass: a chunk of G tokens per row whose device tensors ARE the state arrays
         self.step = PagedStep(seq_ids=[None] * rows, counts=[group] * rows, starts=[0] * rows, max_len=max_len, decode=False,
                               pos=self.pos.view(-1), slots=self.slots.view(-1), block_table=self.block_table, last_pos=self.start,
                               cu_tokens=torch.arange(rows + 1, **i32) * group, start_pos=self.start)
-        self._graph = None
-        self._used = u_stride
 
     def _decode_step(self) -> None:
         logits = self.lm(self.ids.view(-1), self.cache, self.step, all_rows=True)
@@ -339,133 +352,29 @@ class SpecDecodeLoop(DecodeLoop):
                          self.block_table, self.remaining, self.eos, self.hist, self.hist_len, self.n_out, self.n_acc,
                          self.cache.block_size, self.ngram_max)
 
-    @torch.no_grad()
-    def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-                 generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None) -> List[List[int]]:
-        """DecodeLoop.generate's contract, admission and cleanup, with a budget of len(prompt) + max_new_tokens - 1 + draft_len keys per
-        sequence (reserved at once; the same sum must not exceed max_len).  The host writes an admitted row's history (the prompt and
-        its first token) and first drafts (ngram_draft); everything after that happens on the device.  The random draws: one torch.rand
-        per prefill pass, one torch.rand(rows, u_stride) at the first step of the call and then whenever u is used up; a step uses
-        draft_len + 1 variates per row, so sampled tokens differ from DecodeLoop's under the same seed."""
-        prompts = [list(p) for p in prompts]
-        if any(not p for p in prompts):
-            raise ValueError("SpecDecodeLoop.generate: every prompt needs at least one token")
-        outs: List[List[int]] = [[] for _ in prompts]
-        max_new_tokens = int(max_new_tokens)
-        if max_new_tokens < 1 or not prompts:
-            return outs
-        K, G = self.draft_len, self.group
-        for p in prompts:
-            if len(p) + max_new_tokens - 1 + K > self.max_len:
-                raise ValueError(f"SpecDecodeLoop.generate: a prompt of {len(p)} tokens, {max_new_tokens} new ones and {K} drafts need "
-                                 f"{len(p) + max_new_tokens - 1 + K} keys, the loop was built for max_len={self.max_len}")
-        if self.graph and self._graph is None:
-            self._capture()
-        self._used = self.u_stride  # this call draws with its own generator alone
+    def _run(self, steps: int, generator) -> None:
+        super()._run(steps, generator)
+        self.steps += steps
+
+    def _start_call(self) -> None:
+        super()._start_call()
         self.accepted = self.row_steps = self.steps = 0
-        cache, dev, bs = self.cache, self.device, self.cache.block_size
-        eos = -1 if eos_token_id is None else int(eos_token_id)
-        tag = object()
-        sid = lambda i: (tag, i)  # noqa: E731
-        waiting = deque(range(len(prompts)))
-        owner: List[Optional[int]] = [None] * self.rows
-        budget = [0] * self.rows  # an upper bound of the row's `remaining`, and so of the steps it still takes
 
-        def admit():
-            new = []
-            idle = [r for r in range(self.rows) if owner[r] is None]
-            while waiting and idle:
-                i = waiting[0]
-                keys = len(prompts[i]) + max_new_tokens - 1 + K
-                if -(-keys // bs) > cache.free_blocks:
-                    break
-                waiting.popleft()
-                cache.add(sid(i))
-                cache.reserve(sid(i), keys)
-                owner[idle[0]] = i
-                new.append((idle.pop(0), i))
-            if not new:
-                if waiting and all(o is None for o in owner):
-                    need = -(-(len(prompts[waiting[0]]) + max_new_tokens - 1 + K) // bs)
-                    raise RuntimeError(f"SpecDecodeLoop.generate: the pool's {cache.free_blocks} free blocks cannot hold a prompt that "
-                                       f"needs {need} (prompt, budget and drafts)")
-                return
-            seqs = [sid(i) for _, i in new]
-            ids = torch.tensor([t for _, i in new for t in prompts[i]], dtype=torch.int64, device=dev)
-            logits = self.lm(ids, cache, cache.step(seqs, [len(prompts[i]) for _, i in new]))
-            u = torch.rand(len(new), generator=generator, device=dev)
-            first = ops.sample_tokens(logits, temperature, top_k, top_p, u).tolist()
-            rows, tok, pos, slots, start, rem, tables, hist, hlen = [], [], [], [], [], [], [], [], []
-            for (r, i), t in zip(new, first):
-                outs[i].append(t)
-                if max_new_tokens == 1 or t == eos:
-                    cache.free(sid(i))
-                    owner[r] = None
-                    continue
-                blocks, p = cache.blocks(sid(i)), len(prompts[i])
-                h = prompts[i] + [t]
-                rows.append(r)
-                tok.append([t] + ngram_draft(h, K, self.ngram_max))
-                pos.append(list(range(p, p + G)))
-                slots.append([blocks[q // bs] * bs + q % bs for q in range(p, p + G)])
-                start.append(p)
-                rem.append(max_new_tokens - 1)
-                tables.append(blocks + [0] * (self.block_table.shape[1] - len(blocks)))
-                hist.append(h + [0] * (self.hist.shape[1] - len(h)))
-                hlen.append(len(h))
-                budget[r] = max_new_tokens - 1
-            if not rows:
-                return
-            at = torch.tensor(rows, dtype=torch.int64, device=dev)
-            n = len(rows)
-            per_draw = lambda t: t.view(self.rows, G)  # noqa: E731
-            for dst, src, dtype in ((self.ids, tok, torch.int64), (self.pos, pos, torch.int64), (self.slots, slots, torch.int64),
-                                    (self.start, start, torch.int64), (self.remaining, rem, torch.int32),
-                                    (self.eos, [eos] * n, torch.int32), (self.n_out, [0] * n, torch.int32),
-                                    (self.n_acc, [0] * n, torch.int32), (self.block_table, tables, torch.int32),
-                                    (self.hist, hist, torch.int32), (self.hist_len, hlen, torch.int32),
-                                    (per_draw(self.temperature), [[float(temperature)] * G] * n, torch.float32),
-                                    (per_draw(self.top_k), [[int(top_k)] * G] * n, torch.int32),
-                                    (per_draw(self.top_p), [[float(top_p)] * G] * n, torch.float32)):
-                dst[at] = torch.tensor(src, dtype=dtype).to(dev)
+    def _budget_words(self, new: int):
+        return self.draft_len, f", {new} new ones and {self.draft_len} drafts", "prompt, budget and drafts"  # the drafts are written too
 
-        try:
-            while True:
-                admit()
-                active = [r for r in range(self.rows) if owner[r] is not None]
-                if not active:
-                    if waiting:
-                        continue
-                    break
-                steps = min(self.sync_every, max(budget[r] for r in active))
-                self._run(steps, generator)
-                self.steps += steps
-                n_out, remaining, n_acc = torch.stack((self.n_out, self.remaining, self.n_acc)).tolist()  # the sync: one transfer
-                done = [r for r in active if remaining[r] == 0]
-                for r in active:
-                    budget[r] = remaining[r]
-                if done:
-                    toks = self.hist[torch.tensor(done, dtype=torch.int64, device=dev)].tolist()
-                    for r, row in zip(done, toks):
-                        i = owner[r]
-                        first = len(prompts[i]) + 1  # the prompt and the prefill's token
-                        outs[i].extend(row[first:first + n_out[r]])
-                        self.accepted += n_acc[r]
-                        self.row_steps += n_out[r] - n_acc[r]  # a row-step emits one token more than it accepts drafts
-                        cache.free(sid(i))
-                        owner[r] = None
-        except BaseException:
-            # leave the loop idle and the caller's pool as it was found
-            for r, i in enumerate(owner):
-                if i is not None:
-                    cache.free(sid(i))
-            self.remaining.zero_()
-            self.pos.fill_(-1)
-            self.slots.fill_(-1)
-            self.start.fill_(-1)
-            self.ids.zero_()
-            raise
-        return outs
+    def _row_state(self, prompt: List[int], first: int, blocks: List[int]) -> dict:
+        p, bs, h = len(prompt), self.cache.block_size, prompt + [first]
+        chunk = range(p, p + self.group)
+        return dict(super()._row_state(prompt, first, blocks), ids=[first] + ngram_draft(h, self.draft_len, self.ngram_max), pos=list(chunk),
+                    slots=[blocks[q // bs] * bs + q % bs for q in chunk], start=p, n_acc=0, hist=h + [0] * (self.hist.shape[1] - len(h)),
+                    hist_len=len(h))
+
+    def _collect(self, row: List[int], n_prompt: int, seq, n: dict) -> List[int]:
+        self.accepted += n["n_acc"]
+        self.row_steps += n["n_out"] - n["n_acc"]  # a row-step emits one token more than it accepts drafts
+        first = n_prompt + 1  # the prompt and the prefill's token
+        return row[first:first + n["n_out"]]
 
 
 __all__ = ["DecodeLoop", "SpecDecodeLoop", "ngram_draft"]
