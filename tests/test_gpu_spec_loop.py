@@ -45,10 +45,21 @@ def _blocks(prompts, n_new=N_NEW):
     return [-(-(len(p) + n_new - 1 + K) // BS) for p in prompts]
 
 
-def _reference(lm, prompts, n_new, dtype, eos=None, sample=None, seed=None):
-    """`prompts` in rows 0 ... of a ROWS-row batch, the other rows idle: the packed prefill, then per step a hand-built PagedStep of G-token
-    chunks, lm(all_rows=True), ops.sample_tokens with the variates the loop documents, and spec_ref.advance on the host.
-    -> (the tokens per prompt, the accepted drafts of every row-step, {(prompt, position): the logits row its token was drawn from})"""
+def _match_end(h, nmax):
+    """the end position c of the occurrence the drafter continues from: the deepest n <= nmax, then the largest c <= L - 2; None: no match"""
+    last = len(h) - 1
+    for n in range(min(nmax, last), 0, -1):
+        for c in range(last - 1, n - 2, -1):
+            if all(h[c - t] == h[last - t] for t in range(n)):
+                return c
+    return None
+
+
+def _reference(lm, prompts, n_new, dtype, eos=None, sample=None, seed=None, max_len=MAX_LEN, rows=ROWS, ends=None):
+    """`prompts` in rows 0 ... of a `rows`-row batch, the other rows idle: the packed prefill, then per step a hand-built PagedStep of
+    G-token chunks, lm(all_rows=True), ops.sample_tokens with the variates the loop documents, and spec_ref.advance on the host.
+    -> (the tokens per prompt, the accepted drafts of every row-step, {(prompt, position): the logits row its token was drawn from});
+    `ends`, a list, receives (prompt, c) for every draft that came from a match: where the scan found it"""
     from qqq_amd import PagedStep, ops
 
     dev = lm.lm_head.weight.device
@@ -63,30 +74,30 @@ def _reference(lm, prompts, n_new, dtype, eos=None, sample=None, seed=None):
     logits = lm(ids, cache, cache.step(sids, [len(p) for p in prompts]))
     first = ops.sample_tokens(logits, T, top_k, top_p, torch.rand(len(prompts), generator=gen, device=dev)).tolist()
     seen = {(s, len(prompts[s])): logits[s].clone() for s in sids}
-    st = spec_ref.new_state(ROWS, K, -(-MAX_LEN // BS), MAX_LEN, BS)
+    st = spec_ref.new_state(rows, K, -(-max_len // BS), max_len, BS)
     for s in sids:
         if n_new > 1 and first[s] != eos:
             spec_ref.seat(st, s, prompts[s] + [first[s]], cache.blocks(s), n_new - 1, NGRAM, -1 if eos is None else eos)
     u_stride = SYNC * G
     used, u, accepted = u_stride, None, []
-    cu = torch.arange(ROWS + 1, dtype=torch.int32, device=dev) * G
+    cu = torch.arange(rows + 1, dtype=torch.int32, device=dev) * G
     table = torch.from_numpy(st["block_table"]).to(dev)
     while (st["remaining"] > 0).any():
         steps = min(SYNC, int(st["remaining"].max()))  # the loop's window: what it read at its last sync
         if used + steps * G > u_stride:
-            u = torch.rand((ROWS, u_stride), generator=gen, device=dev)
+            u = torch.rand((rows, u_stride), generator=gen, device=dev)
             st["tick"][:] = 0
             used = 0
         used += steps * G
         for _ in range(steps):
             start = torch.from_numpy(st["start"]).to(dev)
-            step = PagedStep(seq_ids=[None] * ROWS, counts=[G] * ROWS, starts=[0] * ROWS, max_len=MAX_LEN, decode=False,
+            step = PagedStep(seq_ids=[None] * rows, counts=[G] * rows, starts=[0] * rows, max_len=max_len, decode=False,
                              pos=torch.from_numpy(st["pos"]).to(dev).view(-1), slots=torch.from_numpy(st["slots"]).to(dev).view(-1),
                              block_table=table, last_pos=start, cu_tokens=cu, start_pos=start)
             logits = lm(torch.from_numpy(st["ids"]).to(dev).view(-1), cache, step, all_rows=True)
             idx = (torch.from_numpy(st["tick"]).to(dev).long()[:, None] * G + torch.arange(G, device=dev)[None]) % u_stride
-            toks = ops.sample_tokens(logits, T, top_k, top_p, u.gather(1, idx).reshape(-1).contiguous()).view(ROWS, G).tolist()
-            live = [r for r in range(ROWS) if st["remaining"][r] > 0]
+            toks = ops.sample_tokens(logits, T, top_k, top_p, u.gather(1, idx).reshape(-1).contiguous()).view(rows, G).tolist()
+            live = [r for r in range(rows) if st["remaining"][r] > 0]
             before = {r: (int(st["hist_len"][r]), int(st["n_acc"][r])) for r in live}
             spec_ref.advance(st, toks, NGRAM)
             for r in live:
@@ -94,6 +105,10 @@ def _reference(lm, prompts, n_new, dtype, eos=None, sample=None, seed=None):
                 accepted.append(int(st["n_acc"][r]) - a0)
                 for j in range(int(st["hist_len"][r]) - n0):  # token n0 + j of the sequence was drawn from logits row r * G + j
                     seen[(r, n0 + j)] = logits[r * G + j].clone()
+                if ends is not None and st["remaining"][r] > 0:
+                    c = _match_end(st["hist"][r, :int(st["hist_len"][r])].tolist(), NGRAM)
+                    if c is not None:
+                        ends.append((r, c))
     outs = []
     for s in sids:
         n = int(st["hist_len"][s])
@@ -106,11 +121,11 @@ def _check_acceptance(accepted):
     assert K in accepted and 0 in accepted and any(0 < a < K for a in accepted), accepted
 
 
-def _loop(lm, dtype, graph, num_blocks, rows=ROWS):
+def _loop(lm, dtype, graph, num_blocks, rows=ROWS, max_len=MAX_LEN):
     from qqq_amd import SpecDecodeLoop
 
     cache = lm.new_cache(num_blocks, BS, dtype)
-    return SpecDecodeLoop(lm, cache, rows=rows, max_len=MAX_LEN, draft_len=K, ngram_max=NGRAM, sync_every=SYNC, graph=graph), cache
+    return SpecDecodeLoop(lm, cache, rows=rows, max_len=max_len, draft_len=K, ngram_max=NGRAM, sync_every=SYNC, graph=graph), cache
 
 
 @pytest.mark.parametrize("gs", [-1, 128])
@@ -162,6 +177,37 @@ def test_captured_loop_equals_the_eager_one(dev, dtype):
         assert graph.generate(prompts, 1) == [o[:1] for o in got]
     assert eager.captures == 0 and graph.captures == 1
     assert c_e.free_blocks == nb and c_g.free_blocks == nb
+
+
+LONG_MAX_LEN, LONG_NEW = 320, 24
+# 290 tokens, a period of two per stretch: the latest occurrence of 1 ends at position 59 (wave 0 of the scan's first pass), of 2 and 3 at
+# 120 and 121 (wave 1), of 4 and 5 at 182 and 183 (wave 2), of 0 at 244 (wave 3); the last stretch, the one the first drafts continue,
+# ends beyond 256, on the second pass
+LONG_PROMPT = [0, 1] * 30 + [2, 3] * 31 + [4, 5] * 31 + [0, 6] * 31 + [7, 6] * 22
+
+
+def test_long_history_loops_equal_the_reference(dev):
+    """the greedy comparison of the two tests above once more in a loop of max_len 320 with a prompt of 290 tokens beside the others: the
+    drafter's scan takes a second pass, and the long row's matches end beyond position 256 as well as past wave 0 of the first pass
+    (asserted on the reference's)"""
+    lm = _make_lm(dev, 128)
+    prompts = _prompts() + [LONG_PROMPT]
+    assert len(LONG_PROMPT) == 290 and len(prompts) == ROWS
+    nb = sum(_blocks(prompts, LONG_NEW))
+    ends = []
+    with torch.no_grad():
+        want, accepted, _ = _reference(lm, prompts, LONG_NEW, torch.float16, max_len=LONG_MAX_LEN, rows=ROWS + 1, ends=ends)
+        where = sorted({((c % 256) // 64, c // 256) for r, c in ends if r == ROWS - 1})
+        print(f"accepted drafts per row-step: {accepted}; the long prompt's matches ended in (wave, pass) {where}: {ends}")
+        _check_acceptance(accepted)
+        assert any(p == 1 for _, p in where) and any(p == 0 and w >= 1 for w, p in where), where
+        eager, c_e = _loop(lm, torch.float16, False, nb, rows=ROWS + 1, max_len=LONG_MAX_LEN)
+        graph, c_g = _loop(lm, torch.float16, True, nb, rows=ROWS + 1, max_len=LONG_MAX_LEN)
+        assert eager.generate(prompts, LONG_NEW) == want and all(len(o) == LONG_NEW for o in want)
+        assert eager.accepted == sum(accepted) and eager.row_steps == len(accepted)
+        assert graph.generate(prompts, LONG_NEW) == want
+        assert (graph.accepted, graph.row_steps, graph.steps) == (eager.accepted, eager.row_steps, eager.steps)
+    assert eager.captures == 0 and graph.captures == 1 and c_e.free_blocks == nb and c_g.free_blocks == nb
 
 
 def test_idle_rows_are_inert(dev):
