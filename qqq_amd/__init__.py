@@ -17,6 +17,8 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     rope_qkv_paged_kv8(...) / decode_attention_paged_kv8(...)                       # over block pools (fp16 / int8) through slots and a block table
     prefill_attention_paged(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale) / prefill_attention_paged_kv8(...)  # ragged causal
                                                                                     # prefill attention over the block pools, output int8-quantised
+    verify_attention_paged(q_out, k_pool, v_pool, block_table, start, tokens, scale) / verify_attention_paged_kv8(...)  # a verify chunk of
+                                                                                    # `tokens` tokens per row through the decode kernel, bit for bit
     KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer                            # attention and the whole layer; qqq_amd/attention.py
     PagedKVCache, PagedStep                                                        # block pools + host-side allocator; qqq_amd/paged.py
     sample_tokens(logits, temperature, top_k, top_p, u)                             # temperature / top-k / top-p / draw for a batch, one launch
@@ -56,6 +58,8 @@ from .ops import (  # noqa: F401
     silu_mul_quant,
     spec_advance,
     token_logprobs,
+    verify_attention_paged,
+    verify_attention_paged_kv8,
 )
 from .qlinear import QuantLinear, fuse_quant_linears  # noqa: F401
 from .blocks import QuantLlamaMLP, QuantRMSNorm  # noqa: F401
@@ -71,4 +75,4 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "decode_attention_paged", "rope_qkv_paged_kv8", "decode_attention_paged_kv8", "prefill_attention_paged",
            "prefill_attention_paged_kv8", "PagedKVCache", "PagedStep", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer",
            "sample_tokens", "QuantLlamaModel", "QuantLlamaForCausalLM", "sample_advance", "DecodeLoop", "token_logprobs", "pack_steps",
-           "spec_advance", "SpecDecodeLoop", "ngram_draft"]
+           "spec_advance", "SpecDecodeLoop", "ngram_draft", "verify_attention_paged", "verify_attention_paged_kv8"]

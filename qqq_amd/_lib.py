@@ -97,6 +97,15 @@ def lib():
     L.qqq_prefill_attn_paged_kv8.restype = ci
     L.qqq_prefill_attn_workspace_bytes.argtypes = [ci, ci, ci]
     L.qqq_prefill_attn_workspace_bytes.restype = ctypes.c_size_t
+    # include/qqq_amd_verify.h
+    L.qqq_verify_attn_paged.argtypes = [vp, vp, vp, vp, ci, vp, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, ci, ci, ci, ci, ci, ci, ci,
+                                        ci, ci, vp]
+    L.qqq_verify_attn_paged.restype = ci
+    L.qqq_verify_attn_paged_kv8.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, ci, ci, ci, ci,
+                                            ci, ci, ci, ci, ci, vp]
+    L.qqq_verify_attn_paged_kv8.restype = ci
+    L.qqq_verify_attn_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci]
+    L.qqq_verify_attn_workspace_bytes.restype = ctypes.c_size_t
     # include/qqq_amd_sample.h
     L.qqq_sample_tokens.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.qqq_sample_tokens.restype = ci

@@ -19,9 +19,10 @@ position and xq [m, hidden] with the sequences' tokens packed in order.  rope_qk
 one token per sequence runs decode_attention_paged(_kv8) through the step's block table, whatever fuse_decode() says; any other step runs
 scaled_dot_product_attention per sequence over PagedKVCache.gather (a contiguous copy), or, after the opt-in fuse_prefill(),
 prefill_attention_paged(_kv8): one ragged causal attention over the whole packed batch that reads the pool in place and writes o_proj's
-input already int8-quantised.
+input already int8-quantised.  After the opt-in fuse_verify() a step that feeds every sequence the same 2 ... 16 tokens (a speculative decode
+step's chunk) runs verify_attention_paged(_kv8): the decode kernel's split over keys, every token bit for bit its decode step.
 Parameter and buffer names are the reference's, so the layers' state-dicts load unchanged; the rope tables, the fused q|k|v copy of
-fuse_qkv() and the fuse_decode() / fuse_prefill() flags are not part of them.
+fuse_qkv() and the fuse_decode() / fuse_prefill() / fuse_verify() flags are not part of them.
 """
 from __future__ import annotations
 
@@ -155,6 +156,7 @@ class QuantLlamaAttention(nn.Module):
         self._qkv = None  # fuse_qkv(): the fused q|k|v layer, kept outside the module tree (not in the state-dict)
         self._decode = False  # fuse_decode(): a plain flag (not in the state-dict; kept by load_state_dict and .to())
         self._prefill = False  # fuse_prefill(): the same kind of flag
+        self._verify = False  # fuse_verify(): the same kind of flag
         # a plain function: a bound method would make module -> hook -> module a reference cycle (see QuantLlamaMLP)
         self._register_load_state_dict_pre_hook(_drop_fused_qkv_on_load, with_module=True)
 
@@ -220,6 +222,33 @@ class QuantLlamaAttention(nn.Module):
     def prefill_fused(self) -> bool:
         return self._prefill
 
+    def fuse_verify(self):
+        """Opt-in: a step over a PagedKVCache that feeds every sequence the same number T of tokens, 2 <= T <= 16 with (h / kvh) * T <= 64
+        -- the chunk of a speculative decode step -- runs verify_attention_paged(_kv8): the decode kernel's split over keys with the
+        chunk's queries in the padding of its operands, every token's row bit for bit the decode step's for that token.  Every other step
+        goes where it goes without the flag (decode steps to the decode kernel, ragged or wider chunks to fuse_prefill()'s path or
+        SDPA).  state_dict(): unchanged.  Returns self."""
+        self._verify = True
+        return self
+
+    def unfuse_verify(self):
+        """Uniform chunks go back to where every other chunk goes."""
+        self._verify = False
+        return self
+
+    @property
+    def verify_fused(self) -> bool:
+        return self._verify
+
+    def _verify_tokens(self, step: PagedStep) -> int:
+        """T if fuse_verify() is set and `step` is a chunk the verify kernel takes (from the step's host lists alone), else 0."""
+        if not self._verify or step.decode or step.start_pos is None or not step.counts:
+            return 0
+        t = step.counts[0]
+        if t < 2 or t > 16 or (self.num_heads // self.num_key_value_heads) * t > 64 or any(c != t for c in step.counts):
+            return 0
+        return t
+
     def _decode_supported(self) -> bool:
         h, kvh, d = self.num_heads, self.num_key_value_heads, self.head_dim
         return d in (64, 128) and h // kvh <= 8 and h * d <= 16384
@@ -278,6 +307,11 @@ class QuantLlamaAttention(nn.Module):
         if step.decode:  # one token per sequence: the decode kernel through the block table, whatever fuse_decode() says
             decode = ops.decode_attention_paged_kv8 if cache.quantized else ops.decode_attention_paged
             aq, a1 = decode(q_out, *pools, step.block_table, step.last_pos, self.scaling, max_len=step.max_len)
+            return self.o_proj.forward_int8(aq, a1)
+        t = self._verify_tokens(step)
+        if t:  # fuse_verify(): a uniform chunk of t tokens per sequence through the decode kernel's split over keys
+            verify = ops.verify_attention_paged_kv8 if cache.quantized else ops.verify_attention_paged
+            aq, a1 = verify(q_out, *pools, step.block_table, step.start_pos, t, self.scaling, max_len=step.max_len)
             return self.o_proj.forward_int8(aq, a1)
         if self._prefill:  # fuse_prefill(): the whole packed batch in one ragged causal attention over the pool, quantised for o_proj
             prefill = ops.prefill_attention_paged_kv8 if cache.quantized else ops.prefill_attention_paged
@@ -398,6 +432,19 @@ class QuantLlamaDecoderLayer(nn.Module):
     @property
     def prefill_fused(self) -> bool:
         return self.self_attn.prefill_fused
+
+    def fuse_verify(self):
+        """self_attn.fuse_verify(): uniform paged chunks of 2 ... 16 tokens per sequence take the verify attention kernel.  Returns self."""
+        self.self_attn.fuse_verify()
+        return self
+
+    def unfuse_verify(self):
+        self.self_attn.unfuse_verify()
+        return self
+
+    @property
+    def verify_fused(self) -> bool:
+        return self.self_attn.verify_fused
 
     def forward(self, hidden: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
         x = hidden.reshape(-1, self.hidden_size)

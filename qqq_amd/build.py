@@ -28,6 +28,7 @@ SAMPLE_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_sample.h")
 STEP_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_step.h")
 SCORE_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_score.h")
 SPEC_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_spec.h")
+VERIFY_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_verify.h")
 DEV_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_dev.h")
 LIB = os.environ.get("QQQ_AMD_LIB") or os.path.join(_HERE, "libqqq_amd.so")  # override: tuning builds only
 DEV_LIB = os.path.join(_HERE, "libqqq_amd_dev.so")
@@ -51,7 +52,8 @@ def _stale(lib: str, extra) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(LIB, [HDR, ACT_HDR, ATTN_HDR, DECODE_HDR, KV8_HDR, PAGED_HDR, PREFILL_HDR, SAMPLE_HDR, STEP_HDR, SCORE_HDR, SPEC_HDR])
+    return _stale(LIB, [HDR, ACT_HDR, ATTN_HDR, DECODE_HDR, KV8_HDR, PAGED_HDR, PREFILL_HDR, SAMPLE_HDR, STEP_HDR, SCORE_HDR, SPEC_HDR,
+                        VERIFY_HDR])
 
 
 def _compile(src: str, out: str, verbose: bool, flags=()) -> str:

@@ -172,16 +172,13 @@ __global__ __launch_bounds__(DEC_WAVES * 64) __attribute__((amdgpu_waves_per_eu(
   }
 }
 
-// One workgroup per batch row: merge the splits of all h heads, round to fp16 once, optionally store the fp16 row, quantise it.
+// The combine of one row: row bi of the partials, whose query sits at position p (0 <= p < the call's max_len).  The body of
+// qqq_decode_combine_kernel, shared with the verify chunk's combine (qqq_verify.hip.h), where a row is a token and p its own position.
 template <int VPT, int NT>
-__global__ __launch_bounds__(NT) void qqq_decode_combine_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
-                                                                const long long* __restrict__ pos, const long long limit,
-                                                                _Float16* __restrict__ o16, int8_t* __restrict__ xq, float* __restrict__ s1,
-                                                                const int h, const int d, const int chunk, const int splits) {
-  __shared__ float red_max[NT / 64];
-  const int bi = blockIdx.x;
-  const long long p = pos[bi];
-  if (p < 0 || p >= limit) return;  // out-of-range row: no fp16 row, no xq, no s1
+__device__ __forceinline__ void qqq_decode_combine_row(const float* __restrict__ ws_o, const float* __restrict__ ws_ml, const int bi,
+                                                       const long long p, _Float16* __restrict__ o16, int8_t* __restrict__ xq,
+                                                       float* __restrict__ s1, const int h, const int d, const int chunk, const int splits,
+                                                       float* red_max) {
   const int nsp = (int)(p / chunk) + 1;  // splits that cover 0 ... p
   const int tid = threadIdx.x;
   const int nvec = (h * d) >> 3;
@@ -214,6 +211,19 @@ __global__ __launch_bounds__(NT) void qqq_decode_combine_kernel(const float* __r
     }
   }
   if (xq) qqq_act_quant_row<VPT, NT>(v, nvec, xq + (size_t)bi * h * d, s1 + bi, red_max);
+}
+
+// One workgroup per batch row: merge the splits of all h heads, round to fp16 once, optionally store the fp16 row, quantise it.
+template <int VPT, int NT>
+__global__ __launch_bounds__(NT) void qqq_decode_combine_kernel(const float* __restrict__ ws_o, const float* __restrict__ ws_ml,
+                                                                const long long* __restrict__ pos, const long long limit,
+                                                                _Float16* __restrict__ o16, int8_t* __restrict__ xq, float* __restrict__ s1,
+                                                                const int h, const int d, const int chunk, const int splits) {
+  __shared__ float red_max[NT / 64];
+  const int bi = blockIdx.x;
+  const long long p = pos[bi];
+  if (p < 0 || p >= limit) return;  // out-of-range row: no fp16 row, no xq, no s1
+  qqq_decode_combine_row<VPT, NT>(ws_o, ws_ml, bi, p, o16, xq, s1, h, d, chunk, splits, red_max);
 }
 
 #endif  // QQQ_AMD_QQQ_DECODE_HIP_H_

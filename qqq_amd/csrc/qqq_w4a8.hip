@@ -81,6 +81,8 @@
 #include "../../include/qqq_amd_step.h"
 #include "qqq_spec.hip.h"
 #include "../../include/qqq_amd_spec.h"
+#include "qqq_verify.hip.h"
+#include "../../include/qqq_amd_verify.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -922,6 +924,132 @@ extern "C" int qqq_decode_attn_paged_kv8(const void* q, const void* k_pool, cons
                                          int block_size, int max_len, int dev, void* stream) {
   return decode_attn_paged("qqq_decode_attn_paged_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, pos, scale,
                            o_fp16, xq, s1, workspace, workspace_bytes, b, h, kvh, d, num_blocks, block_size, max_len, dev, stream);
+}
+
+// ---- the verify chunk's attention (include/qqq_amd_verify.h; kernels in qqq_verify.hip.h): decode_attn_paged's two launches for t tokens
+// per batch row.  One body for the pair; `name` is the entry point's.
+extern "C" size_t qqq_verify_attn_workspace_bytes(int b, int t, int h, int kvh, int d, int max_len) {
+  if (b < 0 || t < 1 || t > VER_TMAX || (long long)b * t > 65535) return 0;
+  return qqq_decode_attn_workspace_bytes(b * t, h, kvh, d, max_len);
+}
+
+template <int VPT>
+static void verify_combine(int rows, hipStream_t st, const float* wo, const float* wml, const long long* start, long long limit, int t,
+                           _Float16* o16, int8_t* xq, float* s1, int h, int d, int chunk, int splits) {
+  hipLaunchKernelGGL((qqq_verify_combine_kernel<VPT, DEC_COMBINE_NT>), dim3(rows), dim3(DEC_COMBINE_NT), 0, st, wo, wml, start, limit, t,
+                     o16, xq, s1, h, d, chunk, splits);
+}
+
+template <int D, int NQ, typename... Args>
+static void verify_split(bool kv8, dim3 grid, hipStream_t st, const _Float16* q, const void* k_pool, const void* v_pool, const void* k_scale,
+                         const void* v_scale, Args... rest) {
+  if (kv8)
+    hipLaunchKernelGGL((qqq_verify_kv8_split_kernel<D, NQ>), grid, dim3(DEC_WAVES * 64), 0, st, q, static_cast<const int8_t*>(k_pool),
+                       static_cast<const int8_t*>(v_pool), static_cast<const float*>(k_scale), static_cast<const float*>(v_scale), rest...);
+  else
+    hipLaunchKernelGGL((qqq_verify_split_kernel<D, NQ>), grid, dim3(DEC_WAVES * 64), 0, st, q, static_cast<const _Float16*>(k_pool),
+                       static_cast<const _Float16*>(v_pool), rest...);
+}
+
+template <int D, typename... Args>
+static void verify_split_tiles(int rows, Args... args) {
+  if (rows <= 16)
+    verify_split<D, 1>(args...);
+  else if (rows <= 32)
+    verify_split<D, 2>(args...);
+  else
+    verify_split<D, 4>(args...);
+}
+
+static int verify_attn_paged(const char* name, bool kv8, const void* q, const void* k_pool, const void* v_pool, const void* k_scale,
+                             const void* v_scale, const void* block_table, int table_stride, const void* start, float scale, void* o_fp16,
+                             void* xq, void* s1, void* workspace, size_t workspace_bytes, int b, int t, int h, int kvh, int d,
+                             int num_blocks, int block_size, int max_len, int dev, void* stream) {
+  g_err[0] = 0;
+  if (b < 0 || t < 0 || h < 0 || kvh < 0 || d < 0 || num_blocks < 0 || block_size < 0 || table_stride < 0 || max_len < 0) {
+    snprintf(g_err, sizeof(g_err), "%s: negative size (b=%d t=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_stride=%d max_len=%d)",
+             name, b, t, h, kvh, d, num_blocks, block_size, table_stride, max_len);
+    return QQQ_ERR_ARG;
+  }
+  if (b == 0) return QQQ_OK;
+  const int lbs = paged_log2_block(block_size);
+  if (decode_shape_error(b, h, kvh, d, max_len) || t < 1 || t > VER_TMAX || (h / kvh) * t > VER_ROWS_MAX || (long long)b * t > 65535 ||
+      lbs < 0 || num_blocks < 1 || (long long)num_blocks * block_size > 0x7fffffffLL || table_stride < 1 ||
+      max_len > (long long)table_stride * block_size) {
+    snprintf(g_err, sizeof(g_err), "%s: bad shape b=%d t=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_stride=%d max_len=%d (need "
+             "h %% kvh == 0, h / kvh <= %d, d 64 or 128, h*d <= 16384, 1 <= t <= %d, (h / kvh) * t <= %d, b * t <= 65535, block_size a power "
+             "of two in [16, 256], num_blocks >= 1, num_blocks * block_size < 2^31, 1 <= max_len <= table_stride * block_size)", name, b, t,
+             h, kvh, d, num_blocks, block_size, table_stride, max_len, DEC_GMAX, VER_TMAX, VER_ROWS_MAX);
+    return QQQ_ERR_ARG;
+  }
+  if (!o_fp16 && !xq && !s1) {
+    snprintf(g_err, sizeof(g_err), "%s: no output (o_fp16 and xq / s1 are all NULL)", name);
+    return QQQ_ERR_ARG;
+  }
+  if (!q || !k_pool || !v_pool || !block_table || !start || !workspace || (!xq) != (!s1) || misaligned(q, 16) || misaligned(k_pool, 16) ||
+      misaligned(v_pool, 16) || misaligned(block_table, 4) || misaligned(start, 8) || misaligned(workspace, 16) ||
+      (o_fp16 && misaligned(o_fp16, 16)) || (xq && misaligned(xq, 8)) || (s1 && misaligned(s1, 4)) ||
+      (kv8 && (!k_scale || !v_scale || misaligned(k_scale, 4) || misaligned(v_scale, 4)))) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (q / pools / scales / block_table / start / workspace must be non-NULL, xq and s1 both "
+             "given or both NULL; q, pools, o_fp16, workspace 16-byte, start / xq 8-byte, block_table, s1 and the scales 4-byte aligned)",
+             name);
+    return QQQ_ERR_ARG;
+  }
+  const size_t need = qqq_verify_attn_workspace_bytes(b, t, h, kvh, d, max_len);
+  if (workspace_bytes < need) {
+    snprintf(g_err, sizeof(g_err), "%s: workspace of %zu bytes, need %zu", name, workspace_bytes, need);
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int splits, chunk;
+  decode_split_plan(dev, b, kvh, max_len, &splits, &chunk);  // b batch rows: the plan of the decode call each token is compared with
+  const int rows = b * t;
+  float* wo = static_cast<float*>(workspace);
+  float* wml = wo + (size_t)rows * h * splits * d;
+  const long long* sp = static_cast<const long long*>(start);
+  const long long limit = max_len;  // <= table_stride * block_size
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const _Float16* qp = static_cast<const _Float16*>(q);
+  const int* tp = static_cast<const int*>(block_table);
+  const dim3 grid(splits, kvh, b);
+  if (d == 64)
+    verify_split_tiles<64>((h / kvh) * t, kv8, grid, st, qp, k_pool, v_pool, k_scale, v_scale, tp, table_stride, sp, limit, scale_log2, wo,
+                           wml, h, kvh, t, num_blocks, lbs, chunk, splits);
+  else
+    verify_split_tiles<128>((h / kvh) * t, kv8, grid, st, qp, k_pool, v_pool, k_scale, v_scale, tp, table_stride, sp, limit, scale_log2, wo,
+                            wml, h, kvh, t, num_blocks, lbs, chunk, splits);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, kv8 ? "qqq_verify_kv8_split_kernel launch" : "qqq_verify_split_kernel launch");
+  _Float16* o16 = static_cast<_Float16*>(o_fp16);
+  int8_t* xqp = static_cast<int8_t*>(xq);
+  float* s1p = static_cast<float*>(s1);
+  const int nvec = h * d / 8;
+  if (nvec <= DEC_COMBINE_NT)
+    verify_combine<1>(rows, st, wo, wml, sp, limit, t, o16, xqp, s1p, h, d, chunk, splits);
+  else if (nvec <= 2 * DEC_COMBINE_NT)
+    verify_combine<2>(rows, st, wo, wml, sp, limit, t, o16, xqp, s1p, h, d, chunk, splits);
+  else
+    verify_combine<4>(rows, st, wo, wml, sp, limit, t, o16, xqp, s1p, h, d, chunk, splits);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_verify_combine_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_verify_attn_paged(const void* q, const void* k_pool, const void* v_pool, const void* block_table, int table_stride,
+                                     const void* start, float scale, void* o_fp16, void* xq, void* s1, void* workspace,
+                                     size_t workspace_bytes, int b, int t, int h, int kvh, int d, int num_blocks, int block_size, int max_len,
+                                     int dev, void* stream) {
+  return verify_attn_paged("qqq_verify_attn_paged", false, q, k_pool, v_pool, nullptr, nullptr, block_table, table_stride, start, scale,
+                           o_fp16, xq, s1, workspace, workspace_bytes, b, t, h, kvh, d, num_blocks, block_size, max_len, dev, stream);
+}
+
+extern "C" int qqq_verify_attn_paged_kv8(const void* q, const void* k_pool, const void* v_pool, const void* k_scale, const void* v_scale,
+                                         const void* block_table, int table_stride, const void* start, float scale, void* o_fp16, void* xq,
+                                         void* s1, void* workspace, size_t workspace_bytes, int b, int t, int h, int kvh, int d,
+                                         int num_blocks, int block_size, int max_len, int dev, void* stream) {
+  return verify_attn_paged("qqq_verify_attn_paged_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, start, scale,
+                           o_fp16, xq, s1, workspace, workspace_bytes, b, t, h, kvh, d, num_blocks, block_size, max_len, dev, stream);
 }
 
 // ---- the paged prefill attention (include/qqq_amd_prefill.h; kernels in qqq_prefill.hip.h): one attention launch over the packed batch's

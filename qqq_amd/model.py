@@ -77,6 +77,13 @@ class QuantLlamaModel(nn.Module):
     def unfuse_prefill(self):
         return self._each_layer("unfuse_prefill")
 
+    def fuse_verify(self):
+        """fuse_verify() on every layer.  Returns self."""
+        return self._each_layer("fuse_verify")
+
+    def unfuse_verify(self):
+        return self._each_layer("unfuse_verify")
+
     def fuse_qkv(self):
         """self_attn.fuse_qkv() on every layer (a second copy of the q / k / v weights).  Returns self."""
         for layer in self.layers:
@@ -141,6 +148,14 @@ class QuantLlamaForCausalLM(nn.Module):
         self.model.fuse_prefill()
         return self
 
+    def fuse_verify(self):
+        self.model.fuse_verify()
+        return self
+
+    def unfuse_verify(self):
+        self.model.unfuse_verify()
+        return self
+
     def fuse_qkv(self):
         self.model.fuse_qkv()
         return self
@@ -174,7 +189,7 @@ class QuantLlamaForCausalLM(nn.Module):
         rounded up to a block: the decode steps replay from one captured graph and the host syncs once per several tokens.  Greedy tokens
         are the same; the random draws are the loop's (one torch.rand(rows, u_stride) per u_stride steps).
 
-        draft_len=K > 0 (with device_loop=True, on a model with fuse_prefill()) makes that loop a SpecDecodeLoop: K tokens drafted by
+        draft_len=K > 0 (with device_loop=True, on a model with fuse_prefill() or fuse_verify()) makes that loop a SpecDecodeLoop: K tokens drafted by
         n-gram lookup ride behind every row's last token and a replay emits 1 ... K + 1 tokens per row.  The output distribution is
         unchanged; the tokens under a seed differ (K + 1 variates per row and step), greedy tokens are the same up to near-ties of the
         logits.  Every sequence needs K more keys of the pool."""

@@ -1100,6 +1100,121 @@ def prefill_attention_paged_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_poo
     return out if return_fp16 else out[:2]
 
 
+# ---- the verify chunk's attention (include/qqq_amd_verify.h): `tokens` consecutive tokens per row through the decode kernel's operand
+# layout, every token bit for bit decode_attention_paged(_kv8) of that token alone.
+
+def _verify_attention_paged_shapes(name, q_out, k_pool, block_table, start, tokens, max_len):
+    # (b, t, h, kvh, d, num_blocks, block_size, table_stride, max_len) from the tensors' shapes
+    if k_pool.dim() != 4:
+        raise RuntimeError(f"{name}: k_pool must be [num_blocks, kvh, block_size, d]")
+    nb, kvh, bs, d = k_pool.shape
+    if block_table.dim() != 2:
+        raise RuntimeError(f"{name}: block_table must be int32 [b, blocks per row]")
+    b, width = block_table.shape
+    t = int(tokens)
+    if t < 1:
+        raise RuntimeError(f"{name}: tokens = {t}, need at least one token per row")
+    if q_out.dim() != 3 or q_out.shape[0] != b * t or q_out.shape[2] != d:
+        raise RuntimeError(f"{name}: q_out {tuple(q_out.shape)} must be [{b * t}, h, {d}] (rope_qkv_paged's output of {b} rows of {t} tokens)")
+    if start.numel() != b:
+        raise RuntimeError(f"{name}: start holds {start.numel()} positions, the block table has {b} rows")
+    max_len = width * bs if max_len is None else int(max_len)
+    return b, t, q_out.shape[1], kvh, d, nb, bs, width, max_len
+
+
+def _verify_attention_paged_impl(q_out, k_pool, v_pool, block_table, start, tokens, scale, max_len, return_fp16, k_scale=None, v_scale=None):
+    kv8 = k_scale is not None
+    name = "verify_attention_paged_kv8" if kv8 else "verify_attention_paged"
+    ts = (q_out, k_pool, v_pool, block_table, start) + ((k_scale, v_scale) if kv8 else ())
+    _same_gpu(name, ts)
+    if q_out.dtype != torch.float16 or start.dtype != torch.int64 or block_table.dtype != torch.int32:
+        raise RuntimeError(f"{name}: q_out must be fp16, start int64 and block_table int32")
+    _paged_check_pools(name, k_pool, v_pool, k_scale, v_scale)
+    b, t, h, kvh, d, nb, bs, width, max_len = _verify_attention_paged_shapes(name, q_out, k_pool, block_table, start, tokens, max_len)
+    dev = q_out.device
+    m = b * t
+    xq = torch.empty((m, h * d), dtype=torch.int8, device=dev)
+    s1 = torch.empty((m, 1), dtype=torch.float32, device=dev)
+    o16 = torch.empty((m, h * d) if return_fp16 else (0,), dtype=torch.float16, device=dev)
+    if b == 0:
+        return xq, s1, o16
+    L = _lib.lib()
+    nbytes = L.qqq_verify_attn_workspace_bytes(b, t, h, kvh, d, max_len)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)  # torch's allocator: also under stream / graph capture
+    q2, start, table = q_out.contiguous(), start.contiguous(), block_table.contiguous()
+    tail = (_ptr(table), width, _ptr(start), float(scale), _ptr(o16), _ptr(xq), _ptr(s1), _ptr(ws), ws.numel(), b, t, h, kvh, d, nb, bs,
+            max_len, dev.index or 0, _stream_for(q_out))
+    if kv8:
+        err = L.qqq_verify_attn_paged_kv8(_ptr(q2), _ptr(k_pool), _ptr(v_pool), _ptr(k_scale), _ptr(v_scale), *tail)
+    else:
+        err = L.qqq_verify_attn_paged(_ptr(q2), _ptr(k_pool), _ptr(v_pool), *tail)
+    _raise_lib(name, err)
+    return xq, s1, o16
+
+
+def _verify_paged_fake(name, q_out, k_pool, block_table, start, tokens, max_len, return_fp16):
+    b, t, h, _, d = _verify_attention_paged_shapes(name, q_out, k_pool, block_table, start, tokens, max_len)[:5]
+    return (q_out.new_empty((b * t, h * d), dtype=torch.int8), q_out.new_empty((b * t, 1), dtype=torch.float32),
+            q_out.new_empty((b * t, h * d) if return_fp16 else (0,), dtype=torch.float16))
+
+
+@torch.library.custom_op("qqq_amd::verify_attn_paged", mutates_args=())
+def _verify_attn_paged_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, start: torch.Tensor,
+                          tokens: int, scale: float, max_len: Optional[int],
+                          return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _verify_attention_paged_impl(q_out, k_pool, v_pool, block_table, start, tokens, scale, max_len, return_fp16)
+
+
+@_verify_attn_paged_op.register_fake
+def _(q_out, k_pool, v_pool, block_table, start, tokens, scale, max_len, return_fp16):
+    return _verify_paged_fake("verify_attention_paged", q_out, k_pool, block_table, start, tokens, max_len, return_fp16)
+
+
+def verify_attention_paged(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor, start: torch.Tensor,
+                           tokens: int, scale: float, max_len: Optional[int] = None, return_fp16: bool = False):
+    """Attention of a verify chunk -- `tokens` consecutive tokens per row, as a speculative decode step feeds them -- over a block pool:
+    (xq int8 [b*tokens, h*d], s1 f32 [b*tokens, 1]), plus the fp16 output [b*tokens, h*d] with `return_fp16`.  Every token's rows are bit
+    for bit decode_attention_paged's for that token alone (its q rows, pos = start + j, equal b and max_len); K and V are read once per KV
+    head for the whole chunk and the keys stay split over workgroups.  Two launches.
+
+    q_out      fp16 [b*tokens, h, d], token-major: rope_qkv_paged's output of the chunk (token j of row r is row r*tokens + j; the chunk's
+               own keys are in the pool already)
+    k_pool, v_pool, block_table   as for decode_attention_paged; only the entries up to (start[r] + tokens - 1) // block_size are read
+    start      int64 [b]: the position of row r's first token; token j attends keys 0 ... start[r] + j
+    tokens     1 ... 16, with (h / kvh) * tokens <= 64 and b * tokens <= 65535
+    max_len    default and upper bound W * block_size; token j of a row with start[r] < 0 or start[r] + j >= max_len writes nothing (its
+               rows are left as torch.empty made them)"""
+    if _compiling(q_out, k_pool, v_pool, block_table, start):
+        out = _verify_attn_paged_op(q_out, k_pool, v_pool, block_table, start, tokens, scale, max_len, return_fp16)
+    else:
+        out = _verify_attention_paged_impl(q_out, k_pool, v_pool, block_table, start, tokens, scale, max_len, return_fp16)
+    return out if return_fp16 else out[:2]
+
+
+@torch.library.custom_op("qqq_amd::verify_attn_paged_kv8", mutates_args=())
+def _verify_attn_paged_kv8_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                              block_table: torch.Tensor, start: torch.Tensor, tokens: int, scale: float, max_len: Optional[int],
+                              return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _verify_attention_paged_impl(q_out, k_pool, v_pool, block_table, start, tokens, scale, max_len, return_fp16, k_scale, v_scale)
+
+
+@_verify_attn_paged_kv8_op.register_fake
+def _(q_out, k_pool, v_pool, k_scale, v_scale, block_table, start, tokens, scale, max_len, return_fp16):
+    return _verify_paged_fake("verify_attention_paged_kv8", q_out, k_pool, block_table, start, tokens, max_len, return_fp16)
+
+
+def verify_attention_paged_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor,
+                               block_table: torch.Tensor, start: torch.Tensor, tokens: int, scale: float, max_len: Optional[int] = None,
+                               return_fp16: bool = False):
+    """verify_attention_paged over an int8 pool (k_pool, v_pool int8 [num_blocks, kvh, block_size, d]; k_scale, v_scale f32 [num_blocks, kvh,
+    block_size]): every token bit for bit decode_attention_paged_kv8's."""
+    if _compiling(q_out, k_pool, v_pool, k_scale, v_scale, block_table, start):
+        out = _verify_attn_paged_kv8_op(q_out, k_pool, v_pool, k_scale, v_scale, block_table, start, tokens, scale, max_len, return_fp16)
+    else:
+        out = _verify_attention_paged_impl(q_out, k_pool, v_pool, block_table, start, tokens, scale, max_len, return_fp16, k_scale, v_scale)
+    return out if return_fp16 else out[:2]
+
+
 # ---- the fused token sampler (include/qqq_amd_sample.h): logits -> next-token ids, one launch for the whole batch
 
 def _sample_param(name, v, rows, dtype, device, op="sample_tokens"):

@@ -294,6 +294,11 @@ def ngram_draft(history: Sequence[int], draft_len: int, ngram_max: int = 3) -> L
     return out
 
 
+def _takes_verify(attn, group: int) -> bool:
+    """fuse_verify() is set on `attn` and its kernel takes a chunk of `group` tokens per row"""
+    return getattr(attn, "_verify", False) and 2 <= group <= 16 and (attn.num_heads // attn.num_key_value_heads) * group <= 64
+
+
 class SpecDecodeLoop(DecodeLoop):
     """DecodeLoop with speculation: every row feeds its last token and `draft_len` drafted tokens through one forward pass (a chunk of
     G = draft_len + 1 tokens per row through the paged prefill attention kernel, every token's logits), and ops.spec_advance draws a token
@@ -303,7 +308,9 @@ class SpecDecodeLoop(DecodeLoop):
     DecodeLoop's at any temperature, top_k and top_p.  The tokens under a seed are not: a step uses G variates per row.  Greedy tokens
     are DecodeLoop's up to near-ties of the logits (the head GEMM runs at another row count).
 
-    The model must have fuse_prefill() set: the per-sequence SDPA path reads lengths on the host.  A sequence needs
+    The model must have fuse_prefill() or fuse_verify() set: the per-sequence SDPA path reads lengths on the host.  With fuse_verify() the
+    step's chunk takes the verify attention kernel, whose rows are bit for bit the decode steps'; admission prefill stays as it is.  A
+    sequence needs
     len(prompt) + max_new_tokens - 1 + draft_len keys of the pool and of max_len: the drafts behind its last token are written too.
     ngram_max   the longest n-gram the drafter looks up (1 ... 4);  u_stride  default sync_every * G, a multiple of G
     After a generate(): `accepted` drafts were accepted in `row_steps` steps of single rows, over `steps` steps of the loop; a row-step
@@ -330,9 +337,10 @@ class SpecDecodeLoop(DecodeLoop):
             raise ValueError(f"SpecDecodeLoop: rows={rows} times draft_len + 1 = {group} exceeds the sampler's 65535 logits rows")
         if max_len <= draft_len:
             raise ValueError(f"SpecDecodeLoop: max_len={max_len} must exceed draft_len={draft_len}")
-        if not all(getattr(layer.self_attn, "_prefill", False) for layer in lm.model.layers):
-            raise RuntimeError("SpecDecodeLoop: the model needs fuse_prefill(): a step is a chunk of draft_len + 1 tokens per row, and only "
-                               "the paged prefill attention kernel serves chunks without reading lengths on the host")
+        if not all(getattr(layer.self_attn, "_prefill", False) or _takes_verify(layer.self_attn, group) for layer in lm.model.layers):
+            raise RuntimeError("SpecDecodeLoop: the model needs fuse_prefill() or fuse_verify(): a step is a chunk of draft_len + 1 tokens per "
+                               "row, and only the paged prefill and the verify attention kernels serve chunks without reading lengths on the "
+                               "host (fuse_verify() alone takes chunks of (h / kvh) * (draft_len + 1) <= 64 query rows)")
         self.draft_len, self.ngram_max, self.group = draft_len, ngram_max, group
         self.accepted = self.row_steps = self.steps = 0
         self._allocate(lm, cache, rows, max_len, sync_every, u_stride, graph, dev)

@@ -27,12 +27,21 @@ KV cache.  Both paths start from the fp16 output of input_layernorm and end with
                 more than the unfused path's spread over the rounds.  The attention op alone is timed from a hipGraph as well and its rate
                 given against the nominal fp16 MFMA peak (FP16_PEAK_TFLOPS).
 
+    verify      (--points verify [--kv8] [--block-size N]: this mode alone) the attention op of a speculative step's chunk alone, three ways
+                over the same pool, block table and positions: verify_attention_paged(_kv8) for the chunk of T tokens per row,
+                prefill_attention_paged(_kv8) for the same chunk (what the step ran before fuse_verify()), and decode_attention_paged(_kv8)
+                for one token per row at the chunk's last position (the floor: the same keys once).  Each is replayed from a hipGraph
+                (tools/bench_llama.time_fn), alternately, VERIFY_ROUNDS times in one process; every round is kept, with median, min and max.
+                Shapes as above, b in {1, 16}, contexts {256, 4096, 16384} where the pool fits VERIFY_POOL_BYTES, T in {3, 5, 8}.
+                `faster_than_prefill` says whether the verify median is below the prefill median by more than the latter's spread.
+
 Points: decode (s = 1) at b in {1, 16} with a context of {1024, 4096} tokens (the new token included), and b = 1 at 16384; prefill of s in
 {128, 1024, 4096} tokens at b = 1 from position 0.  Before each point one dynamic_quant of POINT_MARK + i rows is launched: its grid marks
 where point i starts in a kernel trace.
 
     python tools/bench_attn.py [--points decode,prefill] [--kv8] [--out FILE]   -> one JSON object on stdout
     python tools/bench_attn.py --points prefill --paged [--kv8] [--block-size N] [--out FILE]   -> the paged prefill points alone
+    python tools/bench_attn.py --points verify [--kv8] [--block-size N] [--out profiles/verify_attn_bench.json]   -> the verify points alone
     python tools/bench_attn.py --summarize TRACE_DIR [--bench FILE]     -> from a rocprofv3 --kernel-trace run of the above: the
                                                                           qqq_rope_qkv_kernel times and HBM fractions, and per decode point
                                                                           (labelled from the run's JSON output FILE) the median times of
@@ -68,6 +77,9 @@ FP16_PEAK_TFLOPS = 2500.0  # MI355X, dense fp16 MFMA (nominal)
 # (name, [(start, count) per sequence]): a prompt, a batch of prompts, a late chunk, and that chunk batched with 15 decoding rows
 PAGED_PREFILL = [("1x2048", [(0, 2048)]), ("8x512", [(0, 512)] * 8), ("chunk512@3584", [(3584, 512)]),
                  ("chunk512@3584+15dec@2048", [(3584, 512)] + [(2047, 1)] * 15)]
+VERIFY_ROUNDS = 5  # --points verify: alternations of the three ops at a point
+VERIFY_CONTEXTS, VERIFY_TOKENS, VERIFY_BATCHES = (256, 4096, 16384), (3, 5, 8), (1, 16)
+VERIFY_POOL_BYTES = 8 << 30  # K and V pools of a point together
 PREFILL_KERNELS = ("qqq_prefill_attn_kernel", "qqq_prefill_quant_kernel", "qqq_paged_rope_qkv_kernel", "qqq_paged_kv8_rope_qkv_kernel",
                    "qqq_dynamic_quant_kernel")
 SPLIT_KERNELS = ("qqq_decode_split_kernel", "qqq_kv8_decode_split_kernel", "qqq_paged_decode_split_kernel",
@@ -418,6 +430,77 @@ def summarize(trace_dir, bench=None):
     return {"unit": "kernel time from rocprofv3 --kernel-trace (median over calls)", "kernels": rows, "points": decode}
 
 
+def run_verify(kv8=False, block_size=128):
+    """--points verify: see the module docstring; --kv8 adds the int8 pool's points behind the fp16 pool's"""
+    out = _run_verify(False, block_size)
+    if kv8:
+        more = _run_verify(True, block_size)
+        out["pool"] = "fp16, then int8"
+        out["points"] += more["points"]
+        out["skipped"] += more["skipped"]
+    return out
+
+
+def _run_verify(kv8, block_size):
+    import statistics
+
+    import torch
+
+    from bench_llama import time_fn
+    from qqq_amd import ops
+
+    dev = torch.device("cuda:0")
+    out = {"tool": "tools/bench_attn.py --points verify", "device": torch.cuda.get_device_name(0),
+           "head_dim": D, "block_size": block_size, "pool": "int8" if kv8 else "fp16", "rounds": VERIFY_ROUNDS,
+           "unit": "us per call of the attention op alone, hipGraph replay (median of a round's replays); per op the rounds, their median, "
+                   "min and max", "points": [], "skipped": []}
+    g = torch.Generator(device=dev).manual_seed(7)
+    for shape, (h, kvh) in SHAPES.items():
+        for b in VERIFY_BATCHES:
+            for ctx in VERIFY_CONTEXTS:  # keys a row holds once the chunk is written: the last token sits at ctx - 1
+                per = -(-ctx // block_size)
+                nb = b * per
+                nbytes = 2 * nb * kvh * block_size * (D + 4 if kv8 else 2 * D)
+                if nbytes > VERIFY_POOL_BYTES:
+                    out["skipped"].append({"shape": shape, "pool": "int8" if kv8 else "fp16", "batch": b, "context": ctx, "why": f"pools of {nbytes >> 20} MiB"})
+                    continue
+                if kv8:
+                    pools = tuple(torch.randint(-127, 128, (nb, kvh, block_size, D), generator=g, device=dev, dtype=torch.int8)
+                                  for _ in range(2))
+                    pools += tuple(torch.rand((nb, kvh, block_size), generator=g, device=dev) * 0.02 + 0.005 for _ in range(2))
+                else:
+                    pools = tuple(torch.randn((nb, kvh, block_size, D), generator=g, device=dev).half() for _ in range(2))
+                table = torch.randperm(nb, generator=torch.Generator().manual_seed(ctx + b)).to(dev).reshape(b, per).to(torch.int32)
+                last = torch.full((b,), ctx - 1, dtype=torch.int64, device=dev)
+                q1 = torch.randn((b, h, D), generator=g, device=dev).half()
+                decode = ops.decode_attention_paged_kv8 if kv8 else ops.decode_attention_paged
+                verify = ops.verify_attention_paged_kv8 if kv8 else ops.verify_attention_paged
+                prefill = ops.prefill_attention_paged_kv8 if kv8 else ops.prefill_attention_paged
+                for t in VERIFY_TOKENS:
+                    start = last - (t - 1)
+                    cu = torch.arange(b + 1, dtype=torch.int32, device=dev) * t
+                    q = torch.randn((b * t, h, D), generator=g, device=dev).half()
+                    fns = {"verify": lambda: verify(q, *pools, table, start, t, D ** -0.5, max_len=ctx),
+                           "prefill": lambda: prefill(q, *pools, table, cu, start, D ** -0.5, max_len=ctx),
+                           "decode": lambda: decode(q1, *pools, table, last, D ** -0.5, max_len=ctx)}
+                    runs = {name: [] for name in fns}
+                    for _ in range(VERIFY_ROUNDS):
+                        for name, fn in fns.items():
+                            runs[name].append(round(time_fn(fn), 2))
+                    pt = {"shape": shape, "pool": "int8" if kv8 else "fp16", "heads": h, "kv_heads": kvh, "batch": b, "context": ctx, "tokens": t}
+                    for name, v in runs.items():
+                        pt[name] = {"median_us": round(statistics.median(v), 2), "min_us": min(v), "max_us": max(v), "rounds_us": v}
+                    spread = round(pt["prefill"]["max_us"] - pt["prefill"]["min_us"], 2)
+                    pt["verify_over_prefill"] = round(pt["verify"]["median_us"] / pt["prefill"]["median_us"], 3)
+                    pt["verify_over_decode"] = round(pt["verify"]["median_us"] / pt["decode"]["median_us"], 3)
+                    pt["prefill_round_spread_us"] = spread
+                    pt["faster_than_prefill"] = bool(pt["verify"]["median_us"] < pt["prefill"]["median_us"] - spread)
+                    out["points"].append(pt)
+                    print(json.dumps(pt), file=sys.stderr, flush=True)
+                del pools
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", default="decode,prefill")
@@ -432,6 +515,8 @@ def main():
     a = ap.parse_args()
     if a.summarize:
         res = summarize_prefill(a.summarize, a.bench) if a.paged and a.points == "prefill" else summarize(a.summarize, a.bench)
+    elif a.points == "verify":
+        res = run_verify(kv8=a.kv8, block_size=a.block_size)
     elif a.paged and a.points == "prefill":
         res = run_paged_prefill([int(v) for v in a.group_sizes.split(",")], kv8=a.kv8, block_size=a.block_size)
     else:

@@ -23,6 +23,14 @@ lm_head row (t + 1) % 16 set to the embedding of t), where nearly every draft do
 and written, not assumed.  Acceptance on real text is not measured: that needs a checkpoint and a tokenizer.
 
     python tools/bench_generate.py --draft-len 0,2,4,7 [--batch 1,16] [--rounds 5] [--out profiles/spec_decode_bench.json]
+
+With --verify as well, every K > 0 is measured twice in the same rotation: with fuse_prefill() alone (the step's chunk through the paged
+prefill attention kernel, the runs above) and with fuse_verify() beside it (the chunk through the verify attention kernel; admission
+prefill keeps the prefill kernel).  A loop captures its step under its own flags in the warm-up, and the flags are set again before each
+of its runs.  Written to profiles/spec_decode_verify_bench.json: both step times with the rounds' min and max, r(K) before and after, and
+the part of the gap to K = 0 that the verify kernel closes.
+
+    python tools/bench_generate.py --draft-len 0,4 --verify [--batch 1,16] [--rounds 5] [--out profiles/spec_decode_verify_bench.json]
 """
 import argparse
 import json
@@ -104,7 +112,7 @@ def rig(lm):
         head[(t + 1) % PERIOD].copy_(emb[t] / RIG_SCALE)
 
 
-def spec_point(lm, batch, drafts, rounds, rigged, dev):
+def spec_point(lm, batch, drafts, rounds, rigged, dev, verify=False):
     import torch
 
     from bench_model import VOCAB
@@ -115,24 +123,27 @@ def spec_point(lm, batch, drafts, rounds, rigged, dev):
         prompts = [[(s + i) % PERIOD for i in range(PROMPT)] for s in range(batch)]
     else:
         prompts = [torch.randint(0, VOCAB, (PROMPT,), generator=g).tolist() for _ in range(batch)]
-    loops = {}
+    loops = {}  # key: K, or "Kv" for the loop whose step takes the verify kernel
     for k in drafts:
         max_len = -(-(PROMPT + NEW - 1 + k) // BS) * BS
-        cache = lm.new_cache(batch * (max_len // BS), BS)
-        loops[k] = (SpecDecodeLoop(lm, cache, rows=batch, max_len=max_len, draft_len=k, sync_every=SYNC_EVERY) if k else
-                    DecodeLoop(lm, cache, rows=batch, max_len=max_len, sync_every=SYNC_EVERY))
+        for key in ([k, f"{k}v"] if verify and k else [k]):
+            cache = lm.new_cache(batch * (max_len // BS), BS)
+            loops[key] = (SpecDecodeLoop(lm, cache, rows=batch, max_len=max_len, draft_len=k, sync_every=SYNC_EVERY) if k else
+                          DecodeLoop(lm, cache, rows=batch, max_len=max_len, sync_every=SYNC_EVERY))
+            loops[key].verify = isinstance(key, str)
 
     def timed(loop, n):
+        (lm.fuse_verify if loop.verify else lm.unfuse_verify)()  # the eager parts follow the flags of the run; the capture is the warm-up's
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         out = loop.generate(prompts, n)
         torch.cuda.synchronize()
         return time.perf_counter() - t0, out
 
-    stats = {}
+    stats, tokens = {}, {}
     for k, loop in loops.items():  # warm-up: code objects, workspaces, rope tables, the capture
         timed(loop, 1)
-        out = timed(loop, NEW)[1]
+        out = tokens[str(k)] = timed(loop, NEW)[1]
         assert all(len(o) == NEW for o in out), k
         steps = loop.steps if k else NEW - 1
         stats[k] = {"steps": steps, "row_steps": loop.row_steps if k else batch * (NEW - 1), "accepted": loop.accepted if k else 0}
@@ -147,7 +158,8 @@ def spec_point(lm, batch, drafts, rounds, rigged, dev):
         sec, st = statistics.median(v), stats[k]
         res["draft_len"][str(k)] = {
             "steps": st["steps"], "accepted_per_row_step": round(st["accepted"] / max(st["row_steps"], 1), 3),
-            "step_us": round(sec / st["steps"] * 1e6, 1), "tokens_per_s": round(batch * (NEW - 1) / sec, 1),
+            "step_us": round(sec / st["steps"] * 1e6, 1), "step_us_min": round(min(v) / st["steps"] * 1e6, 1),
+            "step_us_max": round(max(v) / st["steps"] * 1e6, 1), "tokens_per_s": round(batch * (NEW - 1) / sec, 1),
             "rounds_ms": [round(x * 1e3, 2) for x in v]}
     base = res["draft_len"].get("0")
     if base:
@@ -155,6 +167,15 @@ def spec_point(lm, batch, drafts, rounds, rigged, dev):
             e["r"] = round(e["step_us"] / base["step_us"], 3)
             e["break_even_accepted_per_row_step"] = round(e["r"] - 1, 3)
             e["tokens_per_s_over_draft_len_0"] = round(e["tokens_per_s"] / base["tokens_per_s"], 3)
+        for k, e in res["draft_len"].items():
+            if k.endswith("v"):  # the verify kernel against the prefill kernel at the same K, timed in the same rotation
+                before = res["draft_len"][k[:-1]]
+                gap = before["step_us"] - base["step_us"]
+                e["attention"], before["attention"] = "verify_attention_paged", "prefill_attention_paged"
+                e["step_us_saved"] = round(before["step_us"] - e["step_us"], 1)
+                e["prefill_path_round_spread_us"] = round(before["step_us_max"] - before["step_us_min"], 1)
+                e["share_of_gap_to_draft_len_0_closed"] = round(e["step_us_saved"] / gap, 3) if gap > 0 else None
+                e["tokens_equal_prefill_path"] = tokens[k] == tokens[k[:-1]]
     return res
 
 
@@ -168,14 +189,16 @@ def spec_main(args):
     lm = build(LAYERS, dev).fuse_prefill()
     batches = list(map(int, args.batch.split(",")))
     with torch.no_grad():
-        points = [spec_point(lm, b, drafts, args.rounds, False, dev) for b in batches]
+        points = [spec_point(lm, b, drafts, args.rounds, False, dev, args.verify) for b in batches]
         rig(lm)
-        points += [spec_point(lm, b, drafts, args.rounds, True, dev) for b in batches]
-    out = {"tool": "tools/bench_generate.py --draft-len " + args.draft_len, "device": torch.cuda.get_device_name(0),
+        points += [spec_point(lm, b, drafts, args.rounds, True, dev, args.verify) for b in batches]
+    lm.unfuse_verify()
+    out = {"tool": "tools/bench_generate.py --draft-len " + args.draft_len + (" --verify" if args.verify else ""),
+           "device": torch.cuda.get_device_name(0),
            "shape": "Llama-2-7B layers, per-channel W4A8, fuse_qkv(), fuse_prefill(), paged fp16 cache, block 16, greedy, ngram_max 3",
            "sync_every": SYNC_EVERY, "rounds": args.rounds,
            "not_measured": "acceptance on real text: no checkpoint or tokenizer was available; the two models bracket it", "points": points}
-    path = args.out or os.path.join(ROOT, "profiles", "spec_decode_bench.json")
+    path = args.out or os.path.join(ROOT, "profiles", "spec_decode_verify_bench.json" if args.verify else "spec_decode_bench.json")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
@@ -192,6 +215,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--baseline-only", action="store_true", help="time generate() alone (runs on a tree without DecodeLoop)")
     ap.add_argument("--draft-len", default=None, help="e.g. 0,2,4,7: measure the speculative loop instead (profiles/spec_decode_bench.json)")
+    ap.add_argument("--verify", action="store_true", help="with --draft-len: every K > 0 also with fuse_verify() "
+                    "(profiles/spec_decode_verify_bench.json)")
     ap.add_argument("--out", default=None, help="default profiles/decode_loop_bench.json, or profiles/spec_decode_bench.json with --draft-len")
     args = ap.parse_args()
     import torch
