@@ -29,6 +29,7 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     spec_advance(logits, ..., u, tick, ids, pos, slots, start, block_table, remaining, eos, hist, hist_len, n_out, n_acc, block_size, ngram_max)
                                                                                     # draft_len + 1 draws per row, accept rule, n-gram drafter
     SpecDecodeLoop(lm, cache, rows, max_len, draft_len=4), ngram_draft              # speculative decode loop, 1 ... draft_len + 1 tokens per replay
+    penalize_logits(logits, ids, pos, seen, n_prompt, repetition, presence, frequency)  # penalties from each row's history, in place, before a sampler
     token_logprobs(logits, targets, return_argmax=True)                             # a target's log-probability and the argmax per logit row, one launch
     QuantLlamaForCausalLM.score / loglikelihood / perplexity, pack_steps            # scoring text over the paged cache; qqq_amd/score.py
 """
@@ -41,6 +42,7 @@ from .ops import (  # noqa: F401
     expand_int8,
     marlin_qqq_gemm,
     mul,
+    penalize_logits,
     prefill_attention_paged,
     prefill_attention_paged_kv8,
     qqq_gemm,
@@ -75,4 +77,4 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "decode_attention_paged", "rope_qkv_paged_kv8", "decode_attention_paged_kv8", "prefill_attention_paged",
            "prefill_attention_paged_kv8", "PagedKVCache", "PagedStep", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer",
            "sample_tokens", "QuantLlamaModel", "QuantLlamaForCausalLM", "sample_advance", "DecodeLoop", "token_logprobs", "pack_steps",
-           "spec_advance", "SpecDecodeLoop", "ngram_draft", "verify_attention_paged", "verify_attention_paged_kv8"]
+           "spec_advance", "SpecDecodeLoop", "ngram_draft", "verify_attention_paged", "verify_attention_paged_kv8", "penalize_logits"]

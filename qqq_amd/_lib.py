@@ -121,6 +121,11 @@ def lib():
     L.qqq_spec_advance.restype = ci
     L.qqq_spec_advance_workspace_bytes.argtypes = [ci, ci]
     L.qqq_spec_advance_workspace_bytes.restype = ctypes.c_size_t
+    # include/qqq_amd_penalty.h
+    L.qqq_penalize_logits.argtypes = [vp, ci, vp, vp, ci, vp, ci, vp, vp, vp, vp, vp, ctypes.c_size_t, ci, ci, ci, vp]
+    L.qqq_penalize_logits.restype = ci
+    L.qqq_penalize_logits_workspace_bytes.argtypes = [ci, ci]
+    L.qqq_penalize_logits_workspace_bytes.restype = ctypes.c_size_t
     L.qqq_amd_abi_version.restype = ci
     L.qqq_amd_last_error.restype = ctypes.c_char_p
     if L.qqq_amd_abi_version() != ABI_VERSION:

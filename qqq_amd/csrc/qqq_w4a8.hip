@@ -36,6 +36,7 @@
 //   qqq_sample.hip.h   the fused token sampler: temperature, top-k, top-p and the draw over a batch of fp16 logit rows, one launch
 //   qqq_score.hip.h    the fused scoring kernel: a target token's log-probability and the argmax per fp16 logit row, one launch (the sampler's weights)
 //   qqq_step.hip.h     the decode loop's step: that sampler with an epilogue that advances each row's decode state on the device
+//   qqq_penalty.hip.h  the repetition / presence / frequency penalty: fp16 logit rows rewritten in place from each row's token history, one launch
 //   qqq_spec.hip.h     the speculative decode loop's step: draft_len + 1 draws per row by that sampler, the accept rule and the n-gram drafter
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
@@ -83,6 +84,8 @@
 #include "../../include/qqq_amd_spec.h"
 #include "qqq_verify.hip.h"
 #include "../../include/qqq_amd_verify.h"
+#include "qqq_penalty.hip.h"
+#include "../../include/qqq_amd_penalty.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1369,6 +1372,55 @@ extern "C" int qqq_spec_advance(const void* logits, int ld, const void* temperat
   hipLaunchKernelGGL(qqq_spec_advance_kernel, dim3(rows), dim3(SPEC_NT), 0, static_cast<hipStream_t>(stream), st);
   e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_spec_advance_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- the repetition / presence / frequency penalty (include/qqq_amd_penalty.h; kernel in qqq_penalty.hip.h): one launch, one workgroup per
+// row, in front of a sampler; the workspace is zero on entry and left zero.
+extern "C" size_t qqq_penalize_logits_workspace_bytes(int rows, int vocab) {
+  if (rows < 1 || rows > 65535 || vocab < 1 || vocab > SMP_MAX_VOCAB) return 0;
+  return (size_t)rows * (size_t)vocab * sizeof(unsigned);
+}
+
+extern "C" int qqq_penalize_logits(void* logits, int ld, const void* ids, const void* pos, int group, void* seen, int seen_stride,
+                                   const void* n_prompt, const void* repetition, const void* presence, const void* frequency,
+                                   void* workspace, size_t workspace_bytes, int rows, int vocab, int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 0 || rows > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_penalize_logits: rows=%d outside [0, 65535]", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  if (group < 1 || group > PEN_MAX_GROUP || (long long)rows * group > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_penalize_logits: group=%d outside [1, %d], or rows=%d times group exceeds 65535 logits rows", group,
+             PEN_MAX_GROUP, rows);
+    return QQQ_ERR_ARG;
+  }
+  if (vocab < 1 || vocab > SMP_MAX_VOCAB || ld < vocab || seen_stride < 1 || seen_stride > PEN_MAX_SEEN) {
+    snprintf(g_err, sizeof(g_err), "qqq_penalize_logits: bad shape vocab=%d ld=%d seen_stride=%d (need 1 <= vocab <= %d, ld >= vocab, "
+             "1 <= seen_stride < 2^30)", vocab, ld, seen_stride, SMP_MAX_VOCAB);
+    return QQQ_ERR_ARG;
+  }
+  if (!logits || !ids || !pos || !seen || !n_prompt || !repetition || !presence || !frequency || !workspace || misaligned(logits, 2) ||
+      misaligned(ids, 8) || misaligned(pos, 8) || misaligned(seen, 4) || misaligned(n_prompt, 4) || misaligned(repetition, 4) ||
+      misaligned(presence, 4) || misaligned(frequency, 4) || misaligned(workspace, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_penalize_logits: bad argument (every pointer must be non-NULL; logits 2-byte, ids / pos 8-byte, "
+             "everything else 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  const size_t need = qqq_penalize_logits_workspace_bytes(rows, vocab);
+  if (workspace_bytes < need) {
+    snprintf(g_err, sizeof(g_err), "qqq_penalize_logits: workspace of %zu bytes, %zu needed (qqq_penalize_logits_workspace_bytes)",
+             workspace_bytes, need);
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_penalize_logits_kernel, dim3(rows), dim3(PEN_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<unsigned short*>(logits), ld, static_cast<const long long*>(ids), static_cast<const long long*>(pos), group,
+                     static_cast<int*>(seen), seen_stride, static_cast<const int*>(n_prompt), static_cast<const float*>(repetition),
+                     static_cast<const float*>(presence), static_cast<const float*>(frequency), static_cast<unsigned*>(workspace), vocab);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_penalize_logits_kernel launch");
   return QQQ_OK;
 }
 

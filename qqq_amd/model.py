@@ -172,7 +172,8 @@ class QuantLlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, cache: Optional[PagedKVCache] = None,
-                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False, draft_len: int = 0) -> List[List[int]]:
+                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False, draft_len: int = 0, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> List[List[int]]:
         """Generate up to `max_new_tokens` tokens for every prompt (token lists of any lengths) -> the generated ids per prompt, the
         eos_token_id that ends a sequence included.
 
@@ -192,10 +193,21 @@ class QuantLlamaForCausalLM(nn.Module):
         draft_len=K > 0 (with device_loop=True, on a model with fuse_prefill() or fuse_verify()) makes that loop a SpecDecodeLoop: K tokens drafted by
         n-gram lookup ride behind every row's last token and a replay emits 1 ... K + 1 tokens per row.  The output distribution is
         unchanged; the tokens under a seed differ (K + 1 variates per row and step), greedy tokens are the same up to near-ties of the
-        logits.  Every sequence needs K more keys of the pool."""
+        logits.  Every sequence needs K more keys of the pool.
+
+        repetition_penalty (transformers' rule: a seen token's logit l becomes l / r if l > 0, else l * r; over prompt and output),
+        presence_penalty and frequency_penalty (vLLM's: l - frequency * c - presence for a token emitted c > 0 times; over the output
+        alone) act on every pass's logits before temperature, top-k and top-p, through ops.penalize_logits on all three paths (the device
+        loops are then built with penalties=True).  1, 0 and 0 mean none, and then nothing of it runs."""
         draft_len = int(draft_len)
         if draft_len < 0 or (draft_len > 0 and not device_loop):
             raise ValueError(f"generate: draft_len={draft_len} must be 0, or positive together with device_loop=True")
+        penalty = (float(repetition_penalty), float(presence_penalty), float(frequency_penalty))
+        if not (penalty[0] > 0.0 and penalty[0] != float("inf")):
+            raise ValueError(f"generate: repetition_penalty={penalty[0]} must be finite and > 0")
+        penalised = penalty != (1.0, 0.0, 0.0)
+        loop_kw = dict(penalties=True) if penalised else {}  # without penalties the loops are built and called as ever
+        gen_kw = dict(zip(("repetition_penalty", "presence_penalty", "frequency_penalty"), penalty)) if penalised else {}
         prompts = [list(p) for p in prompts]
         if any(not p for p in prompts):
             raise ValueError("generate: every prompt needs at least one token")
@@ -209,20 +221,30 @@ class QuantLlamaForCausalLM(nn.Module):
         if draft_len:
             from .serve import SpecDecodeLoop
 
-            loop = SpecDecodeLoop(self, cache, rows=min(len(prompts), 64), max_len=max(need) * cache.block_size, draft_len=draft_len)
-            return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id)
+            loop = SpecDecodeLoop(self, cache, rows=min(len(prompts), 64), max_len=max(need) * cache.block_size, draft_len=draft_len,
+                                  **loop_kw)
+            return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, **gen_kw)
         if device_loop:
             from .serve import DecodeLoop
 
-            loop = DecodeLoop(self, cache, rows=min(len(prompts), 64), max_len=max(need) * cache.block_size)
-            return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id)
+            loop = DecodeLoop(self, cache, rows=min(len(prompts), 64), max_len=max(need) * cache.block_size, **loop_kw)
+            return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, **gen_kw)
         tag = object()  # sequence ids no other user of the cache can hold
         sid = lambda i: (tag, i)  # noqa: E731
         waiting, running = deque(range(len(prompts))), []
         cur = None  # int64 [len(running)] on the device: the running sequences' last tokens
 
-        def sample(ids, step):
+        workspace = torch.zeros(len(prompts) * self.lm_head.weight.shape[0], dtype=torch.int32, device=dev) if penalised else None
+
+        def sample(ids, step, seqs):
             logits = self(ids, cache, step)
+            if penalised:  # the history is host-side like the rest of the bookkeeping: the prompt and what was emitted, padded per pass
+                hist = [prompts[i] + out[i] for i in seqs]
+                width = max(len(h) for h in hist)
+                seen = torch.tensor([h + [-1] * (width - len(h)) for h in hist], dtype=torch.int32).to(dev)
+                ops.penalize_logits(logits, torch.tensor([h[-1] for h in hist], dtype=torch.int64, device=dev),
+                                    torch.tensor([len(h) - 1 for h in hist], dtype=torch.int64, device=dev), seen,
+                                    torch.tensor([len(prompts[i]) for i in seqs], dtype=torch.int32, device=dev), *penalty, workspace)
             u = torch.rand(logits.shape[0], generator=generator, device=logits.device)
             return ops.sample_tokens(logits, temperature, top_k, top_p, u)
 
@@ -243,7 +265,7 @@ class QuantLlamaForCausalLM(nn.Module):
 
         while waiting or running:
             if running:
-                toks = sample(cur, cache.step([sid(i) for i in running], [1] * len(running)))
+                toks = sample(cur, cache.step([sid(i) for i in running], [1] * len(running)), running)
                 running, rows = settle(running, toks)
                 cur = take(toks, rows)
             new = []
@@ -259,7 +281,7 @@ class QuantLlamaForCausalLM(nn.Module):
                                        f"{need[waiting[0]]} (prompt and budget)")
                 continue
             ids = torch.tensor([t for i in new for t in prompts[i]], dtype=torch.int64, device=dev)
-            toks = sample(ids, cache.step([sid(i) for i in new], [len(prompts[i]) for i in new]))
+            toks = sample(ids, cache.step([sid(i) for i in new], [len(prompts[i]) for i in new]), new)
             alive, rows = settle(new, toks)
             first = take(toks, rows)
             cur = first if not running else torch.cat([cur, first])

@@ -1576,3 +1576,108 @@ def spec_advance(logits: torch.Tensor, temperature, top_k, top_p, u: torch.Tenso
     if _compiling(*args):
         return _spec_advance_op(*args, int(block_size), int(ngram_max))
     return _spec_advance_impl(*args, int(block_size), int(ngram_max))
+
+
+# ---- the repetition / presence / frequency penalty (include/qqq_amd_penalty.h): the logits rewritten in place from each row's history, in
+# front of any of the three samplers above
+
+_PENALTY_ROW_STATE = (("n_prompt", torch.int32), ("repetition_penalty", torch.float32), ("presence_penalty", torch.float32),
+                      ("frequency_penalty", torch.float32))
+
+
+def _penalize_logits_check(logits, ids, pos, seen, n_prompt, repetition_penalty, presence_penalty, frequency_penalty, workspace):
+    # dtypes, shapes and strides: needs no device, shared by the launch and the fake implementation -> (rows, group, vocab)
+    op = "penalize_logits"
+    if logits.dtype != torch.float16 or logits.dim() != 2:
+        raise RuntimeError(f"{op}: logits must be fp16 [rows * group, vocab]")
+    m, vocab = logits.shape
+    if ids.dtype != torch.int64 or ids.dim() not in (1, 2) or (ids.dim() == 2 and not 1 <= ids.shape[1] <= 16):
+        raise RuntimeError(f"{op}: ids must be int64 [rows] or [rows, group] with 1 <= group <= 16, not {_dt(ids.dtype)} {tuple(ids.shape)}")
+    rows, group = ids.shape[0], (ids.shape[1] if ids.dim() == 2 else 1)
+    if m != rows * group:
+        raise RuntimeError(f"{op}: logits hold {m} rows, ids {tuple(ids.shape)} asks for {rows * group}")
+    if pos.dtype != torch.int64 or pos.shape != ids.shape:
+        raise RuntimeError(f"{op}: pos must be int64 {tuple(ids.shape)} like ids, not {_dt(pos.dtype)} {tuple(pos.shape)}")
+    if seen.dtype != torch.int32 or seen.dim() != 2 or seen.shape[0] != rows or seen.shape[1] < 1:
+        raise RuntimeError(f"{op}: seen must be int32 [{rows}, seen_stride >= 1], not {_dt(seen.dtype)} {tuple(seen.shape)}")
+    state = dict(n_prompt=n_prompt, repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                 frequency_penalty=frequency_penalty)
+    for name, dtype in _PENALTY_ROW_STATE:
+        t = state[name]
+        if t.dtype != dtype or t.dim() != 1 or t.shape[0] != rows:
+            raise RuntimeError(f"{op}: {name} must be {_dt(dtype)} [{rows}], not {_dt(t.dtype)} {tuple(t.shape)}")
+    if workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.shape[0] < rows * vocab:
+        raise RuntimeError(f"{op}: workspace must be int32 [>= rows * vocab = {rows * vocab}], zero on entry, not {_dt(workspace.dtype)} "
+                           f"{tuple(workspace.shape)}")
+    if vocab < 1 or vocab > 262144 or m > 65535 or seen.shape[1] >= 1 << 30:
+        raise RuntimeError(f"{op}: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows * group <= 65535, or seen_stride "
+                           f"{seen.shape[1]} >= 2^30")
+    if m and (logits.stride(1) != 1 or logits.stride(0) < vocab):
+        raise RuntimeError(f"{op}: logits must have unit column stride and a row stride >= vocab (they are rewritten in place, never "
+                           f"copied), not strides {tuple(logits.stride())}")
+    return rows, group, vocab
+
+
+def _penalize_logits_impl(logits, ids, pos, seen, n_prompt, repetition_penalty, presence_penalty, frequency_penalty, workspace):
+    ts = (logits, ids, pos, seen, n_prompt, repetition_penalty, presence_penalty, frequency_penalty, workspace)
+    _same_gpu("penalize_logits", ts)
+    rows, group, vocab = _penalize_logits_check(*ts)
+    if rows == 0:
+        return
+    _in_place_check("penalize_logits", (("ids", ids), ("pos", pos), ("seen", seen), ("n_prompt", n_prompt),
+                                        ("repetition_penalty", repetition_penalty), ("presence_penalty", presence_penalty),
+                                        ("frequency_penalty", frequency_penalty), ("workspace", workspace)))
+    err = _lib.lib().qqq_penalize_logits(_ptr(logits), logits.stride(0), _ptr(ids), _ptr(pos), group, _ptr(seen), seen.shape[1],
+                                         _ptr(n_prompt), _ptr(repetition_penalty), _ptr(presence_penalty), _ptr(frequency_penalty),
+                                         _ptr(workspace), workspace.numel() * 4, rows, vocab, logits.device.index or 0, _stream_for(logits))
+    _raise_lib("penalize_logits", err)
+
+
+@torch.library.custom_op("qqq_amd::penalize_logits", mutates_args=("logits", "seen", "workspace"))
+def _penalize_logits_op(logits: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, seen: torch.Tensor, n_prompt: torch.Tensor,
+                        repetition_penalty: torch.Tensor, presence_penalty: torch.Tensor, frequency_penalty: torch.Tensor,
+                        workspace: torch.Tensor) -> None:
+    _penalize_logits_impl(logits, ids, pos, seen, n_prompt, repetition_penalty, presence_penalty, frequency_penalty, workspace)
+
+
+@_penalize_logits_op.register_fake
+def _(logits, ids, pos, seen, n_prompt, repetition_penalty, presence_penalty, frequency_penalty, workspace):
+    _penalize_logits_check(logits, ids, pos, seen, n_prompt, repetition_penalty, presence_penalty, frequency_penalty, workspace)
+
+
+def penalize_logits(logits: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, seen: torch.Tensor, n_prompt: torch.Tensor,
+                    repetition_penalty, presence_penalty, frequency_penalty, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Repetition, presence and frequency penalties on fp16 logits [rows * G, vocab], in place and in one launch, in front of
+    sample_tokens, sample_advance or spec_advance -> `logits`.  logits, seen and the workspace are updated in place.
+
+    ids, pos     int64 [rows] (G = 1) or [rows, G <= 16]: a loop's state arrays -- the tokens a row feeds through the forward (its last
+                 token, then its drafts) and their positions, of which pos[r, 0] alone is read; < 0 (an idle row) or >= seen_stride: the
+                 row is left alone altogether
+    seen         int32 [rows, seen_stride]: the sequence so far.  The op records ids[r, 0] at seen[r, pos[r, 0]] itself
+    n_prompt     int32 [rows]: the prompt's length; presence and frequency count the occurrences at indices >= n_prompt alone
+    repetition_penalty, presence_penalty, frequency_penalty   f32 [rows] or a float: 1, 0 and 0 leave a row's logits alone
+    workspace    int32 [>= rows * vocab], zero on entry and left zero (allocate once, reuse); None allocates a zeroed one
+    Logits row r * G + j is conditioned on seen[r, :pos[r, 0] + 1] and the drafts ids[r, 1 ... j]: every token t in it takes
+    l = l > 0 ? l / repetition : l * repetition (transformers' rule), then, with c > 0 occurrences among the outputs,
+    l - frequency * c - presence (vLLM's); each step one f32 operation, the result rounded to fp16.  The exact semantics of a row are
+    stated in include/qqq_amd_penalty.h.  Nothing is read on the host and the launch size depends on the shapes alone, so a step with this
+    call in it replays from a captured graph.  The logits are never copied: unit column stride and a row stride >= vocab, or it raises."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(ids, torch.Tensor) or logits.dim() != 2 or ids.dim() not in (1, 2):
+        raise RuntimeError("penalize_logits: logits must be an fp16 [rows * group, vocab] tensor and ids an int64 [rows] or [rows, group] "
+                           "tensor")
+    if not isinstance(repetition_penalty, torch.Tensor):
+        repetition_penalty = float(repetition_penalty)
+        if not (repetition_penalty > 0.0 and repetition_penalty != float("inf")):
+            raise ValueError(f"penalize_logits: repetition_penalty={repetition_penalty} must be finite and > 0")
+    rows, dev = ids.shape[0], logits.device
+    repetition_penalty = _sample_param("repetition_penalty", repetition_penalty, rows, torch.float32, dev, "penalize_logits")
+    presence_penalty = _sample_param("presence_penalty", presence_penalty, rows, torch.float32, dev, "penalize_logits")
+    frequency_penalty = _sample_param("frequency_penalty", frequency_penalty, rows, torch.float32, dev, "penalize_logits")
+    if workspace is None:
+        workspace = torch.zeros((rows * logits.shape[1],), dtype=torch.int32, device=dev)
+    args = (logits, ids, pos, seen, n_prompt, repetition_penalty, presence_penalty, frequency_penalty, workspace)
+    if _compiling(*args):
+        _penalize_logits_op(*args)
+    else:
+        _penalize_logits_impl(*args)
+    return logits

@@ -13,7 +13,7 @@ ops.sample_tokens), writes the admitted rows' state with indexed copies, replays
 steps.  A row that is idle (pos -1, slot -1, remaining 0) rides along in every step and is inert: see include/qqq_amd_step.h.
 
 generate() -- admission, prefill, the run / sync / retire loop and the cleanup -- exists once, on DecodeLoop.  SpecDecodeLoop inherits it
-and overrides _decode_step, _run, _start_call, _budget_words, _row_state and _collect, and the attributes _tokens, _synced and _idle.
+and overrides _decode_step, _run, _start_call, _budget_words, _row_state, _penalty_state and _collect, and the attributes _tokens, _synced and _idle.
 """
 from __future__ import annotations
 
@@ -54,6 +54,10 @@ class DecodeLoop:
     sync_every  decode steps between two host syncs;  u_stride  uniform variates per row and refill (>= sync_every)
     graph       True: the step is captured once into a torch.cuda.CUDAGraph (on a side stream; single-stream, straight-line) and replayed;
                 False: the same calls run eagerly.  Both give the same tokens.
+    penalties   True: the loop owns what ops.penalize_logits takes -- `seen` (int32 [rows, max_len], the rows' prompts and emitted tokens),
+                n_prompt, repetition, presence, frequency and the op's workspace -- and its step runs that op between the forward and the
+                sampler, inside the captured graph; generate() then takes repetition_penalty, presence_penalty and frequency_penalty.
+                A row whose three values are 1, 0 and 0 rides through it with its logits untouched.  False: none of that exists.
     `captures` counts the captures: 1 for the life of the loop with graph=True.  The graph holds addresses: a model that is changed after
     the first generate() (fuse_*(), load_state_dict, .to()) needs a new loop."""
 
@@ -62,13 +66,17 @@ class DecodeLoop:
     _tokens = "out"                  # the array a finished row's tokens are read from
     _synced = ("n_out", "remaining")  # what a sync transfers
     _idle = (("remaining", 0), ("pos", -1), ("slots", -1), ("ids", 0))  # what the cleanup resets
+    penalties = False                # True: the step runs ops.penalize_logits in front of the sampler (_allocate_penalties)
 
-    def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, sync_every: int = 8, u_stride: int = 64, graph: bool = True):
+    def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, sync_every: int = 8, u_stride: int = 64, graph: bool = True,
+                 penalties: bool = False):
         rows, max_len, sync_every, u_stride = int(rows), int(max_len), int(sync_every), int(u_stride)
         short = u_stride < sync_every and f"u_stride={u_stride} must cover the sync_every={sync_every} steps between two refills"
         dev = _check_loop("DecodeLoop", lm, cache, rows, max_len, sync_every, graph, short)
         self._allocate(lm, cache, rows, max_len, sync_every, u_stride, graph, dev)
         self.out = torch.zeros((rows, max_len), dtype=torch.int64, device=dev)
+        if penalties:  # this loop keeps no history of its own: the penalty op records a row's input token at its position
+            self._allocate_penalties(torch.zeros((rows, max_len), dtype=torch.int32, device=dev))
         # the one step of every decode pass: its device tensors ARE the state arrays (a row's position is its last position)
         self.step = PagedStep(seq_ids=[None] * rows, counts=[1] * rows, starts=[0] * rows, max_len=max_len, decode=True, pos=self.pos,
                               slots=self.slots, block_table=self.block_table, last_pos=self.pos,
@@ -97,10 +105,28 @@ class DecodeLoop:
         self._graph = None
         self._used = u_stride  # variates of u consumed since its last refill: none are left
 
+    def _allocate_penalties(self, seen: torch.Tensor) -> None:
+        """What ops.penalize_logits takes beside ids and pos, for a loop built with penalties=True: `seen` is the rows' history (of
+        prompt and emitted tokens, int32 [rows, max_len]); every row starts neutral (1, 0, 0)."""
+        i32 = dict(dtype=torch.int32, device=self.device)
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.penalties, self.seen = True, seen
+        self.n_prompt = torch.zeros(self.rows, **i32)
+        self.repetition = torch.ones(self.rows, **f32)
+        self.presence = torch.zeros(self.rows, **f32)
+        self.frequency = torch.zeros(self.rows, **f32)
+        self.penalty_workspace = torch.zeros(self.rows * self.lm.lm_head.weight.shape[0], **i32)  # zero between any two calls
+
+    def _penalize(self, logits: torch.Tensor) -> None:
+        ops.penalize_logits(logits, self.ids, self.pos, self.seen, self.n_prompt, self.repetition, self.presence, self.frequency,
+                            self.penalty_workspace)
+
     # ---- one decode step
 
     def _decode_step(self) -> None:
         logits = self.lm(self.ids, self.cache, self.step)
+        if self.penalties:
+            self._penalize(logits)
         ops.sample_advance(logits, self.temperature, self.top_k, self.top_p, self.u, self.tick, self.ids, self.pos, self.slots,
                            self.block_table, self.remaining, self.eos, self.out, self.n_out, self.cache.block_size)
 
@@ -147,7 +173,12 @@ class DecodeLoop:
         """What an admitted row writes, per state array: `prompt` is in the cache, `first` the token the prefill drew."""
         p, bs = len(prompt), self.cache.block_size
         table = blocks + [0] * (self.block_table.shape[1] - len(blocks))
-        return dict(ids=first, pos=p, slots=blocks[p // bs] * bs + p % bs, block_table=table)
+        penalty = self._penalty_state(prompt) if self.penalties else {}
+        return dict(ids=first, pos=p, slots=blocks[p // bs] * bs + p % bs, block_table=table, **penalty)
+
+    def _penalty_state(self, prompt: List[int]) -> dict:
+        """What an admitted row of a loop with penalties writes besides: the prompt is what the row has seen (the op records the rest)."""
+        return dict(n_prompt=len(prompt), seen=prompt + [0] * (self.seen.shape[1] - len(prompt)))
 
     def _collect(self, row: List[int], n_prompt: int, seq, n: dict) -> List[int]:
         """The tokens a finished row emitted, from its line `row` of the `_tokens` array and its synced counts `n`."""
@@ -158,7 +189,8 @@ class DecodeLoop:
 
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-                 generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None) -> List[List[int]]:
+                 generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, repetition_penalty: float = 1.0,
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> List[List[int]]:
         """QuantLlamaForCausalLM.generate's contract -- up to `max_new_tokens` ids per prompt, the eos that ends a sequence included --
         served by this loop's rows: waiting prompts are admitted into idle rows, in order, whenever the pool's free blocks cover a
         prompt's whole budget (taken at once with PagedKVCache.reserve), prefilled eagerly in one packed step with their first token from
@@ -170,8 +202,20 @@ class DecodeLoop:
         SpecDecodeLoop: the budget is len(prompt) + max_new_tokens - 1 + draft_len keys per sequence (reserved at once; the same sum must
         not exceed max_len).  The host writes an admitted row's history (the prompt and its first token) and first drafts (ngram_draft);
         everything after that happens on the device.  u is refilled whenever it is used up; a step uses draft_len + 1 variates per row,
-        so sampled tokens differ from DecodeLoop's under the same seed."""
+        so sampled tokens differ from DecodeLoop's under the same seed.
+
+        repetition_penalty, presence_penalty, frequency_penalty (1, 0, 0: none) need a loop built with penalties=True, whose step runs
+        ops.penalize_logits between the forward and the sampler: every draw is made from logits penalised over the row's prompt and
+        emitted tokens (include/qqq_amd_penalty.h) -- the first one from the prefill's logits penalised over the prompt, where every
+        index is a prompt index and the repetition rule alone acts; a draft's logits row over the drafts in front of it too."""
         name = f"{self._name}.generate"
+        penalty = (float(repetition_penalty), float(presence_penalty), float(frequency_penalty))
+        if not (penalty[0] > 0.0 and penalty[0] != float("inf")):
+            raise ValueError(f"{name}: repetition_penalty={penalty[0]} must be finite and > 0")
+        penalised = penalty != (1.0, 0.0, 0.0)
+        if penalised and not self.penalties:
+            raise ValueError(f"{name}: repetition_penalty={penalty[0]}, presence_penalty={penalty[1]} and frequency_penalty={penalty[2]} "
+                             f"need a loop built with penalties=True")
         prompts = [list(p) for p in prompts]
         if any(not p for p in prompts):
             raise ValueError(f"{name}: every prompt needs at least one token")
@@ -195,6 +239,8 @@ class DecodeLoop:
         owner: List[Optional[int]] = [None] * self.rows  # the prompt each row serves
         budget = [0] * self.rows                         # an upper bound of the row's `remaining`, and so of the steps it still takes
         per_row = dict(remaining=max_new_tokens - 1, eos=eos, n_out=0, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p))
+        if self.penalties:
+            per_row.update(repetition=penalty[0], presence=penalty[1], frequency=penalty[2])
 
         def admit():
             new = []
@@ -217,6 +263,12 @@ class DecodeLoop:
             seqs = [sid(i) for _, i in new]
             ids = torch.tensor([t for _, i in new for t in prompts[i]], dtype=torch.int64, device=dev)
             logits = self.lm(ids, cache, cache.step(seqs, [len(prompts[i]) for _, i in new]))
+            if penalised:  # over the prompt: its last token sits at index len - 1 and every index is a prompt index
+                lens = [len(prompts[i]) for _, i in new]
+                seen = torch.tensor([prompts[i] + [-1] * (max(lens) - len(prompts[i])) for _, i in new], dtype=torch.int32).to(dev)
+                at_last = torch.tensor([n - 1 for n in lens], dtype=torch.int64, device=dev)
+                ops.penalize_logits(logits, torch.tensor([prompts[i][-1] for _, i in new], dtype=torch.int64, device=dev), at_last, seen,
+                                    torch.tensor(lens, dtype=torch.int32, device=dev), *penalty, self.penalty_workspace)
             u = torch.rand(len(new), generator=generator, device=dev)
             first = ops.sample_tokens(logits, temperature, top_k, top_p, u).tolist()
             rows, state = [], {}
@@ -313,6 +365,8 @@ class SpecDecodeLoop(DecodeLoop):
     sequence needs
     len(prompt) + max_new_tokens - 1 + draft_len keys of the pool and of max_len: the drafts behind its last token are written too.
     ngram_max   the longest n-gram the drafter looks up (1 ... 4);  u_stride  default sync_every * G, a multiple of G
+    penalties   as in DecodeLoop, with `seen` being `hist` itself: logits row j of a row is penalised over its history and the drafts
+                1 ... j in front of it, so an emitted token is still a plain sampler draw from (penalised) logits of the true prefix
     After a generate(): `accepted` drafts were accepted in `row_steps` steps of single rows, over `steps` steps of the loop; a row-step
     emits 1 + its accepted drafts tokens."""
 
@@ -322,7 +376,7 @@ class SpecDecodeLoop(DecodeLoop):
     _idle = DecodeLoop._idle + (("start", -1),)
 
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, draft_len: int = 4, ngram_max: int = 3, sync_every: int = 8,
-                 u_stride: Optional[int] = None, graph: bool = True):
+                 u_stride: Optional[int] = None, graph: bool = True, penalties: bool = False):
         rows, max_len, sync_every, draft_len, ngram_max = int(rows), int(max_len), int(sync_every), int(draft_len), int(ngram_max)
         if draft_len < 1 or draft_len > 15 or ngram_max < 1 or ngram_max > 4:
             raise ValueError(f"SpecDecodeLoop: draft_len={draft_len} must be in [1, 15] and ngram_max={ngram_max} in [1, 4]")
@@ -349,6 +403,8 @@ class SpecDecodeLoop(DecodeLoop):
         self.hist = torch.zeros((rows, max_len), **i32)
         self.hist_len = torch.zeros(rows, **i32)
         self.n_acc = torch.zeros(rows, **i32)
+        if penalties:  # the history the drafter reads is what the rows have seen; the op's write into it is the identity
+            self._allocate_penalties(self.hist)
         # the one step of every pass: a chunk of G tokens per row whose device tensors ARE the state arrays
         self.step = PagedStep(seq_ids=[None] * rows, counts=[group] * rows, starts=[0] * rows, max_len=max_len, decode=False,
                               pos=self.pos.view(-1), slots=self.slots.view(-1), block_table=self.block_table, last_pos=self.start,
@@ -356,6 +412,8 @@ class SpecDecodeLoop(DecodeLoop):
 
     def _decode_step(self) -> None:
         logits = self.lm(self.ids.view(-1), self.cache, self.step, all_rows=True)
+        if self.penalties:
+            self._penalize(logits)
         ops.spec_advance(logits, self.temperature, self.top_k, self.top_p, self.u, self.tick, self.ids, self.pos, self.slots, self.start,
                          self.block_table, self.remaining, self.eos, self.hist, self.hist_len, self.n_out, self.n_acc,
                          self.cache.block_size, self.ngram_max)
@@ -377,6 +435,9 @@ class SpecDecodeLoop(DecodeLoop):
         return dict(super()._row_state(prompt, first, blocks), ids=[first] + ngram_draft(h, self.draft_len, self.ngram_max), pos=list(chunk),
                     slots=[blocks[q // bs] * bs + q % bs for q in chunk], start=p, n_acc=0, hist=h + [0] * (self.hist.shape[1] - len(h)),
                     hist_len=len(h))
+
+    def _penalty_state(self, prompt: List[int]) -> dict:
+        return dict(n_prompt=len(prompt))  # `seen` is hist
 
     def _collect(self, row: List[int], n_prompt: int, seq, n: dict) -> List[int]:
         self.accepted += n["n_acc"]

@@ -31,6 +31,15 @@ of its runs.  Written to profiles/spec_decode_verify_bench.json: both step times
 the part of the gap to K = 0 that the verify kernel closes.
 
     python tools/bench_generate.py --draft-len 0,4 --verify [--batch 1,16] [--rounds 5] [--out profiles/spec_decode_verify_bench.json]
+
+With --penalties the tool times the replayed step with and without ops.penalize_logits in it, in one rotation: per batch and draft length
+K (default 0,4; 0 is DecodeLoop) a loop built with penalties=True serving generate(repetition_penalty=1.3, presence_penalty=0.5,
+frequency_penalty=0.25) beside a loop built without, by the protocol above.  Written to profiles/penalty_loop_bench.json: both step times
+with the rounds' min and max, their difference, and whether it exceeds the plain step's own round-to-round spread.  A row's history is
+the prompt and what it emitted, 128 ... 255 tokens here; the op's time at longer histories is in profiles/penalty_bench.json
+(tools/bench_sample.py --penalties).
+
+    python tools/bench_generate.py --penalties [--draft-len 0,4] [--batch 1,16] [--rounds 5] [--out profiles/penalty_loop_bench.json]
 """
 import argparse
 import json
@@ -209,6 +218,81 @@ def spec_main(args):
             for k, e in p["draft_len"].items()))
 
 
+PENALTIES = dict(repetition_penalty=1.3, presence_penalty=0.5, frequency_penalty=0.25)
+
+
+def penalty_point(lm, batch, drafts, rounds, dev):
+    import torch
+
+    from bench_model import VOCAB
+    from qqq_amd import DecodeLoop, SpecDecodeLoop
+
+    g = torch.Generator().manual_seed(batch)
+    prompts = [torch.randint(0, VOCAB, (PROMPT,), generator=g).tolist() for _ in range(batch)]
+    loops = {}  # key: (K, with the op)
+    for k in drafts:
+        max_len = -(-(PROMPT + NEW - 1 + k) // BS) * BS
+        for on in (False, True):
+            cache = lm.new_cache(batch * (max_len // BS), BS)
+            kw = dict(rows=batch, max_len=max_len, sync_every=SYNC_EVERY, **(dict(penalties=True) if on else {}))
+            loops[(k, on)] = SpecDecodeLoop(lm, cache, draft_len=k, **kw) if k else DecodeLoop(lm, cache, **kw)
+
+    def timed(key, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = loops[key].generate(prompts, n, **(PENALTIES if key[1] else {}))
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    steps = {}
+    for key, loop in loops.items():  # warm-up: code objects, workspaces, rope tables, the capture
+        timed(key, 1)
+        assert all(len(o) == NEW for o in timed(key, NEW)[1]), key
+        steps[key] = loop.steps if key[0] else NEW - 1
+    values = {key: [] for key in loops}
+    for _ in range(rounds):
+        for key in loops:
+            short, full = timed(key, 1)[0], timed(key, NEW)[0]
+            values[key].append((full - short) / steps[key] * 1e6)
+    res = {"batch": batch, "prompt_tokens": PROMPT, "new_tokens": NEW, "layers": LAYERS, "draft_len": {}}
+    for k in drafts:
+        e = {}
+        for on, name in ((False, "plain"), (True, "penalised")):
+            v = values[(k, on)]
+            e[name] = {"steps": steps[(k, on)], "step_us": round(statistics.median(v), 1), "step_us_min": round(min(v), 1),
+                       "step_us_max": round(max(v), 1), "rounds_step_us": [round(x, 1) for x in v]}
+        e["op_us_per_step"] = round(e["penalised"]["step_us"] - e["plain"]["step_us"], 1)
+        e["plain_round_spread_us"] = round(e["plain"]["step_us_max"] - e["plain"]["step_us_min"], 1)
+        e["op_exceeds_the_plain_steps_spread"] = bool(e["op_us_per_step"] > e["plain_round_spread_us"])
+        res["draft_len"][str(k)] = e
+    return res
+
+
+def penalty_main(args):
+    import torch
+
+    from bench_model import build
+
+    drafts = sorted({int(k) for k in (args.draft_len or "0,4").split(",")})
+    dev = torch.device("cuda:0")
+    lm = build(LAYERS, dev).fuse_prefill()
+    with torch.no_grad():
+        points = [penalty_point(lm, b, drafts, args.rounds, dev) for b in map(int, args.batch.split(","))]
+    out = {"tool": "tools/bench_generate.py --penalties", "device": torch.cuda.get_device_name(0),
+           "shape": "Llama-2-7B layers, per-channel W4A8, fuse_qkv(), fuse_prefill(), paged fp16 cache, block 16, greedy, ngram_max 3",
+           "penalties": PENALTIES, "history_tokens": [PROMPT, PROMPT + NEW - 1], "sync_every": SYNC_EVERY, "rounds": args.rounds,
+           "points": points}
+    path = args.out or os.path.join(ROOT, "profiles", "penalty_loop_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"batch {p['batch']:3d}: " + "  ".join(
+            f"K={k} plain {e['plain']['step_us']:.1f} penalised {e['penalised']['step_us']:.1f} us/step (+{e['op_us_per_step']}, plain spread "
+            f"{e['plain_round_spread_us']})" for k, e in p["draft_len"].items()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", default="1,16")
@@ -217,12 +301,16 @@ def main():
     ap.add_argument("--draft-len", default=None, help="e.g. 0,2,4,7: measure the speculative loop instead (profiles/spec_decode_bench.json)")
     ap.add_argument("--verify", action="store_true", help="with --draft-len: every K > 0 also with fuse_verify() "
                     "(profiles/spec_decode_verify_bench.json)")
+    ap.add_argument("--penalties", action="store_true", help="time the replayed step with and without ops.penalize_logits "
+                    "(profiles/penalty_loop_bench.json)")
     ap.add_argument("--out", default=None, help="default profiles/decode_loop_bench.json, or profiles/spec_decode_bench.json with --draft-len")
     args = ap.parse_args()
     import torch
 
     if not torch.cuda.is_available():
         sys.exit("bench_generate.py needs a GPU: a timing taken elsewhere says nothing")
+    if args.penalties:
+        return penalty_main(args)
     if args.draft_len:
         return spec_main(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "decode_loop_bench.json")

@@ -11,6 +11,18 @@ A round's value is the median of its calls; the JSON keeps every round and repor
 torch / fused.  Logits are fp16(4 N(0, 1)), T = 0.8, k = 50, p = 0.9; `--mode` picks which cuts are on.
 
     python tools/bench_sample.py [--out profiles/sample_bench.json] [--rows 1,16,64] [--vocab 32000,128256,151936]
+
+With --penalties the tool times ops.penalize_logits alone instead, against a torch composition of the same semantics, by the same protocol:
+
+    fused   ops.penalize_logits(logits, ids, pos, seen, n_prompt, repetition, presence, frequency, workspace): one launch
+    torch   per logits row of a row: the history and the drafts in front of it as one index tensor; the output counts by a scatter_add
+            into [rows, vocab] (a bincount per row); gather of the counts and of the logits at the history's tokens; where() for the
+            repetition rule and for c > 0; scatter of the results back (equal tokens write equal values)
+Both rewrite fp16 [rows * G, vocab] in place.  Points: every vocab and rows above x histories of 128, 2048 and 16384 tokens x G = 1 and 5 x
+the all-distinct and the all-one-token history, half of it prompt; penalties 1.3, 0.5, 0.25.  Written: the op's time per point, torch's,
+torch / fused with the range over the rounds, and the share of logit bits the two agree on after one call.
+
+    python tools/bench_sample.py --penalties [--out profiles/penalty_bench.json] [--rows 1,16,64] [--vocab 32000,128256,151936]
 """
 import argparse
 import json
@@ -103,9 +115,98 @@ def point(rows, vocab, mode, dev):
     return res
 
 
+PENALTIES, HISTORIES, GROUPS, CONTENTS = (1.3, 0.5, 0.25), (128, 2048, 16384), (1, 5), ("distinct", "one_token")
+
+
+def torch_penalize(logits, ids, pos, seen, n_prompt, rep, pres, freq):
+    """The semantics of include/qqq_amd_penalty.h for rows that share one position and hold valid tokens only (what the points are)."""
+    import torch
+
+    rows, group = ids.shape
+    vocab, n = logits.shape[1], seen.shape[1]  # the history fills `seen`: p + 1 = seen_stride
+    seen[:, n - 1] = ids[:, 0]
+    hist = seen.long()
+    for j in range(group):
+        seq = torch.cat([hist, ids[:, 1:j + 1]], dim=1)
+        is_out = (torch.arange(n + j, device=seq.device)[None] >= n_prompt[:, None]).float()
+        counts = torch.zeros((rows, vocab), device=seq.device).scatter_add_(1, seq, is_out)
+        c = counts.gather(1, seq)
+        row = logits[j::group]
+        x = row.gather(1, seq).float()
+        x = torch.where(x > 0, x / rep[:, None], x * rep[:, None])
+        x = torch.where(c > 0, x - freq[:, None] * c - pres[:, None], x)
+        row.scatter_(1, seq, x.half())
+    return logits
+
+
+def penalty_point(rows, vocab, n, group, content, dev):
+    import torch
+
+    from qqq_amd import ops
+
+    g = torch.Generator(device=dev).manual_seed(vocab + rows + n + group)
+    fresh = (4.0 * torch.randn((rows * group, vocab), generator=g, device=dev)).half()
+    if content == "distinct":
+        tokens = torch.stack([torch.randperm(vocab, generator=g, device=dev)[:n + group - 1] for _ in range(rows)])
+    else:
+        tokens = torch.randint(0, vocab, (rows, 1), generator=g, device=dev).expand(rows, n + group - 1).contiguous()
+    seen = tokens[:, :n].int().contiguous()
+    ids = tokens[:, n - 1:].contiguous()
+    pos = (n - 1 + torch.arange(group, device=dev))[None].expand(rows, group).contiguous()
+    n_prompt = torch.full((rows,), n // 2, dtype=torch.int32, device=dev)
+    rep, pres, freq = (torch.full((rows,), v, dtype=torch.float32, device=dev) for v in PENALTIES)
+    ws = torch.zeros(rows * vocab, dtype=torch.int32, device=dev)
+    bufs = {"fused": fresh.clone(), "torch": fresh.clone()}
+    fns = {"fused": lambda: ops.penalize_logits(bufs["fused"], ids, pos, seen, n_prompt, rep, pres, freq, ws),
+           "torch": lambda: torch_penalize(bufs["torch"], ids, pos, seen, n_prompt, rep, pres, freq)}
+    same = float((fns["fused"]().view(torch.int16) == fns["torch"]().view(torch.int16)).float().mean())
+    res = {"rows": rows, "vocab": vocab, "history": n, "group": group, "content": content, "bits_equal_fraction": same}
+    for how in ("eager", "graph"):  # the values drift as the penalties pile up call after call; the work does not depend on them
+        run = fns if how == "eager" else {name: capture(f).replay for name, f in fns.items()}
+        for f in run.values():
+            for _ in range(WARMUP):
+                f()
+        torch.cuda.synchronize()
+        rounds = {name: [] for name in run}
+        for _ in range(ROUNDS):
+            for name, f in run.items():
+                rounds[name].append(statistics.median(time_calls(f, CALLS)))
+        r = {}
+        for name, v in rounds.items():
+            r[name] = {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
+                       "rounds_us": [round(x, 2) for x in v]}
+        r["torch_over_fused"] = round(r["torch"]["median_us"] / r["fused"]["median_us"], 2)
+        r["torch_over_fused_range"] = [round(r["torch"]["min_us"] / r["fused"]["max_us"], 2), round(r["torch"]["max_us"] / r["fused"]["min_us"], 2)]
+        res[how] = r
+    assert int(torch.count_nonzero(ws)) == 0
+    return res
+
+
+def penalty_main(args, dev):
+    import torch
+
+    points = [penalty_point(r, v, n, g, c, dev) for v in map(int, args.vocab.split(",")) for r in map(int, args.rows.split(","))
+              for n in HISTORIES for g in GROUPS for c in CONTENTS]
+    notes = [f"rows={p['rows']} vocab={p['vocab']} history={p['history']} G={p['group']} {p['content']} {how}: the op does not win "
+             f"({p[how]['torch_over_fused']}x)" for p in points for how in ("eager", "graph") if p[how]["torch_over_fused_range"][0] <= 1.0]
+    out = {"tool": "tools/bench_sample.py --penalties", "device": torch.cuda.get_device_name(0), "rounds": ROUNDS, "calls_per_round": CALLS,
+           "penalties": dict(zip(("repetition", "presence", "frequency"), PENALTIES)), "points": points,
+           "notes": notes or ["the op wins at every point, also at the unfavourable ends of both spreads"]}
+    path = args.out or os.path.join(ROOT, "profiles", "penalty_bench.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"rows {p['rows']:3d} vocab {p['vocab']:6d} history {p['history']:5d} G {p['group']} {p['content']:9s}: " + "  ".join(
+            f"{how} fused {p[how]['fused']['median_us']:8.1f} us torch {p[how]['torch']['median_us']:8.1f} us ({p[how]['torch_over_fused']}x)"
+            for how in ("eager", "graph")))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sample_bench.json"))
+    ap.add_argument("--out", default=None, help="default profiles/sample_bench.json, or profiles/penalty_bench.json with --penalties")
+    ap.add_argument("--penalties", action="store_true", help="time ops.penalize_logits against a torch composition instead")
     ap.add_argument("--rows", default="1,16,64")
     ap.add_argument("--vocab", default="32000,128256,151936")
     ap.add_argument("--modes", default="sample,top_k_top_p")
@@ -115,6 +216,9 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("bench_sample.py needs a GPU: a timing taken elsewhere says nothing")
     dev = torch.device("cuda:0")
+    if args.penalties:
+        return penalty_main(args, dev)
+    args.out = args.out or os.path.join(ROOT, "profiles", "sample_bench.json")
     points = [point(r, v, m, dev) for m in args.modes.split(",") for v in map(int, args.vocab.split(",")) for r in map(int, args.rows.split(","))]
     notes = [f"{p['mode']} rows={p['rows']} vocab={p['vocab']} {how}: the fused op does not win ({p[how]['torch_over_fused']}x)"
              for p in points for how in ("eager", "graph") if p[how]["torch_over_fused_range"][0] <= 1.0]
