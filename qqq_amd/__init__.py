@@ -19,6 +19,8 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
                                                                                     # prefill attention over the block pools, output int8-quantised
     verify_attention_paged(q_out, k_pool, v_pool, block_table, start, tokens, scale) / verify_attention_paged_kv8(...)  # a verify chunk of
                                                                                     # `tokens` tokens per row through the decode kernel, bit for bit
+    decode_attention_paged_shared(q_out, k_pool, v_pool, block_table, pos, family, shared, pack, scale) / ..._kv8(...)  # decode attention of
+                                                                                    # forked siblings: shared keys read once per pack, bit for bit
     KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer                            # attention and the whole layer; qqq_amd/attention.py
     PagedKVCache, PagedStep                                                        # block pools + host-side allocator; qqq_amd/paged.py
     sample_tokens(logits, temperature, top_k, top_p, u)                             # temperature / top-k / top-p / draw for a batch, one launch
@@ -62,6 +64,9 @@ from .ops import (  # noqa: F401
     token_logprobs,
     verify_attention_paged,
     verify_attention_paged_kv8,
+    decode_attention_paged_shared,
+    decode_attention_paged_shared_kv8,
+    decode_attention_shared_plan,
 )
 from .qlinear import QuantLinear, fuse_quant_linears  # noqa: F401
 from .blocks import QuantLlamaMLP, QuantRMSNorm  # noqa: F401
@@ -77,4 +82,5 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "decode_attention_paged", "rope_qkv_paged_kv8", "decode_attention_paged_kv8", "prefill_attention_paged",
            "prefill_attention_paged_kv8", "PagedKVCache", "PagedStep", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer",
            "sample_tokens", "QuantLlamaModel", "QuantLlamaForCausalLM", "sample_advance", "DecodeLoop", "token_logprobs", "pack_steps",
-           "spec_advance", "SpecDecodeLoop", "ngram_draft", "verify_attention_paged", "verify_attention_paged_kv8", "penalize_logits"]
+           "spec_advance", "SpecDecodeLoop", "ngram_draft", "verify_attention_paged", "verify_attention_paged_kv8", "penalize_logits",
+           "decode_attention_paged_shared", "decode_attention_paged_shared_kv8", "decode_attention_shared_plan"]

@@ -106,6 +106,15 @@ def lib():
     L.qqq_verify_attn_paged_kv8.restype = ci
     L.qqq_verify_attn_workspace_bytes.argtypes = [ci, ci, ci, ci, ci, ci]
     L.qqq_verify_attn_workspace_bytes.restype = ctypes.c_size_t
+    # include/qqq_amd_shared.h
+    L.qqq_decode_attn_paged_shared.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t, ci, ci, ci,
+                                               ci, ci, ci, ci, ci, vp]
+    L.qqq_decode_attn_paged_shared.restype = ci
+    L.qqq_decode_attn_paged_shared_kv8.argtypes = [vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, ci, ctypes.c_float, vp, vp, vp, vp, ctypes.c_size_t,
+                                                   ci, ci, ci, ci, ci, ci, ci, ci, vp]
+    L.qqq_decode_attn_paged_shared_kv8.restype = ci
+    L.qqq_decode_attn_shared_plan.argtypes = [ci, ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    L.qqq_decode_attn_shared_plan.restype = ci
     # include/qqq_amd_sample.h
     L.qqq_sample_tokens.argtypes = [vp, ci, vp, vp, vp, vp, vp, ci, ci, ci, vp]
     L.qqq_sample_tokens.restype = ci

@@ -22,7 +22,7 @@ prefill_attention_paged(_kv8): one ragged causal attention over the whole packed
 input already int8-quantised.  After the opt-in fuse_verify() a step that feeds every sequence the same 2 ... 16 tokens (a speculative decode
 step's chunk) runs verify_attention_paged(_kv8): the decode kernel's split over keys, every token bit for bit its decode step.
 Parameter and buffer names are the reference's, so the layers' state-dicts load unchanged; the rope tables, the fused q|k|v copy of
-fuse_qkv() and the fuse_decode() / fuse_prefill() / fuse_verify() flags are not part of them.
+fuse_qkv() and the fuse_decode() / fuse_prefill() / fuse_verify() / fuse_shared() flags are not part of them.
 """
 from __future__ import annotations
 
@@ -157,6 +157,7 @@ class QuantLlamaAttention(nn.Module):
         self._decode = False  # fuse_decode(): a plain flag (not in the state-dict; kept by load_state_dict and .to())
         self._prefill = False  # fuse_prefill(): the same kind of flag
         self._verify = False  # fuse_verify(): the same kind of flag
+        self._shared = False  # fuse_shared(): the same kind of flag
         # a plain function: a bound method would make module -> hook -> module a reference cycle (see QuantLlamaMLP)
         self._register_load_state_dict_pre_hook(_drop_fused_qkv_on_load, with_module=True)
 
@@ -240,6 +241,24 @@ class QuantLlamaAttention(nn.Module):
     def verify_fused(self) -> bool:
         return self._verify
 
+    def fuse_shared(self):
+        """Opt-in: a decode step over a PagedKVCache in which adjacent sequences were forked from one prompt (PagedStep.family is set: the
+        n completions of parallel sampling) runs decode_attention_paged_shared(_kv8) with pack = min(family_max, 64 // (h // kvh)): the
+        splits inside a family's shared keys are read once per pack of rows, every row bit for bit the plain decode step's.  Every other
+        step goes where it goes without the flag; without it a step with families runs the plain paged decode op over the aliased
+        tables.  state_dict(): unchanged.  Returns self."""
+        self._shared = True
+        return self
+
+    def unfuse_shared(self):
+        """Decode steps with families go back to the plain paged decode op."""
+        self._shared = False
+        return self
+
+    @property
+    def shared_fused(self) -> bool:
+        return self._shared
+
     def _verify_tokens(self, step: PagedStep) -> int:
         """T if fuse_verify() is set and `step` is a chunk the verify kernel takes (from the step's host lists alone), else 0."""
         if not self._verify or step.decode or step.start_pos is None or not step.counts:
@@ -304,6 +323,12 @@ class QuantLlamaAttention(nn.Module):
         li = self.layer_idx
         pools = (cache.k[li], cache.v[li]) + ((cache.k_scale[li], cache.v_scale[li]) if cache.quantized else ())
         q_out = (ops.rope_qkv_paged_kv8 if cache.quantized else ops.rope_qkv_paged)(q, k, v, cos, sin, step.pos, step.slots, *pools)
+        if step.decode and self._shared and step.family is not None:  # fuse_shared(): siblings read their common keys once per pack
+            shared = ops.decode_attention_paged_shared_kv8 if cache.quantized else ops.decode_attention_paged_shared
+            pack = min(int(step.family_max), 64 // (self.num_heads // self.num_key_value_heads))
+            aq, a1 = shared(q_out, *pools, step.block_table, step.last_pos, step.family, step.shared, pack, self.scaling,
+                            max_len=step.max_len)
+            return self.o_proj.forward_int8(aq, a1)
         if step.decode:  # one token per sequence: the decode kernel through the block table, whatever fuse_decode() says
             decode = ops.decode_attention_paged_kv8 if cache.quantized else ops.decode_attention_paged
             aq, a1 = decode(q_out, *pools, step.block_table, step.last_pos, self.scaling, max_len=step.max_len)
@@ -445,6 +470,19 @@ class QuantLlamaDecoderLayer(nn.Module):
     @property
     def verify_fused(self) -> bool:
         return self.self_attn.verify_fused
+
+    def fuse_shared(self):
+        """self_attn.fuse_shared(): paged decode steps over forked siblings take the shared-prefix decode attention kernel.  Returns self."""
+        self.self_attn.fuse_shared()
+        return self
+
+    def unfuse_shared(self):
+        self.self_attn.unfuse_shared()
+        return self
+
+    @property
+    def shared_fused(self) -> bool:
+        return self.self_attn.shared_fused
 
     def forward(self, hidden: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
         x = hidden.reshape(-1, self.hidden_size)

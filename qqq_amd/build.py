@@ -29,6 +29,7 @@ STEP_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_step.h")
 SCORE_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_score.h")
 SPEC_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_spec.h")
 VERIFY_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_verify.h")
+SHARED_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_shared.h")
 PENALTY_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_penalty.h")
 DEV_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_dev.h")
 LIB = os.environ.get("QQQ_AMD_LIB") or os.path.join(_HERE, "libqqq_amd.so")  # override: tuning builds only
@@ -54,7 +55,7 @@ def _stale(lib: str, extra) -> bool:
 
 def needs_build() -> bool:
     return _stale(LIB, [HDR, ACT_HDR, ATTN_HDR, DECODE_HDR, KV8_HDR, PAGED_HDR, PREFILL_HDR, SAMPLE_HDR, STEP_HDR, SCORE_HDR, SPEC_HDR,
-                        VERIFY_HDR, PENALTY_HDR])
+                        VERIFY_HDR, SHARED_HDR, PENALTY_HDR])
 
 
 def _compile(src: str, out: str, verbose: bool, flags=()) -> str:

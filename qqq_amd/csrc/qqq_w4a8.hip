@@ -31,6 +31,7 @@
 //   qqq_small.hip.h    split-K reduce, dynamic quantiser, int4 packer / unpacker, int8 expander
 //   qqq_act.hip.h, qqq_attn.hip.h, qqq_decode.hip.h   the decoder block's fused quantisers, RoPE + KV-cache write, split-K decode attention
 //   qqq_kv8.hip.h      the int8 KV cache: the quantising RoPE / cache write and the decode split kernel that reads it
+//   qqq_shared.hip.h   decode attention of sibling rows over a shared prefix of their block tables: joint splits, bit for bit the paged decode
 //   qqq_paged.hip.h    the block-table (paged) KV cache, fp16 and int8: the cache writes by slot and the decode split kernels through a block table
 //   qqq_prefill.hip.h  paged, ragged, causal prefill attention over the block pools (fp16 and int8) and the quantisation of its rows
 //   qqq_sample.hip.h   the fused token sampler: temperature, top-k, top-p and the draw over a batch of fp16 logit rows, one launch
@@ -84,6 +85,8 @@
 #include "../../include/qqq_amd_spec.h"
 #include "qqq_verify.hip.h"
 #include "../../include/qqq_amd_verify.h"
+#include "qqq_shared.hip.h"
+#include "../../include/qqq_amd_shared.h"
 #include "qqq_penalty.hip.h"
 #include "../../include/qqq_amd_penalty.h"
 #include "qqq_plan.h"
@@ -1053,6 +1056,129 @@ extern "C" int qqq_verify_attn_paged_kv8(const void* q, const void* k_pool, cons
                                          int num_blocks, int block_size, int max_len, int dev, void* stream) {
   return verify_attn_paged("qqq_verify_attn_paged_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, start, scale,
                            o_fp16, xq, s1, workspace, workspace_bytes, b, t, h, kvh, d, num_blocks, block_size, max_len, dev, stream);
+}
+
+// ---- the decode attention of rows that share a prefix (include/qqq_amd_shared.h; kernels in qqq_shared.hip.h): decode_attn_paged's two
+// launches, the first one with the family descriptors.  One body for the pair; `name` is the entry point's.
+template <int D, int NQ, typename... Args>
+static void shared_split(bool kv8, dim3 grid, hipStream_t st, const _Float16* q, const void* k_pool, const void* v_pool, const void* k_scale,
+                         const void* v_scale, Args... rest) {
+  if (kv8)
+    hipLaunchKernelGGL((qqq_shared_kv8_split_kernel<D, NQ>), grid, dim3(DEC_WAVES * 64), 0, st, q, static_cast<const int8_t*>(k_pool),
+                       static_cast<const int8_t*>(v_pool), static_cast<const float*>(k_scale), static_cast<const float*>(v_scale), rest...);
+  else
+    hipLaunchKernelGGL((qqq_shared_split_kernel<D, NQ>), grid, dim3(DEC_WAVES * 64), 0, st, q, static_cast<const _Float16*>(k_pool),
+                       static_cast<const _Float16*>(v_pool), rest...);
+}
+
+template <int D, typename... Args>
+static void shared_split_tiles(int rows, Args... args) {
+  if (rows <= 16)
+    shared_split<D, 1>(args...);
+  else if (rows <= 32)
+    shared_split<D, 2>(args...);
+  else
+    shared_split<D, 4>(args...);
+}
+
+extern "C" int qqq_decode_attn_shared_plan(int b, int h, int kvh, int max_len, int pack, int* splits, int* chunk) {
+  g_err[0] = 0;
+  if (!splits || !chunk || b < 1 || decode_shape_error(b, h, kvh, 64, max_len) || pack < 1 || (long long)(h / kvh) * pack > SHR_ROWS_MAX) {
+    snprintf(g_err, sizeof(g_err), "qqq_decode_attn_shared_plan: bad argument b=%d h=%d kvh=%d max_len=%d pack=%d (need result pointers, "
+             "1 <= b <= 65535, h %% kvh == 0, h / kvh <= %d, max_len >= 1, pack >= 1, (h / kvh) * pack <= %d)", b, h, kvh, max_len, pack,
+             DEC_GMAX, SHR_ROWS_MAX);
+    return QQQ_ERR_ARG;
+  }
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) dev = -1;
+  decode_split_plan(dev, b, kvh, max_len, splits, chunk);
+  return QQQ_OK;
+}
+
+static int decode_attn_paged_shared(const char* name, bool kv8, const void* q, const void* k_pool, const void* v_pool, const void* k_scale,
+                                    const void* v_scale, const void* block_table, int table_stride, const void* pos, const void* family,
+                                    const void* shared, int pack, float scale, void* o_fp16, void* xq, void* s1, void* workspace,
+                                    size_t workspace_bytes, int b, int h, int kvh, int d, int num_blocks, int block_size, int max_len,
+                                    int dev, void* stream) {
+  g_err[0] = 0;
+  if (b < 0 || h < 0 || kvh < 0 || d < 0 || num_blocks < 0 || block_size < 0 || table_stride < 0 || max_len < 0) {
+    snprintf(g_err, sizeof(g_err), "%s: negative size (b=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_stride=%d max_len=%d)", name,
+             b, h, kvh, d, num_blocks, block_size, table_stride, max_len);
+    return QQQ_ERR_ARG;
+  }
+  if (b == 0) return QQQ_OK;
+  const int lbs = paged_log2_block(block_size);
+  if (decode_shape_error(b, h, kvh, d, max_len) || pack < 1 || (long long)(h / kvh) * pack > SHR_ROWS_MAX || lbs < 0 || num_blocks < 1 ||
+      (long long)num_blocks * block_size > 0x7fffffffLL || table_stride < 1 || max_len > (long long)table_stride * block_size) {
+    snprintf(g_err, sizeof(g_err), "%s: bad shape b=%d h=%d kvh=%d d=%d pack=%d num_blocks=%d block_size=%d table_stride=%d max_len=%d (need "
+             "h %% kvh == 0, h / kvh <= %d, d 64 or 128, h*d <= 16384, b <= 65535, pack >= 1, (h / kvh) * pack <= %d, block_size a power of "
+             "two in [16, 256], num_blocks >= 1, num_blocks * block_size < 2^31, 1 <= max_len <= table_stride * block_size)", name, b, h,
+             kvh, d, pack, num_blocks, block_size, table_stride, max_len, DEC_GMAX, SHR_ROWS_MAX);
+    return QQQ_ERR_ARG;
+  }
+  if (!o_fp16 && !xq && !s1) {
+    snprintf(g_err, sizeof(g_err), "%s: no output (o_fp16 and xq / s1 are all NULL)", name);
+    return QQQ_ERR_ARG;
+  }
+  if (!q || !k_pool || !v_pool || !block_table || !pos || !family || !shared || !workspace || (!xq) != (!s1) || misaligned(q, 16) ||
+      misaligned(k_pool, 16) || misaligned(v_pool, 16) || misaligned(block_table, 4) || misaligned(pos, 8) || misaligned(family, 4) ||
+      misaligned(shared, 8) || misaligned(workspace, 16) || (o_fp16 && misaligned(o_fp16, 16)) || (xq && misaligned(xq, 8)) ||
+      (s1 && misaligned(s1, 4)) || (kv8 && (!k_scale || !v_scale || misaligned(k_scale, 4) || misaligned(v_scale, 4)))) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (q / pools / scales / block_table / pos / family / shared / workspace must be non-NULL, "
+             "xq and s1 both given or both NULL; q, pools, o_fp16, workspace 16-byte, pos / shared / xq 8-byte, block_table, family, s1 and "
+             "the scales 4-byte aligned)", name);
+    return QQQ_ERR_ARG;
+  }
+  const size_t need = qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len);
+  if (workspace_bytes < need) {
+    snprintf(g_err, sizeof(g_err), "%s: workspace of %zu bytes, need %zu", name, workspace_bytes, need);
+    return QQQ_ERR_ARG;
+  }
+  if (pack == 1)  // nothing can be taken jointly: the plain call
+    return decode_attn_paged(name, kv8, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, pos, scale, o_fp16, xq, s1,
+                             workspace, workspace_bytes, b, h, kvh, d, num_blocks, block_size, max_len, dev, stream);
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  int splits, chunk;
+  decode_split_plan(dev, b, kvh, max_len, &splits, &chunk);
+  float* wo = static_cast<float*>(workspace);
+  float* wml = wo + (size_t)b * h * splits * d;
+  const long long* pp = static_cast<const long long*>(pos);
+  const long long limit = max_len;  // <= table_stride * block_size
+  const float scale_log2 = scale * 1.4426950408889634f;
+  const _Float16* qp = static_cast<const _Float16*>(q);
+  const int* tp = static_cast<const int*>(block_table);
+  const int* fp = static_cast<const int*>(family);
+  const long long* shp = static_cast<const long long*>(shared);
+  const dim3 grid(splits, kvh, b);
+  if (d == 64)
+    shared_split_tiles<64>((h / kvh) * pack, kv8, grid, st, qp, k_pool, v_pool, k_scale, v_scale, tp, table_stride, pp, limit, fp, shp, pack,
+                           scale_log2, wo, wml, h, kvh, num_blocks, lbs, chunk, splits);
+  else
+    shared_split_tiles<128>((h / kvh) * pack, kv8, grid, st, qp, k_pool, v_pool, k_scale, v_scale, tp, table_stride, pp, limit, fp, shp, pack,
+                            scale_log2, wo, wml, h, kvh, num_blocks, lbs, chunk, splits);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, kv8 ? "qqq_shared_kv8_split_kernel launch" : "qqq_shared_split_kernel launch");
+  return decode_combine_launch(b, st, wo, wml, pp, limit, o_fp16, xq, s1, h, d, chunk, splits);
+}
+
+extern "C" int qqq_decode_attn_paged_shared(const void* q, const void* k_pool, const void* v_pool, const void* block_table, int table_stride,
+                                            const void* pos, const void* family, const void* shared, int pack, float scale, void* o_fp16,
+                                            void* xq, void* s1, void* workspace, size_t workspace_bytes, int b, int h, int kvh, int d,
+                                            int num_blocks, int block_size, int max_len, int dev, void* stream) {
+  return decode_attn_paged_shared("qqq_decode_attn_paged_shared", false, q, k_pool, v_pool, nullptr, nullptr, block_table, table_stride, pos,
+                                  family, shared, pack, scale, o_fp16, xq, s1, workspace, workspace_bytes, b, h, kvh, d, num_blocks,
+                                  block_size, max_len, dev, stream);
+}
+
+extern "C" int qqq_decode_attn_paged_shared_kv8(const void* q, const void* k_pool, const void* v_pool, const void* k_scale,
+                                                const void* v_scale, const void* block_table, int table_stride, const void* pos,
+                                                const void* family, const void* shared, int pack, float scale, void* o_fp16, void* xq,
+                                                void* s1, void* workspace, size_t workspace_bytes, int b, int h, int kvh, int d,
+                                                int num_blocks, int block_size, int max_len, int dev, void* stream) {
+  return decode_attn_paged_shared("qqq_decode_attn_paged_shared_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride,
+                                  pos, family, shared, pack, scale, o_fp16, xq, s1, workspace, workspace_bytes, b, h, kvh, d, num_blocks,
+                                  block_size, max_len, dev, stream);
 }
 
 // ---- the paged prefill attention (include/qqq_amd_prefill.h; kernels in qqq_prefill.hip.h): one attention launch over the packed batch's

@@ -84,6 +84,17 @@ class QuantLlamaModel(nn.Module):
     def unfuse_verify(self):
         return self._each_layer("unfuse_verify")
 
+    def fuse_shared(self):
+        """fuse_shared() on every layer.  Returns self."""
+        return self._each_layer("fuse_shared")
+
+    def unfuse_shared(self):
+        return self._each_layer("unfuse_shared")
+
+    @property
+    def shared_fused(self) -> bool:
+        return all(layer.shared_fused for layer in self.layers)
+
     def fuse_qkv(self):
         """self_attn.fuse_qkv() on every layer (a second copy of the q / k / v weights).  Returns self."""
         for layer in self.layers:
@@ -156,6 +167,18 @@ class QuantLlamaForCausalLM(nn.Module):
         self.model.unfuse_verify()
         return self
 
+    def fuse_shared(self):
+        self.model.fuse_shared()
+        return self
+
+    def unfuse_shared(self):
+        self.model.unfuse_shared()
+        return self
+
+    @property
+    def shared_fused(self) -> bool:
+        return self.model.shared_fused
+
     def fuse_qkv(self):
         self.model.fuse_qkv()
         return self
@@ -172,8 +195,8 @@ class QuantLlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, cache: Optional[PagedKVCache] = None,
-                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False, draft_len: int = 0, repetition_penalty: float = 1.0,
-                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> List[List[int]]:
+                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False, n: int = 1, draft_len: int = 0,
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> List[List[int]]:
         """Generate up to `max_new_tokens` tokens for every prompt (token lists of any lengths) -> the generated ids per prompt, the
         eos_token_id that ends a sequence included.
 
@@ -198,8 +221,23 @@ class QuantLlamaForCausalLM(nn.Module):
         repetition_penalty (transformers' rule: a seen token's logit l becomes l / r if l > 0, else l * r; over prompt and output),
         presence_penalty and frequency_penalty (vLLM's: l - frequency * c - presence for a token emitted c > 0 times; over the output
         alone) act on every pass's logits before temperature, top-k and top-p, through ops.penalize_logits on all three paths (the device
-        loops are then built with penalties=True).  1, 0 and 0 mean none, and then nothing of it runs."""
+        loops are then built with penalties=True).  1, 0 and 0 mean none, and then nothing of it runs.
+
+        n=N > 1 (parallel sampling) returns per prompt a list of N completions.  A prompt is prefilled once; its N first tokens are N
+        sampler draws from the one last-position logits row (repeated, and penalised when penalties are on), PagedKVCache.fork makes the
+        siblings that go on, and from then on each is an ordinary row with its own variates, history, penalties, eos and budget.  The
+        siblings share the prompt's full blocks until the last of them ends, so a prompt of L keys and a budget of B blocks takes
+        B + (N - 1) * (B - L // block_size) blocks in place of N * B.  The draws: one torch.rand of (admitted prompts * N) per prefill
+        pass, then as for n = 1 one per decode pass over the running rows; equal seeds give equal tokens.  Siblings are adjacent in every
+        step, so a model with fuse_shared() reads their common keys once per pack of rows (the tokens are the same either way).
+        device_loop=True builds the DecodeLoop with family=N; n > 1 with draft_len > 0 raises (there is no shared verify kernel).
+        n=1 is the call described above, draw for draw."""
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"generate: n={n} must be at least 1")
         draft_len = int(draft_len)
+        if n > 1 and draft_len > 0:
+            raise ValueError(f"generate: n={n} > 1 cannot be combined with draft_len={draft_len} (speculative steps have no shared-prefix kernel)")
         if draft_len < 0 or (draft_len > 0 and not device_loop):
             raise ValueError(f"generate: draft_len={draft_len} must be 0, or positive together with device_loop=True")
         penalty = (float(repetition_penalty), float(presence_penalty), float(frequency_penalty))
@@ -211,13 +249,20 @@ class QuantLlamaForCausalLM(nn.Module):
         prompts = [list(p) for p in prompts]
         if any(not p for p in prompts):
             raise ValueError("generate: every prompt needs at least one token")
-        out: List[List[int]] = [[] for _ in prompts]
+        out: List[List[int]] = [[] for _ in range(len(prompts) * n)]  # per sibling: prompt i's are i * n ... i * n + n - 1
+
+        def result():
+            return out if n == 1 else [out[i * n:(i + 1) * n] for i in range(len(prompts))]
+
         if max_new_tokens < 1 or not prompts:
-            return out
+            return result()
         dev = self.lm_head.weight.device
-        need = [-(-(len(p) + max_new_tokens - 1 + draft_len) // (cache.block_size if cache is not None else block_size)) for p in prompts]
+        bs = cache.block_size if cache is not None else block_size
+        need = [-(-(len(p) + max_new_tokens - 1 + draft_len) // bs) for p in prompts]
+        # a family: the prompt's blocks once plus, per further sibling, the blocks beyond the shared ones
+        fam_need = [nd + (n - 1) * (nd - len(p) // bs) for nd, p in zip(need, prompts)]
         if cache is None:
-            cache = self.new_cache(sum(need), block_size, dtype)
+            cache = self.new_cache(sum(fam_need), block_size, dtype)
         if draft_len:
             from .serve import SpecDecodeLoop
 
@@ -227,37 +272,49 @@ class QuantLlamaForCausalLM(nn.Module):
         if device_loop:
             from .serve import DecodeLoop
 
-            loop = DecodeLoop(self, cache, rows=min(len(prompts), 64), max_len=max(need) * cache.block_size, **loop_kw)
+            if n > 1:
+                loop = DecodeLoop(self, cache, rows=max(1, min(len(prompts), 64 // n)) * n, max_len=max(need) * cache.block_size, family=n,
+                                  **loop_kw)
+            else:
+                loop = DecodeLoop(self, cache, rows=min(len(prompts), 64), max_len=max(need) * cache.block_size, **loop_kw)
             return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, **gen_kw)
         tag = object()  # sequence ids no other user of the cache can hold
         sid = lambda i: (tag, i)  # noqa: E731
-        waiting, running = deque(range(len(prompts))), []
+        waiting, running = deque(range(len(prompts))), []  # prompts that wait; siblings that run (i * n + j)
         cur = None  # int64 [len(running)] on the device: the running sequences' last tokens
 
-        workspace = torch.zeros(len(prompts) * self.lm_head.weight.shape[0], dtype=torch.int32, device=dev) if penalised else None
+        workspace = torch.zeros(len(out) * self.lm_head.weight.shape[0], dtype=torch.int32, device=dev) if penalised else None
 
-        def sample(ids, step, seqs):
+        def sample(ids, step, seqs, repeat=1):
             logits = self(ids, cache, step)
+            if repeat > 1:  # a prompt's row serves the first draw of each of its siblings
+                logits = logits.repeat_interleave(repeat, dim=0)
             if penalised:  # the history is host-side like the rest of the bookkeeping: the prompt and what was emitted, padded per pass
-                hist = [prompts[i] + out[i] for i in seqs]
+                hist = [prompts[i // n] + out[i] for i in seqs]
                 width = max(len(h) for h in hist)
                 seen = torch.tensor([h + [-1] * (width - len(h)) for h in hist], dtype=torch.int32).to(dev)
                 ops.penalize_logits(logits, torch.tensor([h[-1] for h in hist], dtype=torch.int64, device=dev),
                                     torch.tensor([len(h) - 1 for h in hist], dtype=torch.int64, device=dev), seen,
-                                    torch.tensor([len(prompts[i]) for i in seqs], dtype=torch.int32, device=dev), *penalty, workspace)
+                                    torch.tensor([len(prompts[i // n]) for i in seqs], dtype=torch.int32, device=dev), *penalty, workspace)
             u = torch.rand(logits.shape[0], generator=generator, device=logits.device)
             return ops.sample_tokens(logits, temperature, top_k, top_p, u)
 
-        def settle(seqs, toks):
-            """record a pass's tokens; -> (the sequences that go on, their rows of the pass)"""
-            alive, rows = [], []
+        def settle(seqs, toks, fork=False):
+            """record a pass's tokens; -> (the sequences that go on, their rows of the pass).  After a prefill pass with n > 1 (`fork`)
+            only sibling 0 of a prompt exists yet: the others that go on are forked from it before it is freed, if it ends."""
+            alive, rows, done = [], [], []
             for row, (i, t) in enumerate(zip(seqs, toks.tolist())):
                 out[i].append(t)
                 if len(out[i]) >= max_new_tokens or (eos_token_id is not None and t == eos_token_id):
-                    cache.free(sid(i))
+                    if not fork or i % n == 0:
+                        done.append(i)
                 else:
+                    if fork and i % n:
+                        cache.fork(sid(i - i % n), sid(i))
                     alive.append(i)
                     rows.append(row)
+            for i in done:
+                cache.free(sid(i))
             return alive, rows
 
         def take(toks, rows):
@@ -269,24 +326,25 @@ class QuantLlamaForCausalLM(nn.Module):
                 running, rows = settle(running, toks)
                 cur = take(toks, rows)
             new = []
-            owed = sum(need[i] - len(cache.blocks(sid(i))) for i in running)  # what the running sequences may still take
-            while waiting and need[waiting[0]] <= cache.free_blocks - owed:
+            owed = sum(need[i // n] - len(cache.blocks(sid(i))) for i in running)  # what the running sequences may still take
+            while waiting and fam_need[waiting[0]] <= cache.free_blocks - owed:
                 i = waiting.popleft()
-                cache.add(sid(i))
-                owed += need[i]
+                cache.add(sid(i * n))
+                owed += fam_need[i]
                 new.append(i)
             if not new:
                 if not running and waiting:
                     raise RuntimeError(f"generate: the pool's {cache.free_blocks} free blocks cannot hold a prompt that needs "
-                                       f"{need[waiting[0]]} (prompt and budget)")
+                                       f"{fam_need[waiting[0]]} (prompt and budget)")
                 continue
             ids = torch.tensor([t for i in new for t in prompts[i]], dtype=torch.int64, device=dev)
-            toks = sample(ids, cache.step([sid(i) for i in new], [len(prompts[i]) for i in new]), new)
-            alive, rows = settle(new, toks)
+            born = [i * n + j for i in new for j in range(n)]
+            toks = sample(ids, cache.step([sid(i * n) for i in new], [len(prompts[i]) for i in new]), born, repeat=n)
+            alive, rows = settle(born, toks, fork=n > 1)
             first = take(toks, rows)
             cur = first if not running else torch.cat([cur, first])
             running = running + alive
-        return out
+        return result()
 
     def score(self, sequences: Sequence[Sequence[int]], cache: Optional[PagedKVCache] = None, chunk_tokens: int = 2048, block_size: int = 16,
               dtype=torch.float16, return_greedy: bool = False):

@@ -983,6 +983,131 @@ def decode_attention_paged_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool
     return out if return_fp16 else out[:2]
 
 
+# ---- the decode attention of sibling rows over a shared prefix (include/qqq_amd_shared.h): the n completions of one prompt read the
+# prompt's keys once per pack of rows; every row bit for bit decode_attention_paged(_kv8)'s.
+
+def _decode_attention_paged_shared_check(name, block_table, family, shared, pack):
+    b = block_table.shape[0] if block_table.dim() == 2 else -1
+    if family.dtype != torch.int32 or shared.dtype != torch.int64:
+        raise RuntimeError(f"{name}: family must be int32 and shared int64")
+    if family.numel() != b or shared.numel() != b:
+        raise RuntimeError(f"{name}: family holds {family.numel()} and shared {shared.numel()} entries, the block table has {b} rows")
+    if int(pack) < 1:
+        raise RuntimeError(f"{name}: pack must be at least 1, not {pack}")
+
+
+def _decode_attention_paged_shared_impl(q_out, k_pool, v_pool, block_table, pos, family, shared, pack, scale, max_len, return_fp16,
+                                        k_scale=None, v_scale=None):
+    kv8 = k_scale is not None
+    name = "decode_attention_paged_shared_kv8" if kv8 else "decode_attention_paged_shared"
+    ts = (q_out, k_pool, v_pool, block_table, pos, family, shared) + ((k_scale, v_scale) if kv8 else ())
+    _same_gpu(name, ts)
+    if q_out.dtype != torch.float16 or pos.dtype != torch.int64 or block_table.dtype != torch.int32:
+        raise RuntimeError(f"{name}: q_out must be fp16, pos int64 and block_table int32")
+    _paged_check_pools(name, k_pool, v_pool, k_scale, v_scale)
+    b, h, kvh, d, nb, bs, width, max_len = _decode_attention_paged_shapes(name, q_out, k_pool, block_table, pos, max_len)
+    _decode_attention_paged_shared_check(name, block_table, family, shared, pack)
+    dev = q_out.device
+    xq = torch.empty((b, h * d), dtype=torch.int8, device=dev)
+    s1 = torch.empty((b, 1), dtype=torch.float32, device=dev)
+    o16 = torch.empty((b, h * d) if return_fp16 else (0,), dtype=torch.float16, device=dev)
+    if b == 0:
+        return xq, s1, o16
+    L = _lib.lib()
+    nbytes = L.qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len)
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)  # torch's allocator: also under stream / graph capture
+    q2, pos, table = q_out.contiguous(), pos.contiguous(), block_table.contiguous()
+    family, shared = family.contiguous(), shared.contiguous()
+    tail = (_ptr(table), width, _ptr(pos), _ptr(family), _ptr(shared), int(pack), float(scale), _ptr(o16), _ptr(xq), _ptr(s1), _ptr(ws),
+            ws.numel(), b, h, kvh, d, nb, bs, max_len, dev.index or 0, _stream_for(q_out))
+    if kv8:
+        err = L.qqq_decode_attn_paged_shared_kv8(_ptr(q2), _ptr(k_pool), _ptr(v_pool), _ptr(k_scale), _ptr(v_scale), *tail)
+    else:
+        err = L.qqq_decode_attn_paged_shared(_ptr(q2), _ptr(k_pool), _ptr(v_pool), *tail)
+    _raise_lib(name, err)
+    return xq, s1, o16
+
+
+def _decode_paged_shared_fake(name, q_out, k_pool, block_table, pos, family, shared, pack, max_len, return_fp16):
+    _decode_attention_paged_shared_check(name, block_table, family, shared, pack)
+    return _decode_paged_fake(name, q_out, k_pool, block_table, pos, max_len, return_fp16)
+
+
+@torch.library.custom_op("qqq_amd::decode_attn_paged_shared", mutates_args=())
+def _decode_attn_paged_shared_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                                 pos: torch.Tensor, family: torch.Tensor, shared: torch.Tensor, pack: int, scale: float,
+                                 max_len: Optional[int], return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _decode_attention_paged_shared_impl(q_out, k_pool, v_pool, block_table, pos, family, shared, pack, scale, max_len, return_fp16)
+
+
+@_decode_attn_paged_shared_op.register_fake
+def _(q_out, k_pool, v_pool, block_table, pos, family, shared, pack, scale, max_len, return_fp16):
+    return _decode_paged_shared_fake("decode_attention_paged_shared", q_out, k_pool, block_table, pos, family, shared, pack, max_len,
+                                     return_fp16)
+
+
+def decode_attention_paged_shared(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                                  pos: torch.Tensor, family: torch.Tensor, shared: torch.Tensor, pack: int, scale: float,
+                                  max_len: Optional[int] = None, return_fp16: bool = False):
+    """decode_attention_paged for rows that share a prefix of their block tables (PagedKVCache.fork): every row's xq, s1 and fp16 output bit
+    for bit decode_attention_paged's on the same tensors, the splits inside a family's shared keys read once per pack of rows.
+
+    q_out, k_pool, v_pool, block_table, pos, scale, max_len   as for decode_attention_paged
+    family     int32 [b]: the index of the first row of row i's family (siblings are adjacent; a lone row names itself)
+    shared     int64 [b]: the leading keys a row has in common with its family, the same on all its rows (0 for a lone row); the rows of a
+               family hold equal table entries for their first shared // block_size blocks
+    pack       sibling rows whose queries share one workgroup: pack >= 1, (h // kvh) * pack <= 64; pack = 1 is decode_attention_paged
+    A row whose position is outside [0, max_len) writes nothing and does not disturb its siblings; descriptors that make no sense make
+    rows compute alone."""
+    ts = (q_out, k_pool, v_pool, block_table, pos, family, shared)
+    if _compiling(*ts):
+        out = _decode_attn_paged_shared_op(*ts, pack, scale, max_len, return_fp16)
+    else:
+        out = _decode_attention_paged_shared_impl(*ts, pack, scale, max_len, return_fp16)
+    return out if return_fp16 else out[:2]
+
+
+@torch.library.custom_op("qqq_amd::decode_attn_paged_shared_kv8", mutates_args=())
+def _decode_attn_paged_shared_kv8_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor,
+                                     v_scale: torch.Tensor, block_table: torch.Tensor, pos: torch.Tensor, family: torch.Tensor,
+                                     shared: torch.Tensor, pack: int, scale: float, max_len: Optional[int],
+                                     return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _decode_attention_paged_shared_impl(q_out, k_pool, v_pool, block_table, pos, family, shared, pack, scale, max_len, return_fp16,
+                                               k_scale, v_scale)
+
+
+@_decode_attn_paged_shared_kv8_op.register_fake
+def _(q_out, k_pool, v_pool, k_scale, v_scale, block_table, pos, family, shared, pack, scale, max_len, return_fp16):
+    return _decode_paged_shared_fake("decode_attention_paged_shared_kv8", q_out, k_pool, block_table, pos, family, shared, pack, max_len,
+                                     return_fp16)
+
+
+def decode_attention_paged_shared_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor,
+                                      v_scale: torch.Tensor, block_table: torch.Tensor, pos: torch.Tensor, family: torch.Tensor,
+                                      shared: torch.Tensor, pack: int, scale: float, max_len: Optional[int] = None,
+                                      return_fp16: bool = False):
+    """decode_attention_paged_shared over an int8 pool: every row bit for bit decode_attention_paged_kv8's."""
+    if _compiling(q_out, k_pool, v_pool, k_scale, v_scale, block_table, pos, family, shared):
+        out = _decode_attn_paged_shared_kv8_op(q_out, k_pool, v_pool, k_scale, v_scale, block_table, pos, family, shared, pack, scale,
+                                               max_len, return_fp16)
+    else:
+        out = _decode_attention_paged_shared_impl(q_out, k_pool, v_pool, block_table, pos, family, shared, pack, scale, max_len,
+                                                  return_fp16, k_scale, v_scale)
+    return out if return_fp16 else out[:2]
+
+
+def decode_attention_shared_plan(b: int, h: int, kvh: int, max_len: int, pack: int):
+    """(splits, chunk) of a decode_attention_paged_shared call on the current device: split s covers keys s * chunk ... (s + 1) * chunk - 1
+    and is taken jointly by siblings that share at least (s + 1) * chunk keys."""
+    import ctypes
+
+    L = _lib.lib()
+    splits, chunk = ctypes.c_int(0), ctypes.c_int(0)
+    _raise_lib("decode_attention_shared_plan", L.qqq_decode_attn_shared_plan(int(b), int(h), int(kvh), int(max_len), int(pack),
+                                                                             ctypes.byref(splits), ctypes.byref(chunk)))
+    return splits.value, chunk.value
+
+
 # ---- the paged prefill attention (include/qqq_amd_prefill.h): any mix of prompts, chunks and decoding rows of a packed batch in one call,
 # K and V read in place through the block table.
 

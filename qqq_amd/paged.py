@@ -3,12 +3,15 @@ with per-sequence lengths, and the per-step metadata the paged ops read (ops.rop
 prefill_attention_paged and their _kv8 forms).
 
     PagedKVCache   k[layer], v[layer] of shape [num_blocks, num_kv_heads, block_size, head_dim] (fp16 or int8; an int8 pool with
-                   k_scale[layer], v_scale[layer] [num_blocks, num_kv_heads, block_size]); add / free / reserve / step / advance / gather
+                   k_scale[layer], v_scale[layer] [num_blocks, num_kv_heads, block_size]); add / fork / free / reserve / step / advance /
+                   gather
     PagedStep      what one forward pass over a packed batch of sequences needs, built once on the host and shared by all layers
 
 Sequences arrive and finish at different times, have different lengths, and a finished sequence's blocks serve the next one.  The allocator
-keeps no reference counts: sharing the blocks of a common prompt between rows is a property of the ops (a block table may name any
-block), not of this class.
+counts the owners of every block: fork() makes a sequence that shares the full blocks of another one (the n completions of one prompt),
+and a shared block returns to the free list with its last owner.  Only full blocks are shared, so no write ever lands in one.  The
+sequences forked from one prompt are a family; a decode step over adjacent siblings says so in PagedStep.family / shared / family_max,
+which ops.decode_attention_paged_shared reads.  The ops themselves need none of this: a block table may name any block.
 """
 from __future__ import annotations
 
@@ -26,7 +29,11 @@ class PagedStep:
     Device tensors: pos int64 [m] and slots int64 [m] per token (m = sum(counts)); block_table int32 [b, W] (row i: the blocks of
     sequence i, padded with 0) and last_pos int64 [b] (the position of each sequence's last token) per sequence; cu_tokens int32 [b + 1]
     (sequence i owns tokens cu_tokens[i] ... cu_tokens[i + 1] - 1 of the packed batch) and start_pos int64 [b] (= starts), which
-    ops.prefill_attention_paged reads."""
+    ops.prefill_attention_paged reads.
+    Families (None unless the step is a decode step in which at least two adjacent sequences were forked from one prompt): family int32
+    [b] (the index within the step of the first row of row i's family; a lone row names itself), shared int64 [b] (the leading keys a row
+    has in common with its family -- a multiple of the block size, the family's minimum, the same on all its rows; 0 for a lone row) and
+    family_max (host: the largest family of the step)."""
     seq_ids: List
     counts: List[int]
     starts: List[int]
@@ -38,6 +45,9 @@ class PagedStep:
     last_pos: torch.Tensor
     cu_tokens: Optional[torch.Tensor] = None
     start_pos: Optional[torch.Tensor] = None
+    family: Optional[torch.Tensor] = None
+    shared: Optional[torch.Tensor] = None
+    family_max: Optional[int] = None
 
 
 class PagedKVCache:
@@ -68,6 +78,9 @@ class PagedKVCache:
         self._free: List[int] = list(range(num_blocks - 1, -1, -1))  # a stack: block 0 goes out first, a freed block is the next one out
         self._blocks: Dict[object, List[int]] = {}
         self._len: Dict[object, int] = {}
+        self._refs: List[int] = [0] * num_blocks  # owners of a block: 0 on the free list, above 1 only for full blocks that fork() shared
+        self._root: Dict[object, object] = {}     # the sequence a family was forked from (a sequence that never forked names itself)
+        self._shared: Dict[object, int] = {}      # leading keys in common with the family: what fork() shared, a multiple of block_size
 
     @property
     def quantized(self) -> bool:
@@ -94,13 +107,64 @@ class PagedKVCache:
         if seq_id in self._blocks:
             raise KeyError(f"PagedKVCache.add: sequence {seq_id!r} exists")
         self._blocks[seq_id], self._len[seq_id] = [], 0
+        self._root[seq_id], self._shared[seq_id] = seq_id, 0
+
+    def _take(self) -> int:
+        blk = self._free.pop()
+        self._refs[blk] = 1
+        return blk
+
+    def fork(self, src, dst) -> None:
+        """Admit `dst` as a copy of `src` at its present length: it shares src's len // block_size full blocks (one more owner each) and,
+        where the length is no multiple of block_size, takes one fresh block that receives a copy of src's partial block in every layer
+        (k, v and an int8 pool's scales).  Blocks src has reserved beyond its length stay src's alone.  dst joins src's family, with
+        shared_keys() the full blocks' keys (for a fork of a fork, no more than its source shares with the root).  Raises, and changes
+        nothing, if dst exists or src does not (KeyError) or the pool cannot supply the block (RuntimeError)."""
+        if dst in self._blocks:
+            raise KeyError(f"PagedKVCache.fork: sequence {dst!r} exists")
+        if src not in self._blocks:
+            raise KeyError(f"PagedKVCache.fork: no sequence {src!r}")
+        n, bs = self._len[src], self.block_size
+        full = n // bs
+        if n % bs and not self._free:
+            raise RuntimeError("PagedKVCache.fork: the pool is exhausted (1 block needed, 0 free)")
+        mine = self._blocks[src][:full]
+        for blk in mine:
+            self._refs[blk] += 1
+        if n % bs:
+            old, new = self._blocks[src][full], self._take()
+            pools = self.k + self.v + ((self.k_scale + self.v_scale) if self.quantized else [])
+            for pool in pools:
+                pool[new].copy_(pool[old])
+            mine.append(new)
+        self._blocks[dst], self._len[dst] = mine, n
+        self._root[dst] = self._root[src]
+        # what a sequence has in common with its root's keys bounds what any two of a family have in common: a fork of the root shares
+        # up to the fork, a fork of a fork no more than its source did
+        if self._root[src] == src:
+            self._shared[dst] = full * bs
+            self._shared[src] = max(self._shared[src], full * bs)
+        else:
+            self._shared[dst] = min(full * bs, self._shared[src])
+
+    def root(self, seq_id):
+        """The sequence this one's family was forked from (itself, if it never took part in a fork)."""
+        return self._root[seq_id]
+
+    def shared_keys(self, seq_id) -> int:
+        """The leading keys, a multiple of block_size, that the sequence has in common with its family (0 without a fork)."""
+        return self._shared[seq_id]
 
     def free(self, seq_id) -> None:
-        """Drop a sequence; its blocks go back to the free list (the last one it took is the first to go out again)."""
+        """Drop a sequence; its blocks go back to the free list (the last one it took is the first to go out again), a shared block only
+        with its last owner."""
         if seq_id not in self._blocks:
             raise KeyError(f"PagedKVCache.free: no sequence {seq_id!r}")
-        self._free.extend(self._blocks.pop(seq_id))
-        del self._len[seq_id]
+        for blk in self._blocks.pop(seq_id):
+            self._refs[blk] -= 1
+            if self._refs[blk] == 0:
+                self._free.append(blk)
+        del self._len[seq_id], self._root[seq_id], self._shared[seq_id]
 
     def length(self, seq_id) -> int:
         return self._len[seq_id]
@@ -118,7 +182,7 @@ class PagedKVCache:
         if need > len(self._free):
             raise RuntimeError(f"PagedKVCache.reserve: the pool is exhausted ({need} blocks needed, {len(self._free)} free)")
         for _ in range(need):
-            self._blocks[seq_id].append(self._free.pop())
+            self._blocks[seq_id].append(self._take())
 
     def advance(self, seq_id, n: int) -> None:
         """Add `n` keys that were written on the device (through the sequence's block table, by a loop the host did not follow token by
@@ -151,7 +215,7 @@ class PagedKVCache:
         for sid, c, n in zip(seq_ids, counts, need):
             mine = self._blocks[sid]
             for _ in range(n):
-                mine.append(self._free.pop())
+                mine.append(self._take())
             start = self._len[sid]
             starts.append(start)
             for p in range(start, start + c):
@@ -165,10 +229,29 @@ class PagedKVCache:
         cu = [0]
         for c in counts:
             cu.append(cu[-1] + c)
-        return PagedStep(seq_ids=seq_ids, counts=counts, starts=starts, max_len=max(last) + 1, decode=all(c == 1 for c in counts),
+        decode = all(c == 1 for c in counts)
+        fam = self._families(seq_ids) if decode else None
+        family, shared, family_max = fam if fam else (None, None, None)
+        return PagedStep(seq_ids=seq_ids, counts=counts, starts=starts, max_len=max(last) + 1, decode=decode,
                          pos=torch.tensor(pos, dtype=torch.int64).to(dev), slots=torch.tensor(slots, dtype=torch.int64).to(dev),
                          block_table=torch.tensor(table, dtype=torch.int32).to(dev), last_pos=torch.tensor(last, dtype=torch.int64).to(dev),
-                         cu_tokens=torch.tensor(cu, dtype=torch.int32).to(dev), start_pos=torch.tensor(starts, dtype=torch.int64).to(dev))
+                         cu_tokens=torch.tensor(cu, dtype=torch.int32).to(dev), start_pos=torch.tensor(starts, dtype=torch.int64).to(dev),
+                         family=None if family is None else torch.tensor(family, dtype=torch.int32).to(dev),
+                         shared=None if shared is None else torch.tensor(shared, dtype=torch.int64).to(dev), family_max=family_max)
+
+    def _families(self, seq_ids):
+        """(family, shared, family_max) of a decode step, or None where no two adjacent sequences have one root."""
+        family, shared, i, largest = [], [], 0, 1
+        while i < len(seq_ids):
+            j = i + 1
+            while j < len(seq_ids) and self._root[seq_ids[j]] == self._root[seq_ids[i]]:
+                j += 1
+            common = min(self._shared[sid] for sid in seq_ids[i:j]) if j - i > 1 else 0
+            family += [i] * (j - i)
+            shared += [common] * (j - i)
+            largest = max(largest, j - i)
+            i = j
+        return (family, shared, largest) if largest > 1 else None
 
     # ---- reading a sequence back (plain torch; CPU tensors too)
 

@@ -58,6 +58,10 @@ class DecodeLoop:
                 n_prompt, repetition, presence, frequency and the op's workspace -- and its step runs that op between the forward and the
                 sampler, inside the captured graph; generate() then takes repetition_penalty, presence_penalty and frequency_penalty.
                 A row whose three values are 1, 0 and 0 rides through it with its logits untouched.  False: none of that exists.
+    family      N > 1 (parallel sampling): rows [k * N, (k + 1) * N) are a fixed slot for the N completions of one prompt, rows % N == 0.  The
+                loop then owns `family_of` (int32 [rows], constant: a row's slot's first row) and `shared` (int64 [rows]: the keys a row has
+                in common with its siblings, written on admission, 0 when idle) inside its PagedStep, as part of the captured graph: a model
+                with fuse_shared() reads a family's common keys once per pack of rows.  generate() then returns N lists per prompt.
     `captures` counts the captures: 1 for the life of the loop with graph=True.  The graph holds addresses: a model that is changed after
     the first generate() (fuse_*(), load_state_dict, .to()) needs a new loop."""
 
@@ -66,13 +70,17 @@ class DecodeLoop:
     _tokens = "out"                  # the array a finished row's tokens are read from
     _synced = ("n_out", "remaining")  # what a sync transfers
     _idle = (("remaining", 0), ("pos", -1), ("slots", -1), ("ids", 0))  # what the cleanup resets
+    family = 1                       # rows per slot: the completions of one prompt (DecodeLoop alone takes more than 1)
     penalties = False                # True: the step runs ops.penalize_logits in front of the sampler (_allocate_penalties)
 
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, sync_every: int = 8, u_stride: int = 64, graph: bool = True,
-                 penalties: bool = False):
-        rows, max_len, sync_every, u_stride = int(rows), int(max_len), int(sync_every), int(u_stride)
+                 penalties: bool = False, family: int = 1):
+        rows, max_len, sync_every, u_stride, family = int(rows), int(max_len), int(sync_every), int(u_stride), int(family)
         short = u_stride < sync_every and f"u_stride={u_stride} must cover the sync_every={sync_every} steps between two refills"
         dev = _check_loop("DecodeLoop", lm, cache, rows, max_len, sync_every, graph, short)
+        if family < 1 or rows % family:
+            raise ValueError(f"DecodeLoop: family={family} must be at least 1 and divide rows={rows}")
+        self.family = family
         self._allocate(lm, cache, rows, max_len, sync_every, u_stride, graph, dev)
         self.out = torch.zeros((rows, max_len), dtype=torch.int64, device=dev)
         if penalties:  # this loop keeps no history of its own: the penalty op records a row's input token at its position
@@ -81,6 +89,10 @@ class DecodeLoop:
         self.step = PagedStep(seq_ids=[None] * rows, counts=[1] * rows, starts=[0] * rows, max_len=max_len, decode=True, pos=self.pos,
                               slots=self.slots, block_table=self.block_table, last_pos=self.pos,
                               cu_tokens=torch.arange(rows + 1, dtype=torch.int32, device=dev), start_pos=self.pos)
+        if family > 1:  # the slots are fixed: what changes from prompt to prompt is `shared`
+            self.family_of = (torch.arange(rows, dtype=torch.int32, device=dev) // family) * family
+            self.shared = torch.zeros(rows, dtype=torch.int64, device=dev)
+            self.step.family, self.step.shared, self.step.family_max = self.family_of, self.shared, family
 
     def _allocate(self, lm, cache, rows, max_len, sync_every, u_stride, graph, dev):
         """The attributes and state arrays every loop has, for rows of `self.group` tokens: [rows] at 1, [rows, group] beyond."""
@@ -199,6 +211,11 @@ class DecodeLoop:
         first decode step of the call and then per u_stride decode steps, so equally seeded generators give equal tokens whatever the
         loop served before.
 
+        A loop built with family=N > 1 returns N completions per prompt (a list of N lists).  A prompt is admitted when a whole slot of N
+        rows is idle and the pool covers the family: the prompt's budget once and, per further sibling, the blocks beyond the prompt's
+        full ones.  It is prefilled once; its N first tokens are N draws from the one logits row (one torch.rand of admitted prompts * N
+        per prefill pass), and the siblings that go on are made with PagedKVCache.fork and reserve.
+
         SpecDecodeLoop: the budget is len(prompt) + max_new_tokens - 1 + draft_len keys per sequence (reserved at once; the same sum must
         not exceed max_len).  The host writes an admitted row's history (the prompt and its first token) and first drafts (ngram_draft);
         everything after that happens on the device.  u is refilled whenever it is used up; a step uses draft_len + 1 variates per row,
@@ -219,10 +236,15 @@ class DecodeLoop:
         prompts = [list(p) for p in prompts]
         if any(not p for p in prompts):
             raise ValueError(f"{name}: every prompt needs at least one token")
-        outs: List[List[int]] = [[] for _ in prompts]
+        fam = self.family
+        outs: List[List[int]] = [[] for _ in range(len(prompts) * fam)]  # per sibling: prompt i's are i * fam ... i * fam + fam - 1
+
+        def result():
+            return outs if fam == 1 else [outs[i * fam:(i + 1) * fam] for i in range(len(prompts))]
+
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1 or not prompts:
-            return outs
+            return result()
         extra, new_words, parts = self._budget_words(max_new_tokens)
         keys = [len(p) + max_new_tokens - 1 + extra for p in prompts]
         for p, k in zip(prompts, keys):
@@ -236,7 +258,9 @@ class DecodeLoop:
         tag = object()  # sequence ids no other user of the cache can hold
         sid = lambda i: (tag, i)  # noqa: E731
         waiting = deque(range(len(prompts)))
-        owner: List[Optional[int]] = [None] * self.rows  # the prompt each row serves
+        owner: List[Optional[int]] = [None] * self.rows  # the sequence (prompt * fam + sibling) each row serves
+        # the blocks a prompt's family takes: its budget once plus, per further sibling, the blocks beyond the prompt's full ones
+        blocks = [-(-k // bs) + (fam - 1) * (-(-k // bs) - len(p) // bs) for p, k in zip(prompts, keys)]
         budget = [0] * self.rows                         # an upper bound of the row's `remaining`, and so of the steps it still takes
         per_row = dict(remaining=max_new_tokens - 1, eos=eos, n_out=0, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p))
         if self.penalties:
@@ -244,44 +268,60 @@ class DecodeLoop:
 
         def admit():
             new = []
-            idle = [r for r in range(self.rows) if owner[r] is None]
+            idle = [r for r in range(0, self.rows, fam) if all(o is None for o in owner[r:r + fam])]  # the first rows of idle slots
+            pending = 0  # blocks the siblings of this round's prompts take once they are forked
             while waiting and idle:
                 i = waiting[0]
-                if -(-keys[i] // bs) > cache.free_blocks:
+                if blocks[i] > cache.free_blocks - pending:
                     break
                 waiting.popleft()
-                cache.add(sid(i))
-                cache.reserve(sid(i), keys[i])
-                owner[idle[0]] = i
+                cache.add(sid(i * fam))
+                cache.reserve(sid(i * fam), keys[i])
+                pending += blocks[i] - -(-keys[i] // bs)
+                owner[idle[0]] = i * fam
                 new.append((idle.pop(0), i))
             if not new:
                 if waiting and all(o is None for o in owner):
                     raise RuntimeError(f"{name}: the pool's {cache.free_blocks} free blocks cannot hold a prompt that needs "
-                                       f"{-(-keys[waiting[0]] // bs)} ({parts})")
+                                       f"{blocks[waiting[0]]} ({parts})")
                 return
             # the packed prefill of the admitted prompts (eager, the existing step) and their first tokens
-            seqs = [sid(i) for _, i in new]
+            seqs = [sid(i * fam) for _, i in new]
             ids = torch.tensor([t for _, i in new for t in prompts[i]], dtype=torch.int64, device=dev)
             logits = self.lm(ids, cache, cache.step(seqs, [len(prompts[i]) for _, i in new]))
+            born = [(r + j, i * fam + j) for r, i in new for j in range(fam)]  # (row, sequence) of every sibling
+            if fam > 1:  # a prompt's row serves the first draw of each of its siblings
+                logits = logits.repeat_interleave(fam, dim=0)
             if penalised:  # over the prompt: its last token sits at index len - 1 and every index is a prompt index
-                lens = [len(prompts[i]) for _, i in new]
-                seen = torch.tensor([prompts[i] + [-1] * (max(lens) - len(prompts[i])) for _, i in new], dtype=torch.int32).to(dev)
+                lens = [len(prompts[q // fam]) for _, q in born]
+                seen = torch.tensor([prompts[q // fam] + [-1] * (max(lens) - len(prompts[q // fam])) for _, q in born],
+                                    dtype=torch.int32).to(dev)
                 at_last = torch.tensor([n - 1 for n in lens], dtype=torch.int64, device=dev)
-                ops.penalize_logits(logits, torch.tensor([prompts[i][-1] for _, i in new], dtype=torch.int64, device=dev), at_last, seen,
-                                    torch.tensor(lens, dtype=torch.int32, device=dev), *penalty, self.penalty_workspace)
-            u = torch.rand(len(new), generator=generator, device=dev)
+                ops.penalize_logits(logits, torch.tensor([prompts[q // fam][-1] for _, q in born], dtype=torch.int64, device=dev), at_last,
+                                    seen, torch.tensor(lens, dtype=torch.int32, device=dev), *penalty, self.penalty_workspace)
+            u = torch.rand(len(born), generator=generator, device=dev)
             first = ops.sample_tokens(logits, temperature, top_k, top_p, u).tolist()
-            rows, state = [], {}
-            for (r, i), t in zip(new, first):
-                outs[i].append(t)
+            rows, state, ended = [], {}, []
+            for (r, q), t in zip(born, first):
+                outs[q].append(t)
                 if max_new_tokens == 1 or t == eos:
-                    cache.free(sid(i))
-                    owner[r] = None
+                    if q % fam == 0:
+                        ended.append((r, q))  # its siblings are forked from it first
                     continue
+                prompt = prompts[q // fam]
+                if q % fam:  # a sibling that goes on: the prompt's full blocks in common, the rest of its budget its own
+                    cache.fork(sid(q - q % fam), sid(q))
+                    owner[r] = q
+                    cache.reserve(sid(q), keys[q // fam])
                 rows.append(r)
-                for array, value in self._row_state(prompts[i], t, cache.blocks(sid(i))).items():
+                for array, value in self._row_state(prompt, t, cache.blocks(sid(q))).items():
                     state.setdefault(array, []).append(value)
+                if fam > 1:
+                    state.setdefault("shared", []).append(len(prompt) // bs * bs)
                 budget[r] = max_new_tokens - 1
+            for r, q in ended:
+                cache.free(sid(q))
+                owner[r] = None
             if not rows:
                 return
             at = torch.tensor(rows, dtype=torch.int64, device=dev)
@@ -306,21 +346,24 @@ class DecodeLoop:
                 for r in active:
                     budget[r] = remaining[r]
                 if done:
-                    toks = getattr(self, self._tokens)[torch.tensor(done, dtype=torch.int64, device=dev)].tolist()
+                    at_done = torch.tensor(done, dtype=torch.int64, device=dev)
+                    toks = getattr(self, self._tokens)[at_done].tolist()
                     for r, row in zip(done, toks):
                         i = owner[r]
-                        outs[i].extend(self._collect(row, len(prompts[i]), sid(i), {a: v[r] for a, v in synced.items()}))
+                        outs[i].extend(self._collect(row, len(prompts[i // fam]), sid(i), {a: v[r] for a, v in synced.items()}))
                         cache.free(sid(i))
                         owner[r] = None
+                    if fam > 1:
+                        self.shared[at_done] = 0
         except BaseException:
             # leave the loop idle and the caller's pool as it was found
             for i in owner:
                 if i is not None:
                     cache.free(sid(i))
-            for array, value in self._idle:
+            for array, value in self._idle + ((("shared", 0),) if fam > 1 else ()):
                 getattr(self, array).fill_(value)
             raise
-        return outs
+        return result()
 
 
 def ngram_draft(history: Sequence[int], draft_len: int, ngram_max: int = 3) -> List[int]:
@@ -376,8 +419,11 @@ class SpecDecodeLoop(DecodeLoop):
     _idle = DecodeLoop._idle + (("start", -1),)
 
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, draft_len: int = 4, ngram_max: int = 3, sync_every: int = 8,
-                 u_stride: Optional[int] = None, graph: bool = True, penalties: bool = False):
+                 u_stride: Optional[int] = None, graph: bool = True, penalties: bool = False, family: int = 1):
         rows, max_len, sync_every, draft_len, ngram_max = int(rows), int(max_len), int(sync_every), int(draft_len), int(ngram_max)
+        if int(family) != 1:
+            raise ValueError(f"SpecDecodeLoop: family={family} is not supported (a chunk of draft_len + 1 tokens per row has no "
+                             f"shared-prefix kernel); DecodeLoop takes families")
         if draft_len < 1 or draft_len > 15 or ngram_max < 1 or ngram_max > 4:
             raise ValueError(f"SpecDecodeLoop: draft_len={draft_len} must be in [1, 15] and ngram_max={ngram_max} in [1, 4]")
         group = draft_len + 1

@@ -35,6 +35,17 @@ KV cache.  Both paths start from the fp16 output of input_layernorm and end with
                 Shapes as above, b in {1, 16}, contexts {256, 4096, 16384} where the pool fits VERIFY_POOL_BYTES, T in {3, 5, 8}.
                 `faster_than_prefill` says whether the verify median is below the prefill median by more than the latter's spread.
 
+    shared      (--points shared [--kv8] [--block-size N]: this mode alone) the decode attention op of one family of N sibling rows alone,
+                two ways over the same pool and the same forked block tables: decode_attention_paged_shared(_kv8) with pack = min(N,
+                64 // (h / kvh)), and decode_attention_paged(_kv8) over the aliased tables (the baseline: every row reads the prefix's
+                blocks for itself, from wherever the caches hold them).  Shapes as above, N in {2, 4, 8, 16}, prefixes of {1024, 4096,
+                16384} shared keys and a private tail of SHARED_TAIL keys per row.  Two protocols, alternately, SHARED_ROUNDS times: `warm`
+                (hipGraph replay back to back, tools/bench_llama.time_fn: the pools stay in whatever cache holds them) and `cold` (one
+                captured call per timing, each behind a write of SHARED_FLUSH_BYTES that evicts the L2s and the Infinity Cache; median of
+                SHARED_COLD_CALLS).  Every round is kept, with median, min and max; `shared_over_plain` per protocol, and `wins` / `loses`
+                where the medians differ by more than the baseline's spread over the rounds.  The split plan of the call and the number of
+                jointly taken splits are written too.
+
 Points: decode (s = 1) at b in {1, 16} with a context of {1024, 4096} tokens (the new token included), and b = 1 at 16384; prefill of s in
 {128, 1024, 4096} tokens at b = 1 from position 0.  Before each point one dynamic_quant of POINT_MARK + i rows is launched: its grid marks
 where point i starts in a kernel trace.
@@ -42,6 +53,7 @@ where point i starts in a kernel trace.
     python tools/bench_attn.py [--points decode,prefill] [--kv8] [--out FILE]   -> one JSON object on stdout
     python tools/bench_attn.py --points prefill --paged [--kv8] [--block-size N] [--out FILE]   -> the paged prefill points alone
     python tools/bench_attn.py --points verify [--kv8] [--block-size N] [--out profiles/verify_attn_bench.json]   -> the verify points alone
+    python tools/bench_attn.py --points shared [--kv8] [--block-size N] [--out profiles/shared_attn_bench.json]   -> the shared points alone
     python tools/bench_attn.py --summarize TRACE_DIR [--bench FILE]     -> from a rocprofv3 --kernel-trace run of the above: the
                                                                           qqq_rope_qkv_kernel times and HBM fractions, and per decode point
                                                                           (labelled from the run's JSON output FILE) the median times of
@@ -80,6 +92,9 @@ PAGED_PREFILL = [("1x2048", [(0, 2048)]), ("8x512", [(0, 512)] * 8), ("chunk512@
 VERIFY_ROUNDS = 5  # --points verify: alternations of the three ops at a point
 VERIFY_CONTEXTS, VERIFY_TOKENS, VERIFY_BATCHES = (256, 4096, 16384), (3, 5, 8), (1, 16)
 VERIFY_POOL_BYTES = 8 << 30  # K and V pools of a point together
+SHARED_ROUNDS, SHARED_COLD_CALLS = 5, 9  # --points shared: alternations of the two ops at a point; cold calls per alternation
+SHARED_FAMILIES, SHARED_PREFIXES, SHARED_TAIL = (2, 4, 8, 16), (1024, 4096, 16384), 64
+SHARED_FLUSH_BYTES = 1 << 30  # four times the 256 MB Infinity Cache
 PREFILL_KERNELS = ("qqq_prefill_attn_kernel", "qqq_prefill_quant_kernel", "qqq_paged_rope_qkv_kernel", "qqq_paged_kv8_rope_qkv_kernel",
                    "qqq_dynamic_quant_kernel")
 SPLIT_KERNELS = ("qqq_decode_split_kernel", "qqq_kv8_decode_split_kernel", "qqq_paged_decode_split_kernel",
@@ -501,6 +516,102 @@ def _run_verify(kv8, block_size):
     return out
 
 
+def run_shared(kv8=False, block_size=128):
+    """--points shared: see the module docstring; --kv8 adds the int8 pool's points behind the fp16 pool's"""
+    out = _run_shared(False, block_size)
+    if kv8:
+        out["pool"] = "fp16, then int8"
+        out["points"] += _run_shared(True, block_size)["points"]
+    return out
+
+
+def _time_cold(torch, fn, flush, calls):
+    """median us of single captured calls of fn, each behind a write that evicts the caches"""
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=side):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(calls)]
+    for a, b in ev:
+        flush.add_(1)
+        a.record()
+        graph.replay()
+        b.record()
+    torch.cuda.synchronize()
+    return _median([a.elapsed_time(b) * 1e3 for a, b in ev])
+
+
+def _run_shared(kv8, block_size):
+    import statistics
+
+    import torch
+
+    from bench_llama import time_fn
+    from qqq_amd import ops
+
+    dev = torch.device("cuda:0")
+    out = {"tool": "tools/bench_attn.py --points shared", "device": torch.cuda.get_device_name(0), "head_dim": D, "block_size": block_size,
+           "pool": "int8" if kv8 else "fp16", "rounds": SHARED_ROUNDS, "private_tail_keys": SHARED_TAIL,
+           "unit": "us per call of the attention op alone; warm: hipGraph replay back to back; cold: one captured call behind a cache "
+                   "flush, median of %d; per op and protocol the rounds, their median, min and max" % SHARED_COLD_CALLS, "points": []}
+    g = torch.Generator(device=dev).manual_seed(11)
+    flush = torch.zeros(SHARED_FLUSH_BYTES // 4, dtype=torch.int32, device=dev)
+    plain = ops.decode_attention_paged_kv8 if kv8 else ops.decode_attention_paged
+    joint = ops.decode_attention_paged_shared_kv8 if kv8 else ops.decode_attention_paged_shared
+    for shape, (h, kvh) in SHAPES.items():
+        for prefix in SHARED_PREFIXES:
+            for n in SHARED_FAMILIES:
+                ctx = prefix + SHARED_TAIL  # keys of a row, its newest included
+                width, common = -(-ctx // block_size), prefix // block_size
+                nb = common + n * (width - common)
+                if kv8:
+                    pools = tuple(torch.randint(-127, 128, (nb, kvh, block_size, D), generator=g, device=dev, dtype=torch.int8)
+                                  for _ in range(2))
+                    pools += tuple(torch.rand((nb, kvh, block_size), generator=g, device=dev) * 0.02 + 0.005 for _ in range(2))
+                else:
+                    pools = tuple(torch.randn((nb, kvh, block_size, D), generator=g, device=dev).half() for _ in range(2))
+                perm = torch.randperm(nb, generator=torch.Generator().manual_seed(prefix + n))
+                table = torch.empty((n, width), dtype=torch.int32)
+                table[:, :common] = perm[:common]
+                table[:, common:] = perm[common:].reshape(n, width - common)
+                table = table.to(dev)
+                pos = torch.full((n,), ctx - 1, dtype=torch.int64, device=dev)
+                family = torch.zeros(n, dtype=torch.int32, device=dev)
+                shared = torch.full((n,), common * block_size, dtype=torch.int64, device=dev)
+                pack = min(n, 64 // (h // kvh))
+                q = torch.randn((n, h, D), generator=g, device=dev).half()
+                fns = {"plain": lambda: plain(q, *pools, table, pos, D ** -0.5, max_len=ctx),
+                       "shared": lambda: joint(q, *pools, table, pos, family, shared, pack, D ** -0.5, max_len=ctx)}
+                a, b_ = fns["plain"](), fns["shared"]()
+                assert torch.equal(a[0], b_[0]) and torch.equal(a[1], b_[1]), "the two ops must agree bit for bit"
+                splits, chunk = ops.decode_attention_shared_plan(n, h, kvh, ctx, pack)
+                runs = {(name, mode): [] for name in fns for mode in ("warm", "cold")}
+                for _ in range(SHARED_ROUNDS):
+                    for name, fn in fns.items():
+                        runs[(name, "warm")].append(round(time_fn(fn), 2))
+                        runs[(name, "cold")].append(round(_time_cold(torch, fn, flush, SHARED_COLD_CALLS), 2))
+                pt = {"shape": shape, "pool": "int8" if kv8 else "fp16", "heads": h, "kv_heads": kvh, "family": n, "pack": pack,
+                      "prefix": prefix, "context": ctx, "splits": splits, "chunk": chunk, "joint_splits": common * block_size // chunk}
+                for mode in ("warm", "cold"):
+                    for name in fns:
+                        v = runs[(name, mode)]
+                        pt[f"{name}_{mode}"] = {"median_us": round(statistics.median(v), 2), "min_us": min(v), "max_us": max(v), "rounds_us": v}
+                    base, new = pt[f"plain_{mode}"], pt[f"shared_{mode}"]
+                    spread = round(base["max_us"] - base["min_us"], 2)
+                    pt[f"shared_over_plain_{mode}"] = round(new["median_us"] / base["median_us"], 3)
+                    pt[f"plain_round_spread_us_{mode}"] = spread
+                    pt[f"verdict_{mode}"] = ("wins" if new["median_us"] < base["median_us"] - spread else
+                                             "loses" if new["median_us"] > base["median_us"] + spread else "ties")
+                out["points"].append(pt)
+                print(json.dumps(pt), file=sys.stderr, flush=True)
+                del pools
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", default="decode,prefill")
@@ -517,6 +628,8 @@ def main():
         res = summarize_prefill(a.summarize, a.bench) if a.paged and a.points == "prefill" else summarize(a.summarize, a.bench)
     elif a.points == "verify":
         res = run_verify(kv8=a.kv8, block_size=a.block_size)
+    elif a.points == "shared":
+        res = run_shared(kv8=a.kv8, block_size=a.block_size)
     elif a.paged and a.points == "prefill":
         res = run_paged_prefill([int(v) for v in a.group_sizes.split(",")], kv8=a.kv8, block_size=a.block_size)
     else:

@@ -40,6 +40,15 @@ the prompt and what it emitted, 128 ... 255 tokens here; the op's time at longer
 (tools/bench_sample.py --penalties).
 
     python tools/bench_generate.py --penalties [--draft-len 0,4] [--batch 1,16] [--rounds 5] [--out profiles/penalty_loop_bench.json]
+
+With --n 1,4,8 the tool measures parallel sampling: per N one prompt of --prompt tokens (default 2048: sixteen 128-key chunks of the decode
+plan) served three ways by a captured DecodeLoop in one rotation -- `repeated`: the prompt N times in N rows (N prefills, N copies of its
+keys); `forked`: DecodeLoop(family=N) without fuse_shared() (one prefill, the prompt's blocks once, the plain paged decode op over the
+aliased tables); `forked_shared`: the same with fuse_shared().  By the protocol above: the time of one replayed step, tokens/s of the N
+rows, and the pool blocks in use at the peak (from the allocator; the saving is exact arithmetic and independent of the kernel).  Sampling
+at temperature 0.8 so that the siblings diverge.  Written to profiles/parallel_sampling_bench.json.
+
+    python tools/bench_generate.py --n 1,4,8 [--prompt 2048] [--rounds 5] [--out profiles/parallel_sampling_bench.json]
 """
 import argparse
 import json
@@ -293,8 +302,104 @@ def penalty_main(args):
             f"{e['plain_round_spread_us']})" for k, e in p["draft_len"].items()))
 
 
+def parallel_point(lm, n, prompt_len, rounds, dev):
+    import torch
+
+    from bench_model import VOCAB
+    from qqq_amd import DecodeLoop
+
+    g = torch.Generator().manual_seed(n)
+    prompt = torch.randint(0, VOCAB, (prompt_len,), generator=g).tolist()
+    per = -(-(prompt_len + NEW - 1) // BS)
+    max_len = per * BS
+    peak = {}
+
+    def watched(cache, name):
+        peak[name] = 0
+        for fn in ("step", "reserve", "fork"):
+            def wrapped(*a, _f=getattr(cache, fn), **kw):
+                out = _f(*a, **kw)
+                peak[name] = max(peak[name], cache.num_blocks - cache.free_blocks)
+                return out
+            setattr(cache, fn, wrapped)
+        return cache
+
+    variants = {}
+    loop = DecodeLoop(lm, watched(lm.new_cache(n * per, BS), "repeated"), rows=n, max_len=max_len, sync_every=SYNC_EVERY)
+    variants["repeated"] = (False, lambda k, loop=loop: loop.generate([prompt] * n, k, temperature=0.8, generator=gen()))
+    for name, fused in (("forked", False), ("forked_shared", True)):
+        if n == 1 and fused:
+            continue
+        (lm.fuse_shared if fused else lm.unfuse_shared)()  # a loop captures its step under its own flag
+        loop = DecodeLoop(lm, watched(lm.new_cache(n * per, BS), name), rows=n, max_len=max_len, sync_every=SYNC_EVERY, family=n)
+        variants[name] = (fused, lambda k, loop=loop: loop.generate([prompt], k, temperature=0.8, generator=gen()))
+
+    def gen():
+        return torch.Generator(device=dev).manual_seed(1234)
+
+    def timed(name, k):
+        fused, f = variants[name]
+        (lm.fuse_shared if fused else lm.unfuse_shared)()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f(k)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    tokens = {}
+    for name in variants:  # warm-up: code objects, workspaces, rope tables, the capture
+        timed(name, 1)
+        tokens[name] = timed(name, NEW)[1]
+    values = {name: [] for name in variants}
+    for _ in range(rounds):
+        for name in variants:
+            short, full = timed(name, 1)[0], timed(name, NEW)[0]
+            values[name].append((full - short) / (NEW - 1) * 1e6)
+    lm.unfuse_shared()
+    res = {"n": n, "prompt_tokens": prompt_len, "new_tokens": NEW, "layers": LAYERS, "block_size": BS,
+           "shared_keys": prompt_len // BS * BS}
+    for name, v in values.items():
+        med = statistics.median(v)
+        res[name] = {"median_us_per_step": round(med, 1), "min_us_per_step": round(min(v), 1), "max_us_per_step": round(max(v), 1),
+                     "rounds_us_per_step": [round(x, 1) for x in v], "tokens_per_s": round(n * 1e6 / med, 1),
+                     "peak_pool_blocks": peak[name]}
+    res["blocks_by_arithmetic"] = {"repeated": n * per, "forked": per + (n - 1) * (per - prompt_len // BS)}
+    if "forked_shared" in res:
+        res["forked_tokens_equal_forked_shared"] = tokens["forked"] == tokens["forked_shared"]
+        base, new = res["forked"], res["forked_shared"]
+        res["forked_over_forked_shared"] = round(base["median_us_per_step"] / new["median_us_per_step"], 3)
+        res["forked_round_spread_us"] = round(base["max_us_per_step"] - base["min_us_per_step"], 1)
+        res["shared_faster_by_more_than_the_spread"] = bool(new["median_us_per_step"] < base["median_us_per_step"] - res["forked_round_spread_us"])
+    res["repeated_over_forked"] = round(res["repeated"]["median_us_per_step"] / res["forked"]["median_us_per_step"], 3)
+    return res
+
+
+def parallel_main(args):
+    import torch
+
+    from bench_model import build
+
+    args.out = args.out or os.path.join(ROOT, "profiles", "parallel_sampling_bench.json")
+    dev = torch.device("cuda:0")
+    lm = build(LAYERS, dev)
+    with torch.no_grad():
+        points = [parallel_point(lm, n, args.prompt, args.rounds, dev) for n in map(int, args.n.split(","))]
+    out = {"tool": "tools/bench_generate.py --n", "device": torch.cuda.get_device_name(0),
+           "shape": "Llama-2-7B layers, per-channel W4A8, fuse_qkv(), paged fp16 cache, block 16, temperature 0.8",
+           "sync_every": SYNC_EVERY, "rounds": args.rounds, "points": points}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"n {p['n']:2d}: " + "  ".join(f"{k} {p[k]['median_us_per_step']:.1f} us/step, {p[k]['peak_pool_blocks']} blocks"
+                                             for k in ("repeated", "forked", "forked_shared") if k in p))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--n", default=None, help="e.g. 1,4,8: measure parallel sampling instead (profiles/parallel_sampling_bench.json)")
+    ap.add_argument("--prompt", type=int, default=2048, help="with --n: tokens of the prompt")
     ap.add_argument("--batch", default="1,16")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--baseline-only", action="store_true", help="time generate() alone (runs on a tree without DecodeLoop)")
@@ -309,6 +414,8 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("bench_generate.py needs a GPU: a timing taken elsewhere says nothing")
+    if args.n:
+        return parallel_main(args)
     if args.penalties:
         return penalty_main(args)
     if args.draft_len:
