@@ -3,9 +3,11 @@ decode_attention_paged(_kv8) called on the same tensors, over both pools, head s
 every size around the pack, shared lengths around the chunk, retired rows anywhere in a pack, senseless descriptors, and hipGraph replay
 with families, shared lengths and positions changed in place.
 
-b <= 24 and max_len = 1024 throughout, so the split plan is eight chunks of 128 keys (asserted through the plan entry point): a family
-with shared >= 128 has shared // 128 jointly taken chunks.  The library entry points are called directly where the workspace and the
-outputs have to be the test's own: the workspace is filled with NaN before each call, the outputs with a sentinel."""
+b <= 24, kvh <= 4 and max_len = 1024 throughout, so the split plan is eight chunks of 128 keys (b * kvh <= 96 leaves at least eight
+planned splits on any device of 192 compute units or more; with a larger kvh the plan has fewer and longer chunks; asserted through the
+plan entry point): a family with shared >= 128 has shared // 128 jointly taken chunks.  The library entry points are called directly
+where the workspace and the outputs have to be the test's own: the workspace is filled with NaN before each call, the outputs with a
+sentinel."""
 import pytest
 import torch
 
@@ -30,25 +32,33 @@ def _pools(dev, g, nb, kvh, bs, d, kv8):
     return (torch.randn((nb, kvh, bs, d), generator=g, device=dev).half(), torch.randn((nb, kvh, bs, d), generator=g, device=dev).half())
 
 
-def _case(dev, g, families, bs, kvh, d, kv8):
+def _case(dev, g, families, bs, kvh, d, kv8, whole_blocks=True):
     """families: [(size, shared, [pos per member])].  Every row gets blocks of its own; the rows of a family then take the first row's
-    ids for their first shared // bs blocks (shared is a multiple of bs here).  -> pools, table, pos, family, shared (device tensors)"""
+    ids for their first shared // bs blocks.  shared is a multiple of bs unless whole_blocks is False: then the block that holds the end
+    of the prefix stays a block of each sibling's own, and its first shared % bs rows are copies of the first row's (what copy-on-write
+    of a partial block leaves).  -> pools, table, pos, family, shared (device tensors)"""
     b = sum(f[0] for f in families)
     width = MAX_LEN // bs
     nb = b * width + 3
     perm = torch.randperm(nb, generator=g, device=dev)
     table = perm[:b * width].reshape(b, width).clone()
-    fam, sh, pos, r = [], [], [], 0
+    fam, sh, pos, r, copies = [], [], [], 0, []
     for size, shared, ps in families:
-        assert shared % bs == 0 and len(ps) == size
+        assert (shared % bs == 0 or not whole_blocks) and len(ps) == size
         for j in range(size):
             table[r + j, :shared // bs] = table[r, :shared // bs]
+            if shared % bs and j:
+                copies.append((int(table[r + j, shared // bs]), int(table[r, shared // bs]), shared % bs))
             fam.append(r)
             sh.append(shared if size > 1 else 0)
         pos += ps
         r += size
     i64 = dict(dtype=torch.int64, device=dev)
-    return (_pools(dev, g, nb, kvh, bs, d, kv8), table.to(torch.int32), torch.tensor(pos, **i64),
+    pools = _pools(dev, g, nb, kvh, bs, d, kv8)
+    for dst, src, n in copies:
+        for t in pools:
+            t[dst, :, :n] = t[src, :, :n]
+    return (pools, table.to(torch.int32), torch.tensor(pos, **i64),
             torch.tensor(fam, dtype=torch.int32, device=dev), torch.tensor(sh, **i64))
 
 
@@ -103,10 +113,10 @@ def _assert_rows_equal(got, want, pos, what, untouched=()):
                 assert bool((g_[r] == (77 if name == "xq" else SENT)).all()), (what, name, r)
 
 
-def _positions(g, size, shared):
+def _positions(g, size, shared, chunk=CHUNK):
     """a member whose last key is the first one behind the prefix (pos = shared), one that has just been forked (pos = shared - 1), one in
     the chunk right behind the prefix, one several chunks later, the rest anywhere behind the prefix"""
-    fixed = [shared, max(shared - 1, 0), shared + 5, min(shared + 3 * CHUNK + 17, MAX_LEN - 1), MAX_LEN - 1]
+    fixed = [shared, max(shared - 1, 0), shared + 5, min(shared + 3 * chunk + 17, MAX_LEN - 1), MAX_LEN - 1]
     rest = [int(torch.randint(shared, MAX_LEN, (1,), generator=g)) for _ in range(max(0, size - len(fixed)))]
     return (fixed + rest)[:size]
 
