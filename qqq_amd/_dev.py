@@ -6,7 +6,7 @@ from __future__ import annotations
 import ctypes
 import os
 
-from . import _lib
+from . import _abi, _lib
 from . import build as _build
 
 _dev = None
@@ -21,26 +21,7 @@ def lib():
     if not os.path.exists(path):
         raise RuntimeError(f"{path} is missing: run `python qqq_amd/build.py` (needs hipcc)")
     L = ctypes.CDLL(path)
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    L.qqq_dev_probe_mfma.argtypes = [ci, vp, vp, vp, ci, vp]
-    L.qqq_dev_probe_mfma.restype = ci
-    L.qqq_dev_probe_glds.argtypes = [vp, vp, vp, ci, vp]
-    L.qqq_dev_probe_glds.restype = ci
-    L.qqq_dev_probe_dequant.argtypes = [vp, vp, vp, vp, ci, ci, vp]
-    L.qqq_dev_probe_dequant.restype = ci
-    L.qqq_dev_probe_fill.argtypes = [vp, ctypes.c_size_t, ctypes.c_size_t, ci, ci, ci, vp, ci, vp, ctypes.POINTER(ctypes.c_float)]
-    L.qqq_dev_probe_fill.restype = ci
-    L.qqq_dev_probe_mfma_rate.argtypes = [ci, vp, ci, ci, vp, ci, vp, ctypes.POINTER(ctypes.c_float)]
-    L.qqq_dev_probe_mfma_rate.restype = ci
-    L.qqq_dev_bench_gemm.argtypes = [vp, vp, ctypes.POINTER(vp), ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp, ci,
-                                     ctypes.POINTER(_lib.QQQTune), ci, ctypes.POINTER(ctypes.c_float)]
-    L.qqq_dev_bench_gemm.restype = ci
-    L.qqq_dev_bench_gemm2.argtypes = [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp, ci,
-                                      ctypes.POINTER(_lib.QQQTune), ci, ctypes.POINTER(ctypes.c_float)]
-    L.qqq_dev_bench_gemm2.restype = ci
-    L.qqq_dev_probe_placement.argtypes = [ctypes.POINTER(ctypes.c_uint32), ci, ci, ci, vp, ci, vp]
-    L.qqq_dev_probe_placement.restype = ci
-    L.qqq_dev_last_error.restype = ctypes.c_char_p
+    _abi.bind(L, _build.header("qqq_amd_dev.h"))
     _dev = L
     return L
 

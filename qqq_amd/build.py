@@ -17,21 +17,7 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_HERE, "csrc", "qqq_w4a8.hip")  # the one translation unit of the operator; it includes csrc/*.hip.h and csrc/qqq_plan.h
 DEV_SRC = os.path.join(_HERE, "csrc", "qqq_dev.hip")
-HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd.h")
-ACT_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_act.h")
-ATTN_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_attn.h")
-DECODE_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_decode.h")
-KV8_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_kv8.h")
-PAGED_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_paged.h")
-PREFILL_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_prefill.h")
-SAMPLE_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_sample.h")
-STEP_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_step.h")
-SCORE_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_score.h")
-SPEC_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_spec.h")
-VERIFY_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_verify.h")
-SHARED_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_shared.h")
-PENALTY_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_penalty.h")
-DEV_HDR = os.path.join(os.path.dirname(_HERE), "include", "qqq_amd_dev.h")
+INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB = os.environ.get("QQQ_AMD_LIB") or os.path.join(_HERE, "libqqq_amd.so")  # override: tuning builds only
 DEV_LIB = os.path.join(_HERE, "libqqq_amd_dev.so")
 ARCH = "gfx950"
@@ -44,6 +30,20 @@ def hipcc_path() -> str:
     raise RuntimeError("hipcc not found: cannot build the gfx950 kernels")
 
 
+def header(name: str) -> str:
+    return os.path.join(INCLUDE, name)
+
+
+def headers() -> list:
+    """every header of the C ABI: one new file under include/ is all a new feature adds here"""
+    return sorted(header(f) for f in os.listdir(INCLUDE) if f.endswith(".h"))
+
+
+def operator_headers() -> list:
+    """the operator library's (libqqq_amd.so): all but the dev companion's"""
+    return [h for h in headers() if h != header("qqq_amd_dev.h")]
+
+
 def _stale(lib: str, extra) -> bool:
     if not os.path.exists(lib):
         return True
@@ -54,8 +54,7 @@ def _stale(lib: str, extra) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(LIB, [HDR, ACT_HDR, ATTN_HDR, DECODE_HDR, KV8_HDR, PAGED_HDR, PREFILL_HDR, SAMPLE_HDR, STEP_HDR, SCORE_HDR, SPEC_HDR,
-                        VERIFY_HDR, SHARED_HDR, PENALTY_HDR])
+    return _stale(LIB, operator_headers())
 
 
 def _compile(src: str, out: str, verbose: bool, flags=()) -> str:
@@ -77,7 +76,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_dev(force: bool = False, verbose: bool = False) -> str:
-    if not force and not _stale(DEV_LIB, [HDR, DEV_HDR]):
+    if not force and not _stale(DEV_LIB, [header("qqq_amd.h"), header("qqq_amd_dev.h")]):
         return DEV_LIB
     return _compile(DEV_SRC, DEV_LIB, verbose)
 
@@ -103,7 +102,7 @@ def build_torch_ext(force: bool = False, verbose: bool = False) -> str:
     default_lib = os.path.join(_HERE, "libqqq_amd.so")
     if not os.path.exists(default_lib):
         raise RuntimeError("build the operator library first (qqq_amd.build.build())")
-    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(TORCH_SRC), os.path.getmtime(HDR), os.path.getmtime(SCORE_HDR)):
+    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(map(os.path.getmtime, (TORCH_SRC, header("qqq_amd.h"), header("qqq_amd_score.h")))):
         return out
     tdir = os.path.dirname(torch.__file__)
     cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",

@@ -18,10 +18,203 @@ def L():
 
 
 def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    hdr = re.sub(r"typedef[^;]*\(\*[^;]*;", "", hdr, flags=re.S)  # function-pointer typedefs are not exports
-    return set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    from qqq_amd import _abi
+
+    return set(_abi.prototypes(os.path.join(ROOT, "include", header)))
+
+
+# ---- the parser the bindings are made with (qqq_amd/_abi.py), on header texts written here
+
+vp, ci, cf, cz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+
+TOY = """\
+/* a header in the style of include/qqq_amd*.h: int toy_commented_out(int x); */
+#ifndef TOY_H_
+#define TOY_H_
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+#define TOY_VERSION 7  /* not 8 */
+typedef struct toy_tune {
+  int a;  /* int hidden; */
+  int b;  // int hidden2;
+} toy_tune_t;
+typedef int (*toy_fn)(const void* A, int n);   /* no export */
+int toy_multi(const void* A, void* argmax /* may be NULL */,
+              int n,   // rows
+              float x,
+              size_t bytes);
+size_t toy_bytes(int rows);
+int  toy_version( void );
+const char *toy_error(void);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+@pytest.fixture
+def toy(tmp_path):
+    p = tmp_path / "toy.h"
+    p.write_text(TOY)
+    return str(p)
+
+
+def test_parser_reads_prototypes_and_nothing_else(toy):
+    from qqq_amd import _abi
+
+    assert _abi.prototypes(toy) == {
+        "toy_multi": ("int", ["const void* A", "void* argmax", "int n", "float x", "size_t bytes"]),  # spans lines, comments inside the list
+        "toy_bytes": ("size_t", ["int rows"]),
+        "toy_version": ("int", []),          # (void)
+        "toy_error": ("const char *", []),
+    }  # neither typedef, nothing from a comment
+    assert _abi.define(toy, "TOY_VERSION") == 7
+    assert _abi.int_fields(toy, "toy_tune") == [("a", ci), ("b", ci)]
+
+
+def test_parser_refuses_what_it_does_not_know(tmp_path):
+    from qqq_amd import _abi
+
+    p = tmp_path / "odd.h"
+    p.write_text("static inline int toy_inline(int x) { return x; }\n")
+    with pytest.raises(RuntimeError, match="not a function prototype"):
+        _abi.prototypes(str(p))
+    p.write_text("typedef struct toy { int a; float b; } toy_t;\n")
+    with pytest.raises(RuntimeError, match="struct toy"):
+        _abi.int_fields(str(p), "toy")
+
+
+@pytest.mark.parametrize("decl, ctype", [
+    ("const void* x", vp), ("void* x", vp), ("int x", ci), ("float x", cf), ("size_t x", cz),
+    ("const qqq_tune_t* x", "tune"), ("qqq_tune_t* x", "tune"), ("int32_t* x", vp),
+    ("double* x", ctypes.POINTER(ctypes.c_double)), ("int* x", ctypes.POINTER(ci)), ("float* x", ctypes.POINTER(cf)),
+    ("const void* const* x", ctypes.POINTER(vp)), ("const uint32_t* x", ctypes.POINTER(ctypes.c_uint32)),
+    ("qqq_gemm_ex_fn x", vp), ("qqq_gemm_ex2_fn x", vp),
+    ("const void *x", vp), ("const void * const * x", ctypes.POINTER(vp)),  # the spelling of the star does not matter
+])
+def test_type_table(decl, ctype):
+    from qqq_amd import _abi, _lib
+
+    assert _abi.ctype_of(decl) is (ctypes.POINTER(_lib.QQQTune) if ctype == "tune" else ctype)
+
+
+@pytest.mark.parametrize("decl", ["long long n", "unsigned n", "int", "const int* x", "void** x", "char x", "int x[4]"])
+def test_unknown_parameter_type_raises_with_header_function_and_parameter(tmp_path, decl):
+    from qqq_amd import _abi
+
+    with pytest.raises(RuntimeError, match="no ctypes type"):
+        _abi.ctype_of(decl)
+    p = tmp_path / "future.h"
+    p.write_text(f"int toy_future(const void* A, {decl});\n")
+
+    class Lib:
+        class toy_future:
+            argtypes = restype = None
+
+    with pytest.raises(RuntimeError) as ei:
+        _abi.bind(Lib, str(p))
+    assert "future.h" in str(ei.value) and "toy_future" in str(ei.value) and f"`{decl}`" in str(ei.value)
+    assert Lib.toy_future.argtypes is None and Lib.toy_future.restype is None  # nothing half-bound
+    p.write_text("long toy_future(int n);\n")
+    with pytest.raises(RuntimeError, match="future.h: toy_future: .*return type `long`"):
+        _abi.bind(Lib, str(p))
+
+
+# ---- the two libraries as bound from the headers
+
+def _headers():
+    return sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
+
+
+OPERATOR_HEADERS = [h for h in _headers() if h != "qqq_amd_dev.h"]
+
+
+@pytest.fixture(scope="module")
+def D():
+    from qqq_amd import _dev, build
+
+    build.build()
+    build.build_dev()
+    return _dev.lib()
+
+
+def test_headers_are_found_by_listing_include():
+    from qqq_amd import build
+
+    inc = os.path.join(ROOT, "include")
+    assert len(_headers()) == 15 and "qqq_amd.h" in OPERATOR_HEADERS
+    assert build.headers() == [os.path.join(inc, h) for h in _headers()]
+    assert build.operator_headers() == [os.path.join(inc, h) for h in OPERATOR_HEADERS]
+
+
+@pytest.mark.parametrize("header", _headers())
+def test_every_declared_function_is_bound_as_declared(L, D, header):
+    from qqq_amd import _abi
+
+    lib = D if header == "qqq_amd_dev.h" else L
+    protos = _abi.prototypes(os.path.join(ROOT, "include", header))
+    assert protos and all(n.startswith("qqq_") for n in protos)
+    for name, (ret, params) in protos.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), name
+        assert fn.restype is {"int": ci, "size_t": cz, "const char*": ctypes.c_char_p}[ret], name
+
+
+def test_signatures_pinned_by_hand(L, D):
+    """every row of the type table on the real headers, written out as the bindings used to be"""
+    from qqq_amd import _lib
+
+    tune, pf = ctypes.POINTER(_lib.QQQTune), ctypes.POINTER(cf)
+    assert L.qqq_decode_attn.argtypes == [vp, vp, vp, vp, cf, vp, vp, vp, vp, cz, ci, ci, ci, ci, ci, ci, ci, vp]
+    assert L.qqq_w4a8_gemm_ex2.argtypes == [vp, vp, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp, ci, ci, ci, ci, tune, vp, vp, vp]
+    assert L.qqq_decode_attn_shared_plan.argtypes == [ci, ci, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)]
+    assert L.qqq_w4a8_plan.argtypes == [ci, ci, ci, ci, ci, ci, ci, tune, tune]
+    assert L.qqq_w4a8_model_us.argtypes == [ci, ci, ci, ci, ci, ctypes.POINTER(ctypes.c_double)]
+    assert D.qqq_dev_probe_fill.argtypes == [vp, cz, cz, ci, ci, ci, vp, ci, vp, pf]
+    assert D.qqq_dev_bench_gemm2.argtypes == [vp, vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ci, vp, vp, vp, vp, vp, ci, ci, ci, vp, ci, ci, vp, ci,
+                                              tune, ci, pf]
+    assert D.qqq_dev_probe_placement.argtypes == [ctypes.POINTER(ctypes.c_uint32), ci, ci, ci, vp, ci, vp]
+    for fn in (L.qqq_decode_attn, L.qqq_w4a8_gemm_ex2, L.qqq_decode_attn_shared_plan, D.qqq_dev_probe_fill, D.qqq_dev_bench_gemm2):
+        assert fn.restype is ci
+    assert L.qqq_decode_attn_workspace_bytes.restype is cz and L.qqq_decode_attn_workspace_bytes.argtypes == [ci] * 5
+    for fn, ret in ((L.qqq_amd_abi_version, ci), (L.qqq_amd_last_error, ctypes.c_char_p), (D.qqq_dev_last_error, ctypes.c_char_p)):
+        assert fn.argtypes == [] and fn.restype is ret
+
+
+def test_tune_struct_and_abi_version_are_the_header_s():
+    from qqq_amd import _lib
+
+    assert _lib.QQQTune._fields_ == [(f, ci) for f in ("kernel", "ksplit", "waves", "fused", "bm", "glds", "pf", "stages", "mt", "pw", "nslots",
+                                                       "split_m", "skew", "w8")]
+    assert _lib.ABI_VERSION == 4
+
+
+def test_the_compiler_checks_every_definition_against_its_prototype():
+    """the two translation units include every header they define, so a definition that disagrees with its prototype does not compile
+    (extern "C": a second declaration with other parameters is an error)"""
+    from qqq_amd import build
+
+    unit = open(build.SRC).read()
+    # qqq_amd.h comes in with the unit's first include, the kernels' common header; the feature headers are included by the unit itself
+    assert '#include "qqq_common.hip.h"' in unit
+    unit += open(os.path.join(os.path.dirname(build.SRC), "qqq_common.hip.h")).read()
+    for h in OPERATOR_HEADERS:
+        assert f'#include "../../include/{h}"' in unit, h
+    assert '#include "../../include/qqq_amd_dev.h"' in open(build.DEV_SRC).read()
+
+
+@pytest.mark.parametrize("header", OPERATOR_HEADERS)
+def test_a_newer_header_rebuilds_the_operator_library(monkeypatch, L, header):
+    from qqq_amd import build
+
+    newer = os.path.join(ROOT, "include", header)
+    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 1.0)
+    assert not build.needs_build()
+    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 3.0 if p == newer else 1.0)
+    assert build.needs_build()
 
 
 def test_exports_every_declared_symbol(L):

@@ -1,7 +1,6 @@
 """Decoder-block activation quantisers without a GPU: the C-ABI of include/qqq_amd_act.h (declared set, exports, argument checks before
 any launch), the kernels' resources in the gfx950 code object, the modules' reference-keyed state-dicts, and the numpy restatement."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -23,9 +22,9 @@ def L():
 
 
 def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    from qqq_amd import _abi
+
+    return set(_abi.prototypes(os.path.join(ROOT, "include", header)))
 
 
 def test_header_declares_the_two_functions_and_the_library_exports_them(L):

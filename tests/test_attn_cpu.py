@@ -3,7 +3,6 @@ kernel's resources in the gfx950 code object, the modules' reference-keyed state
 (tests/attn_ref.py) against transformers when it is installed."""
 import gc
 import os
-import re
 import sys
 import weakref
 
@@ -25,9 +24,9 @@ def L():
 
 
 def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    from qqq_amd import _abi
+
+    return set(_abi.prototypes(os.path.join(ROOT, "include", header)))
 
 
 def test_header_declares_rope_qkv_and_the_library_exports_it(L):

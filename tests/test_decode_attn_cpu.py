@@ -2,7 +2,6 @@
 workspace sizes), the kernels' resources in the gfx950 code object, and the modules' opt-in flag (state-dict, loading, no cycles)."""
 import gc
 import os
-import re
 import sys
 import weakref
 
@@ -22,9 +21,9 @@ def L():
 
 
 def _declared(header):
-    hdr = open(os.path.join(ROOT, "include", header)).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    from qqq_amd import _abi
+
+    return set(_abi.prototypes(os.path.join(ROOT, "include", header)))
 
 
 def test_header_declares_the_two_functions_and_the_library_exports_them(L):

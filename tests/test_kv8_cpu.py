@@ -1,7 +1,6 @@
 """The int8 KV cache without a GPU: the C-ABI of include/qqq_amd_kv8.h (declared set, exports, argument checks before any launch), the two
 kernels' resources in the gfx950 code object, the ops' CPU refusal, and KVCache(dtype=torch.int8): layout, nbytes, dequant."""
 import os
-import re
 import sys
 
 import pytest
@@ -22,9 +21,9 @@ def L():
 
 
 def test_header_declares_the_two_functions_and_the_library_exports_them(L):
-    hdr = open(os.path.join(ROOT, "include", "qqq_amd_kv8.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    from qqq_amd import _abi
+
+    names = set(_abi.prototypes(os.path.join(ROOT, "include", "qqq_amd_kv8.h")))
     assert names == {"qqq_rope_qkv_kv8", "qqq_decode_attn_kv8"}
     for n in names:
         assert hasattr(L, n)

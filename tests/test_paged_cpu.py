@@ -2,7 +2,6 @@
 qqq_paged_* kernels' resources in the gfx950 code object, the ops' CPU refusal and fake implementations, and PagedKVCache on CPU tensors:
 allocation order, step() metadata, exhaustion, free and reuse, gather / dequant, nbytes."""
 import os
-import re
 import sys
 
 import pytest
@@ -24,9 +23,9 @@ def L():
 
 
 def test_header_declares_the_four_functions_and_the_library_exports_them(L):
-    hdr = open(os.path.join(ROOT, "include", "qqq_amd_paged.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    from qqq_amd import _abi
+
+    names = set(_abi.prototypes(os.path.join(ROOT, "include", "qqq_amd_paged.h")))
     assert names == ENTRIES
     for n in names:
         assert hasattr(L, n), n

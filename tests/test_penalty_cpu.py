@@ -3,7 +3,6 @@ include/qqq_amd_penalty.h (declared set, exports, the workspace size, argument c
 resources in the gfx950 code object, the op's refusals and fake implementation, and the bookkeeping of the two loops and of
 QuantLlamaForCausalLM.generate over host stubs of the forward pass and the ops."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -72,18 +71,15 @@ def L():
 
 
 def test_header_declares_the_entries_and_the_library_exports_them(L):
-    from qqq_amd import build
+    from qqq_amd import _abi
 
-    hdr = open(os.path.join(ROOT, "include", "qqq_amd_penalty.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    names = set(_abi.prototypes(os.path.join(ROOT, "include", "qqq_amd_penalty.h")))
     assert names == {"qqq_penalize_logits", "qqq_penalize_logits_workspace_bytes"}
     for n in names:
         assert hasattr(L, n), n
     assert L.qqq_amd_abi_version() == 4
-    main = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "qqq_amd.h")).read(), flags=re.S)
-    assert "qqq_penal" not in main  # the feature has its own header
-    assert build.PENALTY_HDR == os.path.join(ROOT, "include", "qqq_amd_penalty.h")
+    main = _abi.source(os.path.join(ROOT, "include", "qqq_amd.h"))
+    assert "qqq_penal" not in main  # the feature has its own header (a newer one rebuilds the library: tests/test_abi_cpu.py)
 
 
 def test_workspace_bytes(L):

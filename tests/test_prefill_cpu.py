@@ -2,7 +2,6 @@
 launch, the workspace, the NULL no-ops), the qqq_prefill_* kernels' resources in the gfx950 code object, the ops' CPU refusal and fake
 implementations, PagedStep.cu_tokens / start_pos, and fuse_prefill() on the module."""
 import os
-import re
 import sys
 
 import pytest
@@ -22,9 +21,9 @@ def L():
 
 
 def test_header_declares_the_three_functions_and_the_library_exports_them(L):
-    hdr = open(os.path.join(ROOT, "include", "qqq_amd_prefill.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    from qqq_amd import _abi
+
+    names = set(_abi.prototypes(os.path.join(ROOT, "include", "qqq_amd_prefill.h")))
     assert names == ENTRIES
     for n in names:
         assert hasattr(L, n), n

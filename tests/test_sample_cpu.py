@@ -2,7 +2,6 @@
 the NULL no-op), the qqq_sample_* kernel's resources in the gfx950 code object, the op's CPU refusal and fake implementation, and
 tests/sample_ref.py against transformers' logits warpers."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -25,14 +24,14 @@ def L():
 
 
 def test_header_declares_the_entry_and_the_library_exports_it(L):
-    hdr = open(os.path.join(ROOT, "include", "qqq_amd_sample.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    from qqq_amd import _abi
+
+    names = set(_abi.prototypes(os.path.join(ROOT, "include", "qqq_amd_sample.h")))
     assert names == ENTRIES
     for n in names:
         assert hasattr(L, n), n
     assert L.qqq_amd_abi_version() == 4
-    main = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "qqq_amd.h")).read(), flags=re.S)
+    main = _abi.source(os.path.join(ROOT, "include", "qqq_amd.h"))
     assert "qqq_sample" not in main  # the feature has its own header
 
 

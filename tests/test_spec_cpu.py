@@ -4,7 +4,6 @@ before any launch, the NULL no-op), the kernels' resources in the gfx950 code ob
 SpecDecodeLoop's bookkeeping over host stubs."""
 import itertools
 import os
-import re
 import sys
 
 import numpy as np
@@ -171,18 +170,15 @@ def L():
 
 
 def test_header_declares_the_entries_and_the_library_exports_them(L):
-    from qqq_amd import build
+    from qqq_amd import _abi
 
-    hdr = open(os.path.join(ROOT, "include", "qqq_amd_spec.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    names = set(_abi.prototypes(os.path.join(ROOT, "include", "qqq_amd_spec.h")))
     assert names == {"qqq_spec_advance", "qqq_spec_advance_workspace_bytes"}
     for n in names:
         assert hasattr(L, n), n
     assert L.qqq_amd_abi_version() == 4
-    main = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "qqq_amd.h")).read(), flags=re.S)
-    assert "qqq_spec" not in main  # the feature has its own header
-    assert build.SPEC_HDR == os.path.join(ROOT, "include", "qqq_amd_spec.h")
+    main = _abi.source(os.path.join(ROOT, "include", "qqq_amd.h"))
+    assert "qqq_spec" not in main  # the feature has its own header (a newer one rebuilds the library: tests/test_abi_cpu.py)
 
 
 def test_workspace_bytes(L):

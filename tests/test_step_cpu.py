@@ -2,7 +2,6 @@
 slots, the C-ABI of include/qqq_amd_step.h (declared set, exports, argument checks before any launch, the NULL no-op), the kernel's
 resources in the gfx950 code object, and the op's CPU refusal and fake implementation."""
 import os
-import re
 import sys
 
 import numpy as np
@@ -215,14 +214,14 @@ def L():
 
 
 def test_header_declares_the_entry_and_the_library_exports_it(L):
-    hdr = open(os.path.join(ROOT, "include", "qqq_amd_step.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    names = set(re.findall(r"\b(qqq_[a-z0-9_]+)\s*\(", hdr))
+    from qqq_amd import _abi
+
+    names = set(_abi.prototypes(os.path.join(ROOT, "include", "qqq_amd_step.h")))
     assert names == {"qqq_sample_advance"}
     for n in names:
         assert hasattr(L, n), n
     assert L.qqq_amd_abi_version() == 4
-    main = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "qqq_amd.h")).read(), flags=re.S)
+    main = _abi.source(os.path.join(ROOT, "include", "qqq_amd.h"))
     assert "qqq_sample_advance" not in main and "qqq_step" not in main  # the feature has its own header
 
 
