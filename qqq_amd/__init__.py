@@ -34,6 +34,8 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     penalize_logits(logits, ids, pos, seen, n_prompt, repetition, presence, frequency)  # penalties from each row's history, in place, before a sampler
     token_logprobs(logits, targets, return_argmax=True)                             # a target's log-probability and the argmax per logit row, one launch
     QuantLlamaForCausalLM.score / loglikelihood / perplexity, pack_steps            # scoring text over the paged cache; qqq_amd/score.py
+    topk_logprobs(logits, tokens=None, k=0) / topk_logprobs_step(...)               # a token's log-probability and rank and the k most probable
+                                                                                    # tokens per logit row, one launch; generate(logprobs=k)
 """
 from .ops import (  # noqa: F401
     decode_attention,
@@ -62,6 +64,8 @@ from .ops import (  # noqa: F401
     silu_mul_quant,
     spec_advance,
     token_logprobs,
+    topk_logprobs,
+    topk_logprobs_step,
     verify_attention_paged,
     verify_attention_paged_kv8,
     decode_attention_paged_shared,
@@ -72,7 +76,7 @@ from .qlinear import QuantLinear, fuse_quant_linears  # noqa: F401
 from .blocks import QuantLlamaMLP, QuantRMSNorm  # noqa: F401
 from .attention import KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer  # noqa: F401
 from .paged import PagedKVCache, PagedStep  # noqa: F401
-from .model import QuantLlamaForCausalLM, QuantLlamaModel  # noqa: F401
+from .model import QuantLlamaForCausalLM, QuantLlamaModel, TokenLogprobs  # noqa: F401
 from .serve import DecodeLoop, SpecDecodeLoop, ngram_draft  # noqa: F401
 from .score import pack_steps  # noqa: F401
 
@@ -83,4 +87,5 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "prefill_attention_paged_kv8", "PagedKVCache", "PagedStep", "KVCache", "QuantLlamaAttention", "QuantLlamaDecoderLayer",
            "sample_tokens", "QuantLlamaModel", "QuantLlamaForCausalLM", "sample_advance", "DecodeLoop", "token_logprobs", "pack_steps",
            "spec_advance", "SpecDecodeLoop", "ngram_draft", "verify_attention_paged", "verify_attention_paged_kv8", "penalize_logits",
-           "decode_attention_paged_shared", "decode_attention_paged_shared_kv8", "decode_attention_shared_plan"]
+           "decode_attention_paged_shared", "decode_attention_paged_shared_kv8", "decode_attention_shared_plan",
+           "topk_logprobs", "topk_logprobs_step", "TokenLogprobs"]

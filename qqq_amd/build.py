@@ -44,6 +44,12 @@ def operator_headers() -> list:
     return [h for h in headers() if h != header("qqq_amd_dev.h")]
 
 
+def serving_headers() -> list:
+    """the serving headers of the operator library (include/serving/*.h): entry points beside the operator's own, bound behind them"""
+    sub = os.path.join(INCLUDE, "serving")
+    return sorted(os.path.join(sub, f) for f in os.listdir(sub) if f.endswith(".h"))
+
+
 def _stale(lib: str, extra) -> bool:
     if not os.path.exists(lib):
         return True
@@ -54,7 +60,7 @@ def _stale(lib: str, extra) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(LIB, operator_headers())
+    return _stale(LIB, operator_headers() + serving_headers())
 
 
 def _compile(src: str, out: str, verbose: bool, flags=()) -> str:

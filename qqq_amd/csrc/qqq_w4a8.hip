@@ -36,6 +36,7 @@
 //   qqq_prefill.hip.h  paged, ragged, causal prefill attention over the block pools (fp16 and int8) and the quantisation of its rows
 //   qqq_sample.hip.h   the fused token sampler: temperature, top-k, top-p and the draw over a batch of fp16 logit rows, one launch
 //   qqq_score.hip.h    the fused scoring kernel: a target token's log-probability and the argmax per fp16 logit row, one launch (the sampler's weights)
+//   qqq_logprobs.hip.h the fused top-k log-probability kernel: a token's log-probability and rank and the k most probable tokens per row, one launch
 //   qqq_step.hip.h     the decode loop's step: that sampler with an epilogue that advances each row's decode state on the device
 //   qqq_penalty.hip.h  the repetition / presence / frequency penalty: fp16 logit rows rewritten in place from each row's token history, one launch
 //   qqq_spec.hip.h     the speculative decode loop's step: draft_len + 1 draws per row by that sampler, the accept rule and the n-gram drafter
@@ -79,6 +80,8 @@
 #include "../../include/qqq_amd_sample.h"
 #include "qqq_score.hip.h"
 #include "../../include/qqq_amd_score.h"
+#include "qqq_logprobs.hip.h"
+#include "../../include/serving/qqq_amd_logprobs.h"
 #include "qqq_step.hip.h"
 #include "../../include/qqq_amd_step.h"
 #include "qqq_spec.hip.h"
@@ -1354,6 +1357,86 @@ extern "C" int qqq_token_logprobs(const void* logits, int ld, const void* target
                      static_cast<long long*>(argmax), vocab);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_token_logprobs_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- the fused top-k log-probability kernel (include/serving/qqq_amd_logprobs.h; kernels in qqq_logprobs.hip.h): one launch, one workgroup
+// per row, no workspace.  The checks the two entries share: shape, k, and the top-k pair.
+static int topk_logprobs_check(const char* name, const void* logits, int ld, const void* top_ids, const void* top_logprobs, int k, int rows,
+                               int vocab) {
+  if (vocab < 1 || vocab > SMP_MAX_VOCAB || ld < vocab || ld % 8 != 0) {
+    snprintf(g_err, sizeof(g_err), "%s: bad shape vocab=%d ld=%d (need 1 <= vocab <= %d, ld >= vocab, ld %% 8 == 0)", name, vocab, ld,
+             SMP_MAX_VOCAB);
+    return QQQ_ERR_ARG;
+  }
+  if (k < 0 || k > LGP_MAX_K || k > vocab) {
+    snprintf(g_err, sizeof(g_err), "%s: k=%d outside [0, min(%d, vocab=%d)]", name, k, LGP_MAX_K, vocab);
+    return QQQ_ERR_ARG;
+  }
+  if ((k == 0) != (top_ids == nullptr) || (k == 0) != (top_logprobs == nullptr)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (top_ids and top_logprobs must be NULL exactly when k == 0; k=%d)", name, k);
+    return QQQ_ERR_ARG;
+  }
+  if (!logits || misaligned(logits, 16) || misaligned(top_ids, 4) || misaligned(top_logprobs, 4)) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (logits must be non-NULL and 16-byte, top_ids and top_logprobs 4-byte aligned)", name);
+    return QQQ_ERR_ARG;
+  }
+  return QQQ_OK;
+}
+
+extern "C" int qqq_topk_logprobs(const void* logits, int ld, const void* tokens, void* logprob, void* rank, void* top_ids, void* top_logprobs,
+                                 int k, int rows, int vocab, int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 0 || rows > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_topk_logprobs: rows=%d outside [0, 65535]", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  const int rc = topk_logprobs_check("qqq_topk_logprobs", logits, ld, top_ids, top_logprobs, k, rows, vocab);
+  if (rc != QQQ_OK) return rc;
+  if ((tokens == nullptr) != (logprob == nullptr) || (tokens == nullptr) != (rank == nullptr) || (!tokens && k == 0) ||
+      misaligned(tokens, 8) || misaligned(logprob, 4) || misaligned(rank, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_topk_logprobs: bad argument (tokens, logprob and rank must be given or NULL together, and not NULL "
+             "with k == 0; tokens 8-byte, logprob and rank 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_topk_kernel, dim3(rows), dim3(SMP_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(logits), ld, static_cast<const long long*>(tokens), static_cast<float*>(logprob),
+                     static_cast<int*>(rank), static_cast<int*>(top_ids), static_cast<float*>(top_logprobs), k, vocab);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_topk_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_topk_logprobs_step(const void* logits, int ld, const void* out, int out_stride, const void* n_out, void* n_rec,
+                                      void* logprob, void* rank, void* top_ids, void* top_logprobs, int cap, int k, int rows, int vocab,
+                                      int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 0 || rows > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_topk_logprobs_step: rows=%d outside [0, 65535]", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  const int rc = topk_logprobs_check("qqq_topk_logprobs_step", logits, ld, top_ids, top_logprobs, k, rows, vocab);
+  if (rc != QQQ_OK) return rc;
+  if (out_stride < 1 || cap < 1) {
+    snprintf(g_err, sizeof(g_err), "qqq_topk_logprobs_step: bad shape out_stride=%d cap=%d (need both >= 1)", out_stride, cap);
+    return QQQ_ERR_ARG;
+  }
+  if (!out || !n_out || !n_rec || !logprob || !rank || misaligned(out, 8) || misaligned(n_out, 4) || misaligned(n_rec, 4) ||
+      misaligned(logprob, 4) || misaligned(rank, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_topk_logprobs_step: bad argument (out, n_out, n_rec, logprob and rank must be non-NULL; out 8-byte, "
+             "everything else 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_topk_step_kernel, dim3(rows), dim3(SMP_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(logits), ld, static_cast<const long long*>(out), out_stride,
+                     static_cast<const int*>(n_out), static_cast<int*>(n_rec), static_cast<float*>(logprob), static_cast<int*>(rank),
+                     static_cast<int*>(top_ids), static_cast<float*>(top_logprobs), cap, k, vocab);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_topk_step_kernel launch");
   return QQQ_OK;
 }
 

@@ -16,7 +16,7 @@ sequence that ends frees its blocks at once, and prompts the pool could not hold
 from __future__ import annotations
 
 from collections import deque
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -26,6 +26,26 @@ from . import ops
 from .attention import KVCache, QuantLlamaDecoderLayer
 from .blocks import QuantRMSNorm
 from .paged import PagedKVCache, PagedStep
+
+
+class TokenLogprobs(NamedTuple):
+    """What generate(logprobs=k) returns per completion, one entry per emitted token (the eos included), as CPU tensors: the token's
+    log-probability (f32 [T]) and rank (int32 [T], 1 = the most probable), and the k most probable tokens of its step with their
+    log-probabilities (int32 / f32 [T, k]); see ops.topk_logprobs."""
+    logprob: torch.Tensor
+    rank: torch.Tensor
+    top_ids: torch.Tensor
+    top_logprobs: torch.Tensor
+
+    @classmethod
+    def gather(cls, parts, index) -> "TokenLogprobs":
+        """the records at `index` (a list of rows) of the four CPU tensors `parts`"""
+        at = torch.tensor(index, dtype=torch.int64)
+        return cls(*(p[at] for p in parts))
+
+    @classmethod
+    def empty(cls, k: int) -> "TokenLogprobs":
+        return cls(torch.empty(0), torch.empty(0, dtype=torch.int32), torch.empty((0, k), dtype=torch.int32), torch.empty((0, k)))
 
 
 class QuantLlamaModel(nn.Module):
@@ -195,8 +215,9 @@ class QuantLlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, cache: Optional[PagedKVCache] = None,
-                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False, n: int = 1, draft_len: int = 0,
-                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> List[List[int]]:
+                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False, n: int = 1, logprobs: Optional[int] = None,
+                 draft_len: int = 0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
+                 frequency_penalty: float = 0.0) -> List[List[int]]:
         """Generate up to `max_new_tokens` tokens for every prompt (token lists of any lengths) -> the generated ids per prompt, the
         eos_token_id that ends a sequence included.
 
@@ -231,11 +252,28 @@ class QuantLlamaForCausalLM(nn.Module):
         pass, then as for n = 1 one per decode pass over the running rows; equal seeds give equal tokens.  Siblings are adjacent in every
         step, so a model with fuse_shared() reads their common keys once per pack of rows (the tokens are the same either way).
         device_loop=True builds the DecodeLoop with family=N; n > 1 with draft_len > 0 raises (there is no shared verify kernel).
-        n=1 is the call described above, draw for draw."""
+        n=1 is the call described above, draw for draw.
+
+        logprobs=k (0 <= k <= 32; None: off, and then nothing of it runs) makes the call return (tokens, records): `records` mirrors the
+        nesting of `tokens` and holds per completion a TokenLogprobs of CPU tensors with one entry per emitted token, the eos included
+        -- the token's log-probability and rank and the k most probable tokens with their log-probabilities, from ops.topk_logprobs
+        behind every ops.sample_tokens (the first token's from the prefill logits; for n > 1 from the repeated rows).  The values are
+        those of the logits row the sampler drew from: AFTER ops.penalize_logits when penalties are on, BEFORE temperature, top-k and
+        top-p -- the model's distribution, not the truncated one the draw was made from.  The tokens are the same as without logprobs,
+        draw for draw; the per-pass results stay on the device until the call returns (no further host sync per pass).
+        device_loop=True builds the DecodeLoop with logprobs=k.  logprobs with draft_len > 0 raises: the speculative loop emits several
+        tokens per row and step."""
         n = int(n)
         if n < 1:
             raise ValueError(f"generate: n={n} must be at least 1")
         draft_len = int(draft_len)
+        if logprobs is not None:
+            logprobs = int(logprobs)
+            if logprobs < 0 or logprobs > 32 or logprobs > self.lm_head.weight.shape[0]:
+                raise ValueError(f"generate: logprobs={logprobs} outside [0, min(32, vocab)]")
+            if draft_len > 0:
+                raise ValueError(f"generate: logprobs={logprobs} cannot be combined with draft_len={draft_len} (the speculative loop keeps "
+                                 f"no records)")
         if n > 1 and draft_len > 0:
             raise ValueError(f"generate: n={n} > 1 cannot be combined with draft_len={draft_len} (speculative steps have no shared-prefix kernel)")
         if draft_len < 0 or (draft_len > 0 and not device_loop):
@@ -245,14 +283,26 @@ class QuantLlamaForCausalLM(nn.Module):
             raise ValueError(f"generate: repetition_penalty={penalty[0]} must be finite and > 0")
         penalised = penalty != (1.0, 0.0, 0.0)
         loop_kw = dict(penalties=True) if penalised else {}  # without penalties the loops are built and called as ever
+        if logprobs is not None:
+            loop_kw["logprobs"] = logprobs  # ... and without logprobs
         gen_kw = dict(zip(("repetition_penalty", "presence_penalty", "frequency_penalty"), penalty)) if penalised else {}
         prompts = [list(p) for p in prompts]
         if any(not p for p in prompts):
             raise ValueError("generate: every prompt needs at least one token")
         out: List[List[int]] = [[] for _ in range(len(prompts) * n)]  # per sibling: prompt i's are i * n ... i * n + n - 1
 
+        lp_parts, lp_rows, lp_count = ([], [], [], []), [[] for _ in out], [0]  # per pass the op's four results; per sibling its rows of them
+
         def result():
-            return out if n == 1 else [out[i * n:(i + 1) * n] for i in range(len(prompts))]
+            if logprobs is None:
+                return out if n == 1 else [out[i * n:(i + 1) * n] for i in range(len(prompts))]
+            if lp_count[0]:  # the one transfer of the records
+                parts = [torch.cat(p).cpu() if p else torch.empty((lp_count[0], 0), dtype=d) for p, d in
+                         zip(lp_parts, (torch.float32, torch.int32, torch.int32, torch.float32))]
+            recs = [TokenLogprobs.gather(parts, at) if at else TokenLogprobs.empty(logprobs) for at in lp_rows]
+            if n == 1:
+                return out, recs
+            return [out[i * n:(i + 1) * n] for i in range(len(prompts))], [recs[i * n:(i + 1) * n] for i in range(len(prompts))]
 
         if max_new_tokens < 1 or not prompts:
             return result()
@@ -297,7 +347,15 @@ class QuantLlamaForCausalLM(nn.Module):
                                     torch.tensor([len(h) - 1 for h in hist], dtype=torch.int64, device=dev), seen,
                                     torch.tensor([len(prompts[i // n]) for i in seqs], dtype=torch.int32, device=dev), *penalty, workspace)
             u = torch.rand(logits.shape[0], generator=generator, device=logits.device)
-            return ops.sample_tokens(logits, temperature, top_k, top_p, u)
+            toks = ops.sample_tokens(logits, temperature, top_k, top_p, u)
+            if logprobs is not None:  # of the rows the sampler drew from; kept on the device until the call returns
+                for part, t in zip(lp_parts, ops.topk_logprobs(logits, toks, logprobs)):
+                    if t is not None:
+                        part.append(t)
+                for row, i in enumerate(seqs):
+                    lp_rows[i].append(lp_count[0] + row)
+                lp_count[0] += len(seqs)
+            return toks
 
         def settle(seqs, toks, fork=False):
             """record a pass's tokens; -> (the sequences that go on, their rows of the pass).  After a prefill pass with n > 1 (`fork`)

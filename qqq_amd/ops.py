@@ -1806,3 +1806,161 @@ def penalize_logits(logits: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, 
     else:
         _penalize_logits_impl(*args)
     return logits
+
+
+# ---- the fused top-k log-probability kernel (include/serving/qqq_amd_logprobs.h): the log-probability and rank of a token and the k most
+# probable tokens of every logits row, one launch; behind a sampler, on the logits it drew from
+
+def _topk_k_check(op, k, vocab):
+    if k < 0 or k > 32 or k > vocab:
+        raise ValueError(f"{op}: k={k} outside [0, min(32, vocab={vocab})]")
+
+
+def _topk_logprobs_check(logits, tokens, k):
+    # dtypes and shapes: needs no device, shared by the launch and the fake implementation -> (rows, vocab)
+    op = "topk_logprobs"
+    if logits.dtype != torch.float16 or logits.dim() != 2:
+        raise RuntimeError(f"{op}: logits must be fp16 [rows, vocab]")
+    rows, vocab = logits.shape
+    if tokens is not None and (tokens.dtype != torch.int64 or tokens.dim() != 1 or tokens.shape[0] != rows):
+        raise RuntimeError(f"{op}: tokens must be int64 [{rows}], one entry per row, not {_dt(tokens.dtype)} {tuple(tokens.shape)}")
+    if vocab < 1 or vocab > 262144 or rows > 65535:
+        raise RuntimeError(f"{op}: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows <= 65535")
+    _topk_k_check(op, k, vocab)
+    if tokens is None and k == 0:
+        raise ValueError(f"{op}: nothing is asked for (tokens is None and k == 0)")
+    return rows, vocab
+
+
+def _topk_logprobs_outputs(like, rows, scored, k):
+    return (like.new_empty((rows if scored else 0,), dtype=torch.float32), like.new_empty((rows if scored else 0,), dtype=torch.int32),
+            like.new_empty((rows, k), dtype=torch.int32), like.new_empty((rows, k), dtype=torch.float32))
+
+
+def _topk_logprobs_impl(logits, tokens, k):
+    _same_gpu("topk_logprobs", (logits,) if tokens is None else (logits, tokens))
+    rows, vocab = _topk_logprobs_check(logits, tokens, k)
+    logprob, rank, top_ids, top_lp = _topk_logprobs_outputs(logits, rows, tokens is not None, k)
+    if rows == 0:
+        return logprob, rank, top_ids, top_lp
+    logits = _logits_rows(logits, vocab)
+    err = _lib.lib().qqq_topk_logprobs(_ptr(logits), logits.stride(0), None if tokens is None else _ptr(tokens.contiguous()), _ptr(logprob),
+                                       _ptr(rank), _ptr(top_ids), _ptr(top_lp), k, rows, vocab, logits.device.index or 0,
+                                       _stream_for(logits))
+    _raise_lib("topk_logprobs", err)
+    return logprob, rank, top_ids, top_lp
+
+
+@torch.library.custom_op("qqq_amd::topk_logprobs", mutates_args=())
+def _topk_logprobs_op(logits: torch.Tensor, tokens: Optional[torch.Tensor], k: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                                                                                              torch.Tensor]:
+    return _topk_logprobs_impl(logits, tokens, k)
+
+
+@_topk_logprobs_op.register_fake
+def _(logits, tokens, k):
+    rows, _ = _topk_logprobs_check(logits, tokens, k)
+    return _topk_logprobs_outputs(logits, rows, tokens is not None, k)
+
+
+def topk_logprobs(logits: torch.Tensor, tokens: Optional[torch.Tensor] = None, k: int = 0):
+    """For every row of fp16 logits [rows, vocab]: the log-probability and the rank of tokens[r] (int64 [rows]) under softmax(logits[r]),
+    and the k most probable tokens with their log-probabilities, in one launch -> (logprob f32 [rows], rank int32 [rows], top_ids int32
+    [rows, k], top_logprobs f32 [rows, k]); the first two are None with tokens=None, the last two with k=0.
+
+    logprob is ops.token_logprobs' value to the bit (tokens < 0 give 0.0, tokens >= vocab NaN, a token whose logit is NaN or -inf
+    -inf); rank is 1 + the number of logits above the token's (0 for a token outside [0, vocab)); the top-k entries are ordered by logit
+    descending, then index ascending, with ties at the cut resolved exactly, and top_logprobs[r, i] is the value logprob has for
+    top_ids[r, i]: entry 0 is sample_tokens' greedy token.  0 <= k <= min(32, vocab).  The exact semantics of a row are stated in
+    include/serving/qqq_amd_logprobs.h.  Nothing is read on the host and the launch size depends on (rows, vocab, k) alone, so a captured
+    graph replays with other contents.  A view whose rows are `vocab` columns of a wider, 16-byte aligned fp16 matrix (row stride a
+    multiple of 8) is read in place; its other columns are never touched."""
+    if not isinstance(logits, torch.Tensor) or (tokens is not None and not isinstance(tokens, torch.Tensor)) or logits.dim() != 2:
+        raise RuntimeError("topk_logprobs: logits must be an fp16 [rows, vocab] tensor and tokens an int64 [rows] tensor or None")
+    k = int(k)
+    if _compiling(logits, tokens):
+        logprob, rank, top_ids, top_lp = _topk_logprobs_op(logits, tokens, k)
+    else:
+        logprob, rank, top_ids, top_lp = _topk_logprobs_impl(logits, tokens, k)
+    scored = tokens is not None
+    return (logprob if scored else None, rank if scored else None, top_ids if k else None, top_lp if k else None)
+
+
+def _topk_logprobs_step_check(logits, out, n_out, n_rec, logprob, rank, top_ids, top_logprobs):
+    # dtypes and shapes -> (rows, vocab, cap, k)
+    op = "topk_logprobs_step"
+    if logits.dtype != torch.float16 or logits.dim() != 2:
+        raise RuntimeError(f"{op}: logits must be fp16 [rows, vocab]")
+    rows, vocab = logits.shape
+    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[0] != rows or out.shape[1] < 1:
+        raise RuntimeError(f"{op}: out must be int64 [{rows}, out_stride >= 1], not {_dt(out.dtype)} {tuple(out.shape)}")
+    for name, t in (("n_out", n_out), ("n_rec", n_rec)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != rows:
+            raise RuntimeError(f"{op}: {name} must be int32 [{rows}], not {_dt(t.dtype)} {tuple(t.shape)}")
+    if logprob.dtype != torch.float32 or logprob.dim() != 2 or logprob.shape[0] != rows or logprob.shape[1] < 1:
+        raise RuntimeError(f"{op}: logprob must be f32 [{rows}, cap >= 1], not {_dt(logprob.dtype)} {tuple(logprob.shape)}")
+    cap = logprob.shape[1]
+    if rank.dtype != torch.int32 or tuple(rank.shape) != (rows, cap):
+        raise RuntimeError(f"{op}: rank must be int32 [{rows}, {cap}] like logprob, not {_dt(rank.dtype)} {tuple(rank.shape)}")
+    if top_ids.dtype != torch.int32 or top_ids.dim() != 3 or tuple(top_ids.shape[:2]) != (rows, cap):
+        raise RuntimeError(f"{op}: top_ids must be int32 [{rows}, {cap}, k], not {_dt(top_ids.dtype)} {tuple(top_ids.shape)}")
+    k = top_ids.shape[2]
+    if top_logprobs.dtype != torch.float32 or tuple(top_logprobs.shape) != (rows, cap, k):
+        raise RuntimeError(f"{op}: top_logprobs must be f32 [{rows}, {cap}, {k}] like top_ids, not {_dt(top_logprobs.dtype)} "
+                           f"{tuple(top_logprobs.shape)}")
+    if vocab < 1 or vocab > 262144 or rows > 65535:
+        raise RuntimeError(f"{op}: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows <= 65535")
+    _topk_k_check(op, k, vocab)
+    return rows, vocab, cap, k
+
+
+def _topk_logprobs_step_impl(logits, out, n_out, n_rec, logprob, rank, top_ids, top_logprobs):
+    ts = (logits, out, n_out, n_rec, logprob, rank, top_ids, top_logprobs)
+    _same_gpu("topk_logprobs_step", ts)
+    rows, vocab, cap, k = _topk_logprobs_step_check(*ts)
+    if rows == 0:
+        return
+    _in_place_check("topk_logprobs_step", (("out", out), ("n_out", n_out), ("n_rec", n_rec), ("logprob", logprob), ("rank", rank),
+                                           ("top_ids", top_ids), ("top_logprobs", top_logprobs)))
+    logits = _logits_rows(logits, vocab)
+    err = _lib.lib().qqq_topk_logprobs_step(_ptr(logits), logits.stride(0), _ptr(out), out.shape[1], _ptr(n_out), _ptr(n_rec), _ptr(logprob),
+                                            _ptr(rank), _ptr(top_ids), _ptr(top_logprobs), cap, k, rows, vocab, logits.device.index or 0,
+                                            _stream_for(logits))
+    _raise_lib("topk_logprobs_step", err)
+
+
+@torch.library.custom_op("qqq_amd::topk_logprobs_step", mutates_args=("n_rec", "logprob", "rank", "top_ids", "top_logprobs"))
+def _topk_logprobs_step_op(logits: torch.Tensor, out: torch.Tensor, n_out: torch.Tensor, n_rec: torch.Tensor, logprob: torch.Tensor,
+                           rank: torch.Tensor, top_ids: torch.Tensor, top_logprobs: torch.Tensor) -> None:
+    _topk_logprobs_step_impl(logits, out, n_out, n_rec, logprob, rank, top_ids, top_logprobs)
+
+
+@_topk_logprobs_step_op.register_fake
+def _(logits, out, n_out, n_rec, logprob, rank, top_ids, top_logprobs):
+    _topk_logprobs_step_check(logits, out, n_out, n_rec, logprob, rank, top_ids, top_logprobs)
+
+
+def topk_logprobs_step(logits: torch.Tensor, out: torch.Tensor, n_out: torch.Tensor, n_rec: torch.Tensor, logprob: torch.Tensor,
+                       rank: torch.Tensor, top_ids: Optional[torch.Tensor] = None, top_logprobs: Optional[torch.Tensor] = None) -> None:
+    """The decode loop's log-probability epilogue, behind sample_advance on the logits that call drew from: a row that holds a token
+    without a record yet gets topk_logprobs' results for it, in place.  Returns nothing; n_rec, logprob, rank, top_ids and top_logprobs
+    are updated in place.
+
+    out, n_out   int64 [rows, out_stride], int32 [rows]: sample_advance's emitted tokens and their number, only read
+    n_rec        int32 [rows]: the records a row has so far
+    logprob, rank             f32 / int32 [rows, cap];  top_ids, top_logprobs  int32 / f32 [rows, cap, k], or both None for k = 0
+    A row with n_rec[r] < n_out[r] and n_rec[r] < cap scores out[r, n_rec[r]] against logits[r] into record (r, n_rec[r]) and counts it;
+    every other row -- idle, nothing emitted in this step, no room -- writes nothing.  At most one record per row and call.  The exact
+    semantics are stated in include/serving/qqq_amd_logprobs.h.  Nothing is read on the host and the launch size depends on the shapes
+    alone, so a decode step with this call behind sample_advance replays from a captured graph."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(logprob, torch.Tensor) or logits.dim() != 2 or logprob.dim() != 2:
+        raise RuntimeError("topk_logprobs_step: logits must be an fp16 [rows, vocab] tensor and logprob an f32 [rows, cap] tensor")
+    if (top_ids is None) != (top_logprobs is None):
+        raise RuntimeError("topk_logprobs_step: top_ids and top_logprobs must be given or None together")
+    if top_ids is None:  # k = 0: nothing of them is ever touched
+        top_ids = logprob.new_empty(tuple(logprob.shape) + (0,), dtype=torch.int32)
+        top_logprobs = logprob.new_empty(tuple(logprob.shape) + (0,))
+    args = (logits, out, n_out, n_rec, logprob, rank, top_ids, top_logprobs)
+    if _compiling(*args):
+        return _topk_logprobs_step_op(*args)
+    return _topk_logprobs_step_impl(*args)

@@ -23,6 +23,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import ops
+from .model import TokenLogprobs
 from .paged import PagedKVCache, PagedStep
 
 
@@ -62,6 +63,10 @@ class DecodeLoop:
                 loop then owns `family_of` (int32 [rows], constant: a row's slot's first row) and `shared` (int64 [rows]: the keys a row has
                 in common with its siblings, written on admission, 0 when idle) inside its PagedStep, as part of the captured graph: a model
                 with fuse_shared() reads a family's common keys once per pack of rows.  generate() then returns N lists per prompt.
+    logprobs    k in [0, 32] (None: off): the loop owns `n_rec` (int32 [rows]: the records a row has), `lp` / `lp_rank` (f32 / int32
+                [rows, max_len]) and `lp_top_ids` / `lp_top` (int32 / f32 [rows, max_len, k]), and its step runs ops.topk_logprobs_step
+                behind ops.sample_advance, inside the captured graph: every emitted token's log-probability, rank and k most probable
+                alternatives, from the logits row it was drawn from.  generate() then returns (tokens, records).  None: none of that exists.
     `captures` counts the captures: 1 for the life of the loop with graph=True.  The graph holds addresses: a model that is changed after
     the first generate() (fuse_*(), load_state_dict, .to()) needs a new loop."""
 
@@ -72,17 +77,27 @@ class DecodeLoop:
     _idle = (("remaining", 0), ("pos", -1), ("slots", -1), ("ids", 0))  # what the cleanup resets
     family = 1                       # rows per slot: the completions of one prompt (DecodeLoop alone takes more than 1)
     penalties = False                # True: the step runs ops.penalize_logits in front of the sampler (_allocate_penalties)
+    logprobs = None                  # k: the step runs ops.topk_logprobs_step behind the sampler (DecodeLoop alone takes it)
 
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, sync_every: int = 8, u_stride: int = 64, graph: bool = True,
-                 penalties: bool = False, family: int = 1):
+                 penalties: bool = False, family: int = 1, logprobs: Optional[int] = None):
         rows, max_len, sync_every, u_stride, family = int(rows), int(max_len), int(sync_every), int(u_stride), int(family)
         short = u_stride < sync_every and f"u_stride={u_stride} must cover the sync_every={sync_every} steps between two refills"
         dev = _check_loop("DecodeLoop", lm, cache, rows, max_len, sync_every, graph, short)
         if family < 1 or rows % family:
             raise ValueError(f"DecodeLoop: family={family} must be at least 1 and divide rows={rows}")
+        if logprobs is not None and not 0 <= int(logprobs) <= min(32, lm.lm_head.weight.shape[0]):
+            raise ValueError(f"DecodeLoop: logprobs={logprobs} outside [0, min(32, vocab)]")
         self.family = family
         self._allocate(lm, cache, rows, max_len, sync_every, u_stride, graph, dev)
         self.out = torch.zeros((rows, max_len), dtype=torch.int64, device=dev)
+        if logprobs is not None:  # one record per emitted token: out's shape
+            self.logprobs = int(logprobs)
+            self.n_rec = torch.zeros(rows, dtype=torch.int32, device=dev)
+            self.lp = torch.zeros((rows, max_len), dtype=torch.float32, device=dev)
+            self.lp_rank = torch.zeros((rows, max_len), dtype=torch.int32, device=dev)
+            self.lp_top_ids = torch.zeros((rows, max_len, self.logprobs), dtype=torch.int32, device=dev)
+            self.lp_top = torch.zeros((rows, max_len, self.logprobs), dtype=torch.float32, device=dev)
         if penalties:  # this loop keeps no history of its own: the penalty op records a row's input token at its position
             self._allocate_penalties(torch.zeros((rows, max_len), dtype=torch.int32, device=dev))
         # the one step of every decode pass: its device tensors ARE the state arrays (a row's position is its last position)
@@ -141,6 +156,8 @@ class DecodeLoop:
             self._penalize(logits)
         ops.sample_advance(logits, self.temperature, self.top_k, self.top_p, self.u, self.tick, self.ids, self.pos, self.slots,
                            self.block_table, self.remaining, self.eos, self.out, self.n_out, self.cache.block_size)
+        if self.logprobs is not None:  # the row that just emitted a token has n_rec < n_out: its record, from the logits it was drawn from
+            ops.topk_logprobs_step(logits, self.out, self.n_out, self.n_rec, self.lp, self.lp_rank, self.lp_top_ids, self.lp_top)
 
     def _capture(self) -> None:
         """Warm up and capture the step with every row idle (nothing but `tick` changes), on a side stream."""
@@ -224,7 +241,13 @@ class DecodeLoop:
         repetition_penalty, presence_penalty, frequency_penalty (1, 0, 0: none) need a loop built with penalties=True, whose step runs
         ops.penalize_logits between the forward and the sampler: every draw is made from logits penalised over the row's prompt and
         emitted tokens (include/qqq_amd_penalty.h) -- the first one from the prefill's logits penalised over the prompt, where every
-        index is a prompt index and the repetition rule alone acts; a draft's logits row over the drafts in front of it too."""
+        index is a prompt index and the repetition rule alone acts; a draft's logits row over the drafts in front of it too.
+
+        A loop built with logprobs=k returns (tokens, records): `records` mirrors the nesting of `tokens` and holds per completion a
+        TokenLogprobs of CPU tensors, one entry per emitted token, the eos included.  The first token's record comes from
+        ops.topk_logprobs on the prefill's logits in admit(), the others from the step's ops.topk_logprobs_step; all of them are taken
+        from the logits row the sampler drew from -- after the penalties, before temperature, top-k and top-p.  A finished row's
+        records are read back with its tokens; the run itself gains no host sync."""
         name = f"{self._name}.generate"
         penalty = (float(repetition_penalty), float(presence_penalty), float(frequency_penalty))
         if not (penalty[0] > 0.0 and penalty[0] != float("inf")):
@@ -239,8 +262,24 @@ class DecodeLoop:
         fam = self.family
         outs: List[List[int]] = [[] for _ in range(len(prompts) * fam)]  # per sibling: prompt i's are i * fam ... i * fam + fam - 1
 
+        k_lp = self.logprobs
+        first_parts, first_at = ([], [], [], []), {}  # the first tokens' records per prefill pass (on the device), and a sequence's row of them
+        step_recs = {}                                # a finished sequence's records of its decode steps (CPU)
+
         def result():
-            return outs if fam == 1 else [outs[i * fam:(i + 1) * fam] for i in range(len(prompts))]
+            if k_lp is None:
+                return outs if fam == 1 else [outs[i * fam:(i + 1) * fam] for i in range(len(prompts))]
+            firsts = [torch.cat(p).cpu() for p in first_parts] if first_at else None
+            recs = []
+            for q in range(len(outs)):
+                if q not in first_at:
+                    recs.append(TokenLogprobs.empty(k_lp))
+                    continue
+                head = TokenLogprobs.gather(firsts, [first_at[q]])
+                recs.append(TokenLogprobs(*(torch.cat(pair) for pair in zip(head, step_recs[q]))) if q in step_recs else head)
+            if fam == 1:
+                return outs, recs
+            return [outs[i * fam:(i + 1) * fam] for i in range(len(prompts))], [recs[i * fam:(i + 1) * fam] for i in range(len(prompts))]
 
         max_new_tokens = int(max_new_tokens)
         if max_new_tokens < 1 or not prompts:
@@ -265,6 +304,8 @@ class DecodeLoop:
         per_row = dict(remaining=max_new_tokens - 1, eos=eos, n_out=0, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p))
         if self.penalties:
             per_row.update(repetition=penalty[0], presence=penalty[1], frequency=penalty[2])
+        if k_lp is not None:
+            per_row.update(n_rec=0)  # with n_out: the step's records are counted like its tokens
 
         def admit():
             new = []
@@ -300,7 +341,16 @@ class DecodeLoop:
                 ops.penalize_logits(logits, torch.tensor([prompts[q // fam][-1] for _, q in born], dtype=torch.int64, device=dev), at_last,
                                     seen, torch.tensor(lens, dtype=torch.int32, device=dev), *penalty, self.penalty_workspace)
             u = torch.rand(len(born), generator=generator, device=dev)
-            first = ops.sample_tokens(logits, temperature, top_k, top_p, u).tolist()
+            first = ops.sample_tokens(logits, temperature, top_k, top_p, u)
+            if k_lp is not None:  # the first token's record: the plain op on the rows the sampler drew from
+                lp, rk, ids, top = ops.topk_logprobs(logits, first, k_lp)
+                if ids is None:
+                    ids, top = lp.new_empty((len(born), 0), dtype=torch.int32), lp.new_empty((len(born), 0))
+                for part, t in zip(first_parts, (lp, rk, ids, top)):
+                    part.append(t)
+                for _, q in born:
+                    first_at[q] = len(first_at)
+            first = first.tolist()
             rows, state, ended = [], {}, []
             for (r, q), t in zip(born, first):
                 outs[q].append(t)
@@ -348,6 +398,10 @@ class DecodeLoop:
                 if done:
                     at_done = torch.tensor(done, dtype=torch.int64, device=dev)
                     toks = getattr(self, self._tokens)[at_done].tolist()
+                    if k_lp is not None:  # read back with the tokens: record j of a row belongs to out[r, j]
+                        parts = [a[at_done].cpu() for a in (self.lp, self.lp_rank, self.lp_top_ids, self.lp_top)]
+                        for j, r in enumerate(done):
+                            step_recs[owner[r]] = tuple(p[j, :synced["n_out"][r]] for p in parts)
                     for r, row in zip(done, toks):
                         i = owner[r]
                         outs[i].extend(self._collect(row, len(prompts[i // fam]), sid(i), {a: v[r] for a, v in synced.items()}))
@@ -362,6 +416,8 @@ class DecodeLoop:
                     cache.free(sid(i))
             for array, value in self._idle + ((("shared", 0),) if fam > 1 else ()):
                 getattr(self, array).fill_(value)
+            if k_lp is not None:
+                self.n_rec.copy_(self.n_out)  # no row owes a record
             raise
         return result()
 

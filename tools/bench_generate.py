@@ -41,6 +41,13 @@ the prompt and what it emitted, 128 ... 255 tokens here; the op's time at longer
 
     python tools/bench_generate.py --penalties [--draft-len 0,4] [--batch 1,16] [--rounds 5] [--out profiles/penalty_loop_bench.json]
 
+With --logprobs 0,5,20 the tool times the replayed step with and without ops.topk_logprobs_step in it, in one rotation: per batch a
+DecodeLoop built without logprobs beside one built with logprobs=k for every k given, by the protocol above.  Written to
+profiles/logprobs_loop_bench.json: the step times and each epilogue's difference to the plain step, beside the plain step's spread over
+the rounds.  The op alone is in profiles/logprobs_bench.json (tools/bench_sample.py --logprobs).
+
+    python tools/bench_generate.py --logprobs 0,5,20 [--batch 1,16] [--rounds 5] [--out profiles/logprobs_loop_bench.json]
+
 With --n 1,4,8 the tool measures parallel sampling: per N one prompt of --prompt tokens (default 2048: sixteen 128-key chunks of the decode
 plan) served three ways by a captured DecodeLoop in one rotation -- `repeated`: the prompt N times in N rows (N prefills, N copies of its
 keys); `forked`: DecodeLoop(family=N) without fuse_shared() (one prefill, the prompt's blocks once, the plain paged decode op over the
@@ -302,6 +309,76 @@ def penalty_main(args):
             f"{e['plain_round_spread_us']})" for k, e in p["draft_len"].items()))
 
 
+def logprobs_point(lm, batch, ks, rounds, dev):
+    import torch
+
+    from bench_model import VOCAB
+    from qqq_amd import DecodeLoop
+
+    g = torch.Generator().manual_seed(batch)
+    prompts = [torch.randint(0, VOCAB, (PROMPT,), generator=g).tolist() for _ in range(batch)]
+    max_len = -(-(PROMPT + NEW - 1) // BS) * BS
+    loops = {}  # key: None (the plain loop) or k
+    for k in [None] + ks:
+        kw = dict(rows=batch, max_len=max_len, sync_every=SYNC_EVERY, **({} if k is None else dict(logprobs=k)))
+        loops[k] = DecodeLoop(lm, lm.new_cache(batch * (max_len // BS), BS), **kw)
+
+    def timed(key, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = loops[key].generate(prompts, n)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, (out if key is None else out[0])
+
+    tokens = {}
+    for key in loops:  # warm-up: code objects, workspaces, rope tables, the capture
+        timed(key, 1)
+        tokens[key] = timed(key, NEW)[1]
+        assert all(len(o) == NEW for o in tokens[key]) and tokens[key] == tokens[None], key
+    values = {key: [] for key in loops}
+    for _ in range(rounds):
+        for key in loops:
+            short, full = timed(key, 1)[0], timed(key, NEW)[0]
+            values[key].append((full - short) / (NEW - 1) * 1e6)
+    res = {"batch": batch, "prompt_tokens": PROMPT, "new_tokens": NEW, "layers": LAYERS, "vocab": VOCAB, "logprobs": {}}
+
+    def entry(v):
+        return {"step_us": round(statistics.median(v), 1), "step_us_min": round(min(v), 1), "step_us_max": round(max(v), 1),
+                "rounds_step_us": [round(x, 1) for x in v]}
+
+    res["plain"] = entry(values[None])
+    res["plain_round_spread_us"] = round(res["plain"]["step_us_max"] - res["plain"]["step_us_min"], 1)
+    for k in ks:
+        e = entry(values[k])
+        e["epilogue_us_per_step"] = round(e["step_us"] - res["plain"]["step_us"], 1)
+        e["epilogue_exceeds_the_plain_steps_spread"] = bool(e["epilogue_us_per_step"] > res["plain_round_spread_us"])
+        res["logprobs"][str(k)] = e
+    return res
+
+
+def logprobs_main(args):
+    import torch
+
+    from bench_model import build
+
+    ks = sorted({int(k) for k in args.logprobs.split(",")})
+    dev = torch.device("cuda:0")
+    lm = build(LAYERS, dev)
+    with torch.no_grad():
+        points = [logprobs_point(lm, b, ks, args.rounds, dev) for b in map(int, args.batch.split(","))]
+    out = {"tool": "tools/bench_generate.py --logprobs", "device": torch.cuda.get_device_name(0),
+           "shape": "Llama-2-7B layers, per-channel W4A8, fuse_qkv(), paged fp16 cache, block 16, greedy", "sync_every": SYNC_EVERY,
+           "rounds": args.rounds, "points": points}
+    path = args.out or os.path.join(ROOT, "profiles", "logprobs_loop_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"batch {p['batch']:3d}: plain {p['plain']['step_us']:.1f} us/step (spread {p['plain_round_spread_us']})  " + "  ".join(
+            f"k={k} {e['step_us']:.1f} (+{e['epilogue_us_per_step']})" for k, e in p["logprobs"].items()))
+
+
 def parallel_point(lm, n, prompt_len, rounds, dev):
     import torch
 
@@ -408,6 +485,8 @@ def main():
                     "(profiles/spec_decode_verify_bench.json)")
     ap.add_argument("--penalties", action="store_true", help="time the replayed step with and without ops.penalize_logits "
                     "(profiles/penalty_loop_bench.json)")
+    ap.add_argument("--logprobs", default=None, help="e.g. 0,5,20: time the replayed step with and without ops.topk_logprobs_step "
+                    "(profiles/logprobs_loop_bench.json)")
     ap.add_argument("--out", default=None, help="default profiles/decode_loop_bench.json, or profiles/spec_decode_bench.json with --draft-len")
     args = ap.parse_args()
     import torch
@@ -418,6 +497,8 @@ def main():
         return parallel_main(args)
     if args.penalties:
         return penalty_main(args)
+    if args.logprobs:
+        return logprobs_main(args)
     if args.draft_len:
         return spec_main(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "decode_loop_bench.json")

@@ -23,6 +23,15 @@ the all-distinct and the all-one-token history, half of it prompt; penalties 1.3
 torch / fused with the range over the rounds, and the share of logit bits the two agree on after one call.
 
     python tools/bench_sample.py --penalties [--out profiles/penalty_bench.json] [--rows 1,16,64] [--vocab 32000,128256,151936]
+
+With --logprobs it times ops.topk_logprobs alone, against a torch composition of the same semantics, by the same protocol:
+
+    fused   ops.topk_logprobs(logits, tokens, k): one launch
+    torch   log_softmax(logits.float()); gather at the tokens; a rank count (logits > the token's logit, summed); torch.topk for k > 0
+Points: every vocab and rows above x k = 0, 5 and 20.  Written: both times per point, torch / fused with the range over the rounds, the
+share of rows whose top-k ids agree and the largest difference of a log-probability.
+
+    python tools/bench_sample.py --logprobs [--out profiles/logprobs_bench.json] [--rows 1,16,64] [--vocab 32000,128256,151936]
 """
 import argparse
 import json
@@ -203,10 +212,76 @@ def penalty_main(args, dev):
             for how in ("eager", "graph")))
 
 
+LOGPROB_KS = (0, 5, 20)
+
+
+def torch_logprobs(logits, tokens, k):
+    import torch
+
+    ls = torch.log_softmax(logits.float(), dim=-1)
+    at = logits.gather(1, tokens[:, None])
+    out = (ls.gather(1, tokens[:, None])[:, 0], 1 + (logits > at).sum(dim=-1))
+    return out + tuple(torch.topk(ls, k, dim=-1)) if k else out
+
+
+def logprobs_point(rows, vocab, k, dev):
+    import torch
+
+    from qqq_amd import ops
+
+    g = torch.Generator(device=dev).manual_seed(vocab + rows + k)
+    logits = (4.0 * torch.randn((rows, vocab), generator=g, device=dev)).half()
+    tokens = torch.randint(0, vocab, (rows,), generator=g, device=dev)
+    fns = {"fused": lambda: ops.topk_logprobs(logits, tokens, k), "torch": lambda: torch_logprobs(logits, tokens, k)}
+    a, b = fns["fused"](), fns["torch"]()
+    res = {"rows": rows, "vocab": vocab, "k": k, "max_logprob_difference": float((a[0] - b[0]).abs().max()),
+           "ranks_equal_fraction": float((a[1] == b[1]).float().mean())}
+    if k:  # torch.topk breaks ties its own way: fp16 logits repeat
+        res["top_ids_equal_fraction"] = float((a[2] == b[3]).all(dim=-1).float().mean())
+    for how in ("eager", "graph"):
+        run = fns if how == "eager" else {name: capture(f).replay for name, f in fns.items()}
+        for f in run.values():
+            for _ in range(WARMUP):
+                f()
+        torch.cuda.synchronize()
+        rounds = {name: [] for name in run}
+        for _ in range(ROUNDS):
+            for name, f in run.items():
+                rounds[name].append(statistics.median(time_calls(f, CALLS)))
+        r = {}
+        for name, v in rounds.items():
+            r[name] = {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
+                       "rounds_us": [round(x, 2) for x in v]}
+        r["torch_over_fused"] = round(r["torch"]["median_us"] / r["fused"]["median_us"], 2)
+        r["torch_over_fused_range"] = [round(r["torch"]["min_us"] / r["fused"]["max_us"], 2), round(r["torch"]["max_us"] / r["fused"]["min_us"], 2)]
+        res[how] = r
+    return res
+
+
+def logprobs_main(args, dev):
+    import torch
+
+    points = [logprobs_point(r, v, k, dev) for v in map(int, args.vocab.split(",")) for r in map(int, args.rows.split(",")) for k in LOGPROB_KS]
+    notes = [f"rows={p['rows']} vocab={p['vocab']} k={p['k']} {how}: the op does not win ({p[how]['torch_over_fused']}x)"
+             for p in points for how in ("eager", "graph") if p[how]["torch_over_fused_range"][0] <= 1.0]
+    out = {"tool": "tools/bench_sample.py --logprobs", "device": torch.cuda.get_device_name(0), "rounds": ROUNDS, "calls_per_round": CALLS,
+           "points": points, "notes": notes or ["the op wins at every point, also at the unfavourable ends of both spreads"]}
+    path = args.out or os.path.join(ROOT, "profiles", "logprobs_bench.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"rows {p['rows']:3d} vocab {p['vocab']:6d} k {p['k']:2d}: " + "  ".join(
+            f"{how} fused {p[how]['fused']['median_us']:8.1f} us torch {p[how]['torch']['median_us']:8.1f} us ({p[how]['torch_over_fused']}x)"
+            for how in ("eager", "graph")))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None, help="default profiles/sample_bench.json, or profiles/penalty_bench.json with --penalties")
+    ap.add_argument("--out", default=None, help="default profiles/sample_bench.json, profiles/penalty_bench.json with --penalties, profiles/logprobs_bench.json with --logprobs")
     ap.add_argument("--penalties", action="store_true", help="time ops.penalize_logits against a torch composition instead")
+    ap.add_argument("--logprobs", action="store_true", help="time ops.topk_logprobs against a torch composition instead")
     ap.add_argument("--rows", default="1,16,64")
     ap.add_argument("--vocab", default="32000,128256,151936")
     ap.add_argument("--modes", default="sample,top_k_top_p")
@@ -218,6 +293,8 @@ def main():
     dev = torch.device("cuda:0")
     if args.penalties:
         return penalty_main(args, dev)
+    if args.logprobs:
+        return logprobs_main(args, dev)
     args.out = args.out or os.path.join(ROOT, "profiles", "sample_bench.json")
     points = [point(r, v, m, dev) for m in args.modes.split(",") for v in map(int, args.vocab.split(",")) for r in map(int, args.rows.split(","))]
     notes = [f"{p['mode']} rows={p['rows']} vocab={p['vocab']} {how}: the fused op does not win ({p[how]['torch_over_fused']}x)"
