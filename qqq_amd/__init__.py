@@ -36,8 +36,12 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     QuantLlamaForCausalLM.score / loglikelihood / perplexity, pack_steps            # scoring text over the paged cache; qqq_amd/score.py
     topk_logprobs(logits, tokens=None, k=0) / topk_logprobs_step(...)               # a token's log-probability and rank and the k most probable
                                                                                     # tokens per logit row, one launch; generate(logprobs=k)
+    ban_tokens(logits, n_out, min_new, eos, ban_ids, base) / stop_check(tokens, base, first, n_out, stop_ids, stop_len, ...)
+                                                                                    # the minimum length in front of a sampler, stop sequences and
+                                                                                    # stop token ids behind a loop's step; generate(stop=, ...)
 """
 from .ops import (  # noqa: F401
+    ban_tokens,
     decode_attention,
     decode_attention_kv8,
     decode_attention_paged,
@@ -63,6 +67,7 @@ from .ops import (  # noqa: F401
     sample_tokens,
     silu_mul_quant,
     spec_advance,
+    stop_check,
     token_logprobs,
     topk_logprobs,
     topk_logprobs_step,
@@ -88,4 +93,4 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "sample_tokens", "QuantLlamaModel", "QuantLlamaForCausalLM", "sample_advance", "DecodeLoop", "token_logprobs", "pack_steps",
            "spec_advance", "SpecDecodeLoop", "ngram_draft", "verify_attention_paged", "verify_attention_paged_kv8", "penalize_logits",
            "decode_attention_paged_shared", "decode_attention_paged_shared_kv8", "decode_attention_shared_plan",
-           "topk_logprobs", "topk_logprobs_step", "TokenLogprobs"]
+           "topk_logprobs", "topk_logprobs_step", "TokenLogprobs", "ban_tokens", "stop_check"]

@@ -50,6 +50,13 @@ def serving_headers() -> list:
     return sorted(os.path.join(sub, f) for f in os.listdir(sub) if f.endswith(".h"))
 
 
+def extension_headers() -> list:
+    """the headers in the subdirectories of include/serving/ (include/serving/<feature>/*.h): one new file is all the next feature adds"""
+    sub = os.path.join(INCLUDE, "serving")
+    dirs = sorted(d for d in os.listdir(sub) if os.path.isdir(os.path.join(sub, d)))
+    return [os.path.join(sub, d, f) for d in dirs for f in sorted(os.listdir(os.path.join(sub, d))) if f.endswith(".h")]
+
+
 def _stale(lib: str, extra) -> bool:
     if not os.path.exists(lib):
         return True
@@ -60,7 +67,7 @@ def _stale(lib: str, extra) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(LIB, operator_headers() + serving_headers())
+    return _stale(LIB, operator_headers() + serving_headers() + extension_headers())
 
 
 def _compile(src: str, out: str, verbose: bool, flags=()) -> str:

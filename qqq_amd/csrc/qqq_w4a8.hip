@@ -40,6 +40,7 @@
 //   qqq_step.hip.h     the decode loop's step: that sampler with an epilogue that advances each row's decode state on the device
 //   qqq_penalty.hip.h  the repetition / presence / frequency penalty: fp16 logit rows rewritten in place from each row's token history, one launch
 //   qqq_spec.hip.h     the speculative decode loop's step: draft_len + 1 draws per row by that sampler, the accept rule and the n-gram drafter
+//   qqq_stop.hip.h     stop sequences, stop token ids and the minimum length: the ban in front of a sampler, the check behind a loop's step
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -92,6 +93,8 @@
 #include "../../include/qqq_amd_shared.h"
 #include "qqq_penalty.hip.h"
 #include "../../include/qqq_amd_penalty.h"
+#include "qqq_stop.hip.h"
+#include "../../include/serving/stop/qqq_amd_stop.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1630,6 +1633,107 @@ extern "C" int qqq_penalize_logits(void* logits, int ld, const void* ids, const 
                      static_cast<const float*>(presence), static_cast<const float*>(frequency), static_cast<unsigned*>(workspace), vocab);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_penalize_logits_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- stop sequences, stop token ids and the minimum length (include/serving/stop/qqq_amd_stop.h; kernels in qqq_stop.hip.h): one launch
+// each, one wave per logits row / per row, no workspace.
+extern "C" int qqq_ban_tokens(void* logits, int ld, const void* n_out, int base, const void* min_new, const void* eos, const void* ban_ids,
+                              int n_ban, int group, int rows, int vocab, int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 0 || rows > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_ban_tokens: rows=%d outside [0, 65535]", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  if (group < 1 || group > STOP_MAX_GROUP || (long long)rows * group > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_ban_tokens: group=%d outside [1, %d], or rows=%d times group exceeds 65535 logits rows", group,
+             STOP_MAX_GROUP, rows);
+    return QQQ_ERR_ARG;
+  }
+  if (vocab < 1 || vocab > SMP_MAX_VOCAB || ld < vocab || n_ban < 0 || n_ban > STOP_MAX) {
+    snprintf(g_err, sizeof(g_err), "qqq_ban_tokens: bad shape vocab=%d ld=%d n_ban=%d (need 1 <= vocab <= %d, ld >= vocab, 0 <= n_ban <= %d)",
+             vocab, ld, n_ban, SMP_MAX_VOCAB, STOP_MAX);
+    return QQQ_ERR_ARG;
+  }
+  if (!logits || !n_out || !min_new || !eos || (n_ban == 0) != (ban_ids == nullptr) || misaligned(logits, 2) || misaligned(n_out, 4) ||
+      misaligned(min_new, 4) || misaligned(eos, 4) || misaligned(ban_ids, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_ban_tokens: bad argument (logits, n_out, min_new and eos must be non-NULL, ban_ids NULL exactly when "
+             "n_ban == 0; logits 2-byte, everything else 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  const int total = rows * group;
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_ban_tokens_kernel, dim3((total + STOP_WAVES - 1) / STOP_WAVES), dim3(STOP_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<unsigned short*>(logits), ld, static_cast<const int*>(n_out), base, static_cast<const int*>(min_new),
+                     static_cast<const int*>(eos), static_cast<const int*>(ban_ids), n_ban, group, total, vocab);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_ban_tokens_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_stop_check(const void* tokens, int token_bytes, int tok_stride, const void* base, const void* first, const void* n_out,
+                              const void* stop_ids, int stop_stride, const void* stop_len, int n_stop, const void* end_ids, int n_end,
+                              const void* eos, const void* min_new, void* n_seen, void* n_trim, void* stop_hit, void* ids, void* pos, void* slots, void* start,
+                              void* remaining, int group, int rows, int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 0 || rows > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_stop_check: rows=%d outside [0, 65535]", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  if (group < 1 || group > STOP_MAX_GROUP) {
+    snprintf(g_err, sizeof(g_err), "qqq_stop_check: group=%d outside [1, %d]", group, STOP_MAX_GROUP);
+    return QQQ_ERR_ARG;
+  }
+  if ((token_bytes != 4 && token_bytes != 8) || tok_stride < 1 || n_stop < 0 || n_stop > STOP_MAX || stop_stride < 1 ||
+      stop_stride > STOP_MAX || n_end < 0 || n_end > STOP_MAX) {
+    snprintf(g_err, sizeof(g_err), "qqq_stop_check: bad shape token_bytes=%d tok_stride=%d n_stop=%d stop_stride=%d n_end=%d (need token_bytes "
+             "4 or 8, tok_stride >= 1, 0 <= n_stop <= %d, 1 <= stop_stride <= %d, 0 <= n_end <= %d)", token_bytes, tok_stride, n_stop,
+             stop_stride, n_end, STOP_MAX, STOP_MAX, STOP_MAX);
+    return QQQ_ERR_ARG;
+  }
+  if (!tokens || !base || !n_out || !min_new || !n_seen || !n_trim || !stop_hit || !ids || !pos || !slots || !remaining ||
+      (n_stop == 0) != (stop_ids == nullptr) || (n_stop == 0) != (stop_len == nullptr) || (n_end == 0) != (end_ids == nullptr) ||
+      misaligned(tokens, token_bytes) || misaligned(base, 4) || misaligned(first, 4) || misaligned(n_out, 4) || misaligned(stop_ids, 4) ||
+      misaligned(stop_len, 4) || misaligned(end_ids, 4) || misaligned(eos, 4) || misaligned(min_new, 4) || misaligned(n_seen, 4) || misaligned(n_trim, 4) ||
+      misaligned(stop_hit, 4) || misaligned(ids, 8) || misaligned(pos, 8) || misaligned(slots, 8) || misaligned(start, 8) ||
+      misaligned(remaining, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_stop_check: bad argument (every pointer but first, eos and start must be non-NULL; stop_ids and stop_len "
+             "NULL exactly when n_stop == 0, end_ids when n_end == 0; tokens token_bytes-aligned, ids / pos / slots / start 8-byte, "
+             "everything else 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_stop_state st;
+  st.tokens = tokens;
+  st.base = static_cast<const int*>(base);
+  st.first = static_cast<const int*>(first);
+  st.n_out = static_cast<const int*>(n_out);
+  st.stop_ids = static_cast<const int*>(stop_ids);
+  st.stop_len = static_cast<const int*>(stop_len);
+  st.end_ids = static_cast<const int*>(end_ids);
+  st.eos = static_cast<const int*>(eos);
+  st.min_new = static_cast<const int*>(min_new);
+  st.n_seen = static_cast<int*>(n_seen);
+  st.n_trim = static_cast<int*>(n_trim);
+  st.stop_hit = static_cast<int*>(stop_hit);
+  st.ids = static_cast<long long*>(ids);
+  st.pos = static_cast<long long*>(pos);
+  st.slots = static_cast<long long*>(slots);
+  st.start = static_cast<long long*>(start);
+  st.remaining = static_cast<int*>(remaining);
+  st.token_bytes = token_bytes;
+  st.tok_stride = tok_stride;
+  st.stop_stride = stop_stride;
+  st.n_stop = n_stop;
+  st.n_end = n_end;
+  st.group = group;
+  st.rows = rows;
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_stop_check_kernel, dim3((rows + STOP_WAVES - 1) / STOP_WAVES), dim3(STOP_NT), 0, static_cast<hipStream_t>(stream),
+                     st);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_stop_check_kernel launch");
   return QQQ_OK;
 }
 

@@ -16,6 +16,7 @@ sequence that ends frees its blocks at once, and prompts the pool could not hold
 from __future__ import annotations
 
 from collections import deque
+from operator import index as _index
 from typing import List, NamedTuple, Optional, Sequence
 
 import torch
@@ -46,6 +47,53 @@ class TokenLogprobs(NamedTuple):
     @classmethod
     def empty(cls, k: int) -> "TokenLogprobs":
         return cls(torch.empty(0), torch.empty(0, dtype=torch.int32), torch.empty((0, k), dtype=torch.int32), torch.empty((0, k)))
+
+
+def stop_arguments(name: str, vocab: int, stop, stop_token_ids, min_new_tokens):
+    """generate()'s `stop`, `stop_token_ids` and `min_new_tokens`, checked -> (the stop sequences as lists, the stop ids, the minimum):
+    at most 32 sequences of 1 ... 32 ids, at most 32 stop ids, every id in [0, vocab), a minimum >= 0.  `name` heads the messages."""
+    def token(arg, t):
+        try:
+            t = None if isinstance(t, bool) else _index(t)
+        except TypeError:
+            t = None
+        if t is None or not 0 <= t < vocab:
+            raise ValueError(f"{name}: {arg} holds an entry that is no token id in [0, {vocab})")
+        return t
+
+    def rows(arg, value, what):
+        # a sequence of any kind (a list, a tuple, an array, a tensor), None for none; a string or a scalar is not one
+        if value is None:
+            return []
+        if isinstance(value, (str, bytes)):
+            raise ValueError(f"{name}: {arg} must be {what}, not a string (encode stop strings first)")
+        try:
+            return list(value)
+        except TypeError:
+            raise ValueError(f"{name}: {arg} must be {what}") from None
+
+    stops = [[token("stop", t) for t in rows("stop", s, "a sequence of token-id sequences")]
+             for s in rows("stop", stop, "a sequence of token-id sequences")]
+    if len(stops) > 32 or any(not 1 <= len(s) <= 32 for s in stops):
+        raise ValueError(f"{name}: stop takes at most 32 sequences of 1 ... 32 token ids each")
+    ids = [token("stop_token_ids", t) for t in rows("stop_token_ids", stop_token_ids, "a sequence of token ids")]
+    if len(ids) > 32:
+        raise ValueError(f"{name}: stop_token_ids takes at most 32 ids")
+    try:
+        least = -1 if isinstance(min_new_tokens, bool) else _index(min_new_tokens)
+    except TypeError:
+        least = -1
+    if least < 0:
+        raise ValueError(f"{name}: min_new_tokens={min_new_tokens!r} must be an int >= 0")
+    return stops, ids, least
+
+
+def stop_match(completion: Sequence[int], stops: Sequence[Sequence[int]]) -> int:
+    """the length of the first stop sequence (lowest index) the completion ends in, 0 for none: include/serving/stop/qqq_amd_stop.h, rule 2"""
+    for s in stops:
+        if len(s) <= len(completion) and list(completion[len(completion) - len(s):]) == list(s):
+            return len(s)
+    return 0
 
 
 class QuantLlamaModel(nn.Module):
@@ -215,7 +263,8 @@ class QuantLlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, cache: Optional[PagedKVCache] = None,
-                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False, n: int = 1, logprobs: Optional[int] = None,
+                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False, stop: Optional[Sequence[Sequence[int]]] = None,
+                 stop_token_ids: Optional[Sequence[int]] = None, min_new_tokens: int = 0, n: int = 1, logprobs: Optional[int] = None,
                  draft_len: int = 0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                  frequency_penalty: float = 0.0) -> List[List[int]]:
         """Generate up to `max_new_tokens` tokens for every prompt (token lists of any lengths) -> the generated ids per prompt, the
@@ -262,7 +311,21 @@ class QuantLlamaForCausalLM(nn.Module):
         top-p -- the model's distribution, not the truncated one the draw was made from.  The tokens are the same as without logprobs,
         draw for draw; the per-pass results stay on the device until the call returns (no further host sync per pass).
         device_loop=True builds the DecodeLoop with logprobs=k.  logprobs with draft_len > 0 raises: the speculative loop emits several
-        tokens per row and step."""
+        tokens per row and step.
+
+        stop, stop_token_ids, min_new_tokens (None, None, 0: off, and then nothing of it runs) are the further ways a completion -- what
+        the call returns for one prompt or sibling -- ends.  stop_token_ids (at most 32 ids) are further eos ids: drawing one ends the
+        completion and the token is included.  stop (at most 32 sequences of 1 ... 32 token ids; encode stop strings first): once the
+        completion ends in one of them it ends and is cut IN FRONT of the match (vLLM's `stop` without include_stop_str_in_output); the
+        match lies in the completion alone, never in the prompt, the earliest end wins and at one end eos_token_id and the stop ids go
+        before a sequence (a completion that ends in its eos keeps it, also where a stop sequence ends in the same token), then the
+        sequence given first.  min_new_tokens=M: while the completion has fewer than M tokens, eos_token_id and every stop id have
+        their logit set to -inf by ops.ban_tokens in the row the sampler draws from -- after the penalties, before temperature, top-k and
+        top-p, so logprobs=k records show the banned row -- and no stop sequence is tested at a length below M; the cut may still leave
+        fewer than M tokens, as in vLLM, and the budget max_new_tokens wins over M.  logprobs records are cut like their tokens.  On the
+        host path the matching is plain Python in the bookkeeping; device_loop=True builds the loop with stops=True, whose captured
+        step runs ops.ban_tokens and ops.stop_check (no host sync per token); a speculative step that emits several tokens is checked at
+        every new length in order, and tokens behind a match are dropped."""
         n = int(n)
         if n < 1:
             raise ValueError(f"generate: n={n} must be at least 1")
@@ -286,6 +349,11 @@ class QuantLlamaForCausalLM(nn.Module):
         if logprobs is not None:
             loop_kw["logprobs"] = logprobs  # ... and without logprobs
         gen_kw = dict(zip(("repetition_penalty", "presence_penalty", "frequency_penalty"), penalty)) if penalised else {}
+        vocab = self.lm_head.weight.shape[0]
+        stops, end_ids, least = stop_arguments("generate", vocab, stop, stop_token_ids, min_new_tokens)
+        if stops or end_ids or least:  # ... and without stops
+            loop_kw["stops"] = True
+            gen_kw.update(stop=stops, stop_token_ids=end_ids, min_new_tokens=least)
         prompts = [list(p) for p in prompts]
         if any(not p for p in prompts):
             raise ValueError("generate: every prompt needs at least one token")
@@ -334,6 +402,11 @@ class QuantLlamaForCausalLM(nn.Module):
         cur = None  # int64 [len(running)] on the device: the running sequences' last tokens
 
         workspace = torch.zeros(len(out) * self.lm_head.weight.shape[0], dtype=torch.int32, device=dev) if penalised else None
+        ends = set(end_ids) | (set() if eos_token_id is None else {int(eos_token_id)})  # the tokens that end a completion, and stay in it
+        if least:
+            ban_ids = torch.tensor(end_ids, dtype=torch.int32, device=dev) if end_ids else None
+            eos_row = torch.full((len(out),), -1 if eos_token_id is None else int(eos_token_id), dtype=torch.int32, device=dev)
+            least_row = torch.full((len(out),), least, dtype=torch.int32, device=dev)
 
         def sample(ids, step, seqs, repeat=1):
             logits = self(ids, cache, step)
@@ -346,6 +419,9 @@ class QuantLlamaForCausalLM(nn.Module):
                 ops.penalize_logits(logits, torch.tensor([h[-1] for h in hist], dtype=torch.int64, device=dev),
                                     torch.tensor([len(h) - 1 for h in hist], dtype=torch.int64, device=dev), seen,
                                     torch.tensor([len(prompts[i // n]) for i in seqs], dtype=torch.int32, device=dev), *penalty, workspace)
+            if least and any(len(out[i]) < least for i in seqs):  # the host has the counts: a pass of rows at their minimum runs nothing
+                ops.ban_tokens(logits, torch.tensor([len(out[i]) for i in seqs], dtype=torch.int32, device=dev), least_row[:len(seqs)],
+                               eos_row[:len(seqs)], ban_ids, base=0)
             u = torch.rand(logits.shape[0], generator=generator, device=logits.device)
             toks = ops.sample_tokens(logits, temperature, top_k, top_p, u)
             if logprobs is not None:  # of the rows the sampler drew from; kept on the device until the call returns
@@ -363,7 +439,12 @@ class QuantLlamaForCausalLM(nn.Module):
             alive, rows, done = [], [], []
             for row, (i, t) in enumerate(zip(seqs, toks.tolist())):
                 out[i].append(t)
-                if len(out[i]) >= max_new_tokens or (eos_token_id is not None and t == eos_token_id):
+                cut = 0 if t in ends or len(out[i]) < least else stop_match(out[i], stops)
+                if cut:  # the completion ends in front of the match, its records with it
+                    del out[i][len(out[i]) - cut:]
+                    if logprobs is not None:
+                        del lp_rows[i][len(out[i]):]
+                if len(out[i]) >= max_new_tokens or t in ends or cut:
                     if not fork or i % n == 0:
                         done.append(i)
                 else:
@@ -378,30 +459,38 @@ class QuantLlamaForCausalLM(nn.Module):
         def take(toks, rows):
             return toks if len(rows) == toks.shape[0] else toks[torch.tensor(rows, dtype=torch.int64, device=toks.device)]
 
-        while waiting or running:
-            if running:
-                toks = sample(cur, cache.step([sid(i) for i in running], [1] * len(running)), running)
-                running, rows = settle(running, toks)
-                cur = take(toks, rows)
-            new = []
-            owed = sum(need[i // n] - len(cache.blocks(sid(i))) for i in running)  # what the running sequences may still take
-            while waiting and fam_need[waiting[0]] <= cache.free_blocks - owed:
-                i = waiting.popleft()
-                cache.add(sid(i * n))
-                owed += fam_need[i]
-                new.append(i)
-            if not new:
-                if not running and waiting:
-                    raise RuntimeError(f"generate: the pool's {cache.free_blocks} free blocks cannot hold a prompt that needs "
-                                       f"{fam_need[waiting[0]]} (prompt and budget)")
-                continue
-            ids = torch.tensor([t for i in new for t in prompts[i]], dtype=torch.int64, device=dev)
-            born = [i * n + j for i in new for j in range(n)]
-            toks = sample(ids, cache.step([sid(i * n) for i in new], [len(prompts[i]) for i in new]), born, repeat=n)
-            alive, rows = settle(born, toks, fork=n > 1)
-            first = take(toks, rows)
-            cur = first if not running else torch.cat([cur, first])
-            running = running + alive
+        try:
+            while waiting or running:
+                if running:
+                    toks = sample(cur, cache.step([sid(i) for i in running], [1] * len(running)), running)
+                    running, rows = settle(running, toks)
+                    cur = take(toks, rows)
+                new = []
+                owed = sum(need[i // n] - len(cache.blocks(sid(i))) for i in running)  # what the running sequences may still take
+                while waiting and fam_need[waiting[0]] <= cache.free_blocks - owed:
+                    i = waiting.popleft()
+                    cache.add(sid(i * n))
+                    owed += fam_need[i]
+                    new.append(i)
+                if not new:
+                    if not running and waiting:
+                        raise RuntimeError(f"generate: the pool's {cache.free_blocks} free blocks cannot hold a prompt that needs "
+                                           f"{fam_need[waiting[0]]} (prompt and budget)")
+                    continue
+                ids = torch.tensor([t for i in new for t in prompts[i]], dtype=torch.int64, device=dev)
+                born = [i * n + j for i in new for j in range(n)]
+                toks = sample(ids, cache.step([sid(i * n) for i in new], [len(prompts[i]) for i in new]), born, repeat=n)
+                alive, rows = settle(born, toks, fork=n > 1)
+                first = take(toks, rows)
+                cur = first if not running else torch.cat([cur, first])
+                running = running + alive
+        except BaseException:  # leave the caller's pool as it was found
+            for i in range(len(out)):
+                try:
+                    cache.free(sid(i))
+                except KeyError:  # ended, or never admitted
+                    pass
+            raise
         return result()
 
     def score(self, sequences: Sequence[Sequence[int]], cache: Optional[PagedKVCache] = None, chunk_tokens: int = 2048, block_size: int = 16,

@@ -1964,3 +1964,185 @@ def topk_logprobs_step(logits: torch.Tensor, out: torch.Tensor, n_out: torch.Ten
     if _compiling(*args):
         return _topk_logprobs_step_op(*args)
     return _topk_logprobs_step_impl(*args)
+
+
+# ---- stop sequences, stop token ids and the minimum length (include/serving/stop/qqq_amd_stop.h): the ban in front of a sampler, the
+# check behind a decode loop's step
+
+def _rows_i32_check(op, rows, named):
+    for name, t in named:
+        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != rows:
+            raise RuntimeError(f"{op}: {name} must be int32 [{rows}], not {_dt(t.dtype)} {tuple(t.shape)}")
+
+
+def _id_list_check(op, name, t):
+    if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] > 32:
+        raise RuntimeError(f"{op}: {name} must be int32 [at most 32], not {_dt(t.dtype)} {tuple(t.shape)}")
+
+
+def _ban_tokens_check(logits, n_out, min_new, eos, ban_ids, base):
+    # dtypes, shapes and strides -> (rows, group, vocab)
+    op = "ban_tokens"
+    if logits.dtype != torch.float16 or logits.dim() != 2:
+        raise RuntimeError(f"{op}: logits must be fp16 [rows * group, vocab]")
+    m, vocab = logits.shape
+    if n_out.dtype != torch.int32 or n_out.dim() != 1:
+        raise RuntimeError(f"{op}: n_out must be int32 [rows], not {_dt(n_out.dtype)} {tuple(n_out.shape)}")
+    rows = n_out.shape[0]
+    group = m // rows if rows else 1
+    if m != rows * group or not 1 <= group <= 16:
+        raise RuntimeError(f"{op}: logits hold {m} rows, n_out {tuple(n_out.shape)} asks for rows * group with 1 <= group <= 16")
+    _rows_i32_check(op, rows, (("min_new", min_new), ("eos", eos)))
+    _id_list_check(op, "ban_ids", ban_ids)
+    if vocab < 1 or vocab > 262144 or m > 65535:
+        raise RuntimeError(f"{op}: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows * group <= 65535")
+    if m and (logits.stride(1) != 1 or logits.stride(0) < vocab):
+        raise RuntimeError(f"{op}: logits must have unit column stride and a row stride >= vocab (they are rewritten in place, never "
+                           f"copied), not strides {tuple(logits.stride())}")
+    return rows, group, vocab
+
+
+def _ban_tokens_impl(logits, n_out, min_new, eos, ban_ids, base):
+    ts = (logits, n_out, min_new, eos, ban_ids)
+    _same_gpu("ban_tokens", ts)
+    rows, group, vocab = _ban_tokens_check(*ts, base)
+    if rows == 0:
+        return
+    _in_place_check("ban_tokens", (("n_out", n_out), ("min_new", min_new), ("eos", eos), ("ban_ids", ban_ids)))
+    err = _lib.lib().qqq_ban_tokens(_ptr(logits), logits.stride(0), _ptr(n_out), base, _ptr(min_new), _ptr(eos), _ptr(ban_ids),
+                                    ban_ids.shape[0], group, rows, vocab, logits.device.index or 0, _stream_for(logits))
+    _raise_lib("ban_tokens", err)
+
+
+@torch.library.custom_op("qqq_amd::ban_tokens", mutates_args=("logits",))
+def _ban_tokens_op(logits: torch.Tensor, n_out: torch.Tensor, min_new: torch.Tensor, eos: torch.Tensor, ban_ids: torch.Tensor,
+                   base: int) -> None:
+    _ban_tokens_impl(logits, n_out, min_new, eos, ban_ids, base)
+
+
+@_ban_tokens_op.register_fake
+def _(logits, n_out, min_new, eos, ban_ids, base):
+    _ban_tokens_check(logits, n_out, min_new, eos, ban_ids, base)
+
+
+def ban_tokens(logits: torch.Tensor, n_out: torch.Tensor, min_new: torch.Tensor, eos: torch.Tensor,
+               ban_ids: Optional[torch.Tensor] = None, base: int = 0) -> torch.Tensor:
+    """The minimum length of a completion on fp16 logits [rows * G, vocab], in place and in one launch, in front of sample_tokens,
+    sample_advance or spec_advance (behind penalize_logits) -> `logits`.
+
+    n_out        int32 [rows]: the tokens a row has emitted;  base  an int added to it (the loops pass 1: n_out does not count the
+                 prefill's token; admission and the host path pass 0 and their own counts)
+    min_new      int32 [rows]: the row's minimum length;  eos  int32 [rows]: the row's eos id, -1 for none
+    ban_ids      int32 [at most 32] or None: the stop token ids, shared by the rows
+    Logits row r * G + j (G = logits rows / rows, at most 16) is the one the completion's token of index n_out[r] + base + j is drawn from:
+    if that index is below min_new[r], the row's eos and every ban id become -inf there.  Ids outside [0, vocab) are ignored; every other
+    entry keeps its bits.  The exact semantics are stated in include/serving/stop/qqq_amd_stop.h.  Nothing is read on the host and the
+    launch size depends on the shapes alone, so a step with this call in it replays from a captured graph.  The logits are never
+    copied: unit column stride and a row stride >= vocab, or it raises."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(n_out, torch.Tensor) or logits.dim() != 2 or n_out.dim() != 1:
+        raise RuntimeError("ban_tokens: logits must be an fp16 [rows * group, vocab] tensor and n_out an int32 [rows] tensor")
+    if ban_ids is None:
+        ban_ids = n_out.new_empty((0,), dtype=torch.int32)
+    args = (logits, n_out, min_new, eos, ban_ids, int(base))
+    if _compiling(*args[:5]):
+        _ban_tokens_op(*args)
+    else:
+        _ban_tokens_impl(*args)
+    return logits
+
+
+def _stop_check_check(tokens, base, first, n_out, stop_ids, stop_len, end_ids, eos, min_new, n_seen, n_trim, stop_hit, ids, pos, slots,
+                      start, remaining):
+    # dtypes and shapes -> (rows, group)
+    op = "stop_check"
+    if tokens.dtype not in (torch.int32, torch.int64) or tokens.dim() != 2 or tokens.shape[1] < 1:
+        raise RuntimeError(f"{op}: tokens must be int32 or int64 [rows, stride >= 1], not {_dt(tokens.dtype)} {tuple(tokens.shape)}")
+    rows = tokens.shape[0]
+    if ids.dtype != torch.int64 or ids.dim() not in (1, 2) or ids.shape[0] != rows or (ids.dim() == 2 and not 1 <= ids.shape[1] <= 16):
+        raise RuntimeError(f"{op}: ids must be int64 [{rows}] or [{rows}, group] with 1 <= group <= 16, not {_dt(ids.dtype)} {tuple(ids.shape)}")
+    group = ids.shape[1] if ids.dim() == 2 else 1
+    for name, t in (("pos", pos), ("slots", slots)):
+        if t.dtype != torch.int64 or t.shape != ids.shape:
+            raise RuntimeError(f"{op}: {name} must be int64 {tuple(ids.shape)} like ids, not {_dt(t.dtype)} {tuple(t.shape)}")
+    if start is not None and (start.dtype != torch.int64 or start.dim() != 1 or start.shape[0] != rows):
+        raise RuntimeError(f"{op}: start must be int64 [{rows}] or None, not {_dt(start.dtype)} {tuple(start.shape)}")
+    named = [("base", base), ("n_out", n_out), ("min_new", min_new), ("n_seen", n_seen), ("n_trim", n_trim), ("stop_hit", stop_hit),
+             ("remaining", remaining)] + ([("first", first)] if first is not None else []) + ([("eos", eos)] if eos is not None else [])
+    _rows_i32_check(op, rows, named)
+    if stop_ids.dtype != torch.int32 or stop_ids.dim() != 2 or stop_ids.shape[0] > 32 or not 1 <= stop_ids.shape[1] <= 32:
+        raise RuntimeError(f"{op}: stop_ids must be int32 [n_stop <= 32, 1 <= stop_stride <= 32], not {_dt(stop_ids.dtype)} "
+                           f"{tuple(stop_ids.shape)}")
+    if stop_len.dtype != torch.int32 or tuple(stop_len.shape) != (stop_ids.shape[0],):
+        raise RuntimeError(f"{op}: stop_len must be int32 [{stop_ids.shape[0]}], one entry per stop sequence, not {_dt(stop_len.dtype)} "
+                           f"{tuple(stop_len.shape)}")
+    _id_list_check(op, "end_ids", end_ids)
+    if rows > 65535:
+        raise RuntimeError(f"{op}: rows={rows} exceeds 65535")
+    return rows, group
+
+
+def _stop_check_impl(tokens, base, first, n_out, stop_ids, stop_len, end_ids, eos, min_new, n_seen, n_trim, stop_hit, ids, pos, slots,
+                     start, remaining):
+    args = (tokens, base, first, n_out, stop_ids, stop_len, end_ids, eos, min_new, n_seen, n_trim, stop_hit, ids, pos, slots, start,
+            remaining)
+    names = ("tokens", "base", "first", "n_out", "stop_ids", "stop_len", "end_ids", "eos", "min_new", "n_seen", "n_trim", "stop_hit", "ids",
+             "pos", "slots", "start", "remaining")
+    given = [(n, t) for n, t in zip(names, args) if t is not None]
+    _same_gpu("stop_check", [t for _, t in given])
+    rows, group = _stop_check_check(*args)
+    if rows == 0:
+        return
+    _in_place_check("stop_check", given)
+    err = _lib.lib().qqq_stop_check(_ptr(tokens), tokens.element_size(), tokens.shape[1], _ptr(base), _ptr(first), _ptr(n_out),
+                                    _ptr(stop_ids), stop_ids.shape[1], _ptr(stop_len), stop_ids.shape[0], _ptr(end_ids), end_ids.shape[0],
+                                    _ptr(eos), _ptr(min_new), _ptr(n_seen), _ptr(n_trim), _ptr(stop_hit), _ptr(ids), _ptr(pos), _ptr(slots), _ptr(start),
+                                    _ptr(remaining), group, rows, tokens.device.index or 0, _stream_for(tokens))
+    _raise_lib("stop_check", err)
+
+
+@torch.library.custom_op("qqq_amd::stop_check", mutates_args=("n_seen", "n_trim", "stop_hit", "ids", "pos", "slots", "start", "remaining"))
+def _stop_check_op(tokens: torch.Tensor, base: torch.Tensor, first: Optional[torch.Tensor], n_out: torch.Tensor, stop_ids: torch.Tensor,
+                   stop_len: torch.Tensor, end_ids: torch.Tensor, eos: Optional[torch.Tensor], min_new: torch.Tensor, n_seen: torch.Tensor,
+                   n_trim: torch.Tensor, stop_hit: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor,
+                   start: Optional[torch.Tensor], remaining: torch.Tensor) -> None:
+    _stop_check_impl(tokens, base, first, n_out, stop_ids, stop_len, end_ids, eos, min_new, n_seen, n_trim, stop_hit, ids, pos, slots, start,
+                     remaining)
+
+
+@_stop_check_op.register_fake
+def _(tokens, base, first, n_out, stop_ids, stop_len, end_ids, eos, min_new, n_seen, n_trim, stop_hit, ids, pos, slots, start, remaining):
+    _stop_check_check(tokens, base, first, n_out, stop_ids, stop_len, end_ids, eos, min_new, n_seen, n_trim, stop_hit, ids, pos, slots,
+                      start, remaining)
+
+
+def stop_check(tokens: torch.Tensor, base: torch.Tensor, first: Optional[torch.Tensor], n_out: torch.Tensor, stop_ids: torch.Tensor,
+               stop_len: torch.Tensor, min_new: torch.Tensor, n_seen: torch.Tensor, n_trim: torch.Tensor, stop_hit: torch.Tensor,
+               ids: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor, remaining: torch.Tensor, start: Optional[torch.Tensor] = None,
+               end_ids: Optional[torch.Tensor] = None, eos: Optional[torch.Tensor] = None) -> None:
+    """A decode loop's stop epilogue, behind sample_advance / spec_advance (and topk_logprobs_step): a row whose completion has run into a
+    stop sequence or a stop token id retires, in one launch.  Returns nothing; n_seen, n_trim, stop_hit, ids, pos, slots, start and
+    remaining are updated in place.
+
+    tokens, base, first   the completion of row r has n_out[r] + 1 tokens; token i is first[r] if base[r] + i < 0, else
+                 tokens[r, base[r] + i].  tokens int32 or int64 [rows, stride], base int32 [rows], first int32 [rows] or None.  DecodeLoop
+                 passes `out` with base -1 and the prefill's token, SpecDecodeLoop `hist` with base = the prompt's length
+    stop_ids, stop_len   int32 [n_stop <= 32, stop_stride <= 32] and int32 [n_stop]: the stop sequences and their lengths, 0 = unused
+    end_ids      int32 [at most 32] or None: the stop token ids, an entry < 0 unused
+    eos          int32 [rows] or None: the rows' eos ids (-1: none), the array the sampler's step took
+    min_new      int32 [rows]: no stop sequence is tested at a length below it;  n_seen  int32 [rows]: the length checked so far
+    n_trim, stop_hit   int32 [rows]: on a match, the tokens the caller drops from the completion's end and the entry that matched
+    ids, pos, slots   int64 [rows] or [rows, G <= 16];  start  int64 [rows] or None;  remaining  int32 [rows]: the row state to retire
+    Every length n_seen[r] < e <= n_out[r] + 1 is tested in order; the first that ends in the row's eos or in an end id (the token
+    stays; they go before a sequence that ends in the same token) or, from min_new[r] on, in a stop sequence (the completion is cut in
+    front of it) retires the row: ids 0, pos / slots / start -1, remaining 0.
+    Then n_seen[r] = n_out[r] + 1.  A row with nothing new writes nothing.  The exact semantics are stated in
+    include/serving/stop/qqq_amd_stop.h.  Nothing is read on the host and the launch size depends on the shapes alone, so a decode
+    step with this call in it replays from a captured graph."""
+    if not isinstance(tokens, torch.Tensor) or not isinstance(ids, torch.Tensor) or tokens.dim() != 2:
+        raise RuntimeError("stop_check: tokens must be an int32 or int64 [rows, stride] tensor and ids an int64 [rows] or [rows, group] tensor")
+    if end_ids is None:
+        end_ids = n_out.new_empty((0,), dtype=torch.int32)
+    args = (tokens, base, first, n_out, stop_ids, stop_len, end_ids, eos, min_new, n_seen, n_trim, stop_hit, ids, pos, slots, start, remaining)
+    if _compiling(*(t for t in args if t is not None)):
+        return _stop_check_op(*args)
+    return _stop_check_impl(*args)

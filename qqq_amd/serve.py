@@ -13,7 +13,8 @@ ops.sample_tokens), writes the admitted rows' state with indexed copies, replays
 steps.  A row that is idle (pos -1, slot -1, remaining 0) rides along in every step and is inert: see include/qqq_amd_step.h.
 
 generate() -- admission, prefill, the run / sync / retire loop and the cleanup -- exists once, on DecodeLoop.  SpecDecodeLoop inherits it
-and overrides _decode_step, _run, _start_call, _budget_words, _row_state, _penalty_state and _collect, and the attributes _tokens, _synced and _idle.
+and overrides _decode_step, _run, _start_call, _budget_words, _row_state, _penalty_state, _stop_state, _stop_check and _collect, and the
+attributes _tokens, _synced and _idle.
 """
 from __future__ import annotations
 
@@ -23,7 +24,7 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import ops
-from .model import TokenLogprobs
+from .model import TokenLogprobs, stop_arguments
 from .paged import PagedKVCache, PagedStep
 
 
@@ -67,6 +68,11 @@ class DecodeLoop:
                 [rows, max_len]) and `lp_top_ids` / `lp_top` (int32 / f32 [rows, max_len, k]), and its step runs ops.topk_logprobs_step
                 behind ops.sample_advance, inside the captured graph: every emitted token's log-probability, rank and k most probable
                 alternatives, from the logits row it was drawn from.  generate() then returns (tokens, records).  None: none of that exists.
+    stops       True: the loop owns what ops.ban_tokens and ops.stop_check take (include/serving/stop/qqq_amd_stop.h) -- min_new, n_seen,
+                n_trim, stop_hit, stop_base and first (int32 [rows]), the table stop_ids / stop_len (int32 [32, 32] / [32]) and the stop
+                token ids ban_ids (int32 [32], -1 = unused) -- and its step runs the ban between the penalties and the sampler and the
+                check behind the sampler (and the records), inside the captured graph; generate() then takes stop, stop_token_ids and
+                min_new_tokens.  The tables have fixed shapes, so one capture serves every call.  False: none of that exists.
     `captures` counts the captures: 1 for the life of the loop with graph=True.  The graph holds addresses: a model that is changed after
     the first generate() (fuse_*(), load_state_dict, .to()) needs a new loop."""
 
@@ -78,9 +84,10 @@ class DecodeLoop:
     family = 1                       # rows per slot: the completions of one prompt (DecodeLoop alone takes more than 1)
     penalties = False                # True: the step runs ops.penalize_logits in front of the sampler (_allocate_penalties)
     logprobs = None                  # k: the step runs ops.topk_logprobs_step behind the sampler (DecodeLoop alone takes it)
+    stops = False                    # True: the step runs ops.ban_tokens in front of the sampler and ops.stop_check behind it (_allocate_stops)
 
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, sync_every: int = 8, u_stride: int = 64, graph: bool = True,
-                 penalties: bool = False, family: int = 1, logprobs: Optional[int] = None):
+                 penalties: bool = False, family: int = 1, logprobs: Optional[int] = None, stops: bool = False):
         rows, max_len, sync_every, u_stride, family = int(rows), int(max_len), int(sync_every), int(u_stride), int(family)
         short = u_stride < sync_every and f"u_stride={u_stride} must cover the sync_every={sync_every} steps between two refills"
         dev = _check_loop("DecodeLoop", lm, cache, rows, max_len, sync_every, graph, short)
@@ -100,6 +107,9 @@ class DecodeLoop:
             self.lp_top = torch.zeros((rows, max_len, self.logprobs), dtype=torch.float32, device=dev)
         if penalties:  # this loop keeps no history of its own: the penalty op records a row's input token at its position
             self._allocate_penalties(torch.zeros((rows, max_len), dtype=torch.int32, device=dev))
+        if stops:  # the completion is the prefill's token and then `out`: index -1 of out is `first`
+            self._allocate_stops(-1)
+            self.first = torch.zeros(rows, dtype=torch.int32, device=dev)
         # the one step of every decode pass: its device tensors ARE the state arrays (a row's position is its last position)
         self.step = PagedStep(seq_ids=[None] * rows, counts=[1] * rows, starts=[0] * rows, max_len=max_len, decode=True, pos=self.pos,
                               slots=self.slots, block_table=self.block_table, last_pos=self.pos,
@@ -144,6 +154,27 @@ class DecodeLoop:
         self.frequency = torch.zeros(self.rows, **f32)
         self.penalty_workspace = torch.zeros(self.rows * self.lm.lm_head.weight.shape[0], **i32)  # zero between any two calls
 
+    def _allocate_stops(self, base: int) -> None:
+        """What ops.ban_tokens and ops.stop_check take, for a loop built with stops=True: every row idle and checked (n_seen = n_out + 1),
+        no stop sequence, no stop id, no minimum.  `base`: where a row's completion begins in its line of the `_tokens` array."""
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self.stops = True
+        self.min_new = torch.zeros(self.rows, **i32)
+        self.n_seen = torch.ones(self.rows, **i32)
+        self.n_trim = torch.zeros(self.rows, **i32)
+        self.stop_hit = torch.full((self.rows,), -1, **i32)
+        self.stop_base = torch.full((self.rows,), base, **i32)
+        self.stop_ids = torch.zeros((32, 32), **i32)
+        self.stop_len = torch.zeros(32, **i32)
+        self.ban_ids = torch.full((32,), -1, **i32)
+
+    def _ban(self, logits: torch.Tensor) -> None:
+        ops.ban_tokens(logits, self.n_out, self.min_new, self.eos, self.ban_ids, base=1)  # n_out does not count the prefill's token
+
+    def _stop_check(self) -> None:
+        ops.stop_check(self.out, self.stop_base, self.first, self.n_out, self.stop_ids, self.stop_len, self.min_new, self.n_seen,
+                       self.n_trim, self.stop_hit, self.ids, self.pos, self.slots, self.remaining, end_ids=self.ban_ids, eos=self.eos)
+
     def _penalize(self, logits: torch.Tensor) -> None:
         ops.penalize_logits(logits, self.ids, self.pos, self.seen, self.n_prompt, self.repetition, self.presence, self.frequency,
                             self.penalty_workspace)
@@ -154,10 +185,14 @@ class DecodeLoop:
         logits = self.lm(self.ids, self.cache, self.step)
         if self.penalties:
             self._penalize(logits)
+        if self.stops:
+            self._ban(logits)
         ops.sample_advance(logits, self.temperature, self.top_k, self.top_p, self.u, self.tick, self.ids, self.pos, self.slots,
                            self.block_table, self.remaining, self.eos, self.out, self.n_out, self.cache.block_size)
         if self.logprobs is not None:  # the row that just emitted a token has n_rec < n_out: its record, from the logits it was drawn from
             ops.topk_logprobs_step(logits, self.out, self.n_out, self.n_rec, self.lp, self.lp_rank, self.lp_top_ids, self.lp_top)
+        if self.stops:  # a row that eos or the budget just retired is checked too: its n_seen is behind its n_out
+            self._stop_check()
 
     def _capture(self) -> None:
         """Warm up and capture the step with every row idle (nothing but `tick` changes), on a side stream."""
@@ -203,11 +238,16 @@ class DecodeLoop:
         p, bs = len(prompt), self.cache.block_size
         table = blocks + [0] * (self.block_table.shape[1] - len(blocks))
         penalty = self._penalty_state(prompt) if self.penalties else {}
-        return dict(ids=first, pos=p, slots=blocks[p // bs] * bs + p % bs, block_table=table, **penalty)
+        stop = self._stop_state(prompt, first) if self.stops else {}
+        return dict(ids=first, pos=p, slots=blocks[p // bs] * bs + p % bs, block_table=table, **penalty, **stop)
 
     def _penalty_state(self, prompt: List[int]) -> dict:
         """What an admitted row of a loop with penalties writes besides: the prompt is what the row has seen (the op records the rest)."""
         return dict(n_prompt=len(prompt), seen=prompt + [0] * (self.seen.shape[1] - len(prompt)))
+
+    def _stop_state(self, prompt: List[int], first: int) -> dict:
+        """What an admitted row of a loop with stops writes besides: how ops.stop_check finds the completion's first token."""
+        return dict(first=first)
 
     def _collect(self, row: List[int], n_prompt: int, seq, n: dict) -> List[int]:
         """The tokens a finished row emitted, from its line `row` of the `_tokens` array and its synced counts `n`."""
@@ -219,7 +259,8 @@ class DecodeLoop:
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, repetition_penalty: float = 1.0,
-                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0) -> List[List[int]]:
+                 presence_penalty: float = 0.0, frequency_penalty: float = 0.0, stop: Optional[Sequence[Sequence[int]]] = None,
+                 stop_token_ids: Optional[Sequence[int]] = None, min_new_tokens: int = 0) -> List[List[int]]:
         """QuantLlamaForCausalLM.generate's contract -- up to `max_new_tokens` ids per prompt, the eos that ends a sequence included --
         served by this loop's rows: waiting prompts are admitted into idle rows, in order, whenever the pool's free blocks cover a
         prompt's whole budget (taken at once with PagedKVCache.reserve), prefilled eagerly in one packed step with their first token from
@@ -247,8 +288,19 @@ class DecodeLoop:
         TokenLogprobs of CPU tensors, one entry per emitted token, the eos included.  The first token's record comes from
         ops.topk_logprobs on the prefill's logits in admit(), the others from the step's ops.topk_logprobs_step; all of them are taken
         from the logits row the sampler drew from -- after the penalties, before temperature, top-k and top-p.  A finished row's
-        records are read back with its tokens; the run itself gains no host sync."""
+        records are read back with its tokens; the run itself gains no host sync.
+
+        stop, stop_token_ids, min_new_tokens (None, None, 0: none; QuantLlamaForCausalLM.generate states their meaning) need a loop built
+        with stops=True.  The call writes the stop table and the stop ids once; the step bans eos and the stop ids below the minimum
+        (ops.ban_tokens) and retires a row whose completion ends in a stop id or a stop sequence (ops.stop_check, which is given the rows' eos too: a row
+        the sampler retired on its eos keeps that token where a sequence ends in it), and a sync reads
+        n_trim with the counts: the tokens -- and records -- a finished row drops from its end.  admit() does the same for the first
+        token on the host: the ban on the prefill's logits, and a length-1 stop sequence that matches the first token leaves an empty
+        completion whose row never starts.  The keys the device wrote are still counted by n_out."""
         name = f"{self._name}.generate"
+        stops, end_ids, least = stop_arguments(name, self.lm.lm_head.weight.shape[0], stop, stop_token_ids, min_new_tokens)
+        if (stops or end_ids or least) and not self.stops:
+            raise ValueError(f"{name}: stop, stop_token_ids and min_new_tokens={least} need a loop built with stops=True")
         penalty = (float(repetition_penalty), float(presence_penalty), float(frequency_penalty))
         if not (penalty[0] > 0.0 and penalty[0] != float("inf")):
             raise ValueError(f"{name}: repetition_penalty={penalty[0]} must be finite and > 0")
@@ -276,7 +328,8 @@ class DecodeLoop:
                     recs.append(TokenLogprobs.empty(k_lp))
                     continue
                 head = TokenLogprobs.gather(firsts, [first_at[q]])
-                recs.append(TokenLogprobs(*(torch.cat(pair) for pair in zip(head, step_recs[q]))) if q in step_recs else head)
+                rec = TokenLogprobs(*(torch.cat(pair) for pair in zip(head, step_recs[q]))) if q in step_recs else head
+                recs.append(TokenLogprobs(*(t[:len(outs[q])] for t in rec)) if self.stops else rec)  # cut like the tokens
             if fam == 1:
                 return outs, recs
             return [outs[i * fam:(i + 1) * fam] for i in range(len(prompts))], [recs[i * fam:(i + 1) * fam] for i in range(len(prompts))]
@@ -306,6 +359,17 @@ class DecodeLoop:
             per_row.update(repetition=penalty[0], presence=penalty[1], frequency=penalty[2])
         if k_lp is not None:
             per_row.update(n_rec=0)  # with n_out: the step's records are counted like its tokens
+        synced_arrays = self._synced
+        if self.stops:  # the tables of the call, once; a row starts with its first token checked (by admit) and nothing to drop
+            table = torch.zeros((32, 32), dtype=torch.int32)
+            for j, s in enumerate(stops):
+                table[j, :len(s)] = torch.tensor(s, dtype=torch.int32)
+            self.stop_ids.copy_(table)
+            self.stop_len.copy_(torch.tensor([len(s) for s in stops] + [0] * (32 - len(stops)), dtype=torch.int32))
+            self.ban_ids.copy_(torch.tensor(end_ids + [-1] * (32 - len(end_ids)), dtype=torch.int32))
+            per_row.update(min_new=least, n_seen=1, n_trim=0, stop_hit=-1)
+            synced_arrays = self._synced + ("n_trim",)
+        ends = set(end_ids) | ({eos} if eos >= 0 else set())  # the tokens that end a completion, and stay in it
 
         def admit():
             new = []
@@ -340,6 +404,9 @@ class DecodeLoop:
                 at_last = torch.tensor([n - 1 for n in lens], dtype=torch.int64, device=dev)
                 ops.penalize_logits(logits, torch.tensor([prompts[q // fam][-1] for _, q in born], dtype=torch.int64, device=dev), at_last,
                                     seen, torch.tensor(lens, dtype=torch.int32, device=dev), *penalty, self.penalty_workspace)
+            if least:  # the first token is index 0 of the completion: below any minimum
+                count = torch.zeros(len(born), dtype=torch.int32, device=dev)
+                ops.ban_tokens(logits, count, torch.full_like(count, least), torch.full_like(count, eos), self.ban_ids, base=0)
             u = torch.rand(len(born), generator=generator, device=dev)
             first = ops.sample_tokens(logits, temperature, top_k, top_p, u)
             if k_lp is not None:  # the first token's record: the plain op on the rows the sampler drew from
@@ -354,7 +421,10 @@ class DecodeLoop:
             rows, state, ended = [], {}, []
             for (r, q), t in zip(born, first):
                 outs[q].append(t)
-                if max_new_tokens == 1 or t == eos:
+                cut = least <= 1 and t not in ends and [t] in stops  # a length-1 stop sequence: the completion is empty
+                if cut:
+                    del outs[q][:]
+                if max_new_tokens == 1 or t in ends or cut:
                     if q % fam == 0:
                         ended.append((r, q))  # its siblings are forked from it first
                     continue
@@ -390,7 +460,7 @@ class DecodeLoop:
                         continue
                     break
                 self._run(min(self.sync_every, max(budget[r] for r in active)), generator)
-                synced = dict(zip(self._synced, torch.stack([getattr(self, a) for a in self._synced]).tolist()))  # the sync: one transfer
+                synced = dict(zip(synced_arrays, torch.stack([getattr(self, a) for a in synced_arrays]).tolist()))  # the sync: one transfer
                 remaining = synced["remaining"]
                 done = [r for r in active if remaining[r] == 0]
                 for r in active:
@@ -405,6 +475,8 @@ class DecodeLoop:
                     for r, row in zip(done, toks):
                         i = owner[r]
                         outs[i].extend(self._collect(row, len(prompts[i // fam]), sid(i), {a: v[r] for a, v in synced.items()}))
+                        if self.stops and synced["n_trim"][r] > 0:  # what ops.stop_check found behind the completion's end
+                            del outs[i][max(0, len(outs[i]) - synced["n_trim"][r]):]
                         cache.free(sid(i))
                         owner[r] = None
                     if fam > 1:
@@ -418,6 +490,9 @@ class DecodeLoop:
                 getattr(self, array).fill_(value)
             if k_lp is not None:
                 self.n_rec.copy_(self.n_out)  # no row owes a record
+            if self.stops:
+                self.n_seen.copy_(self.n_out + 1)  # ... or a check
+                self.n_trim.zero_()
             raise
         return result()
 
@@ -475,7 +550,7 @@ class SpecDecodeLoop(DecodeLoop):
     _idle = DecodeLoop._idle + (("start", -1),)
 
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, draft_len: int = 4, ngram_max: int = 3, sync_every: int = 8,
-                 u_stride: Optional[int] = None, graph: bool = True, penalties: bool = False, family: int = 1):
+                 u_stride: Optional[int] = None, graph: bool = True, penalties: bool = False, family: int = 1, stops: bool = False):
         rows, max_len, sync_every, draft_len, ngram_max = int(rows), int(max_len), int(sync_every), int(draft_len), int(ngram_max)
         if int(family) != 1:
             raise ValueError(f"SpecDecodeLoop: family={family} is not supported (a chunk of draft_len + 1 tokens per row has no "
@@ -507,6 +582,8 @@ class SpecDecodeLoop(DecodeLoop):
         self.n_acc = torch.zeros(rows, **i32)
         if penalties:  # the history the drafter reads is what the rows have seen; the op's write into it is the identity
             self._allocate_penalties(self.hist)
+        if stops:  # the completion is what follows the prompt in hist: stop_base is the prompt's length, written on admission
+            self._allocate_stops(0)
         # the one step of every pass: a chunk of G tokens per row whose device tensors ARE the state arrays
         self.step = PagedStep(seq_ids=[None] * rows, counts=[group] * rows, starts=[0] * rows, max_len=max_len, decode=False,
                               pos=self.pos.view(-1), slots=self.slots.view(-1), block_table=self.block_table, last_pos=self.start,
@@ -516,9 +593,17 @@ class SpecDecodeLoop(DecodeLoop):
         logits = self.lm(self.ids.view(-1), self.cache, self.step, all_rows=True)
         if self.penalties:
             self._penalize(logits)
+        if self.stops:  # logits row j of a row is the one its completion's token n_out + 1 + j is drawn from
+            self._ban(logits)
         ops.spec_advance(logits, self.temperature, self.top_k, self.top_p, self.u, self.tick, self.ids, self.pos, self.slots, self.start,
                          self.block_table, self.remaining, self.eos, self.hist, self.hist_len, self.n_out, self.n_acc,
                          self.cache.block_size, self.ngram_max)
+        if self.stops:  # every length the step added, in order: the tokens behind a match are dropped with it
+            self._stop_check()
+
+    def _stop_check(self) -> None:
+        ops.stop_check(self.hist, self.stop_base, None, self.n_out, self.stop_ids, self.stop_len, self.min_new, self.n_seen, self.n_trim,
+                       self.stop_hit, self.ids, self.pos, self.slots, self.remaining, start=self.start, end_ids=self.ban_ids, eos=self.eos)
 
     def _run(self, steps: int, generator) -> None:
         super()._run(steps, generator)
@@ -540,6 +625,9 @@ class SpecDecodeLoop(DecodeLoop):
 
     def _penalty_state(self, prompt: List[int]) -> dict:
         return dict(n_prompt=len(prompt))  # `seen` is hist
+
+    def _stop_state(self, prompt: List[int], first: int) -> dict:
+        return dict(stop_base=len(prompt))  # the first token is hist[len(prompt)]
 
     def _collect(self, row: List[int], n_prompt: int, seq, n: dict) -> List[int]:
         self.accepted += n["n_acc"]

@@ -48,6 +48,16 @@ the rounds.  The op alone is in profiles/logprobs_bench.json (tools/bench_sample
 
     python tools/bench_generate.py --logprobs 0,5,20 [--batch 1,16] [--rounds 5] [--out profiles/logprobs_loop_bench.json]
 
+With --stops the tool times the replayed step with and without ops.ban_tokens and ops.stop_check in it, in one rotation: per batch and
+draft length K (default 0,4; 0 is DecodeLoop) a loop built with stops=True serving generate(stop=eight 4-token sequences,
+stop_token_ids=two ids, min_new_tokens=8) beside a loop built without, by the protocol above, and beside them the plain loop at
+sync_every=1 -- a host sync per step, the only way to honour a stop sequence without the two ops.  The stop sequences and ids are
+chosen not to occur (every run must emit all its tokens), so all three loops run the same steps.  Written to
+profiles/stop_loop_bench.json: the three step times with the rounds' min and max, the ops' difference to the plain step beside the spread
+of both runs over the rounds, and what a sync per step costs against it.  No threshold: the feature is opt-in.
+
+    python tools/bench_generate.py --stops [--draft-len 0,4] [--batch 1,16] [--rounds 5] [--out profiles/stop_loop_bench.json]
+
 With --n 1,4,8 the tool measures parallel sampling: per N one prompt of --prompt tokens (default 2048: sixteen 128-key chunks of the decode
 plan) served three ways by a captured DecodeLoop in one rotation -- `repeated`: the prompt N times in N rows (N prefills, N copies of its
 keys); `forked`: DecodeLoop(family=N) without fuse_shared() (one prefill, the prompt's blocks once, the plain paged decode op over the
@@ -379,6 +389,85 @@ def logprobs_main(args):
             f"k={k} {e['step_us']:.1f} (+{e['epilogue_us_per_step']})" for k, e in p["logprobs"].items()))
 
 
+def stops_point(lm, batch, drafts, rounds, dev):
+    import torch
+
+    from bench_model import VOCAB
+    from qqq_amd import DecodeLoop, SpecDecodeLoop
+
+    g = torch.Generator().manual_seed(batch)
+    prompts = [torch.randint(0, VOCAB, (PROMPT,), generator=g).tolist() for _ in range(batch)]
+    loops = {}  # key: (K, "plain" | "stops" | "sync1")
+    for k in drafts:
+        max_len = -(-(PROMPT + NEW - 1 + k) // BS) * BS
+        for name in ("plain", "stops", "sync1"):
+            cache = lm.new_cache(batch * (max_len // BS), BS)
+            kw = dict(rows=batch, max_len=max_len, sync_every=1 if name == "sync1" else SYNC_EVERY, **(dict(stops=True) if name == "stops" else {}))
+            loops[(k, name)] = SpecDecodeLoop(lm, cache, draft_len=k, **kw) if k else DecodeLoop(lm, cache, **kw)
+
+    free = loops[(drafts[0], "plain")].generate(prompts, NEW)
+    emitted = {t for o in free for t in o}
+    unused = [t for t in range(VOCAB) if t not in emitted]  # the speculative loop may leave the plain loop's tokens at a near-tie: asserted below
+    stops = dict(stop=[unused[4 * i:4 * i + 4] for i in range(8)], stop_token_ids=unused[32:34], min_new_tokens=8)
+
+    def timed(key, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = loops[key].generate(prompts, n, **(stops if key[1] == "stops" else {}))
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    steps = {}
+    for key, loop in loops.items():  # warm-up: code objects, workspaces, rope tables, the capture
+        timed(key, 1)
+        assert all(len(o) == NEW for o in timed(key, NEW)[1]), key  # no stop occurred: the loops ran the same steps
+        steps[key] = loop.steps if key[0] else NEW - 1
+    values = {key: [] for key in loops}
+    for _ in range(rounds):
+        for key in loops:
+            short, full = timed(key, 1)[0], timed(key, NEW)[0]
+            values[key].append((full - short) / steps[key] * 1e6)
+    res = {"batch": batch, "prompt_tokens": PROMPT, "new_tokens": NEW, "layers": LAYERS, "draft_len": {}}
+    for k in drafts:
+        e = {}
+        for name in ("plain", "stops", "sync1"):
+            v = values[(k, name)]
+            e[name] = {"steps": steps[(k, name)], "sync_every": 1 if name == "sync1" else SYNC_EVERY, "step_us": round(statistics.median(v), 1),
+                       "step_us_min": round(min(v), 1), "step_us_max": round(max(v), 1), "rounds_step_us": [round(x, 1) for x in v]}
+        e["ops_us_per_step"] = round(e["stops"]["step_us"] - e["plain"]["step_us"], 1)
+        e["plain_round_spread_us"] = round(e["plain"]["step_us_max"] - e["plain"]["step_us_min"], 1)
+        e["stops_round_spread_us"] = round(e["stops"]["step_us_max"] - e["stops"]["step_us_min"], 1)
+        e["ops_exceed_both_spreads"] = bool(e["ops_us_per_step"] > max(e["plain_round_spread_us"], e["stops_round_spread_us"]))
+        e["sync_per_step_us_over_plain"] = round(e["sync1"]["step_us"] - e["plain"]["step_us"], 1)
+        res["draft_len"][str(k)] = e
+    return res
+
+
+def stops_main(args):
+    import torch
+
+    from bench_model import build
+
+    drafts = sorted({int(k) for k in (args.draft_len or "0,4").split(",")})
+    dev = torch.device("cuda:0")
+    lm = build(LAYERS, dev).fuse_prefill()
+    with torch.no_grad():
+        points = [stops_point(lm, b, drafts, args.rounds, dev) for b in map(int, args.batch.split(","))]
+    out = {"tool": "tools/bench_generate.py --stops", "device": torch.cuda.get_device_name(0),
+           "shape": "Llama-2-7B layers, per-channel W4A8, fuse_qkv(), fuse_prefill(), paged fp16 cache, block 16, greedy, ngram_max 3",
+           "stops": "eight 4-token stop sequences, two stop token ids, min_new_tokens 8; none occurs", "sync_every": SYNC_EVERY,
+           "rounds": args.rounds, "points": points}
+    path = args.out or os.path.join(ROOT, "profiles", "stop_loop_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"batch {p['batch']:3d}: " + "  ".join(
+            f"K={k} plain {e['plain']['step_us']:.1f} stops {e['stops']['step_us']:.1f} us/step (+{e['ops_us_per_step']}, spreads "
+            f"{e['plain_round_spread_us']} / {e['stops_round_spread_us']}) sync_every=1 {e['sync1']['step_us']:.1f}" for k, e in p["draft_len"].items()))
+
+
 def parallel_point(lm, n, prompt_len, rounds, dev):
     import torch
 
@@ -487,6 +576,8 @@ def main():
                     "(profiles/penalty_loop_bench.json)")
     ap.add_argument("--logprobs", default=None, help="e.g. 0,5,20: time the replayed step with and without ops.topk_logprobs_step "
                     "(profiles/logprobs_loop_bench.json)")
+    ap.add_argument("--stops", action="store_true", help="time the replayed step with and without ops.ban_tokens and ops.stop_check, and "
+                    "the plain loop at sync_every=1 (profiles/stop_loop_bench.json)")
     ap.add_argument("--out", default=None, help="default profiles/decode_loop_bench.json, or profiles/spec_decode_bench.json with --draft-len")
     args = ap.parse_args()
     import torch
@@ -499,6 +590,8 @@ def main():
         return penalty_main(args)
     if args.logprobs:
         return logprobs_main(args)
+    if args.stops:
+        return stops_main(args)
     if args.draft_len:
         return spec_main(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "decode_loop_bench.json")
