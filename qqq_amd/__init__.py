@@ -81,7 +81,8 @@ from .qlinear import QuantLinear, fuse_quant_linears  # noqa: F401
 from .blocks import QuantLlamaMLP, QuantRMSNorm  # noqa: F401
 from .attention import KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer  # noqa: F401
 from .paged import PagedKVCache, PagedStep  # noqa: F401
-from .model import QuantLlamaForCausalLM, QuantLlamaModel, TokenLogprobs  # noqa: F401
+from .request import TokenLogprobs  # noqa: F401
+from .model import QuantLlamaForCausalLM, QuantLlamaModel  # noqa: F401
 from .serve import DecodeLoop, SpecDecodeLoop, ngram_draft  # noqa: F401
 from .score import pack_steps  # noqa: F401
 

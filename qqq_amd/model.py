@@ -16,84 +16,17 @@ sequence that ends frees its blocks at once, and prompts the pool could not hold
 from __future__ import annotations
 
 from collections import deque
-from operator import index as _index
-from typing import List, NamedTuple, Optional, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import ops, serve
 from .attention import KVCache, QuantLlamaDecoderLayer
 from .blocks import QuantRMSNorm
 from .paged import PagedKVCache, PagedStep
-
-
-class TokenLogprobs(NamedTuple):
-    """What generate(logprobs=k) returns per completion, one entry per emitted token (the eos included), as CPU tensors: the token's
-    log-probability (f32 [T]) and rank (int32 [T], 1 = the most probable), and the k most probable tokens of its step with their
-    log-probabilities (int32 / f32 [T, k]); see ops.topk_logprobs."""
-    logprob: torch.Tensor
-    rank: torch.Tensor
-    top_ids: torch.Tensor
-    top_logprobs: torch.Tensor
-
-    @classmethod
-    def gather(cls, parts, index) -> "TokenLogprobs":
-        """the records at `index` (a list of rows) of the four CPU tensors `parts`"""
-        at = torch.tensor(index, dtype=torch.int64)
-        return cls(*(p[at] for p in parts))
-
-    @classmethod
-    def empty(cls, k: int) -> "TokenLogprobs":
-        return cls(torch.empty(0), torch.empty(0, dtype=torch.int32), torch.empty((0, k), dtype=torch.int32), torch.empty((0, k)))
-
-
-def stop_arguments(name: str, vocab: int, stop, stop_token_ids, min_new_tokens):
-    """generate()'s `stop`, `stop_token_ids` and `min_new_tokens`, checked -> (the stop sequences as lists, the stop ids, the minimum):
-    at most 32 sequences of 1 ... 32 ids, at most 32 stop ids, every id in [0, vocab), a minimum >= 0.  `name` heads the messages."""
-    def token(arg, t):
-        try:
-            t = None if isinstance(t, bool) else _index(t)
-        except TypeError:
-            t = None
-        if t is None or not 0 <= t < vocab:
-            raise ValueError(f"{name}: {arg} holds an entry that is no token id in [0, {vocab})")
-        return t
-
-    def rows(arg, value, what):
-        # a sequence of any kind (a list, a tuple, an array, a tensor), None for none; a string or a scalar is not one
-        if value is None:
-            return []
-        if isinstance(value, (str, bytes)):
-            raise ValueError(f"{name}: {arg} must be {what}, not a string (encode stop strings first)")
-        try:
-            return list(value)
-        except TypeError:
-            raise ValueError(f"{name}: {arg} must be {what}") from None
-
-    stops = [[token("stop", t) for t in rows("stop", s, "a sequence of token-id sequences")]
-             for s in rows("stop", stop, "a sequence of token-id sequences")]
-    if len(stops) > 32 or any(not 1 <= len(s) <= 32 for s in stops):
-        raise ValueError(f"{name}: stop takes at most 32 sequences of 1 ... 32 token ids each")
-    ids = [token("stop_token_ids", t) for t in rows("stop_token_ids", stop_token_ids, "a sequence of token ids")]
-    if len(ids) > 32:
-        raise ValueError(f"{name}: stop_token_ids takes at most 32 ids")
-    try:
-        least = -1 if isinstance(min_new_tokens, bool) else _index(min_new_tokens)
-    except TypeError:
-        least = -1
-    if least < 0:
-        raise ValueError(f"{name}: min_new_tokens={min_new_tokens!r} must be an int >= 0")
-    return stops, ids, least
-
-
-def stop_match(completion: Sequence[int], stops: Sequence[Sequence[int]]) -> int:
-    """the length of the first stop sequence (lowest index) the completion ends in, 0 for none: include/serving/stop/qqq_amd_stop.h, rule 2"""
-    for s in stops:
-        if len(s) <= len(completion) and list(completion[len(completion) - len(s):]) == list(s):
-            return len(s)
-    return 0
+from .request import Request, TokenLogprobs, stop_arguments, stop_match  # noqa: F401  (the last three: re-exported)
 
 
 class QuantLlamaModel(nn.Module):
@@ -326,10 +259,9 @@ class QuantLlamaForCausalLM(nn.Module):
         host path the matching is plain Python in the bookkeeping; device_loop=True builds the loop with stops=True, whose captured
         step runs ops.ban_tokens and ops.stop_check (no host sync per token); a speculative step that emits several tokens is checked at
         every new length in order, and tokens behind a match are dropped."""
-        n = int(n)
+        n, draft_len = int(n), int(draft_len)
         if n < 1:
             raise ValueError(f"generate: n={n} must be at least 1")
-        draft_len = int(draft_len)
         if logprobs is not None:
             logprobs = int(logprobs)
             if logprobs < 0 or logprobs > 32 or logprobs > self.lm_head.weight.shape[0]:
@@ -341,110 +273,36 @@ class QuantLlamaForCausalLM(nn.Module):
             raise ValueError(f"generate: n={n} > 1 cannot be combined with draft_len={draft_len} (speculative steps have no shared-prefix kernel)")
         if draft_len < 0 or (draft_len > 0 and not device_loop):
             raise ValueError(f"generate: draft_len={draft_len} must be 0, or positive together with device_loop=True")
-        penalty = (float(repetition_penalty), float(presence_penalty), float(frequency_penalty))
-        if not (penalty[0] > 0.0 and penalty[0] != float("inf")):
-            raise ValueError(f"generate: repetition_penalty={penalty[0]} must be finite and > 0")
-        penalised = penalty != (1.0, 0.0, 0.0)
-        loop_kw = dict(penalties=True) if penalised else {}  # without penalties the loops are built and called as ever
-        if logprobs is not None:
-            loop_kw["logprobs"] = logprobs  # ... and without logprobs
-        gen_kw = dict(zip(("repetition_penalty", "presence_penalty", "frequency_penalty"), penalty)) if penalised else {}
-        vocab = self.lm_head.weight.shape[0]
-        stops, end_ids, least = stop_arguments("generate", vocab, stop, stop_token_ids, min_new_tokens)
-        if stops or end_ids or least:  # ... and without stops
-            loop_kw["stops"] = True
-            gen_kw.update(stop=stops, stop_token_ids=end_ids, min_new_tokens=least)
-        prompts = [list(p) for p in prompts]
-        if any(not p for p in prompts):
-            raise ValueError("generate: every prompt needs at least one token")
-        out: List[List[int]] = [[] for _ in range(len(prompts) * n)]  # per sibling: prompt i's are i * n ... i * n + n - 1
-
-        lp_parts, lp_rows, lp_count = ([], [], [], []), [[] for _ in out], [0]  # per pass the op's four results; per sibling its rows of them
-
-        def result():
-            if logprobs is None:
-                return out if n == 1 else [out[i * n:(i + 1) * n] for i in range(len(prompts))]
-            if lp_count[0]:  # the one transfer of the records
-                parts = [torch.cat(p).cpu() if p else torch.empty((lp_count[0], 0), dtype=d) for p, d in
-                         zip(lp_parts, (torch.float32, torch.int32, torch.int32, torch.float32))]
-            recs = [TokenLogprobs.gather(parts, at) if at else TokenLogprobs.empty(logprobs) for at in lp_rows]
-            if n == 1:
-                return out, recs
-            return [out[i * n:(i + 1) * n] for i in range(len(prompts))], [recs[i * n:(i + 1) * n] for i in range(len(prompts))]
-
+        req = Request("generate", self.lm_head.weight.shape[0], temperature, top_k, top_p, generator, eos_token_id, repetition_penalty,
+                      presence_penalty, frequency_penalty, stop, stop_token_ids, min_new_tokens, n, logprobs)
+        prompts, out = req.begin(prompts)  # out, per sibling: prompt i's are i * n ... i * n + n - 1
         if max_new_tokens < 1 or not prompts:
-            return result()
+            return req.result()
         dev = self.lm_head.weight.device
         bs = cache.block_size if cache is not None else block_size
-        need = [-(-(len(p) + max_new_tokens - 1 + draft_len) // bs) for p in prompts]
-        # a family: the prompt's blocks once plus, per further sibling, the blocks beyond the shared ones
-        fam_need = [nd + (n - 1) * (nd - len(p) // bs) for nd, p in zip(need, prompts)]
+        keys = [len(p) + max_new_tokens - 1 + draft_len for p in prompts]
+        need = [-(-k // bs) for k in keys]
+        fam_need = [req.family_blocks(len(p), k, bs) for p, k in zip(prompts, keys)]
         if cache is None:
             cache = self.new_cache(sum(fam_need), block_size, dtype)
-        if draft_len:
-            from .serve import SpecDecodeLoop
-
-            loop = SpecDecodeLoop(self, cache, rows=min(len(prompts), 64), max_len=max(need) * cache.block_size, draft_len=draft_len,
-                                  **loop_kw)
-            return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, **gen_kw)
-        if device_loop:
-            from .serve import DecodeLoop
-
-            if n > 1:
-                loop = DecodeLoop(self, cache, rows=max(1, min(len(prompts), 64 // n)) * n, max_len=max(need) * cache.block_size, family=n,
-                                  **loop_kw)
-            else:
-                loop = DecodeLoop(self, cache, rows=min(len(prompts), 64), max_len=max(need) * cache.block_size, **loop_kw)
-            return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, **gen_kw)
+        if device_loop:  # the classes are looked up in qqq_amd.serve at the call
+            build, call = req.loop_keywords()
+            rows, max_len = max(1, min(len(prompts), 64 // n)) * n, max(need) * cache.block_size
+            loop = (serve.SpecDecodeLoop(self, cache, rows=rows, max_len=max_len, draft_len=draft_len, **build) if draft_len else
+                    serve.DecodeLoop(self, cache, rows=rows, max_len=max_len, **build))
+            return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, **call)
         tag = object()  # sequence ids no other user of the cache can hold
         sid = lambda i: (tag, i)  # noqa: E731
         waiting, running = deque(range(len(prompts))), []  # prompts that wait; siblings that run (i * n + j)
         cur = None  # int64 [len(running)] on the device: the running sequences' last tokens
-
-        workspace = torch.zeros(len(out) * self.lm_head.weight.shape[0], dtype=torch.int32, device=dev) if penalised else None
-        ends = set(end_ids) | (set() if eos_token_id is None else {int(eos_token_id)})  # the tokens that end a completion, and stay in it
-        if least:
-            ban_ids = torch.tensor(end_ids, dtype=torch.int32, device=dev) if end_ids else None
-            eos_row = torch.full((len(out),), -1 if eos_token_id is None else int(eos_token_id), dtype=torch.int32, device=dev)
-            least_row = torch.full((len(out),), least, dtype=torch.int32, device=dev)
-
-        def sample(ids, step, seqs, repeat=1):
-            logits = self(ids, cache, step)
-            if repeat > 1:  # a prompt's row serves the first draw of each of its siblings
-                logits = logits.repeat_interleave(repeat, dim=0)
-            if penalised:  # the history is host-side like the rest of the bookkeeping: the prompt and what was emitted, padded per pass
-                hist = [prompts[i // n] + out[i] for i in seqs]
-                width = max(len(h) for h in hist)
-                seen = torch.tensor([h + [-1] * (width - len(h)) for h in hist], dtype=torch.int32).to(dev)
-                ops.penalize_logits(logits, torch.tensor([h[-1] for h in hist], dtype=torch.int64, device=dev),
-                                    torch.tensor([len(h) - 1 for h in hist], dtype=torch.int64, device=dev), seen,
-                                    torch.tensor([len(prompts[i // n]) for i in seqs], dtype=torch.int32, device=dev), *penalty, workspace)
-            if least and any(len(out[i]) < least for i in seqs):  # the host has the counts: a pass of rows at their minimum runs nothing
-                ops.ban_tokens(logits, torch.tensor([len(out[i]) for i in seqs], dtype=torch.int32, device=dev), least_row[:len(seqs)],
-                               eos_row[:len(seqs)], ban_ids, base=0)
-            u = torch.rand(logits.shape[0], generator=generator, device=logits.device)
-            toks = ops.sample_tokens(logits, temperature, top_k, top_p, u)
-            if logprobs is not None:  # of the rows the sampler drew from; kept on the device until the call returns
-                for part, t in zip(lp_parts, ops.topk_logprobs(logits, toks, logprobs)):
-                    if t is not None:
-                        part.append(t)
-                for row, i in enumerate(seqs):
-                    lp_rows[i].append(lp_count[0] + row)
-                lp_count[0] += len(seqs)
-            return toks
+        workspace = torch.zeros(len(out) * self.lm_head.weight.shape[0], dtype=torch.int32, device=dev) if req.penalised else None
 
         def settle(seqs, toks, fork=False):
-            """record a pass's tokens; -> (the sequences that go on, their rows of the pass).  After a prefill pass with n > 1 (`fork`)
+            """record a pass's tokens; -> (the sequences that go on, their tokens of the pass).  After a prefill pass with n > 1 (`fork`)
             only sibling 0 of a prompt exists yet: the others that go on are forked from it before it is freed, if it ends."""
             alive, rows, done = [], [], []
             for row, (i, t) in enumerate(zip(seqs, toks.tolist())):
-                out[i].append(t)
-                cut = 0 if t in ends or len(out[i]) < least else stop_match(out[i], stops)
-                if cut:  # the completion ends in front of the match, its records with it
-                    del out[i][len(out[i]) - cut:]
-                    if logprobs is not None:
-                        del lp_rows[i][len(out[i]):]
-                if len(out[i]) >= max_new_tokens or t in ends or cut:
+                if req.receive(i, t, max_new_tokens):
                     if not fork or i % n == 0:
                         done.append(i)
                 else:
@@ -454,17 +312,14 @@ class QuantLlamaForCausalLM(nn.Module):
                     rows.append(row)
             for i in done:
                 cache.free(sid(i))
-            return alive, rows
-
-        def take(toks, rows):
-            return toks if len(rows) == toks.shape[0] else toks[torch.tensor(rows, dtype=torch.int64, device=toks.device)]
+            return alive, toks if len(rows) == toks.shape[0] else toks[torch.tensor(rows, dtype=torch.int64, device=toks.device)]
 
         try:
             while waiting or running:
                 if running:
-                    toks = sample(cur, cache.step([sid(i) for i in running], [1] * len(running)), running)
-                    running, rows = settle(running, toks)
-                    cur = take(toks, rows)
+                    logits = self(cur, cache, cache.step([sid(i) for i in running], [1] * len(running)))
+                    toks = req.sample(logits, running, workspace)
+                    running, cur = settle(running, toks)
                 new = []
                 owed = sum(need[i // n] - len(cache.blocks(sid(i))) for i in running)  # what the running sequences may still take
                 while waiting and fam_need[waiting[0]] <= cache.free_blocks - owed:
@@ -479,9 +334,9 @@ class QuantLlamaForCausalLM(nn.Module):
                     continue
                 ids = torch.tensor([t for i in new for t in prompts[i]], dtype=torch.int64, device=dev)
                 born = [i * n + j for i in new for j in range(n)]
-                toks = sample(ids, cache.step([sid(i * n) for i in new], [len(prompts[i]) for i in new]), born, repeat=n)
-                alive, rows = settle(born, toks, fork=n > 1)
-                first = take(toks, rows)
+                logits = self(ids, cache, cache.step([sid(i * n) for i in new], [len(prompts[i]) for i in new]))
+                toks = req.sample(logits, born, workspace)
+                alive, first = settle(born, toks, fork=n > 1)
                 cur = first if not running else torch.cat([cur, first])
                 running = running + alive
         except BaseException:  # leave the caller's pool as it was found
@@ -491,7 +346,7 @@ class QuantLlamaForCausalLM(nn.Module):
                 except KeyError:  # ended, or never admitted
                     pass
             raise
-        return result()
+        return req.result()
 
     def score(self, sequences: Sequence[Sequence[int]], cache: Optional[PagedKVCache] = None, chunk_tokens: int = 2048, block_size: int = 16,
               dtype=torch.float16, return_greedy: bool = False):

@@ -12,9 +12,10 @@ of every kernel, a tolist() before the next step.  Here the host only admits pro
 ops.sample_tokens), writes the admitted rows' state with indexed copies, replays, and reads (n_out, remaining) back once per `sync_every`
 steps.  A row that is idle (pos -1, slot -1, remaining 0) rides along in every step and is inert: see include/qqq_amd_step.h.
 
-generate() -- admission, prefill, the run / sync / retire loop and the cleanup -- exists once, on DecodeLoop.  SpecDecodeLoop inherits it
-and overrides _decode_step, _run, _start_call, _budget_words, _row_state, _penalty_state, _stop_state, _stop_check and _collect, and the
-attributes _tokens, _synced and _idle.
+generate() -- admission, prefill, the run / sync / retire loop and the cleanup -- exists once, on DecodeLoop; the checks of its keywords,
+an admitted prompt's first token, the rule by which a completion ends and the shape of the result are the Request's (qqq_amd/request.py),
+as in QuantLlamaForCausalLM.generate.  SpecDecodeLoop inherits it and overrides _decode_step, _run, _start_call, _budget_words, _row_state,
+_penalty_state, _stop_state, _stop_check and _collect, and the attributes _tokens, _synced and _idle.
 """
 from __future__ import annotations
 
@@ -24,8 +25,8 @@ from typing import List, Optional, Sequence
 import torch
 
 from . import ops
-from .model import TokenLogprobs, stop_arguments
 from .paged import PagedKVCache, PagedStep
+from .request import Request
 
 
 def _check_loop(name, lm, cache, rows, max_len, sync_every, graph, u_stride_error=None):
@@ -286,57 +287,30 @@ class DecodeLoop:
 
         A loop built with logprobs=k returns (tokens, records): `records` mirrors the nesting of `tokens` and holds per completion a
         TokenLogprobs of CPU tensors, one entry per emitted token, the eos included.  The first token's record comes from
-        ops.topk_logprobs on the prefill's logits in admit(), the others from the step's ops.topk_logprobs_step; all of them are taken
+        ops.topk_logprobs on the prefill's logits (Request.sample), the others from the step's ops.topk_logprobs_step; all of them are taken
         from the logits row the sampler drew from -- after the penalties, before temperature, top-k and top-p.  A finished row's
         records are read back with its tokens; the run itself gains no host sync.
 
         stop, stop_token_ids, min_new_tokens (None, None, 0: none; QuantLlamaForCausalLM.generate states their meaning) need a loop built
         with stops=True.  The call writes the stop table and the stop ids once; the step bans eos and the stop ids below the minimum
-        (ops.ban_tokens) and retires a row whose completion ends in a stop id or a stop sequence (ops.stop_check, which is given the rows' eos too: a row
-        the sampler retired on its eos keeps that token where a sequence ends in it), and a sync reads
-        n_trim with the counts: the tokens -- and records -- a finished row drops from its end.  admit() does the same for the first
-        token on the host: the ban on the prefill's logits, and a length-1 stop sequence that matches the first token leaves an empty
-        completion whose row never starts.  The keys the device wrote are still counted by n_out."""
+        (ops.ban_tokens) and retires a row whose completion ends in a stop id or a stop sequence (ops.stop_check, which is given the rows'
+        eos too: a row the sampler retired on its eos keeps that token where a sequence ends in it), and a sync reads n_trim with the
+        counts: the tokens -- and records -- a finished row drops from its end.  admit() does the same for the first token by the host
+        path's own routines: Request.sample bans on the prefill's logits, and Request.receive ends a completion on its first token (a
+        length-1 stop sequence that matches it leaves an empty completion whose row never starts).  The keys the device wrote are still
+        counted by n_out."""
         name = f"{self._name}.generate"
-        stops, end_ids, least = stop_arguments(name, self.lm.lm_head.weight.shape[0], stop, stop_token_ids, min_new_tokens)
-        if (stops or end_ids or least) and not self.stops:
-            raise ValueError(f"{name}: stop, stop_token_ids and min_new_tokens={least} need a loop built with stops=True")
-        penalty = (float(repetition_penalty), float(presence_penalty), float(frequency_penalty))
-        if not (penalty[0] > 0.0 and penalty[0] != float("inf")):
-            raise ValueError(f"{name}: repetition_penalty={penalty[0]} must be finite and > 0")
-        penalised = penalty != (1.0, 0.0, 0.0)
-        if penalised and not self.penalties:
-            raise ValueError(f"{name}: repetition_penalty={penalty[0]}, presence_penalty={penalty[1]} and frequency_penalty={penalty[2]} "
-                             f"need a loop built with penalties=True")
-        prompts = [list(p) for p in prompts]
-        if any(not p for p in prompts):
-            raise ValueError(f"{name}: every prompt needs at least one token")
-        fam = self.family
-        outs: List[List[int]] = [[] for _ in range(len(prompts) * fam)]  # per sibling: prompt i's are i * fam ... i * fam + fam - 1
-
-        k_lp = self.logprobs
-        first_parts, first_at = ([], [], [], []), {}  # the first tokens' records per prefill pass (on the device), and a sequence's row of them
-        step_recs = {}                                # a finished sequence's records of its decode steps (CPU)
-
-        def result():
-            if k_lp is None:
-                return outs if fam == 1 else [outs[i * fam:(i + 1) * fam] for i in range(len(prompts))]
-            firsts = [torch.cat(p).cpu() for p in first_parts] if first_at else None
-            recs = []
-            for q in range(len(outs)):
-                if q not in first_at:
-                    recs.append(TokenLogprobs.empty(k_lp))
-                    continue
-                head = TokenLogprobs.gather(firsts, [first_at[q]])
-                rec = TokenLogprobs(*(torch.cat(pair) for pair in zip(head, step_recs[q]))) if q in step_recs else head
-                recs.append(TokenLogprobs(*(t[:len(outs[q])] for t in rec)) if self.stops else rec)  # cut like the tokens
-            if fam == 1:
-                return outs, recs
-            return [outs[i * fam:(i + 1) * fam] for i in range(len(prompts))], [recs[i * fam:(i + 1) * fam] for i in range(len(prompts))]
-
-        max_new_tokens = int(max_new_tokens)
+        req = Request(name, self.lm.lm_head.weight.shape[0], temperature, top_k, top_p, generator, eos_token_id, repetition_penalty,
+                      presence_penalty, frequency_penalty, stop, stop_token_ids, min_new_tokens, self.family, self.logprobs)
+        if req.stopping and not self.stops:
+            raise ValueError(f"{name}: stop, stop_token_ids and min_new_tokens={req.least} need a loop built with stops=True")
+        if req.penalised and not self.penalties:
+            raise ValueError(f"{name}: repetition_penalty={req.penalty[0]}, presence_penalty={req.penalty[1]} and "
+                             f"frequency_penalty={req.penalty[2]} need a loop built with penalties=True")
+        fam, max_new_tokens = self.family, int(max_new_tokens)
+        prompts, outs = req.begin(prompts)  # outs, per sibling: prompt i's are i * fam ... i * fam + fam - 1
         if max_new_tokens < 1 or not prompts:
-            return result()
+            return req.result()
         extra, new_words, parts = self._budget_words(max_new_tokens)
         keys = [len(p) + max_new_tokens - 1 + extra for p in prompts]
         for p, k in zip(prompts, keys):
@@ -346,30 +320,23 @@ class DecodeLoop:
             self._capture()
         self._start_call()
         cache, dev, bs = self.cache, self.device, self.cache.block_size
-        eos = -1 if eos_token_id is None else int(eos_token_id)
         tag = object()  # sequence ids no other user of the cache can hold
         sid = lambda i: (tag, i)  # noqa: E731
         waiting = deque(range(len(prompts)))
         owner: List[Optional[int]] = [None] * self.rows  # the sequence (prompt * fam + sibling) each row serves
-        # the blocks a prompt's family takes: its budget once plus, per further sibling, the blocks beyond the prompt's full ones
-        blocks = [-(-k // bs) + (fam - 1) * (-(-k // bs) - len(p) // bs) for p, k in zip(prompts, keys)]
+        blocks = [req.family_blocks(len(p), k, bs) for p, k in zip(prompts, keys)]  # what a prompt's family takes
         budget = [0] * self.rows                         # an upper bound of the row's `remaining`, and so of the steps it still takes
-        per_row = dict(remaining=max_new_tokens - 1, eos=eos, n_out=0, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p))
+        per_row = dict(remaining=max_new_tokens - 1, eos=req.eos, n_out=0, temperature=float(temperature), top_k=int(top_k), top_p=float(top_p))
         if self.penalties:
-            per_row.update(repetition=penalty[0], presence=penalty[1], frequency=penalty[2])
-        if k_lp is not None:
+            per_row.update(zip(("repetition", "presence", "frequency"), req.penalty))
+        if req.records is not None:
             per_row.update(n_rec=0)  # with n_out: the step's records are counted like its tokens
-        synced_arrays = self._synced
+        synced_arrays = self._synced + (("n_trim",) if self.stops else ())
         if self.stops:  # the tables of the call, once; a row starts with its first token checked (by admit) and nothing to drop
-            table = torch.zeros((32, 32), dtype=torch.int32)
-            for j, s in enumerate(stops):
-                table[j, :len(s)] = torch.tensor(s, dtype=torch.int32)
-            self.stop_ids.copy_(table)
-            self.stop_len.copy_(torch.tensor([len(s) for s in stops] + [0] * (32 - len(stops)), dtype=torch.int32))
-            self.ban_ids.copy_(torch.tensor(end_ids + [-1] * (32 - len(end_ids)), dtype=torch.int32))
-            per_row.update(min_new=least, n_seen=1, n_trim=0, stop_hit=-1)
-            synced_arrays = self._synced + ("n_trim",)
-        ends = set(end_ids) | ({eos} if eos >= 0 else set())  # the tokens that end a completion, and stay in it
+            self.stop_ids.copy_(torch.tensor([s + [0] * (32 - len(s)) for s in req.stops] + [[0] * 32] * (32 - len(req.stops)), dtype=torch.int32))
+            self.stop_len.copy_(torch.tensor([len(s) for s in req.stops] + [0] * (32 - len(req.stops)), dtype=torch.int32))
+            self.ban_ids.copy_(torch.tensor(req.end_ids + [-1] * (32 - len(req.end_ids)), dtype=torch.int32))
+            per_row.update(min_new=req.least, n_seen=1, n_trim=0, stop_hit=-1)
 
         def admit():
             new = []
@@ -391,40 +358,13 @@ class DecodeLoop:
                                        f"{blocks[waiting[0]]} ({parts})")
                 return
             # the packed prefill of the admitted prompts (eager, the existing step) and their first tokens
-            seqs = [sid(i * fam) for _, i in new]
             ids = torch.tensor([t for _, i in new for t in prompts[i]], dtype=torch.int64, device=dev)
-            logits = self.lm(ids, cache, cache.step(seqs, [len(prompts[i]) for _, i in new]))
+            logits = self.lm(ids, cache, cache.step([sid(i * fam) for _, i in new], [len(prompts[i]) for _, i in new]))
             born = [(r + j, i * fam + j) for r, i in new for j in range(fam)]  # (row, sequence) of every sibling
-            if fam > 1:  # a prompt's row serves the first draw of each of its siblings
-                logits = logits.repeat_interleave(fam, dim=0)
-            if penalised:  # over the prompt: its last token sits at index len - 1 and every index is a prompt index
-                lens = [len(prompts[q // fam]) for _, q in born]
-                seen = torch.tensor([prompts[q // fam] + [-1] * (max(lens) - len(prompts[q // fam])) for _, q in born],
-                                    dtype=torch.int32).to(dev)
-                at_last = torch.tensor([n - 1 for n in lens], dtype=torch.int64, device=dev)
-                ops.penalize_logits(logits, torch.tensor([prompts[q // fam][-1] for _, q in born], dtype=torch.int64, device=dev), at_last,
-                                    seen, torch.tensor(lens, dtype=torch.int32, device=dev), *penalty, self.penalty_workspace)
-            if least:  # the first token is index 0 of the completion: below any minimum
-                count = torch.zeros(len(born), dtype=torch.int32, device=dev)
-                ops.ban_tokens(logits, count, torch.full_like(count, least), torch.full_like(count, eos), self.ban_ids, base=0)
-            u = torch.rand(len(born), generator=generator, device=dev)
-            first = ops.sample_tokens(logits, temperature, top_k, top_p, u)
-            if k_lp is not None:  # the first token's record: the plain op on the rows the sampler drew from
-                lp, rk, ids, top = ops.topk_logprobs(logits, first, k_lp)
-                if ids is None:
-                    ids, top = lp.new_empty((len(born), 0), dtype=torch.int32), lp.new_empty((len(born), 0))
-                for part, t in zip(first_parts, (lp, rk, ids, top)):
-                    part.append(t)
-                for _, q in born:
-                    first_at[q] = len(first_at)
-            first = first.tolist()
+            first = req.sample(logits, [q for _, q in born], self.penalty_workspace if self.penalties else None)
             rows, state, ended = [], {}, []
-            for (r, q), t in zip(born, first):
-                outs[q].append(t)
-                cut = least <= 1 and t not in ends and [t] in stops  # a length-1 stop sequence: the completion is empty
-                if cut:
-                    del outs[q][:]
-                if max_new_tokens == 1 or t in ends or cut:
+            for (r, q), t in zip(born, first.tolist()):
+                if req.receive(q, t, max_new_tokens):  # also on a stop sequence of length 1: an empty completion
                     if q % fam == 0:
                         ended.append((r, q))  # its siblings are forked from it first
                     continue
@@ -468,15 +408,15 @@ class DecodeLoop:
                 if done:
                     at_done = torch.tensor(done, dtype=torch.int64, device=dev)
                     toks = getattr(self, self._tokens)[at_done].tolist()
-                    if k_lp is not None:  # read back with the tokens: record j of a row belongs to out[r, j]
-                        parts = [a[at_done].cpu() for a in (self.lp, self.lp_rank, self.lp_top_ids, self.lp_top)]
+                    if req.records is not None:  # read back with the tokens: record j of a row belongs to out[r, j]
+                        lp = [a[at_done].cpu() for a in (self.lp, self.lp_rank, self.lp_top_ids, self.lp_top)]
                         for j, r in enumerate(done):
-                            step_recs[owner[r]] = tuple(p[j, :synced["n_out"][r]] for p in parts)
+                            req.records.tail[owner[r]] = tuple(p[j, :synced["n_out"][r]] for p in lp)
                     for r, row in zip(done, toks):
                         i = owner[r]
                         outs[i].extend(self._collect(row, len(prompts[i // fam]), sid(i), {a: v[r] for a, v in synced.items()}))
-                        if self.stops and synced["n_trim"][r] > 0:  # what ops.stop_check found behind the completion's end
-                            del outs[i][max(0, len(outs[i]) - synced["n_trim"][r]):]
+                        if self.stops:  # what ops.stop_check found behind the completion's end
+                            req.cut(i, synced["n_trim"][r])
                         cache.free(sid(i))
                         owner[r] = None
                     if fam > 1:
@@ -488,13 +428,13 @@ class DecodeLoop:
                     cache.free(sid(i))
             for array, value in self._idle + ((("shared", 0),) if fam > 1 else ()):
                 getattr(self, array).fill_(value)
-            if k_lp is not None:
+            if req.records is not None:
                 self.n_rec.copy_(self.n_out)  # no row owes a record
             if self.stops:
                 self.n_seen.copy_(self.n_out + 1)  # ... or a check
                 self.n_trim.zero_()
             raise
-        return result()
+        return req.result()
 
 
 def ngram_draft(history: Sequence[int], draft_len: int, ngram_max: int = 3) -> List[int]:

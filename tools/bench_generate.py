@@ -8,9 +8,10 @@ of 128, intermediate 11008, vocab 32000, per-channel W4A8, fuse_qkv()) over a pa
 
 A round times every variant once, alternately.  A variant's value in a round is (wall time of a run with NEW tokens - wall time of a run with
 1 token) / (NEW - 1): the prefill and the first token are in both runs, the NEW - 1 decode steps in one.  Both runs end in a device
-synchronise.  The capture happens in the warm-up, outside the timed runs.  Written: the per-round values, their median, min and max, the
-ratio generate / loop graph, and at batch 1 whether the captured loop's median lies below generate's by more than generate's own
-round-to-round spread (max - min).
+synchronise.  The wall time of the 1-token run -- admission, the prefill and the first token -- is written beside it (one_token_us).  The
+capture happens in the warm-up, outside the timed runs.  Written: the per-round values, their median, min and max, the ratio generate /
+loop graph, and at batch 1 whether the captured loop's median lies below generate's by more than generate's own round-to-round spread
+(max - min).
 
     python tools/bench_generate.py [--batch 1,16] [--rounds 5] [--baseline-only] [--out profiles/decode_loop_bench.json]
 
@@ -111,15 +112,18 @@ def point(lm, batch, rounds, baseline_only, dev):
         timed(f, 1)
         tokens[name] = timed(f, NEW)[1]
         assert all(len(o) == NEW for o in tokens[name]), name
-    values = {name: [] for name in variants}
+    values, shorts = {name: [] for name in variants}, {name: [] for name in variants}
     for _ in range(rounds):
         for name, f in variants.items():
             short, full = timed(f, 1)[0], timed(f, NEW)[0]
             values[name].append((full - short) / (NEW - 1) * 1e6)
+            shorts[name].append(short * 1e6)
     res = {"batch": batch, "prompt_tokens": PROMPT, "new_tokens": NEW, "layers": LAYERS}
     for name, v in values.items():
         res[name] = {"median_us_per_token": round(statistics.median(v), 1), "min_us_per_token": round(min(v), 1),
-                     "max_us_per_token": round(max(v), 1), "rounds_us_per_token": [round(x, 1) for x in v]}
+                     "max_us_per_token": round(max(v), 1), "rounds_us_per_token": [round(x, 1) for x in v],
+                     "one_token_us": {"median": round(statistics.median(shorts[name]), 1), "min": round(min(shorts[name]), 1),
+                                      "max": round(max(shorts[name]), 1), "rounds": [round(x, 1) for x in shorts[name]]}}
     if not baseline_only:
         assert tokens["loop_graph"] == tokens["loop_eager"], "the captured loop and the eager loop must emit the same tokens"
         # generate's decode batch is sized for the running sequences' lengths, the loop's for max_len: another split plan, so the last
