@@ -39,9 +39,15 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     ban_tokens(logits, n_out, min_new, eos, ban_ids, base) / stop_check(tokens, base, first, n_out, stop_ids, stop_len, ...)
                                                                                     # the minimum length in front of a sampler, stop sequences and
                                                                                     # stop token ids behind a loop's step; generate(stop=, ...)
+    beam_step(logits, cum, live, num_beams, eos) / copy_blocks(pools, src, dst, block_bytes, num_blocks)
+                                                                                    # a beam-search step behind a pass's logits, one launch; the
+                                                                                    # block copies of PagedKVCache.reorder, one launch
+    QuantLlamaForCausalLM.beam_search(prompts, max_new_tokens, num_beams=4, ...), BeamHypothesis   # beam search; qqq_amd/beam.py
 """
 from .ops import (  # noqa: F401
     ban_tokens,
+    beam_step,
+    copy_blocks,
     decode_attention,
     decode_attention_kv8,
     decode_attention_paged,
@@ -85,6 +91,7 @@ from .request import TokenLogprobs  # noqa: F401
 from .model import QuantLlamaForCausalLM, QuantLlamaModel  # noqa: F401
 from .serve import DecodeLoop, SpecDecodeLoop, ngram_draft  # noqa: F401
 from .score import pack_steps  # noqa: F401
+from .beam import BeamHypothesis  # noqa: F401
 
 __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_int8", "mul", "marlin_qqq_gemm", "dynamic_quant", "quantlinear_forward",
            "rmsnorm_quant", "silu_mul_quant", "QuantLinear", "fuse_quant_linears", "QuantRMSNorm", "QuantLlamaMLP",
@@ -94,4 +101,5 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "sample_tokens", "QuantLlamaModel", "QuantLlamaForCausalLM", "sample_advance", "DecodeLoop", "token_logprobs", "pack_steps",
            "spec_advance", "SpecDecodeLoop", "ngram_draft", "verify_attention_paged", "verify_attention_paged_kv8", "penalize_logits",
            "decode_attention_paged_shared", "decode_attention_paged_shared_kv8", "decode_attention_shared_plan",
-           "topk_logprobs", "topk_logprobs_step", "TokenLogprobs", "ban_tokens", "stop_check"]
+           "topk_logprobs", "topk_logprobs_step", "TokenLogprobs", "ban_tokens", "stop_check",
+           "beam_step", "copy_blocks", "BeamHypothesis"]

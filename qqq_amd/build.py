@@ -57,6 +57,17 @@ def extension_headers() -> list:
     return [os.path.join(sub, d, f) for d in dirs for f in sorted(os.listdir(os.path.join(sub, d))) if f.endswith(".h")]
 
 
+def feature_headers() -> list:
+    """every header in a subdirectory of include/ other than serving/ (include/<feature>/*.h): the next feature adds a file and no lister"""
+    dirs = sorted(d for d in os.listdir(INCLUDE) if d != "serving" and os.path.isdir(os.path.join(INCLUDE, d)))
+    return sorted(os.path.join(INCLUDE, d, f) for d in dirs for f in os.listdir(os.path.join(INCLUDE, d)) if f.endswith(".h"))
+
+
+def bound_headers() -> list:
+    """what libqqq_amd.so is bound from and rebuilt for, in binding order"""
+    return operator_headers() + serving_headers() + extension_headers() + feature_headers()
+
+
 def _stale(lib: str, extra) -> bool:
     if not os.path.exists(lib):
         return True
@@ -67,7 +78,7 @@ def _stale(lib: str, extra) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(LIB, operator_headers() + serving_headers() + extension_headers())
+    return _stale(LIB, bound_headers())
 
 
 def _compile(src: str, out: str, verbose: bool, flags=()) -> str:

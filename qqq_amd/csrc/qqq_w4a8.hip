@@ -83,6 +83,8 @@
 #include "../../include/qqq_amd_score.h"
 #include "qqq_logprobs.hip.h"
 #include "../../include/serving/qqq_amd_logprobs.h"
+#include "qqq_beam.hip.h"
+#include "../../include/search/qqq_amd_beam.h"
 #include "qqq_step.hip.h"
 #include "../../include/qqq_amd_step.h"
 #include "qqq_spec.hip.h"
@@ -1734,6 +1736,102 @@ extern "C" int qqq_stop_check(const void* tokens, int token_bytes, int tok_strid
                      st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_stop_check_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- beam search (include/search/qqq_amd_beam.h; kernels in qqq_beam.hip.h): the step behind a pass's logits -- a workgroup per row into the
+// workspace, then a wave per prompt that merges -- and the block copies of a cache reorder.
+extern "C" size_t qqq_beam_step_workspace_bytes(int rows, int num_beams) {
+  if (num_beams < 1 || num_beams > BEAM_MAX || rows < 1 || rows > 65535 || rows % num_beams != 0) return 0;
+  return sizeof(int) * 2 * (size_t)rows * (size_t)(2 * num_beams);
+}
+
+extern "C" int qqq_beam_step(const void* logits, int ld, const void* cum, const void* live, void* cand_score, void* cand_logprob,
+                             void* cand_parent, void* cand_token, void* next_ids, void* next_parent, void* next_cum, void* next_live,
+                             void* workspace, size_t workspace_bytes, int num_beams, int eos, int rows, int vocab, int dev, void* stream) {
+  g_err[0] = 0;
+  if (num_beams < 1 || num_beams > BEAM_MAX) {
+    snprintf(g_err, sizeof(g_err), "qqq_beam_step: num_beams=%d outside [1, %d]", num_beams, BEAM_MAX);
+    return QQQ_ERR_ARG;
+  }
+  if (rows < 0 || rows > 65535 || rows % num_beams != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_beam_step: rows=%d outside [0, 65535] or no multiple of num_beams=%d", rows, num_beams);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  if (vocab < 2 * num_beams || vocab > SMP_MAX_VOCAB || ld < vocab || ld % 8 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_beam_step: bad shape vocab=%d ld=%d (need 2 * num_beams = %d <= vocab <= %d, ld >= vocab, ld %% 8 == 0)",
+             vocab, ld, 2 * num_beams, SMP_MAX_VOCAB);
+    return QQQ_ERR_ARG;
+  }
+  if (!logits || !cum || !live || !cand_score || !cand_logprob || !cand_parent || !cand_token || !next_ids || !next_parent || !next_cum ||
+      !next_live || !workspace || misaligned(logits, 16) || misaligned(cum, 4) || misaligned(live, 4) || misaligned(cand_score, 4) ||
+      misaligned(cand_logprob, 4) || misaligned(cand_parent, 4) || misaligned(cand_token, 4) || misaligned(next_ids, 8) ||
+      misaligned(next_parent, 4) || misaligned(next_cum, 4) || misaligned(next_live, 4) || misaligned(workspace, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_beam_step: bad argument (every pointer must be non-NULL; logits 16-byte, next_ids 8-byte, everything "
+             "else 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  const size_t need = qqq_beam_step_workspace_bytes(rows, num_beams);
+  if (workspace_bytes < need) {
+    snprintf(g_err, sizeof(g_err), "qqq_beam_step: workspace of %zu bytes, %zu needed (qqq_beam_step_workspace_bytes)", workspace_bytes, need);
+    return QQQ_ERR_ARG;
+  }
+  const size_t cands = (size_t)rows * (size_t)(2 * num_beams);
+  qqq_beam_args a;
+  a.cum = static_cast<const float*>(cum);
+  a.live = static_cast<const int*>(live);
+  a.cand_score = static_cast<float*>(cand_score);
+  a.cand_logprob = static_cast<float*>(cand_logprob);
+  a.cand_parent = static_cast<int*>(cand_parent);
+  a.cand_token = static_cast<int*>(cand_token);
+  a.next_ids = static_cast<long long*>(next_ids);
+  a.next_parent = static_cast<int*>(next_parent);
+  a.next_cum = static_cast<float*>(next_cum);
+  a.next_live = static_cast<int*>(next_live);
+  int* ws_ids = static_cast<int*>(workspace);
+  float* ws_lp = reinterpret_cast<float*>(ws_ids + cands);
+  a.ws_ids = ws_ids;
+  a.ws_lp = ws_lp;
+  a.B = num_beams;
+  a.eos = eos;
+  a.prompts = rows / num_beams;
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_beam_rows_kernel, dim3(rows), dim3(SMP_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const unsigned short*>(logits), ld, a.live, ws_ids, ws_lp, 2 * num_beams, vocab);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_beam_rows_kernel launch");
+  hipLaunchKernelGGL(qqq_beam_merge_kernel, dim3((a.prompts + BEAM_WAVES - 1) / BEAM_WAVES), dim3(BEAM_NT), 0,
+                     static_cast<hipStream_t>(stream), a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_beam_merge_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_copy_blocks(const void* pools, int n_pools, const void* src, const void* dst, int n, size_t block_bytes, int num_blocks,
+                               int dev, void* stream) {
+  g_err[0] = 0;
+  if (n < 0 || n > 65535 * 16) {
+    snprintf(g_err, sizeof(g_err), "qqq_copy_blocks: n=%d outside [0, %d]", n, 65535 * 16);
+    return QQQ_ERR_ARG;
+  }
+  if (n == 0) return QQQ_OK;
+  if (n_pools < 1 || n_pools > 65535 || num_blocks < 1 || block_bytes < 16 || block_bytes % 16 != 0 || block_bytes / 16 > 0xffffffffull) {
+    snprintf(g_err, sizeof(g_err), "qqq_copy_blocks: bad shape n_pools=%d num_blocks=%d block_bytes=%zu (need 1 <= n_pools <= 65535, "
+             "num_blocks >= 1, block_bytes a positive multiple of 16)", n_pools, num_blocks, block_bytes);
+    return QQQ_ERR_ARG;
+  }
+  if (!pools || !src || !dst || misaligned(pools, 8) || misaligned(src, 4) || misaligned(dst, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_copy_blocks: bad argument (pools, src and dst must be non-NULL; pools 8-byte, src and dst 4-byte "
+             "aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_copy_blocks_kernel, dim3(n, n_pools), dim3(COPY_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const void* const*>(pools), static_cast<const int*>(src), static_cast<const int*>(dst),
+                     (unsigned)(block_bytes / 16), num_blocks);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_copy_blocks_kernel launch");
   return QQQ_OK;
 }
 

@@ -348,6 +348,38 @@ class QuantLlamaForCausalLM(nn.Module):
             raise
         return req.result()
 
+    def beam_search(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, num_beams: int = 4, length_penalty: float = 1.0,
+                    early_stopping: bool = False, eos_token_id: Optional[int] = None, num_return_sequences: int = 1,
+                    cache: Optional[PagedKVCache] = None, block_size: int = 16, dtype=torch.float16):
+        """Beam search with `num_beams` beams (1 ... 16) for every prompt -> per prompt a list of `num_return_sequences` BeamHypothesis
+        (tokens, score, logprob), best first.  The rules are transformers' (model.generate(num_beams=...), no sampling).
+
+        One packed prefill of the admitted prompts, then one pass per token over all beams of all running prompts (row p * B + b).
+        ops.beam_step runs behind every pass: each live beam's 2B most probable tokens, the beam's summed log-probability added in f32, a
+        prompt's candidates merged and ordered, the first 2B kept; the first B of them that are not eos are the next beams, and their
+        tokens feed the next pass without leaving the device.  One read-back per pass brings the candidates and the parents for the
+        bookkeeping, and PagedKVCache.reorder re-points the beams' blocks once per pass: full blocks by reference, the partial blocks
+        of a parent taken several times through one ops.copy_blocks launch.
+
+        A candidate whose token is eos_token_id among the first B of its pass is a finished hypothesis and keeps its eos; at the budget
+        max_new_tokens the live beams finish as they are.  score = logprob / len(tokens) ** length_penalty, the eos counted; the B best
+        per prompt are kept.  early_stopping=True ends a prompt once B are held; False ends it when B are held and the best live beam's
+        logprob / its length ** length_penalty is not above the worst held score (transformers' default heuristic).  A prompt that is
+        done leaves the batch and frees its blocks; the call ends when every prompt is done.  num_beams=1 gives greedy generate's tokens.
+
+        `cache`: a PagedKVCache to run in (other sequences in it are left alone); default: a new one with room for everything.  A prompt
+        of L tokens is admitted once the free blocks cover own + (num_beams - 1) * (own - L // block_size), own = ceil((L +
+        max_new_tokens - 1) / block_size), on top of what the running prompts may still take (beam.blocks_needed: the prompt's full
+        blocks are held once, everything else once per beam); prompts that do not fit wait in order, and one that can never fit raises
+        RuntimeError ("cannot hold a prompt").  Newly admitted prompts are prefilled in a pass of their own.  fuse_prefill(),
+        fuse_decode() and the cache dtype are honoured as in generate.  Sampling inside the beam, penalties, stop sequences, logprobs
+        records, device_loop, draft_len and n are not part of this call."""
+        from . import beam as _beam
+
+        return _beam.beam_search(self, prompts, max_new_tokens, num_beams=num_beams, length_penalty=length_penalty,
+                                 early_stopping=early_stopping, eos_token_id=eos_token_id, num_return_sequences=num_return_sequences,
+                                 cache=cache, block_size=block_size, dtype=dtype)
+
     def score(self, sequences: Sequence[Sequence[int]], cache: Optional[PagedKVCache] = None, chunk_tokens: int = 2048, block_size: int = 16,
               dtype=torch.float16, return_greedy: bool = False):
         """Per-token log-probabilities log p(seq[t + 1] | seq[:t + 1]) of every sequence, f32 [len - 1] each (with return_greedy also the

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -2146,3 +2146,168 @@ def stop_check(tokens: torch.Tensor, base: torch.Tensor, first: Optional[torch.T
     if _compiling(*(t for t in args if t is not None)):
         return _stop_check_op(*args)
     return _stop_check_impl(*args)
+
+
+# ---- beam search (include/search/qqq_amd_beam.h): the step behind a pass's logits, and the block copies of a cache reorder
+
+class BeamStep(NamedTuple):
+    """What beam_step returns.  cand_* and next_parent are views of `packed` (int32, the f32 arrays bit for bit), so that one copy of
+    `packed` brings everything the host's bookkeeping reads; unpack_beam_step(packed.cpu(), prompts, num_beams) cuts it up again."""
+    cand_score: torch.Tensor
+    cand_logprob: torch.Tensor
+    cand_parent: torch.Tensor
+    cand_token: torch.Tensor
+    next_ids: torch.Tensor
+    next_parent: torch.Tensor
+    next_cum: torch.Tensor
+    next_live: torch.Tensor
+    packed: torch.Tensor
+
+
+def unpack_beam_step(packed: torch.Tensor, prompts: int, num_beams: int):
+    """beam_step's packed int32 [prompts * 9 * num_beams] -> (cand_score f32, cand_logprob f32, cand_parent int32, cand_token int32, each
+    [prompts, 2 * num_beams], next_parent int32 [prompts * num_beams]), as views."""
+    c = prompts * 2 * num_beams
+    return (packed[:c].view(torch.float32).view(prompts, -1), packed[c:2 * c].view(torch.float32).view(prompts, -1),
+            packed[2 * c:3 * c].view(prompts, -1), packed[3 * c:4 * c].view(prompts, -1), packed[4 * c:])
+
+
+def beam_step_workspace(rows: int, num_beams: int, device) -> torch.Tensor:
+    """A workspace for beam_step over `rows` rows: int32 [4 * rows * num_beams] (the rows' candidates between the op's two launches).
+    One workspace serves call after call on one stream."""
+    return torch.empty((4 * rows * num_beams,), dtype=torch.int32, device=device)
+
+
+def _beam_step_check(logits, cum, live, num_beams, workspace):
+    # dtypes and shapes: needs no device, shared by the launch and the fake implementation -> (rows, vocab, prompts)
+    op = "beam_step"
+    if logits.dtype != torch.float16 or logits.dim() != 2:
+        raise RuntimeError(f"{op}: logits must be fp16 [prompts * num_beams, vocab]")
+    rows, vocab = logits.shape
+    if num_beams < 1 or num_beams > 16:
+        raise ValueError(f"{op}: num_beams={num_beams} outside [1, 16]")
+    if rows % num_beams or rows > 65535:
+        raise RuntimeError(f"{op}: logits hold {rows} rows: no multiple of num_beams={num_beams}, or more than 65535")
+    if vocab < 2 * num_beams or vocab > 262144:
+        raise RuntimeError(f"{op}: vocab={vocab} outside [2 * num_beams = {2 * num_beams}, 262144]")
+    if cum.dtype != torch.float32 or cum.dim() != 1 or cum.shape[0] != rows:
+        raise RuntimeError(f"{op}: cum must be f32 [{rows}], one entry per row, not {_dt(cum.dtype)} {tuple(cum.shape)}")
+    if live.dtype != torch.int32 or live.dim() != 1 or live.shape[0] != rows:
+        raise RuntimeError(f"{op}: live must be int32 [{rows}], one entry per row, not {_dt(live.dtype)} {tuple(live.shape)}")
+    need = 4 * rows * num_beams
+    if workspace.dtype != torch.int32 or workspace.dim() != 1 or workspace.shape[0] < need:
+        raise RuntimeError(f"{op}: workspace must be int32 [at least {need}] (beam_step_workspace), not {_dt(workspace.dtype)} "
+                           f"{tuple(workspace.shape)}")
+    return rows, vocab, rows // num_beams
+
+
+def _beam_step_outputs(like, rows, prompts, num_beams):
+    return (like.new_empty((prompts * 9 * num_beams,), dtype=torch.int32), like.new_empty((rows,), dtype=torch.int64),
+            like.new_empty((rows,), dtype=torch.float32), like.new_empty((rows,), dtype=torch.int32))
+
+
+def _beam_step_impl(logits, cum, live, num_beams, eos, workspace):
+    ts = (logits, cum, live, workspace)
+    _same_gpu("beam_step", ts)
+    rows, vocab, prompts = _beam_step_check(logits, cum, live, num_beams, workspace)
+    packed, next_ids, next_cum, next_live = _beam_step_outputs(logits, rows, prompts, num_beams)
+    if rows == 0:
+        return packed, next_ids, next_cum, next_live
+    _in_place_check("beam_step", (("cum", cum), ("live", live), ("workspace", workspace)))
+    logits = _logits_rows(logits, vocab)
+    c = prompts * 2 * num_beams  # the packed layout: cand_score, cand_logprob, cand_parent, cand_token [prompts, 2B], next_parent [rows]
+    at = lambda i: packed.data_ptr() + 4 * c * i  # noqa: E731
+    err = _lib.lib().qqq_beam_step(_ptr(logits), logits.stride(0), _ptr(cum), _ptr(live), at(0), at(1), at(2), at(3), _ptr(next_ids), at(4),
+                                   _ptr(next_cum), _ptr(next_live), _ptr(workspace), 4 * workspace.shape[0], num_beams, eos, rows, vocab,
+                                   logits.device.index or 0, _stream_for(logits))
+    _raise_lib("beam_step", err)
+    return packed, next_ids, next_cum, next_live
+
+
+@torch.library.custom_op("qqq_amd::beam_step", mutates_args=("workspace",))
+def _beam_step_op(logits: torch.Tensor, cum: torch.Tensor, live: torch.Tensor, num_beams: int, eos: int,
+                  workspace: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _beam_step_impl(logits, cum, live, num_beams, eos, workspace)
+
+
+@_beam_step_op.register_fake
+def _(logits, cum, live, num_beams, eos, workspace):
+    rows, _, prompts = _beam_step_check(logits, cum, live, num_beams, workspace)
+    return _beam_step_outputs(logits, rows, prompts, num_beams)
+
+
+def beam_step(logits: torch.Tensor, cum: torch.Tensor, live: torch.Tensor, num_beams: int, eos: Optional[int] = None,
+              workspace: Optional[torch.Tensor] = None) -> BeamStep:
+    """One step of beam search behind a pass's fp16 logits [P * B, vocab] (row p * B + b: beam b of prompt p): a launch over the rows and one
+    that merges them -> BeamStep.
+
+    cum          f32 [P * B]: the beams' summed log-probabilities;  live  int32 [P * B]: a row with 0 contributes nothing
+    num_beams    B, 1 ... 16;  eos  the id that ends a hypothesis, None or -1 for none
+    workspace    int32, from beam_step_workspace(rows, B, device); None: a new one per call
+    Every live row yields topk_logprobs' first 2B tokens; a candidate (b, i) has score = cum + that op's log-probability, one f32 addition;
+    a prompt's candidates are ordered by score descending (NaN and -inf last), then b, then i, and the first 2B are cand_score,
+    cand_logprob, cand_parent, cand_token [P, 2B].  The first B of them whose token is not eos become the next beams: next_ids int64 (the
+    next pass's input, on the device), next_parent int32, next_cum f32, next_live int32, each [P * B].  A prompt without a live row writes
+    parent = token = -1, score -inf and stays dead.  The exact semantics are stated in include/search/qqq_amd_beam.h.  Nothing is read on
+    the host and the launch size depends on the shapes alone, so a captured graph replays with other contents.  A view whose rows are
+    `vocab` columns of a wider, 16-byte aligned fp16 matrix (row stride a multiple of 8) is read in place."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(cum, torch.Tensor) or not isinstance(live, torch.Tensor) or logits.dim() != 2:
+        raise RuntimeError("beam_step: logits must be an fp16 [prompts * num_beams, vocab] tensor, cum an f32 and live an int32 [rows] tensor")
+    num_beams, eos = int(num_beams), -1 if eos is None else int(eos)
+    if workspace is None:
+        workspace = beam_step_workspace(logits.shape[0], max(num_beams, 1), logits.device)
+    args = (logits, cum, live, num_beams, eos, workspace)
+    packed, next_ids, next_cum, next_live = _beam_step_op(*args) if _compiling(logits, cum, live, workspace) else _beam_step_impl(*args)
+    score, lp, parent, token, next_parent = unpack_beam_step(packed, logits.shape[0] // num_beams, num_beams)
+    return BeamStep(score, lp, parent, token, next_ids, next_parent, next_cum, next_live, packed)
+
+
+def _copy_blocks_check(pools, src, dst, block_bytes, num_blocks):
+    # dtypes and shapes -> n
+    op = "copy_blocks"
+    if pools.dtype != torch.int64 or pools.dim() != 1 or not 1 <= pools.shape[0] <= 65535:
+        raise RuntimeError(f"{op}: pools must be int64 [1 ... 65535 base addresses], not {_dt(pools.dtype)} {tuple(pools.shape)}")
+    for name, t in (("src", src), ("dst", dst)):
+        if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != src.shape[0]:
+            raise RuntimeError(f"{op}: {name} must be int32 [n], one entry per copy, not {_dt(t.dtype)} {tuple(t.shape)}")
+    if block_bytes < 16 or block_bytes % 16 or num_blocks < 1:
+        raise ValueError(f"{op}: block_bytes={block_bytes} must be a positive multiple of 16 and num_blocks={num_blocks} at least 1")
+    return src.shape[0]
+
+
+def _copy_blocks_impl(pools, src, dst, block_bytes, num_blocks):
+    ts = (pools, src, dst)
+    _same_gpu("copy_blocks", ts)
+    n = _copy_blocks_check(pools, src, dst, block_bytes, num_blocks)
+    if n == 0:
+        return
+    _in_place_check("copy_blocks", (("pools", pools), ("src", src), ("dst", dst)))
+    err = _lib.lib().qqq_copy_blocks(_ptr(pools), pools.shape[0], _ptr(src), _ptr(dst), n, block_bytes, num_blocks, pools.device.index or 0,
+                                     _stream_for(pools))
+    _raise_lib("copy_blocks", err)
+
+
+@torch.library.custom_op("qqq_amd::copy_blocks", mutates_args=())
+def _copy_blocks_op(pools: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, block_bytes: int, num_blocks: int) -> None:
+    _copy_blocks_impl(pools, src, dst, block_bytes, num_blocks)
+
+
+@_copy_blocks_op.register_fake
+def _(pools, src, dst, block_bytes, num_blocks):
+    _copy_blocks_check(pools, src, dst, block_bytes, num_blocks)
+
+
+def copy_blocks(pools: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, block_bytes: int, num_blocks: int) -> None:
+    """Copy block src[j] to block dst[j] in every pool of a table, in one launch (PagedKVCache.reorder's partial-block copies).
+
+    pools        int64 [n_pools] on the device: the pools' base addresses (tensor.data_ptr()), every pool [num_blocks] blocks of
+                 block_bytes bytes (a multiple of 16), 16-byte aligned.  The caller keeps the pools alive; the op sees addresses only.
+    src, dst     int32 [n] on the device; the dst entries are distinct and none equals a src entry, one src may feed several dst; an id
+                 outside [0, num_blocks) copies nothing.  n = 0 is a no-op.
+    Nothing is read on the host.  The exact semantics are stated in include/search/qqq_amd_beam.h."""
+    if not all(isinstance(t, torch.Tensor) for t in (pools, src, dst)):
+        raise RuntimeError("copy_blocks: pools must be an int64 [n_pools] tensor, src and dst int32 [n] tensors")
+    args = (pools, src, dst, int(block_bytes), int(num_blocks))
+    if _compiling(pools, src, dst):
+        return _copy_blocks_op(*args)
+    return _copy_blocks_impl(*args)

@@ -3,13 +3,14 @@ with per-sequence lengths, and the per-step metadata the paged ops read (ops.rop
 prefill_attention_paged and their _kv8 forms).
 
     PagedKVCache   k[layer], v[layer] of shape [num_blocks, num_kv_heads, block_size, head_dim] (fp16 or int8; an int8 pool with
-                   k_scale[layer], v_scale[layer] [num_blocks, num_kv_heads, block_size]); add / fork / free / reserve / step / advance /
-                   gather
+                   k_scale[layer], v_scale[layer] [num_blocks, num_kv_heads, block_size]); add / fork / reorder / free / reserve / step /
+                   advance / gather
     PagedStep      what one forward pass over a packed batch of sequences needs, built once on the host and shared by all layers
 
 Sequences arrive and finish at different times, have different lengths, and a finished sequence's blocks serve the next one.  The allocator
 counts the owners of every block: fork() makes a sequence that shares the full blocks of another one (the n completions of one prompt),
-and a shared block returns to the free list with its last owner.  Only full blocks are shared, so no write ever lands in one.  The
+and a shared block returns to the free list with its last owner.  Only full blocks are shared, so no write ever lands in one.
+reorder() re-points a group of sequences at one another's blocks by the same rules (the beams of a beam search, every pass).  The
 sequences forked from one prompt are a family; a decode step over adjacent siblings says so in PagedStep.family / shared / family_max,
 which ops.decode_attention_paged_shared reads.  The ops themselves need none of this: a block table may name any block.
 """
@@ -50,6 +51,14 @@ class PagedStep:
     family_max: Optional[int] = None
 
 
+class _Family:
+    """The root of a family PagedKVCache.reorder() formed: equal to itself alone, and no sequence id."""
+    __slots__ = ()
+
+    def __repr__(self):
+        return f"<family {id(self):#x}>"
+
+
 class PagedKVCache:
     """Key / value block pools of `num_layers` layers and the allocator of their blocks (one block id covers all layers).
 
@@ -81,6 +90,7 @@ class PagedKVCache:
         self._refs: List[int] = [0] * num_blocks  # owners of a block: 0 on the free list, above 1 only for full blocks that fork() shared
         self._root: Dict[object, object] = {}     # the sequence a family was forked from (a sequence that never forked names itself)
         self._shared: Dict[object, int] = {}      # leading keys in common with the family: what fork() shared, a multiple of block_size
+        self._tables = None                       # reorder()'s pointer tables of the pools (GPU pools only), built at its first copy
 
     @property
     def quantized(self) -> bool:
@@ -147,8 +157,97 @@ class PagedKVCache:
         else:
             self._shared[dst] = min(full * bs, self._shared[src])
 
+    def _pools(self):
+        """([k and v pools], [an int8 pool's scale pools]): within a list every pool has one block size in bytes"""
+        return self.k + self.v, (self.k_scale + self.v_scale) if self.quantized else []
+
+    def _pool_tables(self):
+        """per list of _pools(): (int64 device tensor of base addresses, bytes per block), built once per cache"""
+        if self._tables is None:
+            self._tables = [(torch.tensor([p.data_ptr() for p in pools], dtype=torch.int64).to(pools[0].device),
+                             pools[0][0].numel() * pools[0].element_size()) for pools in self._pools() if pools]
+        return self._tables
+
+    def reorder(self, seq_ids: Sequence, parents: Sequence[int]) -> None:
+        """Re-point a group of sequences (the beams of a beam search, of any number of prompts; the beams of one prompt have one
+        length): afterwards seq_ids[i] holds what seq_ids[parents[i]] held, at its length.  A parent chosen once hands its blocks over, no copy.  A parent chosen m times is shared m ways: its
+        first taker gets its blocks, the others share the len // block_size full blocks by reference (one more owner each) and get a fresh
+        block with a copy of the partial last block, where there is one -- m - 1 copies.  A sequence nobody chose releases its blocks,
+        before the fresh ones are taken.  A seq_ids[i] the cache does not hold yet is admitted by the call (it cannot be a parent).
+
+        Families: the given sequences that had one root are one family afterwards, named by a root object of its own (no sequence id: a
+        later fork() of one of them shares no more than it already does), and shared_keys() of each is what ALL of them have in common
+        now, the keys of their common leading blocks.  Sequences of the old family outside the call keep their root and are no longer
+        in a family with these.
+
+        On GPU pools all copies of the call are one ops.copy_blocks launch (a second one for an int8 pool's scales) over a pointer table
+        built once per cache; on CPU pools torch's copy_, as in fork().  Raises, and changes nothing, on bad arguments (ValueError,
+        KeyError) or when the pool cannot supply the fresh blocks (RuntimeError)."""
+        seq_ids, parents = list(seq_ids), [int(j) for j in parents]
+        if len(seq_ids) != len(parents) or not seq_ids or len(set(seq_ids)) != len(seq_ids):
+            raise ValueError("PagedKVCache.reorder: seq_ids and parents must be non-empty, of one length, without repeated sequences")
+        if any(j < 0 or j >= len(seq_ids) for j in parents):
+            raise ValueError(f"PagedKVCache.reorder: every parent must be an index into the {len(seq_ids)} sequences")
+        for j in set(parents):
+            if seq_ids[j] not in self._blocks:
+                raise KeyError(f"PagedKVCache.reorder: no sequence {seq_ids[j]!r}")
+        held = [sid in self._blocks for sid in seq_ids]
+        bs = self.block_size
+        takers: Dict[int, List[int]] = {}
+        for i, j in enumerate(parents):
+            takers.setdefault(j, []).append(i)
+        unchosen = [i for i, h in enumerate(held) if h and i not in takers]
+        refs = {}
+        for i in unchosen:
+            for blk in self._blocks[seq_ids[i]]:
+                refs[blk] = refs.get(blk, self._refs[blk]) - 1
+        released = sum(1 for r in refs.values() if r == 0)
+        fresh = sum(len(t) - 1 for j, t in takers.items() if self._len[seq_ids[j]] % bs)
+        if fresh > len(self._free) + released:
+            raise RuntimeError(f"PagedKVCache.reorder: the pool is exhausted ({fresh} blocks needed, {len(self._free) + released} free)")
+        old = {j: (self._blocks[seq_ids[j]], self._root[seq_ids[j]], self._len[seq_ids[j]]) for j in takers}
+        for i in unchosen:
+            self.free(seq_ids[i])
+        src, dst, groups = [], [], {}
+        for j, (blocks, root, n) in old.items():
+            full, part = n // bs, n % bs != 0
+            for nth, i in enumerate(takers[j]):
+                if nth == 0:
+                    mine = blocks
+                else:
+                    mine = blocks[:full]
+                    for blk in mine:
+                        self._refs[blk] += 1
+                    if part:
+                        mine.append(self._take())
+                        src.append(blocks[full])
+                        dst.append(mine[-1])
+                self._blocks[seq_ids[i]], self._len[seq_ids[i]] = mine, n
+                groups.setdefault(root, []).append(i)
+        for members in groups.values():
+            lists = [self._blocks[seq_ids[i]] for i in members]
+            full, common = min(self._len[seq_ids[i]] for i in members) // bs, 0
+            while len(members) > 1 and common < full and all(b[common] == lists[0][common] for b in lists):
+                common += 1
+            root = _Family()
+            for i in members:
+                self._root[seq_ids[i]], self._shared[seq_ids[i]] = root, common * bs
+        if not src:
+            return
+        if self.k[0].is_cuda:
+            from . import ops
+
+            s, d = (torch.tensor(x, dtype=torch.int32).to(self.k[0].device) for x in (src, dst))
+            for table, block_bytes in self._pool_tables():
+                ops.copy_blocks(table, s, d, block_bytes, self.num_blocks)
+        else:
+            for pools in self._pools():
+                for pool in pools:
+                    pool[dst] = pool[src]
+
     def root(self, seq_id):
-        """The sequence this one's family was forked from (itself, if it never took part in a fork)."""
+        """The sequence this one's family was forked from (itself, if it never took part in a fork; an object of the family's own once
+        reorder() has formed it)."""
         return self._root[seq_id]
 
     def shared_keys(self, seq_id) -> int:
