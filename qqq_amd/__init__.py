@@ -43,6 +43,10 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
                                                                                     # a beam-search step behind a pass's logits, one launch; the
                                                                                     # block copies of PagedKVCache.reorder, one launch
     QuantLlamaForCausalLM.beam_search(prompts, max_new_tokens, num_beams=4, ...), BeamHypothesis   # beam search; qqq_amd/beam.py
+    fsm_mask(logits, state, fsm_tensors, eos, remaining) / fsm_advance(out, n_out, n_fsm, state, fsm_tensors, ids, pos, slots, remaining, eos)
+                                                                                    # guided decoding: a token automaton in device memory masks
+                                                                                    # the row in front of a sampler and advances behind it
+    TokenFSM, QuantLlamaForCausalLM.generate_guided(prompts, fsm, max_new_tokens, ...), GuidedDecodeLoop   # qqq_amd/guided.py, serve.py
 """
 from .ops import (  # noqa: F401
     ban_tokens,
@@ -54,6 +58,8 @@ from .ops import (  # noqa: F401
     decode_attention_paged_kv8,
     dynamic_quant,
     expand_int8,
+    fsm_advance,
+    fsm_mask,
     marlin_qqq_gemm,
     mul,
     penalize_logits,
@@ -89,7 +95,8 @@ from .attention import KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer  # n
 from .paged import PagedKVCache, PagedStep  # noqa: F401
 from .request import TokenLogprobs  # noqa: F401
 from .model import QuantLlamaForCausalLM, QuantLlamaModel  # noqa: F401
-from .serve import DecodeLoop, SpecDecodeLoop, ngram_draft  # noqa: F401
+from .serve import DecodeLoop, GuidedDecodeLoop, SpecDecodeLoop, ngram_draft  # noqa: F401
+from .guided import TokenFSM  # noqa: F401
 from .score import pack_steps  # noqa: F401
 from .beam import BeamHypothesis  # noqa: F401
 
@@ -102,4 +109,4 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "spec_advance", "SpecDecodeLoop", "ngram_draft", "verify_attention_paged", "verify_attention_paged_kv8", "penalize_logits",
            "decode_attention_paged_shared", "decode_attention_paged_shared_kv8", "decode_attention_shared_plan",
            "topk_logprobs", "topk_logprobs_step", "TokenLogprobs", "ban_tokens", "stop_check",
-           "beam_step", "copy_blocks", "BeamHypothesis"]
+           "beam_step", "copy_blocks", "BeamHypothesis", "fsm_mask", "fsm_advance", "TokenFSM", "GuidedDecodeLoop"]

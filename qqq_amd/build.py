@@ -63,6 +63,16 @@ def feature_headers() -> list:
     return sorted(os.path.join(INCLUDE, d, f) for d in dirs for f in os.listdir(os.path.join(INCLUDE, d)) if f.endswith(".h"))
 
 
+def nested_headers() -> list:
+    """every header two levels below include/, in a group other than serving/ (include/<group>/<feature>/*.h): bound behind bound_headers()"""
+    out = []
+    for group in sorted(d for d in os.listdir(INCLUDE) if d != "serving" and os.path.isdir(os.path.join(INCLUDE, d))):
+        for feature in sorted(d for d in os.listdir(os.path.join(INCLUDE, group)) if os.path.isdir(os.path.join(INCLUDE, group, d))):
+            sub = os.path.join(INCLUDE, group, feature)
+            out += [os.path.join(sub, f) for f in sorted(os.listdir(sub)) if f.endswith(".h")]
+    return out
+
+
 def bound_headers() -> list:
     """what libqqq_amd.so is bound from and rebuilt for, in binding order"""
     return operator_headers() + serving_headers() + extension_headers() + feature_headers()
@@ -78,7 +88,7 @@ def _stale(lib: str, extra) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(LIB, bound_headers())
+    return _stale(LIB, bound_headers() + nested_headers())
 
 
 def _compile(src: str, out: str, verbose: bool, flags=()) -> str:

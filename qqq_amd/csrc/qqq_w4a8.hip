@@ -41,6 +41,7 @@
 //   qqq_penalty.hip.h  the repetition / presence / frequency penalty: fp16 logit rows rewritten in place from each row's token history, one launch
 //   qqq_spec.hip.h     the speculative decode loop's step: draft_len + 1 draws per row by that sampler, the accept rule and the n-gram drafter
 //   qqq_stop.hip.h     stop sequences, stop token ids and the minimum length: the ban in front of a sampler, the check behind a loop's step
+//   qqq_guided.hip.h   guided decoding over a token automaton in device memory: the mask in front of a sampler, the advance behind a loop's step
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -97,6 +98,8 @@
 #include "../../include/qqq_amd_penalty.h"
 #include "qqq_stop.hip.h"
 #include "../../include/serving/stop/qqq_amd_stop.h"
+#include "qqq_guided.hip.h"
+#include "../../include/ext/guided/qqq_amd_guided.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1736,6 +1739,86 @@ extern "C" int qqq_stop_check(const void* tokens, int token_bytes, int tok_strid
                      st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_stop_check_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- guided decoding (include/ext/guided/qqq_amd_guided.h; kernels in qqq_guided.hip.h): one launch each, a row's columns over several
+// workgroups / one wave per row, no workspace.
+extern "C" int qqq_fsm_mask(void* logits, int ld, const void* state, const void* eos, const void* remaining, const void* offsets,
+                            const void* tokens, const void* accept, int n_states, int n_edges, int rows, int vocab, int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 0 || rows > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_fsm_mask: rows=%d outside [0, 65535]", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  if (vocab < 1 || vocab > SMP_MAX_VOCAB || ld < vocab || n_states < 1 || n_edges < 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_fsm_mask: bad shape vocab=%d ld=%d n_states=%d n_edges=%d (need 1 <= vocab <= %d, ld >= vocab, "
+             "n_states >= 1, n_edges >= 0)", vocab, ld, n_states, n_edges, SMP_MAX_VOCAB);
+    return QQQ_ERR_ARG;
+  }
+  if (!logits || !state || !offsets || !accept || (n_edges == 0) != (tokens == nullptr) || misaligned(logits, 2) || misaligned(state, 4) ||
+      misaligned(eos, 4) || misaligned(remaining, 4) || misaligned(offsets, 4) || misaligned(tokens, 4) || misaligned(accept, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_fsm_mask: bad argument (logits, state, offsets and accept must be non-NULL, tokens NULL exactly when "
+             "n_edges == 0; logits 2-byte, everything else 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  const int width = fsm_mask_width(rows, vocab);
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_fsm_mask_kernel, dim3((vocab + width - 1) / width, rows), dim3(FSM_NT), 0, static_cast<hipStream_t>(stream),
+                     static_cast<unsigned short*>(logits), ld, static_cast<const int*>(state), static_cast<const int*>(eos),
+                     static_cast<const int*>(remaining), static_cast<const int*>(offsets), static_cast<const int*>(tokens),
+                     static_cast<const int*>(accept), n_states, n_edges, vocab, width);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_fsm_mask_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_fsm_advance(const void* out, int out_stride, const void* n_out, void* n_fsm, void* state, const void* eos,
+                               const void* offsets, const void* tokens, const void* next, const void* accept, int n_states, int n_edges,
+                               void* ids, void* pos, void* slots, void* remaining, int rows, int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 0 || rows > 65535) {
+    snprintf(g_err, sizeof(g_err), "qqq_fsm_advance: rows=%d outside [0, 65535]", rows);
+    return QQQ_ERR_ARG;
+  }
+  if (rows == 0) return QQQ_OK;
+  if (out_stride < 1 || n_states < 1 || n_edges < 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_fsm_advance: bad shape out_stride=%d n_states=%d n_edges=%d (need out_stride >= 1, n_states >= 1, "
+             "n_edges >= 0)", out_stride, n_states, n_edges);
+    return QQQ_ERR_ARG;
+  }
+  if (!out || !n_out || !n_fsm || !state || !offsets || !accept || !ids || !pos || !slots || !remaining ||
+      (n_edges == 0) != (tokens == nullptr) || (n_edges == 0) != (next == nullptr) || misaligned(out, 8) || misaligned(n_out, 4) ||
+      misaligned(n_fsm, 4) || misaligned(state, 4) || misaligned(eos, 4) || misaligned(offsets, 4) || misaligned(tokens, 4) ||
+      misaligned(next, 4) || misaligned(accept, 4) || misaligned(ids, 8) || misaligned(pos, 8) || misaligned(slots, 8) ||
+      misaligned(remaining, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_fsm_advance: bad argument (every pointer but eos must be non-NULL, tokens and next NULL exactly when "
+             "n_edges == 0; out, ids, pos and slots 8-byte, everything else 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_fsm_advance_args a;
+  a.out = static_cast<const long long*>(out);
+  a.n_out = static_cast<const int*>(n_out);
+  a.n_fsm = static_cast<int*>(n_fsm);
+  a.state = static_cast<int*>(state);
+  a.eos = static_cast<const int*>(eos);
+  a.offsets = static_cast<const int*>(offsets);
+  a.tokens = static_cast<const int*>(tokens);
+  a.next = static_cast<const int*>(next);
+  a.accept = static_cast<const int*>(accept);
+  a.ids = static_cast<long long*>(ids);
+  a.pos = static_cast<long long*>(pos);
+  a.slots = static_cast<long long*>(slots);
+  a.remaining = static_cast<int*>(remaining);
+  a.out_stride = out_stride;
+  a.n_states = n_states;
+  a.n_edges = n_edges;
+  a.rows = rows;
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_fsm_advance_kernel, dim3((rows + FSM_WAVES - 1) / FSM_WAVES), dim3(FSM_NT), 0, static_cast<hipStream_t>(stream), a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_fsm_advance_kernel launch");
   return QQQ_OK;
 }
 

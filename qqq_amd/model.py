@@ -26,7 +26,7 @@ from . import ops, serve
 from .attention import KVCache, QuantLlamaDecoderLayer
 from .blocks import QuantRMSNorm
 from .paged import PagedKVCache, PagedStep
-from .request import Request, TokenLogprobs, stop_arguments, stop_match  # noqa: F401  (the last three: re-exported)
+from .request import GuidedRequest, Request, TokenLogprobs, stop_arguments, stop_match  # noqa: F401  (the last three: re-exported)
 
 
 class QuantLlamaModel(nn.Module):
@@ -275,6 +275,13 @@ class QuantLlamaForCausalLM(nn.Module):
             raise ValueError(f"generate: draft_len={draft_len} must be 0, or positive together with device_loop=True")
         req = Request("generate", self.lm_head.weight.shape[0], temperature, top_k, top_p, generator, eos_token_id, repetition_penalty,
                       presence_penalty, frequency_penalty, stop, stop_token_ids, min_new_tokens, n, logprobs)
+        return self._generate(req, prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, cache, block_size, dtype,
+                              device_loop, draft_len)
+
+    def _generate(self, req, prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, cache, block_size, dtype,
+                  device_loop, draft_len):
+        """generate() behind its keyword checks, for the request object `req` (a GuidedRequest: generate_guided's)"""
+        n = req.n
         prompts, out = req.begin(prompts)  # out, per sibling: prompt i's are i * n ... i * n + n - 1
         if max_new_tokens < 1 or not prompts:
             return req.result()
@@ -288,6 +295,11 @@ class QuantLlamaForCausalLM(nn.Module):
         if device_loop:  # the classes are looked up in qqq_amd.serve at the call
             build, call = req.loop_keywords()
             rows, max_len = max(1, min(len(prompts), 64 // n)) * n, max(need) * cache.block_size
+            if isinstance(req, GuidedRequest):  # capacities rounded up from the call's automaton: powers of two, at least 64
+                room = lambda count: max(64, 1 << (count - 1).bit_length())  # noqa: E731
+                loop = serve.GuidedDecodeLoop(self, cache, rows=rows, max_len=max_len, fsm_states=room(req.fsm.n_states),
+                                              fsm_edges=room(req.fsm.n_edges), **build)
+                return loop.generate_guided(prompts, req._given, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, **call)
             loop = (serve.SpecDecodeLoop(self, cache, rows=rows, max_len=max_len, draft_len=draft_len, **build) if draft_len else
                     serve.DecodeLoop(self, cache, rows=rows, max_len=max_len, **build))
             return loop.generate(prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, **call)
@@ -347,6 +359,45 @@ class QuantLlamaForCausalLM(nn.Module):
                     pass
             raise
         return req.result()
+
+    @torch.no_grad()
+    def generate_guided(self, prompts: Sequence[Sequence[int]], fsm, max_new_tokens: int, temperature: float = 0.0, top_k: int = 0,
+                        top_p: float = 1.0, generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
+                        cache: Optional[PagedKVCache] = None, block_size: int = 16, dtype=torch.float16, device_loop: bool = False,
+                        stop: Optional[Sequence[Sequence[int]]] = None, stop_token_ids: Optional[Sequence[int]] = None,
+                        min_new_tokens: int = 0, n: int = 1, logprobs: Optional[int] = None, repetition_penalty: float = 1.0,
+                        presence_penalty: float = 0.0, frequency_penalty: float = 0.0):
+        """generate() with every completion held to a token automaton (qqq_amd/guided.py): `fsm` is one TokenFSM for all prompts, or a
+        sequence with one entry per prompt (None: that prompt is unconstrained).  Returns what generate() returns; every other keyword
+        means what it means there.
+
+        In front of every draw ops.fsm_mask sets the logit of every token the completion's state has no edge for to -inf -- the row's
+        eos_token_id stays drawable in an accepting state -- and the state then moves on over the token drawn.  The mask sits behind
+        the penalties and the minimum-length ban, in front of temperature, top-k and top-p, so logprobs=k records show the masked row as
+        they show the banned one.  A completion that reaches a terminal state (one without edges: the end of a choice nothing extends)
+        ends there, with no eos; in an accepting state with edges it ends when it draws its eos; the budget, stop and stop_token_ids
+        end it as in generate().  On the host path the states are plain Python in the bookkeeping (GuidedRequest); device_loop=True
+        builds a GuidedDecodeLoop whose captured step runs ops.fsm_mask and ops.fsm_advance over the automaton in device memory, with
+        capacities rounded up from this call's automaton: no token is read on the host between two syncs.
+
+        A completion can leave its automaton only where every allowed logit was -inf or NaN (the ban of a minimum length in a state
+        that allows nothing else, a model that overflowed): the call then raises RuntimeError, after the pool is left as it was found.
+        There is no draft_len: a speculative step draws several tokens from logits computed before any of them is known, so its rows
+        cannot be masked by the state behind the token in front -- guided decoding and SpecDecodeLoop do not combine."""
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"generate_guided: n={n} must be at least 1")
+        if logprobs is not None:
+            logprobs = int(logprobs)
+            if logprobs < 0 or logprobs > 32 or logprobs > self.lm_head.weight.shape[0]:
+                raise ValueError(f"generate_guided: logprobs={logprobs} outside [0, min(32, vocab)]")
+        req = GuidedRequest(fsm, "generate_guided", self.lm_head.weight.shape[0], temperature, top_k, top_p, generator, eos_token_id,
+                            repetition_penalty, presence_penalty, frequency_penalty, stop, stop_token_ids, min_new_tokens, n, logprobs)
+        result = self._generate(req, prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, cache, block_size, dtype,
+                                device_loop, 0)
+        if not device_loop:  # (the loop has raised for its own request)
+            req.check()
+        return result
 
     def beam_search(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, num_beams: int = 4, length_penalty: float = 1.0,
                     early_stopping: bool = False, eos_token_id: Optional[int] = None, num_return_sequences: int = 1,

@@ -2311,3 +2311,153 @@ def copy_blocks(pools: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, block
     if _compiling(pools, src, dst):
         return _copy_blocks_op(*args)
     return _copy_blocks_impl(*args)
+
+
+# ---- guided decoding (include/ext/guided/qqq_amd_guided.h): the mask in front of a sampler, the advance behind a loop's step
+
+def _fsm_tables_check(op, fsm_tensors):
+    # the automaton's four CSR arrays -> (n_states, n_edges)
+    if not isinstance(fsm_tensors, (tuple, list)) or len(fsm_tensors) != 4 or not all(isinstance(t, torch.Tensor) for t in fsm_tensors):
+        raise RuntimeError(f"{op}: fsm_tensors must be the four tensors (offsets, tokens, next, accept) of TokenFSM.tensors()")
+    offsets, tokens, nxt, accept = fsm_tensors
+    for name, t in (("offsets", offsets), ("tokens", tokens), ("next", nxt), ("accept", accept)):
+        if t.dtype != torch.int32 or t.dim() != 1:
+            raise RuntimeError(f"{op}: {name} must be int32 and one-dimensional, not {_dt(t.dtype)} {tuple(t.shape)}")
+    if accept.shape[0] < 1 or offsets.shape[0] != accept.shape[0] + 1:
+        raise RuntimeError(f"{op}: accept must hold S >= 1 states and offsets S + 1 entries, not {tuple(accept.shape)} and {tuple(offsets.shape)}")
+    if nxt.shape[0] != tokens.shape[0]:
+        raise RuntimeError(f"{op}: next must hold one entry per edge like tokens {tuple(tokens.shape)}, not {tuple(nxt.shape)}")
+    return accept.shape[0], tokens.shape[0]
+
+
+def _fsm_mask_check(logits, state, offsets, tokens, nxt, accept, eos, remaining):
+    # dtypes, shapes and strides -> (rows, vocab, n_states, n_edges)
+    op = "fsm_mask"
+    if logits.dtype != torch.float16 or logits.dim() != 2:
+        raise RuntimeError(f"{op}: logits must be fp16 [rows, vocab]")
+    rows, vocab = logits.shape
+    _rows_i32_check(op, rows, [("state", state)] + ([("eos", eos)] if eos is not None else []) +
+                    ([("remaining", remaining)] if remaining is not None else []))
+    n_states, n_edges = _fsm_tables_check(op, (offsets, tokens, nxt, accept))
+    if vocab < 1 or vocab > 262144 or rows > 65535:
+        raise RuntimeError(f"{op}: logits {tuple(logits.shape)} outside 1 <= vocab <= 262144, rows <= 65535")
+    if rows and (logits.stride(1) != 1 or logits.stride(0) < vocab):
+        raise RuntimeError(f"{op}: logits must have unit column stride and a row stride >= vocab (they are rewritten in place, never "
+                           f"copied), not strides {tuple(logits.stride())}")
+    return rows, vocab, n_states, n_edges
+
+
+def _fsm_mask_impl(logits, state, offsets, tokens, nxt, accept, eos, remaining):
+    names = ("logits", "state", "offsets", "tokens", "next", "accept", "eos", "remaining")
+    given = [(n, t) for n, t in zip(names, (logits, state, offsets, tokens, nxt, accept, eos, remaining)) if t is not None]
+    _same_gpu("fsm_mask", [t for _, t in given])
+    rows, vocab, n_states, n_edges = _fsm_mask_check(logits, state, offsets, tokens, nxt, accept, eos, remaining)
+    if rows == 0:
+        return
+    _in_place_check("fsm_mask", given[1:])
+    err = _lib.lib().qqq_fsm_mask(_ptr(logits), logits.stride(0), _ptr(state), _ptr(eos), _ptr(remaining), _ptr(offsets), _ptr(tokens),
+                                  _ptr(accept), n_states, n_edges, rows, vocab, logits.device.index or 0, _stream_for(logits))
+    _raise_lib("fsm_mask", err)
+
+
+@torch.library.custom_op("qqq_amd::fsm_mask", mutates_args=("logits",))
+def _fsm_mask_op(logits: torch.Tensor, state: torch.Tensor, offsets: torch.Tensor, tokens: torch.Tensor, nxt: torch.Tensor,
+                 accept: torch.Tensor, eos: Optional[torch.Tensor], remaining: Optional[torch.Tensor]) -> None:
+    _fsm_mask_impl(logits, state, offsets, tokens, nxt, accept, eos, remaining)
+
+
+@_fsm_mask_op.register_fake
+def _(logits, state, offsets, tokens, nxt, accept, eos, remaining):
+    _fsm_mask_check(logits, state, offsets, tokens, nxt, accept, eos, remaining)
+
+
+def fsm_mask(logits: torch.Tensor, state: torch.Tensor, fsm_tensors, eos: Optional[torch.Tensor] = None,
+             remaining: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Guided decoding's mask on fp16 logits [rows, vocab], in place and in one launch, in front of sample_tokens or sample_advance (behind
+    penalize_logits and ban_tokens) -> `logits`.
+
+    state        int32 [rows]: the rows' states in the automaton; a row whose state is outside [0, S) -- -1: no automaton -- is untouched
+    fsm_tensors  (offsets int32 [S + 1], tokens int32 [E], next int32 [E], accept int32 [S]): TokenFSM.tensors(device), or a loop's buffers
+    eos          int32 [rows] or None: the rows' eos ids (-1: none), allowed in an accepting state
+    remaining    int32 [rows] or None: a decode loop's budgets; a row with 0 is idle and untouched
+    Every column of [0, vocab) that is neither a token of the row's state nor its allowed eos becomes -inf; an allowed column keeps its
+    bits, and the logits are never read.  The exact semantics are stated in include/ext/guided/qqq_amd_guided.h.  Nothing is read on the
+    host and the launch size depends on the shapes alone, so a step with this call in it replays from a captured graph.  The logits are
+    never copied: unit column stride and a row stride >= vocab, or it raises."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(state, torch.Tensor) or logits.dim() != 2 or state.dim() != 1:
+        raise RuntimeError("fsm_mask: logits must be an fp16 [rows, vocab] tensor and state an int32 [rows] tensor")
+    _fsm_tables_check("fsm_mask", fsm_tensors)
+    args = (logits, state, *fsm_tensors, eos, remaining)
+    if _compiling(*(t for t in args if t is not None)):
+        _fsm_mask_op(*args)
+    else:
+        _fsm_mask_impl(*args)
+    return logits
+
+
+def _fsm_advance_check(out, n_out, n_fsm, state, offsets, tokens, nxt, accept, ids, pos, slots, remaining, eos):
+    # dtypes and shapes -> (rows, n_states, n_edges)
+    op = "fsm_advance"
+    if out.dtype != torch.int64 or out.dim() != 2 or out.shape[1] < 1:
+        raise RuntimeError(f"{op}: out must be int64 [rows, out_stride >= 1], not {_dt(out.dtype)} {tuple(out.shape)}")
+    rows = out.shape[0]
+    _rows_i32_check(op, rows, [("n_out", n_out), ("n_fsm", n_fsm), ("state", state), ("remaining", remaining)] +
+                    ([("eos", eos)] if eos is not None else []))
+    for name, t in (("ids", ids), ("pos", pos), ("slots", slots)):
+        if t.dtype != torch.int64 or t.dim() != 1 or t.shape[0] != rows:
+            raise RuntimeError(f"{op}: {name} must be int64 [{rows}], not {_dt(t.dtype)} {tuple(t.shape)}")
+    n_states, n_edges = _fsm_tables_check(op, (offsets, tokens, nxt, accept))
+    if rows > 65535:
+        raise RuntimeError(f"{op}: rows={rows} exceeds 65535")
+    return rows, n_states, n_edges
+
+
+def _fsm_advance_impl(out, n_out, n_fsm, state, offsets, tokens, nxt, accept, ids, pos, slots, remaining, eos):
+    names = ("out", "n_out", "n_fsm", "state", "offsets", "tokens", "next", "accept", "ids", "pos", "slots", "remaining", "eos")
+    args = (out, n_out, n_fsm, state, offsets, tokens, nxt, accept, ids, pos, slots, remaining, eos)
+    given = [(n, t) for n, t in zip(names, args) if t is not None]
+    _same_gpu("fsm_advance", [t for _, t in given])
+    rows, n_states, n_edges = _fsm_advance_check(*args)
+    if rows == 0:
+        return
+    _in_place_check("fsm_advance", given)
+    err = _lib.lib().qqq_fsm_advance(_ptr(out), out.shape[1], _ptr(n_out), _ptr(n_fsm), _ptr(state), _ptr(eos), _ptr(offsets), _ptr(tokens),
+                                     _ptr(nxt), _ptr(accept), n_states, n_edges, _ptr(ids), _ptr(pos), _ptr(slots), _ptr(remaining), rows,
+                                     out.device.index or 0, _stream_for(out))
+    _raise_lib("fsm_advance", err)
+
+
+@torch.library.custom_op("qqq_amd::fsm_advance", mutates_args=("n_fsm", "state", "ids", "pos", "slots", "remaining"))
+def _fsm_advance_op(out: torch.Tensor, n_out: torch.Tensor, n_fsm: torch.Tensor, state: torch.Tensor, offsets: torch.Tensor,
+                    tokens: torch.Tensor, nxt: torch.Tensor, accept: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor,
+                    remaining: torch.Tensor, eos: Optional[torch.Tensor]) -> None:
+    _fsm_advance_impl(out, n_out, n_fsm, state, offsets, tokens, nxt, accept, ids, pos, slots, remaining, eos)
+
+
+@_fsm_advance_op.register_fake
+def _(out, n_out, n_fsm, state, offsets, tokens, nxt, accept, ids, pos, slots, remaining, eos):
+    _fsm_advance_check(out, n_out, n_fsm, state, offsets, tokens, nxt, accept, ids, pos, slots, remaining, eos)
+
+
+def fsm_advance(out: torch.Tensor, n_out: torch.Tensor, n_fsm: torch.Tensor, state: torch.Tensor, fsm_tensors, ids: torch.Tensor,
+                pos: torch.Tensor, slots: torch.Tensor, remaining: torch.Tensor, eos: Optional[torch.Tensor] = None) -> None:
+    """Guided decoding's epilogue of a decode loop's step, behind sample_advance (and stop_check): every row's state moves on over the
+    tokens it emitted since it was last advanced, in one launch.  Returns nothing; n_fsm, state, ids, pos, slots and remaining are
+    updated in place.
+
+    out, n_out   int64 [rows, out_stride] and int32 [rows]: the rows' emitted tokens and their counts (sample_advance's)
+    n_fsm        int32 [rows]: the count up to which a row's state has been advanced;  state  int32 [rows]
+    fsm_tensors  (offsets, tokens, next, accept) as for fsm_mask
+    ids, pos, slots   int64 [rows];  remaining  int32 [rows]: the row state to retire;  eos  int32 [rows] or None
+    A token with an edge moves the state to the edge's target, and a terminal target (no edges) retires the row: ids 0, pos / slots -1,
+    remaining 0.  The row's eos without an edge in an accepting state leaves the state (the sampler retired the row).  Any other token
+    sets the state to -2 and retires the row.  A state outside [0, S) stays.  Then n_fsm[r] = n_out[r]; a row with nothing new writes
+    nothing.  The exact semantics are stated in include/ext/guided/qqq_amd_guided.h.  Nothing is read on the host and the launch size
+    depends on the shapes alone, so a decode step with this call in it replays from a captured graph."""
+    if not isinstance(out, torch.Tensor) or not isinstance(state, torch.Tensor) or out.dim() != 2:
+        raise RuntimeError("fsm_advance: out must be an int64 [rows, out_stride] tensor and state an int32 [rows] tensor")
+    _fsm_tables_check("fsm_advance", fsm_tensors)
+    args = (out, n_out, n_fsm, state, *fsm_tensors, ids, pos, slots, remaining, eos)
+    if _compiling(*(t for t in args if t is not None)):
+        return _fsm_advance_op(*args)
+    return _fsm_advance_impl(*args)

@@ -2,7 +2,8 @@
 QuantLlamaForCausalLM.generate (qqq_amd/model.py) and DecodeLoop.generate (qqq_amd/serve.py) keep the scheduling that is theirs and take
 from a Request the checked keywords, the blocks a prompt's family needs, the keywords a loop is built and called with, sample() -- the
 one pipeline from a pass's logits to its tokens --, receive() -- the one rule by which a completion ends -- and the shape of what the
-call returns; Records collects the logprobs records.  Completions are numbered prompt * n + sibling throughout.
+call returns; Records collects the logprobs records.  Completions are numbered prompt * n + sibling throughout.  GuidedRequest is the
+Request of generate_guided(): the same pipeline with ops.fsm_mask between the ban and the draw, and one automaton state per completion.
 """
 from __future__ import annotations
 
@@ -172,11 +173,15 @@ class Request:
             r = len(seqs)  # one transfer: the rows' counts, minimum and eos and the stop ids (none: an empty view)
             packed = torch.tensor([len(outs[q]) for q in seqs] + [self.least] * r + [self.eos] * r + self.end_ids, dtype=torch.int32, device=dev)
             ops.ban_tokens(logits, *packed.split([r, r, r, len(self.end_ids)]), base=0)
+        self._constrain(logits, seqs)
         u = torch.rand(logits.shape[0], generator=self.generator, device=dev)
         toks = ops.sample_tokens(logits, self.temperature, self.top_k, self.top_p, u)
         if self.records is not None:  # of the rows the sampler drew from; kept on the device until the call returns
             self.records.add(ops.topk_logprobs(logits, toks, self.k), seqs)
         return toks
+
+    def _constrain(self, logits: torch.Tensor, seqs: Sequence[int]) -> None:
+        """a subclass's last word on the rows the completions `seqs` draw from, behind the ban and in front of the draw: nothing here"""
 
     def receive(self, q: int, t: int, budget: int) -> bool:
         """completion q takes the token t it drew: whether it ends there -- on a token of `ends`, which stays; else, from `least` tokens
@@ -200,4 +205,57 @@ class Request:
         return nest(self.outs) if self.records is None else (nest(self.outs), nest(self.records.result(self.outs)))
 
 
-__all__ = ["Request", "Records", "TokenLogprobs", "stop_arguments", "stop_match"]
+def merge_automata(name: str, fsm, prompts: int):
+    """a guided call's `fsm` -- one TokenFSM for every prompt, or a sequence with one entry per prompt (None: unconstrained) -- checked
+    -> (the merged automaton, the start state per prompt: TokenFSM.merge).  `name` heads the messages."""
+    from .guided import TokenFSM
+
+    given = [fsm] * prompts if fsm is None or isinstance(fsm, TokenFSM) else list(fsm)
+    if len(given) != prompts:
+        raise ValueError(f"{name}: fsm holds {len(given)} entries for {prompts} prompts (one TokenFSM, or one entry per prompt)")
+    if any(f is not None and not isinstance(f, TokenFSM) for f in given):
+        raise ValueError(f"{name}: fsm must be a TokenFSM, or a sequence of TokenFSM and None")
+    return TokenFSM.merge(given)
+
+
+class GuidedRequest(Request):
+    """A Request whose completions follow token automata (qqq_amd/guided.py): `fsm` is one TokenFSM for every prompt or a sequence with one
+    entry per prompt (None: that prompt is unconstrained).  begin() merges them and gives every completion its start state; `state` holds
+    one host state per completion: -1 for no automaton, -2 once a token outside the automaton was drawn.  sample() masks the rows by
+    those states (ops.fsm_mask, behind the penalties and the ban), receive() steps them by the rules of include/ext/guided/
+    qqq_amd_guided.h and ends a completion that reaches a terminal state; a loop writes the states its rows ended in back into `state`."""
+
+    def __init__(self, fsm, *args):
+        super().__init__(*args)
+        self._given = fsm
+
+    def begin(self, prompts):
+        prompts, outs = super().begin(prompts)
+        self.fsm, starts = merge_automata(self.name, self._given, len(prompts))
+        self.state = [s for s in starts for _ in range(self.n)]
+        return prompts, outs
+
+    def _constrain(self, logits: torch.Tensor, seqs: Sequence[int]) -> None:
+        packed = torch.tensor([self.state[q] for q in seqs] + [self.eos] * len(seqs), dtype=torch.int32, device=logits.device)
+        state, eos = packed.split([len(seqs), len(seqs)])
+        ops.fsm_mask(logits, state, self.fsm.tensors(logits.device), eos=eos)
+
+    def receive(self, q: int, t: int, budget: int) -> bool:
+        s, ended = self.state[q], super().receive(q, t, budget)
+        if not 0 <= s < self.fsm.n_states:
+            return ended
+        to = self.fsm.step(s, t)
+        if to < 0 and self.fsm.accept[s] and t == self.eos >= 0:
+            return ended  # the eos in an accepting state: the state stays
+        self.state[q] = to
+        return ended or to < 0 or self.fsm.terminal(to)
+
+    def check(self) -> None:
+        """raises if a completion drew a token outside its automaton (state -2)"""
+        bad = [q for q, s in enumerate(self.state) if s == -2]
+        if bad:
+            raise RuntimeError(f"{self.name}: completion {bad[0]} (of {len(bad)}) drew a token outside its automaton: every token its state "
+                               f"allows had a logit of -inf or NaN")
+
+
+__all__ = ["GuidedRequest", "merge_automata", "Request", "Records", "TokenLogprobs", "stop_arguments", "stop_match"]

@@ -5,6 +5,8 @@ replayed `sync_every` times between host syncs while rows finish and join withou
     DecodeLoop      the rows' state arrays (include/qqq_amd_step.h), the one PagedStep built over them, the captured step, and generate()
     SpecDecodeLoop  the same loop with draft_len guessed tokens behind every row's last one, verified on the device by ops.spec_advance
                     (include/qqq_amd_spec.h): a replay emits 1 ... draft_len + 1 tokens per row.  Opt-in.
+    GuidedDecodeLoop  DecodeLoop whose rows follow token automata held in device memory (qqq_amd/guided.py): ops.fsm_mask in front of the
+                    sampler and ops.fsm_advance behind it, through DecodeLoop's _before_sample / _after_sample hooks.  Opt-in.
     ngram_draft     the drafter's rule in plain Python: what the device computes from a row's history, and what the host writes at admission
 
 QuantLlamaForCausalLM.generate (qqq_amd/model.py) builds its batch anew on the host for every token: a PagedKVCache.step, an eager launch
@@ -26,7 +28,7 @@ import torch
 
 from . import ops
 from .paged import PagedKVCache, PagedStep
-from .request import Request
+from .request import GuidedRequest, Request, merge_automata
 
 
 def _check_loop(name, lm, cache, rows, max_len, sync_every, graph, u_stride_error=None):
@@ -188,12 +190,20 @@ class DecodeLoop:
             self._penalize(logits)
         if self.stops:
             self._ban(logits)
+        self._before_sample(logits)
         ops.sample_advance(logits, self.temperature, self.top_k, self.top_p, self.u, self.tick, self.ids, self.pos, self.slots,
                            self.block_table, self.remaining, self.eos, self.out, self.n_out, self.cache.block_size)
         if self.logprobs is not None:  # the row that just emitted a token has n_rec < n_out: its record, from the logits it was drawn from
             ops.topk_logprobs_step(logits, self.out, self.n_out, self.n_rec, self.lp, self.lp_rank, self.lp_top_ids, self.lp_top)
         if self.stops:  # a row that eos or the budget just retired is checked too: its n_seen is behind its n_out
             self._stop_check()
+        self._after_sample(logits)
+
+    def _before_sample(self, logits: torch.Tensor) -> None:
+        """a subclass's last word on the step's logits, behind the penalties and the ban: nothing here"""
+
+    def _after_sample(self, logits: torch.Tensor) -> None:
+        """a subclass's epilogue of the step, behind the sampler, the records and the stop check: nothing here"""
 
     def _capture(self) -> None:
         """Warm up and capture the step with every row idle (nothing but `tick` changes), on a side stream."""
@@ -255,6 +265,20 @@ class DecodeLoop:
         self.cache.advance(seq, n["n_out"])  # the keys the device wrote: one per decode step the row took
         return row[:n["n_out"]]
 
+    def _request(self, *args) -> Request:
+        """The request object of one generate() call, from Request's own arguments: a subclass builds its own kind."""
+        return Request(*args)
+
+    def _admit_state(self, req: Request, q: int) -> dict:
+        """What an admitted row writes besides _row_state, from the request's knowledge of its completion q: nothing here."""
+        return {}
+
+    def _settle(self, req: Request, q: int, n: dict) -> None:
+        """A finished row's synced values `n` that the request keeps for its completion q: none here."""
+
+    def _reset(self) -> None:
+        """What the cleanup after an exception resets beyond `_idle`: nothing here."""
+
     # ---- the loop
 
     @torch.no_grad()
@@ -300,7 +324,7 @@ class DecodeLoop:
         length-1 stop sequence that matches it leaves an empty completion whose row never starts).  The keys the device wrote are still
         counted by n_out."""
         name = f"{self._name}.generate"
-        req = Request(name, self.lm.lm_head.weight.shape[0], temperature, top_k, top_p, generator, eos_token_id, repetition_penalty,
+        req = self._request(name, self.lm.lm_head.weight.shape[0], temperature, top_k, top_p, generator, eos_token_id, repetition_penalty,
                       presence_penalty, frequency_penalty, stop, stop_token_ids, min_new_tokens, self.family, self.logprobs)
         if req.stopping and not self.stops:
             raise ValueError(f"{name}: stop, stop_token_ids and min_new_tokens={req.least} need a loop built with stops=True")
@@ -374,7 +398,7 @@ class DecodeLoop:
                     owner[r] = q
                     cache.reserve(sid(q), keys[q // fam])
                 rows.append(r)
-                for array, value in self._row_state(prompt, t, cache.blocks(sid(q))).items():
+                for array, value in dict(self._row_state(prompt, t, cache.blocks(sid(q))), **self._admit_state(req, q)).items():
                     state.setdefault(array, []).append(value)
                 if fam > 1:
                     state.setdefault("shared", []).append(len(prompt) // bs * bs)
@@ -417,6 +441,7 @@ class DecodeLoop:
                         outs[i].extend(self._collect(row, len(prompts[i // fam]), sid(i), {a: v[r] for a, v in synced.items()}))
                         if self.stops:  # what ops.stop_check found behind the completion's end
                             req.cut(i, synced["n_trim"][r])
+                        self._settle(req, i, {a: v[r] for a, v in synced.items()})
                         cache.free(sid(i))
                         owner[r] = None
                     if fam > 1:
@@ -433,8 +458,99 @@ class DecodeLoop:
             if self.stops:
                 self.n_seen.copy_(self.n_out + 1)  # ... or a check
                 self.n_trim.zero_()
+            self._reset()
             raise
         return req.result()
+
+
+class GuidedDecodeLoop(DecodeLoop):
+    """DecodeLoop whose rows follow token automata (qqq_amd/guided.py) held in device memory: the step runs ops.fsm_mask between the ban and
+    the sampler and ops.fsm_advance behind the stop check, inside the captured graph, so a guided completion costs no host sync per token.
+
+    fsm_states, fsm_edges   the capacities of the loop's CSR buffers: fsm_offsets int32 [fsm_states + 1], fsm_tokens / fsm_next int32
+                [fsm_edges], fsm_accept int32 [fsm_states].  Every generate_guided() copies its (merged) automaton into them, as the stop
+                table is copied, and the ops are launched with the capacities: one capture serves every call.  An automaton that exceeds
+                them raises before anything runs.
+    The loop owns fsm_state (int32 [rows]: a row's state; -1 when idle or unconstrained, -2 once a token outside the automaton was drawn)
+    and n_fsm (int32 [rows]: the count of emitted tokens up to which fsm_state has been advanced).  Admission masks the prefill's logits
+    and steps the first token on the host (GuidedRequest) and writes fsm_state and n_fsm = 0; a first token that already reaches a terminal
+    state ends the completion there and the row never starts.  fsm_state is read back with the counts at every sync.  penalties, family,
+    logprobs and stops are DecodeLoop's.  generate() serves unconstrained calls; generate_guided() takes the automata."""
+
+    _name = "GuidedDecodeLoop"
+    _synced = DecodeLoop._synced + ("fsm_state",)
+    _idle = DecodeLoop._idle + (("fsm_state", -1),)
+
+    def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, fsm_states: int = 1024, fsm_edges: int = 65536, sync_every: int = 8,
+                 u_stride: int = 64, graph: bool = True, penalties: bool = False, family: int = 1, logprobs: Optional[int] = None,
+                 stops: bool = False):
+        fsm_states, fsm_edges = int(fsm_states), int(fsm_edges)
+        if fsm_states < 1 or fsm_edges < 1:
+            raise ValueError(f"GuidedDecodeLoop: fsm_states={fsm_states} and fsm_edges={fsm_edges} must be at least 1")
+        super().__init__(lm, cache, rows, max_len, sync_every=sync_every, u_stride=u_stride, graph=graph, penalties=penalties, family=family,
+                         logprobs=logprobs, stops=stops)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self.fsm_states, self.fsm_edges = fsm_states, fsm_edges
+        self.fsm_state = torch.full((self.rows,), -1, **i32)
+        self.n_fsm = torch.zeros(self.rows, **i32)
+        self.fsm_offsets = torch.zeros(fsm_states + 1, **i32)
+        self.fsm_tokens = torch.zeros(fsm_edges, **i32)
+        self.fsm_next = torch.zeros(fsm_edges, **i32)
+        self.fsm_accept = torch.zeros(fsm_states, **i32)
+        self._tables = (self.fsm_offsets, self.fsm_tokens, self.fsm_next, self.fsm_accept)
+        self._given = self._guided = None
+
+    def _before_sample(self, logits: torch.Tensor) -> None:
+        ops.fsm_mask(logits, self.fsm_state, self._tables, eos=self.eos, remaining=self.remaining)
+
+    def _after_sample(self, logits: torch.Tensor) -> None:
+        ops.fsm_advance(self.out, self.n_out, self.n_fsm, self.fsm_state, self._tables, self.ids, self.pos, self.slots, self.remaining,
+                        eos=self.eos)
+
+    def _request(self, *args) -> Request:
+        self._guided = GuidedRequest(self._given, *args)
+        return self._guided
+
+    def _start_call(self) -> None:
+        """the call's automaton into the loop's buffers, once: the states beyond it have no edges and nothing leads to them"""
+        super()._start_call()
+        fsm = self._guided.fsm  # (generate_guided has held it against the capacities)
+        pad = lambda a, size, fill: torch.cat([torch.from_numpy(a), torch.full((size - a.shape[0],), fill, dtype=torch.int32)])  # noqa: E731
+        self.fsm_offsets.copy_(pad(fsm.offsets, self.fsm_states + 1, fsm.n_edges))
+        self.fsm_tokens.copy_(pad(fsm.tokens, self.fsm_edges, 0))
+        self.fsm_next.copy_(pad(fsm.next, self.fsm_edges, 0))
+        self.fsm_accept.copy_(pad(fsm.accept, self.fsm_states, 0))
+
+    def _too_large(self, fsm) -> str:
+        return (f"{self._name}.generate_guided: an automaton of {fsm.n_states} states and {fsm.n_edges} edges exceeds the loop's capacities "
+                f"fsm_states={self.fsm_states} and fsm_edges={self.fsm_edges}")
+
+    def _admit_state(self, req: Request, q: int) -> dict:
+        return dict(fsm_state=req.state[q], n_fsm=0)
+
+    def _settle(self, req: Request, q: int, n: dict) -> None:
+        req.state[q] = n["fsm_state"]
+
+    def _reset(self) -> None:
+        self.n_fsm.copy_(self.n_out)  # no row owes an advance
+
+    @torch.no_grad()
+    def generate_guided(self, prompts: Sequence[Sequence[int]], fsm, max_new_tokens: int, *args, **kw):
+        """generate() with every completion held to `fsm`: one TokenFSM for all prompts, or a sequence with one entry per prompt (None:
+        unconstrained); the further arguments are generate()'s.  The merged automaton must fit the loop's capacities, or the call raises
+        ValueError before anything runs.  A completion that left its automaton (every allowed logit -inf or NaN) makes the call raise
+        RuntimeError once the pool is left as it was found and the loop idle."""
+        prompts = [list(p) for p in prompts]
+        merged, _ = merge_automata(f"{self._name}.generate_guided", fsm, len(prompts))
+        if merged.n_states > self.fsm_states or merged.n_edges > self.fsm_edges:
+            raise ValueError(self._too_large(merged))
+        self._given = fsm
+        try:
+            result = self.generate(prompts, max_new_tokens, *args, **kw)
+        finally:
+            self._given = None
+        self._guided.check()
+        return result
 
 
 def ngram_draft(history: Sequence[int], draft_len: int, ngram_max: int = 3) -> List[int]:
@@ -576,4 +692,4 @@ class SpecDecodeLoop(DecodeLoop):
         return row[first:first + n["n_out"]]
 
 
-__all__ = ["DecodeLoop", "SpecDecodeLoop", "ngram_draft"]
+__all__ = ["DecodeLoop", "GuidedDecodeLoop", "SpecDecodeLoop", "ngram_draft"]

@@ -67,6 +67,15 @@ rows, and the pool blocks in use at the peak (from the allocator; the saving is 
 at temperature 0.8 so that the siblings diverge.  Written to profiles/parallel_sampling_bench.json.
 
     python tools/bench_generate.py --n 1,4,8 [--prompt 2048] [--rounds 5] [--out profiles/parallel_sampling_bench.json]
+
+With --guided the tool times the replayed step with and without ops.fsm_mask and ops.fsm_advance in it, in one rotation: per batch a plain
+DecodeLoop beside a GuidedDecodeLoop serving generate_guided() with one automaton per prompt that allows exactly the plain loop's own
+completion (TokenFSM.from_choices of that one sequence: one allowed token per state, so the mask writes the whole row, its dearest case),
+by the protocol above.  Both loops emit the same tokens (asserted) and so run the same steps.  Written to
+profiles/guided_loop_bench.json: both step times with the rounds' min and max, the ops' difference to the plain step and the spread of
+both runs over the rounds.  No threshold: the feature is opt-in.  The ops alone are in profiles/fsm_bench.json (tools/bench_sample.py --fsm).
+
+    python tools/bench_generate.py --guided [--batch 1,16] [--rounds 5] [--out profiles/guided_loop_bench.json]
 """
 import argparse
 import json
@@ -472,6 +481,72 @@ def stops_main(args):
             f"{e['plain_round_spread_us']} / {e['stops_round_spread_us']}) sync_every=1 {e['sync1']['step_us']:.1f}" for k, e in p["draft_len"].items()))
 
 
+def guided_point(lm, batch, rounds, dev):
+    import torch
+
+    from bench_model import VOCAB
+    from qqq_amd import DecodeLoop, GuidedDecodeLoop, TokenFSM
+
+    g = torch.Generator().manual_seed(batch)
+    prompts = [torch.randint(0, VOCAB, (PROMPT,), generator=g).tolist() for _ in range(batch)]
+    max_len = -(-(PROMPT + NEW - 1) // BS) * BS
+    room = 1 << (batch * (NEW + 1) - 1).bit_length()
+    loops = {"plain": DecodeLoop(lm, lm.new_cache(batch * (max_len // BS), BS), rows=batch, max_len=max_len, sync_every=SYNC_EVERY),
+             "guided": GuidedDecodeLoop(lm, lm.new_cache(batch * (max_len // BS), BS), rows=batch, max_len=max_len, sync_every=SYNC_EVERY,
+                                        fsm_states=room, fsm_edges=room)}
+    free = loops["plain"].generate(prompts, NEW)
+    fsms = [TokenFSM.from_choices([o], vocab=VOCAB) for o in free]  # the plain loop's own completions: the same steps, one allowed token each
+
+    def timed(name, n):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = loops[name].generate(prompts, n) if name == "plain" else loops[name].generate_guided(prompts, fsms, n)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    for name in loops:  # warm-up: code objects, workspaces, rope tables, the capture
+        timed(name, 1)
+        assert timed(name, NEW)[1] == free, name
+    values = {name: [] for name in loops}
+    for _ in range(rounds):
+        for name in loops:
+            short, full = timed(name, 1)[0], timed(name, NEW)[0]
+            values[name].append((full - short) / (NEW - 1) * 1e6)
+    res = {"batch": batch, "prompt_tokens": PROMPT, "new_tokens": NEW, "layers": LAYERS, "fsm_states": sum(f.n_states for f in fsms),
+           "fsm_capacity": room}
+    for name, v in values.items():
+        res[name] = {"sync_every": SYNC_EVERY, "step_us": round(statistics.median(v), 1), "step_us_min": round(min(v), 1),
+                     "step_us_max": round(max(v), 1), "rounds_step_us": [round(x, 1) for x in v]}
+    res["ops_us_per_step"] = round(res["guided"]["step_us"] - res["plain"]["step_us"], 1)
+    res["plain_round_spread_us"] = round(res["plain"]["step_us_max"] - res["plain"]["step_us_min"], 1)
+    res["guided_round_spread_us"] = round(res["guided"]["step_us_max"] - res["guided"]["step_us_min"], 1)
+    res["ops_exceed_both_spreads"] = bool(res["ops_us_per_step"] > max(res["plain_round_spread_us"], res["guided_round_spread_us"]))
+    return res
+
+
+def guided_main(args):
+    import torch
+
+    from bench_model import build
+
+    dev = torch.device("cuda:0")
+    lm = build(LAYERS, dev).fuse_prefill()
+    with torch.no_grad():
+        points = [guided_point(lm, b, args.rounds, dev) for b in map(int, args.batch.split(","))]
+    out = {"tool": "tools/bench_generate.py --guided", "device": torch.cuda.get_device_name(0),
+           "shape": "Llama-2-7B layers, per-channel W4A8, fuse_qkv(), fuse_prefill(), paged fp16 cache, block 16, greedy",
+           "automaton": "per prompt the chain of the plain loop's own completion: one allowed token per state", "sync_every": SYNC_EVERY,
+           "rounds": args.rounds, "points": points}
+    path = args.out or os.path.join(ROOT, "profiles", "guided_loop_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"batch {p['batch']:3d}: plain {p['plain']['step_us']:.1f} guided {p['guided']['step_us']:.1f} us/step (+{p['ops_us_per_step']}, spreads "
+              f"{p['plain_round_spread_us']} / {p['guided_round_spread_us']})")
+
+
 def parallel_point(lm, n, prompt_len, rounds, dev):
     import torch
 
@@ -582,6 +657,8 @@ def main():
                     "(profiles/logprobs_loop_bench.json)")
     ap.add_argument("--stops", action="store_true", help="time the replayed step with and without ops.ban_tokens and ops.stop_check, and "
                     "the plain loop at sync_every=1 (profiles/stop_loop_bench.json)")
+    ap.add_argument("--guided", action="store_true", help="time the replayed step with and without ops.fsm_mask and ops.fsm_advance "
+                    "(profiles/guided_loop_bench.json)")
     ap.add_argument("--out", default=None, help="default profiles/decode_loop_bench.json, or profiles/spec_decode_bench.json with --draft-len")
     args = ap.parse_args()
     import torch
@@ -596,6 +673,8 @@ def main():
         return logprobs_main(args)
     if args.stops:
         return stops_main(args)
+    if args.guided:
+        return guided_main(args)
     if args.draft_len:
         return spec_main(args)
     args.out = args.out or os.path.join(ROOT, "profiles", "decode_loop_bench.json")

@@ -32,6 +32,19 @@ Points: every vocab and rows above x k = 0, 5 and 20.  Written: both times per p
 share of rows whose top-k ids agree and the largest difference of a log-probability.
 
     python tools/bench_sample.py --logprobs [--out profiles/logprobs_bench.json] [--rows 1,16,64] [--vocab 32000,128256,151936]
+
+With --fsm it times ops.fsm_mask and ops.fsm_advance (guided decoding) alone, each against a torch composition, by the same protocol:
+
+    fused   ops.fsm_mask(logits, state, tables): one launch;  ops.fsm_advance(out, n_out, n_fsm, state, tables, ...): one launch
+    torch   the automaton as dense tables: a bool [S, vocab] indexed by the rows' states and masked_fill_ of its complement; an int32
+            [S, vocab] of next states (-2: no edge) gathered at (state, the row's last token).  The dense tables take S * vocab * 5 bytes, which
+            is what rules them out beyond small automata; retiring a row and the eos rule are left out of the torch side.
+Points: every vocab and rows above x 1, 64 and 20000 allowed tokens per state, 16 states that share one token set (so that every call of
+the advance finds an edge) with random targets.  Every call of either advance is preceded by n_fsm.fill_(n_out - 1), or the op would find
+nothing new from the second call on; both sides carry that launch, and each call advances over one token.  Written: both times per point and op, torch / fused with the range over the
+rounds, and whether the two agree after one call.
+
+    python tools/bench_sample.py --fsm [--out profiles/fsm_bench.json] [--rows 1,16,64] [--vocab 32000,128256,151936]
 """
 import argparse
 import json
@@ -277,11 +290,106 @@ def logprobs_main(args, dev):
             for how in ("eager", "graph")))
 
 
+FSM_ALLOWED, FSM_STATES = (1, 64, 20000), 16
+
+
+def rotate(fns):
+    """the protocol of every point: eager, then replayed from a graph each; ROUNDS rounds of the median of CALLS calls, alternately"""
+    import torch
+
+    res = {}
+    for how in ("eager", "graph"):
+        run = fns if how == "eager" else {name: capture(f).replay for name, f in fns.items()}
+        for f in run.values():
+            for _ in range(WARMUP):
+                f()
+        torch.cuda.synchronize()
+        rounds = {name: [] for name in run}
+        for _ in range(ROUNDS):
+            for name, f in run.items():
+                rounds[name].append(statistics.median(time_calls(f, CALLS)))
+        r = {}
+        for name, v in rounds.items():
+            r[name] = {"median_us": round(statistics.median(v), 2), "min_us": round(min(v), 2), "max_us": round(max(v), 2),
+                       "rounds_us": [round(x, 2) for x in v]}
+        r["torch_over_fused"] = round(r["torch"]["median_us"] / r["fused"]["median_us"], 2)
+        r["torch_over_fused_range"] = [round(r["torch"]["min_us"] / r["fused"]["max_us"], 2), round(r["torch"]["max_us"] / r["fused"]["min_us"], 2)]
+        res[how] = r
+    return res
+
+
+def fsm_point(rows, vocab, allowed, dev):
+    import numpy as np
+    import torch
+
+    from qqq_amd import TokenFSM, ops
+
+    rng = np.random.default_rng(vocab + rows + allowed)
+    S = FSM_STATES
+    toks = np.sort(rng.choice(vocab, size=allowed, replace=False))
+    fsm = TokenFSM(np.arange(S + 1) * allowed, np.tile(toks, S), rng.integers(0, S, size=S * allowed), np.zeros(S, np.int32), 0, vocab)
+    tables = fsm.tensors(dev)
+    dense_ok = torch.zeros((S, vocab), dtype=torch.bool, device=dev)
+    dense_ok[:, torch.from_numpy(toks).to(dev)] = True
+    dense_next = torch.full((S, vocab), -2, dtype=torch.int32, device=dev)
+    dense_next[:, torch.from_numpy(toks).to(dev)] = tables[2].view(S, allowed)
+    g = torch.Generator(device=dev).manual_seed(vocab + rows + allowed)
+    fresh = (4.0 * torch.randn((rows, vocab), generator=g, device=dev)).half()
+    state0 = torch.randint(0, S, (rows,), generator=g, device=dev, dtype=torch.int32)
+    out = torch.from_numpy(rng.choice(toks, size=(rows, 4))).to(dev)
+    i32, i64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.int64, device=dev)
+    n_out, n_fsm, remaining = torch.full((rows,), 3, **i32), torch.zeros(rows, **i32), torch.ones(rows, **i32)
+    ids, pos, slots = torch.zeros(rows, **i64), torch.zeros(rows, **i64), torch.zeros(rows, **i64)
+    bufs = {"fused": fresh.clone(), "torch": fresh.clone()}
+    states = {"fused": state0.clone(), "torch": state0.clone()}
+
+    def torch_mask():
+        return bufs["torch"].masked_fill_(~dense_ok[state0.long()], float("-inf"))
+
+    def fused_advance():
+        n_fsm.fill_(2)
+        ops.fsm_advance(out, n_out, n_fsm, states["fused"], tables, ids, pos, slots, remaining)
+
+    def torch_advance():
+        n_fsm.fill_(2)
+        states["torch"].copy_(dense_next[states["torch"].long(), out[:, 2]])
+
+    mask = {"fused": lambda: ops.fsm_mask(bufs["fused"], state0, tables), "torch": torch_mask}
+    same = bool((mask["fused"]().view(torch.int16) == mask["torch"]().view(torch.int16)).all())
+    fused_advance()
+    torch_advance()
+    same_state = bool((states["fused"] == states["torch"]).all()) and int(remaining.min()) == 1
+    res = {"rows": rows, "vocab": vocab, "allowed": allowed, "states": S, "mask_bits_equal": same, "advance_states_equal": same_state,
+           "mask": rotate(mask), "advance": rotate({"fused": fused_advance, "torch": torch_advance})}
+    assert bool((states["fused"] == states["torch"]).all())
+    return res
+
+
+def fsm_main(args, dev):
+    import torch
+
+    points = [fsm_point(r, v, a, dev) for v in map(int, args.vocab.split(",")) for r in map(int, args.rows.split(",")) for a in FSM_ALLOWED]
+    notes = [f"{op} rows={p['rows']} vocab={p['vocab']} allowed={p['allowed']} {how}: the op does not win ({p[op][how]['torch_over_fused']}x)"
+             for p in points for op in ("mask", "advance") for how in ("eager", "graph") if p[op][how]["torch_over_fused_range"][0] <= 1.0]
+    out = {"tool": "tools/bench_sample.py --fsm", "device": torch.cuda.get_device_name(0), "rounds": ROUNDS, "calls_per_round": CALLS,
+           "points": points, "notes": notes or ["both ops win at every point, also at the unfavourable ends of both spreads"]}
+    path = args.out or os.path.join(ROOT, "profiles", "fsm_bench.json")
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"rows {p['rows']:3d} vocab {p['vocab']:6d} allowed {p['allowed']:5d}: " + "  ".join(
+            f"{op} {how} fused {p[op][how]['fused']['median_us']:7.1f} us torch {p[op][how]['torch']['median_us']:7.1f} us ({p[op][how]['torch_over_fused']}x)"
+            for op in ("mask", "advance") for how in ("eager", "graph")))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/sample_bench.json, profiles/penalty_bench.json with --penalties, profiles/logprobs_bench.json with --logprobs")
     ap.add_argument("--penalties", action="store_true", help="time ops.penalize_logits against a torch composition instead")
     ap.add_argument("--logprobs", action="store_true", help="time ops.topk_logprobs against a torch composition instead")
+    ap.add_argument("--fsm", action="store_true", help="time ops.fsm_mask and ops.fsm_advance against torch compositions instead (profiles/fsm_bench.json)")
     ap.add_argument("--rows", default="1,16,64")
     ap.add_argument("--vocab", default="32000,128256,151936")
     ap.add_argument("--modes", default="sample,top_k_top_p")
@@ -295,6 +403,8 @@ def main():
         return penalty_main(args, dev)
     if args.logprobs:
         return logprobs_main(args, dev)
+    if args.fsm:
+        return fsm_main(args, dev)
     args.out = args.out or os.path.join(ROOT, "profiles", "sample_bench.json")
     points = [point(r, v, m, dev) for m in args.modes.split(",") for v in map(int, args.vocab.split(",")) for r in map(int, args.rows.split(","))]
     notes = [f"{p['mode']} rows={p['rows']} vocab={p['vocab']} {how}: the fused op does not win ({p[how]['torch_over_fused']}x)"
