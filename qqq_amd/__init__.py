@@ -47,6 +47,9 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
                                                                                     # guided decoding: a token automaton in device memory masks
                                                                                     # the row in front of a sampler and advances behind it
     TokenFSM, QuantLlamaForCausalLM.generate_guided(prompts, fsm, max_new_tokens, ...), GuidedDecodeLoop   # qqq_amd/guided.py, serve.py
+    lora_add(y, xq, s1, A, B, scale, slot, part_cols)                               # batched LoRA beside the GEMM: every row adds its own
+                                                                                    # adapter's low-rank product, its slot read on the device
+    LoraBank(lm, slots, rank), LoraStep, generate(..., lora=bank, adapters=[...])   # multi-LoRA serving; qqq_amd/lora.py
 """
 from .ops import (  # noqa: F401
     ban_tokens,
@@ -60,6 +63,7 @@ from .ops import (  # noqa: F401
     expand_int8,
     fsm_advance,
     fsm_mask,
+    lora_add,
     marlin_qqq_gemm,
     mul,
     penalize_logits,
@@ -97,6 +101,7 @@ from .request import TokenLogprobs  # noqa: F401
 from .model import QuantLlamaForCausalLM, QuantLlamaModel  # noqa: F401
 from .serve import DecodeLoop, GuidedDecodeLoop, SpecDecodeLoop, ngram_draft  # noqa: F401
 from .guided import TokenFSM  # noqa: F401
+from .lora import LoraBank, LoraStep  # noqa: F401
 from .score import pack_steps  # noqa: F401
 from .beam import BeamHypothesis  # noqa: F401
 
@@ -109,4 +114,5 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "spec_advance", "SpecDecodeLoop", "ngram_draft", "verify_attention_paged", "verify_attention_paged_kv8", "penalize_logits",
            "decode_attention_paged_shared", "decode_attention_paged_shared_kv8", "decode_attention_shared_plan",
            "topk_logprobs", "topk_logprobs_step", "TokenLogprobs", "ban_tokens", "stop_check",
-           "beam_step", "copy_blocks", "BeamHypothesis", "fsm_mask", "fsm_advance", "TokenFSM", "GuidedDecodeLoop"]
+           "beam_step", "copy_blocks", "BeamHypothesis", "fsm_mask", "fsm_advance", "TokenFSM", "GuidedDecodeLoop",
+           "lora_add", "LoraBank", "LoraStep"]

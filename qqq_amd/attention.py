@@ -34,7 +34,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .blocks import QuantLlamaMLP, QuantRMSNorm
+from .blocks import QuantLlamaMLP, QuantRMSNorm, _no_lora, forward_int8_lora, lora_add_slices
 from .paged import PagedKVCache, PagedStep
 from .qlinear import QuantLinear, fuse_quant_linears
 
@@ -278,13 +278,19 @@ class QuantLlamaAttention(nn.Module):
             self._qkv._apply(fn, recurse=recurse)
         return self
 
-    def project_qkv(self, xq: torch.Tensor, s1: torch.Tensor):
-        """(q, k, v) fp16 token rows [b*s, h*d], [b*s, kvh*d], [b*s, kvh*d]: three views into one output after fuse_qkv()."""
+    def project_qkv(self, xq: torch.Tensor, s1: torch.Tensor, lora=None):
+        """(q, k, v) fp16 token rows [b*s, h*d], [b*s, kvh*d], [b*s, kvh*d]: three views into one output after fuse_qkv().  `lora`: None, or
+        the layer's LayerLora (qqq_amd/lora.py), whose adapters are added to the projections it holds."""
+        pick = lora if lora is not None else _no_lora
         if self._qkv is not None:
-            qkv = self._qkv.forward_int8(xq, s1)
+            qkv = forward_int8_lora(self._qkv, xq, s1, pick("qkv"))
             nq, nk = self.num_heads * self.head_dim, self.num_key_value_heads * self.head_dim
-            return qkv[:, :nq], qkv[:, nq:nq + nk], qkv[:, nq + nk:]
-        return self.q_proj.forward_int8(xq, s1), self.k_proj.forward_int8(xq, s1), self.v_proj.forward_int8(xq, s1)
+            q, k, v = qkv[:, :nq], qkv[:, nq:nq + nk], qkv[:, nq + nk:]
+            if lora is not None and pick("qkv") is None:  # part of the group is targeted: its columns of the fused output
+                lora_add_slices(xq, s1, lora, (("q_proj", q), ("k_proj", k), ("v_proj", v)))
+            return q, k, v
+        return (forward_int8_lora(self.q_proj, xq, s1, pick("q_proj")), forward_int8_lora(self.k_proj, xq, s1, pick("k_proj")),
+                forward_int8_lora(self.v_proj, xq, s1, pick("v_proj")))
 
     def attend(self, q_out: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
         """scaled_dot_product_attention of q_out [b, h, s, d] over the cache slice [:, :, :start+s] -> fp16 [b, s, h*d]: causal for a
@@ -319,8 +325,10 @@ class QuantLlamaAttention(nn.Module):
                                       f"16384 (h={self.num_heads}, kvh={self.num_key_value_heads}, head_dim={self.head_dim})")
         # the tables grow in powers of two with the longest sequence, not with the pool (which may hold millions of keys)
         cos, sin = self.rope_tables(min(cache.capacity, max(1024, 1 << (step.max_len - 1).bit_length())))
-        q, k, v = self.project_qkv(xq, s1)
         li = self.layer_idx
+        lora = step.lora.layer(li) if step.lora is not None else None
+        o_lora = lora("o_proj") if lora is not None else None
+        q, k, v = self.project_qkv(xq, s1) if lora is None else self.project_qkv(xq, s1, lora)
         pools = (cache.k[li], cache.v[li]) + ((cache.k_scale[li], cache.v_scale[li]) if cache.quantized else ())
         q_out = (ops.rope_qkv_paged_kv8 if cache.quantized else ops.rope_qkv_paged)(q, k, v, cos, sin, step.pos, step.slots, *pools)
         if step.decode and self._shared and step.family is not None:  # fuse_shared(): siblings read their common keys once per pack
@@ -328,27 +336,27 @@ class QuantLlamaAttention(nn.Module):
             pack = min(int(step.family_max), 64 // (self.num_heads // self.num_key_value_heads))
             aq, a1 = shared(q_out, *pools, step.block_table, step.last_pos, step.family, step.shared, pack, self.scaling,
                             max_len=step.max_len)
-            return self.o_proj.forward_int8(aq, a1)
+            return forward_int8_lora(self.o_proj, aq, a1, o_lora)
         if step.decode:  # one token per sequence: the decode kernel through the block table, whatever fuse_decode() says
             decode = ops.decode_attention_paged_kv8 if cache.quantized else ops.decode_attention_paged
             aq, a1 = decode(q_out, *pools, step.block_table, step.last_pos, self.scaling, max_len=step.max_len)
-            return self.o_proj.forward_int8(aq, a1)
+            return forward_int8_lora(self.o_proj, aq, a1, o_lora)
         t = self._verify_tokens(step)
         if t:  # fuse_verify(): a uniform chunk of t tokens per sequence through the decode kernel's split over keys
             verify = ops.verify_attention_paged_kv8 if cache.quantized else ops.verify_attention_paged
             aq, a1 = verify(q_out, *pools, step.block_table, step.start_pos, t, self.scaling, max_len=step.max_len)
-            return self.o_proj.forward_int8(aq, a1)
+            return forward_int8_lora(self.o_proj, aq, a1, o_lora)
         if self._prefill:  # fuse_prefill(): the whole packed batch in one ragged causal attention over the pool, quantised for o_proj
             prefill = ops.prefill_attention_paged_kv8 if cache.quantized else ops.prefill_attention_paged
             aq, a1 = prefill(q_out, *pools, step.block_table, step.cu_tokens, step.start_pos, self.scaling, max_len=step.max_len)
-            return self.o_proj.forward_int8(aq, a1)
+            return forward_int8_lora(self.o_proj, aq, a1, o_lora)
         outs, t = [], 0
         for sid, c, start in zip(step.seq_ids, step.counts, step.starts):  # prefill / chunks: SDPA over a gathered copy, per sequence
             kc, vc = cache.gather(li, sid, start + c)
             outs.append(self._sdpa(q_out[t:t + c].transpose(0, 1)[None], kc, vc, start)[0])
             t += c
         aq, a1 = ops.dynamic_quant(torch.cat(outs) if len(outs) > 1 else outs[0])
-        return self.o_proj.forward_int8(aq.reshape(m, -1), a1.reshape(m, 1))
+        return forward_int8_lora(self.o_proj, aq.reshape(m, -1), a1.reshape(m, 1), o_lora)
 
     def forward_int8(self, xq: torch.Tensor, s1: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
         if isinstance(cache, PagedKVCache):  # `start` is the PagedStep of this forward pass
@@ -484,12 +492,17 @@ class QuantLlamaDecoderLayer(nn.Module):
     def shared_fused(self) -> bool:
         return self.self_attn.shared_fused
 
+    def _lora(self, step):
+        """the layer's adapters of a PagedStep that carries some (step.lora: a LoraStep), else None; a start position carries none"""
+        held = getattr(step, "lora", None)
+        return held.layer(self.self_attn.layer_idx) if held is not None else None
+
     def forward(self, hidden: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
         x = hidden.reshape(-1, self.hidden_size)
         a = self.self_attn.forward_int8(*self.input_layernorm(x), cache, start)
         # a becomes h = fp16(a + x), torch's `residual + attn_out` (fp16 addition commutes), in the launch that quantises its norm
         mq, ms = self.post_attention_layernorm(x, a)
-        return (a + self.mlp.forward_int8(mq, ms)).reshape(hidden.shape)
+        return (a + forward_int8_lora(self.mlp, mq, ms, self._lora(start))).reshape(hidden.shape)
 
     def forward_chained(self, delta: torch.Tensor, residual: Optional[torch.Tensor], cache: KVCache, start: int):
         """The layer on a hidden state handed over as an unformed sum, hidden = residual + delta, returned the same way: (delta, residual)
@@ -504,7 +517,7 @@ class QuantLlamaDecoderLayer(nn.Module):
             xq, s1 = self.input_layernorm(delta, residual)  # residual becomes the hidden state
         a = self.self_attn.forward_int8(xq, s1, cache, start)
         mq, ms = self.post_attention_layernorm(residual, a)  # a becomes h = hidden + attention
-        return self.mlp.forward_int8(mq, ms), a
+        return forward_int8_lora(self.mlp, mq, ms, self._lora(start)), a
 
 
 __all__ = ["KVCache", "PagedKVCache", "PagedStep", "QuantLlamaAttention", "QuantLlamaDecoderLayer", "rope_inv_freq", "rope_tables"]

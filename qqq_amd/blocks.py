@@ -35,6 +35,26 @@ class QuantRMSNorm(nn.Module):
         return f"{self.weight.shape[0]}, eps={self.variance_epsilon}"
 
 
+def _no_lora(name):
+    return None
+
+
+def forward_int8_lora(mod, xq: torch.Tensor, s1: torch.Tensor, lora):
+    """mod.forward_int8(xq, s1), with `lora` behind them only when there is one: a call without adapters is the call it always was"""
+    return mod.forward_int8(xq, s1) if lora is None else mod.forward_int8(xq, s1, lora)
+
+
+def lora_add_slices(xq: torch.Tensor, s1: torch.Tensor, lora, named) -> None:
+    """ops.lora_add on the column slices `named` = ((projection, its view of a fused output), ...) for which `lora` holds adapters: what a
+    fused holder runs when only part of its group is targeted"""
+    for name, y in named:
+        g = lora(name)
+        if g is not None and y.shape[0]:
+            if y.dim() != 2 or xq.dim() != 2:
+                raise RuntimeError("lora: adapters take packed token rows, xq [tokens, infeatures]")
+            ops.lora_add(y, xq, s1.reshape(-1), *g)
+
+
 def _drop_fused_on_load(module, *args, **kwargs):
     module._gate_up = None  # a state-dict is being loaded: the fused gate|up copy would be stale
 
@@ -86,14 +106,20 @@ class QuantLlamaMLP(nn.Module):
             self._gate_up._apply(fn, recurse=recurse)
         return self
 
-    def forward_int8(self, xq: torch.Tensor, s1: torch.Tensor) -> torch.Tensor:
+    def forward_int8(self, xq: torch.Tensor, s1: torch.Tensor, lora=None) -> torch.Tensor:
+        """`lora`: None, or the layer's LayerLora (qqq_amd/lora.py): lora(name) -> what QuantLinear.forward_int8(lora=) takes, or None"""
+        pick = lora if lora is not None else _no_lora
         if self._gate_up is not None:
-            gu = self._gate_up.forward_int8(xq, s1)
+            gu = forward_int8_lora(self._gate_up, xq, s1, pick("gate_up"))
             i = self.intermediate_size
-            hq, hs = ops.silu_mul_quant(gu[..., :i], gu[..., i:])
+            gate, up = gu[..., :i], gu[..., i:]
+            if lora is not None and pick("gate_up") is None:  # part of the group is targeted: its columns of the fused output
+                lora_add_slices(xq, s1, lora, (("gate_proj", gate), ("up_proj", up)))
+            hq, hs = ops.silu_mul_quant(gate, up)
         else:
-            hq, hs = ops.silu_mul_quant(self.gate_proj.forward_int8(xq, s1), self.up_proj.forward_int8(xq, s1))
-        return self.down_proj.forward_int8(hq, hs)
+            hq, hs = ops.silu_mul_quant(forward_int8_lora(self.gate_proj, xq, s1, pick("gate_proj")),
+                                        forward_int8_lora(self.up_proj, xq, s1, pick("up_proj")))
+        return forward_int8_lora(self.down_proj, hq, hs, pick("down_proj"))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.forward_int8(*ops.dynamic_quant(x.half()))

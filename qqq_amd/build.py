@@ -73,6 +73,16 @@ def nested_headers() -> list:
     return out
 
 
+def deep_headers() -> list:
+    """every header three or more levels below include/, wherever it sits (include/<group>/<area>/<feature>/.../*.h): bound behind
+    nested_headers().  It walks the whole tree below that depth, so a later feature adds a file and no lister."""
+    out = []
+    for top, _, files in os.walk(INCLUDE):
+        if os.path.relpath(top, INCLUDE).count(os.sep) >= 2:
+            out += [os.path.join(top, f) for f in files if f.endswith(".h")]
+    return sorted(out)
+
+
 def bound_headers() -> list:
     """what libqqq_amd.so is bound from and rebuilt for, in binding order"""
     return operator_headers() + serving_headers() + extension_headers() + feature_headers()
@@ -88,7 +98,7 @@ def _stale(lib: str, extra) -> bool:
 
 
 def needs_build() -> bool:
-    return _stale(LIB, bound_headers() + nested_headers())
+    return _stale(LIB, bound_headers() + nested_headers() + deep_headers())
 
 
 def _compile(src: str, out: str, verbose: bool, flags=()) -> str:

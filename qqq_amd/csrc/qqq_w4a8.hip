@@ -42,6 +42,7 @@
 //   qqq_spec.hip.h     the speculative decode loop's step: draft_len + 1 draws per row by that sampler, the accept rule and the n-gram drafter
 //   qqq_stop.hip.h     stop sequences, stop token ids and the minimum length: the ban in front of a sampler, the check behind a loop's step
 //   qqq_guided.hip.h   guided decoding over a token automaton in device memory: the mask in front of a sampler, the advance behind a loop's step
+//   qqq_lora.hip.h     the batched LoRA op: fp16 low-rank adapters added to a GEMM's output, every token's adapter read from device memory
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -100,6 +101,8 @@
 #include "../../include/serving/stop/qqq_amd_stop.h"
 #include "qqq_guided.hip.h"
 #include "../../include/ext/guided/qqq_amd_guided.h"
+#include "qqq_lora.hip.h"
+#include "../../include/ext/adapters/lora/qqq_amd_lora.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1819,6 +1822,75 @@ extern "C" int qqq_fsm_advance(const void* out, int out_stride, const void* n_ou
   hipLaunchKernelGGL(qqq_fsm_advance_kernel, dim3((rows + FSM_WAVES - 1) / FSM_WAVES), dim3(FSM_NT), 0, static_cast<hipStream_t>(stream), a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_fsm_advance_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- batched LoRA (include/ext/adapters/lora/qqq_amd_lora.h; kernel in qqq_lora.hip.h): one launch, a workgroup per 16 tokens and column
+// chunk, no workspace.
+extern "C" int qqq_lora_add(void* y, int ldy, const void* xq, const void* s1, const void* A, size_t a_stride, const void* B, size_t b_stride,
+                            const void* scale, const void* slot, const void* part_cols_host, int P, int T, int N, int K, int R, int S, int dev,
+                            void* stream) {
+  g_err[0] = 0;
+  const int* part_cols = static_cast<const int*>(part_cols_host);
+  if (T < 0 || T > 1048576) {
+    snprintf(g_err, sizeof(g_err), "qqq_lora_add: T=%d outside [0, 1048576]", T);
+    return QQQ_ERR_ARG;
+  }
+  if (T == 0) return QQQ_OK;
+  if (R != 8 && R != 16 && R != 32 && R != 64) {
+    snprintf(g_err, sizeof(g_err), "qqq_lora_add: R=%d is not one of 8, 16, 32, 64", R);
+    return QQQ_ERR_ARG;
+  }
+  if (N < 64 || K < 64 || N % 64 != 0 || K % 64 != 0 || S < 1 || P < 1 || P > 3 || ldy < N || ldy % 2 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_lora_add: bad shape N=%d K=%d S=%d P=%d ldy=%d (need N and K positive multiples of 64, S >= 1, "
+             "1 <= P <= 3, ldy >= N and even)", N, K, S, P, ldy);
+    return QQQ_ERR_ARG;
+  }
+  if (!part_cols) {
+    snprintf(g_err, sizeof(g_err), "qqq_lora_add: part_cols must be non-NULL (P + 1 ints in host memory)");
+    return QQQ_ERR_ARG;
+  }
+  bool cols_ok = part_cols[0] == 0 && part_cols[P] == N;
+  for (int p = 0; p < P; ++p) cols_ok = cols_ok && part_cols[p] % 64 == 0 && part_cols[p] >= 0 && part_cols[p + 1] > part_cols[p];
+  if (!cols_ok) {
+    snprintf(g_err, sizeof(g_err), "qqq_lora_add: part_cols must ascend strictly from 0 to N=%d in multiples of 64 (P=%d: %d, %d, %d, %d)", N, P,
+             part_cols[0], part_cols[1], P > 1 ? part_cols[2] : -1, P > 2 ? part_cols[3] : -1);
+    return QQQ_ERR_ARG;
+  }
+  if (a_stride < (size_t)P * R * K || a_stride % 8 != 0 || b_stride < (size_t)N * R || b_stride % 8 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_lora_add: bad slot stride a_stride=%zu b_stride=%zu (need multiples of 8 elements, a_stride >= "
+             "P * R * K = %zu, b_stride >= N * R = %zu)", a_stride, b_stride, (size_t)P * R * K, (size_t)N * R);
+    return QQQ_ERR_ARG;
+  }
+  if (!y || !xq || !s1 || !A || !B || !scale || !slot || misaligned(y, 4) || misaligned(xq, 16) || misaligned(s1, 4) || misaligned(A, 16) ||
+      misaligned(B, 16) || misaligned(scale, 4) || misaligned(slot, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_lora_add: bad argument (every pointer must be non-NULL; xq, A and B 16-byte, everything else 4-byte "
+             "aligned)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_lora_args a;
+  a.y = static_cast<unsigned short*>(y);
+  a.xq = static_cast<const signed char*>(xq);
+  a.s1 = static_cast<const float*>(s1);
+  a.A = static_cast<const _Float16*>(A);
+  a.B = static_cast<const _Float16*>(B);
+  a.scale = static_cast<const float*>(scale);
+  a.slot = static_cast<const int*>(slot);
+  a.ldy = ldy;
+  a.a_stride = (long long)a_stride;
+  a.b_stride = (long long)b_stride;
+  a.T = T;
+  a.N = N;
+  a.K = K;
+  a.S = S;
+  a.P = P;
+  for (int p = 0; p < 4; ++p) a.pc[p] = p <= P ? part_cols[p] : N;
+  a.chunk_w = lora_chunk_width(T, P, part_cols);
+  const dim3 grid((T + LORA_TILE - 1) / LORA_TILE, lora_chunks(P, part_cols, a.chunk_w));
+  DeviceGuard guard(dev);
+  lora_launch(R, grid, static_cast<hipStream_t>(stream), a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_lora_add_kernel launch");
   return QQQ_OK;
 }
 

@@ -196,7 +196,8 @@ class QuantLlamaForCausalLM(nn.Module):
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
                  generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, cache: Optional[PagedKVCache] = None,
-                 block_size: int = 16, dtype=torch.float16, device_loop: bool = False, stop: Optional[Sequence[Sequence[int]]] = None,
+                 block_size: int = 16, dtype=torch.float16, lora=None, adapters: Optional[Sequence[Optional[int]]] = None,
+                 device_loop: bool = False, stop: Optional[Sequence[Sequence[int]]] = None,
                  stop_token_ids: Optional[Sequence[int]] = None, min_new_tokens: int = 0, n: int = 1, logprobs: Optional[int] = None,
                  draft_len: int = 0, repetition_penalty: float = 1.0, presence_penalty: float = 0.0,
                  frequency_penalty: float = 0.0) -> List[List[int]]:
@@ -258,7 +259,14 @@ class QuantLlamaForCausalLM(nn.Module):
         fewer than M tokens, as in vLLM, and the budget max_new_tokens wins over M.  logprobs records are cut like their tokens.  On the
         host path the matching is plain Python in the bookkeeping; device_loop=True builds the loop with stops=True, whose captured
         step runs ops.ban_tokens and ops.stop_check (no host sync per token); a speculative step that emits several tokens is checked at
-        every new length in order, and tokens behind a match are dropped."""
+        every new length in order, and tokens behind a match are dropped.
+
+        lora=bank, adapters=[slot or None per prompt] (None, None: off, and then nothing of it runs): every prompt is served through the
+        adapter in its slot of the LoraBank (qqq_amd/lora.py) -- ops.lora_add behind every targeted projection, the slot of every token of
+        a pass in PagedStep.lora -- and a prompt with None through the base model.  The adapters of a batch are mixed per token and a row's
+        result depends on its own adapter alone, so a prompt's tokens are those it gets when it is run alone with its adapter.  n > 1:
+        the siblings inherit their prompt's slot.  device_loop=True builds the loop with lora=bank: its captured step holds the rows' slots
+        in device memory, one capture serves every mix of adapters, and bank.load() / unload() between calls need no new capture."""
         n, draft_len = int(n), int(draft_len)
         if n < 1:
             raise ValueError(f"generate: n={n} must be at least 1")
@@ -274,7 +282,7 @@ class QuantLlamaForCausalLM(nn.Module):
         if draft_len < 0 or (draft_len > 0 and not device_loop):
             raise ValueError(f"generate: draft_len={draft_len} must be 0, or positive together with device_loop=True")
         req = Request("generate", self.lm_head.weight.shape[0], temperature, top_k, top_p, generator, eos_token_id, repetition_penalty,
-                      presence_penalty, frequency_penalty, stop, stop_token_ids, min_new_tokens, n, logprobs)
+                      presence_penalty, frequency_penalty, stop, stop_token_ids, min_new_tokens, n, logprobs, lora=lora, adapters=adapters)
         return self._generate(req, prompts, max_new_tokens, temperature, top_k, top_p, generator, eos_token_id, cache, block_size, dtype,
                               device_loop, draft_len)
 
@@ -329,7 +337,8 @@ class QuantLlamaForCausalLM(nn.Module):
         try:
             while waiting or running:
                 if running:
-                    logits = self(cur, cache, cache.step([sid(i) for i in running], [1] * len(running)))
+                    step = cache.step([sid(i) for i in running], [1] * len(running))
+                    logits = self(cur, cache, req.with_adapters(step, [i // n for i in running], step.counts))
                     toks = req.sample(logits, running, workspace)
                     running, cur = settle(running, toks)
                 new = []
@@ -346,7 +355,8 @@ class QuantLlamaForCausalLM(nn.Module):
                     continue
                 ids = torch.tensor([t for i in new for t in prompts[i]], dtype=torch.int64, device=dev)
                 born = [i * n + j for i in new for j in range(n)]
-                logits = self(ids, cache, cache.step([sid(i * n) for i in new], [len(prompts[i]) for i in new]))
+                step = cache.step([sid(i * n) for i in new], [len(prompts[i]) for i in new])
+                logits = self(ids, cache, req.with_adapters(step, new, step.counts))
                 toks = req.sample(logits, born, workspace)
                 alive, first = settle(born, toks, fork=n > 1)
                 cur = first if not running else torch.cat([cur, first])

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import NamedTuple, Optional
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -2461,3 +2461,87 @@ def fsm_advance(out: torch.Tensor, n_out: torch.Tensor, n_fsm: torch.Tensor, sta
     if _compiling(*(t for t in args if t is not None)):
         return _fsm_advance_op(*args)
     return _fsm_advance_impl(*args)
+
+
+# ---- batched LoRA (include/ext/adapters/lora/qqq_amd_lora.h): low-rank fp16 adapters beside the W4A8 GEMM, every token's adapter on the device
+
+def _lora_add_check(y, xq, s1, A, B, scale, slot, part_cols):
+    # dtypes, shapes and strides -> (T, N, K, R, S, P); R's list, the offsets' rules and the alignment are the library's to refuse
+    op = "lora_add"
+    for name, t, dt in (("y", y, torch.float16), ("xq", xq, torch.int8), ("s1", s1, torch.float32), ("A", A, torch.float16),
+                        ("B", B, torch.float16), ("scale", scale, torch.float32), ("slot", slot, torch.int32)):
+        if t.dtype != dt:
+            raise RuntimeError(f"{op}: {name} must be {_dt(dt)}, not {_dt(t.dtype)}")
+    if y.dim() != 2 or xq.dim() != 2 or xq.shape[0] != y.shape[0]:
+        raise RuntimeError(f"{op}: y must be fp16 [T, N] and xq int8 [T, K], not {tuple(y.shape)} and {tuple(xq.shape)}")
+    (T, N), K = y.shape, xq.shape[1]
+    if s1.numel() != T or s1.dim() not in (1, 2) or slot.dim() != 1 or slot.shape[0] != T:
+        raise RuntimeError(f"{op}: s1 must be f32 [{T}] or [{T}, 1] and slot int32 [{T}], not {tuple(s1.shape)} and {tuple(slot.shape)}")
+    P = len(part_cols) - 1
+    if A.dim() != 3 or B.dim() != 3 or scale.dim() != 1 or P < 1:
+        raise RuntimeError(f"{op}: A must be fp16 [S, P * R, K], B fp16 [S, N, R], scale f32 [S] and part_cols P + 1 >= 2 offsets")
+    S, R = B.shape[0], B.shape[2]
+    if A.shape != (S, P * R, K) or B.shape[1] != N or scale.shape[0] != S or S < 1:
+        raise RuntimeError(f"{op}: with y {tuple(y.shape)}, xq {tuple(xq.shape)} and {P} part(s), A must be [S, {P} * R, {K}], B [S, {N}, R] and "
+                           f"scale [S], not {tuple(A.shape)}, {tuple(B.shape)} and {tuple(scale.shape)}")
+    if T and (y.stride(1) != 1 or y.stride(0) < N):
+        raise RuntimeError(f"{op}: y must have unit column stride and a row stride >= N (it is updated in place, never copied), not strides "
+                           f"{tuple(y.stride())}")
+    if A.stride()[1:] != (K, 1) or B.stride()[1:] != (R, 1) or (S > 1 and (A.stride(0) < P * R * K or B.stride(0) < N * R)):
+        raise RuntimeError(f"{op}: A and B must have contiguous rows and columns (only the slot stride is free), not strides "
+                           f"{tuple(A.stride())} and {tuple(B.stride())}")
+    return T, N, K, R, S, P
+
+
+def _lora_add_impl(y, xq, s1, A, B, scale, slot, part_cols):
+    _same_gpu("lora_add", (y, xq, s1, A, B, scale, slot))
+    T, N, K, R, S, P = _lora_add_check(y, xq, s1, A, B, scale, slot, part_cols)
+    if T == 0:
+        return
+    _in_place_check("lora_add", (("xq", xq), ("s1", s1), ("scale", scale), ("slot", slot)))
+    cols = (ctypes.c_int * (P + 1))(*part_cols)
+    err = _lib.lib().qqq_lora_add(_ptr(y), y.stride(0), _ptr(xq), _ptr(s1), _ptr(A), max(A.stride(0), P * R * K), _ptr(B),
+                                  max(B.stride(0), N * R), _ptr(scale), _ptr(slot), cols, P, T, N, K, R, S, y.device.index or 0,
+                                  _stream_for(y))
+    _raise_lib("lora_add", err)
+
+
+@torch.library.custom_op("qqq_amd::lora_add", mutates_args=("y",))
+def _lora_add_op(y: torch.Tensor, xq: torch.Tensor, s1: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scale: torch.Tensor,
+                 slot: torch.Tensor, part_cols: Sequence[int]) -> None:
+    _lora_add_impl(y, xq, s1, A, B, scale, slot, part_cols)
+
+
+@_lora_add_op.register_fake
+def _(y, xq, s1, A, B, scale, slot, part_cols):
+    _lora_add_check(y, xq, s1, A, B, scale, slot, part_cols)
+
+
+def lora_add(y: torch.Tensor, xq: torch.Tensor, s1: torch.Tensor, A: torch.Tensor, B: torch.Tensor, scale: torch.Tensor, slot: torch.Tensor,
+             part_cols=None) -> torch.Tensor:
+    """Batched LoRA beside the W4A8 GEMM, in place and in one launch -> `y`: every row adds its own adapter's low-rank product.
+
+    y            fp16 [T, N]: the GEMM's output, bias included; unit column stride, an even row stride >= N, never copied
+    xq, s1       int8 [T, K] and f32 [T] or [T, 1]: the quantised activation the GEMM consumed (dynamic_quant, rmsnorm_quant, ...)
+    A, B, scale  fp16 [S, P * R, K], fp16 [S, N, R], f32 [S]: S adapter slots of rank R in {8, 16, 32, 64}; A and B may be views with
+                 their own slot stride (rows and columns contiguous)
+    slot         int32 [T] on the device: the row's slot; -1 -- or anything outside [0, S) -- leaves the row's bits alone
+    part_cols    P + 1 column offsets (ints; a list, tuple or CPU tensor), ascending from 0 to N in multiples of 64: column n of part p
+                 uses the rows p * R ... (p + 1) * R - 1 of A (q|k|v, gate|up).  None: one part, [0, N].
+    For slot[t] = a >= 0:  y[t, n] <- fp16(float(y[t, n]) + scale[a] * sum_r B[a, n, r] * (s1[t] * sum_k A[a, p * R + r, k] * xq[t, k])),
+    every product and sum in f32, one rounding.  A row's bits depend on that row and its slot's matrices alone, and a call with P parts
+    gives the bits of P calls on the column slices.  The exact semantics are stated in include/ext/adapters/lora/qqq_amd_lora.h.  Nothing
+    is read on the host and the launch size depends on the shapes alone, so a step with this call in it replays from a captured graph."""
+    ts = (y, xq, s1, A, B, scale, slot)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        raise RuntimeError("lora_add: y, xq, s1, A, B, scale and slot must be tensors")
+    if part_cols is None:
+        part_cols = (0, y.shape[-1])
+    elif isinstance(part_cols, torch.Tensor):
+        part_cols = part_cols.tolist()
+    part_cols = tuple(int(c) for c in part_cols)
+    if _compiling(*ts):
+        _lora_add_op(*ts, part_cols)
+    else:
+        _lora_add_impl(*ts, part_cols)
+    return y

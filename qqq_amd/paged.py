@@ -34,7 +34,9 @@ class PagedStep:
     Families (None unless the step is a decode step in which at least two adjacent sequences were forked from one prompt): family int32
     [b] (the index within the step of the first row of row i's family; a lone row names itself), shared int64 [b] (the leading keys a row
     has in common with its family -- a multiple of the block size, the family's minimum, the same on all its rows; 0 for a lone row) and
-    family_max (host: the largest family of the step)."""
+    family_max (host: the largest family of the step).
+    lora (None: no adapters, and then nothing of it runs): a LoraStep (qqq_amd/lora.py) -- the bank and token_slot int32 [m] on the device,
+    the adapter slot of every token of the step, -1 for none."""
     seq_ids: List
     counts: List[int]
     starts: List[int]
@@ -49,6 +51,7 @@ class PagedStep:
     family: Optional[torch.Tensor] = None
     shared: Optional[torch.Tensor] = None
     family_max: Optional[int] = None
+    lora: Optional[object] = None
 
 
 class _Family:

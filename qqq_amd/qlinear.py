@@ -162,10 +162,11 @@ class QuantLinear(nn.Module):
                                     self.bias, max_par=self.max_par, W8=self.W8)
         return D if out_shape is None else D.reshape(out_shape)
 
-    def forward_int8(self, xq: torch.Tensor, s1: torch.Tensor) -> torch.Tensor:
+    def forward_int8(self, xq: torch.Tensor, s1: torch.Tensor, lora=None) -> torch.Tensor:
         """forward() on an input that is already quantised per token -- (int8 [..., infeatures], f32 [..., 1]) as dynamic_quant,
         rmsnorm_quant or silu_mul_quant return them: the same GEMM, bias and W8 handling, so forward_int8(*dynamic_quant(x)) is
-        bit-identical to forward(x).  Output fp16 [..., outfeatures]."""
+        bit-identical to forward(x).  Output fp16 [..., outfeatures].  `lora`: None, or (A, B, scale, slot, part_cols) -- the adapters
+        ops.lora_add then adds to the output, per token by `slot`, from the same (xq, s1)."""
         if xq.dtype != torch.int8 or xq.shape[-1] != self.infeatures:
             raise RuntimeError(f"forward_int8: xq must be int8 [..., {self.infeatures}]")
         out_shape = xq.shape[:-1] + (self.outfeatures,)
@@ -174,8 +175,11 @@ class QuantLinear(nn.Module):
             raise RuntimeError(f"forward_int8: s1 must hold one scale per token ({A.shape[0]}), got {tuple(s1.shape)}")
         D = torch.empty((A.shape[0], self.outfeatures), dtype=torch.float16, device=xq.device)
         if A.shape[0]:
-            ops.qqq_gemm_w8(A, self.B, self.reduce_buffer, D, s1.reshape(-1, 1).contiguous(), self.s_channel, self.s_group, self.workspace,
+            s1 = s1.reshape(-1, 1).contiguous()
+            ops.qqq_gemm_w8(A, self.B, self.reduce_buffer, D, s1, self.s_channel, self.s_group, self.workspace,
                             bias=self.bias, W8=self.W8, max_par=self.max_par)
+            if lora is not None:
+                ops.lora_add(D, A, s1, *lora)
         return D.reshape(out_shape)
 
 

@@ -76,6 +76,26 @@ def stop_match(completion: Sequence[int], stops: Sequence[Sequence[int]]) -> int
     return 0
 
 
+def adapter_slots(name: str, lora, adapters, prompts: int) -> List[int]:
+    """generate()'s `adapters` -- one slot of the bank `lora` or None per prompt; None: no prompt has one -- checked -> the slot per prompt,
+    -1 for none.  `name` heads the messages."""
+    if adapters is None:
+        return [-1] * prompts
+    if isinstance(adapters, (str, bytes)) or not hasattr(adapters, "__len__") or len(adapters) != prompts:
+        raise ValueError(f"{name}: adapters must hold one entry per prompt ({prompts}): a slot of the bank, or None")
+    slots = []
+    for a in adapters:
+        if a is not None:
+            try:
+                a = -1 if isinstance(a, bool) else _index(a)
+            except TypeError:
+                a = -1
+            if not 0 <= a < lora.slots:
+                raise ValueError(f"{name}: adapters holds an entry that is neither None nor a slot in [0, {lora.slots})")
+        slots.append(-1 if a is None else a)
+    return slots
+
+
 class Records:
     """The logprobs=k records of one call: per pass the four device results of ops.topk_logprobs (k = 0 has no top-k parts), per completion
     its rows of them, in order, and `tail`: the four CPU parts a loop read back for its decode steps, which follow its first token's."""
@@ -110,10 +130,12 @@ class Request:
     """The keywords of one generate() call, checked (`name` heads the messages: "generate", "DecodeLoop.generate", ...): temperature, top_k,
     top_p and generator as given; eos (-1: none); penalty (repetition, presence, frequency) and penalised; stops, end_ids and least
     (stop_arguments), stopping (one of the three is set) and ends, the tokens that end a completion and stay in it; n completions per
-    prompt; k logprobs per record (None: no records).  begin() adds the call's prompts, its completions `outs` and their `records`."""
+    prompt; k logprobs per record (None: no records); lora, the LoraBank of the call (None: no adapters, and then nothing of it runs) with
+    `adapters`, one slot or None per prompt.  begin() adds the call's prompts, its completions `outs`, their `records` and `slots`, the
+    prompts' adapter slots (-1: none)."""
 
     def __init__(self, name: str, vocab: int, temperature, top_k, top_p, generator, eos_token_id, repetition_penalty, presence_penalty,
-                 frequency_penalty, stop, stop_token_ids, min_new_tokens, n, logprobs):
+                 frequency_penalty, stop, stop_token_ids, min_new_tokens, n, logprobs, lora=None, adapters=None):
         self.name, self.temperature, self.top_k, self.top_p, self.generator = name, temperature, top_k, top_p, generator
         self.n, self.k = n, logprobs  # checked where they are given: generate()'s keywords, a loop's family and logprobs
         self.penalty = (float(repetition_penalty), float(presence_penalty), float(frequency_penalty))
@@ -124,6 +146,14 @@ class Request:
         self.stopping = bool(self.stops or self.end_ids or self.least)
         self.eos = -1 if eos_token_id is None else int(eos_token_id)
         self.ends = set(self.end_ids) | ({self.eos} if self.eos >= 0 else set())
+        self.lora, self.adapters = lora, adapters
+        if lora is not None:
+            from .lora import LoraBank
+
+            if not isinstance(lora, LoraBank):
+                raise ValueError(f"{name}: lora must be a LoraBank")
+        elif adapters is not None:
+            raise ValueError(f"{name}: adapters need lora, the LoraBank that holds them")
 
     def begin(self, prompts):
         """-> (the prompts as lists, the completions: n empty lists per prompt)"""
@@ -132,7 +162,17 @@ class Request:
             raise ValueError(f"{self.name}: every prompt needs at least one token")
         self.outs: List[List[int]] = [[] for _ in range(len(self.prompts) * self.n)]
         self.records = Records(self.k, len(self.outs)) if self.k is not None else None
+        self.slots = adapter_slots(self.name, self.lora, self.adapters, len(self.prompts))
         return self.prompts, self.outs
+
+    def with_adapters(self, step, prompt_ids: Sequence[int], counts: Sequence[int]):
+        """`step` (a PagedStep whose sequence j feeds counts[j] tokens of prompt prompt_ids[j]) with the tokens' adapter slots in
+        step.lora -> step; untouched without a bank, and when no token of the step has an adapter"""
+        if self.lora is not None:
+            slots = [self.slots[i] for i, c in zip(prompt_ids, counts) for _ in range(c)]
+            if any(s >= 0 for s in slots):
+                step.lora = self.lora.step(self.lora.token_slots(slots))
+        return step
 
     def family_blocks(self, prompt_len: int, keys: int, block_size: int) -> int:
         """the blocks a prompt's n completions of at most `keys` keys take: one budget plus, per further sibling, the blocks beyond the shared ones"""
@@ -152,6 +192,9 @@ class Request:
         if self.stopping:
             build["stops"] = True
             call.update(stop=self.stops, stop_token_ids=self.end_ids, min_new_tokens=self.least)
+        if self.lora is not None:
+            build["lora"] = self.lora
+            call["adapters"] = self.adapters
         return build, call
 
     def sample(self, logits: torch.Tensor, seqs: Sequence[int], workspace: Optional[torch.Tensor]) -> torch.Tensor:
@@ -225,8 +268,8 @@ class GuidedRequest(Request):
     those states (ops.fsm_mask, behind the penalties and the ban), receive() steps them by the rules of include/ext/guided/
     qqq_amd_guided.h and ends a completion that reaches a terminal state; a loop writes the states its rows ended in back into `state`."""
 
-    def __init__(self, fsm, *args):
-        super().__init__(*args)
+    def __init__(self, fsm, *args, **kw):
+        super().__init__(*args, **kw)
         self._given = fsm
 
     def begin(self, prompts):
@@ -258,4 +301,4 @@ class GuidedRequest(Request):
                                f"allows had a logit of -inf or NaN")
 
 
-__all__ = ["GuidedRequest", "merge_automata", "Request", "Records", "TokenLogprobs", "stop_arguments", "stop_match"]
+__all__ = ["adapter_slots", "GuidedRequest", "merge_automata", "Request", "Records", "TokenLogprobs", "stop_arguments", "stop_match"]

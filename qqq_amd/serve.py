@@ -76,6 +76,10 @@ class DecodeLoop:
                 token ids ban_ids (int32 [32], -1 = unused) -- and its step runs the ban between the penalties and the sampler and the
                 check behind the sampler (and the records), inside the captured graph; generate() then takes stop, stop_token_ids and
                 min_new_tokens.  The tables have fixed shapes, so one capture serves every call.  False: none of that exists.
+    lora        a LoraBank (qqq_amd/lora.py; None: off): the loop owns `lora_slot` (int32 [rows]: a row's adapter slot, written on admission,
+                -1 for none and when idle) inside its PagedStep, as part of the captured graph: every targeted projection of the step is
+                followed by ops.lora_add, which reads the slots on the device; generate() then takes adapters, one slot or None per prompt.
+                One capture serves every mix of adapters, and the bank's load() / unload() between calls.  None: none of that exists.
     `captures` counts the captures: 1 for the life of the loop with graph=True.  The graph holds addresses: a model that is changed after
     the first generate() (fuse_*(), load_state_dict, .to()) needs a new loop."""
 
@@ -88,9 +92,10 @@ class DecodeLoop:
     penalties = False                # True: the step runs ops.penalize_logits in front of the sampler (_allocate_penalties)
     logprobs = None                  # k: the step runs ops.topk_logprobs_step behind the sampler (DecodeLoop alone takes it)
     stops = False                    # True: the step runs ops.ban_tokens in front of the sampler and ops.stop_check behind it (_allocate_stops)
+    lora = None                      # a LoraBank: the step's projections are followed by ops.lora_add over `lora_slot` (_allocate_lora)
 
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, sync_every: int = 8, u_stride: int = 64, graph: bool = True,
-                 penalties: bool = False, family: int = 1, logprobs: Optional[int] = None, stops: bool = False):
+                 penalties: bool = False, family: int = 1, logprobs: Optional[int] = None, lora=None, stops: bool = False):
         rows, max_len, sync_every, u_stride, family = int(rows), int(max_len), int(sync_every), int(u_stride), int(family)
         short = u_stride < sync_every and f"u_stride={u_stride} must cover the sync_every={sync_every} steps between two refills"
         dev = _check_loop("DecodeLoop", lm, cache, rows, max_len, sync_every, graph, short)
@@ -121,6 +126,17 @@ class DecodeLoop:
             self.family_of = (torch.arange(rows, dtype=torch.int32, device=dev) // family) * family
             self.shared = torch.zeros(rows, dtype=torch.int64, device=dev)
             self.step.family, self.step.shared, self.step.family_max = self.family_of, self.shared, family
+        if lora is not None:
+            self._allocate_lora(lora)
+
+    def _allocate_lora(self, bank) -> None:
+        """What a loop built with lora=bank owns: `lora_slot`, one adapter slot per token of the step (a row's slot repeated over its
+        chunk), every row idle (-1), held by the step the graph captures."""
+        if bank.device != self.device:
+            raise RuntimeError(f"{self._name}: the bank and the model must be on the same device")
+        self.lora = bank
+        self.lora_slot = torch.full((self.rows,) if self.group == 1 else (self.rows, self.group), -1, dtype=torch.int32, device=self.device)
+        self.step.lora = bank.step(self.lora_slot.view(-1))
 
     def _allocate(self, lm, cache, rows, max_len, sync_every, u_stride, graph, dev):
         """The attributes and state arrays every loop has, for rows of `self.group` tokens: [rows] at 1, [rows, group] beyond."""
@@ -265,13 +281,16 @@ class DecodeLoop:
         self.cache.advance(seq, n["n_out"])  # the keys the device wrote: one per decode step the row took
         return row[:n["n_out"]]
 
-    def _request(self, *args) -> Request:
+    def _request(self, *args, **kw) -> Request:
         """The request object of one generate() call, from Request's own arguments: a subclass builds its own kind."""
-        return Request(*args)
+        return Request(*args, **kw)
 
     def _admit_state(self, req: Request, q: int) -> dict:
-        """What an admitted row writes besides _row_state, from the request's knowledge of its completion q: nothing here."""
-        return {}
+        """What an admitted row writes besides _row_state, from the request's knowledge of its completion q: its prompt's adapter slot."""
+        if self.lora is None:
+            return {}
+        slot = req.slots[q // self.family]
+        return dict(lora_slot=slot if self.group == 1 else [slot] * self.group)
 
     def _settle(self, req: Request, q: int, n: dict) -> None:
         """A finished row's synced values `n` that the request keeps for its completion q: none here."""
@@ -283,7 +302,8 @@ class DecodeLoop:
 
     @torch.no_grad()
     def generate(self, prompts: Sequence[Sequence[int]], max_new_tokens: int, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0,
-                 generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None, repetition_penalty: float = 1.0,
+                 generator: Optional[torch.Generator] = None, eos_token_id: Optional[int] = None,
+                 adapters: Optional[Sequence[Optional[int]]] = None, repetition_penalty: float = 1.0,
                  presence_penalty: float = 0.0, frequency_penalty: float = 0.0, stop: Optional[Sequence[Sequence[int]]] = None,
                  stop_token_ids: Optional[Sequence[int]] = None, min_new_tokens: int = 0) -> List[List[int]]:
         """QuantLlamaForCausalLM.generate's contract -- up to `max_new_tokens` ids per prompt, the eos that ends a sequence included --
@@ -322,10 +342,17 @@ class DecodeLoop:
         counts: the tokens -- and records -- a finished row drops from its end.  admit() does the same for the first token by the host
         path's own routines: Request.sample bans on the prefill's logits, and Request.receive ends a completion on its first token (a
         length-1 stop sequence that matches it leaves an empty completion whose row never starts).  The keys the device wrote are still
-        counted by n_out."""
+        counted by n_out.
+
+        adapters (None: no prompt has one) needs a loop built with lora=bank: one slot of the bank or None per prompt.  The admission
+        prefill carries the prompts' slots per token, an admitted row writes its slot into lora_slot and a finished one -1; the
+        siblings of a family inherit their prompt's."""
         name = f"{self._name}.generate"
+        if adapters is not None and self.lora is None:
+            raise ValueError(f"{name}: adapters need a loop built with lora=bank")
         req = self._request(name, self.lm.lm_head.weight.shape[0], temperature, top_k, top_p, generator, eos_token_id, repetition_penalty,
-                      presence_penalty, frequency_penalty, stop, stop_token_ids, min_new_tokens, self.family, self.logprobs)
+                            presence_penalty, frequency_penalty, stop, stop_token_ids, min_new_tokens, self.family, self.logprobs,
+                            lora=self.lora, adapters=adapters)
         if req.stopping and not self.stops:
             raise ValueError(f"{name}: stop, stop_token_ids and min_new_tokens={req.least} need a loop built with stops=True")
         if req.penalised and not self.penalties:
@@ -383,7 +410,8 @@ class DecodeLoop:
                 return
             # the packed prefill of the admitted prompts (eager, the existing step) and their first tokens
             ids = torch.tensor([t for _, i in new for t in prompts[i]], dtype=torch.int64, device=dev)
-            logits = self.lm(ids, cache, cache.step([sid(i * fam) for _, i in new], [len(prompts[i]) for _, i in new]))
+            step = cache.step([sid(i * fam) for _, i in new], [len(prompts[i]) for _, i in new])
+            logits = self.lm(ids, cache, req.with_adapters(step, [i for _, i in new], step.counts))
             born = [(r + j, i * fam + j) for r, i in new for j in range(fam)]  # (row, sequence) of every sibling
             first = req.sample(logits, [q for _, q in born], self.penalty_workspace if self.penalties else None)
             rows, state, ended = [], {}, []
@@ -446,12 +474,14 @@ class DecodeLoop:
                         owner[r] = None
                     if fam > 1:
                         self.shared[at_done] = 0
+                    if self.lora is not None:
+                        self.lora_slot[at_done] = -1
         except BaseException:
             # leave the loop idle and the caller's pool as it was found
             for i in owner:
                 if i is not None:
                     cache.free(sid(i))
-            for array, value in self._idle + ((("shared", 0),) if fam > 1 else ()):
+            for array, value in self._idle + ((("shared", 0),) if fam > 1 else ()) + ((("lora_slot", -1),) if self.lora is not None else ()):
                 getattr(self, array).fill_(value)
             if req.records is not None:
                 self.n_rec.copy_(self.n_out)  # no row owes a record
@@ -507,8 +537,8 @@ class GuidedDecodeLoop(DecodeLoop):
         ops.fsm_advance(self.out, self.n_out, self.n_fsm, self.fsm_state, self._tables, self.ids, self.pos, self.slots, self.remaining,
                         eos=self.eos)
 
-    def _request(self, *args) -> Request:
-        self._guided = GuidedRequest(self._given, *args)
+    def _request(self, *args, **kw) -> Request:
+        self._guided = GuidedRequest(self._given, *args, **kw)
         return self._guided
 
     def _start_call(self) -> None:
@@ -595,6 +625,7 @@ class SpecDecodeLoop(DecodeLoop):
     sequence needs
     len(prompt) + max_new_tokens - 1 + draft_len keys of the pool and of max_len: the drafts behind its last token are written too.
     ngram_max   the longest n-gram the drafter looks up (1 ... 4);  u_stride  default sync_every * G, a multiple of G
+    lora        as in DecodeLoop, with lora_slot [rows, draft_len + 1]: the row's slot repeated over its chunk
     penalties   as in DecodeLoop, with `seen` being `hist` itself: logits row j of a row is penalised over its history and the drafts
                 1 ... j in front of it, so an emitted token is still a plain sampler draw from (penalised) logits of the true prefix
     After a generate(): `accepted` drafts were accepted in `row_steps` steps of single rows, over `steps` steps of the loop; a row-step
@@ -606,7 +637,8 @@ class SpecDecodeLoop(DecodeLoop):
     _idle = DecodeLoop._idle + (("start", -1),)
 
     def __init__(self, lm, cache: PagedKVCache, rows: int, max_len: int, draft_len: int = 4, ngram_max: int = 3, sync_every: int = 8,
-                 u_stride: Optional[int] = None, graph: bool = True, penalties: bool = False, family: int = 1, stops: bool = False):
+                 u_stride: Optional[int] = None, graph: bool = True, penalties: bool = False, family: int = 1, lora=None,
+                 stops: bool = False):
         rows, max_len, sync_every, draft_len, ngram_max = int(rows), int(max_len), int(sync_every), int(draft_len), int(ngram_max)
         if int(family) != 1:
             raise ValueError(f"SpecDecodeLoop: family={family} is not supported (a chunk of draft_len + 1 tokens per row has no "
@@ -644,6 +676,8 @@ class SpecDecodeLoop(DecodeLoop):
         self.step = PagedStep(seq_ids=[None] * rows, counts=[group] * rows, starts=[0] * rows, max_len=max_len, decode=False,
                               pos=self.pos.view(-1), slots=self.slots.view(-1), block_table=self.block_table, last_pos=self.start,
                               cu_tokens=torch.arange(rows + 1, **i32) * group, start_pos=self.start)
+        if lora is not None:  # lora_slot [rows, draft_len + 1]: the row's slot on every token of its chunk
+            self._allocate_lora(lora)
 
     def _decode_step(self) -> None:
         logits = self.lm(self.ids.view(-1), self.cache, self.step, all_rows=True)

@@ -68,6 +68,14 @@ at temperature 0.8 so that the siblings diverge.  Written to profiles/parallel_s
 
     python tools/bench_generate.py --n 1,4,8 [--prompt 2048] [--rounds 5] [--out profiles/parallel_sampling_bench.json]
 
+With --lora the tool times the replayed step of a loop built without a LoraBank (`off`), of a loop with one (ops.lora_add behind every
+projection: rank 16, every row on slot 0 -- `one` -- and row r on slot r -- `distinct`) and of the same loop with the op replaced by the
+torch composition of tools/bench_lora.py (`torch_one`, `torch_distinct`), in one rotation, at K = 0 and 4 (--draft-len), and writes
+profiles/lora_loop_bench.json: the step times with the rounds' min and max, what each adds to `off`, the largest spread of the rounds, and
+whether the op's addition is below the composition's by more than that spread.
+
+    python tools/bench_generate.py --lora [--batch 1,16] [--draft-len 0,4] [--rounds 5] [--out profiles/lora_loop_bench.json]
+
 With --guided the tool times the replayed step with and without ops.fsm_mask and ops.fsm_advance in it, in one rotation: per batch a plain
 DecodeLoop beside a GuidedDecodeLoop serving generate_guided() with one automaton per prompt that allows exactly the plain loop's own
 completion (TokenFSM.from_choices of that one sequence: one allowed token per state, so the mask writes the whole row, its dearest case),
@@ -547,6 +555,116 @@ def guided_main(args):
               f"{p['plain_round_spread_us']} / {p['guided_round_spread_us']})")
 
 
+def torch_lora_in_step(y, xq, s1, A, B, scale, slot, part_cols=None):
+    """what ops.lora_add does, from torch calls that are safe inside a captured step: index_select of A and B by the rows' slots (an idle
+    row's -1 reads slot 0 and is scaled by 0), two bmm in f32, scale, and the add into y"""
+    import torch
+
+    cols = part_cols if part_cols is not None else (0, y.shape[1])
+    idx = slot.clamp_min(0).long()
+    R = B.shape[2]
+    h = torch.bmm(A.index_select(0, idx).float(), (xq.float() * s1.reshape(-1, 1)).unsqueeze(2))
+    sc = (scale.index_select(0, idx) * (slot >= 0))[:, None]
+    Bt = B.index_select(0, idx).float()
+    for p in range(len(cols) - 1):
+        part = y[:, cols[p]:cols[p + 1]]
+        part.copy_(part.float() + sc * torch.bmm(Bt[:, cols[p]:cols[p + 1]], h[:, p * R:(p + 1) * R]).squeeze(2))
+    return y
+
+
+def lora_point(lm, bank, batch, drafts, rounds, dev):
+    import torch
+
+    from bench_model import VOCAB
+    from qqq_amd import DecodeLoop, SpecDecodeLoop, ops
+
+    g = torch.Generator().manual_seed(batch)
+    prompts = [torch.randint(0, VOCAB, (PROMPT,), generator=g).tolist() for _ in range(batch)]
+    adapters = {"off": None, "one": [0] * batch, "distinct": list(range(batch)), "torch_one": [0] * batch, "torch_distinct": list(range(batch))}
+    loops = {}  # key: (K, "off" | "fused" | "torch"); the fused and the torch loop serve "one" and "distinct" each
+    for k in drafts:
+        max_len = -(-(PROMPT + NEW - 1 + k) // BS) * BS
+        for name in ("off", "fused", "torch"):
+            kw = dict(rows=batch, max_len=max_len, sync_every=SYNC_EVERY, **({} if name == "off" else dict(lora=bank)))
+            cache = lm.new_cache(batch * (max_len // BS), BS)
+            loops[(k, name)] = SpecDecodeLoop(lm, cache, draft_len=k, **kw) if k else DecodeLoop(lm, cache, **kw)
+    loop_of = {"off": "off", "one": "fused", "distinct": "fused", "torch_one": "torch", "torch_distinct": "torch"}
+    fused_op = ops.lora_add
+
+    def timed(k, variant, n):
+        ops.lora_add = torch_lora_in_step if loop_of[variant] == "torch" else fused_op  # the torch loop's capture and prefill take the composition
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            kw = {} if variant == "off" else dict(adapters=adapters[variant])
+            out = loops[(k, loop_of[variant])].generate(prompts, n, **kw)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, out
+        finally:
+            ops.lora_add = fused_op
+
+    steps = {}
+    for k in drafts:
+        for variant in adapters:  # warm-up: code objects, workspaces, rope tables, the capture
+            timed(k, variant, 1)
+            assert all(len(o) == NEW for o in timed(k, variant, NEW)[1]), (k, variant)
+            steps[(k, variant)] = loops[(k, loop_of[variant])].steps if k else NEW - 1
+    values = {key: [] for key in steps}
+    for _ in range(rounds):
+        for k, variant in steps:
+            short, full = timed(k, variant, 1)[0], timed(k, variant, NEW)[0]
+            values[(k, variant)].append((full - short) / steps[(k, variant)] * 1e6)
+    res = {"batch": batch, "prompt_tokens": PROMPT, "new_tokens": NEW, "layers": LAYERS, "draft_len": {}}
+    for k in drafts:
+        e = {}
+        for variant in adapters:
+            v = values[(k, variant)]
+            e[variant] = {"steps": steps[(k, variant)], "step_us": round(statistics.median(v), 1), "step_us_min": round(min(v), 1),
+                          "step_us_max": round(max(v), 1), "rounds_step_us": [round(x, 1) for x in v]}
+        spread = max(e[v]["step_us_max"] - e[v]["step_us_min"] for v in e)
+        e["largest_round_spread_us"] = round(spread, 1)
+        for variant in ("one", "distinct"):
+            added, torch_added = e[variant]["step_us"] - e["off"]["step_us"], e["torch_" + variant]["step_us"] - e["off"]["step_us"]
+            e[variant + "_added_us"], e["torch_" + variant + "_added_us"] = round(added, 1), round(torch_added, 1)
+            e[variant + "_below_torch_by_more_than_the_spread"] = bool(torch_added - added > spread)
+        res["draft_len"][str(k)] = e
+    return res
+
+
+def lora_main(args):
+    import torch
+
+    from bench_model import build
+    from qqq_amd import LoraBank
+
+    drafts = sorted({int(k) for k in (args.draft_len or "0,4").split(",")})
+    batches = [int(b) for b in args.batch.split(",")]
+    dev = torch.device("cuda:0")
+    lm = build(LAYERS, dev).fuse_prefill()
+    bank = LoraBank(lm, slots=max(batches), rank=16)
+    g = torch.Generator(device=dev).manual_seed(1)
+    for t in bank._storage:  # every slot a random adapter of the bank's rank
+        t.normal_(0, 0.02, generator=g)
+    bank.scale.fill_(2.0)
+    with torch.no_grad():
+        points = [lora_point(lm, bank, b, drafts, args.rounds, dev) for b in batches]
+    out = {"tool": "tools/bench_generate.py --lora", "device": torch.cuda.get_device_name(0),
+           "shape": "Llama-2-7B layers, per-channel W4A8, fuse_qkv(), fuse_prefill(), paged fp16 cache, block 16, greedy, ngram_max 3",
+           "lora": "rank 16 on all seven projections: five ops.lora_add per layer (q|k|v fused, o, gate, up, down); `one`: every row on slot 0, "
+                   "`distinct`: row r on slot r; torch_*: the same loop with the op replaced by index_select, two f32 bmm, scale and add; "
+                   "`off`: a loop built without a bank", "bank_bytes": bank.nbytes, "sync_every": SYNC_EVERY, "rounds": args.rounds, "points": points}
+    path = args.out or os.path.join(ROOT, "profiles", "lora_loop_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        for k, e in p["draft_len"].items():
+            print(f"batch {p['batch']:3d} K={k}: off {e['off']['step_us']:.1f}  one {e['one']['step_us']:.1f} (+{e['one_added_us']})  distinct "
+                  f"{e['distinct']['step_us']:.1f} (+{e['distinct_added_us']})  torch one +{e['torch_one_added_us']} distinct "
+                  f"+{e['torch_distinct_added_us']}  largest spread {e['largest_round_spread_us']} us/step")
+
+
 def parallel_point(lm, n, prompt_len, rounds, dev):
     import torch
 
@@ -659,6 +777,8 @@ def main():
                     "the plain loop at sync_every=1 (profiles/stop_loop_bench.json)")
     ap.add_argument("--guided", action="store_true", help="time the replayed step with and without ops.fsm_mask and ops.fsm_advance "
                     "(profiles/guided_loop_bench.json)")
+    ap.add_argument("--lora", action="store_true", help="time the replayed step without a LoraBank, with ops.lora_add and with a torch "
+                    "composition in its place (profiles/lora_loop_bench.json); --draft-len picks the K, default 0,4")
     ap.add_argument("--out", default=None, help="default profiles/decode_loop_bench.json, or profiles/spec_decode_bench.json with --draft-len")
     args = ap.parse_args()
     import torch
@@ -673,6 +793,8 @@ def main():
         return logprobs_main(args)
     if args.stops:
         return stops_main(args)
+    if args.lora:
+        return lora_main(args)
     if args.guided:
         return guided_main(args)
     if args.draft_len:
