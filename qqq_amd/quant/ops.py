@@ -1,0 +1,76 @@
+"""Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h states the exact semantics).
+Both ops enqueue one launch on the current stream of their tensors' device and read nothing on the host."""
+from __future__ import annotations
+
+import torch
+
+from ..ops import _dt, _ptr, _same_gpu, _stream_for
+from . import _lib
+
+
+def _raise_lib(name, err):
+    if err:
+        raise RuntimeError(f"qqq_amd.quant: {name} error {err}: {_lib.last_error()}")
+
+
+def _matrix(name, what, t, cols=None):
+    # an f32 matrix with unit column stride and a row stride that holds its columns; a view is fine, nothing is copied
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+        got = f"{_dt(t.dtype)} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{name}: {what} must be a float32 matrix, got {got}")
+    if t.shape[0] < 1 or t.shape[1] < 1 or (cols is not None and t.shape[1] != cols):
+        raise RuntimeError(f"{name}: {what} has the shape {tuple(t.shape)}" + (f", {cols} columns expected" if cols is not None else ""))
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or t.stride(0) >= 2**31:
+        raise RuntimeError(f"{name}: {what} must have unit column stride and a row stride >= its columns, got strides {tuple(t.stride())}")
+    if t.data_ptr() % 4:
+        raise RuntimeError(f"{name}: {what} must be 4-byte aligned")
+    return max(t.stride(0), t.shape[1])
+
+
+def _row_vector(name, what, t, rows):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != rows or not t.is_contiguous():
+        got = f"{_dt(t.dtype)} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{name}: {what} must be contiguous float32 with one entry per row ({rows}), got {got}")
+
+
+def weight_scales(W: torch.Tensor, grouped: bool, mse: bool = False) -> torch.Tensor:
+    """The symmetric 4-bit scale of every row of `W` (f32 [rows, cols]; a column slice of a wider matrix is fine) -> f32 [rows, 1].
+    grouped=False: xmax / 7 (codes -7 ... 7); grouped=True: 2 xmax / 15 (codes 0 ... 15, zero 8); xmax = max |w|, 1 for an all-zero row.
+    mse=True: the reference's shrink search over 80 ranges, error |q - w| ^ 2.4, the earliest least."""
+    name = "weight_scales"
+    ldw = _matrix(name, "W", W)
+    _same_gpu(name, (W,))
+    rows, cols = W.shape
+    out = torch.empty((rows, 1), dtype=torch.float32, device=W.device)
+    err = _lib.lib().qqq_gptq_scales(_ptr(W), ldw, rows, cols, int(bool(grouped)), int(bool(mse)), _ptr(out), W.device.index or 0,
+                                     _stream_for(W))
+    _raise_lib(name, err)
+    return out
+
+
+def gptq_block(W1: torch.Tensor, Hinv1: torch.Tensor, scale: torch.Tensor, grouped: bool, out=None):
+    """The column sweep of one GPTQ block in one launch -> (Q1, Err1), both f32 [rows, count]: new, or the pair given as `out` (views
+    with their own row stride are fine: a caller may sweep into column slices of whole-matrix buffers).
+    W1 f32 [rows, count] (count 64 or 128), Hinv1 f32 [count, count]: the diagonal block of the upper Cholesky factor of the inverse
+    Hessian -- both may be views with their own row stride; scale f32 [rows] or [rows, 1].  Column by column: q = quantise(w, scale),
+    e = (w - q) / Hinv1[i, i], the columns to the right lose e * Hinv1[i, j] (product rounded, then subtracted).  W1 is left as it is."""
+    name = "gptq_block"
+    ldw = _matrix(name, "W1", W1)
+    rows, count = W1.shape
+    if count not in (64, 128):
+        raise RuntimeError(f"{name}: W1 must have 64 or 128 columns, got {count}")
+    ldh = _matrix(name, "Hinv1", Hinv1, count)
+    if Hinv1.shape[0] != count:
+        raise RuntimeError(f"{name}: Hinv1 must be [{count}, {count}], got {tuple(Hinv1.shape)}")
+    _row_vector(name, "scale", scale, rows)
+    if out is None:
+        out = (torch.empty((rows, count), dtype=torch.float32, device=W1.device), torch.empty((rows, count), dtype=torch.float32, device=W1.device))
+    Q1, Err1 = out
+    ldq, lde = _matrix(name, "Q1", Q1, count), _matrix(name, "Err1", Err1, count)
+    if Q1.shape[0] != rows or Err1.shape[0] != rows:
+        raise RuntimeError(f"{name}: Q1 and Err1 must have {rows} rows, got {Q1.shape[0]} and {Err1.shape[0]}")
+    _same_gpu(name, (W1, Hinv1, scale, Q1, Err1))
+    err = _lib.lib().qqq_gptq_block(_ptr(W1), ldw, _ptr(Hinv1), ldh, _ptr(scale), rows, count, int(bool(grouped)), _ptr(Q1), ldq,
+                                    _ptr(Err1), lde, W1.device.index or 0, _stream_for(W1))
+    _raise_lib(name, err)
+    return Q1, Err1

@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""A QQQ W4A8 checkpoint from an fp16 one, on the GPU: a thin wrapper over qqq_amd.quant.quantize_model (GPTQ layer by layer, the
+reference's examples/quant_model.py without its rotation and smoothing stages).
+
+    python tools/quantize_model.py --config config.json --weights model.pt --tokens calib.npy --out DIR [--group-size 128]
+                                   [--seqlen 2048] [--nsamples 128] [--mse] [--percdamp 0.01] [--seq-batch 1]
+
+--config   a transformers config.json of a Llama or Qwen2 model (read as plain JSON; transformers is not needed)
+--weights  the fp16 state dict with Hugging Face parameter names: a torch.save file, or .safetensors where the safetensors package can
+           be imported
+--tokens   a .npy of calibration token ids of any integer dtype and shape, read in order and cut into windows of --seqlen (there is no
+           tokenizer here: tokenise elsewhere)
+--out      a directory: model.pt (the packed state dict, the reference's names: tools/eval_ppl.py --weights takes it) and
+           quant_config.json ({"group_size", "wbits"}, as the reference writes it)
+Prints one JSON line: group_size, nsamples, seqlen, linears, seconds.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+from types import SimpleNamespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from eval_ppl import load_state_dict  # noqa: E402  (tools/eval_ppl.py: the same checkpoint formats)
+
+
+def main():
+    ap = argparse.ArgumentParser(description="GPTQ-quantise an fp16 Llama / Qwen2 state dict into a QQQ W4A8 checkpoint")
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--weights", required=True)
+    ap.add_argument("--tokens", required=True)
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--group-size", type=int, default=128, choices=(-1, 128))
+    ap.add_argument("--seqlen", type=int, default=2048)
+    ap.add_argument("--nsamples", type=int, default=128, help="at most this many windows of the token file")
+    ap.add_argument("--mse", action="store_true", help="the shrink search for the scales (the reference's pairing for rotated models)")
+    ap.add_argument("--percdamp", type=float, default=0.01)
+    ap.add_argument("--seq-batch", type=int, default=1)
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+
+    if not torch.cuda.is_available():
+        sys.exit("quantize_model.py needs a GPU: there is no CPU path")
+    from qqq_amd.quant import quantize_model
+
+    cfg = json.load(open(args.config))
+    tokens = np.load(args.tokens)
+    if not np.issubdtype(tokens.dtype, np.integer):
+        sys.exit(f"quantize_model.py: {args.tokens} holds {tokens.dtype}, not token ids")
+    tokens = np.asarray(tokens, dtype=np.int64).reshape(-1)
+    nsamples = min(args.nsamples, tokens.size // args.seqlen)
+    if nsamples < 1:
+        sys.exit(f"quantize_model.py: {tokens.size} tokens are fewer than one window of {args.seqlen}")
+    if tokens.min() < 0 or tokens.max() >= cfg["vocab_size"]:
+        sys.exit(f"quantize_model.py: token ids outside [0, {cfg['vocab_size']})")
+    ids = torch.from_numpy(tokens[:nsamples * args.seqlen].reshape(nsamples, args.seqlen))
+    results = {}
+    t0 = time.perf_counter()
+    lm = quantize_model(load_state_dict(args.weights), SimpleNamespace(**cfg), ids, args.group_size, mse=args.mse, percdamp=args.percdamp,
+                        seq_batch=args.seq_batch, results=results)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    os.makedirs(args.out, exist_ok=True)
+    torch.save({k: v.cpu() for k, v in lm.state_dict().items()}, os.path.join(args.out, "model.pt"))
+    with open(os.path.join(args.out, "quant_config.json"), "w") as f:
+        json.dump({"group_size": args.group_size, "wbits": 4}, f)
+    print(json.dumps({"group_size": args.group_size, "nsamples": nsamples, "seqlen": args.seqlen, "linears": len(results),
+                      "seconds": round(dt, 2)}))
+
+
+if __name__ == "__main__":
+    main()
