@@ -1,14 +1,18 @@
 // qqq_quant.hip -- the one translation unit of libqqq_amd_quant.so: the C-ABI entry points of the GPTQ quantiser
-// (qqq_amd/quant/include/qqq_amd_quant.h) over the kernels of qqq_gptq.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
+// (qqq_amd/quant/include/qqq_amd_quant.h) over the kernels of qqq_gptq.hip.h, and of the rotation op (qqq_amd/quant/include/qqq_amd_rotate.h)
+// over the kernel of qqq_hadamard.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
 // (qqq_amd/build.py, build_quant): the entry points promise bits.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 
 #include "../../../include/qqq_amd.h"  // the return codes
 #include "../include/qqq_amd_quant.h"
+#include "../include/qqq_amd_rotate.h"
 #include "qqq_gptq.hip.h"
+#include "qqq_hadamard.hip.h"
 
 static thread_local char g_err[512] = "";
 
@@ -112,5 +116,80 @@ extern "C" int qqq_gptq_block(const void* W1, int ldw, const void* Hinv1, int ld
     hipLaunchKernelGGL((qqq_gptq_block_kernel<128, false>), grid, dim3(GPTQ_NT), 0, st, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_gptq_block_kernel launch");
+  return QQQ_OK;
+}
+
+template <typename T, bool VEC>
+static void hadamard_launch(const qqq_hadamard_args& a, hipStream_t st) {
+  // the tile holds whole blocks: 2048 elements up to n = 2048, then the block itself
+  if (a.n <= 2048)
+    hipLaunchKernelGGL((qqq_hadamard_kernel<T, VEC, 11>), dim3(static_cast<unsigned>((a.units + 255) / 256)), dim3(256), 0, st, a);
+  else if (a.n == 4096)
+    hipLaunchKernelGGL((qqq_hadamard_kernel<T, VEC, 12>), dim3(static_cast<unsigned>((a.units + 511) / 512)), dim3(512), 0, st, a);
+  else
+    hipLaunchKernelGGL((qqq_hadamard_kernel<T, VEC, 13>), dim3(static_cast<unsigned>((a.units + 1023) / 1024)), dim3(1024), 0, st, a);
+}
+
+extern "C" int qqq_hadamard_rows(const void* X, int ldx, void* Y, int ldy, int rows, int cols, int n, const void* sign, int dtype, int dev,
+                                 void* stream) {
+  g_err[0] = 0;
+  if (dtype != 0 && dtype != 1) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows: dtype=%d is not 0 (fp16) or 1 (f32)", dtype);
+    return QQQ_ERR_ARG;
+  }
+  if (n < 2 || n > HAD_MAX_N || (n & (n - 1)) != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows: n=%d is not a power of two in 2 ... %d", n, HAD_MAX_N);
+    return QQQ_ERR_ARG;
+  }
+  if (rows < 1 || cols < n || cols % n != 0 || ldx < cols || ldy < cols) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows: bad shape rows=%d cols=%d ldx=%d ldy=%d (need rows >= 1, cols a positive multiple of n=%d, both strides >= cols)",
+             rows, cols, ldx, ldy, n);
+    return QQQ_ERR_ARG;
+  }
+  const uintptr_t es = dtype == 0 ? 2 : 4;
+  if (!X || !Y || misaligned(X, es) || misaligned(Y, es)) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows: bad argument (X and Y must be non-NULL and aligned to their element, %d bytes)", static_cast<int>(es));
+    return QQQ_ERR_ARG;
+  }
+  const uintptr_t x0 = reinterpret_cast<uintptr_t>(X), y0 = reinterpret_cast<uintptr_t>(Y);
+  const uintptr_t xspan = (static_cast<uintptr_t>(rows - 1) * ldx + cols) * es, yspan = (static_cast<uintptr_t>(rows - 1) * ldy + cols) * es;
+  if (x0 == y0 ? ldx != ldy : (x0 < y0 + yspan && y0 < x0 + xspan)) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows: X and Y overlap (only Y == X with ldy == ldx, in place, is allowed)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_hadamard_args a;
+  a.X = X;
+  a.Y = Y;
+  a.sign = static_cast<const signed char*>(sign);
+  a.ldx = ldx;
+  a.ldy = ldy;
+  a.run = n < HAD_RUN ? n : HAD_RUN;
+  a.units_per_row = cols / a.run;
+  a.units = static_cast<long long>(rows) * a.units_per_row;
+  a.n = n;
+  a.log2n = 0;
+  while ((1 << a.log2n) < n) ++a.log2n;
+  a.d = static_cast<double>(sqrtf(static_cast<float>(n)));
+  a.rd = 1.0 / a.d;
+  if ((a.units + 255) / 256 > 0x7fffffffLL) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows: rows=%d x cols=%d is more than one launch holds", rows, cols);
+    return QQQ_ERR_ARG;
+  }
+  // 16-byte loads and stores of a run (and one 8-byte load of its signs) where every run of both matrices is 16-byte aligned and the
+  // sign vector 8-byte; the bits do not depend on it
+  const uintptr_t per16 = 16 / es;
+  const bool vec = a.run == HAD_RUN && !misaligned(X, 16) && !misaligned(Y, 16) && ldx % per16 == 0 && ldy % per16 == 0 && !misaligned(sign, 8);
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dtype == 0 && vec)
+    hadamard_launch<_Float16, true>(a, st);
+  else if (dtype == 0)
+    hadamard_launch<_Float16, false>(a, st);
+  else if (vec)
+    hadamard_launch<float, true>(a, st);
+  else
+    hadamard_launch<float, false>(a, st);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_hadamard_kernel launch");
   return QQQ_OK;
 }

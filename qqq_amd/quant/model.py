@@ -4,6 +4,7 @@ accumulates the Hessians of its linears' inputs with its FLOAT weights (all seve
 once more with the quantised weights to feed the next layer."""
 from __future__ import annotations
 
+import copy
 from typing import Optional
 
 import torch
@@ -12,6 +13,7 @@ import torch.nn.functional as F
 from ..attention import _config_rope, rope_inv_freq, rope_tables
 from ..model import QuantLlamaForCausalLM
 from .gptq import Hessian, gptq_quantize
+from .rotation import rotate_model
 
 ATTN = ("q_proj", "k_proj", "v_proj", "o_proj")
 MLP = ("gate_proj", "up_proj", "down_proj")
@@ -88,11 +90,26 @@ def _run(layer, inps, seq_batch, taps=None):
 
 @torch.no_grad()
 def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size: int, mse: bool = False, percdamp: float = 0.01,
-                   seq_batch: int = 1, device=None, results: Optional[dict] = None) -> QuantLlamaForCausalLM:
+                   seq_batch: int = 1, device=None, results: Optional[dict] = None, rotation=None) -> QuantLlamaForCausalLM:
     """A packed QuantLlamaForCausalLM from an fp16 Hugging Face state dict, a (duck-typed) Llama or Qwen2 config and calibration token
     ids [samples, seqlen].  `seq_batch` sequences run through a layer at a time (1, the reference's, counts every sequence as one sample
-    of the Hessian).  `results`: a dict that receives the GPTQResult of every linear under its state-dict prefix."""
+    of the Hessian).  `results`: a dict that receives the GPTQResult of every linear under its state-dict prefix.
+    `rotation`: None, or what rotation.rotate_model is to do to the state dict first (the reference's --rotation; pair it with mse=True):
+    "hadamard", "random", an int8 [hidden] sign vector, or an f64 [hidden, hidden] Q.  The model is then built UNTIED (its lm_head
+    carries the final norm), its norms are ones, and results["rotation"] receives the signs or Q that were used."""
     dev = torch.device(device if device is not None else "cuda:0")
+    if rotation is not None:
+        if isinstance(rotation, str):
+            kw = dict(mode=rotation)
+        elif isinstance(rotation, torch.Tensor):
+            kw = dict(signs=rotation) if rotation.dtype == torch.int8 else dict(Q=rotation)
+        else:
+            raise RuntimeError(f"quantize_model: rotation must be None, 'hadamard', 'random' or a tensor (signs or Q), got {type(rotation).__name__}")
+        state_dict, used = rotate_model(state_dict, config, device=dev, **kw)
+        config = copy.copy(config)
+        config.tie_word_embeddings = False
+        if results is not None:
+            results["rotation"] = used
     lm = QuantLlamaForCausalLM.from_config(config, group_size).to(dev)
     embed = state_dict["model.embed_tokens.weight"].to(dev).half()
     ids = torch.as_tensor(calib_ids, dtype=torch.int64, device=dev)

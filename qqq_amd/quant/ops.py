@@ -1,5 +1,5 @@
-"""Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h states the exact semantics).
-Both ops enqueue one launch on the current stream of their tensors' device and read nothing on the host."""
+"""Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h and qqq_amd_rotate.h state the
+exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing on the host."""
 from __future__ import annotations
 
 import torch
@@ -74,3 +74,65 @@ def gptq_block(W1: torch.Tensor, Hinv1: torch.Tensor, scale: torch.Tensor, group
                                     _ptr(Err1), lde, W1.device.index or 0, _stream_for(W1))
     _raise_lib(name, err)
     return Q1, Err1
+
+
+_HAD_DTYPES = {torch.float16: 0, torch.float32: 1}
+
+
+def _had_matrix(name, what, t, shape=None, dtype=None):
+    # an fp16 or f32 matrix with unit column stride and a row stride that holds its columns; a view is fine, nothing is copied
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype not in _HAD_DTYPES or (dtype is not None and t.dtype != dtype):
+        got = f"{_dt(t.dtype)} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{name}: {what} must be a {'float16 or float32' if dtype is None else _dt(dtype)} matrix, got {got}")
+    if t.shape[0] < 1 or t.shape[1] < 1 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError(f"{name}: {what} has the shape {tuple(t.shape)}" + (f", {tuple(shape)} expected" if shape is not None else ""))
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or t.stride(0) >= 2**31:
+        raise RuntimeError(f"{name}: {what} must have unit column stride and a row stride >= its columns, got strides {tuple(t.stride())}")
+    if t.data_ptr() % t.element_size():
+        raise RuntimeError(f"{name}: {what} must be aligned to its element ({t.element_size()} bytes)")
+    return max(t.stride(0), t.shape[1])
+
+
+def _sign_vector(name, sign, n):
+    if not isinstance(sign, torch.Tensor) or sign.dtype != torch.int8 or sign.dim() != 1 or sign.numel() != n or not sign.is_contiguous():
+        got = f"{_dt(sign.dtype)} {tuple(sign.shape)}" if isinstance(sign, torch.Tensor) else type(sign).__name__
+        raise RuntimeError(f"{name}: sign must be contiguous int8 [{n}], got {got}")
+
+
+def check_signs(sign: torch.Tensor, n: int, name: str = "check_signs") -> torch.Tensor:
+    """`sign` as hadamard_rows takes it: contiguous int8 [n] with every entry +1 or -1.  The entries are READ ON THE HOST (one sync when
+    the tensor is on a GPU), so this is not part of hadamard_rows: a caller checks a sign vector once, then launches as often as it likes."""
+    _sign_vector(name, sign, n)
+    if not bool((sign.abs() == 1).all()):
+        raise RuntimeError(f"{name}: every entry of sign must be +1 or -1")
+    return sign
+
+
+def hadamard_rows(x: torch.Tensor, n: int, sign=None, out=None) -> torch.Tensor:
+    """The Walsh-Hadamard transform of every block of `n` consecutive columns of every row of `x` (fp16 or f32 [rows, cols], cols a
+    multiple of n, n a power of two 2 ... 8192; a view with its own row stride is fine) in one launch -> `out`: new, `x` itself (in
+    place), or a matrix of x's shape and dtype that does not overlap it.  Per block: y = (x * sign) . H_n / sqrt(n), H the natural-order
+    Sylvester matrix, summed in f64 (exactly, for fp16), divided once and rounded to f32, then to fp16: bit for bit what torch's
+    `(x.double() * sign @ H / d).to(dtype)` stores wherever that product is exact.  sign: None, or int8 [n] of +-1 on x's device; its
+    entries are not read here (check_signs does that, once, on the host)."""
+    name = "hadamard_rows"
+    ldx = _had_matrix(name, "x", x)
+    rows, cols = x.shape
+    if not isinstance(n, int) or n < 2 or n > 8192 or n & (n - 1):
+        raise RuntimeError(f"{name}: n must be a power of two in 2 ... 8192, got {n!r}")
+    if cols % n:
+        raise RuntimeError(f"{name}: x has {cols} columns, no multiple of n = {n}")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=x.dtype, device=x.device)
+    ldy = _had_matrix(name, "out", out, (rows, cols), x.dtype)
+    if out.data_ptr() == x.data_ptr() and ldy != ldx:
+        raise RuntimeError(f"{name}: out starts where x does with another row stride; in place means the same view")
+    tensors = [x, out]
+    if sign is not None:
+        _sign_vector(name, sign, n)
+        tensors.append(sign)
+    _same_gpu(name, tensors)
+    err = _lib.lib().qqq_hadamard_rows(_ptr(x), ldx, _ptr(out), ldy, rows, cols, n, _ptr(sign) if sign is not None else None,
+                                       _HAD_DTYPES[x.dtype], x.device.index or 0, _stream_for(x))
+    _raise_lib(name, err)
+    return out

@@ -1,0 +1,189 @@
+"""Rotation in front of GPTQ: the reference's QQQ/rotation/rotation.py over plain state dicts (Hugging Face parameter names, the way
+quant/model.py works without transformers).  fuse_layer_norms folds every RMSNorm weight into the linears behind it, rotate_state_dict
+turns the residual stream by an orthogonal Q (embeddings, lm_head, q/k/v, gate/up: W <- W Q;  o_proj, down_proj: W <- Q^T W) and then
+applies the per-head Hadamard to v_proj (output side) and o_proj (input side).  The function the model computes does not change, the
+norms are all ones and every weight keeps its shape: the result loads into the same modules and needs no kernel at inference.
+
+With Q = diag(s) H / d (mode="hadamard", the reference's default; s random signs, H the Sylvester matrix, d = sqrt(hidden)) every
+product with Q is one launch of ops.hadamard_rows instead of the reference's O(n^2) f64 matmul, and the per-head step is the same op
+with n = head_dim in place of the reference's CUDA package.  Every other Q (mode="random", an explicit matrix) takes the reference's
+line in torch, `(W.double() @ Q).to(dtype)`, and still the op for the per-head step.
+
+Where the bits differ from the reference's:
+  * its per-head step is an f32 butterfly inside a CUDA package (fast_hadamard_transform) whose rounding order is its own; ours is the
+    exact sum divided once and rounded once, so single fp16 elements can differ by one ulp.  That cannot be measured here (no CUDA);
+    against an f32 product with the Sylvester matrix as a stand-in, tests/golden/rotate_small.npz records how many do.
+  * for a hidden size that is an odd power of two (d is not a power of two) its f64 matmul rounds every product w * (1 / d) and then
+    the sums, while we divide the exact sum once.  The fp16 results agree on the fixture (32 x 128, bit for bit).
+A power-of-four hidden size (64, 1024, 4096) gives the reference's Q-stage bits exactly: both are exact sums scaled by a power of two.
+
+Not here: Hadamard matrices of sizes that are no power of two (the reference's Paley-type tables), smoothing, any online Hadamard."""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+
+from . import ops
+
+_RIGHT = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight")
+_LEFT = ("self_attn.o_proj", "mlp.down_proj")  # weight and bias
+_FUSED_BY = {"input_layernorm.weight": ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight"),
+             "post_attention_layernorm.weight": ("mlp.gate_proj.weight", "mlp.up_proj.weight")}
+
+
+def _is_pow2(n: int) -> bool:
+    return n > 0 and n & (n - 1) == 0
+
+
+def _check_dtype(name, key, t):
+    if t.dtype not in (torch.float16, torch.float32):
+        raise RuntimeError(f"{name}: {key} is {str(t.dtype).replace('torch.', '')}; only float16 and float32 state dicts are rotated")
+
+
+def _layer_prefixes(state_dict) -> list:
+    idx = sorted({int(k.split(".")[2]) for k in state_dict if k.startswith("model.layers.")})
+    return [f"model.layers.{i}." for i in idx]
+
+
+def fuse_layer_norms(state_dict: dict, config) -> dict:
+    """A new state dict with every RMSNorm weight folded into the linears that read the norm's output, `(W.double() * g.double())
+    .to(dtype)` as the reference: input_layernorm into q/k/v, post_attention_layernorm into gate/up, model.norm into lm_head; the norm
+    weights become ones.  Tensors that do not change are shared with the input, nothing is modified in place.
+
+    THE RESULT IS UNTIED.  With `config.tie_word_embeddings`, or without an lm_head.weight in the input, the result gets an
+    lm_head.weight of its own: a copy of the embedding made before anything is fused, which then takes model.norm.  The embedding stays
+    as it was (the reference, given a tied matrix, folds the norm into the embedding as well and later rotates it twice).  Build the
+    model that loads the result with tie_word_embeddings = False."""
+    name = "fuse_layer_norms"
+    out = dict(state_dict)
+    if bool(getattr(config, "tie_word_embeddings", False)) or "lm_head.weight" not in state_dict:
+        out["lm_head.weight"] = state_dict["model.embed_tokens.weight"].clone()
+
+    def fuse(norm_key, linear_keys):
+        g = out[norm_key]
+        _check_dtype(name, norm_key, g)
+        for k in linear_keys:
+            W = out[k]
+            _check_dtype(name, k, W)
+            out[k] = (W.double() * g.to(W.device).double()).to(W.dtype)
+        out[norm_key] = torch.ones_like(g)
+
+    for prefix in _layer_prefixes(state_dict):
+        for norm, linears in _FUSED_BY.items():
+            fuse(prefix + norm, [prefix + k for k in linears])
+    fuse("model.norm.weight", ["lm_head.weight"])
+    return out
+
+
+def hadamard_signs(n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """int8 [n] of +-1, uniform: the diagonal of the reference's random_hadamard_matrix (on the CPU; seed the generator to repeat it)"""
+    return (torch.randint(0, 2, (n,), generator=generator) * 2 - 1).to(torch.int8)
+
+
+def random_orthogonal(n: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+    """f64 [n, n]: the Q of a QR decomposition of a normal matrix with the signs of diag(R) folded in (the reference's mode "random")"""
+    q, r = torch.linalg.qr(torch.randn((n, n), dtype=torch.float64, generator=generator))
+    return q * torch.sign(torch.diag(r)).unsqueeze(0)
+
+
+def hadamard_matrix(signs: torch.Tensor) -> torch.Tensor:
+    """f64 [n, n]: diag(signs) H / d, the matrix the Hadamard path multiplies by without forming it (for checks and for the dense path
+    of another tool); d = sqrt(n) in f32, as the op"""
+    n = signs.numel()
+    i = torch.arange(n)
+    bits = i[:, None] & i[None, :]
+    par = torch.zeros_like(bits)
+    while bool(bits.any()):
+        par ^= bits & 1
+        bits = bits >> 1
+    H = (1 - 2 * par).double()
+    return signs.double()[:, None] * H / torch.tensor(n).sqrt().double()
+
+
+def _had(W, n, sign, dev):
+    # the op on a 2-D tensor from anywhere: computed on `dev`, returned where W lives, W itself untouched
+    return ops.hadamard_rows(W.to(dev).contiguous(), n, sign=sign).to(W.device)
+
+
+def rotate_state_dict(state_dict: dict, config, mode: str = "hadamard", signs: Optional[torch.Tensor] = None,
+                      Q: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, device=None):
+    """The rotated copy of an UNTIED state dict whose norm weights are ones (fuse_layer_norms makes one) -> (dict, signs or Q).
+
+    mode="hadamard": Q = diag(signs) H / sqrt(hidden); `signs` int8 [hidden] of +-1, or drawn from `generator` (hadamard_signs); the
+    hidden size must be a power of two up to 8192.  Returns the signs.  mode="random": Q from random_orthogonal(hidden, generator).  An
+    explicit `Q` (f64 [hidden, hidden], orthogonal: not checked) overrides the mode.  Both return Q, and take the reference's dense line.
+    Then the per-head Hadamard of size head_dim on v_proj (output side, weight and bias) and o_proj (input side), each a separate
+    rounding to the weight's dtype, as the reference rounds between the two steps.
+
+    float16 and float32 tensors; every tensor is computed on `device` (default cuda:0: the op has no CPU path) and returned where it
+    lived.  Tensors that do not change are shared with the input."""
+    name = "rotate_state_dict"
+    dev = torch.device(device if device is not None else "cuda:0")
+    hidden = config.hidden_size
+    heads = config.num_attention_heads
+    head_dim = getattr(config, "head_dim", None) or hidden // heads
+    if not _is_pow2(head_dim) or head_dim < 2:
+        raise RuntimeError(f"{name}: head_dim = {head_dim} is not a power of two: the per-head Hadamard needs one")
+    if "lm_head.weight" not in state_dict:
+        raise RuntimeError(f"{name}: the state dict has no lm_head.weight; a tied model is untied by fuse_layer_norms first")
+    if mode not in ("hadamard", "random"):
+        raise RuntimeError(f"{name}: mode must be 'hadamard' or 'random', got {mode!r}")
+    dense = Q is not None or mode == "random"
+    if signs is not None and dense:
+        raise RuntimeError(f"{name}: signs belong to mode='hadamard' without an explicit Q")
+    if dense:
+        if Q is None:
+            Q = random_orthogonal(hidden, generator)
+        if not isinstance(Q, torch.Tensor) or Q.dtype != torch.float64 or tuple(Q.shape) != (hidden, hidden):
+            raise RuntimeError(f"{name}: Q must be a float64 [{hidden}, {hidden}] matrix")
+        Qd = Q.to(dev)
+        sign_dev = None
+    else:
+        if not _is_pow2(hidden) or hidden > 8192:
+            raise RuntimeError(f"{name}: hidden_size = {hidden} is not a power of two up to 8192; the Paley-type Hadamard tables the "
+                               "reference uses for other sizes are not part of the repository: use mode='random'")
+        if signs is None:
+            signs = hadamard_signs(hidden, generator)
+        ops.check_signs(signs, hidden, name)  # the one host read of the signs
+        sign_dev = signs.to(dev)
+
+    def right(W):  # W Q
+        if dense:
+            return (W.to(dev).double() @ Qd).to(W.dtype).to(W.device)
+        return _had(W, hidden, sign_dev, dev)
+
+    def left(W):  # Q^T W, a bias as a column
+        if dense:
+            return (Qd.T @ W.to(dev).double()).to(W.dtype).to(W.device)
+        if W.dim() == 1:
+            return _had(W.unsqueeze(0), hidden, sign_dev, dev).squeeze(0)
+        return _had(W.t(), hidden, sign_dev, dev).t().contiguous()
+
+    out = dict(state_dict)
+    for k, W in state_dict.items():
+        tail = k.split(".", 3)[3] if k.startswith("model.layers.") and k.count(".") >= 4 else None
+        if k in ("model.embed_tokens.weight", "lm_head.weight") or tail in _RIGHT:
+            _check_dtype(name, k, W)
+            out[k] = right(W)
+        elif tail is not None and tail.rsplit(".", 1)[0] in _LEFT:
+            _check_dtype(name, k, W)
+            out[k] = left(W)
+        elif k.endswith("norm.weight") or k.endswith("layernorm.weight"):
+            if not bool((W == 1).all()):
+                raise RuntimeError(f"{name}: {k} is not all ones: a rotation commutes with RMSNorm only after fuse_layer_norms")
+    # the reference's rotate_ov_proj: H_head on the output side of v_proj and the input side of o_proj, each block of head_dim
+    for prefix in _layer_prefixes(state_dict):
+        v, o = prefix + "self_attn.v_proj.", prefix + "self_attn.o_proj."
+        out[v + "weight"] = _had(out[v + "weight"].t(), head_dim, None, dev).t().contiguous()
+        if v + "bias" in out:
+            _check_dtype(name, v + "bias", out[v + "bias"])
+            out[v + "bias"] = _had(out[v + "bias"].unsqueeze(0), head_dim, None, dev).squeeze(0)
+        out[o + "weight"] = _had(out[o + "weight"], head_dim, None, dev)
+    return out, (Q if dense else signs)
+
+
+def rotate_model(state_dict: dict, config, mode: str = "hadamard", signs: Optional[torch.Tensor] = None, Q: Optional[torch.Tensor] = None,
+                 generator: Optional[torch.Generator] = None, device=None):
+    """fuse_layer_norms, then rotate_state_dict -> (dict, signs or Q).  The result is UNTIED (see fuse_layer_norms)."""
+    return rotate_state_dict(fuse_layer_norms(state_dict, config), config, mode=mode, signs=signs, Q=Q, generator=generator, device=device)

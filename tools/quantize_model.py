@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """A QQQ W4A8 checkpoint from an fp16 one, on the GPU: a thin wrapper over qqq_amd.quant.quantize_model (GPTQ layer by layer, the
-reference's examples/quant_model.py without its rotation and smoothing stages).
+reference's examples/quant_model.py without its smoothing stage; --rotation is its rotation stage).
 
     python tools/quantize_model.py --config config.json --weights model.pt --tokens calib.npy --out DIR [--group-size 128]
                                    [--seqlen 2048] [--nsamples 128] [--mse] [--percdamp 0.01] [--seq-batch 1]
+                                   [--rotation {none,hadamard,random}] [--rotation-seed 0]
 
 --config   a transformers config.json of a Llama or Qwen2 model (read as plain JSON; transformers is not needed)
 --weights  the fp16 state dict with Hugging Face parameter names: a torch.save file, or .safetensors where the safetensors package can
@@ -12,7 +13,10 @@ reference's examples/quant_model.py without its rotation and smoothing stages).
            tokenizer here: tokenise elsewhere)
 --out      a directory: model.pt (the packed state dict, the reference's names: tools/eval_ppl.py --weights takes it) and
            quant_config.json ({"group_size", "wbits"}, as the reference writes it)
-Prints one JSON line: group_size, nsamples, seqlen, linears, seconds.
+--rotation hadamard | random: fuse the norms and rotate the state dict first (qqq_amd.quant.rotate_model; the reference runs this with
+           --mse).  The checkpoint is then UNTIED: --out also gets config.json, the input's with "tie_word_embeddings": false, and
+           quant_config.json also records {"rotation", "rotation_seed"}.  The signs / Q come from --rotation-seed.
+Prints one JSON line: group_size, nsamples, seqlen, linears, seconds (and rotation).
 """
 import argparse
 import json
@@ -40,13 +44,15 @@ def main():
     ap.add_argument("--mse", action="store_true", help="the shrink search for the scales (the reference's pairing for rotated models)")
     ap.add_argument("--percdamp", type=float, default=0.01)
     ap.add_argument("--seq-batch", type=int, default=1)
+    ap.add_argument("--rotation", choices=("none", "hadamard", "random"), default="none", help="rotate the state dict before GPTQ")
+    ap.add_argument("--rotation-seed", type=int, default=0)
     args = ap.parse_args()
     import numpy as np
     import torch
 
     if not torch.cuda.is_available():
         sys.exit("quantize_model.py needs a GPU: there is no CPU path")
-    from qqq_amd.quant import quantize_model
+    from qqq_amd.quant import hadamard_signs, quantize_model, random_orthogonal
 
     cfg = json.load(open(args.config))
     tokens = np.load(args.tokens)
@@ -60,17 +66,30 @@ def main():
         sys.exit(f"quantize_model.py: token ids outside [0, {cfg['vocab_size']})")
     ids = torch.from_numpy(tokens[:nsamples * args.seqlen].reshape(nsamples, args.seqlen))
     results = {}
+    rotation = None
+    if args.rotation != "none":
+        gen = torch.Generator().manual_seed(args.rotation_seed)
+        rotation = hadamard_signs(cfg["hidden_size"], gen) if args.rotation == "hadamard" else random_orthogonal(cfg["hidden_size"], gen)
+        if not args.mse:
+            print("quantize_model.py: hint: the reference pairs rotation with the scale search; consider --mse", file=sys.stderr)
     t0 = time.perf_counter()
     lm = quantize_model(load_state_dict(args.weights), SimpleNamespace(**cfg), ids, args.group_size, mse=args.mse, percdamp=args.percdamp,
-                        seq_batch=args.seq_batch, results=results)
+                        seq_batch=args.seq_batch, results=results, rotation=rotation)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     os.makedirs(args.out, exist_ok=True)
     torch.save({k: v.cpu() for k, v in lm.state_dict().items()}, os.path.join(args.out, "model.pt"))
+    quant_config = {"group_size": args.group_size, "wbits": 4}
+    summary = {"group_size": args.group_size, "nsamples": nsamples, "seqlen": args.seqlen, "linears": len(results) - (rotation is not None),
+               "seconds": round(dt, 2)}
+    if rotation is not None:
+        quant_config.update(rotation=args.rotation, rotation_seed=args.rotation_seed)
+        summary.update(rotation=args.rotation)
+        with open(os.path.join(args.out, "config.json"), "w") as f:  # the rotated model's lm_head is its own
+            json.dump(dict(cfg, tie_word_embeddings=False), f, indent=2)
     with open(os.path.join(args.out, "quant_config.json"), "w") as f:
-        json.dump({"group_size": args.group_size, "wbits": 4}, f)
-    print(json.dumps({"group_size": args.group_size, "nsamples": nsamples, "seqlen": args.seqlen, "linears": len(results),
-                      "seconds": round(dt, 2)}))
+        json.dump(quant_config, f)
+    print(json.dumps(summary))
 
 
 if __name__ == "__main__":
