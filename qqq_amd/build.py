@@ -123,9 +123,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 QUANT_DIR = os.path.join(_HERE, "quant")
-QUANT_SRC = os.path.join(QUANT_DIR, "csrc", "qqq_quant.hip")  # the one translation unit of the quantiser; it includes quant/csrc/qqq_gptq.hip.h and qqq_hadamard.hip.h
+QUANT_SRC = os.path.join(QUANT_DIR, "csrc", "qqq_quant.hip")  # the one translation unit of the quantiser; it includes quant/csrc/qqq_gptq.hip.h, qqq_gptq_order.hip.h and qqq_hadamard.hip.h
 QUANT_HEADER = os.path.join(QUANT_DIR, "include", "qqq_amd_quant.h")  # outside include/: the listers above do not see it
 ROTATE_HEADER = os.path.join(QUANT_DIR, "include", "qqq_amd_rotate.h")  # the rotation op of the same library: a header of its own
+ORDER_HEADER = os.path.join(QUANT_DIR, "include", "qqq_amd_gptq_order.h")  # act-order / static groups: the per-column sweep and the batched group scales
 QUANT_LIB = os.path.join(_HERE, "libqqq_amd_quant.so")
 # the quantiser's entry points promise bits: no fused multiply-add the source does not spell, a correctly rounded divide, subnormals kept
 QUANT_FLAGS = ("-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-fno-gpu-flush-denormals-to-zero")
@@ -134,7 +135,7 @@ QUANT_FLAGS = ("-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", 
 def build_quant(force: bool = False, verbose: bool = False) -> str:
     """the GPTQ quantiser's library (qqq_amd/quant): an offline tool with a library of its own, libqqq_amd.so stays as it is"""
     csrc = os.path.dirname(QUANT_SRC)
-    deps = [QUANT_HEADER, ROTATE_HEADER, header("qqq_amd.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
+    deps = [QUANT_HEADER, ROTATE_HEADER, ORDER_HEADER, header("qqq_amd.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
     if not force and os.path.exists(QUANT_LIB) and os.path.getmtime(QUANT_LIB) >= max(map(os.path.getmtime, deps)):
         return QUANT_LIB
     return _compile(QUANT_SRC, QUANT_LIB, verbose, QUANT_FLAGS)

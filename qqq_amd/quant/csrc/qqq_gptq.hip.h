@@ -14,6 +14,8 @@
 //   qqq_gptq_scales_kernel<TPR>    the scale of a row from TPR threads (64 up to 512 columns -- four rows per workgroup -- else 256): the
 //       row's max |w|, then with mse the 80 candidates' error sums in 80 registers per thread over one pass of the row, reduced through
 //       the wave and, for TPR = 256, in wave order through LDS; one thread picks the earliest least.
+// Both kernels are thin wrappers of a body (gptq_block_body, gptq_scales_body) that the kernels of qqq_gptq_order.hip.h run too: the sweep
+// with a scale per (row, column) and the scales of every (row, group) pair share these bits by running this code.
 #ifndef QQQ_AMD_QQQ_GPTQ_HIP_H_
 #define QQQ_AMD_QQQ_GPTQ_HIP_H_
 
@@ -74,14 +76,27 @@ __device__ __forceinline__ void gptq_step(float (&w)[COUNT / 8], float (&qv)[COU
   }
 }
 
-template <int COUNT, bool GROUPED, int... I>
+// the scale of a step: one per row here; qqq_gptq_order.hip.h has the per-column source.  A source is built from the kernel's arguments for
+// the row and lane, and step<COUNT, I>() gives every lane of the row the scale of step I.
+struct gptq_row_scale {
+  float s;
+  template <class ARGS>
+  __device__ __forceinline__ gptq_row_scale(const ARGS& a, const long long row, const int) : s(a.scale[row]) {}
+  template <int COUNT, int I>
+  __device__ __forceinline__ float step() const {
+    return s;
+  }
+};
+
+template <int COUNT, bool GROUPED, class SCALE, int... I>
 __device__ __forceinline__ void gptq_sweep(std::integer_sequence<int, I...>, float (&w)[COUNT / 8], float (&qv)[COUNT / 8],
-                                           float (&ev)[COUNT / 8], const float* h_s, const int l, const float s) {
-  (gptq_step<COUNT, GROUPED, I>(w, qv, ev, h_s, l, s), ...);
+                                           float (&ev)[COUNT / 8], const float* h_s, const int l, const SCALE& sc) {
+  (gptq_step<COUNT, GROUPED, I>(w, qv, ev, h_s, l, sc.template step<COUNT, I>()), ...);
 }
 
-template <int COUNT, bool GROUPED>
-__global__ __launch_bounds__(GPTQ_NT) void qqq_gptq_block_kernel(const qqq_gptq_block_args a) {
+// the body of a sweep kernel: ARGS has W1, Hinv1, Q1, Err1, their strides and rows, and whatever SCALE reads
+template <int COUNT, bool GROUPED, class SCALE, class ARGS>
+__device__ __forceinline__ void gptq_block_body(const ARGS& a) {
   constexpr int CH = COUNT / 32;  // 32-column chunks
   __shared__ __attribute__((aligned(16))) float h_s[COUNT * COUNT];
   const int tid = threadIdx.x, l = tid & (GPTQ_LANES - 1), g = tid / GPTQ_LANES;
@@ -90,7 +105,7 @@ __global__ __launch_bounds__(GPTQ_NT) void qqq_gptq_block_kernel(const qqq_gptq_
   const long long row_raw = (long long)blockIdx.x * GPTQ_ROWS + g;
   const bool live = row_raw < a.rows;
   const long long row = live ? row_raw : a.rows - 1;
-  const float s = a.scale[row];
+  const SCALE sc(a, row, l);
   float w[CH * 4], qv[CH * 4], ev[CH * 4];
   const float* wp = a.W1 + row * a.ldw + 4 * l;
 #pragma unroll
@@ -103,7 +118,7 @@ __global__ __launch_bounds__(GPTQ_NT) void qqq_gptq_block_kernel(const qqq_gptq_
     }
   __syncthreads();
 
-  gptq_sweep<COUNT, GROUPED>(std::make_integer_sequence<int, COUNT>{}, w, qv, ev, h_s, l, s);
+  gptq_sweep<COUNT, GROUPED>(std::make_integer_sequence<int, COUNT>{}, w, qv, ev, h_s, l, sc);
 
   if (!live) return;
   float* qp = a.Q1 + row * a.ldq + 4 * l;
@@ -115,6 +130,11 @@ __global__ __launch_bounds__(GPTQ_NT) void qqq_gptq_block_kernel(const qqq_gptq_
       qp[32 * c + e] = qv[4 * c + e];
       ep[32 * c + e] = ev[4 * c + e];
     }
+}
+
+template <int COUNT, bool GROUPED>
+__global__ __launch_bounds__(GPTQ_NT) void qqq_gptq_block_kernel(const qqq_gptq_block_args a) {
+  gptq_block_body<COUNT, GROUPED, gptq_row_scale>(a);
 }
 
 struct qqq_gptq_scales_args {
@@ -135,8 +155,12 @@ __device__ __forceinline__ float gptq_wave_sum(float v) {
   return v;
 }
 
+// the scale of the `cols` values at x from TPR threads, written to *out where `live` (every thread of the workgroup comes here, with
+// workgroup-uniform cols, grouped and mse; TPR = 64: the workgroup's four waves take a row each).  Shared by the kernel below and by
+// qqq_gptq_group_scales_kernel (qqq_gptq_order.hip.h), whose bits are this body's at 128 columns.
 template <int TPR>
-__global__ __launch_bounds__(GPTQ_SC_NT) void qqq_gptq_scales_kernel(const qqq_gptq_scales_args a) {
+__device__ __forceinline__ void gptq_scales_body(const float* x, const int cols, const bool grouped, const bool mse, const bool live,
+                                                 float* out) {
   constexpr int WAVES = GPTQ_SC_NT / 64;
   constexpr int RPW = GPTQ_SC_NT / TPR;  // rows of a workgroup: 4 (a wave each) or 1
   __shared__ float max_s[WAVES];
@@ -144,13 +168,9 @@ __global__ __launch_bounds__(GPTQ_SC_NT) void qqq_gptq_scales_kernel(const qqq_g
   __shared__ float part_s[WAVES][GPTQ_GRID];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int rl = tid / TPR, t = tid % TPR;
-  const long long row_raw = (long long)blockIdx.x * RPW + rl;
-  const bool live = row_raw < a.rows;
-  const float* x = a.W + (live ? row_raw : (long long)a.rows - 1) * a.ldw;
-  const bool grouped = a.grouped != 0;
 
   float m = 0.f;
-  for (int c = t; c < a.cols; c += TPR) m = fmaxf(m, fabsf(x[c]));
+  for (int c = t; c < cols; c += TPR) m = fmaxf(m, fabsf(x[c]));
   m = gptq_wave_max(m);
   if (TPR > 64) {
     if (lane == 0) max_s[wave] = m;
@@ -160,8 +180,8 @@ __global__ __launch_bounds__(GPTQ_SC_NT) void qqq_gptq_scales_kernel(const qqq_g
     for (int w = 1; w < WAVES; ++w) m = fmaxf(m, max_s[w]);
   }
   const float xmax = m == 0.f ? 1.f : m;
-  if (!a.mse) {  // (uniform)
-    if (t == 0 && live) a.out[row_raw] = gptq_scale_of(xmax, grouped);
+  if (!mse) {  // (uniform)
+    if (t == 0 && live) *out = gptq_scale_of(xmax, grouped);
     return;
   }
 
@@ -170,7 +190,7 @@ __global__ __launch_bounds__(GPTQ_SC_NT) void qqq_gptq_scales_kernel(const qqq_g
   float acc[GPTQ_GRID];
 #pragma unroll
   for (int i = 0; i < GPTQ_GRID; ++i) acc[i] = 0.f;
-  for (int c = t; c < a.cols; c += TPR) {
+  for (int c = t; c < cols; c += TPR) {
     const float w = x[c];
 #pragma unroll
     for (int i = 0; i < GPTQ_GRID; ++i) {
@@ -199,8 +219,16 @@ __global__ __launch_bounds__(GPTQ_SC_NT) void qqq_gptq_scales_kernel(const qqq_g
         s = cand_s[rl][i];
       }
     }
-    a.out[row_raw] = s;
+    *out = s;
   }
+}
+
+template <int TPR>
+__global__ __launch_bounds__(GPTQ_SC_NT) void qqq_gptq_scales_kernel(const qqq_gptq_scales_args a) {
+  const long long row_raw = (long long)blockIdx.x * (GPTQ_SC_NT / TPR) + threadIdx.x / TPR;
+  const bool live = row_raw < a.rows;
+  const long long row = live ? row_raw : (long long)a.rows - 1;
+  gptq_scales_body<TPR>(a.W + row * a.ldw, a.cols, a.grouped != 0, a.mse != 0, live, a.out + row);
 }
 
 #endif  // QQQ_AMD_QQQ_GPTQ_HIP_H_

@@ -1,6 +1,7 @@
 // qqq_quant.hip -- the one translation unit of libqqq_amd_quant.so: the C-ABI entry points of the GPTQ quantiser
-// (qqq_amd/quant/include/qqq_amd_quant.h) over the kernels of qqq_gptq.hip.h, and of the rotation op (qqq_amd/quant/include/qqq_amd_rotate.h)
-// over the kernel of qqq_hadamard.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
+// (qqq_amd/quant/include/qqq_amd_quant.h) over the kernels of qqq_gptq.hip.h, of its act-order / static-groups ops
+// (qqq_amd/quant/include/qqq_amd_gptq_order.h) over those of qqq_gptq_order.hip.h, and of the rotation op
+// (qqq_amd/quant/include/qqq_amd_rotate.h) over the kernel of qqq_hadamard.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
 // (qqq_amd/build.py, build_quant): the entry points promise bits.
 #include <hip/hip_runtime.h>
 
@@ -9,9 +10,11 @@
 #include <cstdio>
 
 #include "../../../include/qqq_amd.h"  // the return codes
+#include "../include/qqq_amd_gptq_order.h"
 #include "../include/qqq_amd_quant.h"
 #include "../include/qqq_amd_rotate.h"
 #include "qqq_gptq.hip.h"
+#include "qqq_gptq_order.hip.h"
 #include "qqq_hadamard.hip.h"
 
 static thread_local char g_err[512] = "";
@@ -116,6 +119,88 @@ extern "C" int qqq_gptq_block(const void* W1, int ldw, const void* Hinv1, int ld
     hipLaunchKernelGGL((qqq_gptq_block_kernel<128, false>), grid, dim3(GPTQ_NT), 0, st, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_gptq_block_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_gptq_group_scales(const void* W, int ldw, int rows, int cols, int mse, void* scales_out, int lds, int dev, void* stream) {
+  g_err[0] = 0;
+  if (rows < 1 || cols < 128 || cols > 1048576 || cols % 128 != 0 || ldw < cols || lds < cols / 128) {
+    snprintf(g_err, sizeof(g_err),
+             "qqq_gptq_group_scales: bad shape rows=%d cols=%d ldw=%d lds=%d (need rows >= 1, cols a multiple of 128 in 128 ... 1048576, ldw >= "
+             "cols, lds >= cols / 128)",
+             rows, cols, ldw, lds);
+    return QQQ_ERR_ARG;
+  }
+  if (mse != 0 && mse != 1) {
+    snprintf(g_err, sizeof(g_err), "qqq_gptq_group_scales: mse=%d must be 0 or 1", mse);
+    return QQQ_ERR_ARG;
+  }
+  if (!W || !scales_out || misaligned(W, 4) || misaligned(scales_out, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_gptq_group_scales: bad argument (W and scales_out must be non-NULL and 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_gptq_group_scales_args a;
+  a.W = static_cast<const float*>(W);
+  a.out = static_cast<float*>(scales_out);
+  a.ldw = ldw;
+  a.lds = lds;
+  a.groups = cols / 128;
+  a.pairs = static_cast<long long>(rows) * a.groups;
+  a.mse = mse;
+  const long long grid = (a.pairs + GPTQ_SC_NT / 64 - 1) / (GPTQ_SC_NT / 64);
+  if (grid > 0x7fffffffLL) {
+    snprintf(g_err, sizeof(g_err), "qqq_gptq_group_scales: rows=%d x cols=%d is more than one launch holds", rows, cols);
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_gptq_group_scales_kernel, dim3(static_cast<unsigned>(grid)), dim3(GPTQ_SC_NT), 0, static_cast<hipStream_t>(stream), a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_gptq_group_scales_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_gptq_block_cols(const void* W1, int ldw, const void* Hinv1, int ldh, const void* scales, int lds, int groups,
+                                   const void* gidx, int rows, int count, void* Q1, int ldq, void* Err1, int lde, int dev, void* stream) {
+  g_err[0] = 0;
+  if (count != 64 && count != 128) {
+    snprintf(g_err, sizeof(g_err), "qqq_gptq_block_cols: count=%d is not one of 64, 128", count);
+    return QQQ_ERR_ARG;
+  }
+  if (rows < 1 || groups < 1 || lds < groups || ldw < count || ldh < count || ldq < count || lde < count) {
+    snprintf(g_err, sizeof(g_err),
+             "qqq_gptq_block_cols: bad shape rows=%d groups=%d lds=%d ldw=%d ldh=%d ldq=%d lde=%d (need rows >= 1, groups >= 1, lds >= groups "
+             "and every other stride >= count=%d)",
+             rows, groups, lds, ldw, ldh, ldq, lde, count);
+    return QQQ_ERR_ARG;
+  }
+  if (!W1 || !Hinv1 || !scales || !gidx || !Q1 || !Err1 || misaligned(W1, 4) || misaligned(Hinv1, 4) || misaligned(scales, 4) ||
+      misaligned(gidx, 4) || misaligned(Q1, 4) || misaligned(Err1, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_gptq_block_cols: bad argument (every pointer must be non-NULL and 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_gptq_block_cols_args a;
+  a.W1 = static_cast<const float*>(W1);
+  a.Hinv1 = static_cast<const float*>(Hinv1);
+  a.scales = static_cast<const float*>(scales);
+  a.gidx = static_cast<const int*>(gidx);
+  a.Q1 = static_cast<float*>(Q1);
+  a.Err1 = static_cast<float*>(Err1);
+  a.ldw = ldw;
+  a.ldh = ldh;
+  a.lds = lds;
+  a.ldq = ldq;
+  a.lde = lde;
+  a.rows = rows;
+  a.groups = groups;
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((rows + GPTQ_ROWS - 1) / GPTQ_ROWS);
+  if (count == 64)
+    hipLaunchKernelGGL(qqq_gptq_block_cols_kernel<64>, grid, dim3(GPTQ_NT), 0, st, a);
+  else
+    hipLaunchKernelGGL(qqq_gptq_block_cols_kernel<128>, grid, dim3(GPTQ_NT), 0, st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_gptq_block_cols_kernel launch");
   return QQQ_OK;
 }
 

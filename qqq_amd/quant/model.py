@@ -12,7 +12,7 @@ import torch.nn.functional as F
 
 from ..attention import _config_rope, rope_inv_freq, rope_tables
 from ..model import QuantLlamaForCausalLM
-from .gptq import Hessian, gptq_quantize
+from .gptq import Hessian, gptq_quantize, gptq_quantize_ordered
 from .rotation import rotate_model
 
 ATTN = ("q_proj", "k_proj", "v_proj", "o_proj")
@@ -90,13 +90,17 @@ def _run(layer, inps, seq_batch, taps=None):
 
 @torch.no_grad()
 def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size: int, mse: bool = False, percdamp: float = 0.01,
-                   seq_batch: int = 1, device=None, results: Optional[dict] = None, rotation=None) -> QuantLlamaForCausalLM:
+                   seq_batch: int = 1, device=None, results: Optional[dict] = None, rotation=None, act_order: bool = False,
+                   static_groups: bool = False) -> QuantLlamaForCausalLM:
     """A packed QuantLlamaForCausalLM from an fp16 Hugging Face state dict, a (duck-typed) Llama or Qwen2 config and calibration token
     ids [samples, seqlen].  `seq_batch` sequences run through a layer at a time (1, the reference's, counts every sequence as one sample
     of the Hessian).  `results`: a dict that receives the GPTQResult of every linear under its state-dict prefix.
     `rotation`: None, or what rotation.rotate_model is to do to the state dict first (the reference's --rotation; pair it with mse=True):
     "hadamard", "random", an int8 [hidden] sign vector, or an f64 [hidden, hidden] Q.  The model is then built UNTIED (its lm_head
-    carries the final norm), its norms are ones, and results["rotation"] receives the signs or Q that were used."""
+    carries the final norm), its norms are ones, and results["rotation"] receives the signs or Q that were used.
+    `act_order`, `static_groups`: the reference's --gptq_act_order / --gptq_static_groups (both on by default THERE, off here): with
+    either, every linear goes through gptq_quantize_ordered; groups with act_order need static_groups too.  The checkpoint's layout does
+    not change."""
     dev = torch.device(device if device is not None else "cuda:0")
     if rotation is not None:
         if isinstance(rotation, str):
@@ -128,7 +132,11 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
             for name in names:
                 key = f"{mod_name}.{name}"
                 W = w[key + ".weight"]
-                res = gptq_quantize(W, hs[HESSIAN_OF[name]].H, group_size, mse=mse, percdamp=percdamp)
+                if act_order or static_groups:
+                    res = gptq_quantize_ordered(W, hs[HESSIAN_OF[name]].H, group_size, mse=mse, percdamp=percdamp, act_order=act_order,
+                                                static_groups=static_groups)
+                else:
+                    res = gptq_quantize(W, hs[HESSIAN_OF[name]].H, group_size, mse=mse, percdamp=percdamp)
                 res.pack_into(getattr(getattr(qlayer, mod_name), name), w.get(key + ".bias"))
                 w[key + ".weight"] = res.weight
                 if results is not None:

@@ -1,5 +1,5 @@
-"""Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h and qqq_amd_rotate.h state the
-exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing on the host."""
+"""Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h, qqq_amd_gptq_order.h and
+qqq_amd_rotate.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing on the host."""
 from __future__ import annotations
 
 import torch
@@ -72,6 +72,55 @@ def gptq_block(W1: torch.Tensor, Hinv1: torch.Tensor, scale: torch.Tensor, group
     _same_gpu(name, (W1, Hinv1, scale, Q1, Err1))
     err = _lib.lib().qqq_gptq_block(_ptr(W1), ldw, _ptr(Hinv1), ldh, _ptr(scale), rows, count, int(bool(grouped)), _ptr(Q1), ldq,
                                     _ptr(Err1), lde, W1.device.index or 0, _stream_for(W1))
+    _raise_lib(name, err)
+    return Q1, Err1
+
+
+def group_scales(W: torch.Tensor, mse: bool = False) -> torch.Tensor:
+    """The grouped 4-bit scale (2 xmax / 15, codes 0 ... 15, zero 8) of every group of 128 columns of every row of `W` (f32 [rows, cols],
+    cols a multiple of 128; a column slice of a wider matrix is fine) in one launch -> f32 [rows, cols / 128].  Entry (r, g) has the bits
+    of weight_scales(W[:, 128 g : 128 g + 128], True, mse)[r]: the static groups of GPTQ, found before the sweep."""
+    name = "group_scales"
+    ldw = _matrix(name, "W", W)
+    rows, cols = W.shape
+    if cols % 128:
+        raise RuntimeError(f"{name}: W has {cols} columns, no multiple of 128")
+    _same_gpu(name, (W,))
+    out = torch.empty((rows, cols // 128), dtype=torch.float32, device=W.device)
+    err = _lib.lib().qqq_gptq_group_scales(_ptr(W), ldw, rows, cols, int(bool(mse)), _ptr(out), cols // 128, W.device.index or 0,
+                                           _stream_for(W))
+    _raise_lib(name, err)
+    return out
+
+
+def gptq_block_cols(W1: torch.Tensor, Hinv1: torch.Tensor, scales: torch.Tensor, gidx: torch.Tensor, out=None):
+    """gptq_block in grouped arithmetic with a scale per (row, column): step i quantises under scales[r, gidx[i]] -> (Q1, Err1), both
+    f32 [rows, count]: new, or the pair given as `out`.  W1 f32 [rows, count] (count 64 or 128), Hinv1 f32 [count, count], Q1 and Err1
+    may be views with their own row strides; scales f32 [rows, groups] may be a column range of a wider table; gidx contiguous int32
+    [count] on the same GPU, read on the device alone (an index outside [0, groups) is clamped into it there).  W1 is left as it is."""
+    name = "gptq_block_cols"
+    ldw = _matrix(name, "W1", W1)
+    rows, count = W1.shape
+    if count not in (64, 128):
+        raise RuntimeError(f"{name}: W1 must have 64 or 128 columns, got {count}")
+    ldh = _matrix(name, "Hinv1", Hinv1, count)
+    if Hinv1.shape[0] != count:
+        raise RuntimeError(f"{name}: Hinv1 must be [{count}, {count}], got {tuple(Hinv1.shape)}")
+    lds = _matrix(name, "scales", scales)
+    if scales.shape[0] != rows:
+        raise RuntimeError(f"{name}: scales must have one row per row of W1 ({rows}), got {scales.shape[0]}")
+    if not isinstance(gidx, torch.Tensor) or gidx.dtype != torch.int32 or gidx.dim() != 1 or gidx.numel() != count or not gidx.is_contiguous():
+        got = f"{_dt(gidx.dtype)} {tuple(gidx.shape)}" if isinstance(gidx, torch.Tensor) else type(gidx).__name__
+        raise RuntimeError(f"{name}: gidx must be contiguous int32 [{count}], got {got}")
+    if out is None:
+        out = (torch.empty((rows, count), dtype=torch.float32, device=W1.device), torch.empty((rows, count), dtype=torch.float32, device=W1.device))
+    Q1, Err1 = out
+    ldq, lde = _matrix(name, "Q1", Q1, count), _matrix(name, "Err1", Err1, count)
+    if Q1.shape[0] != rows or Err1.shape[0] != rows:
+        raise RuntimeError(f"{name}: Q1 and Err1 must have {rows} rows, got {Q1.shape[0]} and {Err1.shape[0]}")
+    _same_gpu(name, (W1, Hinv1, scales, gidx, Q1, Err1))
+    err = _lib.lib().qqq_gptq_block_cols(_ptr(W1), ldw, _ptr(Hinv1), ldh, _ptr(scales), lds, scales.shape[1], _ptr(gidx), rows, count,
+                                         _ptr(Q1), ldq, _ptr(Err1), lde, W1.device.index or 0, _stream_for(W1))
     _raise_lib(name, err)
     return Q1, Err1
 

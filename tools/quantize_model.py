@@ -4,7 +4,7 @@ reference's examples/quant_model.py without its smoothing stage; --rotation is i
 
     python tools/quantize_model.py --config config.json --weights model.pt --tokens calib.npy --out DIR [--group-size 128]
                                    [--seqlen 2048] [--nsamples 128] [--mse] [--percdamp 0.01] [--seq-batch 1]
-                                   [--rotation {none,hadamard,random}] [--rotation-seed 0]
+                                   [--rotation {none,hadamard,random}] [--rotation-seed 0] [--act-order] [--static-groups]
 
 --config   a transformers config.json of a Llama or Qwen2 model (read as plain JSON; transformers is not needed)
 --weights  the fp16 state dict with Hugging Face parameter names: a torch.save file, or .safetensors where the safetensors package can
@@ -16,6 +16,10 @@ reference's examples/quant_model.py without its smoothing stage; --rotation is i
 --rotation hadamard | random: fuse the norms and rotate the state dict first (qqq_amd.quant.rotate_model; the reference runs this with
            --mse).  The checkpoint is then UNTIED: --out also gets config.json, the input's with "tie_word_embeddings": false, and
            quant_config.json also records {"rotation", "rotation_seed"}.  The signs / Q come from --rotation-seed.
+--act-order, --static-groups   the reference's --gptq_act_order / --gptq_static_groups, which are ON by default there and off here:
+           sweep the columns by falling diag(H), and find every group's scale before the sweep.  With --group-size 128, --act-order
+           needs --static-groups.  The checkpoint's layout does not change; quant_config.json records the two where set.  The
+           reference's default recipe is --rotation hadamard --mse --act-order --static-groups.
 Prints one JSON line: group_size, nsamples, seqlen, linears, seconds (and rotation).
 """
 import argparse
@@ -46,7 +50,12 @@ def main():
     ap.add_argument("--seq-batch", type=int, default=1)
     ap.add_argument("--rotation", choices=("none", "hadamard", "random"), default="none", help="rotate the state dict before GPTQ")
     ap.add_argument("--rotation-seed", type=int, default=0)
+    ap.add_argument("--act-order", action="store_true", help="sweep the columns by falling diag(H) (the reference's default; off here)")
+    ap.add_argument("--static-groups", action="store_true",
+                    help="find every group's scale before the sweep (the reference's default; off here; needed by --act-order with groups)")
     args = ap.parse_args()
+    if args.act_order and args.group_size != -1 and not args.static_groups:
+        ap.error("--act-order with --group-size 128 needs --static-groups (moving groups cannot be packed)")
     import numpy as np
     import torch
 
@@ -74,7 +83,8 @@ def main():
             print("quantize_model.py: hint: the reference pairs rotation with the scale search; consider --mse", file=sys.stderr)
     t0 = time.perf_counter()
     lm = quantize_model(load_state_dict(args.weights), SimpleNamespace(**cfg), ids, args.group_size, mse=args.mse, percdamp=args.percdamp,
-                        seq_batch=args.seq_batch, results=results, rotation=rotation)
+                        seq_batch=args.seq_batch, results=results, rotation=rotation, act_order=args.act_order,
+                        static_groups=args.static_groups)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     os.makedirs(args.out, exist_ok=True)
@@ -82,6 +92,9 @@ def main():
     quant_config = {"group_size": args.group_size, "wbits": 4}
     summary = {"group_size": args.group_size, "nsamples": nsamples, "seqlen": args.seqlen, "linears": len(results) - (rotation is not None),
                "seconds": round(dt, 2)}
+    if args.act_order or args.static_groups:
+        quant_config.update(act_order=args.act_order, static_groups=args.static_groups)
+        summary.update(act_order=args.act_order, static_groups=args.static_groups)
     if rotation is not None:
         quant_config.update(rotation=args.rotation, rotation_seed=args.rotation_seed)
         summary.update(rotation=args.rotation)
