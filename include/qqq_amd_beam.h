@@ -1,6 +1,6 @@
 /*
- * qqq_amd_beam.h -- C-ABI of beam search on the device (exported by libqqq_amd.so; a feature header: every *.h in a subdirectory of include/
- * other than serving/ is one, found by listing, bound behind the serving headers): the step that follows a pass's logits, and the block
+ * qqq_amd_beam.h -- C-ABI of beam search on the device (exported by libqqq_amd.so, beside include/qqq_amd.h and the other per-feature
+ * headers): the step that follows a pass's logits, and the block
  * copies of a cache reorder.
  *
  * qqq_beam_step: P prompts of B = num_beams beams each; row p * B + b of every per-row array is beam b of prompt p.
@@ -12,7 +12,7 @@
  *   2B <= vocab <= 262144; rows = P * B, a multiple of B, 0 <= rows <= 65535; rows == 0 is a no-op (NULL pointers allowed).
  *
  * One prompt (this is the definition; tests/beam_ref.py restates it in numpy):
- *   1. every live row yields its first 2B tokens in the order of qqq_topk_logprobs' rule 4 (include/serving/qqq_amd_logprobs.h), with that
+ *   1. every live row yields its first 2B tokens in the order of qqq_topk_logprobs' rule 4 (include/qqq_amd_logprobs.h), with that
  *      entry's top_logprobs to the bit.
  *   2. a candidate is (b, i): the token ids[i] of row b, lp = top_logprobs[i], score = cum[row] + lp as ONE f32 addition.
  *   3. candidates are ordered by score descending -- NaN and -inf are equal and below everything, -0 equals +0, as in the key order --
@@ -48,7 +48,7 @@
 #ifndef QQQ_AMD_BEAM_H_
 #define QQQ_AMD_BEAM_H_
 
-#include "../qqq_amd.h"
+#include "qqq_amd.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,6 +1,6 @@
 /*
- * qqq_amd_guided.h -- C-ABI of the two device ops behind guided decoding (exported by libqqq_amd.so; a nested header, two levels below
- * include/): a completion follows a deterministic automaton over token ids that lives in device memory.  qqq_fsm_mask runs in FRONT of a
+ * qqq_amd_guided.h -- C-ABI of the two device ops behind guided decoding (exported by libqqq_amd.so, beside include/qqq_amd.h and the
+ * other per-feature headers): a completion follows a deterministic automaton over token ids that lives in device memory.  qqq_fsm_mask runs in FRONT of a
  * sampler and leaves only the tokens the row's state allows; qqq_fsm_advance runs BEHIND qqq_sample_advance (include/qqq_amd_step.h) and
  * moves the state on over the token just drawn.  Both sit inside a decode loop's captured step, so no token leaves the device between
  * two syncs.  All of it is integer and bit work.
@@ -58,7 +58,7 @@
 #ifndef QQQ_AMD_GUIDED_H_
 #define QQQ_AMD_GUIDED_H_
 
-#include "../../qqq_amd.h"
+#include "qqq_amd.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,6 +1,6 @@
 /*
- * qqq_amd_logprobs.h -- C-ABI of the fused top-k log-probability kernel (exported by libqqq_amd.so; a serving header, beside the
- * operator's in include/): for every row of a batch of fp16 logits the log-probability and the rank of ONE token, and the k most probable
+ * qqq_amd_logprobs.h -- C-ABI of the fused top-k log-probability kernel (exported by libqqq_amd.so, beside include/qqq_amd.h and
+ * the other per-feature headers): for every row of a batch of fp16 logits the log-probability and the rank of ONE token, and the k most probable
  * tokens with their log-probabilities, in ONE launch.  It is what OpenAI-style `logprobs` / `top_logprobs` need from the logits a sampler
  * drew from, without an fp32 copy of them and without a sort of the vocabulary.
  *
@@ -46,7 +46,7 @@
 #ifndef QQQ_AMD_LOGPROBS_H_
 #define QQQ_AMD_LOGPROBS_H_
 
-#include "../qqq_amd.h"
+#include "qqq_amd.h"
 
 #ifdef __cplusplus
 extern "C" {

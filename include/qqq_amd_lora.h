@@ -1,6 +1,6 @@
 /*
- * qqq_amd_lora.h -- C-ABI of the batched LoRA op (exported by libqqq_amd.so; a header three levels below include/, found by
- * build.deep_headers()): low-rank fp16 adapters added beside the W4A8 GEMM, several adapters mixed in one batch, the adapter of every
+ * qqq_amd_lora.h -- C-ABI of the batched LoRA op (exported by libqqq_amd.so, beside include/qqq_amd.h and the other
+ * per-feature headers): low-rank fp16 adapters added beside the W4A8 GEMM, several adapters mixed in one batch, the adapter of every
  * token read from device memory.
  *
  * qqq_lora_add
@@ -31,7 +31,7 @@
 #ifndef QQQ_AMD_LORA_H_
 #define QQQ_AMD_LORA_H_
 
-#include "../../../qqq_amd.h"
+#include "qqq_amd.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -1,6 +1,6 @@
 /*
  * qqq_amd_stop.h -- C-ABI of the two device ops behind generate()'s `stop`, `stop_token_ids` and `min_new_tokens` (exported by
- * libqqq_amd.so; an extension header, in a subdirectory of include/serving/): the ways a completion ends besides its budget and its one
+ * libqqq_amd.so, beside include/qqq_amd.h and the other per-feature headers): the ways a completion ends besides its budget and its one
  * eos id, decided where eos is decided -- on the device, inside a decode loop's captured step.  All of it is integer work.
  *
  * qqq_ban_tokens runs in FRONT of a sampler and rewrites fp16 logits in place: the minimum length.
@@ -53,7 +53,7 @@
 #ifndef QQQ_AMD_STOP_H_
 #define QQQ_AMD_STOP_H_
 
-#include "../../qqq_amd.h"
+#include "qqq_amd.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -30,7 +30,7 @@ def lib():
     L = ctypes.CDLL(path)
     if L.qqq_amd_abi_version() != ABI_VERSION:  # (int(void): callable before it is bound; a stale library may lack what the headers declare)
         raise RuntimeError("libqqq_amd.so ABI version mismatch; rebuild")
-    for hdr in _build.bound_headers() + _build.nested_headers() + _build.deep_headers():
+    for hdr in _build.operator_headers():
         _abi.bind(L, hdr)
     _lib = L
     return L

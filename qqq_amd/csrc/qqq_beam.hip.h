@@ -1,4 +1,4 @@
-// qqq_beam.hip.h -- beam search on the device (include/search/qqq_amd_beam.h): the step behind a pass's logits and the block copies of a
+// qqq_beam.hip.h -- beam search on the device (include/qqq_amd_beam.h): the step behind a pass's logits and the block copies of a
 // cache reorder.  Part of the single translation unit qqq_w4a8.hip, behind qqq_logprobs.hip.h, whose row body it calls: key order,
 // fixed-point weights, radix select and the scorer's logarithm are that header's device functions, not copies of them.
 //

@@ -1,4 +1,4 @@
-// qqq_guided.hip.h -- guided decoding (include/ext/guided/qqq_amd_guided.h): a completion follows a token automaton held in device memory
+// qqq_guided.hip.h -- guided decoding (include/qqq_amd_guided.h): a completion follows a token automaton held in device memory
 // in CSR form.  Two integer kernels around a decode loop's sampler, both inside its captured step.  Part of the single translation unit
 // qqq_w4a8.hip.
 //

@@ -1,4 +1,4 @@
-// qqq_logprobs.hip.h -- the fused top-k log-probability kernel (include/serving/qqq_amd_logprobs.h): for every row of a batch of fp16 logits
+// qqq_logprobs.hip.h -- the fused top-k log-probability kernel (include/qqq_amd_logprobs.h): for every row of a batch of fp16 logits
 // the log-probability and the rank of ONE token, and the k most probable tokens with their log-probabilities, in ONE launch.  Part of the
 // single translation unit qqq_w4a8.hip, behind qqq_score.hip.h: the key order, the fixed-point weights and the radix select are the
 // sampler's, the row walk the scorer's, and a value is the scorer's to the bit.

@@ -1,4 +1,4 @@
-// qqq_lora.hip.h -- the batched LoRA op (include/ext/adapters/lora/qqq_amd_lora.h): fp16 low-rank adapters added to a W4A8 GEMM's output,
+// qqq_lora.hip.h -- the batched LoRA op (include/qqq_amd_lora.h): fp16 low-rank adapters added to a W4A8 GEMM's output,
 // the adapter of every token read from device memory.  One kernel, one launch.  Part of the single translation unit qqq_w4a8.hip.
 //
 //   qqq_lora_add_kernel<R>  grid (token tiles, column chunks): a workgroup of 8 waves owns 16 tokens and a chunk of the columns of ONE

@@ -1,4 +1,4 @@
-// qqq_stop.hip.h -- stop sequences, stop token ids and the minimum length of a completion (include/serving/stop/qqq_amd_stop.h): two integer
+// qqq_stop.hip.h -- stop sequences, stop token ids and the minimum length of a completion (include/qqq_amd_stop.h): two integer
 // kernels around a decode loop's sampler, both inside its captured step.  Part of the single translation unit qqq_w4a8.hip.
 //
 //   qqq_ban_tokens_kernel   One wave per logits row (4 per workgroup).  A row whose completion index is below the row's minimum length

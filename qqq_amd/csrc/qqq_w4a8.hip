@@ -84,9 +84,9 @@
 #include "qqq_score.hip.h"
 #include "../../include/qqq_amd_score.h"
 #include "qqq_logprobs.hip.h"
-#include "../../include/serving/qqq_amd_logprobs.h"
+#include "../../include/qqq_amd_logprobs.h"
 #include "qqq_beam.hip.h"
-#include "../../include/search/qqq_amd_beam.h"
+#include "../../include/qqq_amd_beam.h"
 #include "qqq_step.hip.h"
 #include "../../include/qqq_amd_step.h"
 #include "qqq_spec.hip.h"
@@ -98,11 +98,11 @@
 #include "qqq_penalty.hip.h"
 #include "../../include/qqq_amd_penalty.h"
 #include "qqq_stop.hip.h"
-#include "../../include/serving/stop/qqq_amd_stop.h"
+#include "../../include/qqq_amd_stop.h"
 #include "qqq_guided.hip.h"
-#include "../../include/ext/guided/qqq_amd_guided.h"
+#include "../../include/qqq_amd_guided.h"
 #include "qqq_lora.hip.h"
-#include "../../include/ext/adapters/lora/qqq_amd_lora.h"
+#include "../../include/qqq_amd_lora.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -1371,7 +1371,7 @@ extern "C" int qqq_token_logprobs(const void* logits, int ld, const void* target
   return QQQ_OK;
 }
 
-// ---- the fused top-k log-probability kernel (include/serving/qqq_amd_logprobs.h; kernels in qqq_logprobs.hip.h): one launch, one workgroup
+// ---- the fused top-k log-probability kernel (include/qqq_amd_logprobs.h; kernels in qqq_logprobs.hip.h): one launch, one workgroup
 // per row, no workspace.  The checks the two entries share: shape, k, and the top-k pair.
 static int topk_logprobs_check(const char* name, const void* logits, int ld, const void* top_ids, const void* top_logprobs, int k, int rows,
                                int vocab) {
@@ -1644,7 +1644,7 @@ extern "C" int qqq_penalize_logits(void* logits, int ld, const void* ids, const 
   return QQQ_OK;
 }
 
-// ---- stop sequences, stop token ids and the minimum length (include/serving/stop/qqq_amd_stop.h; kernels in qqq_stop.hip.h): one launch
+// ---- stop sequences, stop token ids and the minimum length (include/qqq_amd_stop.h; kernels in qqq_stop.hip.h): one launch
 // each, one wave per logits row / per row, no workspace.
 extern "C" int qqq_ban_tokens(void* logits, int ld, const void* n_out, int base, const void* min_new, const void* eos, const void* ban_ids,
                               int n_ban, int group, int rows, int vocab, int dev, void* stream) {
@@ -1745,7 +1745,7 @@ extern "C" int qqq_stop_check(const void* tokens, int token_bytes, int tok_strid
   return QQQ_OK;
 }
 
-// ---- guided decoding (include/ext/guided/qqq_amd_guided.h; kernels in qqq_guided.hip.h): one launch each, a row's columns over several
+// ---- guided decoding (include/qqq_amd_guided.h; kernels in qqq_guided.hip.h): one launch each, a row's columns over several
 // workgroups / one wave per row, no workspace.
 extern "C" int qqq_fsm_mask(void* logits, int ld, const void* state, const void* eos, const void* remaining, const void* offsets,
                             const void* tokens, const void* accept, int n_states, int n_edges, int rows, int vocab, int dev, void* stream) {
@@ -1825,7 +1825,7 @@ extern "C" int qqq_fsm_advance(const void* out, int out_stride, const void* n_ou
   return QQQ_OK;
 }
 
-// ---- batched LoRA (include/ext/adapters/lora/qqq_amd_lora.h; kernel in qqq_lora.hip.h): one launch, a workgroup per 16 tokens and column
+// ---- batched LoRA (include/qqq_amd_lora.h; kernel in qqq_lora.hip.h): one launch, a workgroup per 16 tokens and column
 // chunk, no workspace.
 extern "C" int qqq_lora_add(void* y, int ldy, const void* xq, const void* s1, const void* A, size_t a_stride, const void* B, size_t b_stride,
                             const void* scale, const void* slot, const void* part_cols_host, int P, int T, int N, int K, int R, int S, int dev,
@@ -1894,7 +1894,7 @@ extern "C" int qqq_lora_add(void* y, int ldy, const void* xq, const void* s1, co
   return QQQ_OK;
 }
 
-// ---- beam search (include/search/qqq_amd_beam.h; kernels in qqq_beam.hip.h): the step behind a pass's logits -- a workgroup per row into the
+// ---- beam search (include/qqq_amd_beam.h; kernels in qqq_beam.hip.h): the step behind a pass's logits -- a workgroup per row into the
 // workspace, then a wave per prompt that merges -- and the block copies of a cache reorder.
 extern "C" size_t qqq_beam_step_workspace_bytes(int rows, int num_beams) {
   if (num_beams < 1 || num_beams > BEAM_MAX || rows < 1 || rows > 65535 || rows % num_beams != 0) return 0;

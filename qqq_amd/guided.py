@@ -1,5 +1,5 @@
-"""Guided decoding: a deterministic automaton over token ids that says which tokens a completion may draw next (include/ext/guided/
-qqq_amd_guided.h).  Pure Python and numpy; ops.fsm_mask / ops.fsm_advance walk the same arrays on the device, GuidedRequest
+"""Guided decoding: a deterministic automaton over token ids that says which tokens a completion may draw next
+(include/qqq_amd_guided.h).  Pure Python and numpy; ops.fsm_mask / ops.fsm_advance walk the same arrays on the device, GuidedRequest
 (qqq_amd/request.py) on the host.
 
     TokenFSM(offsets, tokens, next, accept, start)   the automaton in CSR form, validated
@@ -102,7 +102,7 @@ class TokenFSM:
         return int(self.next[at]) if at < hi and self.tokens[at] == t else NO_EDGE
 
     def walk(self, tokens: Sequence[int], eos: Optional[int] = None, start: Optional[int] = None) -> int:
-        """the state behind `tokens` from `start` by the device's rules (include/ext/guided/qqq_amd_guided.h): a token without an edge that
+        """the state behind `tokens` from `start` by the device's rules (include/qqq_amd_guided.h): a token without an edge that
         is `eos` in an accepting state leaves the state as it is, any other gives NO_EDGE"""
         s = self.start if start is None else start
         for t in tokens:

@@ -1,5 +1,5 @@
 """Multi-LoRA serving over the quantised base: the int4 weights are shared, every tenant brings fp16 low-rank matrices, and the adapters of
-one batch are mixed per token by ops.lora_add (include/ext/adapters/lora/qqq_amd_lora.h) on the output of every targeted projection.
+one batch are mixed per token by ops.lora_add (include/qqq_amd_lora.h) on the output of every targeted projection.
 
     LoraBank   the stacked adapters of a model: `slots` adapter slots of rank `rank`, per layer the A / B of four projection groups
                (q|k|v, o, gate|up, down) at addresses that stay fixed for the bank's life, so a captured graph survives load() / unload()

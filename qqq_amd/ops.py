@@ -1808,7 +1808,7 @@ def penalize_logits(logits: torch.Tensor, ids: torch.Tensor, pos: torch.Tensor, 
     return logits
 
 
-# ---- the fused top-k log-probability kernel (include/serving/qqq_amd_logprobs.h): the log-probability and rank of a token and the k most
+# ---- the fused top-k log-probability kernel (include/qqq_amd_logprobs.h): the log-probability and rank of a token and the k most
 # probable tokens of every logits row, one launch; behind a sampler, on the logits it drew from
 
 def _topk_k_check(op, k, vocab):
@@ -1872,7 +1872,7 @@ def topk_logprobs(logits: torch.Tensor, tokens: Optional[torch.Tensor] = None, k
     -inf); rank is 1 + the number of logits above the token's (0 for a token outside [0, vocab)); the top-k entries are ordered by logit
     descending, then index ascending, with ties at the cut resolved exactly, and top_logprobs[r, i] is the value logprob has for
     top_ids[r, i]: entry 0 is sample_tokens' greedy token.  0 <= k <= min(32, vocab).  The exact semantics of a row are stated in
-    include/serving/qqq_amd_logprobs.h.  Nothing is read on the host and the launch size depends on (rows, vocab, k) alone, so a captured
+    include/qqq_amd_logprobs.h.  Nothing is read on the host and the launch size depends on (rows, vocab, k) alone, so a captured
     graph replays with other contents.  A view whose rows are `vocab` columns of a wider, 16-byte aligned fp16 matrix (row stride a
     multiple of 8) is read in place; its other columns are never touched."""
     if not isinstance(logits, torch.Tensor) or (tokens is not None and not isinstance(tokens, torch.Tensor)) or logits.dim() != 2:
@@ -1951,7 +1951,7 @@ def topk_logprobs_step(logits: torch.Tensor, out: torch.Tensor, n_out: torch.Ten
     logprob, rank             f32 / int32 [rows, cap];  top_ids, top_logprobs  int32 / f32 [rows, cap, k], or both None for k = 0
     A row with n_rec[r] < n_out[r] and n_rec[r] < cap scores out[r, n_rec[r]] against logits[r] into record (r, n_rec[r]) and counts it;
     every other row -- idle, nothing emitted in this step, no room -- writes nothing.  At most one record per row and call.  The exact
-    semantics are stated in include/serving/qqq_amd_logprobs.h.  Nothing is read on the host and the launch size depends on the shapes
+    semantics are stated in include/qqq_amd_logprobs.h.  Nothing is read on the host and the launch size depends on the shapes
     alone, so a decode step with this call behind sample_advance replays from a captured graph."""
     if not isinstance(logits, torch.Tensor) or not isinstance(logprob, torch.Tensor) or logits.dim() != 2 or logprob.dim() != 2:
         raise RuntimeError("topk_logprobs_step: logits must be an fp16 [rows, vocab] tensor and logprob an f32 [rows, cap] tensor")
@@ -1966,7 +1966,7 @@ def topk_logprobs_step(logits: torch.Tensor, out: torch.Tensor, n_out: torch.Ten
     return _topk_logprobs_step_impl(*args)
 
 
-# ---- stop sequences, stop token ids and the minimum length (include/serving/stop/qqq_amd_stop.h): the ban in front of a sampler, the
+# ---- stop sequences, stop token ids and the minimum length (include/qqq_amd_stop.h): the ban in front of a sampler, the
 # check behind a decode loop's step
 
 def _rows_i32_check(op, rows, named):
@@ -2036,7 +2036,7 @@ def ban_tokens(logits: torch.Tensor, n_out: torch.Tensor, min_new: torch.Tensor,
     ban_ids      int32 [at most 32] or None: the stop token ids, shared by the rows
     Logits row r * G + j (G = logits rows / rows, at most 16) is the one the completion's token of index n_out[r] + base + j is drawn from:
     if that index is below min_new[r], the row's eos and every ban id become -inf there.  Ids outside [0, vocab) are ignored; every other
-    entry keeps its bits.  The exact semantics are stated in include/serving/stop/qqq_amd_stop.h.  Nothing is read on the host and the
+    entry keeps its bits.  The exact semantics are stated in include/qqq_amd_stop.h.  Nothing is read on the host and the
     launch size depends on the shapes alone, so a step with this call in it replays from a captured graph.  The logits are never
     copied: unit column stride and a row stride >= vocab, or it raises."""
     if not isinstance(logits, torch.Tensor) or not isinstance(n_out, torch.Tensor) or logits.dim() != 2 or n_out.dim() != 1:
@@ -2136,7 +2136,7 @@ def stop_check(tokens: torch.Tensor, base: torch.Tensor, first: Optional[torch.T
     stays; they go before a sequence that ends in the same token) or, from min_new[r] on, in a stop sequence (the completion is cut in
     front of it) retires the row: ids 0, pos / slots / start -1, remaining 0.
     Then n_seen[r] = n_out[r] + 1.  A row with nothing new writes nothing.  The exact semantics are stated in
-    include/serving/stop/qqq_amd_stop.h.  Nothing is read on the host and the launch size depends on the shapes alone, so a decode
+    include/qqq_amd_stop.h.  Nothing is read on the host and the launch size depends on the shapes alone, so a decode
     step with this call in it replays from a captured graph."""
     if not isinstance(tokens, torch.Tensor) or not isinstance(ids, torch.Tensor) or tokens.dim() != 2:
         raise RuntimeError("stop_check: tokens must be an int32 or int64 [rows, stride] tensor and ids an int64 [rows] or [rows, group] tensor")
@@ -2148,7 +2148,7 @@ def stop_check(tokens: torch.Tensor, base: torch.Tensor, first: Optional[torch.T
     return _stop_check_impl(*args)
 
 
-# ---- beam search (include/search/qqq_amd_beam.h): the step behind a pass's logits, and the block copies of a cache reorder
+# ---- beam search (include/qqq_amd_beam.h): the step behind a pass's logits, and the block copies of a cache reorder
 
 class BeamStep(NamedTuple):
     """What beam_step returns.  cand_* and next_parent are views of `packed` (int32, the f32 arrays bit for bit), so that one copy of
@@ -2248,7 +2248,7 @@ def beam_step(logits: torch.Tensor, cum: torch.Tensor, live: torch.Tensor, num_b
     a prompt's candidates are ordered by score descending (NaN and -inf last), then b, then i, and the first 2B are cand_score,
     cand_logprob, cand_parent, cand_token [P, 2B].  The first B of them whose token is not eos become the next beams: next_ids int64 (the
     next pass's input, on the device), next_parent int32, next_cum f32, next_live int32, each [P * B].  A prompt without a live row writes
-    parent = token = -1, score -inf and stays dead.  The exact semantics are stated in include/search/qqq_amd_beam.h.  Nothing is read on
+    parent = token = -1, score -inf and stays dead.  The exact semantics are stated in include/qqq_amd_beam.h.  Nothing is read on
     the host and the launch size depends on the shapes alone, so a captured graph replays with other contents.  A view whose rows are
     `vocab` columns of a wider, 16-byte aligned fp16 matrix (row stride a multiple of 8) is read in place."""
     if not isinstance(logits, torch.Tensor) or not isinstance(cum, torch.Tensor) or not isinstance(live, torch.Tensor) or logits.dim() != 2:
@@ -2304,7 +2304,7 @@ def copy_blocks(pools: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, block
                  block_bytes bytes (a multiple of 16), 16-byte aligned.  The caller keeps the pools alive; the op sees addresses only.
     src, dst     int32 [n] on the device; the dst entries are distinct and none equals a src entry, one src may feed several dst; an id
                  outside [0, num_blocks) copies nothing.  n = 0 is a no-op.
-    Nothing is read on the host.  The exact semantics are stated in include/search/qqq_amd_beam.h."""
+    Nothing is read on the host.  The exact semantics are stated in include/qqq_amd_beam.h."""
     if not all(isinstance(t, torch.Tensor) for t in (pools, src, dst)):
         raise RuntimeError("copy_blocks: pools must be an int64 [n_pools] tensor, src and dst int32 [n] tensors")
     args = (pools, src, dst, int(block_bytes), int(num_blocks))
@@ -2313,7 +2313,7 @@ def copy_blocks(pools: torch.Tensor, src: torch.Tensor, dst: torch.Tensor, block
     return _copy_blocks_impl(*args)
 
 
-# ---- guided decoding (include/ext/guided/qqq_amd_guided.h): the mask in front of a sampler, the advance behind a loop's step
+# ---- guided decoding (include/qqq_amd_guided.h): the mask in front of a sampler, the advance behind a loop's step
 
 def _fsm_tables_check(op, fsm_tensors):
     # the automaton's four CSR arrays -> (n_states, n_edges)
@@ -2381,7 +2381,7 @@ def fsm_mask(logits: torch.Tensor, state: torch.Tensor, fsm_tensors, eos: Option
     eos          int32 [rows] or None: the rows' eos ids (-1: none), allowed in an accepting state
     remaining    int32 [rows] or None: a decode loop's budgets; a row with 0 is idle and untouched
     Every column of [0, vocab) that is neither a token of the row's state nor its allowed eos becomes -inf; an allowed column keeps its
-    bits, and the logits are never read.  The exact semantics are stated in include/ext/guided/qqq_amd_guided.h.  Nothing is read on the
+    bits, and the logits are never read.  The exact semantics are stated in include/qqq_amd_guided.h.  Nothing is read on the
     host and the launch size depends on the shapes alone, so a step with this call in it replays from a captured graph.  The logits are
     never copied: unit column stride and a row stride >= vocab, or it raises."""
     if not isinstance(logits, torch.Tensor) or not isinstance(state, torch.Tensor) or logits.dim() != 2 or state.dim() != 1:
@@ -2452,7 +2452,7 @@ def fsm_advance(out: torch.Tensor, n_out: torch.Tensor, n_fsm: torch.Tensor, sta
     A token with an edge moves the state to the edge's target, and a terminal target (no edges) retires the row: ids 0, pos / slots -1,
     remaining 0.  The row's eos without an edge in an accepting state leaves the state (the sampler retired the row).  Any other token
     sets the state to -2 and retires the row.  A state outside [0, S) stays.  Then n_fsm[r] = n_out[r]; a row with nothing new writes
-    nothing.  The exact semantics are stated in include/ext/guided/qqq_amd_guided.h.  Nothing is read on the host and the launch size
+    nothing.  The exact semantics are stated in include/qqq_amd_guided.h.  Nothing is read on the host and the launch size
     depends on the shapes alone, so a decode step with this call in it replays from a captured graph."""
     if not isinstance(out, torch.Tensor) or not isinstance(state, torch.Tensor) or out.dim() != 2:
         raise RuntimeError("fsm_advance: out must be an int64 [rows, out_stride] tensor and state an int32 [rows] tensor")
@@ -2463,7 +2463,7 @@ def fsm_advance(out: torch.Tensor, n_out: torch.Tensor, n_fsm: torch.Tensor, sta
     return _fsm_advance_impl(*args)
 
 
-# ---- batched LoRA (include/ext/adapters/lora/qqq_amd_lora.h): low-rank fp16 adapters beside the W4A8 GEMM, every token's adapter on the device
+# ---- batched LoRA (include/qqq_amd_lora.h): low-rank fp16 adapters beside the W4A8 GEMM, every token's adapter on the device
 
 def _lora_add_check(y, xq, s1, A, B, scale, slot, part_cols):
     # dtypes, shapes and strides -> (T, N, K, R, S, P); R's list, the offsets' rules and the alignment are the library's to refuse
@@ -2530,7 +2530,7 @@ def lora_add(y: torch.Tensor, xq: torch.Tensor, s1: torch.Tensor, A: torch.Tenso
                  uses the rows p * R ... (p + 1) * R - 1 of A (q|k|v, gate|up).  None: one part, [0, N].
     For slot[t] = a >= 0:  y[t, n] <- fp16(float(y[t, n]) + scale[a] * sum_r B[a, n, r] * (s1[t] * sum_k A[a, p * R + r, k] * xq[t, k])),
     every product and sum in f32, one rounding.  A row's bits depend on that row and its slot's matrices alone, and a call with P parts
-    gives the bits of P calls on the column slices.  The exact semantics are stated in include/ext/adapters/lora/qqq_amd_lora.h.  Nothing
+    gives the bits of P calls on the column slices.  The exact semantics are stated in include/qqq_amd_lora.h.  Nothing
     is read on the host and the launch size depends on the shapes alone, so a step with this call in it replays from a captured graph."""
     ts = (y, xq, s1, A, B, scale, slot)
     if not all(isinstance(t, torch.Tensor) for t in ts):

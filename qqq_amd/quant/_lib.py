@@ -1,5 +1,5 @@
-"""ctypes binding of libqqq_amd_quant.so, bound from the prototypes of qqq_amd/quant/include/qqq_amd_quant.h, qqq_amd_rotate.h and
-qqq_amd_gptq_order.h (qqq_amd/_abi.py).  No fallback: if the library is missing, every entry point raises."""
+"""ctypes binding of libqqq_amd_quant.so, bound from the prototypes of every header in qqq_amd/quant/include/ (build.quant_headers(),
+qqq_amd/_abi.py).  No fallback: if the library is missing, every entry point raises."""
 from __future__ import annotations
 
 import ctypes
@@ -10,8 +10,6 @@ from .. import build as _build
 
 _lib = None
 HEADER = _build.QUANT_HEADER
-ROTATE_HEADER = _build.ROTATE_HEADER
-ORDER_HEADER = _build.ORDER_HEADER
 ABI_VERSION = _abi.define(HEADER, "QQQ_AMD_QUANT_ABI_VERSION")
 ERR_ARG = _abi.define(_build.header("qqq_amd.h"), "QQQ_ERR_ARG")
 
@@ -31,9 +29,8 @@ def lib():
     L = ctypes.CDLL(path)
     if L.qqq_quant_abi_version() != ABI_VERSION:
         raise RuntimeError("libqqq_amd_quant.so ABI version mismatch; rebuild")
-    _abi.bind(L, HEADER)
-    _abi.bind(L, ROTATE_HEADER)
-    _abi.bind(L, ORDER_HEADER)
+    for hdr in _build.quant_headers():
+        _abi.bind(L, hdr)
     _lib = L
     return L
 

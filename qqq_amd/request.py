@@ -69,7 +69,7 @@ def stop_arguments(name: str, vocab: int, stop, stop_token_ids, min_new_tokens):
 
 
 def stop_match(completion: Sequence[int], stops: Sequence[Sequence[int]]) -> int:
-    """the length of the first stop sequence (lowest index) the completion ends in, 0 for none: include/serving/stop/qqq_amd_stop.h, rule 2"""
+    """the length of the first stop sequence (lowest index) the completion ends in, 0 for none: include/qqq_amd_stop.h, rule 2"""
     for s in stops:
         if len(s) <= len(completion) and list(completion[len(completion) - len(s):]) == list(s):
             return len(s)
@@ -265,8 +265,8 @@ class GuidedRequest(Request):
     """A Request whose completions follow token automata (qqq_amd/guided.py): `fsm` is one TokenFSM for every prompt or a sequence with one
     entry per prompt (None: that prompt is unconstrained).  begin() merges them and gives every completion its start state; `state` holds
     one host state per completion: -1 for no automaton, -2 once a token outside the automaton was drawn.  sample() masks the rows by
-    those states (ops.fsm_mask, behind the penalties and the ban), receive() steps them by the rules of include/ext/guided/
-    qqq_amd_guided.h and ends a completion that reaches a terminal state; a loop writes the states its rows ended in back into `state`."""
+    those states (ops.fsm_mask, behind the penalties and the ban), receive() steps them by the rules of
+    include/qqq_amd_guided.h and ends a completion that reaches a terminal state; a loop writes the states its rows ended in back into `state`."""
 
     def __init__(self, fsm, *args, **kw):
         super().__init__(*args, **kw)

@@ -71,7 +71,7 @@ class DecodeLoop:
                 [rows, max_len]) and `lp_top_ids` / `lp_top` (int32 / f32 [rows, max_len, k]), and its step runs ops.topk_logprobs_step
                 behind ops.sample_advance, inside the captured graph: every emitted token's log-probability, rank and k most probable
                 alternatives, from the logits row it was drawn from.  generate() then returns (tokens, records).  None: none of that exists.
-    stops       True: the loop owns what ops.ban_tokens and ops.stop_check take (include/serving/stop/qqq_amd_stop.h) -- min_new, n_seen,
+    stops       True: the loop owns what ops.ban_tokens and ops.stop_check take (include/qqq_amd_stop.h) -- min_new, n_seen,
                 n_trim, stop_hit, stop_base and first (int32 [rows]), the table stop_ids / stop_len (int32 [32, 32] / [32]) and the stop
                 token ids ban_ids (int32 [32], -1 = unused) -- and its step runs the ban between the penalties and the sampler and the
                 check behind the sampler (and the records), inside the captured graph; generate() then takes stop, stop_token_ids and

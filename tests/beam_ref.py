@@ -1,4 +1,4 @@
-"""Numpy reference of the beam-search step (include/search/qqq_amd_beam.h) and of a whole search, written from the definition.
+"""Numpy reference of the beam-search step (include/qqq_amd_beam.h) and of a whole search, written from the definition.
 
     merge(ids, lps, cum, live, B, eos)      rules 2 - 5 on the rows' candidates: f32 arithmetic, exact.  With ids / lps from
                                             ops.topk_logprobs (rule 1: "that op's top_logprobs to the bit") it is what ops.beam_step must

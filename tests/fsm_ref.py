@@ -1,4 +1,4 @@
-"""numpy reference of the two guided-decoding ops, written from the rules in include/ext/guided/qqq_amd_guided.h: integer and bit work, so a
+"""numpy reference of the two guided-decoding ops, written from the rules in include/qqq_amd_guided.h: integer and bit work, so a
 test compares with equality.  Logits are uint16 bit patterns of fp16 values; every array is updated in place."""
 import numpy as np
 

@@ -1,4 +1,4 @@
-"""Float64 numpy reference of the top-k log-probability kernel's per-row semantics (include/serving/qqq_amd_logprobs.h), written from the
+"""Float64 numpy reference of the top-k log-probability kernel's per-row semantics (include/qqq_amd_logprobs.h), written from the
 definition: the values are tests/score_ref.py's, the order is a sort on (-value, index) with -0 equal to +0 and NaN and -inf last."""
 import numpy as np
 

@@ -1,4 +1,4 @@
-"""The f64 reference of ops.lora_add (include/ext/adapters/lora/qqq_amd_lora.h), the error bound an f32 implementation may use up, and the
+"""The f64 reference of ops.lora_add (include/qqq_amd_lora.h), the error bound an f32 implementation may use up, and the
 cases tests/test_gpu_lora.py runs (tests/test_lora_ref_cpu.py holds the reference and the bound against them without a GPU).
 
     y[t, n] <- fp16( y[t, n] + scale[a] * sum_r B[a, n, r] * ( s1[t] * sum_k A[a, p * R + r, k] * xq[t, k] ) )      a = slot[t] >= 0

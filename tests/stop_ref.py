@@ -1,4 +1,4 @@
-"""Plain-Python restatement of the per-row rules of qqq_ban_tokens and qqq_stop_check (include/serving/stop/qqq_amd_stop.h), written from
+"""Plain-Python restatement of the per-row rules of qqq_ban_tokens and qqq_stop_check (include/qqq_amd_stop.h), written from
 the header, on numpy arrays that are updated in place like the device's.  No vectorisation: one row, one end, one sequence at a time."""
 import numpy as np
 

@@ -145,9 +145,32 @@ def test_headers_are_found_by_listing_include():
     from qqq_amd import build
 
     inc = os.path.join(ROOT, "include")
-    assert len(_headers()) == 15 and "qqq_amd.h" in OPERATOR_HEADERS
+    assert len(_headers()) == 20 and len(OPERATOR_HEADERS) == 19 and "qqq_amd.h" in OPERATOR_HEADERS
     assert build.headers() == [os.path.join(inc, h) for h in _headers()]
     assert build.operator_headers() == [os.path.join(inc, h) for h in OPERATOR_HEADERS]
+
+
+def test_the_include_directories_are_flat():
+    """headers() and quant_headers() list one directory each: a header in a subdirectory would go unbound and unwatched"""
+    from qqq_amd import build
+
+    dirs = (os.path.join(ROOT, "include"), os.path.join(ROOT, "qqq_amd", "quant", "include"))
+    assert dirs == (build.INCLUDE, build.QUANT_INCLUDE)
+    for inc in dirs:
+        assert [d for d in os.listdir(inc) if os.path.isdir(os.path.join(inc, d))] == [], inc
+
+
+@pytest.mark.parametrize("lister", ["operator_headers", "quant_headers"])
+def test_no_function_is_declared_in_two_headers_of_one_library(lister):
+    """every header of a library is bound onto the same handle, in listing order: a name declared twice would be bound twice"""
+    from qqq_amd import _abi, build
+
+    seen = {}
+    for h in getattr(build, lister)():
+        for name in _abi.prototypes(h):
+            assert name not in seen, (name, seen[name], h)
+            seen[name] = h
+    assert seen
 
 
 @pytest.mark.parametrize("header", _headers())

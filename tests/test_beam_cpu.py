@@ -1,4 +1,4 @@
-"""Beam search without a GPU: where the header sits and how it is bound, the C-ABI's argument checks before any launch, the kernels'
+"""Beam search without a GPU: what the header declares and how it is bound, the C-ABI's argument checks before any launch, the kernels'
 resources in the gfx950 code object, the ops' CPU refusal and fake implementations, tests/beam_ref.py on hand-made cases,
 PagedKVCache.reorder on CPU pools, and QuantLlamaForCausalLM.beam_search over a stub model with ops.beam_step replaced by the reference."""
 import ctypes
@@ -12,7 +12,7 @@ import torch
 import beam_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "search", "qqq_amd_beam.h")
+HEADER = os.path.join(ROOT, "include", "qqq_amd_beam.h")
 ERR_ARG = 17
 
 
@@ -26,15 +26,9 @@ def L():
 
 # ---- the header and its binding
 
-def test_the_header_is_found_by_the_fourth_lister_and_the_other_three_are_as_they_were(L):
+def test_the_header_declares_the_three_entries(L):
     from qqq_amd import _abi, _lib, build
 
-    inc = os.path.join(ROOT, "include")
-    assert build.feature_headers() == [HEADER]
-    assert len(build.headers()) == 15 and HEADER not in build.headers()
-    assert build.serving_headers() == [os.path.join(inc, "serving", "qqq_amd_logprobs.h")]
-    assert build.extension_headers() == [os.path.join(inc, "serving", "stop", "qqq_amd_stop.h")]
-    assert build.bound_headers() == build.operator_headers() + build.serving_headers() + build.extension_headers() + [HEADER]
     assert _lib.ABI_VERSION == 4 and L.qqq_amd_abi_version() == 4
     protos = _abi.prototypes(HEADER)
     assert set(protos) == {"qqq_beam_step", "qqq_beam_step_workspace_bytes", "qqq_copy_blocks"}
@@ -43,32 +37,12 @@ def test_the_header_is_found_by_the_fourth_lister_and_the_other_three_are_as_the
         assert fn.restype is {"int": ctypes.c_int, "size_t": ctypes.c_size_t}[ret] and len(fn.argtypes) == len(params), name
         assert all(p.rsplit(" ", 1)[0] in ("const void*", "void*", "int", "size_t") for p in params), params
     unit = open(build.SRC).read()
-    assert '#include "qqq_beam.hip.h"' in unit and '#include "../../include/search/qqq_amd_beam.h"' in unit
+    assert '#include "qqq_beam.hip.h"' in unit and '#include "../../include/qqq_amd_beam.h"' in unit
     assert unit.index('#include "qqq_logprobs.hip.h"') < unit.index('#include "qqq_beam.hip.h"')
     kernels = open(os.path.join(os.path.dirname(build.SRC), "qqq_beam.hip.h")).read()
     assert "qqq_logprobs_row(" in kernels and "qqq_sample_select" not in kernels  # the row body is called, not copied
-    main = _abi.source(os.path.join(inc, "qqq_amd.h"))
+    main = _abi.source(build.header("qqq_amd.h"))
     assert "qqq_beam" not in main and "qqq_copy_blocks" not in main
-
-
-def test_a_feature_header_in_any_new_directory_is_listed(tmp_path, monkeypatch):
-    from qqq_amd import build
-
-    for d, f in (("search", "a.h"), ("zeta", "b.h"), ("serving", "c.h"), ("zeta", "notes.txt")):
-        os.makedirs(tmp_path / d, exist_ok=True)
-        (tmp_path / d / f).write_text("")
-    (tmp_path / "top.h").write_text("")
-    monkeypatch.setattr(build, "INCLUDE", str(tmp_path))
-    assert build.feature_headers() == [str(tmp_path / "search" / "a.h"), str(tmp_path / "zeta" / "b.h")]
-
-
-def test_a_newer_feature_header_rebuilds_the_operator_library(monkeypatch, L):
-    from qqq_amd import build
-
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 1.0)
-    assert not build.needs_build()
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 3.0 if p == HEADER else 1.0)
-    assert build.needs_build()
 
 
 # ---- the C ABI: fake device addresses with the alignment the entries ask for; every call below must fail in the checks, before any launch

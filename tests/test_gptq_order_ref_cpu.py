@@ -2,7 +2,6 @@
 the reference's own GPTQ.fasterquant(actorder, static_groups) (tests/golden/gptq_order_small.npz, gen_gptq_order_golden.py), what the
 fixture exercises, the binding of the two entries from a header of their own, and the refusals of the entries and the Python layer."""
 import ctypes
-import inspect
 import os
 
 import numpy as np
@@ -103,16 +102,16 @@ def test_library_binds_the_two_entries_from_a_header_of_their_own():
     from qqq_amd.quant import _lib as qlib
 
     L = qlib.lib()
-    protos = _abi.prototypes(build.ORDER_HEADER)
+    header, rotate = (os.path.join(build.QUANT_INCLUDE, h) for h in ("qqq_amd_gptq_order.h", "qqq_amd_rotate.h"))
+    protos = _abi.prototypes(header)
     assert set(protos) == {"qqq_gptq_group_scales", "qqq_gptq_block_cols"}
     for name, (_, params) in protos.items():
         assert len(getattr(L, name).argtypes or []) == len(params), name
         for p in params:
             assert _abi.ctype_of(p) in (ctypes.c_void_p, ctypes.c_int), p
-    assert os.path.dirname(build.ORDER_HEADER) == os.path.dirname(build.QUANT_HEADER)
-    assert not set(protos) & set(_abi.prototypes(build.QUANT_HEADER)) and not set(protos) & set(_abi.prototypes(build.ROTATE_HEADER))
+    assert header in build.quant_headers() and os.path.dirname(header) == os.path.dirname(build.QUANT_HEADER)
+    assert not set(protos) & set(_abi.prototypes(build.QUANT_HEADER)) and not set(protos) & set(_abi.prototypes(rotate))
     assert L.qqq_quant_abi_version() == qlib.ABI_VERSION == 1
-    assert "ORDER_HEADER" in inspect.getsource(build.build_quant)
 
 
 def _refused(fn, *args):

@@ -113,15 +113,43 @@ def test_library_loads_and_binds_from_its_header_beside_the_operator():
         for p in params:  # only the parameter types the operator's headers already use
             assert _abi.ctype_of(p) in (ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t), p
     assert L.qqq_quant_abi_version() == qlib.ABI_VERSION == 1
-    # the operator library and its listers do not know the quantiser
+    # the operator library and its lister do not know the quantiser
     assert _lib.lib().qqq_amd_abi_version() == _lib.ABI_VERSION == 4
     assert not hasattr(_lib.lib(), "qqq_gptq_block")
     inc = os.path.join(ROOT, "include") + os.sep
-    every = build.bound_headers() + build.nested_headers() + build.deep_headers() + build.headers()
-    assert every and all(h.startswith(inc) for h in every) and not build.QUANT_HEADER.startswith(inc)
+    every = build.headers()
+    assert every and all(h.startswith(inc) for h in every)
+    assert build.QUANT_HEADER in build.quant_headers() and not any(h.startswith(inc) for h in build.quant_headers())
     found = sorted(os.path.join(top, f) for top, _, fs in os.walk(inc) for f in fs if f.endswith(".h"))
-    assert sorted(set(every) | {build.header("qqq_amd_dev.h")}) == found
+    assert every == found
     assert os.path.basename(build.QUANT_LIB) == "libqqq_amd_quant.so" and build.LIB != build.QUANT_LIB
+
+
+def _quant_headers():
+    inc = os.path.join(ROOT, "qqq_amd", "quant", "include")
+    return sorted(f for f in os.listdir(inc) if f.endswith(".h"))
+
+
+def test_quant_headers_are_found_by_listing_the_quant_include_directory():
+    from qqq_amd import build
+
+    assert _quant_headers() == ["qqq_amd_gptq_order.h", "qqq_amd_quant.h", "qqq_amd_rotate.h"]
+    assert build.quant_headers() == [os.path.join(ROOT, "qqq_amd", "quant", "include", h) for h in _quant_headers()]
+
+
+@pytest.mark.parametrize("header", _quant_headers())
+def test_a_newer_header_rebuilds_the_quantiser_library(monkeypatch, header):
+    """build_quant returns early when the library is the newest file and compiles when this one header is newer (nothing is compiled here)"""
+    from qqq_amd import build
+
+    build.build_quant()  # the library exists
+    newer = os.path.join(ROOT, "qqq_amd", "quant", "include", header)
+    compiled = []
+    monkeypatch.setattr(build, "_compile", lambda src, out, verbose, flags=(): compiled.append((src, out, tuple(flags))) or out)
+    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.QUANT_LIB else 1.0)
+    assert build.build_quant() == build.QUANT_LIB and not compiled
+    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.QUANT_LIB else 3.0 if p == newer else 1.0)
+    assert build.build_quant() == build.QUANT_LIB and compiled == [(build.QUANT_SRC, build.QUANT_LIB, build.QUANT_FLAGS)]
 
 
 def _refused(fn, *args):

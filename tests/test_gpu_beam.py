@@ -1,6 +1,6 @@
 """ops.beam_step and ops.copy_blocks on the GPU.
 
-beam_step against tests/beam_ref.py, bit for bit: rule 1 of include/search/qqq_amd_beam.h defines a row's candidates as ops.topk_logprobs'
+beam_step against tests/beam_ref.py, bit for bit: rule 1 of include/qqq_amd_beam.h defines a row's candidates as ops.topk_logprobs'
 (ids exactly, values to the bit), so the reference merge runs on that op's output for the same logits -- f32 arithmetic that numpy repeats
 exactly -- and every output of beam_step is compared as a bit pattern.  The candidates' ids are checked against the float64 reference of
 the order as well.  copy_blocks byte for byte against torch indexing."""

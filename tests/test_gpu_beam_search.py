@@ -1,6 +1,6 @@
 """QuantLlamaForCausalLM.beam_search on the GPU, on the two-layer model of tests/test_gpu_model.py: token for token, and bit for bit in
 logprob, against a reference search written here.  The reference drives the same model's forward over the same rows in the same order,
-takes every row's candidates from ops.topk_logprobs (rule 1 of include/search/qqq_amd_beam.h), selects on the CPU with
+takes every row's candidates from ops.topk_logprobs (rule 1 of include/qqq_amd_beam.h), selects on the CPU with
 tests/beam_ref.py's merge and keeps the hypotheses with its Held, and manages the cache with fork / free alone."""
 import numpy as np
 import pytest

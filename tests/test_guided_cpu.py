@@ -1,4 +1,4 @@
-"""Guided decoding without a GPU: where the nested header sits and what it declares, the two entries' argument checks (before any launch),
+"""Guided decoding without a GPU: what the header declares, the two entries' argument checks (before any launch),
 TokenFSM and its builders, tests/fsm_ref.py against TokenFSM on random automata, the kernels' code-object facts, the ops' refusals and fake
 implementations, and generate_guided / GuidedDecodeLoop over the stub model of tests/test_step_cpu.py with fsm_ref standing in for the ops."""
 import ctypes
@@ -17,7 +17,7 @@ from hypothesis import strategies as st
 import fsm_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "ext", "guided", "qqq_amd_guided.h")
+HEADER = os.path.join(ROOT, "include", "qqq_amd_guided.h")
 ERR_ARG = 17
 
 
@@ -29,35 +29,7 @@ def L():
     return _lib.lib()
 
 
-# ---- the lister, the header, the binding
-
-def test_the_nested_lister_finds_the_one_header_and_the_four_others_stay(tmp_path, monkeypatch):
-    from qqq_amd import build
-
-    inc = build.INCLUDE
-    assert build.nested_headers() == [HEADER]
-    assert len(build.headers()) == 15 and HEADER not in build.bound_headers()
-    assert build.serving_headers() == [os.path.join(inc, "serving", "qqq_amd_logprobs.h")]
-    assert build.extension_headers() == [os.path.join(inc, "serving", "stop", "qqq_amd_stop.h")]
-    assert build.feature_headers() == [os.path.join(inc, "search", "qqq_amd_beam.h")]
-    assert build.bound_headers() == build.operator_headers() + build.serving_headers() + build.extension_headers() + build.feature_headers()
-    # another tree: include/x/y/*.h is found, include/serving/y/*.h and include/x/*.h are not
-    for sub in (("x", "y"), ("serving", "z"), ("x",)):
-        os.makedirs(tmp_path.joinpath(*sub), exist_ok=True)
-        tmp_path.joinpath(*sub, "a.h").write_text("int f(void);\n")
-    tmp_path.joinpath("x", "y", "notes.txt").write_text("")
-    monkeypatch.setattr(build, "INCLUDE", str(tmp_path))
-    assert build.nested_headers() == [str(tmp_path / "x" / "y" / "a.h")]
-
-
-def test_a_newer_nested_header_rebuilds_the_operator_library(monkeypatch, L):
-    from qqq_amd import build
-
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 1.0)
-    assert not build.needs_build()
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 3.0 if p == HEADER else 1.0)
-    assert build.needs_build()
-
+# ---- the header, the binding
 
 def test_the_header_declares_the_two_entries_and_they_are_bound(L):
     from qqq_amd import _abi, _lib, build
@@ -71,7 +43,7 @@ def test_the_header_declares_the_two_entries_and_they_are_bound(L):
         assert ret == "int" and fn.restype is ctypes.c_int and len(fn.argtypes) == len(params), name
         assert all(p.rsplit(" ", 1)[0] in ("const void*", "void*", "int") for p in params), params
     unit = open(build.SRC).read()
-    assert '#include "qqq_guided.hip.h"' in unit and '#include "../../include/ext/guided/qqq_amd_guided.h"' in unit
+    assert '#include "qqq_guided.hip.h"' in unit and '#include "../../include/qqq_amd_guided.h"' in unit
 
 
 # fake device addresses with the alignment the entries ask for: the calls below must fail in the checks, before any launch

@@ -1,4 +1,4 @@
-"""Per-token top-k log-probabilities without a GPU: where the C ABI's serving header sits and what it declares, the two entries' argument
+"""Per-token top-k log-probabilities without a GPU: what the C ABI's header declares, the two entries' argument
 checks (before any launch), the ops' refusals and fake implementations, generate()'s `logprobs` keyword, and the bookkeeping of the
 records on the host path and in DecodeLoop with host stubs for the forward pass, the samplers and the two new ops."""
 import inspect
@@ -12,7 +12,7 @@ import logprobs_ref
 import score_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "serving", "qqq_amd_logprobs.h")
+HEADER = os.path.join(ROOT, "include", "qqq_amd_logprobs.h")
 
 
 @pytest.fixture(scope="module")
@@ -25,11 +25,10 @@ def L():
 
 # ---- the C ABI
 
-def test_the_header_sits_under_serving_and_declares_the_two_entries(L):
+def test_the_header_declares_the_two_entries(L):
     from qqq_amd import _abi, _lib, build
 
-    assert build.serving_headers() == [HEADER] and HEADER not in build.headers() and HEADER not in build.operator_headers()
-    assert len(build.headers()) == 15 and _lib.ABI_VERSION == 4 and L.qqq_amd_abi_version() == 4
+    assert _lib.ABI_VERSION == 4 and L.qqq_amd_abi_version() == 4
     protos = _abi.prototypes(HEADER)
     assert set(protos) == {"qqq_topk_logprobs", "qqq_topk_logprobs_step"}
     assert len(protos["qqq_topk_logprobs"][1]) == 12 and len(protos["qqq_topk_logprobs_step"][1]) == 16
@@ -38,17 +37,8 @@ def test_the_header_sits_under_serving_and_declares_the_two_entries(L):
         assert ret == "int" and fn.restype is __import__("ctypes").c_int and len(fn.argtypes) == len(params), name
         assert all(p.rsplit(" ", 1)[0] in ("const void*", "void*", "int") for p in params), params
     unit = open(build.SRC).read()
-    assert '#include "../../include/serving/qqq_amd_logprobs.h"' in unit  # the compiler holds the definitions against the prototypes
+    assert '#include "../../include/qqq_amd_logprobs.h"' in unit  # the compiler holds the definitions against the prototypes
     assert unit.index('#include "qqq_score.hip.h"') < unit.index('#include "qqq_logprobs.hip.h"')
-
-
-def test_a_newer_serving_header_rebuilds_the_operator_library(monkeypatch, L):
-    from qqq_amd import build
-
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 1.0)
-    assert not build.needs_build()
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 3.0 if p == HEADER else 1.0)
-    assert build.needs_build()
 
 
 def _plain(L, k=5, rows=2, vocab=100, ld=104, logits=None, tokens=None, logprob=None, rank=None, top_ids=None, top=None):

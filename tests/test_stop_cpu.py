@@ -1,4 +1,4 @@
-"""Stop sequences, stop token ids and min_new_tokens without a GPU: where the extension header sits and what it declares, the two entries'
+"""Stop sequences, stop token ids and min_new_tokens without a GPU: what the header declares, the two entries'
 argument checks (before any launch), the ops' refusals and fake implementations, generate()'s three keywords and how they reach the
 loops, and the bookkeeping of the host path, DecodeLoop and SpecDecodeLoop with host stubs for the forward pass, the samplers and --
 through tests/stop_ref.py -- the two new ops."""
@@ -13,7 +13,7 @@ import torch
 import stop_ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "serving", "stop", "qqq_amd_stop.h")
+HEADER = os.path.join(ROOT, "include", "qqq_amd_stop.h")
 ERR_ARG = 17
 
 
@@ -88,10 +88,9 @@ def test_reference_ban_tokens_by_hand():
 
 # ---- the C ABI
 
-def test_the_header_sits_in_a_subdirectory_of_serving_and_declares_the_two_entries(L):
+def test_the_header_declares_the_two_entries(L):
     from qqq_amd import _abi, _lib, build
 
-    assert build.extension_headers() == [HEADER] and HEADER not in build.serving_headers() and HEADER not in build.headers()
     assert _lib.ABI_VERSION == 4 and L.qqq_amd_abi_version() == 4
     protos = _abi.prototypes(HEADER)
     assert set(protos) == {"qqq_ban_tokens", "qqq_stop_check"}
@@ -100,16 +99,7 @@ def test_the_header_sits_in_a_subdirectory_of_serving_and_declares_the_two_entri
         assert ret == "int" and fn.restype is __import__("ctypes").c_int and len(fn.argtypes) == len(params), name
         assert all(p.rsplit(" ", 1)[0] in ("const void*", "void*", "int") for p in params), params
     unit = open(build.SRC).read()
-    assert '#include "qqq_stop.hip.h"' in unit and '#include "../../include/serving/stop/qqq_amd_stop.h"' in unit
-
-
-def test_a_newer_extension_header_rebuilds_the_operator_library(monkeypatch, L):
-    from qqq_amd import build
-
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 1.0)
-    assert not build.needs_build()
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 3.0 if p == HEADER else 1.0)
-    assert build.needs_build()
+    assert '#include "qqq_stop.hip.h"' in unit and '#include "../../include/qqq_amd_stop.h"' in unit
 
 
 # fake device addresses with the alignment the entries ask for: the calls below must fail in the checks, before any launch
