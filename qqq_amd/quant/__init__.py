@@ -1,6 +1,6 @@
 """qqq_amd.quant -- the GPTQ weight quantiser on the device: makes the (fake-quantised weight, scales) pair QuantLinear.pack takes, and
 whole QQQ W4A8 checkpoints from fp16 ones, rotated first where asked.  A sub-package with a HIP library of its own
-(libqqq_amd_quant.so, include/qqq_amd_quant.h and qqq_amd_rotate.h here): an offline tool, nothing of it is loaded by serving.
+(libqqq_amd_quant.so, the headers of include/ and include_ext/ here): an offline tool, nothing of it is loaded by serving.
 
     ops.weight_scales, ops.gptq_block   the two HIP ops: a row's 4-bit scale (optionally the reference's shrink search) and the column
                                         sweep of one 128-column GPTQ block in one launch
@@ -15,15 +15,22 @@ whole QQQ W4A8 checkpoints from fp16 ones, rotated first where asked.  A sub-pac
     ops.hadamard_rows, ops.check_signs  the third HIP op: the blocked Walsh-Hadamard transform of matrix rows, exact for fp16
     fuse_layer_norms, hadamard_signs,   rotation over state dicts (rotation.py): norms folded into the linears, the residual stream
     rotate_state_dict, rotate_model     turned by a randomised Hadamard (or any orthogonal) matrix, the per-head Hadamard on v / o
+    ops.hadamard_rows_k, ops.check_table  the HIP op for hidden sizes K * 2^p: the Sylvester stages of every sub-block and the K x K
+                                        Hadamard table that mixes them, one launch; the table is an argument
+    hadamard_table, hadamard_factor,    our tables for K = 12, 20, 28, 40 by construction, the (K, m) the reference picks for a size,
+    hadamard_matrix_k                   and the dense Q of mode="hadamard_k" (rotate_model, quantize_model(rotation="hadamard_k"))
 
-Out of scope: smoothing, Hadamard sizes that are no power of two, act-order with moving (non-static) groups, asymmetric modes, other bit
+Out of scope: smoothing, Hadamard tables of other orders (pass one as table=), a head_dim that is no power of two, act-order with moving (non-static) groups, asymmetric modes, other bit
 widths and group sizes."""
 from . import ops
 from .gptq import BlockTrace, GPTQResult, Hessian, gptq_quantize, gptq_quantize_ordered, round_to_nearest
 from .model import FloatDecoderLayer, quantize_model
 from .ops import gptq_block_cols, group_scales
-from .rotation import fuse_layer_norms, hadamard_matrix, hadamard_signs, random_orthogonal, rotate_model, rotate_state_dict
+from .ops import check_table, hadamard_rows_k
+from .rotation import (fuse_layer_norms, hadamard_factor, hadamard_matrix, hadamard_matrix_k, hadamard_signs, hadamard_table,
+                       random_orthogonal, rotate_model, rotate_state_dict)
 
 __all__ = ["ops", "Hessian", "gptq_quantize", "gptq_quantize_ordered", "group_scales", "gptq_block_cols", "round_to_nearest", "GPTQResult",
            "BlockTrace", "FloatDecoderLayer", "quantize_model",
-           "fuse_layer_norms", "hadamard_signs", "hadamard_matrix", "random_orthogonal", "rotate_state_dict", "rotate_model"]
+           "fuse_layer_norms", "hadamard_signs", "hadamard_matrix", "random_orthogonal", "rotate_state_dict", "rotate_model",
+           "hadamard_rows_k", "check_table", "hadamard_table", "hadamard_factor", "hadamard_matrix_k"]

@@ -1,7 +1,7 @@
 // qqq_quant.hip -- the one translation unit of libqqq_amd_quant.so: the C-ABI entry points of the GPTQ quantiser
 // (qqq_amd/quant/include/qqq_amd_quant.h) over the kernels of qqq_gptq.hip.h, of its act-order / static-groups ops
-// (qqq_amd/quant/include/qqq_amd_gptq_order.h) over those of qqq_gptq_order.hip.h, and of the rotation op
-// (qqq_amd/quant/include/qqq_amd_rotate.h) over the kernel of qqq_hadamard.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
+// (qqq_amd/quant/include/qqq_amd_gptq_order.h) over those of qqq_gptq_order.hip.h, and of the rotation ops
+// (qqq_amd/quant/include/qqq_amd_rotate.h, qqq_amd/quant/include_ext/qqq_amd_rotate_k.h) over the kernels of qqq_hadamard.hip.h and qqq_hadamard_k.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
 // (qqq_amd/build.py, build_quant): the entry points promise bits.
 #include <hip/hip_runtime.h>
 
@@ -13,9 +13,11 @@
 #include "../include/qqq_amd_gptq_order.h"
 #include "../include/qqq_amd_quant.h"
 #include "../include/qqq_amd_rotate.h"
+#include "../include_ext/qqq_amd_rotate_k.h"
 #include "qqq_gptq.hip.h"
 #include "qqq_gptq_order.hip.h"
 #include "qqq_hadamard.hip.h"
+#include "qqq_hadamard_k.hip.h"
 
 static thread_local char g_err[512] = "";
 
@@ -276,5 +278,94 @@ extern "C" int qqq_hadamard_rows(const void* X, int ldx, void* Y, int ldy, int r
     hadamard_launch<float, false>(a, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_hadamard_kernel launch");
+  return QQQ_OK;
+}
+
+template <typename T, bool VEC>
+static void hadamard_k_launch(const qqq_hadamard_k_args& a, unsigned grid, hipStream_t st) {
+  // the workgroup holds whole blocks: as many as fit 256 runs up to n = 2048, then the block itself
+  if (a.n <= 2048)
+    hipLaunchKernelGGL((qqq_hadamard_k_kernel<T, VEC, 11>), dim3(grid), dim3(256), 0, st, a);
+  else if (a.n <= 4096)
+    hipLaunchKernelGGL((qqq_hadamard_k_kernel<T, VEC, 12>), dim3(grid), dim3(512), 0, st, a);
+  else
+    hipLaunchKernelGGL((qqq_hadamard_k_kernel<T, VEC, 13>), dim3(grid), dim3(1024), 0, st, a);
+}
+
+extern "C" int qqq_hadamard_rows_k(const void* X, int ldx, void* Y, int ldy, int rows, int cols, int K, int m, const void* table,
+                                   const void* sign, int dtype, int dev, void* stream) {
+  g_err[0] = 0;
+  if (dtype != 0 && dtype != 1) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows_k: dtype=%d is not 0 (fp16) or 1 (f32)", dtype);
+    return QQQ_ERR_ARG;
+  }
+  if (K < 4 || K > HAD_K_MAX || K % 4 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows_k: K=%d is not a multiple of 4 in 4 ... %d", K, HAD_K_MAX);
+    return QQQ_ERR_ARG;
+  }
+  if (m < 1 || m > HAD_MAX_N / K || (m & (m - 1)) != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows_k: m=%d is not a power of two with K * m = %d * m <= %d", m, K, HAD_MAX_N);
+    return QQQ_ERR_ARG;
+  }
+  const int n = K * m;
+  if (rows < 1 || cols < n || cols % n != 0 || ldx < cols || ldy < cols) {
+    snprintf(g_err, sizeof(g_err),
+             "qqq_hadamard_rows_k: bad shape rows=%d cols=%d ldx=%d ldy=%d (need rows >= 1, cols a positive multiple of n=%d, both strides >= cols)",
+             rows, cols, ldx, ldy, n);
+    return QQQ_ERR_ARG;
+  }
+  const uintptr_t es = dtype == 0 ? 2 : 4;
+  if (!X || !Y || !table || misaligned(X, es) || misaligned(Y, es)) {
+    snprintf(g_err, sizeof(g_err),
+             "qqq_hadamard_rows_k: bad argument (X, Y and table must be non-NULL, X and Y aligned to their element, %d bytes)", static_cast<int>(es));
+    return QQQ_ERR_ARG;
+  }
+  const uintptr_t x0 = reinterpret_cast<uintptr_t>(X), y0 = reinterpret_cast<uintptr_t>(Y);
+  const uintptr_t xspan = (static_cast<uintptr_t>(rows - 1) * ldx + cols) * es, yspan = (static_cast<uintptr_t>(rows - 1) * ldy + cols) * es;
+  if (x0 == y0 ? ldx != ldy : (x0 < y0 + yspan && y0 < x0 + xspan)) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows_k: X and Y overlap (only Y == X with ldy == ldx, in place, is allowed)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_hadamard_k_args a;
+  a.X = X;
+  a.Y = Y;
+  a.sign = static_cast<const signed char*>(sign);
+  a.table = static_cast<const signed char*>(table);
+  a.ldx = ldx;
+  a.ldy = ldy;
+  a.blocks_per_row = cols / n;
+  a.blocks = static_cast<long long>(rows) * a.blocks_per_row;
+  a.run = n % HAD_RUN == 0 ? HAD_RUN : HAD_RUN / 2;  // K is a multiple of 4: n % 8 is 0 or 4
+  a.group = n <= 2048 ? 256 * a.run / n : 1;
+  a.n = n;
+  a.K = K;
+  a.m = m;
+  a.log2m = 0;
+  while ((1 << a.log2m) < m) ++a.log2m;
+  a.uniform = m % 8 == 0 && (a.group * m) % 64 == 0;
+  a.d = static_cast<double>(sqrtf(static_cast<float>(n)));
+  a.rd = 1.0 / a.d;
+  const long long grid = (a.blocks + a.group - 1) / a.group;
+  if (grid > 0x7fffffffLL) {
+    snprintf(g_err, sizeof(g_err), "qqq_hadamard_rows_k: rows=%d x cols=%d is more than one launch holds", rows, cols);
+    return QQQ_ERR_ARG;
+  }
+  // 16-byte loads and stores of a run (and one 8-byte load of its signs) where every run of both matrices is 16-byte aligned and the
+  // sign vector 8-byte; the bits do not depend on it
+  const uintptr_t per16 = 16 / es;
+  const bool vec = a.run == HAD_RUN && !misaligned(X, 16) && !misaligned(Y, 16) && ldx % per16 == 0 && ldy % per16 == 0 && !misaligned(sign, 8);
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const unsigned blocks = static_cast<unsigned>(grid);
+  if (dtype == 0 && vec)
+    hadamard_k_launch<_Float16, true>(a, blocks, st);
+  else if (dtype == 0)
+    hadamard_k_launch<_Float16, false>(a, blocks, st);
+  else if (vec)
+    hadamard_k_launch<float, true>(a, blocks, st);
+  else
+    hadamard_k_launch<float, false>(a, blocks, st);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_hadamard_k_kernel launch");
   return QQQ_OK;
 }

@@ -96,8 +96,9 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
     ids [samples, seqlen].  `seq_batch` sequences run through a layer at a time (1, the reference's, counts every sequence as one sample
     of the Hessian).  `results`: a dict that receives the GPTQResult of every linear under its state-dict prefix.
     `rotation`: None, or what rotation.rotate_model is to do to the state dict first (the reference's --rotation; pair it with mse=True):
-    "hadamard", "random", an int8 [hidden] sign vector, or an f64 [hidden, hidden] Q.  The model is then built UNTIED (its lm_head
-    carries the final norm), its norms are ones, and results["rotation"] receives the signs or Q that were used.
+    "hadamard", "hadamard_k" (hidden sizes K * 2^p), "random", an int8 [hidden] sign vector, an f64 [hidden, hidden] Q, or the pair
+    ("hadamard_k", signs).  The model is then built UNTIED (its lm_head carries the final norm), its norms are ones, and
+    results["rotation"] receives the signs or Q that were used.
     `act_order`, `static_groups`: the reference's --gptq_act_order / --gptq_static_groups (both on by default THERE, off here): with
     either, every linear goes through gptq_quantize_ordered; groups with act_order need static_groups too.  The checkpoint's layout does
     not change."""
@@ -107,8 +108,11 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
             kw = dict(mode=rotation)
         elif isinstance(rotation, torch.Tensor):
             kw = dict(signs=rotation) if rotation.dtype == torch.int8 else dict(Q=rotation)
+        elif isinstance(rotation, tuple) and len(rotation) == 2 and rotation[0] == "hadamard_k" and isinstance(rotation[1], torch.Tensor):
+            kw = dict(mode="hadamard_k", signs=rotation[1])
         else:
-            raise RuntimeError(f"quantize_model: rotation must be None, 'hadamard', 'random' or a tensor (signs or Q), got {type(rotation).__name__}")
+            raise RuntimeError("quantize_model: rotation must be None, 'hadamard', 'hadamard_k', 'random', a tensor (signs or Q) or "
+                               f"('hadamard_k', signs), got {type(rotation).__name__}")
         state_dict, used = rotate_model(state_dict, config, device=dev, **kw)
         config = copy.copy(config)
         config.tie_word_embeddings = False

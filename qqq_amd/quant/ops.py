@@ -1,5 +1,5 @@
-"""Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h, qqq_amd_gptq_order.h and
-qqq_amd_rotate.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing on the host."""
+"""Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h, qqq_amd_gptq_order.h,
+qqq_amd_rotate.h and, in qqq_amd/quant/include_ext/, qqq_amd_rotate_k.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing on the host."""
 from __future__ import annotations
 
 import torch
@@ -183,5 +183,61 @@ def hadamard_rows(x: torch.Tensor, n: int, sign=None, out=None) -> torch.Tensor:
     _same_gpu(name, tensors)
     err = _lib.lib().qqq_hadamard_rows(_ptr(x), ldx, _ptr(out), ldy, rows, cols, n, _ptr(sign) if sign is not None else None,
                                        _HAD_DTYPES[x.dtype], x.device.index or 0, _stream_for(x))
+    _raise_lib(name, err)
+    return out
+
+
+def _table_matrix(name, table):
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.int8 or table.dim() != 2 or table.shape[0] != table.shape[1] or not table.is_contiguous():
+        got = f"{_dt(table.dtype)} {tuple(table.shape)}" if isinstance(table, torch.Tensor) else type(table).__name__
+        raise RuntimeError(f"{name}: table must be contiguous int8 [K, K], got {got}")
+    K = table.shape[0]
+    if K % 4 or K < 4 or K > 64:
+        raise RuntimeError(f"{name}: table has K = {K}, no multiple of 4 in 4 ... 64")
+    return K
+
+
+def check_table(table: torch.Tensor, name: str = "check_table") -> torch.Tensor:
+    """`table` as hadamard_rows_k takes it: contiguous int8 [K, K], K a multiple of 4 in 4 ... 64, every entry +1 or -1, and Hadamard:
+    table . table^T == K I in integer arithmetic.  The entries are READ ON THE HOST (one sync when the tensor is on a GPU), so this is
+    not part of hadamard_rows_k: a caller checks a table once, then launches as often as it likes."""
+    K = _table_matrix(name, table)
+    if not bool((table.abs() == 1).all()):
+        raise RuntimeError(f"{name}: every entry of table must be +1 or -1")
+    t = table.cpu().to(torch.int64)
+    if not torch.equal(t @ t.t(), K * torch.eye(K, dtype=torch.int64)):
+        raise RuntimeError(f"{name}: table is no Hadamard matrix (table . table^T != {K} I)")
+    return table
+
+
+def hadamard_rows_k(x: torch.Tensor, m: int, table: torch.Tensor, sign=None, out=None) -> torch.Tensor:
+    """hadamard_rows for blocks of n = K * m columns, K no power of two: every block of `x` (fp16 or f32 [rows, cols], cols a multiple
+    of n <= 8192; a view with its own row stride is fine) becomes (x * sign) . (table^T (x) H_m) / sqrt(n) in one launch -> `out`: new,
+    `x` itself (in place), or a matrix of x's shape and dtype that does not overlap it.  H_m is the natural-order Sylvester matrix on
+    every sub-block of m = 2^p >= 1 entries; `table` (int8 [K, K] of +-1 on x's device, K a multiple of 4 in 4 ... 64) then mixes the
+    K sub-blocks: y[k m + c] = sum_k' table[k][k'] t[k' m + c], k' ascending, in f64 (exactly, for fp16), divided once and rounded to
+    f32, then to fp16 -- the reference's matmul_hadU with hadK = table.  sign: None, or int8 [n] of +-1.  Neither the table's nor the
+    signs' entries are read here (check_table and check_signs do that, once, on the host)."""
+    name = "hadamard_rows_k"
+    ldx = _had_matrix(name, "x", x)
+    rows, cols = x.shape
+    K = _table_matrix(name, table)
+    if not isinstance(m, int) or m < 1 or m & (m - 1) or K * m > 8192:
+        raise RuntimeError(f"{name}: m must be a power of two with K * m = {K} * m <= 8192, got {m!r}")
+    n = K * m
+    if cols % n:
+        raise RuntimeError(f"{name}: x has {cols} columns, no multiple of n = {n}")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=x.dtype, device=x.device)
+    ldy = _had_matrix(name, "out", out, (rows, cols), x.dtype)
+    if out.data_ptr() == x.data_ptr() and ldy != ldx:
+        raise RuntimeError(f"{name}: out starts where x does with another row stride; in place means the same view")
+    tensors = [x, out, table]
+    if sign is not None:
+        _sign_vector(name, sign, n)
+        tensors.append(sign)
+    _same_gpu(name, tensors)
+    err = _lib.lib().qqq_hadamard_rows_k(_ptr(x), ldx, _ptr(out), ldy, rows, cols, K, m, _ptr(table), _ptr(sign) if sign is not None else None,
+                                         _HAD_DTYPES[x.dtype], x.device.index or 0, _stream_for(x))
     _raise_lib(name, err)
     return out

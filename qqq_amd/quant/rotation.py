@@ -17,7 +17,16 @@ Where the bits differ from the reference's:
     the sums, while we divide the exact sum once.  The fp16 results agree on the fixture (32 x 128, bit for bit).
 A power-of-four hidden size (64, 1024, 4096) gives the reference's Q-stage bits exactly: both are exact sums scaled by a power of two.
 
-Not here: Hadamard matrices of sizes that are no power of two (the reference's Paley-type tables), smoothing, any online Hadamard."""
+Hidden sizes K * 2^p (mode="hadamard_k": 896, 1536, 3072, 3584, 5120 ...).  The reference multiplies by hadK (x) H_m there, hadK one of
+its literal K x K tables.  ops.hadamard_rows_k takes the table as an argument and does the sub-block stages and the K-mix in one
+launch; hadamard_table builds OUR tables for K = 12, 20, 28, 40 by construction (Paley I, Paley II, Sylvester doubling).
+  * OUR TABLES DIFFER FROM THE REFERENCE'S (no plain Paley construction gives its tables, their transposes or negatives): Q is another
+    matrix, equally orthogonal.  A checkpoint carries no Q -- the rotation is folded into the weights -- so nothing downstream depends
+    on which table was used.  Given the reference's table (`table=`), the Q stage has the reference's bits wherever its per-product
+    rounding agrees with one divide of the exact sum (tests/golden/rotate_k_small.npz records the count of elements where not).
+
+Not here: tables of other orders than 12, 20, 28, 40 (a caller may pass any Hadamard matrix of order K <= 64), a head_dim that is no
+power of two, smoothing, any online Hadamard."""
 from __future__ import annotations
 
 from typing import Optional
@@ -101,18 +110,101 @@ def hadamard_matrix(signs: torch.Tensor) -> torch.Tensor:
     return signs.double()[:, None] * H / torch.tensor(n).sqrt().double()
 
 
-def _had(W, n, sign, dev):
+_TABLE_ORDERS = (28, 40, 20, 12)  # the reference's precedence among the tables built here
+_NOT_BUILT = (172, 156, 140, 108, 60, 52, 36)  # the reference's other tables, which it tries first
+
+
+def _jacobsthal(q: int) -> torch.Tensor:
+    # [q, q] of chi(i - j): the quadratic character of the prime field GF(q), 0 on the diagonal
+    squares = {x * x % q for x in range(1, q)}
+    chi = [0] + [1 if a in squares else -1 for a in range(1, q)]
+    return torch.tensor([[chi[(i - j) % q] for j in range(q)] for i in range(q)], dtype=torch.int64)
+
+
+def _paley(q: int) -> torch.Tensor:
+    """Paley I for a prime q = 3 (mod 4): I + S of order q + 1, S = [[0, 1], [-1, J]] skew; Paley II for a prime q = 1 (mod 4):
+    S = [[0, 1], [1, J]] symmetric, every entry replaced by a 2 x 2 block, of order 2 (q + 1); J the Jacobsthal matrix"""
+    S = torch.zeros((q + 1, q + 1), dtype=torch.int64)
+    S[0, 1:] = 1
+    S[1:, 0] = -1 if q % 4 == 3 else 1
+    S[1:, 1:] = _jacobsthal(q)
+    eye = torch.eye(q + 1, dtype=torch.int64)
+    if q % 4 == 3:
+        return S + eye
+    return torch.kron(S, torch.tensor([[1, 1], [1, -1]])) + torch.kron(eye, torch.tensor([[1, -1], [-1, -1]]))
+
+
+def hadamard_table(K: int) -> torch.Tensor:
+    """int8 [K, K] of +-1, a Hadamard matrix of order K in {12, 20, 28, 40}, built by construction: Paley I over GF(11) and GF(19),
+    Paley II over GF(13), and the Sylvester double of the order-20 one.  NOT the reference's literal tables (see the module's text)."""
+    if K == 12:
+        H = _paley(11)
+    elif K == 20:
+        H = _paley(19)
+    elif K == 28:
+        H = _paley(13)
+    elif K == 40:
+        H = torch.kron(torch.tensor([[1, 1], [1, -1]]), _paley(19))
+    else:
+        raise RuntimeError(f"hadamard_table: no table of order K = {K!r} is built here (12, 20, 28 and 40 are); pass your own as table=")
+    return ops.check_table(H.to(torch.int8).contiguous(), "hadamard_table")
+
+
+def hadamard_factor(n: int):
+    """(K, m) with n = K * m, m a power of two: the table order the reference's get_hadK picks for n among those built here (28, then
+    40, then 20, then 12), or K = 1 for a power of two.  An n the reference sends to a table that is not built here (a multiple of
+    172, 156, 140, 108, 60, 52 or 36, which it tries first) and an n that is none of these raise by name."""
+    name = "hadamard_factor"
+    if not isinstance(n, int) or n < 1:
+        raise RuntimeError(f"{name}: n must be a positive integer, got {n!r}")
+    for K in _NOT_BUILT:
+        if n % K == 0:
+            raise RuntimeError(f"{name}: n = {n} is a multiple of {K}: the reference takes its table of order {K} there, and none of that "
+                               "order is built here; pass a Hadamard matrix of an order K <= 64 that divides n as table=")
+    for K in _TABLE_ORDERS:
+        if n % K == 0:
+            if not _is_pow2(n // K):
+                raise RuntimeError(f"{name}: n = {n} = {K} * {n // K}, and {n // K} is not a power of two; pass a Hadamard matrix of an "
+                                   "order K <= 64 with n / K a power of two as table=")
+            return K, n // K
+    if not _is_pow2(n):
+        raise RuntimeError(f"{name}: n = {n} is neither a power of two nor 12, 20, 28 or 40 times one; pass a Hadamard matrix of an "
+                           "order K <= 64 with n / K a power of two as table=")
+    return 1, n
+
+
+def hadamard_matrix_k(signs: torch.Tensor, table: torch.Tensor, m: int) -> torch.Tensor:
+    """f64 [n, n], n = K m: diag(signs) (table^T (x) H_m) / d, the matrix mode="hadamard_k" multiplies by without forming it (for
+    checks and for the dense path of another tool); d = sqrt(n) in f32, as the op.  With the reference's table it is the reference's
+    random_hadamard_matrix for these signs."""
+    K = table.shape[0]
+    n = K * m
+    if signs.numel() != n:
+        raise RuntimeError(f"hadamard_matrix_k: {signs.numel()} signs for n = {K} * {m} = {n}")
+    H = (hadamard_matrix(torch.ones(m, dtype=torch.int8)) * torch.tensor(m).sqrt().double()).round()  # the +-1 Sylvester matrix
+    M = torch.kron(table.cpu().double().t().contiguous(), H)
+    return signs.cpu().double()[:, None] * M / torch.tensor(n).sqrt().double()
+
+
+def _had(W, n, sign, dev, table=None):
     # the op on a 2-D tensor from anywhere: computed on `dev`, returned where W lives, W itself untouched
+    if table is not None:
+        return ops.hadamard_rows_k(W.to(dev).contiguous(), n // table.shape[0], table, sign=sign).to(W.device)
     return ops.hadamard_rows(W.to(dev).contiguous(), n, sign=sign).to(W.device)
 
 
 def rotate_state_dict(state_dict: dict, config, mode: str = "hadamard", signs: Optional[torch.Tensor] = None,
-                      Q: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, device=None):
+                      Q: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None, device=None,
+                      table: Optional[torch.Tensor] = None):
     """The rotated copy of an UNTIED state dict whose norm weights are ones (fuse_layer_norms makes one) -> (dict, signs or Q).
 
     mode="hadamard": Q = diag(signs) H / sqrt(hidden); `signs` int8 [hidden] of +-1, or drawn from `generator` (hadamard_signs); the
     hidden size must be a power of two up to 8192.  Returns the signs.  mode="random": Q from random_orthogonal(hidden, generator).  An
     explicit `Q` (f64 [hidden, hidden], orthogonal: not checked) overrides the mode.  Both return Q, and take the reference's dense line.
+    mode="hadamard_k": hidden = K * 2^p up to 8192; Q = diag(signs) (table^T (x) H_m) / sqrt(hidden), one launch of
+    ops.hadamard_rows_k per weight.  `table` int8 [K, K], a Hadamard matrix (checked: ops.check_table) whose order divides hidden into a
+    power of two; None: hadamard_factor(hidden) picks K and hadamard_table(K) builds it.  For a power-of-two hidden size without a table
+    the mode IS "hadamard".  Returns the signs.
     Then the per-head Hadamard of size head_dim on v_proj (output side, weight and bias) and o_proj (input side), each a separate
     rounding to the weight's dtype, as the reference rounds between the two steps.
 
@@ -127,11 +219,14 @@ def rotate_state_dict(state_dict: dict, config, mode: str = "hadamard", signs: O
         raise RuntimeError(f"{name}: head_dim = {head_dim} is not a power of two: the per-head Hadamard needs one")
     if "lm_head.weight" not in state_dict:
         raise RuntimeError(f"{name}: the state dict has no lm_head.weight; a tied model is untied by fuse_layer_norms first")
-    if mode not in ("hadamard", "random"):
-        raise RuntimeError(f"{name}: mode must be 'hadamard' or 'random', got {mode!r}")
+    if mode not in ("hadamard", "hadamard_k", "random"):
+        raise RuntimeError(f"{name}: mode must be 'hadamard', 'hadamard_k' or 'random', got {mode!r}")
     dense = Q is not None or mode == "random"
     if signs is not None and dense:
         raise RuntimeError(f"{name}: signs belong to mode='hadamard' without an explicit Q")
+    if table is not None and (dense or mode != "hadamard_k"):
+        raise RuntimeError(f"{name}: table belongs to mode='hadamard_k' without an explicit Q")
+    table_dev = None
     if dense:
         if Q is None:
             Q = random_orthogonal(hidden, generator)
@@ -140,25 +235,42 @@ def rotate_state_dict(state_dict: dict, config, mode: str = "hadamard", signs: O
         Qd = Q.to(dev)
         sign_dev = None
     else:
-        if not _is_pow2(hidden) or hidden > 8192:
+        if mode == "hadamard_k":
+            if not isinstance(hidden, int) or hidden < 1 or hidden > 8192:
+                raise RuntimeError(f"{name}: hidden_size = {hidden} is not in 1 ... 8192")
+            if table is not None:
+                ops.check_table(table, name)  # the one host read of the table
+                K = table.shape[0]
+                if hidden % K or not _is_pow2(hidden // K):
+                    raise RuntimeError(f"{name}: hidden_size = {hidden} is not the table's order {K} times a power of two")
+            else:
+                try:
+                    K, _ = hadamard_factor(hidden)
+                except RuntimeError as e:
+                    raise RuntimeError(f"{name}: hidden_size: {e}") from None
+                if K > 1:
+                    table = hadamard_table(K)
+        elif not _is_pow2(hidden) or hidden > 8192:
             raise RuntimeError(f"{name}: hidden_size = {hidden} is not a power of two up to 8192; the Paley-type Hadamard tables the "
-                               "reference uses for other sizes are not part of the repository: use mode='random'")
+                               "reference uses for sizes K * 2^p are not part of the repository: mode='hadamard_k' builds its own for "
+                               "K = 12, 20, 28, 40 or takes one as table=; for any other size use mode='random'")
         if signs is None:
             signs = hadamard_signs(hidden, generator)
         ops.check_signs(signs, hidden, name)  # the one host read of the signs
         sign_dev = signs.to(dev)
+        table_dev = table.to(dev) if table is not None else None
 
     def right(W):  # W Q
         if dense:
             return (W.to(dev).double() @ Qd).to(W.dtype).to(W.device)
-        return _had(W, hidden, sign_dev, dev)
+        return _had(W, hidden, sign_dev, dev, table_dev)
 
     def left(W):  # Q^T W, a bias as a column
         if dense:
             return (Qd.T @ W.to(dev).double()).to(W.dtype).to(W.device)
         if W.dim() == 1:
-            return _had(W.unsqueeze(0), hidden, sign_dev, dev).squeeze(0)
-        return _had(W.t(), hidden, sign_dev, dev).t().contiguous()
+            return _had(W.unsqueeze(0), hidden, sign_dev, dev, table_dev).squeeze(0)
+        return _had(W.t(), hidden, sign_dev, dev, table_dev).t().contiguous()
 
     out = dict(state_dict)
     for k, W in state_dict.items():
@@ -184,6 +296,7 @@ def rotate_state_dict(state_dict: dict, config, mode: str = "hadamard", signs: O
 
 
 def rotate_model(state_dict: dict, config, mode: str = "hadamard", signs: Optional[torch.Tensor] = None, Q: Optional[torch.Tensor] = None,
-                 generator: Optional[torch.Generator] = None, device=None):
+                 generator: Optional[torch.Generator] = None, device=None, table: Optional[torch.Tensor] = None):
     """fuse_layer_norms, then rotate_state_dict -> (dict, signs or Q).  The result is UNTIED (see fuse_layer_norms)."""
-    return rotate_state_dict(fuse_layer_norms(state_dict, config), config, mode=mode, signs=signs, Q=Q, generator=generator, device=device)
+    return rotate_state_dict(fuse_layer_norms(state_dict, config), config, mode=mode, signs=signs, Q=Q, generator=generator, device=device,
+                             table=table)

@@ -4,7 +4,7 @@ reference's examples/quant_model.py without its smoothing stage; --rotation is i
 
     python tools/quantize_model.py --config config.json --weights model.pt --tokens calib.npy --out DIR [--group-size 128]
                                    [--seqlen 2048] [--nsamples 128] [--mse] [--percdamp 0.01] [--seq-batch 1]
-                                   [--rotation {none,hadamard,random}] [--rotation-seed 0] [--act-order] [--static-groups]
+                                   [--rotation {none,hadamard,hadamard_k,random}] [--rotation-seed 0] [--act-order] [--static-groups]
 
 --config   a transformers config.json of a Llama or Qwen2 model (read as plain JSON; transformers is not needed)
 --weights  the fp16 state dict with Hugging Face parameter names: a torch.save file, or .safetensors where the safetensors package can
@@ -13,8 +13,9 @@ reference's examples/quant_model.py without its smoothing stage; --rotation is i
            tokenizer here: tokenise elsewhere)
 --out      a directory: model.pt (the packed state dict, the reference's names: tools/eval_ppl.py --weights takes it) and
            quant_config.json ({"group_size", "wbits"}, as the reference writes it)
---rotation hadamard | random: fuse the norms and rotate the state dict first (qqq_amd.quant.rotate_model; the reference runs this with
-           --mse).  The checkpoint is then UNTIED: --out also gets config.json, the input's with "tie_word_embeddings": false, and
+--rotation hadamard | hadamard_k | random: fuse the norms and rotate the state dict first (qqq_amd.quant.rotate_model; the reference
+           runs this with --mse).  hadamard needs a power-of-two hidden size; hadamard_k takes 12, 20, 28 or 40 times a power of two as
+           well (896, 1536, 3072, 3584, 5120: a Hadamard table built here mixes the K sub-blocks), and is hadamard at a power of two.  The checkpoint is then UNTIED: --out also gets config.json, the input's with "tie_word_embeddings": false, and
            quant_config.json also records {"rotation", "rotation_seed"}.  The signs / Q come from --rotation-seed.
 --act-order, --static-groups   the reference's --gptq_act_order / --gptq_static_groups, which are ON by default there and off here:
            sweep the columns by falling diag(H), and find every group's scale before the sweep.  With --group-size 128, --act-order
@@ -48,7 +49,7 @@ def main():
     ap.add_argument("--mse", action="store_true", help="the shrink search for the scales (the reference's pairing for rotated models)")
     ap.add_argument("--percdamp", type=float, default=0.01)
     ap.add_argument("--seq-batch", type=int, default=1)
-    ap.add_argument("--rotation", choices=("none", "hadamard", "random"), default="none", help="rotate the state dict before GPTQ")
+    ap.add_argument("--rotation", choices=("none", "hadamard", "hadamard_k", "random"), default="none", help="rotate the state dict before GPTQ")
     ap.add_argument("--rotation-seed", type=int, default=0)
     ap.add_argument("--act-order", action="store_true", help="sweep the columns by falling diag(H) (the reference's default; off here)")
     ap.add_argument("--static-groups", action="store_true",
@@ -78,7 +79,12 @@ def main():
     rotation = None
     if args.rotation != "none":
         gen = torch.Generator().manual_seed(args.rotation_seed)
-        rotation = hadamard_signs(cfg["hidden_size"], gen) if args.rotation == "hadamard" else random_orthogonal(cfg["hidden_size"], gen)
+        if args.rotation == "random":
+            rotation = random_orthogonal(cfg["hidden_size"], gen)
+        else:
+            rotation = hadamard_signs(cfg["hidden_size"], gen)
+            if args.rotation == "hadamard_k":
+                rotation = ("hadamard_k", rotation)
         if not args.mse:
             print("quantize_model.py: hint: the reference pairs rotation with the scale search; consider --mse", file=sys.stderr)
     t0 = time.perf_counter()
