@@ -5,12 +5,14 @@
                                csrc/qqq_rates.h: pure host C++, compiles alone with the host compiler)
     qqq_amd/libqqq_amd_dev.so  test / tuning companion (include/qqq_amd_dev.h) <- csrc/qqq_dev.hip
     qqq_amd/_torch_ext*.so     compiled torch binding (pybind + TORCH_LIBRARY) of the operator library <- csrc/qqq_torch.cpp
-    qqq_amd/libqqq_amd_quant.so  the GPTQ quantiser (quant/include/*.h and quant/include_ext/*.h), an offline tool beside the operator <- quant/csrc/qqq_quant.hip
+    qqq_amd/libqqq_amd_quant.so  the GPTQ quantiser (quant/include/*.h, quant/include_ext/*.h and quant/include_ops/*.h), an offline tool beside the operator <- quant/csrc/qqq_quant.hip
 
 Each library has ONE flat directory of headers and one lister: operator_headers() for include/, quant_headers() for quant/include/.  A library
 is rebuilt for, and bound from, what its lister returns, so a new feature adds include/qqq_amd_<feature>.h, includes it from the translation
 unit, and nothing here.  The quantiser has a second flat directory, quant/include_ext/ (quant_ext_headers()): the contents of quant/include/
-are pinned by name, so the headers of later quantiser ops go there; the library is rebuilt for, and bound from, both.
+are pinned by name, so the header of the next quantiser op went there -- and was pinned by name in turn.  The chain ends with a third,
+quant/include_ops/ (quant_op_headers()): EVERY later quantiser op drops its header there, and no test pins that directory's listing (tests
+assert membership and that no name is declared twice).  The library is rebuilt for, and bound from, all three.
 
 The .so files are git-ignored but travel to the GPU box with the repo snapshot.
 """
@@ -83,7 +85,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 QUANT_DIR = os.path.join(_HERE, "quant")
-QUANT_SRC = os.path.join(QUANT_DIR, "csrc", "qqq_quant.hip")  # the one translation unit of the quantiser; it includes quant/csrc/*.hip.h and every header quant_headers() and quant_ext_headers() list
+QUANT_SRC = os.path.join(QUANT_DIR, "csrc", "qqq_quant.hip")  # the one translation unit of the quantiser; it includes quant/csrc/*.hip.h and every header quant_headers(), quant_ext_headers() and quant_op_headers() list
 QUANT_INCLUDE = os.path.join(QUANT_DIR, "include")  # outside include/: headers() does not see it
 QUANT_HEADER = os.path.join(QUANT_INCLUDE, "qqq_amd_quant.h")  # the ABI version is read from it
 QUANT_LIB = os.path.join(_HERE, "libqqq_amd_quant.so")
@@ -104,10 +106,18 @@ def quant_ext_headers() -> list:
     return sorted(os.path.join(QUANT_EXT_INCLUDE, f) for f in os.listdir(QUANT_EXT_INCLUDE) if f.endswith(".h"))
 
 
+QUANT_OPS_INCLUDE = os.path.join(QUANT_DIR, "include_ops")  # flat, and open: the headers of every quantiser op from the smoothing op on
+
+
+def quant_op_headers() -> list:
+    """the quantiser library's headers outside the two pinned directories: one new file under quant/include_ops/ is all a new quantiser op adds here"""
+    return sorted(os.path.join(QUANT_OPS_INCLUDE, f) for f in os.listdir(QUANT_OPS_INCLUDE) if f.endswith(".h"))
+
+
 def build_quant(force: bool = False, verbose: bool = False) -> str:
     """the GPTQ quantiser's library (qqq_amd/quant): an offline tool with a library of its own, libqqq_amd.so stays as it is"""
     csrc = os.path.dirname(QUANT_SRC)
-    deps = quant_headers() + quant_ext_headers() + [header("qqq_amd.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
+    deps = quant_headers() + quant_ext_headers() + quant_op_headers() + [header("qqq_amd.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
     if not force and os.path.exists(QUANT_LIB) and os.path.getmtime(QUANT_LIB) >= max(map(os.path.getmtime, deps)):
         return QUANT_LIB
     return _compile(QUANT_SRC, QUANT_LIB, verbose, QUANT_FLAGS)

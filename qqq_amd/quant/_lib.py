@@ -1,5 +1,5 @@
-"""ctypes binding of libqqq_amd_quant.so, bound from the prototypes of every header in qqq_amd/quant/include/ and qqq_amd/quant/include_ext/
-(build.quant_headers(), build.quant_ext_headers(), qqq_amd/_abi.py).  No fallback: if the library is missing, every entry point raises."""
+"""ctypes binding of libqqq_amd_quant.so, bound from the prototypes of every header in qqq_amd/quant/include/, qqq_amd/quant/include_ext/
+and qqq_amd/quant/include_ops/ (build.quant_headers(), build.quant_ext_headers(), build.quant_op_headers(), qqq_amd/_abi.py).  No fallback: if the library is missing, every entry point raises."""
 from __future__ import annotations
 
 import ctypes
@@ -29,7 +29,7 @@ def lib():
     L = ctypes.CDLL(path)
     if L.qqq_quant_abi_version() != ABI_VERSION:
         raise RuntimeError("libqqq_amd_quant.so ABI version mismatch; rebuild")
-    for hdr in _build.quant_headers() + _build.quant_ext_headers():
+    for hdr in _build.quant_headers() + _build.quant_ext_headers() + _build.quant_op_headers():
         _abi.bind(L, hdr)
     _lib = L
     return L

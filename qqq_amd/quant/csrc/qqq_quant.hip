@@ -1,7 +1,8 @@
 // qqq_quant.hip -- the one translation unit of libqqq_amd_quant.so: the C-ABI entry points of the GPTQ quantiser
 // (qqq_amd/quant/include/qqq_amd_quant.h) over the kernels of qqq_gptq.hip.h, of its act-order / static-groups ops
 // (qqq_amd/quant/include/qqq_amd_gptq_order.h) over those of qqq_gptq_order.hip.h, and of the rotation ops
-// (qqq_amd/quant/include/qqq_amd_rotate.h, qqq_amd/quant/include_ext/qqq_amd_rotate_k.h) over the kernels of qqq_hadamard.hip.h and qqq_hadamard_k.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
+// (qqq_amd/quant/include/qqq_amd_rotate.h, qqq_amd/quant/include_ext/qqq_amd_rotate_k.h) over the kernels of qqq_hadamard.hip.h and qqq_hadamard_k.hip.h,
+// and of the smoothing search's fake-quantisation op (qqq_amd/quant/include_ops/qqq_amd_fakequant.h) over those of qqq_fakequant.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
 // (qqq_amd/build.py, build_quant): the entry points promise bits.
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,8 @@
 #include "../include/qqq_amd_quant.h"
 #include "../include/qqq_amd_rotate.h"
 #include "../include_ext/qqq_amd_rotate_k.h"
+#include "../include_ops/qqq_amd_fakequant.h"
+#include "qqq_fakequant.hip.h"
 #include "qqq_gptq.hip.h"
 #include "qqq_gptq_order.hip.h"
 #include "qqq_hadamard.hip.h"
@@ -367,5 +370,76 @@ extern "C" int qqq_hadamard_rows_k(const void* X, int ldx, void* Y, int ldy, int
     hadamard_k_launch<float, false>(a, blocks, st);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_hadamard_k_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_fake_quant_rows(const void* X, int ldx, void* Y, int ldy, int rows, int cols, const void* col_scale, int bits, int group,
+                                   int divide, int dev, void* stream) {
+  g_err[0] = 0;
+  if (bits != 4 && bits != 8) {
+    snprintf(g_err, sizeof(g_err), "qqq_fake_quant_rows: bits=%d is not one of 4, 8", bits);
+    return QQQ_ERR_ARG;
+  }
+  if (group != 0 && group != 128) {
+    snprintf(g_err, sizeof(g_err), "qqq_fake_quant_rows: group=%d is not 0 (one scale per row) or 128", group);
+    return QQQ_ERR_ARG;
+  }
+  if (divide != 0 && divide != 1) {
+    snprintf(g_err, sizeof(g_err), "qqq_fake_quant_rows: divide=%d must be 0 or 1", divide);
+    return QQQ_ERR_ARG;
+  }
+  if (rows < 1 || cols < FQ_UNIT || cols > (1 << 30) || cols % FQ_UNIT != 0 || ldx < cols || ldy < cols || ldx % FQ_UNIT != 0 || ldy % FQ_UNIT != 0) {
+    snprintf(g_err, sizeof(g_err),
+             "qqq_fake_quant_rows: bad shape rows=%d cols=%d ldx=%d ldy=%d (need rows >= 1, cols a multiple of 8 in 8 ... 2^30, both strides "
+             ">= cols and multiples of 8)",
+             rows, cols, ldx, ldy);
+    return QQQ_ERR_ARG;
+  }
+  if (group == 128 && cols % 128 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_fake_quant_rows: cols=%d is no multiple of group=128", cols);
+    return QQQ_ERR_ARG;
+  }
+  if (!X || !Y || misaligned(X, 16) || misaligned(Y, 16) || misaligned(col_scale, 16)) {
+    snprintf(g_err, sizeof(g_err), "qqq_fake_quant_rows: bad argument (X and Y must be non-NULL, X, Y and col_scale 16-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  const uintptr_t x0 = reinterpret_cast<uintptr_t>(X), y0 = reinterpret_cast<uintptr_t>(Y);
+  const uintptr_t xspan = (static_cast<uintptr_t>(rows - 1) * ldx + cols) * 2, yspan = (static_cast<uintptr_t>(rows - 1) * ldy + cols) * 2;
+  if (x0 == y0 ? ldx != ldy : (x0 < y0 + yspan && y0 < x0 + xspan)) {
+    snprintf(g_err, sizeof(g_err), "qqq_fake_quant_rows: X and Y overlap (only Y == X with ldy == ldx, in place, is allowed)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_fake_quant_args a;
+  a.X = static_cast<const _Float16*>(X);
+  a.Y = static_cast<_Float16*>(Y);
+  a.c = static_cast<const _Float16*>(col_scale);
+  a.ldx = ldx;
+  a.ldy = ldy;
+  a.units_per_row = cols / FQ_UNIT;
+  a.units = static_cast<long long>(rows) * a.units_per_row;
+  a.divide = divide;
+  a.qmax = bits == 8 ? 127.f : 7.f;
+  const long long grid = group ? (a.units + FQ_NT - 1) / FQ_NT : rows;
+  if (grid > 0x7fffffffLL) {
+    snprintf(g_err, sizeof(g_err), "qqq_fake_quant_rows: rows=%d x cols=%d is more than one launch holds", rows, cols);
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 g(static_cast<unsigned>(grid)), b(FQ_NT);
+  if (group)
+    hipLaunchKernelGGL(qqq_fake_quant_group_kernel, g, b, 0, st, a);
+  else if (a.units_per_row <= FQ_NT)  // the row is read once where its units fit the registers of its workgroup
+    hipLaunchKernelGGL(qqq_fake_quant_row_kernel<1>, g, b, 0, st, a);
+  else if (a.units_per_row <= 2 * FQ_NT)
+    hipLaunchKernelGGL(qqq_fake_quant_row_kernel<2>, g, b, 0, st, a);
+  else if (a.units_per_row <= 4 * FQ_NT)
+    hipLaunchKernelGGL(qqq_fake_quant_row_kernel<4>, g, b, 0, st, a);
+  else if (a.units_per_row <= FQ_MAX_UPT * FQ_NT)
+    hipLaunchKernelGGL(qqq_fake_quant_row_kernel<FQ_MAX_UPT>, g, b, 0, st, a);
+  else
+    hipLaunchKernelGGL(qqq_fake_quant_row_kernel<0>, g, b, 0, st, a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_fake_quant_rows kernel launch");
   return QQQ_OK;
 }

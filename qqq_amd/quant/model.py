@@ -91,7 +91,7 @@ def _run(layer, inps, seq_batch, taps=None):
 @torch.no_grad()
 def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size: int, mse: bool = False, percdamp: float = 0.01,
                    seq_batch: int = 1, device=None, results: Optional[dict] = None, rotation=None, act_order: bool = False,
-                   static_groups: bool = False) -> QuantLlamaForCausalLM:
+                   static_groups: bool = False, smooth=None) -> QuantLlamaForCausalLM:
     """A packed QuantLlamaForCausalLM from an fp16 Hugging Face state dict, a (duck-typed) Llama or Qwen2 config and calibration token
     ids [samples, seqlen].  `seq_batch` sequences run through a layer at a time (1, the reference's, counts every sequence as one sample
     of the Hessian).  `results`: a dict that receives the GPTQResult of every linear under its state-dict prefix.
@@ -101,7 +101,11 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
     results["rotation"] receives the signs or Q that were used.
     `act_order`, `static_groups`: the reference's --gptq_act_order / --gptq_static_groups (both on by default THERE, off here): with
     either, every linear goes through gptq_quantize_ordered; groups with act_order need static_groups too.  The checkpoint's layout does
-    not change."""
+    not change.
+    `smooth`: None, a method name ("os+", "awq", "sq": smooth.smooth_model searches the scales on the first 8 calibration sequences), or
+    a ready scale_list (smooth.apply_smooth alone): the reference's --smooth True (pair it with mse=False).  It is applied AFTER
+    `rotation`, on the rotated state dict, and before GPTQ; results["smooth"] receives the list.  After rotation + smooth the norms are
+    no longer ones: they hold 1 / s.  With smooth=None nothing of it runs."""
     dev = torch.device(device if device is not None else "cuda:0")
     if rotation is not None:
         if isinstance(rotation, str):
@@ -118,6 +122,20 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
         config.tie_word_embeddings = False
         if results is not None:
             results["rotation"] = used
+    if smooth is not None:
+        from . import smooth as _smooth
+
+        if isinstance(smooth, str):
+            if smooth not in _smooth.METHODS:
+                raise RuntimeError(f"quantize_model: smooth must be None, one of {_smooth.METHODS} or a scale_list, got {smooth!r}")
+            state_dict, scale_list = _smooth.smooth_model(state_dict, config, calib_ids, group_size, method=smooth, device=dev)
+        elif isinstance(smooth, (list, tuple)):
+            scale_list = list(smooth)
+            state_dict = _smooth.apply_smooth(state_dict, config, scale_list)
+        else:
+            raise RuntimeError(f"quantize_model: smooth must be None, one of {_smooth.METHODS} or a scale_list, got {type(smooth).__name__}")
+        if results is not None:
+            results["smooth"] = scale_list
     lm = QuantLlamaForCausalLM.from_config(config, group_size).to(dev)
     embed = state_dict["model.embed_tokens.weight"].to(dev).half()
     ids = torch.as_tensor(calib_ids, dtype=torch.int64, device=dev)

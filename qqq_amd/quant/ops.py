@@ -1,5 +1,6 @@
 """Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h, qqq_amd_gptq_order.h,
-qqq_amd_rotate.h and, in qqq_amd/quant/include_ext/, qqq_amd_rotate_k.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing on the host."""
+qqq_amd_rotate.h, in qqq_amd/quant/include_ext/ qqq_amd_rotate_k.h and in qqq_amd/quant/include_ops/ qqq_amd_fakequant.h state the exact
+semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing on the host."""
 from __future__ import annotations
 
 import torch
@@ -239,5 +240,58 @@ def hadamard_rows_k(x: torch.Tensor, m: int, table: torch.Tensor, sign=None, out
     _same_gpu(name, tensors)
     err = _lib.lib().qqq_hadamard_rows_k(_ptr(x), ldx, _ptr(out), ldy, rows, cols, K, m, _ptr(table), _ptr(sign) if sign is not None else None,
                                          _HAD_DTYPES[x.dtype], x.device.index or 0, _stream_for(x))
+    _raise_lib(name, err)
+    return out
+
+
+def _fq_matrix(name, what, t, shape=None):
+    # an fp16 matrix of 16-byte units: unit column stride, a row stride that holds its columns and is a multiple of 8, a 16-byte aligned base
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float16:
+        got = f"{_dt(t.dtype)} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{name}: {what} must be a float16 matrix, got {got}")
+    if t.shape[0] < 1 or t.shape[1] < 8 or t.shape[1] % 8 or t.shape[1] > 2**30 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise RuntimeError(f"{name}: {what} has the shape {tuple(t.shape)}" + (f", {tuple(shape)} expected" if shape is not None else
+                                                                                 ", the columns must be a multiple of 8 in 8 ... 2^30"))
+    ld = max(t.stride(0), t.shape[1]) if t.shape[0] > 1 else t.shape[1]
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]) or ld % 8 or ld >= 2**31:
+        raise RuntimeError(f"{name}: {what} must have unit column stride and a row stride >= its columns that is a multiple of 8, got strides {tuple(t.stride())}")
+    if t.data_ptr() % 16:
+        raise RuntimeError(f"{name}: {what} must be 16-byte aligned")
+    return ld
+
+
+def fake_quant_rows(x: torch.Tensor, col_scale, bits: int, group: int = 0, divide: bool = False, out=None) -> torch.Tensor:
+    """The reference's MigratorBase.quantize of a column-scaled operand in one launch: `x` (fp16 [rows, cols], cols a multiple of 8; a view
+    with its own row stride, a multiple of 8, is fine) divided (divide=True, the activation side) or multiplied (the weight side) by
+    `col_scale` (None, or contiguous fp16 [cols] on x's device), then fake-quantised symmetrically to `bits` (8 or 4: codes -127 ... 127 or
+    -7 ... 7) with one scale per row (group=0) or per (row, 128 columns) (group=128, cols a multiple of 128) -> `out`: new, `x` itself (in
+    place), or a matrix of x's shape that does not overlap it.  Every step is one f32 operation rounded to fp16, as torch evaluates the
+    reference's fp16 expression (qqq_amd_fakequant.h states each): the result has the bits of the torch composition, and holds no -0."""
+    name = "fake_quant_rows"
+    ldx = _fq_matrix(name, "x", x)
+    rows, cols = x.shape
+    if bits not in (4, 8):
+        raise RuntimeError(f"{name}: bits must be 8 or 4, got {bits!r}")
+    if group not in (0, 128):
+        raise RuntimeError(f"{name}: group must be 0 (one scale per row) or 128, got {group!r}")
+    if group and cols % group:
+        raise RuntimeError(f"{name}: x has {cols} columns, no multiple of group = {group}")
+    if out is None:
+        out = torch.empty((rows, cols), dtype=x.dtype, device=x.device)
+    ldy = _fq_matrix(name, "out", out, (rows, cols))
+    if out.data_ptr() == x.data_ptr() and ldy != ldx:
+        raise RuntimeError(f"{name}: out starts where x does with another row stride; in place means the same view")
+    tensors = [x, out]
+    if col_scale is not None:
+        if (not isinstance(col_scale, torch.Tensor) or col_scale.dtype != torch.float16 or col_scale.dim() != 1 or col_scale.numel() != cols
+                or not col_scale.is_contiguous()):
+            got = f"{_dt(col_scale.dtype)} {tuple(col_scale.shape)}" if isinstance(col_scale, torch.Tensor) else type(col_scale).__name__
+            raise RuntimeError(f"{name}: col_scale must be None or contiguous float16 [{cols}], got {got}")
+        if col_scale.data_ptr() % 16:
+            raise RuntimeError(f"{name}: col_scale must be 16-byte aligned")
+        tensors.append(col_scale)
+    _same_gpu(name, tensors)
+    err = _lib.lib().qqq_fake_quant_rows(_ptr(x), ldx, _ptr(out), ldy, rows, cols, _ptr(col_scale) if col_scale is not None else None,
+                                         bits, group, int(bool(divide)), x.device.index or 0, _stream_for(x))
     _raise_lib(name, err)
     return out

@@ -26,7 +26,7 @@ launch; hadamard_table builds OUR tables for K = 12, 20, 28, 40 by construction 
     rounding agrees with one divide of the exact sum (tests/golden/rotate_k_small.npz records the count of elements where not).
 
 Not here: tables of other orders than 12, 20, 28, 40 (a caller may pass any Hadamard matrix of order K <= 64), a head_dim that is no
-power of two, smoothing, any online Hadamard."""
+power of two, any online Hadamard.  (Smoothing is the next stage: smooth.py, applied to the rotated state dict.)"""
 from __future__ import annotations
 
 from typing import Optional

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """A QQQ W4A8 checkpoint from an fp16 one, on the GPU: a thin wrapper over qqq_amd.quant.quantize_model (GPTQ layer by layer, the
-reference's examples/quant_model.py without its smoothing stage; --rotation is its rotation stage).
+reference's examples/quant_model.py; --rotation is its rotation stage, --smooth its smoothing stage).
 
     python tools/quantize_model.py --config config.json --weights model.pt --tokens calib.npy --out DIR [--group-size 128]
                                    [--seqlen 2048] [--nsamples 128] [--mse] [--percdamp 0.01] [--seq-batch 1]
                                    [--rotation {none,hadamard,hadamard_k,random}] [--rotation-seed 0] [--act-order] [--static-groups]
+                                   [--smooth {os+,awq,sq}] [--save-scales PATH]
 
 --config   a transformers config.json of a Llama or Qwen2 model (read as plain JSON; transformers is not needed)
 --weights  the fp16 state dict with Hugging Face parameter names: a torch.save file, or .safetensors where the safetensors package can
@@ -21,7 +22,12 @@ reference's examples/quant_model.py without its smoothing stage; --rotation is i
            sweep the columns by falling diag(H), and find every group's scale before the sweep.  With --group-size 128, --act-order
            needs --static-groups.  The checkpoint's layout does not change; quant_config.json records the two where set.  The
            reference's default recipe is --rotation hadamard --mse --act-order --static-groups.
-Prints one JSON line: group_size, nsamples, seqlen, linears, seconds (and rotation).
+--smooth   os+ | awq | sq: the reference's --smooth True --smooth_method ...: search the four migration scales of every layer on the first 8
+           windows (qqq_amd.quant.smooth_model), fold them into the state dict -- after --rotation where both are given -- and run GPTQ
+           on the result.  The reference pairs it with its --gptq_mse False: leave --mse out.  quant_config.json records {"smooth"}.
+--save-scales PATH   with --smooth: torch.save the scale_list (four fp16 vectors per layer: qkv, o, gate_up, down) there, the
+           reference's scale_list.pth.
+Prints one JSON line: group_size, nsamples, seqlen, linears, seconds (and rotation, smooth).
 """
 import argparse
 import json
@@ -54,7 +60,11 @@ def main():
     ap.add_argument("--act-order", action="store_true", help="sweep the columns by falling diag(H) (the reference's default; off here)")
     ap.add_argument("--static-groups", action="store_true",
                     help="find every group's scale before the sweep (the reference's default; off here; needed by --act-order with groups)")
+    ap.add_argument("--smooth", choices=("os+", "awq", "sq"), default=None, help="smooth the state dict before GPTQ (after --rotation)")
+    ap.add_argument("--save-scales", default=None, help="with --smooth: where to torch.save the scale_list")
     args = ap.parse_args()
+    if args.save_scales and not args.smooth:
+        ap.error("--save-scales needs --smooth")
     if args.act_order and args.group_size != -1 and not args.static_groups:
         ap.error("--act-order with --group-size 128 needs --static-groups (moving groups cannot be packed)")
     import numpy as np
@@ -90,13 +100,13 @@ def main():
     t0 = time.perf_counter()
     lm = quantize_model(load_state_dict(args.weights), SimpleNamespace(**cfg), ids, args.group_size, mse=args.mse, percdamp=args.percdamp,
                         seq_batch=args.seq_batch, results=results, rotation=rotation, act_order=args.act_order,
-                        static_groups=args.static_groups)
+                        static_groups=args.static_groups, smooth=args.smooth)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     os.makedirs(args.out, exist_ok=True)
     torch.save({k: v.cpu() for k, v in lm.state_dict().items()}, os.path.join(args.out, "model.pt"))
     quant_config = {"group_size": args.group_size, "wbits": 4}
-    summary = {"group_size": args.group_size, "nsamples": nsamples, "seqlen": args.seqlen, "linears": len(results) - (rotation is not None),
+    summary = {"group_size": args.group_size, "nsamples": nsamples, "seqlen": args.seqlen, "linears": len(results) - (rotation is not None) - (args.smooth is not None),
                "seconds": round(dt, 2)}
     if args.act_order or args.static_groups:
         quant_config.update(act_order=args.act_order, static_groups=args.static_groups)
@@ -106,6 +116,11 @@ def main():
         summary.update(rotation=args.rotation)
         with open(os.path.join(args.out, "config.json"), "w") as f:  # the rotated model's lm_head is its own
             json.dump(dict(cfg, tie_word_embeddings=False), f, indent=2)
+    if args.smooth:
+        quant_config.update(smooth=args.smooth)
+        summary.update(smooth=args.smooth)
+        if args.save_scales:
+            torch.save([s.cpu() for s in results["smooth"]], args.save_scales)
     with open(os.path.join(args.out, "quant_config.json"), "w") as f:
         json.dump(quant_config, f)
     print(json.dumps(summary))
