@@ -21,6 +21,9 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
                                                                                     # `tokens` tokens per row through the decode kernel, bit for bit
     decode_attention_paged_shared(q_out, k_pool, v_pool, block_table, pos, family, shared, pack, scale) / ..._kv8(...)  # decode attention of
                                                                                     # forked siblings: shared keys read once per pack, bit for bit
+    rope_qkv_norm(q, k, v, q_weight, k_weight, eps, cos, sin, pos, k_cache, v_cache) / rope_qkv_norm_kv8(...) / rope_qkv_norm_paged(...) /
+    rope_qkv_norm_paged_kv8(...)                                                    # the four RoPE / cache-write ops with Qwen3's per-head
+                                                                                    # q_norm / k_norm in front of the rotation, still one launch
     KVCache, QuantLlamaAttention, QuantLlamaDecoderLayer                            # attention and the whole layer; qqq_amd/attention.py
     PagedKVCache, PagedStep                                                        # block pools + host-side allocator; qqq_amd/paged.py
     sample_tokens(logits, temperature, top_k, top_p, u)                             # temperature / top-k / top-p / draw for a batch, one launch
@@ -79,6 +82,10 @@ from .ops import (  # noqa: F401
     rope_qkv_kv8,
     rope_qkv_paged,
     rope_qkv_paged_kv8,
+    rope_qkv_norm,
+    rope_qkv_norm_kv8,
+    rope_qkv_norm_paged,
+    rope_qkv_norm_paged_kv8,
     sample_advance,
     sample_tokens,
     silu_mul_quant,
@@ -115,4 +122,4 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "decode_attention_paged_shared", "decode_attention_paged_shared_kv8", "decode_attention_shared_plan",
            "topk_logprobs", "topk_logprobs_step", "TokenLogprobs", "ban_tokens", "stop_check",
            "beam_step", "copy_blocks", "BeamHypothesis", "fsm_mask", "fsm_advance", "TokenFSM", "GuidedDecodeLoop",
-           "lora_add", "LoraBank", "LoraStep"]
+           "lora_add", "LoraBank", "LoraStep", "rope_qkv_norm", "rope_qkv_norm_kv8", "rope_qkv_norm_paged", "rope_qkv_norm_paged_kv8"]

@@ -1,4 +1,4 @@
-"""ctypes binding of the C-ABI in include/qqq_amd*.h, bound from the headers' own prototypes (qqq_amd/_abi.py).  No fallback: if the HIP
+"""ctypes binding of the C-ABI in include/qqq_amd*.h and include_ops/qqq_amd*.h, bound from the headers' own prototypes (qqq_amd/_abi.py).  No fallback: if the HIP
 library is missing or does not load, every entry point raises -- the product path never routes through a CPU implementation."""
 from __future__ import annotations
 
@@ -30,7 +30,7 @@ def lib():
     L = ctypes.CDLL(path)
     if L.qqq_amd_abi_version() != ABI_VERSION:  # (int(void): callable before it is bound; a stale library may lack what the headers declare)
         raise RuntimeError("libqqq_amd.so ABI version mismatch; rebuild")
-    for hdr in _build.operator_headers():
+    for hdr in _build.operator_headers() + _build.operator_op_headers():
         _abi.bind(L, hdr)
     _lib = L
     return L

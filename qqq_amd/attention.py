@@ -21,6 +21,8 @@ scaled_dot_product_attention per sequence over PagedKVCache.gather (a contiguous
 prefill_attention_paged(_kv8): one ragged causal attention over the whole packed batch that reads the pool in place and writes o_proj's
 input already int8-quantised.  After the opt-in fuse_verify() a step that feeds every sequence the same 2 ... 16 tokens (a speculative decode
 step's chunk) runs verify_attention_paged(_kv8): the decode kernel's split over keys, every token bit for bit its decode step.
+Qwen3 (qk_norm=True): a per-head RMSNorm of q and k between the projections and RoPE; every rope_qkv* call above is then its
+rope_qkv_norm* counterpart, the norm inside the same launch (include_ops/qqq_amd_qknorm.h).
 Parameter and buffer names are the reference's, so the layers' state-dicts load unchanged; the rope tables, the fused q|k|v copy of
 fuse_qkv() and the fuse_decode() / fuse_prefill() / fuse_verify() / fuse_shared() flags are not part of them.
 """
@@ -123,6 +125,16 @@ class KVCache:
                      for c, sc in ((self.k[layer], self.k_scale[layer]), (self.v[layer], self.v_scale[layer])))
 
 
+class _HeadNorm(nn.Module):
+    """The holder of a Qwen3 q_norm / k_norm: `weight` fp16 [head_dim] (ones at construction) under transformers' state-dict name, and
+    eps.  It has no forward: the norm runs inside the rope_qkv_norm* launch of the attention module that owns it."""
+
+    def __init__(self, head_dim: int, eps: float):
+        super().__init__()
+        self.eps = float(eps)
+        self.weight = nn.Parameter(torch.ones(head_dim, dtype=torch.float16), requires_grad=False)
+
+
 def _drop_fused_qkv_on_load(module, *args, **kwargs):
     module._qkv = None  # a state-dict is being loaded: the fused q|k|v copy would be stale
 
@@ -133,13 +145,18 @@ class QuantLlamaAttention(nn.Module):
     forward_int8(xq, s1, cache, start): (xq int8 [b*s, hidden], s1 f32 [b*s, 1]) as QuantRMSNorm returns them, tokens at positions
     start ... start+s-1 (the same for every batch row) -> fp16 [b*s, hidden].  forward(x, cache, start) quantises its fp16 input first.
     With a PagedKVCache `start` is a PagedStep and xq [m, hidden] holds the sequences' tokens packed in order (see the module docstring).
-    Llama: qkv_bias = o_bias = config.attention_bias;  Qwen2: qkv_bias=True, o_bias=False."""
+    Llama: qkv_bias = o_bias = config.attention_bias;  Qwen2: qkv_bias=True, o_bias=False.
+    Qwen3: qk_norm=True -- the module owns q_norm.weight and k_norm.weight (fp16 [head_dim], transformers' names), a per-head RMSNorm with
+    eps = rms_norm_eps between the q / k projections and RoPE, and every RoPE / cache-write launch is its rope_qkv_norm* counterpart
+    (the norm runs inside that launch).  Without qk_norm nothing of this is registered, allocated or run."""
 
     def __init__(self, hidden: int, num_heads: int, num_kv_heads: int, group_size: int, head_dim: Optional[int] = None,
                  qkv_bias: bool = False, o_bias: bool = False, rope_theta: float = 10000.0, rope_scaling: Optional[dict] = None,
-                 layer_idx: int = 0):
+                 layer_idx: int = 0, qk_norm: bool = False, rms_norm_eps: float = 1e-6):
         super().__init__()
         head_dim = head_dim or hidden // num_heads
+        if qk_norm and head_dim not in (64, 128):
+            raise ValueError(f"qk_norm needs head_dim 64 or 128, not {head_dim}")
         if num_heads % num_kv_heads:
             raise ValueError(f"num_heads {num_heads} must be a multiple of num_kv_heads {num_kv_heads}")
         if head_dim % 16 or head_dim > 256:
@@ -151,6 +168,9 @@ class QuantLlamaAttention(nn.Module):
         self.k_proj = QuantLinear(4, group_size, hidden, num_kv_heads * head_dim, bias=qkv_bias)
         self.v_proj = QuantLinear(4, group_size, hidden, num_kv_heads * head_dim, bias=qkv_bias)
         self.o_proj = QuantLinear(4, group_size, num_heads * head_dim, hidden, bias=o_bias)
+        self.qk_norm = bool(qk_norm)
+        if self.qk_norm:
+            self.q_norm, self.k_norm = _HeadNorm(head_dim, rms_norm_eps), _HeadNorm(head_dim, rms_norm_eps)
         self.inv_freq, self.attention_scaling = rope_inv_freq(head_dim, rope_theta, rope_scaling)  # plain attributes: not in the state-dict
         self._cos = self._sin = None  # rope tables, built lazily up to the cache capacity on the module's device
         self._qkv = None  # fuse_qkv(): the fused q|k|v layer, kept outside the module tree (not in the state-dict)
@@ -330,7 +350,11 @@ class QuantLlamaAttention(nn.Module):
         o_lora = lora("o_proj") if lora is not None else None
         q, k, v = self.project_qkv(xq, s1) if lora is None else self.project_qkv(xq, s1, lora)
         pools = (cache.k[li], cache.v[li]) + ((cache.k_scale[li], cache.v_scale[li]) if cache.quantized else ())
-        q_out = (ops.rope_qkv_paged_kv8 if cache.quantized else ops.rope_qkv_paged)(q, k, v, cos, sin, step.pos, step.slots, *pools)
+        if self.qk_norm:
+            q_out = (ops.rope_qkv_norm_paged_kv8 if cache.quantized else ops.rope_qkv_norm_paged)(
+                q, k, v, self.q_norm.weight, self.k_norm.weight, self.q_norm.eps, cos, sin, step.pos, step.slots, *pools)
+        else:
+            q_out = (ops.rope_qkv_paged_kv8 if cache.quantized else ops.rope_qkv_paged)(q, k, v, cos, sin, step.pos, step.slots, *pools)
         if step.decode and self._shared and step.family is not None:  # fuse_shared(): siblings read their common keys once per pack
             shared = ops.decode_attention_paged_shared_kv8 if cache.quantized else ops.decode_attention_paged_shared
             pack = min(int(step.family_max), 64 // (self.num_heads // self.num_key_value_heads))
@@ -377,12 +401,18 @@ class QuantLlamaAttention(nn.Module):
         kc, vc = cache.k[self.layer_idx], cache.v[self.layer_idx]
         if cache.quantized:  # the int8 cache is the opt-in: one-token steps take its decode kernel whatever fuse_decode() says
             ksc, vsc = cache.k_scale[self.layer_idx], cache.v_scale[self.layer_idx]
-            q_out = ops.rope_qkv_kv8(q, k, v, cos, sin, pos, kc, vc, ksc, vsc)
+            if self.qk_norm:
+                q_out = ops.rope_qkv_norm_kv8(q, k, v, self.q_norm.weight, self.k_norm.weight, self.q_norm.eps, cos, sin, pos, kc, vc, ksc, vsc)
+            else:
+                q_out = ops.rope_qkv_kv8(q, k, v, cos, sin, pos, kc, vc, ksc, vsc)
             if s == 1:
                 aq, a1 = ops.decode_attention_kv8(q_out, kc, vc, ksc, vsc, pos, self.scaling, max_len=start + 1)
                 return self.o_proj.forward_int8(aq, a1)
         else:
-            q_out = ops.rope_qkv(q, k, v, cos, sin, pos, kc, vc)
+            if self.qk_norm:
+                q_out = ops.rope_qkv_norm(q, k, v, self.q_norm.weight, self.k_norm.weight, self.q_norm.eps, cos, sin, pos, kc, vc)
+            else:
+                q_out = ops.rope_qkv(q, k, v, cos, sin, pos, kc, vc)
             if self._decode and s == 1 and self._decode_supported():
                 aq, a1 = ops.decode_attention(q_out, kc, vc, pos, self.scaling, max_len=start + 1)
                 return self.o_proj.forward_int8(aq, a1)
@@ -412,25 +442,30 @@ class QuantLlamaDecoderLayer(nn.Module):
 
     def __init__(self, hidden: int, num_heads: int, num_kv_heads: int, intermediate: int, group_size: int, head_dim: Optional[int] = None,
                  qkv_bias: bool = False, o_bias: bool = False, rms_norm_eps: float = 1e-6, rope_theta: float = 10000.0,
-                 rope_scaling: Optional[dict] = None, layer_idx: int = 0):
+                 rope_scaling: Optional[dict] = None, layer_idx: int = 0, qk_norm: bool = False):
         super().__init__()
         self.hidden_size = hidden
         self.self_attn = QuantLlamaAttention(hidden, num_heads, num_kv_heads, group_size, head_dim=head_dim, qkv_bias=qkv_bias,
-                                             o_bias=o_bias, rope_theta=rope_theta, rope_scaling=rope_scaling, layer_idx=layer_idx)
+                                             o_bias=o_bias, rope_theta=rope_theta, rope_scaling=rope_scaling, layer_idx=layer_idx,
+                                             qk_norm=qk_norm, rms_norm_eps=rms_norm_eps)
         self.mlp = QuantLlamaMLP(hidden, intermediate, group_size)
         self.input_layernorm = QuantRMSNorm(hidden, eps=rms_norm_eps)
         self.post_attention_layernorm = QuantRMSNorm(hidden, eps=rms_norm_eps)
 
     @classmethod
     def from_config(cls, config, group_size: int, layer_idx: int = 0):
-        """The layer of a transformers LlamaConfig or Qwen2Config (duck-typed, 4.x or 5.x attribute style).  Qwen2: q/k/v with bias, o
-        without; Llama: all four follow `attention_bias`.  Sliding-window Qwen2 and rope types other than "default" / "llama3" raise
-        NotImplementedError."""
+        """The layer of a transformers LlamaConfig, Qwen2Config or Qwen3Config (duck-typed, 4.x or 5.x attribute style).  Qwen2: q/k/v
+        with bias, o without; Llama and Qwen3: all four follow `attention_bias`; Qwen3: q_norm / k_norm (qk_norm=True), head_dim from the
+        config.  Sliding-window Qwen2 / Qwen3 (`use_sliding_window`, or a `layer_types` entry other than "full_attention") and rope types
+        other than "default" / "llama3" raise NotImplementedError."""
         if getattr(config, "hidden_act", "silu") != "silu":
             raise NotImplementedError(f"hidden_act {config.hidden_act!r}: only SiLU MLPs are supported")
         qwen2 = getattr(config, "model_type", "") == "qwen2"
-        if qwen2 and getattr(config, "use_sliding_window", False):
+        qwen3 = getattr(config, "model_type", "") == "qwen3"
+        if (qwen2 or qwen3) and getattr(config, "use_sliding_window", False):
             raise NotImplementedError("sliding-window attention is not supported")
+        if qwen3 and any(t != "full_attention" for t in (getattr(config, "layer_types", None) or ())):
+            raise NotImplementedError("layer_types other than 'full_attention' (sliding-window layers) are not supported")
         theta, rope = _config_rope(config)
         heads = config.num_attention_heads
         kv = getattr(config, "num_key_value_heads", None) or heads
@@ -438,7 +473,7 @@ class QuantLlamaDecoderLayer(nn.Module):
         return cls(config.hidden_size, heads, kv, config.intermediate_size, group_size,
                    head_dim=getattr(config, "head_dim", None) or config.hidden_size // heads,
                    qkv_bias=True if qwen2 else bias, o_bias=False if qwen2 else bias, rms_norm_eps=config.rms_norm_eps,
-                   rope_theta=theta, rope_scaling=rope, layer_idx=layer_idx)
+                   rope_theta=theta, rope_scaling=rope, layer_idx=layer_idx, qk_norm=qwen3)
 
     def fuse_decode(self):
         """self_attn.fuse_decode(): one-token steps take the split-K decode attention kernel.  Returns self."""

@@ -77,6 +77,8 @@
 #include "../../include/qqq_amd_kv8.h"
 #include "qqq_paged.hip.h"
 #include "../../include/qqq_amd_paged.h"
+#include "qqq_qknorm.hip.h"
+#include "../../include_ops/qqq_amd_qknorm.h"
 #include "qqq_prefill.hip.h"
 #include "../../include/qqq_amd_prefill.h"
 #include "qqq_sample.hip.h"
@@ -857,6 +859,116 @@ extern "C" int qqq_rope_qkv_paged_kv8(const void* q, int ld_q, const void* k, in
                                       int block_size, int dev, void* stream) {
   return rope_qkv_paged("qqq_rope_qkv_paged_kv8", true, q, ld_q, k, ld_k, v, ld_v, cos, sin, table_len, pos, slots, q_out, k_pool, v_pool,
                         k_scale, v_scale, m, h, kvh, d, num_blocks, block_size, dev, stream);
+}
+
+// ---- Qwen3's per-head q / k RMSNorm in front of the rotation (include_ops/qqq_amd_qknorm.h; kernel in qqq_qknorm.hip.h): the four RoPE /
+// cache-write launches above with one kernel template of their own.  One body for the four; `name` is the entry point's.  The static
+// cache comes as (b, s, cap) with slots = nullptr, the pool as (m, num_blocks, block_size) with b = m, s = 1.
+static int rope_qkv_norm(const char* name, bool paged, bool kv8, const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v,
+                         const void* q_weight, const void* k_weight, float eps, const void* cos, const void* sin, int table_len,
+                         const void* pos, const void* slots, void* q_out, void* k_dst, void* v_dst, void* k_scale, void* v_scale, int b,
+                         int s, int h, int kvh, int d, int cap, int num_blocks, int block_size, int dev, void* stream) {
+  g_err[0] = 0;
+  if (b < 0 || s < 0 || h < 0 || kvh < 0 || d < 0 || cap < 0 || num_blocks < 0 || block_size < 0 || table_len < 0) {
+    if (paged)
+      snprintf(g_err, sizeof(g_err), "%s: negative size (m=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_len=%d)", name, b, h, kvh,
+               d, num_blocks, block_size, table_len);
+    else
+      snprintf(g_err, sizeof(g_err), "%s: negative size (b=%d s=%d h=%d kvh=%d d=%d cap=%d table_len=%d)", name, b, s, h, kvh, d, cap,
+               table_len);
+    return QQQ_ERR_ARG;
+  }
+  if (b == 0 || s == 0) return QQQ_OK;
+  const int lbs = paged ? paged_log2_block(block_size) : 0;
+  if ((long long)b * s > 0x7fffffffLL || h < 1 || kvh < 1 || h % kvh != 0 || (d != 64 && d != 128) ||
+      (long long)(h + 2LL * kvh) * d > (1LL << 20) ||
+      (paged && (lbs < 0 || num_blocks < 1 || (long long)num_blocks * block_size > 0x7fffffffLL))) {
+    if (paged)
+      snprintf(g_err, sizeof(g_err), "%s: bad shape m=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d (need h %% kvh == 0, d 64 or 128, "
+               "(h + 2 kvh) d <= 2^20, block_size a power of two in [16, 256], num_blocks >= 1, num_blocks * block_size < 2^31)", name, b,
+               h, kvh, d, num_blocks, block_size);
+    else
+      snprintf(g_err, sizeof(g_err), "%s: bad shape b=%d s=%d h=%d kvh=%d d=%d (need b*s < 2^31, h %% kvh == 0, d 64 or 128, "
+               "(h + 2 kvh) d <= 2^20)", name, b, s, h, kvh, d);
+    return QQQ_ERR_ARG;
+  }
+  if (ld_q < h * d || ld_k < kvh * d || ld_v < kvh * d || ld_q % 8 || ld_k % 8 || ld_v % 8) {
+    snprintf(g_err, sizeof(g_err), "%s: bad row strides ld_q=%d ld_k=%d ld_v=%d (need multiples of 8, >= h*d=%d / kvh*d=%d)", name, ld_q,
+             ld_k, ld_v, h * d, kvh * d);
+    return QQQ_ERR_ARG;
+  }
+  if (!(eps >= 0.f) || eps > 3.0e38f) {
+    snprintf(g_err, sizeof(g_err), "%s: bad eps %g (need a finite eps >= 0)", name, (double)eps);
+    return QQQ_ERR_ARG;
+  }
+  if (!q || !k || !v || !q_weight || !k_weight || !cos || !sin || !pos || (paged && !slots) || !q_out || !k_dst || !v_dst ||
+      misaligned(q, 16) || misaligned(k, 16) || misaligned(v, 16) || misaligned(q_weight, 16) || misaligned(k_weight, 16) ||
+      misaligned(cos, 16) || misaligned(sin, 16) || misaligned(pos, 8) || (paged && misaligned(slots, 8)) || misaligned(q_out, 16) ||
+      misaligned(k_dst, 16) || misaligned(v_dst, 16) ||
+      (kv8 && (!k_scale || !v_scale || misaligned(k_scale, 4) || misaligned(v_scale, 4)))) {
+    snprintf(g_err, sizeof(g_err), "%s: bad argument (every pointer must be non-NULL; fp16 tensors, the norm weights and the %s 16-byte, "
+             "pos%s 8-byte, the scales 4-byte aligned)", name, paged ? "pools" : "caches", paged ? " / slots" : "");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  const int items = (h + 2 * kvh) * (d / 16);
+  const dim3 grid(b * s, (items + ROPE_NT - 1) / ROPE_NT);
+  const long long limit = paged ? table_len : (cap < table_len ? cap : table_len);
+  const long long nslots = (long long)num_blocks * block_size;
+  const int where = paged ? lbs : cap;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define QQQ_QKNORM_LAUNCH(PAGED, KV8)                                                                                                      \
+  hipLaunchKernelGGL((qqq_rope_qkv_norm_kernel<ROPE_NT, PAGED, KV8>), grid, dim3(ROPE_NT), 0, st, static_cast<const _Float16*>(q), ld_q,   \
+                     static_cast<const _Float16*>(k), ld_k, static_cast<const _Float16*>(v), ld_v,                                         \
+                     static_cast<const _Float16*>(q_weight), static_cast<const _Float16*>(k_weight), eps,                                  \
+                     static_cast<const _Float16*>(cos), static_cast<const _Float16*>(sin), static_cast<const long long*>(pos), limit,      \
+                     static_cast<const long long*>(slots), nslots, static_cast<_Float16*>(q_out), k_dst, v_dst,                            \
+                     static_cast<float*>(k_scale), static_cast<float*>(v_scale), s, h, kvh, d, where)
+  if (paged && kv8)
+    QQQ_QKNORM_LAUNCH(true, true);
+  else if (paged)
+    QQQ_QKNORM_LAUNCH(true, false);
+  else if (kv8)
+    QQQ_QKNORM_LAUNCH(false, true);
+  else
+    QQQ_QKNORM_LAUNCH(false, false);
+#undef QQQ_QKNORM_LAUNCH
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_rope_qkv_norm_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_rope_qkv_norm(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, const void* q_weight,
+                                 const void* k_weight, float eps, const void* cos, const void* sin, int table_len, const void* pos,
+                                 void* q_out, void* k_cache, void* v_cache, int b, int s, int h, int kvh, int d, int cap, int dev,
+                                 void* stream) {
+  return rope_qkv_norm("qqq_rope_qkv_norm", false, false, q, ld_q, k, ld_k, v, ld_v, q_weight, k_weight, eps, cos, sin, table_len, pos,
+                       nullptr, q_out, k_cache, v_cache, nullptr, nullptr, b, s, h, kvh, d, cap, 0, 0, dev, stream);
+}
+
+extern "C" int qqq_rope_qkv_norm_kv8(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, const void* q_weight,
+                                     const void* k_weight, float eps, const void* cos, const void* sin, int table_len, const void* pos,
+                                     void* q_out, void* k_cache, void* v_cache, void* k_scale, void* v_scale, int b, int s, int h, int kvh,
+                                     int d, int cap, int dev, void* stream) {
+  return rope_qkv_norm("qqq_rope_qkv_norm_kv8", false, true, q, ld_q, k, ld_k, v, ld_v, q_weight, k_weight, eps, cos, sin, table_len, pos,
+                       nullptr, q_out, k_cache, v_cache, k_scale, v_scale, b, s, h, kvh, d, cap, 0, 0, dev, stream);
+}
+
+extern "C" int qqq_rope_qkv_norm_paged(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, const void* q_weight,
+                                       const void* k_weight, float eps, const void* cos, const void* sin, int table_len, const void* pos,
+                                       const void* slots, void* q_out, void* k_pool, void* v_pool, int m, int h, int kvh, int d,
+                                       int num_blocks, int block_size, int dev, void* stream) {
+  return rope_qkv_norm("qqq_rope_qkv_norm_paged", true, false, q, ld_q, k, ld_k, v, ld_v, q_weight, k_weight, eps, cos, sin, table_len,
+                       pos, slots, q_out, k_pool, v_pool, nullptr, nullptr, m, 1, h, kvh, d, 0, num_blocks, block_size, dev, stream);
+}
+
+extern "C" int qqq_rope_qkv_norm_paged_kv8(const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v, const void* q_weight,
+                                           const void* k_weight, float eps, const void* cos, const void* sin, int table_len,
+                                           const void* pos, const void* slots, void* q_out, void* k_pool, void* v_pool, void* k_scale,
+                                           void* v_scale, int m, int h, int kvh, int d, int num_blocks, int block_size, int dev,
+                                           void* stream) {
+  return rope_qkv_norm("qqq_rope_qkv_norm_paged_kv8", true, true, q, ld_q, k, ld_k, v, ld_v, q_weight, k_weight, eps, cos, sin, table_len,
+                       pos, slots, q_out, k_pool, v_pool, k_scale, v_scale, m, 1, h, kvh, d, 0, num_blocks, block_size, dev, stream);
 }
 
 static int decode_attn_paged(const char* name, bool kv8, const void* q, const void* k_pool, const void* v_pool, const void* k_scale,

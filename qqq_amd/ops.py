@@ -875,6 +875,188 @@ def rope_qkv_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: t
     return _rope_qkv_paged_impl(*ts)
 
 
+# ---- Qwen3's per-head q / k RMSNorm fused into the four RoPE / cache-write ops above (include_ops/qqq_amd_qknorm.h): still one launch each.
+
+def _qknorm_check(name, q, k, v, cos, sin, idx, q_weight, k_weight, eps, d):
+    if any(t.dtype != torch.float16 for t in (q, k, v, cos, sin, q_weight, k_weight)) or any(t.dtype != torch.int64 for t in idx):
+        raise RuntimeError(f"{name}: q, k, v, cos, sin and the norm weights must be fp16, {' and '.join(('pos', 'slots')[:len(idx)])} int64")
+    if d not in (64, 128):
+        raise RuntimeError(f"{name}: head_dim {d} is not supported (the fused q / k norm takes 64 or 128)")
+    if q_weight.shape != (d,) or k_weight.shape != (d,):
+        raise RuntimeError(f"{name}: q_weight {tuple(q_weight.shape)} and k_weight {tuple(k_weight.shape)} must be fp16 [{d}]")
+    if sin.shape != cos.shape:
+        raise RuntimeError(f"{name}: sin must have cos's shape")
+    if not (0.0 <= float(eps) < float("inf")):
+        raise RuntimeError(f"{name}: eps {eps} must be finite and >= 0")
+
+
+def _norm_weight(w):
+    # [d] fp16 where the kernel can read it: contiguous, 16-byte aligned (a copy otherwise; a Parameter's storage is both)
+    w = w.contiguous()
+    return w if w.data_ptr() % 16 == 0 else w.clone()
+
+
+def _rope_qkv_norm_impl(q, k, v, q_weight, k_weight, eps, cos, sin, pos, k_cache, v_cache, k_scale=None, v_scale=None):
+    kv8 = k_scale is not None
+    name = "rope_qkv_norm_kv8" if kv8 else "rope_qkv_norm"
+    ts = (q, k, v, q_weight, k_weight, cos, sin, pos, k_cache, v_cache) + ((k_scale, v_scale) if kv8 else ())
+    _same_gpu(name, ts)
+    if kv8:
+        _kv8_check_caches(name, k_cache, v_cache, k_scale, v_scale)
+    else:
+        if k_cache.dtype != torch.float16 or v_cache.dtype != torch.float16 or k_cache.dim() != 4 or v_cache.shape != k_cache.shape:
+            raise RuntimeError(f"{name}: k_cache and v_cache must be fp16 [b, kvh, cap, d] of one shape")
+        for nm, t in (("k_cache", k_cache), ("v_cache", v_cache)):
+            if not t.is_contiguous():
+                raise RuntimeError(f"{name}: {nm} must be contiguous (it is written in place)")
+    try:
+        b, s, h, kvh, d, cap = _rope_qkv_shapes(q, k, v, cos, pos, k_cache)
+    except RuntimeError as e:
+        raise RuntimeError(str(e).replace("rope_qkv:", name + ":", 1)) from None
+    _qknorm_check(name, q, k, v, cos, sin, (pos,), q_weight, k_weight, eps, d)
+    q_out = torch.empty((b, h, s, d), dtype=torch.float16, device=q.device)
+    if q_out.numel() == 0:
+        return q_out
+    (q2, ld_q), (k2, ld_k), (v2, ld_v) = _rows(q, h * d), _rows(k, kvh * d), _rows(v, kvh * d)
+    cos, sin, pos, qw, kw = cos.contiguous(), sin.contiguous(), pos.contiguous(), _norm_weight(q_weight), _norm_weight(k_weight)
+    L = _lib.lib()
+    head = (_ptr(q2), ld_q, _ptr(k2), ld_k, _ptr(v2), ld_v, _ptr(qw), _ptr(kw), float(eps), _ptr(cos), _ptr(sin), cos.shape[0], _ptr(pos),
+            _ptr(q_out), _ptr(k_cache), _ptr(v_cache))
+    tail = (b, s, h, kvh, d, cap, q.device.index or 0, _stream_for(q))
+    if kv8:
+        err = L.qqq_rope_qkv_norm_kv8(*head, _ptr(k_scale), _ptr(v_scale), *tail)
+    else:
+        err = L.qqq_rope_qkv_norm(*head, *tail)
+    _raise_lib(name, err)
+    return q_out
+
+
+@torch.library.custom_op("qqq_amd::rope_qkv_norm", mutates_args=("k_cache", "v_cache"))
+def _rope_qkv_norm_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_weight: torch.Tensor, k_weight: torch.Tensor, eps: float,
+                      cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
+                      v_cache: torch.Tensor) -> torch.Tensor:
+    return _rope_qkv_norm_impl(q, k, v, q_weight, k_weight, eps, cos, sin, pos, k_cache, v_cache)
+
+
+@_rope_qkv_norm_op.register_fake
+def _(q, k, v, q_weight, k_weight, eps, cos, sin, pos, k_cache, v_cache):
+    b, s, h, _, d, _ = _rope_qkv_shapes(q, k, v, cos, pos, k_cache)
+    return q.new_empty((b, h, s, d), dtype=torch.float16)
+
+
+def rope_qkv_norm(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_weight: torch.Tensor, k_weight: torch.Tensor, eps: float,
+                  cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor) -> torch.Tensor:
+    """rope_qkv with Qwen3's per-head RMSNorm of q and k in front of the rotation, one launch: every q / k head row x becomes
+    fp16(w * fp16(x * rsqrt(mean(x^2) + eps))) -- transformers' Qwen3RMSNorm on fp16, the mean in f64 in the order
+    include_ops/qqq_amd_qknorm.h states -- and is then rotated and stored exactly as rope_qkv does; v is untouched.
+
+    q_weight, k_weight   fp16 [head_dim]: q_norm.weight and k_norm.weight;  eps  rms_norm_eps;  head_dim 64 or 128
+    Everything else, the return value and the out-of-range rule are rope_qkv's."""
+    ts = (q, k, v, q_weight, k_weight, cos, sin, pos, k_cache, v_cache)
+    if _compiling(*ts):
+        return _rope_qkv_norm_op(q, k, v, q_weight, k_weight, float(eps), cos, sin, pos, k_cache, v_cache)
+    return _rope_qkv_norm_impl(q, k, v, q_weight, k_weight, eps, cos, sin, pos, k_cache, v_cache)
+
+
+@torch.library.custom_op("qqq_amd::rope_qkv_norm_kv8", mutates_args=("k_cache", "v_cache", "k_scale", "v_scale"))
+def _rope_qkv_norm_kv8_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_weight: torch.Tensor, k_weight: torch.Tensor, eps: float,
+                          cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                          k_scale: torch.Tensor, v_scale: torch.Tensor) -> torch.Tensor:
+    return _rope_qkv_norm_impl(q, k, v, q_weight, k_weight, eps, cos, sin, pos, k_cache, v_cache, k_scale, v_scale)
+
+
+@_rope_qkv_norm_kv8_op.register_fake
+def _(q, k, v, q_weight, k_weight, eps, cos, sin, pos, k_cache, v_cache, k_scale, v_scale):
+    b, s, h, _, d, _ = _rope_qkv_shapes(q, k, v, cos, pos, k_cache)
+    return q.new_empty((b, h, s, d), dtype=torch.float16)
+
+
+def rope_qkv_norm_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_weight: torch.Tensor, k_weight: torch.Tensor, eps: float,
+                      cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                      k_scale: torch.Tensor, v_scale: torch.Tensor) -> torch.Tensor:
+    """rope_qkv_norm into an int8 cache: q_out is rope_qkv_norm's, every cached row is dynamic_quant of the fp16 row rope_qkv_norm would
+    have cached, bit for bit.  The caches and scales are rope_qkv_kv8's."""
+    ts = (q, k, v, q_weight, k_weight, cos, sin, pos, k_cache, v_cache, k_scale, v_scale)
+    if _compiling(*ts):
+        return _rope_qkv_norm_kv8_op(q, k, v, q_weight, k_weight, float(eps), cos, sin, pos, k_cache, v_cache, k_scale, v_scale)
+    return _rope_qkv_norm_impl(q, k, v, q_weight, k_weight, eps, cos, sin, pos, k_cache, v_cache, k_scale, v_scale)
+
+
+def _rope_qkv_norm_paged_impl(q, k, v, q_weight, k_weight, eps, cos, sin, pos, slots, k_pool, v_pool, k_scale=None, v_scale=None):
+    kv8 = k_scale is not None
+    name = "rope_qkv_norm_paged_kv8" if kv8 else "rope_qkv_norm_paged"
+    ts = (q, k, v, q_weight, k_weight, cos, sin, pos, slots, k_pool, v_pool) + ((k_scale, v_scale) if kv8 else ())
+    _same_gpu(name, ts)
+    _paged_check_pools(name, k_pool, v_pool, k_scale, v_scale)
+    m, h, kvh, d, nb, bs = _rope_qkv_paged_shapes(name, q, k, v, cos, pos, slots, k_pool)
+    _qknorm_check(name, q, k, v, cos, sin, (pos, slots), q_weight, k_weight, eps, d)
+    q_out = torch.empty((m, h, d), dtype=torch.float16, device=q.device)
+    if q_out.numel() == 0:
+        return q_out
+    (q2, ld_q), (k2, ld_k), (v2, ld_v) = _rows(q, h * d), _rows(k, kvh * d), _rows(v, kvh * d)
+    cos, sin, pos, slots = cos.contiguous(), sin.contiguous(), pos.contiguous(), slots.contiguous()
+    qw, kw = _norm_weight(q_weight), _norm_weight(k_weight)
+    L = _lib.lib()
+    head = (_ptr(q2), ld_q, _ptr(k2), ld_k, _ptr(v2), ld_v, _ptr(qw), _ptr(kw), float(eps), _ptr(cos), _ptr(sin), cos.shape[0], _ptr(pos),
+            _ptr(slots), _ptr(q_out), _ptr(k_pool), _ptr(v_pool))
+    tail = (m, h, kvh, d, nb, bs, q.device.index or 0, _stream_for(q))
+    if kv8:
+        err = L.qqq_rope_qkv_norm_paged_kv8(*head, _ptr(k_scale), _ptr(v_scale), *tail)
+    else:
+        err = L.qqq_rope_qkv_norm_paged(*head, *tail)
+    _raise_lib(name, err)
+    return q_out
+
+
+@torch.library.custom_op("qqq_amd::rope_qkv_norm_paged", mutates_args=("k_pool", "v_pool"))
+def _rope_qkv_norm_paged_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_weight: torch.Tensor, k_weight: torch.Tensor, eps: float,
+                            cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor, k_pool: torch.Tensor,
+                            v_pool: torch.Tensor) -> torch.Tensor:
+    return _rope_qkv_norm_paged_impl(q, k, v, q_weight, k_weight, eps, cos, sin, pos, slots, k_pool, v_pool)
+
+
+@_rope_qkv_norm_paged_op.register_fake
+def _(q, k, v, q_weight, k_weight, eps, cos, sin, pos, slots, k_pool, v_pool):
+    m, h, _, d, _, _ = _rope_qkv_paged_shapes("rope_qkv_norm_paged", q, k, v, cos, pos, slots, k_pool)
+    return q.new_empty((m, h, d), dtype=torch.float16)
+
+
+def rope_qkv_norm_paged(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_weight: torch.Tensor, k_weight: torch.Tensor, eps: float,
+                        cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor, k_pool: torch.Tensor,
+                        v_pool: torch.Tensor) -> torch.Tensor:
+    """rope_qkv_paged with Qwen3's per-head RMSNorm of q and k in front of the rotation (rope_qkv_norm's arithmetic), one launch for all m
+    tokens.  q_weight, k_weight fp16 [head_dim], eps rms_norm_eps; everything else, the return value and the padding / out-of-range
+    rules are rope_qkv_paged's."""
+    ts = (q, k, v, q_weight, k_weight, cos, sin, pos, slots, k_pool, v_pool)
+    if _compiling(*ts):
+        return _rope_qkv_norm_paged_op(q, k, v, q_weight, k_weight, float(eps), cos, sin, pos, slots, k_pool, v_pool)
+    return _rope_qkv_norm_paged_impl(q, k, v, q_weight, k_weight, eps, cos, sin, pos, slots, k_pool, v_pool)
+
+
+@torch.library.custom_op("qqq_amd::rope_qkv_norm_paged_kv8", mutates_args=("k_pool", "v_pool", "k_scale", "v_scale"))
+def _rope_qkv_norm_paged_kv8_op(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_weight: torch.Tensor, k_weight: torch.Tensor,
+                                eps: float, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor,
+                                k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor) -> torch.Tensor:
+    return _rope_qkv_norm_paged_impl(q, k, v, q_weight, k_weight, eps, cos, sin, pos, slots, k_pool, v_pool, k_scale, v_scale)
+
+
+@_rope_qkv_norm_paged_kv8_op.register_fake
+def _(q, k, v, q_weight, k_weight, eps, cos, sin, pos, slots, k_pool, v_pool, k_scale, v_scale):
+    m, h, _, d, _, _ = _rope_qkv_paged_shapes("rope_qkv_norm_paged_kv8", q, k, v, cos, pos, slots, k_pool)
+    return q.new_empty((m, h, d), dtype=torch.float16)
+
+
+def rope_qkv_norm_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_weight: torch.Tensor, k_weight: torch.Tensor, eps: float,
+                            cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, slots: torch.Tensor, k_pool: torch.Tensor,
+                            v_pool: torch.Tensor, k_scale: torch.Tensor, v_scale: torch.Tensor) -> torch.Tensor:
+    """rope_qkv_norm_paged into an int8 pool: every cached row as rope_qkv_norm_kv8 stores it, bit for bit.  The pools and scales are
+    rope_qkv_paged_kv8's."""
+    ts = (q, k, v, q_weight, k_weight, cos, sin, pos, slots, k_pool, v_pool, k_scale, v_scale)
+    if _compiling(*ts):
+        return _rope_qkv_norm_paged_kv8_op(q, k, v, q_weight, k_weight, float(eps), cos, sin, pos, slots, k_pool, v_pool, k_scale, v_scale)
+    return _rope_qkv_norm_paged_impl(q, k, v, q_weight, k_weight, eps, cos, sin, pos, slots, k_pool, v_pool, k_scale, v_scale)
+
+
 def _decode_attention_paged_shapes(name, q_out, k_pool, block_table, pos, max_len):
     # (b, h, kvh, d, num_blocks, block_size, table_stride, max_len) from the tensors' shapes
     if k_pool.dim() != 4:

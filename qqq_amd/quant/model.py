@@ -65,6 +65,9 @@ class FloatDecoderLayer:
         q = self._linear("self_attn.q_proj", h).view(b, s, self.heads, self.head_dim).transpose(1, 2)
         k = self._linear("self_attn.k_proj", h).view(b, s, self.kv_heads, self.head_dim).transpose(1, 2)
         v = self._linear("self_attn.v_proj", h).view(b, s, self.kv_heads, self.head_dim).transpose(1, 2)
+        if "self_attn.q_norm.weight" in self.w:  # Qwen3: RMSNorm over head_dim between the q / k projections and RoPE
+            q = _rms_norm(q, self.w["self_attn.q_norm.weight"], self.eps)
+            k = _rms_norm(k, self.w["self_attn.k_norm.weight"], self.eps)
         cos, sin = self._rope(s, x.device)
         q = q * cos + _rotate_half(q) * sin
         k = k * cos + _rotate_half(k) * sin
@@ -165,6 +168,9 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
                     results[prefix + key] = res
         qlayer.input_layernorm.weight.data.copy_(w["input_layernorm.weight"])
         qlayer.post_attention_layernorm.weight.data.copy_(w["post_attention_layernorm.weight"])
+        if qlayer.self_attn.qk_norm:  # Qwen3: the per-head norms go into the packed model as they are
+            qlayer.self_attn.q_norm.weight.data.copy_(w["self_attn.q_norm.weight"])
+            qlayer.self_attn.k_norm.weight.data.copy_(w["self_attn.k_norm.weight"])
         inps = _run(layer, inps, seq_batch)
         del hs
     lm.model.embed_tokens.weight.data.copy_(embed)

@@ -37,6 +37,7 @@ from . import ops
 
 _RIGHT = ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight")
 _LEFT = ("self_attn.o_proj", "mlp.down_proj")  # weight and bias
+_HEAD_NORMS = ("self_attn.q_norm.weight", "self_attn.k_norm.weight")  # Qwen3: carried through, folded nowhere
 _FUSED_BY = {"input_layernorm.weight": ("self_attn.q_proj.weight", "self_attn.k_proj.weight", "self_attn.v_proj.weight"),
              "post_attention_layernorm.weight": ("mlp.gate_proj.weight", "mlp.up_proj.weight")}
 
@@ -281,6 +282,9 @@ def rotate_state_dict(state_dict: dict, config, mode: str = "hadamard", signs: O
         elif tail is not None and tail.rsplit(".", 1)[0] in _LEFT:
             _check_dtype(name, k, W)
             out[k] = left(W)
+        elif tail in _HEAD_NORMS:
+            pass  # Qwen3's q_norm / k_norm act per head on a projection's OUTPUT: the residual rotation is on the input side, the per-head
+            # Hadamard on v / o only, so they pass through as they are (and need not be ones)
         elif k.endswith("norm.weight") or k.endswith("layernorm.weight"):
             if not bool((W == 1).all()):
                 raise RuntimeError(f"{name}: {k} is not all ones: a rotation commutes with RMSNorm only after fuse_layer_norms")

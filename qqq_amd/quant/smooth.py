@@ -58,8 +58,9 @@ def causal_mask(length: int, device, dtype=torch.float16) -> torch.Tensor:
     return torch.full((length, length), torch.finfo(dtype).min, dtype=dtype, device=device).triu(1)[None, None]
 
 
-def attention_extra(config, length: int, device, bias=None) -> dict:
-    """the `extra` of kind "qkv" for a (duck-typed) Llama / Qwen2 config: head counts, RoPE tables [length, head_dim], the causal mask"""
+def attention_extra(config, length: int, device, bias=None, q_norm=None, k_norm=None) -> dict:
+    """the `extra` of kind "qkv" for a (duck-typed) Llama / Qwen2 / Qwen3 config: head counts, RoPE tables [length, head_dim], the causal
+    mask; `q_norm`, `k_norm`: a Qwen3 layer's per-head norm weights [head_dim] (applied to q and k before RoPE, eps = rms_norm_eps)"""
     heads = config.num_attention_heads
     kv_heads = getattr(config, "num_key_value_heads", None) or heads
     head_dim = getattr(config, "head_dim", None) or config.hidden_size // heads
@@ -67,13 +68,15 @@ def attention_extra(config, length: int, device, bias=None) -> dict:
     inv_freq, scaling = rope_inv_freq(head_dim, theta, rope)
     cos, sin = rope_tables(inv_freq, scaling, length, device)
     return {"num_heads": heads, "num_key_value_heads": kv_heads, "head_dim": head_dim, "cos": cos[:length], "sin": sin[:length],
-            "mask": causal_mask(length, device), "bias": bias}
+            "mask": causal_mask(length, device), "bias": bias, "q_norm": q_norm, "k_norm": k_norm, "eps": config.rms_norm_eps}
 
 
 def _attend(q, k, v, extra):
     # q [B, heads, N, d], k and v [B, kv_heads, N, d] -> [B, N, heads * d]; the reference's explicit composition, no SDPA
     B, _, N, d = q.shape
     cos, sin = extra["cos"][None, None], extra["sin"][None, None]
+    if extra.get("q_norm") is not None:  # Qwen3: RMSNorm over head_dim between the projections and RoPE
+        q, k = _rms_norm(q, extra["q_norm"], extra["eps"]), _rms_norm(k, extra["k_norm"], extra["eps"])
     q = q * cos + _rotate_half(q) * sin
     k = k * cos + _rotate_half(k) * sin
     rep = extra["num_heads"] // extra["num_key_value_heads"]
@@ -263,7 +266,7 @@ def smooth_scales(state_dict: dict, config, calib_ids: torch.Tensor, group_size:
         names = ("self_attn.q_proj", "self_attn.k_proj", "self_attn.v_proj")
         biases = [w.get(n + ".bias") for n in names]
         bias = torch.cat(biases) if all(b is not None for b in biases) else None
-        extra = attention_extra(config, N, dev, bias)
+        extra = attention_extra(config, N, dev, bias, w.get("self_attn.q_norm.weight"), w.get("self_attn.k_norm.weight"))
         # q | k | v
         h = _rms_norm(x, w["input_layernorm.weight"], eps)
         wqkv = torch.cat([w[n + ".weight"] for n in names])

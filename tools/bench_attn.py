@@ -46,6 +46,15 @@ KV cache.  Both paths start from the fp16 output of input_layernorm and end with
                 where the medians differ by more than the baseline's spread over the rounds.  The split plan of the call and the number of
                 jointly taken splits are written too.
 
+    qknorm      (--points qknorm [--block-size N]: this mode alone) the RoPE / cache-write launch of a Qwen3 layer alone, three ways over
+                the same fused q|k|v buffer, positions, slots and pool: rope_qkv_norm_paged(_kv8) (`fused`: the per-head q / k RMSNorm
+                inside the launch), the torch composition (`composed`: Qwen3RMSNorm's lines on the q and k views, then
+                rope_qkv_paged(_kv8)), and rope_qkv_paged(_kv8) without any norm (`plain`: fused - plain is what the norm costs).  Qwen3-8B
+                (32 / 8 heads of 128) and Qwen3-32B (64 / 8), {1, 16, 2048} tokens, fp16 and int8 pools.  The `cold` protocol of the shared
+                points (one captured call per timing behind a cache flush, median of SHARED_COLD_CALLS), alternately, QKNORM_ROUNDS times;
+                every round is kept, with median, min and max; `verdict` says wins / loses only where the medians differ by more than the
+                composition's spread over the rounds.
+
 Points: decode (s = 1) at b in {1, 16} with a context of {1024, 4096} tokens (the new token included), and b = 1 at 16384; prefill of s in
 {128, 1024, 4096} tokens at b = 1 from position 0.  Before each point one dynamic_quant of POINT_MARK + i rows is launched: its grid marks
 where point i starts in a kernel trace.
@@ -54,6 +63,7 @@ where point i starts in a kernel trace.
     python tools/bench_attn.py --points prefill --paged [--kv8] [--block-size N] [--out FILE]   -> the paged prefill points alone
     python tools/bench_attn.py --points verify [--kv8] [--block-size N] [--out profiles/verify_attn_bench.json]   -> the verify points alone
     python tools/bench_attn.py --points shared [--kv8] [--block-size N] [--out profiles/shared_attn_bench.json]   -> the shared points alone
+    python tools/bench_attn.py --points qknorm [--block-size N] [--out profiles/qknorm_bench.json]   -> the q / k norm points alone
     python tools/bench_attn.py --summarize TRACE_DIR [--bench FILE]     -> from a rocprofv3 --kernel-trace run of the above: the
                                                                           qqq_rope_qkv_kernel times and HBM fractions, and per decode point
                                                                           (labelled from the run's JSON output FILE) the median times of
@@ -95,6 +105,8 @@ VERIFY_POOL_BYTES = 8 << 30  # K and V pools of a point together
 SHARED_ROUNDS, SHARED_COLD_CALLS = 5, 9  # --points shared: alternations of the two ops at a point; cold calls per alternation
 SHARED_FAMILIES, SHARED_PREFIXES, SHARED_TAIL = (2, 4, 8, 16), (1024, 4096, 16384), 64
 SHARED_FLUSH_BYTES = 1 << 30  # four times the 256 MB Infinity Cache
+QKNORM_SHAPES = {"qwen3_8b": (32, 8), "qwen3_32b": (64, 8)}  # --points qknorm: (heads, KV heads) of 128
+QKNORM_TOKENS, QKNORM_ROUNDS, QKNORM_EPS = (1, 16, 2048), 5, 1e-6
 PREFILL_KERNELS = ("qqq_prefill_attn_kernel", "qqq_prefill_quant_kernel", "qqq_paged_rope_qkv_kernel", "qqq_paged_kv8_rope_qkv_kernel",
                    "qqq_dynamic_quant_kernel")
 SPLIT_KERNELS = ("qqq_decode_split_kernel", "qqq_kv8_decode_split_kernel", "qqq_paged_decode_split_kernel",
@@ -612,6 +624,72 @@ def _run_shared(kv8, block_size):
     return out
 
 
+def run_qknorm(block_size=128):
+    """--points qknorm: see the module docstring"""
+    import statistics
+
+    import torch
+
+    from qqq_amd import ops
+
+    dev = torch.device("cuda:0")
+    out = {"tool": "tools/bench_attn.py --points qknorm", "device": torch.cuda.get_device_name(0), "head_dim": D, "block_size": block_size,
+           "eps": QKNORM_EPS, "rounds": QKNORM_ROUNDS,
+           "unit": "us per call; cold: one captured call behind a cache flush, median of %d; per op the rounds, their median, min and max"
+                   % SHARED_COLD_CALLS, "points": []}
+    g = torch.Generator(device=dev).manual_seed(13)
+    flush = torch.zeros(SHARED_FLUSH_BYTES // 4, dtype=torch.int32, device=dev)
+
+    def hf_norm(x, w):  # transformers' Qwen3RMSNorm.forward, line for line
+        dtype = x.dtype
+        x = x.to(torch.float32)
+        variance = x.pow(2).mean(-1, keepdim=True)
+        x = x * torch.rsqrt(variance + QKNORM_EPS)
+        return w * x.to(dtype)
+
+    for shape, (h, kvh) in QKNORM_SHAPES.items():
+        for kv8 in (False, True):
+            for m in QKNORM_TOKENS:
+                nb = -(-m // block_size) + 1
+                if kv8:
+                    pools = tuple(torch.zeros((nb, kvh, block_size, D), dtype=torch.int8, device=dev) for _ in range(2))
+                    pools += tuple(torch.zeros((nb, kvh, block_size), dtype=torch.float32, device=dev) for _ in range(2))
+                else:
+                    pools = tuple(torch.zeros((nb, kvh, block_size, D), dtype=torch.float16, device=dev) for _ in range(2))
+                nq, nk = h * D, kvh * D
+                qkv = torch.randn((m, nq + 2 * nk), generator=g, device=dev).half()  # the fused GEMM's output, read in place
+                q, k, v = qkv[:, :nq], qkv[:, nq:nq + nk], qkv[:, nq + nk:]
+                qw = (1 + 0.3 * torch.randn(D, generator=g, device=dev)).half()
+                kw = (1 + 0.3 * torch.randn(D, generator=g, device=dev)).half()
+                cos, sin = (torch.rand((m + 8, D), generator=g, device=dev) * 2 - 1).half(), (torch.rand((m + 8, D), generator=g, device=dev) * 2 - 1).half()
+                pos = torch.arange(m, device=dev)
+                slots = torch.randperm(nb * block_size, generator=torch.Generator().manual_seed(m))[:m].to(dev)
+                fused_op = ops.rope_qkv_norm_paged_kv8 if kv8 else ops.rope_qkv_norm_paged
+                plain_op = ops.rope_qkv_paged_kv8 if kv8 else ops.rope_qkv_paged
+                fns = {"fused": lambda: fused_op(q, k, v, qw, kw, QKNORM_EPS, cos, sin, pos, slots, *pools),
+                       "composed": lambda: plain_op(hf_norm(q.view(m, h, D), qw).view(m, nq), hf_norm(k.view(m, kvh, D), kw).view(m, nk), v,
+                                                    cos, sin, pos, slots, *pools),
+                       "plain": lambda: plain_op(q, k, v, cos, sin, pos, slots, *pools)}
+                runs = {name: [] for name in fns}
+                for _ in range(QKNORM_ROUNDS):
+                    for name, fn in fns.items():
+                        runs[name].append(round(_time_cold(torch, fn, flush, SHARED_COLD_CALLS), 2))
+                pt = {"shape": shape, "pool": "int8" if kv8 else "fp16", "heads": h, "kv_heads": kvh, "tokens": m}
+                for name, r in runs.items():
+                    pt[name] = {"median_us": round(statistics.median(r), 2), "min_us": min(r), "max_us": max(r), "rounds_us": r}
+                spread = round(pt["composed"]["max_us"] - pt["composed"]["min_us"], 2)
+                pt["composed_round_spread_us"] = spread
+                pt["fused_over_composed"] = round(pt["fused"]["median_us"] / pt["composed"]["median_us"], 3)
+                pt["norm_cost_us"] = round(pt["fused"]["median_us"] - pt["plain"]["median_us"], 2)  # what the norm adds to the launch
+                pt["plain_round_spread_us"] = round(pt["plain"]["max_us"] - pt["plain"]["min_us"], 2)
+                pt["verdict"] = ("wins" if pt["fused"]["median_us"] < pt["composed"]["median_us"] - spread else
+                                 "loses" if pt["fused"]["median_us"] > pt["composed"]["median_us"] + spread else "ties")
+                out["points"].append(pt)
+                print(json.dumps(pt), file=sys.stderr, flush=True)
+                del pools
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", default="decode,prefill")
@@ -630,6 +708,8 @@ def main():
         res = run_verify(kv8=a.kv8, block_size=a.block_size)
     elif a.points == "shared":
         res = run_shared(kv8=a.kv8, block_size=a.block_size)
+    elif a.points == "qknorm":
+        res = run_qknorm(block_size=a.block_size)
     elif a.paged and a.points == "prefill":
         res = run_paged_prefill([int(v) for v in a.group_sizes.split(",")], kv8=a.kv8, block_size=a.block_size)
     else:

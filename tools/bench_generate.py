@@ -84,6 +84,15 @@ profiles/guided_loop_bench.json: both step times with the rounds' min and max, t
 both runs over the rounds.  No threshold: the feature is opt-in.  The ops alone are in profiles/fsm_bench.json (tools/bench_sample.py --fsm).
 
     python tools/bench_generate.py --guided [--batch 1,16] [--rounds 5] [--out profiles/guided_loop_bench.json]
+
+With --qwen3 the model is four Qwen3-8B-shaped layers (hidden 4096, 32 / 8 heads of 128, intermediate 12288, random q_norm / k_norm) and
+the tool times the replayed step of a DecodeLoop three ways in one rotation, by the protocol above: `fused` (ops.rope_qkv_norm_paged, the
+per-head norm inside the RoPE / cache-write launch), `composed` (the same loop with that op replaced by Qwen3RMSNorm's torch lines on the
+q and k views and ops.rope_qkv_paged) and `no_norm` (the layers with qk_norm off: another function, it shows what the norm costs in a
+step).  Written to profiles/qwen3_loop_bench.json: the step times with the rounds' min and max, the two differences, the largest spread
+of the rounds, and whether each difference exceeds it.
+
+    python tools/bench_generate.py --qwen3 [--batch 1,16] [--rounds 5] [--out profiles/qwen3_loop_bench.json]
 """
 import argparse
 import json
@@ -759,8 +768,133 @@ def parallel_main(args):
                                              for k in ("repeated", "forked", "forked_shared") if k in p))
 
 
+QWEN3_8B = dict(model_type="qwen3", vocab_size=32000, hidden_size=4096, num_attention_heads=32, num_key_value_heads=8, head_dim=128,
+                intermediate_size=12288, num_hidden_layers=LAYERS, rms_norm_eps=1e-6, rope_theta=1000000.0, attention_bias=False,
+                tie_word_embeddings=False)  # Qwen3-8B's layer; the vocabulary is the other modes' 32000, not its 151936
+
+
+def build_qwen3(dev):
+    import types
+
+    import torch
+
+    from qqq_amd import QuantLlamaForCausalLM, pack
+
+    lm = QuantLlamaForCausalLM.from_config(types.SimpleNamespace(**QWEN3_8B), -1).to(dev)
+    g = torch.Generator(device=dev).manual_seed(0)
+    for mod in lm.modules():
+        if hasattr(mod, "s_channel"):
+            k, n = mod.infeatures, mod.outfeatures
+            mod.B.copy_(pack.pack_codes(torch.randint(-7, 8, (k, n), generator=g, dtype=torch.int8, device=dev), False))
+            mod.s_channel.copy_(torch.rand((1, n), generator=g, device=dev) * 2e-4 + 1e-5)
+    for layer in lm.model.layers:
+        for norm in (layer.self_attn.q_norm, layer.self_attn.k_norm):
+            norm.weight.data = (1 + 0.3 * torch.randn(norm.weight.shape, generator=g, device=dev)).half()
+    lm.model.embed_tokens.weight.data = torch.randn((lm.model.embed_tokens.weight.shape), generator=g, device=dev).half()
+    lm.lm_head.weight.data = (0.05 * torch.randn(lm.lm_head.weight.shape, generator=g, device=dev)).half()
+    return lm.eval().fuse_qkv()
+
+
+def torch_qknorm_in_step(plain_op):
+    """ops.rope_qkv_norm_paged(_kv8) from torch calls that are safe inside a captured step: Qwen3RMSNorm's lines on the q and k views of
+    the fused GEMM output, then the op without the norm"""
+    import torch
+
+    def norm(x, w, eps, d):
+        rows = x.reshape(x.shape[0], -1, d)
+        h = rows.to(torch.float32)
+        h = h * torch.rsqrt(h.pow(2).mean(-1, keepdim=True) + eps)
+        return (w * h.to(x.dtype)).reshape(x.shape[0], -1)
+
+    def composed(q, k, v, q_weight, k_weight, eps, cos, sin, pos, slots, *pools):
+        d = q_weight.shape[0]
+        return plain_op(norm(q, q_weight, eps, d), norm(k, k_weight, eps, d), v, cos, sin, pos, slots, *pools)
+
+    return composed
+
+
+def qwen3_point(lm, batch, rounds, dev):
+    import torch
+
+    from qqq_amd import DecodeLoop, ops
+
+    vocab = QWEN3_8B["vocab_size"]
+    g = torch.Generator().manual_seed(batch)
+    prompts = [torch.randint(0, vocab, (PROMPT,), generator=g).tolist() for _ in range(batch)]
+    max_len = -(-(PROMPT + NEW - 1) // BS) * BS
+    loops = {name: DecodeLoop(lm, lm.new_cache(batch * (max_len // BS), BS), rows=batch, max_len=max_len, sync_every=SYNC_EVERY)
+             for name in ("fused", "composed", "no_norm")}
+    fused_op = ops.rope_qkv_norm_paged
+    composed_op = torch_qknorm_in_step(ops.rope_qkv_paged)
+
+    def timed(name, n):
+        # a loop captures its step in the warm-up under its own variant; the eager prefill of every run follows the same switch
+        ops.rope_qkv_norm_paged = composed_op if name == "composed" else fused_op
+        for layer in lm.model.layers:
+            layer.self_attn.qk_norm = name != "no_norm"
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = loops[name].generate(prompts, n)
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, out
+        finally:
+            ops.rope_qkv_norm_paged = fused_op
+            for layer in lm.model.layers:
+                layer.self_attn.qk_norm = True
+
+    tokens = {}
+    for name in loops:  # warm-up: code objects, workspaces, rope tables, the capture
+        timed(name, 1)
+        tokens[name] = timed(name, NEW)[1]
+        assert all(len(o) == NEW for o in tokens[name]), name
+    values = {name: [] for name in loops}
+    for _ in range(rounds):
+        for name in loops:
+            short, full = timed(name, 1)[0], timed(name, NEW)[0]
+            values[name].append((full - short) / (NEW - 1) * 1e6)
+    res = {"batch": batch, "prompt_tokens": PROMPT, "new_tokens": NEW, "layers": LAYERS}
+    for name, v in values.items():
+        res[name] = {"step_us": round(statistics.median(v), 1), "step_us_min": round(min(v), 1), "step_us_max": round(max(v), 1),
+                     "rounds_step_us": [round(x, 1) for x in v]}
+    spread = max(res[n]["step_us_max"] - res[n]["step_us_min"] for n in loops)
+    res["largest_round_spread_us"] = round(spread, 1)
+    res["composed_minus_fused_us_per_step"] = round(res["composed"]["step_us"] - res["fused"]["step_us"], 1)
+    res["fused_minus_no_norm_us_per_step"] = round(res["fused"]["step_us"] - res["no_norm"]["step_us"], 1)
+    res["fused_below_composed_by_more_than_the_spread"] = bool(res["composed"]["step_us"] - res["fused"]["step_us"] > spread)
+    res["norm_cost_exceeds_the_spread"] = bool(res["fused"]["step_us"] - res["no_norm"]["step_us"] > spread)
+    res["composed_tokens_equal_fused"] = tokens["composed"] == tokens["fused"]
+    return res
+
+
+def qwen3_main(args):
+    import torch
+
+    dev = torch.device("cuda:0")
+    lm = build_qwen3(dev).fuse_prefill()
+    with torch.no_grad():
+        points = [qwen3_point(lm, b, args.rounds, dev) for b in map(int, args.batch.split(","))]
+    out = {"tool": "tools/bench_generate.py --qwen3", "device": torch.cuda.get_device_name(0),
+           "shape": "Qwen3-8B layers (hidden 4096, 32 / 8 heads of 128, intermediate 12288, q_norm / k_norm), vocabulary 32000, per-channel "
+                    "W4A8, fuse_qkv(), fuse_prefill(), paged fp16 cache, block 16, greedy",
+           "variants": "`fused`: rope_qkv_norm_paged in the captured step; `composed`: the same loop with the op replaced by Qwen3RMSNorm's "
+                       "torch lines on q and k and rope_qkv_paged; `no_norm`: the layers with qk_norm off (another function: what the norm costs)",
+           "sync_every": SYNC_EVERY, "rounds": args.rounds, "points": points}
+    path = args.out or os.path.join(ROOT, "profiles", "qwen3_loop_bench.json")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    for p in points:
+        print(f"batch {p['batch']:3d}: fused {p['fused']['step_us']:.1f}  composed {p['composed']['step_us']:.1f}  no norm "
+              f"{p['no_norm']['step_us']:.1f} us/step (composed - fused {p['composed_minus_fused_us_per_step']}, fused - no norm "
+              f"{p['fused_minus_no_norm_us_per_step']}, largest spread {p['largest_round_spread_us']})")
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--qwen3", action="store_true", help="time the replayed step of four Qwen3-8B-shaped layers with the fused q / k norm op, "
+                    "with a torch composition in its place and without the norm (profiles/qwen3_loop_bench.json)")
     ap.add_argument("--n", default=None, help="e.g. 1,4,8: measure parallel sampling instead (profiles/parallel_sampling_bench.json)")
     ap.add_argument("--prompt", type=int, default=2048, help="with --n: tokens of the prompt")
     ap.add_argument("--batch", default="1,16")
@@ -785,6 +919,8 @@ def main():
 
     if not torch.cuda.is_available():
         sys.exit("bench_generate.py needs a GPU: a timing taken elsewhere says nothing")
+    if args.qwen3:
+        return qwen3_main(args)
     if args.n:
         return parallel_main(args)
     if args.penalties:
