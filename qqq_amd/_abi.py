@@ -52,7 +52,7 @@ _PARAM = {
     "int": ctypes.c_int, "float": ctypes.c_float, "size_t": ctypes.c_size_t,
     "const qqq_tune_t*": ctypes.POINTER(QQQTune), "qqq_tune_t*": ctypes.POINTER(QQQTune),
     "int32_t*": ctypes.c_void_p,  # acc_out: a device pointer
-    "double*": ctypes.POINTER(ctypes.c_double), "int*": ctypes.POINTER(ctypes.c_int), "float*": ctypes.POINTER(ctypes.c_float),
+    "long long*": ctypes.POINTER(ctypes.c_longlong), "double*": ctypes.POINTER(ctypes.c_double), "int*": ctypes.POINTER(ctypes.c_int), "float*": ctypes.POINTER(ctypes.c_float),
     "const void* const*": ctypes.POINTER(ctypes.c_void_p), "const uint32_t*": ctypes.POINTER(ctypes.c_uint32),
     "qqq_gemm_ex_fn": ctypes.c_void_p, "qqq_gemm_ex2_fn": ctypes.c_void_p,
 }

@@ -103,7 +103,8 @@ QUANT_INCLUDE = os.path.join(QUANT_DIR, "include")  # outside include/: headers(
 QUANT_HEADER = os.path.join(QUANT_INCLUDE, "qqq_amd_quant.h")  # the ABI version is read from it
 QUANT_LIB = os.path.join(_HERE, "libqqq_amd_quant.so")
 # the quantiser's entry points promise bits: no fused multiply-add the source does not spell, a correctly rounded divide, subnormals kept
-QUANT_FLAGS = ("-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-fno-gpu-flush-denormals-to-zero")
+QUANT_FLAGS = ("-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-fno-gpu-flush-denormals-to-zero",
+               "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")  # every f32 operation stays a scalar-per-lane one, as written
 
 
 def quant_headers() -> list:

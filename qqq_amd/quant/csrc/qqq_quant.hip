@@ -2,7 +2,8 @@
 // (qqq_amd/quant/include/qqq_amd_quant.h) over the kernels of qqq_gptq.hip.h, of its act-order / static-groups ops
 // (qqq_amd/quant/include/qqq_amd_gptq_order.h) over those of qqq_gptq_order.hip.h, and of the rotation ops
 // (qqq_amd/quant/include/qqq_amd_rotate.h, qqq_amd/quant/include_ext/qqq_amd_rotate_k.h) over the kernels of qqq_hadamard.hip.h and qqq_hadamard_k.hip.h,
-// and of the smoothing search's fake-quantisation op (qqq_amd/quant/include_ops/qqq_amd_fakequant.h) over those of qqq_fakequant.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
+// of the smoothing search's fake-quantisation op (qqq_amd/quant/include_ops/qqq_amd_fakequant.h) over those of qqq_fakequant.hip.h,
+// and of the Cholesky factor op (qqq_amd/quant/include_ops/qqq_amd_factor.h) over those of qqq_factor.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
 // (qqq_amd/build.py, build_quant): the entry points promise bits.
 #include <hip/hip_runtime.h>
 
@@ -15,7 +16,9 @@
 #include "../include/qqq_amd_quant.h"
 #include "../include/qqq_amd_rotate.h"
 #include "../include_ext/qqq_amd_rotate_k.h"
+#include "../include_ops/qqq_amd_factor.h"
 #include "../include_ops/qqq_amd_fakequant.h"
+#include "qqq_factor.hip.h"
 #include "qqq_fakequant.hip.h"
 #include "qqq_gptq.hip.h"
 #include "qqq_gptq_order.hip.h"
@@ -441,5 +444,134 @@ extern "C" int qqq_fake_quant_rows(const void* X, int ldx, void* Y, int ldy, int
     hipLaunchKernelGGL(qqq_fake_quant_row_kernel<0>, g, b, 0, st, a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_fake_quant_rows kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_upper_factor_work(int n, long long* bytes) {
+  g_err[0] = 0;
+  if (n < 64 || n > 32768 || n % 64 != 0 || !bytes) {
+    snprintf(g_err, sizeof(g_err), "qqq_upper_factor_work: n=%d is not a multiple of 64 in 64 ... 32768, or bytes is NULL", n);
+    return QQQ_ERR_ARG;
+  }
+  *bytes = (static_cast<long long>(n) * n + static_cast<long long>(n) * FAC_BLOCK) * 4;  // the running matrix, and the strip T
+  return QQQ_OK;
+}
+
+template <bool BT, bool NEG>
+static void factor_gemm(const qqq_factor_gemm_args& a, dim3 grid, hipStream_t st) {
+  hipLaunchKernelGGL((qqq_factor_gemm_kernel<BT, NEG>), grid, dim3(FAC_NT), 0, st, a);
+}
+
+extern "C" int qqq_upper_factor(const void* H, int ldh, void* U, int ldu, int n, void* work, void* info, int dev, void* stream) {
+  g_err[0] = 0;
+  if (n < 64 || n > 32768 || n % 64 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_upper_factor: n=%d is not a multiple of 64 in 64 ... 32768", n);
+    return QQQ_ERR_ARG;
+  }
+  if (ldh < n || ldu < n || ldh % 4 != 0 || ldu % 4 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_upper_factor: bad strides ldh=%d ldu=%d (need both >= n=%d and multiples of 4)", ldh, ldu, n);
+    return QQQ_ERR_ARG;
+  }
+  if (!H || !U || !work || !info || misaligned(H, 16) || misaligned(U, 16) || misaligned(work, 16) || misaligned(info, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_upper_factor: bad argument (H, U, work and info must be non-NULL, H, U and work 16-byte aligned, info 4-byte)");
+    return QQQ_ERR_ARG;
+  }
+  const uintptr_t h0 = reinterpret_cast<uintptr_t>(H), u0 = reinterpret_cast<uintptr_t>(U), w0 = reinterpret_cast<uintptr_t>(work),
+                  i0 = reinterpret_cast<uintptr_t>(info);
+  const uintptr_t hspan = (static_cast<uintptr_t>(n - 1) * ldh + n) * 4, uspan = (static_cast<uintptr_t>(n - 1) * ldu + n) * 4;
+  const uintptr_t wspan = (static_cast<uintptr_t>(n) * n + static_cast<uintptr_t>(n) * FAC_BLOCK) * 4;
+  auto meet = [](uintptr_t p, uintptr_t ps, uintptr_t q, uintptr_t qs) { return p < q + qs && q < p + ps; };
+  if (meet(h0, hspan, u0, uspan) || meet(h0, hspan, w0, wspan) || meet(u0, uspan, w0, wspan) || meet(i0, 4, h0, hspan) ||
+      meet(i0, 4, u0, uspan) || meet(i0, 4, w0, wspan)) {
+    snprintf(g_err, sizeof(g_err), "qqq_upper_factor: H, U, work and info overlap (the four must be disjoint)");
+    return QQQ_ERR_ARG;
+  }
+  const float* Hp = static_cast<const float*>(H);
+  float* Up = static_cast<float*>(U);
+  float* W = static_cast<float*>(work);
+  float* T = W + static_cast<long long>(n) * n;
+  const long long ldw = n;
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int tiles = n / FAC_TILE;
+  if (tiles > 1) {
+    qqq_factor_zero_args z;
+    z.U = Up;
+    z.ldu = ldu;
+    hipLaunchKernelGGL(qqq_factor_zero_kernel, dim3(static_cast<unsigned>(tiles * (tiles - 1) / 2)), dim3(FAC_NT), 0, st, z);
+  }
+  // the factorisation: diagonal blocks of 128 from the end, a first block of 64 where n is an odd multiple of 64
+  bool first = true;
+  for (int c1 = n; c1 > 0;) {
+    const int bw = c1 >= FAC_BLOCK ? FAC_BLOCK : FAC_TILE, c0 = c1 - bw, t0 = c0 / FAC_TILE;
+    const float* src = first ? Hp : W;
+    const long long lds = first ? ldh : ldw;
+    qqq_factor_diag_args d;
+    d.src = src + c0 * lds + c0;
+    d.U = Up + static_cast<long long>(c0) * ldu + c0;
+    d.info = static_cast<int*>(info);
+    d.lds = lds;
+    d.ldu = ldu;
+    d.base = c0;
+    d.first = first ? 1 : 0;
+    if (bw == FAC_BLOCK)
+      hipLaunchKernelGGL(qqq_factor_diag_kernel<FAC_BLOCK>, dim3(1), dim3(FAC_NT), 0, st, d);
+    else
+      hipLaunchKernelGGL(qqq_factor_diag_kernel<FAC_TILE>, dim3(1), dim3(FAC_NT), 0, st, d);
+    if (t0 > 0) {
+      qqq_factor_gemm_args g;
+      g.A = src + c0;  // panel: U_iJ = src_iJ . U_JJ^T
+      g.lda = lds;
+      g.B = d.U;
+      g.ldb = ldu;
+      g.Cin = nullptr;
+      g.ldcin = 0;
+      g.C = Up + c0;
+      g.ldc = ldu;
+      g.K = bw;
+      g.tri_grid = 0;
+      g.tri_k = 0;
+      factor_gemm<true, false>(g, dim3(t0, bw / FAC_TILE), st);
+      g.A = Up + c0;  // update: W_ik = src_ik - U_iJ . U_kJ^T, i <= k < J
+      g.lda = ldu;
+      g.B = Up + c0;
+      g.ldb = ldu;
+      g.Cin = src;
+      g.ldcin = lds;
+      g.C = W;
+      g.ldc = ldw;
+      g.tri_grid = 1;
+      factor_gemm<true, true>(g, dim3(static_cast<unsigned>(t0 * (t0 + 1) / 2)), st);
+    }
+    first = false;
+    c1 = c0;
+  }
+  // the inverse: block columns ascending (the first has nothing above it)
+  for (int c0 = n % FAC_BLOCK ? FAC_TILE : FAC_BLOCK; c0 < n; c0 += FAC_BLOCK) {
+    const int t0 = c0 / FAC_TILE;
+    qqq_factor_gemm_args g;
+    g.A = Up + c0;  // T = R_{0:c0, J} . U_JJ
+    g.lda = ldu;
+    g.B = Up + static_cast<long long>(c0) * ldu + c0;
+    g.ldb = ldu;
+    g.Cin = nullptr;
+    g.ldcin = 0;
+    g.C = T;
+    g.ldc = FAC_BLOCK;
+    g.K = FAC_BLOCK;
+    g.tri_grid = 0;
+    g.tri_k = 0;
+    factor_gemm<false, false>(g, dim3(t0, FAC_BLOCK / FAC_TILE), st);
+    g.A = Up;  // U_{0:c0, J} = - U_{0:c0, 0:c0} . T
+    g.B = T;
+    g.ldb = FAC_BLOCK;
+    g.C = Up + c0;
+    g.ldc = ldu;
+    g.K = c0;
+    g.tri_k = 1;
+    factor_gemm<false, true>(g, dim3(t0, FAC_BLOCK / FAC_TILE), st);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_upper_factor launch chain");
   return QQQ_OK;
 }

@@ -1,6 +1,8 @@
 """GPTQ for one linear layer on the device: the reference's `GPTQ.add_batch` and `GPTQ.fasterquant` (QQQ/gptq/gptq.py) in their order, with
 the two launch-bound pieces -- the scale search and the column sweep of a block -- as one HIP launch each (qqq_amd/quant/ops.py).  The
-Hessian, the three Cholesky steps and the trailing GEMM between blocks stay in torch: they are a few large launches.
+Hessian and the trailing GEMM between blocks stay in torch: they are a few large launches.  The factor of the inverse Hessian is torch's
+three Cholesky steps (factor="torch", the default and the reference's bits) or ops.upper_factor (factor="fused": the same matrix by one
+factorisation and one triangular inverse in hand-written kernels, about half the arithmetic).
 
 Only what QuantLinear.pack can hold: symmetric 4-bit, per-channel (group_size -1) or groups of 128.  gptq_quantize is the plain flow;
 gptq_quantize_ordered adds the reference's act-order (columns swept by falling diag(H)) and static groups (every group's scale found
@@ -110,11 +112,19 @@ def _block_composed(W1, Hinv1, scale, grouped):
     return Q1, Err1
 
 
-def _upper_factor(H, percdamp):
-    """the reference's damping and three Cholesky steps on `H` (modified in place) -> the upper factor of its inverse"""
+FACTORS = ("torch", "fused")
+
+
+def _upper_factor(H, percdamp, factor="torch"):
+    """the reference's damping and three Cholesky steps on `H` (modified in place) -> the upper factor of its inverse.  factor="fused":
+    the damping as ever (the op sees the bits the chain sees), then ops.upper_factor in place of the three steps"""
+    if factor not in FACTORS:
+        raise RuntimeError(f"_upper_factor: factor must be one of {FACTORS}, got {factor!r}")
     damp = percdamp * torch.mean(torch.diag(H))
     diag = torch.arange(H.shape[0], device=H.device)
     H[diag, diag] += damp
+    if factor == "fused":
+        return ops.upper_factor(H)
     H = torch.linalg.cholesky(H)
     H = torch.cholesky_inverse(H)
     return torch.linalg.cholesky(H, upper=True).contiguous()  # (the upper factor may come back as a transposed view)
@@ -129,12 +139,15 @@ def _s_extra(weight):
 @torch.no_grad()
 def gptq_quantize(W: torch.Tensor, H: torch.Tensor, group_size: int = -1, mse: bool = False, percdamp: float = 0.01, fused: bool = True,
                   trace: bool = False, bits: int = 4, sym: bool = True, act_order: bool = False, static_groups: bool = False,
-                  timers=None) -> GPTQResult:
+                  timers=None, factor: str = "torch") -> GPTQResult:
     """GPTQ of one weight `W` [N, K] (on the GPU, any float dtype) under the Hessian `H` f32 [K, K] (Hessian.H; not modified).
     group_size -1: per-channel scales found from the whole row before dead columns are zeroed; 128: a group's scale found from the
     block as it stands when the sweep reaches it.  fused=False runs the sweep as torch calls (same bits, the benchmark's baseline).
     trace=True keeps every block's input, outputs and scale, and the factor.  `timers`: None, or an object whose section(name) returns a
-    context manager (tools/bench_gptq.py splits the time with it)."""
+    context manager (tools/bench_gptq.py splits the time with it).  factor: "torch" (the three Cholesky steps) or "fused"
+    (ops.upper_factor: the same factor from the project's own kernels, not torch's bits; the sweep's bits follow the factor it is given)."""
+    if factor not in FACTORS:
+        raise RuntimeError(f"gptq_quantize: factor must be one of {FACTORS}, got {factor!r}")
     if bits != 4 or not sym or act_order or static_groups:
         raise NotImplementedError("gptq_quantize: only symmetric 4-bit without act_order / static_groups (what QuantLinear.pack holds)")
     if group_size not in (-1, BLOCK):
@@ -157,7 +170,7 @@ def gptq_quantize(W: torch.Tensor, H: torch.Tensor, group_size: int = -1, mse: b
     H[dead, dead] = 1
     Wf[:, dead] = 0
     with section("cholesky"):
-        Hinv = _upper_factor(H, percdamp)
+        Hinv = _upper_factor(H, percdamp, factor)
     Q = torch.empty_like(Wf)
     Err1_buf = torch.empty((N, BLOCK), dtype=torch.float32, device=W.device)
     loss = torch.zeros((), dtype=torch.float32, device=W.device)
@@ -204,7 +217,7 @@ def _block_cols_composed(W1, Hinv1, scale_cols):
 @torch.no_grad()
 def gptq_quantize_ordered(W: torch.Tensor, H: torch.Tensor, group_size: int = -1, mse: bool = False, percdamp: float = 0.01,
                           act_order: bool = True, static_groups: bool = True, perm: Optional[torch.Tensor] = None, fused: bool = True,
-                          trace: bool = False, timers=None) -> GPTQResult:
+                          trace: bool = False, timers=None, factor: str = "torch") -> GPTQResult:
     """gptq_quantize with the reference's act_order and static_groups (the defaults of its examples/quant_model.py), in the order of
     GPTQ.fasterquant(actorder=True, static_groups=True):
       per-channel scales from the whole row, dead columns zeroed, then -- grouped -- EVERY group's scale from the unswept weight in one
@@ -216,8 +229,10 @@ def gptq_quantize_ordered(W: torch.Tensor, H: torch.Tensor, group_size: int = -1
     `perm`: the sweep order to use instead of the argsort (a permutation of range(K)); the result carries the order used.
     Grouped act_order without static_groups is refused: the groups would follow the permutation, which QuantLinear.pack cannot hold.
     static_groups has no effect per-channel (as in the reference); with neither switch this is gptq_quantize.  trace, fused, timers: as
-    gptq_quantize; the timers also see "group_scales" and "permute" (the gathers)."""
+    gptq_quantize; the timers also see "group_scales" and "permute" (the gathers).  factor: as gptq_quantize, on the permuted H."""
     name = "gptq_quantize_ordered"
+    if factor not in FACTORS:
+        raise RuntimeError(f"{name}: factor must be one of {FACTORS}, got {factor!r}")
     if group_size not in (-1, BLOCK):
         raise NotImplementedError(f"{name}: only group_size -1 and 128 are supported")
     grouped = group_size == BLOCK
@@ -227,7 +242,7 @@ def gptq_quantize_ordered(W: torch.Tensor, H: torch.Tensor, group_size: int = -1
     if W.dim() != 2 or not W.is_cuda:
         raise RuntimeError(f"{name}: W must be a matrix on the GPU (there is no CPU path)")
     if not act_order and not (grouped and static_groups):
-        return gptq_quantize(W, H, group_size, mse=mse, percdamp=percdamp, fused=fused, trace=trace, timers=timers)
+        return gptq_quantize(W, H, group_size, mse=mse, percdamp=percdamp, fused=fused, trace=trace, timers=timers, factor=factor)
     N, K = W.shape
     if H.shape != (K, K) or H.dtype != torch.float32 or H.device != W.device:
         raise RuntimeError(f"{name}: H must be float32 [{K}, {K}] on W's device")
@@ -266,7 +281,7 @@ def gptq_quantize_ordered(W: torch.Tensor, H: torch.Tensor, group_size: int = -1
         order = perm if act_order else torch.arange(K, device=W.device)
         gidx_all = (order // BLOCK).to(torch.int32)
     with section("cholesky"):
-        Hinv = _upper_factor(H, percdamp)
+        Hinv = _upper_factor(H, percdamp, factor)
     Q = torch.empty_like(Wf)
     Err1_buf = torch.empty((N, BLOCK), dtype=torch.float32, device=W.device)
     loss = torch.zeros((), dtype=torch.float32, device=W.device)

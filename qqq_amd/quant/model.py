@@ -94,7 +94,7 @@ def _run(layer, inps, seq_batch, taps=None):
 @torch.no_grad()
 def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size: int, mse: bool = False, percdamp: float = 0.01,
                    seq_batch: int = 1, device=None, results: Optional[dict] = None, rotation=None, act_order: bool = False,
-                   static_groups: bool = False, smooth=None) -> QuantLlamaForCausalLM:
+                   static_groups: bool = False, smooth=None, factor: str = "torch") -> QuantLlamaForCausalLM:
     """A packed QuantLlamaForCausalLM from an fp16 Hugging Face state dict, a (duck-typed) Llama or Qwen2 config and calibration token
     ids [samples, seqlen].  `seq_batch` sequences run through a layer at a time (1, the reference's, counts every sequence as one sample
     of the Hessian).  `results`: a dict that receives the GPTQResult of every linear under its state-dict prefix.
@@ -108,7 +108,9 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
     `smooth`: None, a method name ("os+", "awq", "sq": smooth.smooth_model searches the scales on the first 8 calibration sequences), or
     a ready scale_list (smooth.apply_smooth alone): the reference's --smooth True (pair it with mse=False).  It is applied AFTER
     `rotation`, on the rotated state dict, and before GPTQ; results["smooth"] receives the list.  After rotation + smooth the norms are
-    no longer ones: they hold 1 / s.  With smooth=None nothing of it runs."""
+    no longer ones: they hold 1 / s.  With smooth=None nothing of it runs.
+    `factor`: "torch" or "fused", handed to every linear's gptq_quantize / gptq_quantize_ordered (the factor of the inverse Hessian from
+    torch's Cholesky chain, or from ops.upper_factor)."""
     dev = torch.device(device if device is not None else "cuda:0")
     if rotation is not None:
         if isinstance(rotation, str):
@@ -159,9 +161,9 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
                 W = w[key + ".weight"]
                 if act_order or static_groups:
                     res = gptq_quantize_ordered(W, hs[HESSIAN_OF[name]].H, group_size, mse=mse, percdamp=percdamp, act_order=act_order,
-                                                static_groups=static_groups)
+                                                static_groups=static_groups, factor=factor)
                 else:
-                    res = gptq_quantize(W, hs[HESSIAN_OF[name]].H, group_size, mse=mse, percdamp=percdamp)
+                    res = gptq_quantize(W, hs[HESSIAN_OF[name]].H, group_size, mse=mse, percdamp=percdamp, factor=factor)
                 res.pack_into(getattr(getattr(qlayer, mod_name), name), w.get(key + ".bias"))
                 w[key + ".weight"] = res.weight
                 if results is not None:

@@ -1,7 +1,10 @@
 """Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h, qqq_amd_gptq_order.h,
-qqq_amd_rotate.h, in qqq_amd/quant/include_ext/ qqq_amd_rotate_k.h and in qqq_amd/quant/include_ops/ qqq_amd_fakequant.h state the exact
-semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing on the host."""
+qqq_amd_rotate.h, in qqq_amd/quant/include_ext/ qqq_amd_rotate_k.h and in qqq_amd/quant/include_ops/ qqq_amd_fakequant.h and
+qqq_amd_factor.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing
+on the host; upper_factor enqueues a chain of launches, and reads one status word where its caller asks for the check."""
 from __future__ import annotations
+
+import ctypes
 
 import torch
 
@@ -294,4 +297,51 @@ def fake_quant_rows(x: torch.Tensor, col_scale, bits: int, group: int = 0, divid
     err = _lib.lib().qqq_fake_quant_rows(_ptr(x), ldx, _ptr(out), ldy, rows, cols, _ptr(col_scale) if col_scale is not None else None,
                                          bits, group, int(bool(divide)), x.device.index or 0, _stream_for(x))
     _raise_lib(name, err)
+    return out
+
+
+def _factor_matrix(name, what, t, n=None):
+    # a square f32 matrix of 16-byte units: unit column stride, a row stride >= n that is a multiple of 4, a 16-byte aligned base
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float32:
+        got = f"{_dt(t.dtype)} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{name}: {what} must be a float32 matrix, got {got}")
+    if t.shape[0] != t.shape[1] or (n is not None and t.shape[0] != n):
+        raise RuntimeError(f"{name}: {what} has the shape {tuple(t.shape)}, " + ("a square matrix" if n is None else f"({n}, {n})") + " expected")
+    if t.shape[0] < 64 or t.shape[0] > 32768 or t.shape[0] % 64:
+        raise RuntimeError(f"{name}: {what} has n = {t.shape[0]}, no multiple of 64 in 64 ... 32768")
+    if t.stride(1) != 1 or t.stride(0) < t.shape[1] or t.stride(0) % 4 or t.stride(0) >= 2**31:
+        raise RuntimeError(f"{name}: {what} must have unit column stride and a row stride >= n that is a multiple of 4, got strides {tuple(t.stride())}")
+    if t.data_ptr() % 16:
+        raise RuntimeError(f"{name}: {what} must be 16-byte aligned")
+    return t.stride(0)
+
+
+def upper_factor(H: torch.Tensor, out=None, check: bool = True):
+    """The upper triangular U with positive diagonal and U^T U = H^-1 -- what GPTQ's chain cholesky, cholesky_inverse, cholesky(upper)
+    returns -- by the direct route H = R R^T, U = R^-1 in hand-written kernels (qqq_amd_factor.h): the chain's matrix at half its
+    arithmetic, as accurate, not its bits.  `H` f32 [n, n], symmetric positive-definite, n a multiple of 64 in 64 ... 32768; a view with
+    its own row stride (a multiple of 4, 16-byte aligned) is fine; only the upper triangle counts, and H is left as it is.  -> `out`: new,
+    or a matrix of H's shape that does not overlap it; its strict lower triangle is exact zeros.  The workspace (n^2 + 128 n floats) and
+    the status word are allocated per call.  check=True reads the status (ONE sync) and raises as torch does in the chain when a pivot
+    is not positive; check=False returns (U, info) -- info an int32 tensor [1] on the device: 0, or 1 + the failed pivot's index -- and
+    stays asynchronous."""
+    name = "upper_factor"
+    ldh = _factor_matrix(name, "H", H)
+    n = H.shape[0]
+    if out is None:
+        out = torch.empty((n, n), dtype=torch.float32, device=H.device)
+    ldu = _factor_matrix(name, "out", out, n)
+    _same_gpu(name, (H, out))
+    L = _lib.lib()
+    nbytes = ctypes.c_longlong(0)
+    _raise_lib(name, L.qqq_upper_factor_work(n, ctypes.byref(nbytes)))
+    work = torch.empty((nbytes.value // 4,), dtype=torch.float32, device=H.device)
+    info = torch.empty((1,), dtype=torch.int32, device=H.device)
+    err = L.qqq_upper_factor(_ptr(H), ldh, _ptr(out), ldu, n, _ptr(work), _ptr(info), H.device.index or 0, _stream_for(H))
+    _raise_lib(name, err)
+    if not check:
+        return out, info
+    pivot = int(info.item())
+    if pivot:
+        raise RuntimeError(f"{name}: the matrix is not positive-definite (pivot {pivot})")
     return out

@@ -9,6 +9,9 @@ the sweep, the trailing GEMM and the Cholesky chain from events around those sec
 --act-order times gptq_quantize_ordered (act-order, and static groups when grouped) instead: fused (ops.gptq_block_cols) against its own
 fused=False, and against plain gptq_quantize fused, with the split also showing the one-launch group scales and the permutation gathers;
 the default --out is then profiles/gptq_order_bench.json.
+--factor torch,fused times gptq_quantize (fused sweep) under each factor of the inverse Hessian instead -- torch's Cholesky chain and
+ops.upper_factor, alternating in one process -- with the "cholesky" section of both; the default --out is then
+profiles/gptq_factor_bench.json.
 
 Writes the JSON and prints one line per point.  Nothing asserts a time.
 """
@@ -61,9 +64,13 @@ def main():
     ap.add_argument("--out", default=None, help="default profiles/gptq_bench.json, with --act-order profiles/gptq_order_bench.json")
     ap.add_argument("--small", action="store_true", help="one 512 x 512 point: the plumbing alone")
     ap.add_argument("--act-order", action="store_true", help="time gptq_quantize_ordered (act-order + static groups) instead")
+    ap.add_argument("--factor", default=None, help="torch,fused: time gptq_quantize under both factors of the inverse Hessian instead")
     args = ap.parse_args()
+    factors = args.factor.split(",") if args.factor else []
+    if factors and (args.act_order or sorted(factors) != ["fused", "torch"]):
+        sys.exit("bench_gptq.py: --factor takes torch,fused (both, so that they share a run), without --act-order")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "gptq_order_bench.json" if args.act_order else "gptq_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "gptq_factor_bench.json" if factors else "gptq_order_bench.json" if args.act_order else "gptq_bench.json")
     import torch
 
     if not torch.cuda.is_available():
@@ -109,7 +116,35 @@ def main():
             point["over_plain_fused"] = round(point["fused_ms_median"] / point["plain_fused_ms_median"], 3)
             print(json.dumps(point))
             points.append(point)
-        for gs in () if args.act_order else (-1, 128):
+        for gs in (-1, 128) if factors else ():
+            point = {"N": N, "K": K, "group_size": gs}
+            wall, chol, weights = {f: [] for f in factors}, {f: [] for f in factors}, {}
+            for f in factors:
+                gptq_quantize(W, h.H, gs, factor=f)  # warm-up
+            for _ in range(args.rounds):
+                for f in factors:  # alternating: both see the same minutes of the machine
+                    timers = EventTimers(torch)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    res = gptq_quantize(W, h.H, gs, timers=timers, factor=f)
+                    torch.cuda.synchronize()
+                    wall[f].append((time.perf_counter() - t0) * 1e3)
+                    chol[f].append(timers.totals()["cholesky"])
+                    weights[f] = res.weight
+            for f in factors:
+                point[f + "_ms"] = [round(t, 3) for t in wall[f]]
+                point[f + "_ms_median"] = round(sorted(wall[f])[len(wall[f]) // 2], 3)
+                point[f + "_cholesky_ms"] = [round(t, 3) for t in chol[f]]
+                point[f + "_cholesky_ms_median"] = round(sorted(chol[f])[len(chol[f]) // 2], 3)
+            spread = max(max(chol[f]) - min(chol[f]) for f in factors)
+            point["cholesky_spread_ms"] = round(spread, 3)
+            point["cholesky_speedup"] = round(point["torch_cholesky_ms_median"] / point["fused_cholesky_ms_median"], 2)
+            point["speedup"] = round(point["torch_ms_median"] / point["fused_ms_median"], 2)
+            point["fused_wins_by_more_than_the_spread"] = bool(min(chol["torch"]) - max(chol["fused"]) > spread)
+            point["weights_that_differ"] = float((weights["torch"] != weights["fused"]).float().mean())
+            print(json.dumps(point))
+            points.append(point)
+        for gs in () if args.act_order or factors else (-1, 128):
             point = {"N": N, "K": K, "group_size": gs}
             weights = {}
             for fused in (True, False):

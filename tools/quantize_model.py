@@ -27,6 +27,8 @@ reference's examples/quant_model.py; --rotation is its rotation stage, --smooth 
            on the result.  The reference pairs it with its --gptq_mse False: leave --mse out.  quant_config.json records {"smooth"}.
 --save-scales PATH   with --smooth: torch.save the scale_list (four fp16 vectors per layer: qkv, o, gate_up, down) there, the
            reference's scale_list.pth.
+--factor   torch | fused: where every linear's factor of the inverse Hessian comes from -- torch's three Cholesky steps (the default) or
+           the project's own kernels (qqq_amd.quant.ops.upper_factor: the same matrix, faster, not torch's bits).
 Prints one JSON line: group_size, nsamples, seqlen, linears, seconds (and rotation, smooth).
 """
 import argparse
@@ -61,6 +63,7 @@ def main():
     ap.add_argument("--static-groups", action="store_true",
                     help="find every group's scale before the sweep (the reference's default; off here; needed by --act-order with groups)")
     ap.add_argument("--smooth", choices=("os+", "awq", "sq"), default=None, help="smooth the state dict before GPTQ (after --rotation)")
+    ap.add_argument("--factor", choices=("torch", "fused"), default="torch", help="the Cholesky chain of torch, or ops.upper_factor")
     ap.add_argument("--save-scales", default=None, help="with --smooth: where to torch.save the scale_list")
     args = ap.parse_args()
     if args.save_scales and not args.smooth:
@@ -100,7 +103,7 @@ def main():
     t0 = time.perf_counter()
     lm = quantize_model(load_state_dict(args.weights), SimpleNamespace(**cfg), ids, args.group_size, mse=args.mse, percdamp=args.percdamp,
                         seq_batch=args.seq_batch, results=results, rotation=rotation, act_order=args.act_order,
-                        static_groups=args.static_groups, smooth=args.smooth)
+                        static_groups=args.static_groups, smooth=args.smooth, factor=args.factor)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     os.makedirs(args.out, exist_ok=True)
