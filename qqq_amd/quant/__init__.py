@@ -26,6 +26,9 @@ whole QQQ W4A8 checkpoints from fp16 ones, rotated first where asked.  A sub-pac
     apply_smooth, smooth_model          migration scale, the layer-wise flow that makes its scale_list, and the fold into the weights
                                         (quantize_model(..., smooth="os+"), after rotation and before GPTQ)
 
+    ops.hessian_update                  the HIP op of the Hessian: H <- alpha H + beta X^T X of fp16 inputs as one symmetric rank-k
+                                        launch on the fp16 matrix path (Hessian(accumulate="fused"), quantize_model(hessian="fused"))
+
 Out of scope: token-wise clipping after smoothing, Hadamard tables of other orders (pass one as table=), a head_dim that is no power of two, act-order with moving (non-static) groups, asymmetric modes, other bit
 widths and group sizes."""
 from . import ops
@@ -34,6 +37,7 @@ from .model import FloatDecoderLayer, quantize_model
 from .ops import gptq_block_cols, group_scales
 from .ops import check_table, hadamard_rows_k
 from .ops import fake_quant_rows
+from .ops import hessian_update
 from .smooth import apply_smooth, migration_scale, smooth_model, smooth_scales
 from .rotation import (fuse_layer_norms, hadamard_factor, hadamard_matrix, hadamard_matrix_k, hadamard_signs, hadamard_table,
                        random_orthogonal, rotate_model, rotate_state_dict)
@@ -42,4 +46,4 @@ __all__ = ["ops", "Hessian", "gptq_quantize", "gptq_quantize_ordered", "group_sc
            "BlockTrace", "FloatDecoderLayer", "quantize_model",
            "fuse_layer_norms", "hadamard_signs", "hadamard_matrix", "random_orthogonal", "rotate_state_dict", "rotate_model",
            "hadamard_rows_k", "check_table", "hadamard_table", "hadamard_factor", "hadamard_matrix_k",
-           "fake_quant_rows", "migration_scale", "smooth_scales", "apply_smooth", "smooth_model"]
+           "fake_quant_rows", "hessian_update", "migration_scale", "smooth_scales", "apply_smooth", "smooth_model"]

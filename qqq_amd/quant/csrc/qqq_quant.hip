@@ -3,7 +3,8 @@
 // (qqq_amd/quant/include/qqq_amd_gptq_order.h) over those of qqq_gptq_order.hip.h, and of the rotation ops
 // (qqq_amd/quant/include/qqq_amd_rotate.h, qqq_amd/quant/include_ext/qqq_amd_rotate_k.h) over the kernels of qqq_hadamard.hip.h and qqq_hadamard_k.hip.h,
 // of the smoothing search's fake-quantisation op (qqq_amd/quant/include_ops/qqq_amd_fakequant.h) over those of qqq_fakequant.hip.h,
-// and of the Cholesky factor op (qqq_amd/quant/include_ops/qqq_amd_factor.h) over those of qqq_factor.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
+// of the Cholesky factor op (qqq_amd/quant/include_ops/qqq_amd_factor.h) over those of qqq_factor.hip.h,
+// and of the Hessian accumulation op (qqq_amd/quant/include_ops/qqq_amd_hessian.h) over the kernel of qqq_hessian.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
 // (qqq_amd/build.py, build_quant): the entry points promise bits.
 #include <hip/hip_runtime.h>
 
@@ -18,12 +19,14 @@
 #include "../include_ext/qqq_amd_rotate_k.h"
 #include "../include_ops/qqq_amd_factor.h"
 #include "../include_ops/qqq_amd_fakequant.h"
+#include "../include_ops/qqq_amd_hessian.h"
 #include "qqq_factor.hip.h"
 #include "qqq_fakequant.hip.h"
 #include "qqq_gptq.hip.h"
 #include "qqq_gptq_order.hip.h"
 #include "qqq_hadamard.hip.h"
 #include "qqq_hadamard_k.hip.h"
+#include "qqq_hessian.hip.h"  // (behind qqq_factor.hip.h: it walks the tile triangle with fac_tri)
 
 static thread_local char g_err[512] = "";
 
@@ -573,5 +576,47 @@ extern "C" int qqq_upper_factor(const void* H, int ldh, void* U, int ldu, int n,
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_upper_factor launch chain");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_hessian_update(void* H, int ldh, const void* X, int ldx, int tokens, int n, float alpha, float beta, int dev, void* stream) {
+  g_err[0] = 0;
+  if (n < 64 || n > 32768 || n % 64 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_hessian_update: n=%d is not a multiple of 64 in 64 ... 32768", n);
+    return QQQ_ERR_ARG;
+  }
+  if (tokens < 1) {
+    snprintf(g_err, sizeof(g_err), "qqq_hessian_update: tokens=%d must be at least 1", tokens);
+    return QQQ_ERR_ARG;
+  }
+  if (ldh < n || ldx < n || ldh % 4 != 0 || ldx % 8 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_hessian_update: bad strides ldh=%d ldx=%d (need both >= n=%d, ldh a multiple of 4, ldx of 8)", ldh, ldx, n);
+    return QQQ_ERR_ARG;
+  }
+  if (!H || !X || misaligned(H, 16) || misaligned(X, 16)) {
+    snprintf(g_err, sizeof(g_err), "qqq_hessian_update: bad argument (H and X must be non-NULL and 16-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  const uintptr_t h0 = reinterpret_cast<uintptr_t>(H), x0 = reinterpret_cast<uintptr_t>(X);
+  const uintptr_t hspan = (static_cast<uintptr_t>(n - 1) * ldh + n) * 4, xspan = (static_cast<uintptr_t>(tokens - 1) * ldx + n) * 2;
+  if (h0 < x0 + xspan && x0 < h0 + hspan) {
+    snprintf(g_err, sizeof(g_err), "qqq_hessian_update: H and X overlap (the two must be disjoint)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_hessian_args a;
+  a.H = static_cast<float*>(H);
+  a.X = static_cast<const _Float16*>(X);
+  a.ldh = ldh;
+  a.ldx = ldx;
+  a.tokens = tokens;
+  a.n = n;
+  a.nb = (n + HES_TILE - 1) / HES_TILE;
+  a.ntiles = a.nb * (a.nb + 1) / 2;  // (at most 256 * 257 / 2)
+  a.alpha = alpha;
+  a.beta = beta;
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_hessian_kernel, dim3(static_cast<unsigned>(a.ntiles)), dim3(HES_NT), 0, static_cast<hipStream_t>(stream), a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_hessian_kernel launch");
   return QQQ_OK;
 }

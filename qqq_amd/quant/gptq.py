@@ -1,6 +1,8 @@
 """GPTQ for one linear layer on the device: the reference's `GPTQ.add_batch` and `GPTQ.fasterquant` (QQQ/gptq/gptq.py) in their order, with
 the two launch-bound pieces -- the scale search and the column sweep of a block -- as one HIP launch each (qqq_amd/quant/ops.py).  The
-Hessian and the trailing GEMM between blocks stay in torch: they are a few large launches.  The factor of the inverse Hessian is torch's
+trailing GEMM between blocks stays in torch: a few large launches.  The Hessian is accumulated as the reference does it -- a scaling pass,
+an f32 copy of the input, an f32 GEMM (accumulate="torch", the default and the reference's bits) -- or by ops.hessian_update
+(accumulate="fused": one symmetric rank-k launch on the fp16 matrix path, scaling in its epilogue).  The factor of the inverse Hessian is torch's
 three Cholesky steps (factor="torch", the default and the reference's bits) or ops.upper_factor (factor="fused": the same matrix by one
 factorisation and one triangular inverse in hand-written kernels, about half the arithmetic).
 
@@ -19,11 +21,19 @@ from . import ops
 BLOCK = 128
 
 
-class Hessian:
-    """The running 2/n X^T X of a linear layer's inputs, as the reference accumulates it (f32 [columns, columns])."""
+ACCUMULATORS = ("torch", "fused")
 
-    def __init__(self, columns: int, device):
+
+class Hessian:
+    """The running 2/n X^T X of a linear layer's inputs, as the reference accumulates it (f32 [columns, columns]).  accumulate="torch":
+    the reference's steps and bits.  accumulate="fused": ops.hessian_update per batch -- H n / (n + b) + (2 / (n + b)) X^T X with exact
+    products of the fp16 inputs summed in f32, the same matrix as accurately, not the same bits; fp16 inputs on the GPU only."""
+
+    def __init__(self, columns: int, device, accumulate: str = "torch"):
+        if accumulate not in ACCUMULATORS:
+            raise RuntimeError(f"Hessian: accumulate must be one of {ACCUMULATORS}, got {accumulate!r}")
         self.columns = columns
+        self.accumulate = accumulate
         self.H = torch.zeros((columns, columns), dtype=torch.float32, device=device)
         self.nsamples = 0
 
@@ -33,6 +43,13 @@ class Hessian:
         if x.shape[-1] != self.columns:
             raise RuntimeError(f"Hessian.add_batch: the input's last dimension is {x.shape[-1]}, {self.columns} expected")
         b = 1 if x.dim() <= 2 else x.shape[0]
+        if self.accumulate == "fused":
+            if x.dtype != torch.float16 or not x.is_cuda:
+                raise RuntimeError(f"Hessian.add_batch: accumulate='fused' takes float16 inputs on the GPU, got {x.dtype} on {x.device} "
+                                   "(there is no fallback)")
+            ops.hessian_update(self.H, x.reshape(-1, self.columns), self.nsamples / (self.nsamples + b), 2 / (self.nsamples + b))
+            self.nsamples += b
+            return
         x = x.reshape(-1, self.columns)
         self.H *= self.nsamples / (self.nsamples + b)
         self.nsamples += b

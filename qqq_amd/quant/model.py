@@ -94,7 +94,7 @@ def _run(layer, inps, seq_batch, taps=None):
 @torch.no_grad()
 def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size: int, mse: bool = False, percdamp: float = 0.01,
                    seq_batch: int = 1, device=None, results: Optional[dict] = None, rotation=None, act_order: bool = False,
-                   static_groups: bool = False, smooth=None, factor: str = "torch") -> QuantLlamaForCausalLM:
+                   static_groups: bool = False, smooth=None, factor: str = "torch", hessian: str = "torch") -> QuantLlamaForCausalLM:
     """A packed QuantLlamaForCausalLM from an fp16 Hugging Face state dict, a (duck-typed) Llama or Qwen2 config and calibration token
     ids [samples, seqlen].  `seq_batch` sequences run through a layer at a time (1, the reference's, counts every sequence as one sample
     of the Hessian).  `results`: a dict that receives the GPTQResult of every linear under its state-dict prefix.
@@ -110,7 +110,9 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
     `rotation`, on the rotated state dict, and before GPTQ; results["smooth"] receives the list.  After rotation + smooth the norms are
     no longer ones: they hold 1 / s.  With smooth=None nothing of it runs.
     `factor`: "torch" or "fused", handed to every linear's gptq_quantize / gptq_quantize_ordered (the factor of the inverse Hessian from
-    torch's Cholesky chain, or from ops.upper_factor)."""
+    torch's Cholesky chain, or from ops.upper_factor).
+    `hessian`: "torch" or "fused", handed to the four Hessians of every layer as their `accumulate` (the reference's f32 steps, or
+    ops.hessian_update on the fp16 taps)."""
     dev = torch.device(device if device is not None else "cuda:0")
     if rotation is not None:
         if isinstance(rotation, str):
@@ -152,8 +154,8 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
         w = {k[len(prefix):]: v.to(dev).half() for k, v in state_dict.items() if k.startswith(prefix)}
         layer = FloatDecoderLayer(config, w)
         hidden, inter = w["mlp.gate_proj.weight"].shape[1], w["mlp.down_proj.weight"].shape[1]
-        hs = {"qkv": Hessian(hidden, dev), "o": Hessian(w["self_attn.o_proj.weight"].shape[1], dev), "gate_up": Hessian(hidden, dev),
-              "down": Hessian(inter, dev)}
+        hs = {"qkv": Hessian(hidden, dev, hessian), "o": Hessian(w["self_attn.o_proj.weight"].shape[1], dev, hessian),
+              "gate_up": Hessian(hidden, dev, hessian), "down": Hessian(inter, dev, hessian)}
         _run(layer, inps, seq_batch, {k: h.add_batch for k, h in hs.items()})
         for mod_name, names in (("self_attn", ATTN), ("mlp", MLP)):
             for name in names:

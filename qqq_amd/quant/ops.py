@@ -1,6 +1,6 @@
 """Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h, qqq_amd_gptq_order.h,
-qqq_amd_rotate.h, in qqq_amd/quant/include_ext/ qqq_amd_rotate_k.h and in qqq_amd/quant/include_ops/ qqq_amd_fakequant.h and
-qqq_amd_factor.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing
+qqq_amd_rotate.h, in qqq_amd/quant/include_ext/ qqq_amd_rotate_k.h and in qqq_amd/quant/include_ops/ qqq_amd_fakequant.h,
+qqq_amd_factor.h and qqq_amd_hessian.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing
 on the host; upper_factor enqueues a chain of launches, and reads one status word where its caller asks for the check."""
 from __future__ import annotations
 
@@ -345,3 +345,28 @@ def upper_factor(H: torch.Tensor, out=None, check: bool = True):
     if pivot:
         raise RuntimeError(f"{name}: the matrix is not positive-definite (pivot {pivot})")
     return out
+
+
+def hessian_update(H: torch.Tensor, x: torch.Tensor, alpha: float, beta: float) -> torch.Tensor:
+    """GPTQ's Hessian accumulation in one launch (qqq_amd_hessian.h): H <- f32(f32(alpha H) + f32(beta x^T x)) in place, every entry of
+    the symmetric matrix.  `H` f32 [n, n], n a multiple of 64 in 64 ... 32768; a view with its own row stride (a multiple of 4, 16-byte
+    aligned) is fine.  `x` fp16 [tokens, n] on H's GPU, tokens >= 1; a view with its own row stride (a multiple of 8, 16-byte aligned) is
+    read in place, any other layout is made contiguous once; never written.  The products are exact and summed in f32 on the fp16 matrix
+    path in one fixed order; alpha == 0 does not read H (torch.empty will do for the first call).  Returns H."""
+    name = "hessian_update"
+    ldh = _factor_matrix(name, "H", H)
+    n = H.shape[0]
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float16:
+        got = f"{_dt(x.dtype)} {tuple(x.shape)}" if isinstance(x, torch.Tensor) else type(x).__name__
+        raise RuntimeError(f"{name}: x must be a float16 matrix, got {got}")
+    if x.shape[0] < 1 or x.shape[1] != n:
+        raise RuntimeError(f"{name}: x has the shape {tuple(x.shape)}, (tokens >= 1, {n}) expected")
+    _same_gpu(name, (H, x))
+    if x.stride(1) != 1 or x.stride(0) < n or x.stride(0) % 8 or x.stride(0) >= 2**31 or x.data_ptr() % 16:
+        x = x.contiguous()
+        if x.data_ptr() % 16:  # (a contiguous tensor that starts off a 16-byte boundary is returned as it is)
+            x = x.clone()
+    err = _lib.lib().qqq_hessian_update(_ptr(H), ldh, _ptr(x), x.stride(0) if x.shape[0] > 1 else n, x.shape[0], n, float(alpha), float(beta),
+                                        H.device.index or 0, _stream_for(H))
+    _raise_lib(name, err)
+    return H

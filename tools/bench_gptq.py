@@ -4,7 +4,7 @@ torch calls (fused=False: a handful of launches per weight column, what the refe
 shapes, per-channel and g128.  Wall time per call with a synchronise on both sides, and the split of the GPU time into the scale search,
 the sweep, the trailing GEMM and the Cholesky chain from events around those sections.
 
-    python tools/bench_gptq.py [--rounds 5] [--out profiles/gptq_bench.json] [--small] [--act-order]
+    python tools/bench_gptq.py [--rounds 5] [--out profiles/gptq_bench.json] [--small] [--act-order] [--factor torch,fused] [--hessian torch,fused]
 
 --act-order times gptq_quantize_ordered (act-order, and static groups when grouped) instead: fused (ops.gptq_block_cols) against its own
 fused=False, and against plain gptq_quantize fused, with the split also showing the one-launch group scales and the permutation gathers;
@@ -12,6 +12,10 @@ the default --out is then profiles/gptq_order_bench.json.
 --factor torch,fused times gptq_quantize (fused sweep) under each factor of the inverse Hessian instead -- torch's Cholesky chain and
 ops.upper_factor, alternating in one process -- with the "cholesky" section of both; the default --out is then
 profiles/gptq_factor_bench.json.
+--hessian torch,fused times Hessian.add_batch under each accumulator instead -- the reference's f32 steps and ops.hessian_update,
+alternating in one process -- at K = 4096 and 11008 with 2048 and 8 x 2048 fp16 tokens per call, 16 calls per Hessian, GPU time between
+events; and quantize_model over ONE Llama-2-7B-shaped layer (the reference's 128 calibration sequences of 2048 tokens) under both, with the share of its
+time the four Hessians take.  The default --out is then profiles/hessian_bench.json.
 
 Writes the JSON and prints one line per point.  Nothing asserts a time.
 """
@@ -65,7 +69,12 @@ def main():
     ap.add_argument("--small", action="store_true", help="one 512 x 512 point: the plumbing alone")
     ap.add_argument("--act-order", action="store_true", help="time gptq_quantize_ordered (act-order + static groups) instead")
     ap.add_argument("--factor", default=None, help="torch,fused: time gptq_quantize under both factors of the inverse Hessian instead")
+    ap.add_argument("--hessian", default=None, help="torch,fused: time Hessian.add_batch under both accumulators, and its share of a layer, instead")
     args = ap.parse_args()
+    if args.hessian is not None:
+        if sorted(args.hessian.split(",")) != ["fused", "torch"] or args.act_order or args.factor:
+            sys.exit("bench_gptq.py: --hessian takes torch,fused (both, so that they share a run), without --act-order / --factor")
+        return hessian_main(args)
     factors = args.factor.split(",") if args.factor else []
     if factors and (args.act_order or sorted(factors) != ["fused", "torch"]):
         sys.exit("bench_gptq.py: --factor takes torch,fused (both, so that they share a run), without --act-order")
@@ -175,6 +184,100 @@ def main():
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump({"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "points": points}, f, indent=1)
+        f.write("\n")
+
+
+def _median(v):
+    return sorted(v)[len(v) // 2]
+
+
+def hessian_main(args):
+    import torch
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_gptq.py needs a GPU")
+    from types import SimpleNamespace
+
+    from qqq_amd.quant import Hessian, quantize_model
+
+    out = args.out or os.path.join(ROOT, "profiles", "hessian_bench.json")
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    kinds, calls, points = ("torch", "fused"), 16, []
+    for K, seqs in [(256, 1)] if args.small else [(4096, 1), (4096, 8), (11008, 1), (11008, 8)]:
+        x = (torch.randn((seqs, 256 if args.small else 2048, K), generator=g, device=dev) * (0.2 + 2 * torch.rand(K, generator=g, device=dev))).half()
+        ms, hs = {k: [] for k in kinds}, {}
+        for rnd in range(args.rounds + 1):  # (round 0 warms up)
+            for k in kinds:  # alternating: both see the same minutes of the machine
+                h = Hessian(K, dev, k)
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(calls):
+                    h.add_batch(x)
+                b.record()
+                torch.cuda.synchronize()
+                if rnd:
+                    ms[k].append(a.elapsed_time(b))
+                hs[k] = h.H
+        point = {"K": K, "tokens_per_call": x.shape[0] * x.shape[1], "calls": calls}
+        for k in kinds:
+            point[k + "_ms"] = [round(t, 3) for t in ms[k]]
+            point[k + "_ms_median"] = round(_median(ms[k]), 3)
+        spread = max(max(ms[k]) - min(ms[k]) for k in kinds)
+        point["spread_ms"] = round(spread, 3)
+        point["speedup"] = round(point["torch_ms_median"] / point["fused_ms_median"], 2)
+        point["fused_wins_by_more_than_the_spread"] = bool(min(ms["torch"]) - max(ms["fused"]) > spread)
+        point["fused_tflops"] = round(2.0 * calls * point["tokens_per_call"] * K * K / (point["fused_ms_median"] * 1e-3) / 1e12, 1)  # of the full, unhalved product
+        point["relative_difference"] = float((hs["fused"].double() - hs["torch"].double()).norm() / hs["torch"].double().norm())
+        print(json.dumps(point))
+        points.append(point)
+        del x, hs, h
+
+    # one layer of Llama-2-7B's shape through quantize_model: what share of it the four Hessians are
+    hid, inter, heads, vocab, nseq, seqlen = (256, 512, 4, 1000, 4, 128) if args.small else (4096, 11008, 32, 1000, 128, 2048)
+    cfg = SimpleNamespace(model_type="llama", vocab_size=vocab, hidden_size=hid, num_attention_heads=heads, num_key_value_heads=heads,
+                          intermediate_size=inter, num_hidden_layers=1, rms_norm_eps=1e-6, rope_theta=10000.0)
+    sd = {"model.embed_tokens.weight": torch.randn((vocab, hid), generator=g, device=dev).half(), "model.norm.weight": torch.ones(hid).half(),
+          "lm_head.weight": (0.2 * torch.randn((vocab, hid), generator=g, device=dev)).half()}
+    for name, (n, k) in {"self_attn.q_proj": (hid, hid), "self_attn.k_proj": (hid, hid), "self_attn.v_proj": (hid, hid), "self_attn.o_proj": (hid, hid),
+                         "mlp.gate_proj": (inter, hid), "mlp.up_proj": (inter, hid), "mlp.down_proj": (hid, inter)}.items():
+        sd[f"model.layers.0.{name}.weight"] = (torch.randn((n, k), generator=g, device=dev) * k ** -0.5).half()
+    for name in ("input_layernorm", "post_attention_layernorm"):
+        sd[f"model.layers.0.{name}.weight"] = torch.ones(hid).half()
+    ids = torch.randint(0, vocab, (nseq, seqlen), generator=torch.Generator().manual_seed(1))
+    timers, plain = None, Hessian.add_batch
+
+    def timed(self, x):
+        with timers.section("hessian"):
+            plain(self, x)
+
+    Hessian.add_batch = timed
+    total, hess = {k: [] for k in kinds}, {k: [] for k in kinds}
+    try:
+        for rnd in range(args.rounds + 1):
+            for k in kinds:
+                timers = EventTimers(torch)
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                quantize_model(sd, cfg, ids, 128, device=dev, hessian=k)
+                b.record()
+                torch.cuda.synchronize()
+                if rnd:
+                    total[k].append(a.elapsed_time(b))
+                    hess[k].append(timers.totals()["hessian"])
+    finally:
+        Hessian.add_batch = plain
+    layer = {"hidden": hid, "intermediate": inter, "sequences": nseq, "seqlen": seqlen, "group_size": 128}
+    for k in kinds:
+        t, h = _median(total[k]), _median(hess[k])
+        layer[k] = {"layer_ms": [round(v, 1) for v in total[k]], "hessian_ms": [round(v, 1) for v in hess[k]], "layer_ms_median": round(t, 1),
+                    "hessian_ms_median": round(h, 1), "hessian_share": round(h / t, 3)}
+    print(json.dumps(layer))
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "points": points, "layer": layer}, f, indent=1)
         f.write("\n")
 
 

@@ -29,6 +29,8 @@ reference's examples/quant_model.py; --rotation is its rotation stage, --smooth 
            reference's scale_list.pth.
 --factor   torch | fused: where every linear's factor of the inverse Hessian comes from -- torch's three Cholesky steps (the default) or
            the project's own kernels (qqq_amd.quant.ops.upper_factor: the same matrix, faster, not torch's bits).
+--hessian  torch | fused: how every layer's four Hessians are accumulated -- the reference's f32 steps (the default) or
+           qqq_amd.quant.ops.hessian_update (one fp16-MFMA launch per batch: the same matrix, faster, not torch's bits).
 Prints one JSON line: group_size, nsamples, seqlen, linears, seconds (and rotation, smooth).
 """
 import argparse
@@ -64,6 +66,7 @@ def main():
                     help="find every group's scale before the sweep (the reference's default; off here; needed by --act-order with groups)")
     ap.add_argument("--smooth", choices=("os+", "awq", "sq"), default=None, help="smooth the state dict before GPTQ (after --rotation)")
     ap.add_argument("--factor", choices=("torch", "fused"), default="torch", help="the Cholesky chain of torch, or ops.upper_factor")
+    ap.add_argument("--hessian", choices=("torch", "fused"), default="torch", help="the reference's f32 accumulation, or ops.hessian_update")
     ap.add_argument("--save-scales", default=None, help="with --smooth: where to torch.save the scale_list")
     args = ap.parse_args()
     if args.save_scales and not args.smooth:
@@ -103,7 +106,7 @@ def main():
     t0 = time.perf_counter()
     lm = quantize_model(load_state_dict(args.weights), SimpleNamespace(**cfg), ids, args.group_size, mse=args.mse, percdamp=args.percdamp,
                         seq_batch=args.seq_batch, results=results, rotation=rotation, act_order=args.act_order,
-                        static_groups=args.static_groups, smooth=args.smooth, factor=args.factor)
+                        static_groups=args.static_groups, smooth=args.smooth, factor=args.factor, hessian=args.hessian)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     os.makedirs(args.out, exist_ok=True)
