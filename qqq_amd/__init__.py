@@ -53,6 +53,10 @@ Public surface (mirrors the reference's hot path, HandH1998/QQQ):
     lora_add(y, xq, s1, A, B, scale, slot, part_cols)                               # batched LoRA beside the GEMM: every row adds its own
                                                                                     # adapter's low-rank product, its slot read on the device
     LoraBank(lm, slots, rank), LoraStep, generate(..., lora=bank, adapters=[...])   # multi-LoRA serving; qqq_amd/lora.py
+    moe_route(logits, top_k, renorm) / moe_gemm(xq, s1, B, s2, s3, ids, offsets, order, top_k, a_div, group_size) / moe_combine(y, w, top_k)
+                                                                                    # a mixture-of-experts MLP: top-k routing sorted by
+                                                                                    # expert, the grouped W4A8 GEMM over routed rows, the combine
+    QuantMoeExperts, QuantSparseMoeBlock                                            # Qwen3-MoE / Mixtral layers; qqq_amd/moe.py
 """
 from .ops import (  # noqa: F401
     ban_tokens,
@@ -68,6 +72,9 @@ from .ops import (  # noqa: F401
     fsm_mask,
     lora_add,
     marlin_qqq_gemm,
+    moe_combine,
+    moe_gemm,
+    moe_route,
     mul,
     penalize_logits,
     prefill_attention_paged,
@@ -109,6 +116,7 @@ from .model import QuantLlamaForCausalLM, QuantLlamaModel  # noqa: F401
 from .serve import DecodeLoop, GuidedDecodeLoop, SpecDecodeLoop, ngram_draft  # noqa: F401
 from .guided import TokenFSM  # noqa: F401
 from .lora import LoraBank, LoraStep  # noqa: F401
+from .moe import QuantMoeExperts, QuantSparseMoeBlock  # noqa: F401
 from .score import pack_steps  # noqa: F401
 from .beam import BeamHypothesis  # noqa: F401
 
@@ -122,4 +130,5 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "decode_attention_paged_shared", "decode_attention_paged_shared_kv8", "decode_attention_shared_plan",
            "topk_logprobs", "topk_logprobs_step", "TokenLogprobs", "ban_tokens", "stop_check",
            "beam_step", "copy_blocks", "BeamHypothesis", "fsm_mask", "fsm_advance", "TokenFSM", "GuidedDecodeLoop",
-           "lora_add", "LoraBank", "LoraStep", "rope_qkv_norm", "rope_qkv_norm_kv8", "rope_qkv_norm_paged", "rope_qkv_norm_paged_kv8"]
+           "lora_add", "LoraBank", "LoraStep", "rope_qkv_norm", "rope_qkv_norm_kv8", "rope_qkv_norm_paged", "rope_qkv_norm_paged_kv8",
+           "moe_route", "moe_gemm", "moe_combine", "QuantMoeExperts", "QuantSparseMoeBlock"]

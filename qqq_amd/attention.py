@@ -442,13 +442,21 @@ class QuantLlamaDecoderLayer(nn.Module):
 
     def __init__(self, hidden: int, num_heads: int, num_kv_heads: int, intermediate: int, group_size: int, head_dim: Optional[int] = None,
                  qkv_bias: bool = False, o_bias: bool = False, rms_norm_eps: float = 1e-6, rope_theta: float = 10000.0,
-                 rope_scaling: Optional[dict] = None, layer_idx: int = 0, qk_norm: bool = False):
+                 rope_scaling: Optional[dict] = None, layer_idx: int = 0, qk_norm: bool = False, moe: Optional[dict] = None):
+        """`moe` (None: the dense MLP): dict(num_experts, top_k, moe_intermediate, norm_topk_prob) -- the layer's MLP is then a
+        QuantSparseMoeBlock (qqq_amd/moe.py), routed on the fp16 output of post_attention_layernorm; `intermediate` is not used."""
         super().__init__()
         self.hidden_size = hidden
         self.self_attn = QuantLlamaAttention(hidden, num_heads, num_kv_heads, group_size, head_dim=head_dim, qkv_bias=qkv_bias,
                                              o_bias=o_bias, rope_theta=rope_theta, rope_scaling=rope_scaling, layer_idx=layer_idx,
                                              qk_norm=qk_norm, rms_norm_eps=rms_norm_eps)
-        self.mlp = QuantLlamaMLP(hidden, intermediate, group_size)
+        if moe is None:
+            self.mlp = QuantLlamaMLP(hidden, intermediate, group_size)
+        else:
+            from .moe import QuantSparseMoeBlock
+
+            self.mlp = QuantSparseMoeBlock(hidden, moe["moe_intermediate"], moe["num_experts"], moe["top_k"], moe["norm_topk_prob"], group_size)
+        self.sparse = moe is not None
         self.input_layernorm = QuantRMSNorm(hidden, eps=rms_norm_eps)
         self.post_attention_layernorm = QuantRMSNorm(hidden, eps=rms_norm_eps)
 
@@ -457,11 +465,26 @@ class QuantLlamaDecoderLayer(nn.Module):
         """The layer of a transformers LlamaConfig, Qwen2Config or Qwen3Config (duck-typed, 4.x or 5.x attribute style).  Qwen2: q/k/v
         with bias, o without; Llama and Qwen3: all four follow `attention_bias`; Qwen3: q_norm / k_norm (qk_norm=True), head_dim from the
         config.  Sliding-window Qwen2 / Qwen3 (`use_sliding_window`, or a `layer_types` entry other than "full_attention") and rope types
-        other than "default" / "llama3" raise NotImplementedError."""
+        other than "default" / "llama3" raise NotImplementedError.
+        Qwen3MoeConfig (`qwen3_moe`): Qwen3's attention; layer i is sparse -- num_experts, num_experts_per_tok, moe_intermediate_size,
+        norm_topk_prob -- unless it is in `mlp_only_layers` or (i + 1) % decoder_sparse_step != 0, and then takes the dense MLP of
+        intermediate_size.  MixtralConfig (`mixtral`): Llama's attention, every layer sparse with num_local_experts experts of
+        intermediate_size, always renormalised; a non-null `sliding_window` raises NotImplementedError."""
         if getattr(config, "hidden_act", "silu") != "silu":
             raise NotImplementedError(f"hidden_act {config.hidden_act!r}: only SiLU MLPs are supported")
         qwen2 = getattr(config, "model_type", "") == "qwen2"
-        qwen3 = getattr(config, "model_type", "") == "qwen3"
+        qwen3 = getattr(config, "model_type", "") in ("qwen3", "qwen3_moe")
+        moe = None
+        if getattr(config, "model_type", "") == "qwen3_moe":
+            step = getattr(config, "decoder_sparse_step", 1) or 1
+            if config.num_experts > 0 and layer_idx not in (getattr(config, "mlp_only_layers", None) or ()) and (layer_idx + 1) % step == 0:
+                moe = dict(num_experts=config.num_experts, top_k=config.num_experts_per_tok, moe_intermediate=config.moe_intermediate_size,
+                           norm_topk_prob=bool(getattr(config, "norm_topk_prob", False)))
+        elif getattr(config, "model_type", "") == "mixtral":
+            if getattr(config, "sliding_window", None) is not None:
+                raise NotImplementedError("sliding-window attention is not supported")
+            moe = dict(num_experts=config.num_local_experts, top_k=config.num_experts_per_tok, moe_intermediate=config.intermediate_size,
+                       norm_topk_prob=True)
         if (qwen2 or qwen3) and getattr(config, "use_sliding_window", False):
             raise NotImplementedError("sliding-window attention is not supported")
         if qwen3 and any(t != "full_attention" for t in (getattr(config, "layer_types", None) or ())):
@@ -473,7 +496,7 @@ class QuantLlamaDecoderLayer(nn.Module):
         return cls(config.hidden_size, heads, kv, config.intermediate_size, group_size,
                    head_dim=getattr(config, "head_dim", None) or config.hidden_size // heads,
                    qkv_bias=True if qwen2 else bias, o_bias=False if qwen2 else bias, rms_norm_eps=config.rms_norm_eps,
-                   rope_theta=theta, rope_scaling=rope, layer_idx=layer_idx, qk_norm=qwen3)
+                   rope_theta=theta, rope_scaling=rope, layer_idx=layer_idx, qk_norm=qwen3, moe=moe)
 
     def fuse_decode(self):
         """self_attn.fuse_decode(): one-token steps take the split-K decode attention kernel.  Returns self."""
@@ -532,12 +555,21 @@ class QuantLlamaDecoderLayer(nn.Module):
         held = getattr(step, "lora", None)
         return held.layer(self.self_attn.layer_idx) if held is not None else None
 
+    def _mlp(self, x: torch.Tensor, a: torch.Tensor, step) -> torch.Tensor:
+        """mlp(post_attention_layernorm(a + x)); `a` becomes h = fp16(a + x) in the launch that quantises its norm.  A sparse block also
+        takes the norm's fp16 output, for its router; a dense layer runs exactly the two calls it always ran."""
+        if self.sparse:
+            mq, ms, y = self.post_attention_layernorm(x, a, return_y=True)
+            return self.mlp.forward_int8(mq, ms, y, self._lora(step))
+        mq, ms = self.post_attention_layernorm(x, a)
+        return forward_int8_lora(self.mlp, mq, ms, self._lora(step))
+
     def forward(self, hidden: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
         x = hidden.reshape(-1, self.hidden_size)
         a = self.self_attn.forward_int8(*self.input_layernorm(x), cache, start)
         # a becomes h = fp16(a + x), torch's `residual + attn_out` (fp16 addition commutes), in the launch that quantises its norm
-        mq, ms = self.post_attention_layernorm(x, a)
-        return (a + forward_int8_lora(self.mlp, mq, ms, self._lora(start))).reshape(hidden.shape)
+        m = self._mlp(x, a, start)
+        return (a + m).reshape(hidden.shape)
 
     def forward_chained(self, delta: torch.Tensor, residual: Optional[torch.Tensor], cache: KVCache, start: int):
         """The layer on a hidden state handed over as an unformed sum, hidden = residual + delta, returned the same way: (delta, residual)
@@ -551,8 +583,7 @@ class QuantLlamaDecoderLayer(nn.Module):
         else:
             xq, s1 = self.input_layernorm(delta, residual)  # residual becomes the hidden state
         a = self.self_attn.forward_int8(xq, s1, cache, start)
-        mq, ms = self.post_attention_layernorm(residual, a)  # a becomes h = hidden + attention
-        return forward_int8_lora(self.mlp, mq, ms, self._lora(start)), a
+        return self._mlp(residual, a, start), a  # a becomes h = hidden + attention
 
 
 __all__ = ["KVCache", "PagedKVCache", "PagedStep", "QuantLlamaAttention", "QuantLlamaDecoderLayer", "rope_inv_freq", "rope_tables"]

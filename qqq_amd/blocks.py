@@ -20,16 +20,17 @@ class QuantRMSNorm(nn.Module):
     """LlamaRMSNorm (fp16) whose output is the per-token int8 quantisation (xq, s1) the next QuantLinear.forward_int8 takes.
 
     forward(x) -> (xq, s1) of y = weight * fp16(float(x) * rsqrt(mean(float(x)^2) + eps)).
-    forward(x, residual) -> the same of the norm of h = fp16(residual + x); `residual` is updated to h in place."""
+    forward(x, residual) -> the same of the norm of h = fp16(residual + x); `residual` is updated to h in place.
+    return_y=True -> (xq, s1, y): the fp16 output as well (a mixture-of-experts block routes on it)."""
 
     def __init__(self, hidden_size: int, eps: float = 1e-6):
         super().__init__()
         self.weight = nn.Parameter(torch.ones(hidden_size, dtype=torch.float16), requires_grad=False)
         self.variance_epsilon = eps
 
-    def forward(self, x: torch.Tensor, residual: torch.Tensor = None):
+    def forward(self, x: torch.Tensor, residual: torch.Tensor = None, return_y: bool = False):
         w = self.weight if self.weight.dtype == torch.float16 else self.weight.half()
-        return ops.rmsnorm_quant(x, w, self.variance_epsilon, residual=residual)
+        return ops.rmsnorm_quant(x, w, self.variance_epsilon, residual=residual, return_y=return_y)
 
     def extra_repr(self) -> str:
         return f"{self.weight.shape[0]}, eps={self.variance_epsilon}"

@@ -43,6 +43,7 @@
 //   qqq_stop.hip.h     stop sequences, stop token ids and the minimum length: the ban in front of a sampler, the check behind a loop's step
 //   qqq_guided.hip.h   guided decoding over a token automaton in device memory: the mask in front of a sampler, the advance behind a loop's step
 //   qqq_lora.hip.h     the batched LoRA op: fp16 low-rank adapters added to a GEMM's output, every token's adapter read from device memory
+//   qqq_moe.hip.h      mixture-of-experts layers: the router's top-k and stable sort by expert, the grouped GEMM over routed rows, the combine
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -105,6 +106,8 @@
 #include "../../include/qqq_amd_guided.h"
 #include "qqq_lora.hip.h"
 #include "../../include/qqq_amd_lora.h"
+#include "qqq_moe.hip.h"
+#include "../../include_ops/qqq_amd_moe.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -2003,6 +2006,102 @@ extern "C" int qqq_lora_add(void* y, int ldy, const void* xq, const void* s1, co
   lora_launch(R, grid, static_cast<hipStream_t>(stream), a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_lora_add_kernel launch");
+  return QQQ_OK;
+}
+
+// ---- mixture-of-experts layers (include_ops/qqq_amd_moe.h; kernels in qqq_moe.hip.h): route = selection + sort, two launches; the
+// grouped GEMM, one launch over (column strip, expert); the combine, one launch.  No workspace anywhere.
+extern "C" int qqq_moe_route(const void* logits, int ld, void* ids, void* w, void* offsets, void* order, int T, int E, int top_k, int renorm,
+                             int dev, void* stream) {
+  g_err[0] = 0;
+  if (E < 2 || E > MOE_MAX_E || top_k < 1 || top_k > MOE_MAX_TOPK || top_k > E) {
+    snprintf(g_err, sizeof(g_err), "qqq_moe_route: E=%d top_k=%d (need 2 <= E <= %d and 1 <= top_k <= min(E, %d))", E, top_k, MOE_MAX_E,
+             MOE_MAX_TOPK);
+    return QQQ_ERR_ARG;
+  }
+  if (T < 0 || (long long)T * top_k > 131072 || ld < E) {
+    snprintf(g_err, sizeof(g_err), "qqq_moe_route: T=%d ld=%d (need T >= 0, T * top_k <= 131072 and ld >= E=%d)", T, ld, E);
+    return QQQ_ERR_ARG;
+  }
+  if (T == 0) return QQQ_OK;
+  if (!logits || !ids || !w || !offsets || !order || misaligned(logits, 2) || misaligned(ids, 4) || misaligned(w, 4) ||
+      misaligned(offsets, 4) || misaligned(order, 4)) {
+    snprintf(g_err, sizeof(g_err), "qqq_moe_route: bad argument (every pointer must be non-NULL; logits 2-byte, the outputs 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(qqq_moe_topk_kernel, dim3((T + MOE_ROUTE_WAVES - 1) / MOE_ROUTE_WAVES), dim3(MOE_ROUTE_WAVES * 64), 0, st,
+                     static_cast<const _Float16*>(logits), ld, static_cast<int*>(ids), static_cast<float*>(w), T, E, top_k, renorm);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_moe_topk_kernel launch");
+  hipLaunchKernelGGL(qqq_moe_sort_kernel, dim3(1), dim3(MOE_SORT_WAVES * 64), 0, st, static_cast<const int*>(ids),
+                     static_cast<int*>(offsets), static_cast<int*>(order), T * top_k, E);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_moe_sort_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_moe_gemm(const void* xq, const void* s1, const void* B, const void* s2, const void* s3, const void* ids,
+                            const void* offsets, const void* order, void* D, int P, int R, int E, int N, int K, int a_div, int group_size,
+                            int dev, void* stream) {
+  g_err[0] = 0;
+  if (K < 128 || K % 128 != 0 || N < 64 || N % 64 != 0 || E < 1 || E > MOE_MAX_E || (group_size != -1 && group_size != 128)) {
+    snprintf(g_err, sizeof(g_err), "qqq_moe_gemm: bad shape E=%d N=%d K=%d group_size=%d (need K a positive multiple of 128, N of 64, "
+             "1 <= E <= %d, group_size -1 or 128)", E, N, K, group_size, MOE_MAX_E);
+    return QQQ_ERR_ARG;
+  }
+  if (P < 0 || P > 2097152 || a_div < 1 || (P > 0 && (long long)R * a_div < P)) {
+    snprintf(g_err, sizeof(g_err), "qqq_moe_gemm: P=%d R=%d a_div=%d (need 0 <= P <= 2097152, a_div >= 1 and R >= ceil(P / a_div) "
+             "activation rows)", P, R, a_div);
+    return QQQ_ERR_ARG;
+  }
+  if (P == 0) return QQQ_OK;
+  const bool grouped = group_size != -1;
+  if (!xq || !s1 || !B || !s2 || (grouped && !s3) || !ids || !offsets || !order || !D || misaligned(xq, 16) || misaligned(s1, 4) ||
+      misaligned(B, 16) || misaligned(s2, 8) || misaligned(s3, 16) || misaligned(offsets, 4) || misaligned(order, 4) || misaligned(D, 8)) {
+    snprintf(g_err, sizeof(g_err), "qqq_moe_gemm: bad argument (every pointer must be non-NULL -- s3 with group_size 128 --; xq, B and s3 "
+             "16-byte, s2 and D 8-byte, s1, offsets and order 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  qqq_moe_gemm_args a;
+  a.xq = static_cast<const int8_t*>(xq);
+  a.s1 = static_cast<const float*>(s1);
+  a.B = static_cast<const unsigned char*>(B);
+  a.s2 = static_cast<const float*>(s2);
+  a.s3 = static_cast<const _Float16*>(s3);
+  a.offsets = static_cast<const int*>(offsets);
+  a.order = static_cast<const int*>(order);
+  a.D = static_cast<_Float16*>(D);
+  a.P = P;
+  a.R = R;
+  a.N = N;
+  a.K = K;
+  a.a_div = a_div;
+  DeviceGuard guard(dev);
+  moe_gemm_launch(grouped, dim3((N + 127) / 128, E), static_cast<hipStream_t>(stream), a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_moe_gemm_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_moe_combine(const void* y, const void* w, void* out, int T, int top_k, int H, int dev, void* stream) {
+  g_err[0] = 0;
+  if (T < 0 || T > 1048576 || top_k < 1 || top_k > MOE_MAX_TOPK || H < 8 || H % 8 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_moe_combine: T=%d top_k=%d H=%d (need 0 <= T <= 1048576, 1 <= top_k <= %d, H a positive multiple "
+             "of 8)", T, top_k, H, MOE_MAX_TOPK);
+    return QQQ_ERR_ARG;
+  }
+  if (T == 0) return QQQ_OK;
+  if (!y || !w || !out || misaligned(y, 16) || misaligned(w, 4) || misaligned(out, 16)) {
+    snprintf(g_err, sizeof(g_err), "qqq_moe_combine: bad argument (every pointer must be non-NULL; y and out 16-byte, w 4-byte aligned)");
+    return QQQ_ERR_ARG;
+  }
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_moe_combine_kernel, dim3(T, (H / 8 + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const _Float16*>(y), static_cast<const float*>(w), static_cast<_Float16*>(out), H, top_k);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_moe_combine_kernel launch");
   return QQQ_OK;
 }
 

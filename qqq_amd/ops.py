@@ -2727,3 +2727,89 @@ def lora_add(y: torch.Tensor, xq: torch.Tensor, s1: torch.Tensor, A: torch.Tenso
     else:
         _lora_add_impl(*ts, part_cols)
     return y
+
+
+# ---- mixture-of-experts layers (include_ops/qqq_amd_moe.h): the router's top-k and sort by expert, the grouped W4A8 GEMM over routed
+# rows, the weighted combine.  Nothing is read on the host and every launch size depends on the shapes alone.
+
+def _moe_check(op, named):
+    for name, t, dt in named:
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise RuntimeError(f"{op}: {name} must be a {_dt(dt)} tensor")
+    _same_gpu(op, [t for _, t, _ in named])
+
+
+def moe_route(logits: torch.Tensor, top_k: int, renorm: bool = True):
+    """The router of a mixture-of-experts layer behind its logits -> (ids int32 [T, top_k], w f32 [T, top_k], offsets int32 [E + 1],
+    order int32 [T * top_k]).  logits fp16 [T, E] (unit column stride), 2 <= E <= 256, 1 <= top_k <= min(E, 16), T * top_k <= 131072.
+    f32 softmax over the row, the top_k largest probabilities in descending order (ties to the lower expert), divided by their sum with
+    `renorm`; then the pairs p = t * top_k + j sorted by expert, stably: order[offsets[e] : offsets[e + 1]] are expert e's pairs,
+    ascending.  A row of NaN or inf logits still gives distinct ids inside [0, E).  Two launches, whatever the routing; the exact
+    arithmetic is stated in include_ops/qqq_amd_moe.h."""
+    _moe_check("moe_route", (("logits", logits, torch.float16),))
+    if logits.dim() != 2 or (logits.shape[0] > 1 and logits.stride(1) != 1):
+        raise RuntimeError(f"moe_route: logits must be fp16 [T, E] with unit column stride, not {tuple(logits.shape)}")
+    if logits.numel() and logits.stride(1) != 1:
+        logits = logits.contiguous()
+    (T, E), k = logits.shape, int(top_k)
+    dev = logits.device
+    ids = torch.empty((T, k), dtype=torch.int32, device=dev)
+    w = torch.empty((T, k), dtype=torch.float32, device=dev)
+    offsets = torch.empty((E + 1,), dtype=torch.int32, device=dev)
+    order = torch.empty((T * k,), dtype=torch.int32, device=dev)
+    if T == 0:
+        offsets.zero_()
+    err = _lib.lib().qqq_moe_route(_ptr(logits), logits.stride(0) if T > 1 else E, _ptr(ids), _ptr(w), _ptr(offsets), _ptr(order), T, E, k,
+                                   int(bool(renorm)), dev.index or 0, _stream_for(logits))
+    _raise_lib("moe_route", err)
+    return ids, w, offsets, order
+
+
+def moe_gemm(xq: torch.Tensor, s1: torch.Tensor, B: torch.Tensor, s2: torch.Tensor, s3: torch.Tensor, ids: torch.Tensor,
+             offsets: torch.Tensor, order: torch.Tensor, top_k: int, a_div: int, group_size: int = -1) -> torch.Tensor:
+    """The grouped W4A8 GEMM of a mixture-of-experts layer, one launch -> D fp16 [T * top_k, N] in pair order.
+
+    xq, s1       int8 [R, K] and f32 [R] or [R, 1]: quantised activation rows; pair p reads row p // a_div (a_div = top_k: the token's row,
+                 the gate | up GEMM; a_div = 1: the pair's own row, the down GEMM)
+    B, s2, s3    int32 [E, K / 16, 2 N], f32 [E, N] (or [E, 1, N]), fp16 [E, K / 128, N] or empty (per-channel): the experts' packed
+                 QuantLinear buffers stacked
+    ids, offsets, order   moe_route's
+    Row p is bit for bit QuantLinear.forward_int8 of its activation row against expert ids[p]'s weights.  K % 128 == 0, N % 64 == 0,
+    any number of rows per expert.  include_ops/qqq_amd_moe.h states the arithmetic."""
+    _moe_check("moe_gemm", (("xq", xq, torch.int8), ("s1", s1, torch.float32), ("B", B, torch.int32), ("s2", s2, torch.float32),
+                            ("s3", s3, torch.float16), ("ids", ids, torch.int32), ("offsets", offsets, torch.int32),
+                            ("order", order, torch.int32)))
+    if xq.dim() != 2 or B.dim() != 3 or B.shape[1] * 16 != xq.shape[1] or B.shape[2] % 128:
+        raise RuntimeError(f"moe_gemm: xq must be int8 [R, K] and B int32 [E, K / 16, 2 N], not {tuple(xq.shape)} and {tuple(B.shape)}")
+    (R, K), E, N, P = xq.shape, B.shape[0], B.shape[2] // 2, order.numel()
+    grouped = s3.numel() != 0
+    if group_size not in (-1, 128) or grouped != (group_size == 128):
+        raise RuntimeError(f"moe_gemm: group_size {group_size} must be -1 with an empty s3 or 128 with s3 fp16 [E, K / 128, N]")
+    if s1.numel() != R or s2.numel() != E * N or (grouped and s3.numel() != E * (K // 128) * N) or ids.numel() != P or \
+            offsets.numel() != E + 1 or P % int(top_k):
+        raise RuntimeError(f"moe_gemm: with xq {tuple(xq.shape)} and B {tuple(B.shape)}: s1 must hold {R}, s2 {E * N}, ids as many as order "
+                           f"(a multiple of top_k) and offsets {E + 1} elements")
+    for name, t in (("xq", xq), ("s1", s1), ("B", B), ("s2", s2), ("s3", s3), ("ids", ids), ("offsets", offsets), ("order", order)):
+        if not t.is_contiguous():
+            raise RuntimeError(f"moe_gemm: {name} must be contiguous")
+    D = torch.empty((P, N), dtype=torch.float16, device=xq.device)
+    err = _lib.lib().qqq_moe_gemm(_ptr(xq), _ptr(s1), _ptr(B), _ptr(s2), _ptr(s3), _ptr(ids), _ptr(offsets), _ptr(order), _ptr(D), P, R, E,
+                                  N, K, int(a_div), group_size, xq.device.index or 0, _stream_for(xq))
+    _raise_lib("moe_gemm", err)
+    return D
+
+
+def moe_combine(y: torch.Tensor, w: torch.Tensor, top_k: int) -> torch.Tensor:
+    """out[t, h] = fp16(sum_j w[t, j] * float(y[t * top_k + j, h])) -> fp16 [T, H]: the experts' outputs of a token, weighted and summed in
+    f32 in slot order (separate multiplies and adds onto 0.0f), one rounding, one launch.  y fp16 [T * top_k, H], H % 8 == 0; w f32
+    [T, top_k].  include_ops/qqq_amd_moe.h states the arithmetic."""
+    _moe_check("moe_combine", (("y", y, torch.float16), ("w", w, torch.float32)))
+    k = int(top_k)
+    if y.dim() != 2 or w.dim() != 2 or w.shape[1] != k or y.shape[0] != w.shape[0] * k or not y.is_contiguous() or not w.is_contiguous():
+        raise RuntimeError(f"moe_combine: y must be a contiguous fp16 [T * {k}, H] and w a contiguous f32 [T, {k}], not {tuple(y.shape)} and "
+                           f"{tuple(w.shape)}")
+    T, H = w.shape[0], y.shape[1]
+    out = torch.empty((T, H), dtype=torch.float16, device=y.device)
+    err = _lib.lib().qqq_moe_combine(_ptr(y), _ptr(w), _ptr(out), T, k, H, y.device.index or 0, _stream_for(y))
+    _raise_lib("moe_combine", err)
+    return out
