@@ -56,7 +56,7 @@
 
 #include <stddef.h>
 
-#include "../include/qqq_amd.h"
+#include "qqq_amd.h"
 
 #ifdef __cplusplus
 extern "C" {

@@ -22,7 +22,7 @@ prefill_attention_paged(_kv8): one ragged causal attention over the whole packed
 input already int8-quantised.  After the opt-in fuse_verify() a step that feeds every sequence the same 2 ... 16 tokens (a speculative decode
 step's chunk) runs verify_attention_paged(_kv8): the decode kernel's split over keys, every token bit for bit its decode step.
 Qwen3 (qk_norm=True): a per-head RMSNorm of q and k between the projections and RoPE; every rope_qkv* call above is then its
-rope_qkv_norm* counterpart, the norm inside the same launch (include_ops/qqq_amd_qknorm.h).
+rope_qkv_norm* counterpart, the norm inside the same launch (include/qqq_amd_qknorm.h).
 Parameter and buffer names are the reference's, so the layers' state-dicts load unchanged; the rope tables, the fused q|k|v copy of
 fuse_qkv() and the fuse_decode() / fuse_prefill() / fuse_verify() / fuse_shared() flags are not part of them.
 """

@@ -5,18 +5,12 @@
                                csrc/qqq_rates.h: pure host C++, compiles alone with the host compiler)
     qqq_amd/libqqq_amd_dev.so  test / tuning companion (include/qqq_amd_dev.h) <- csrc/qqq_dev.hip
     qqq_amd/_torch_ext*.so     compiled torch binding (pybind + TORCH_LIBRARY) of the operator library <- csrc/qqq_torch.cpp
-    qqq_amd/libqqq_amd_quant.so  the GPTQ quantiser (quant/include/*.h, quant/include_ext/*.h and quant/include_ops/*.h), an offline tool beside the operator <- quant/csrc/qqq_quant.hip
+    qqq_amd/libqqq_amd_quant.so  the GPTQ quantiser (quant/include/*.h), an offline tool beside the operator <- quant/csrc/qqq_quant.hip
 
 Each library has ONE flat directory of headers and one lister: operator_headers() for include/, quant_headers() for quant/include/.  A library
-is rebuilt for, and bound from, what its lister returns, so a new feature adds include/qqq_amd_<feature>.h, includes it from the translation
-unit, and nothing here.  The quantiser has a second flat directory, quant/include_ext/ (quant_ext_headers()): the contents of quant/include/
-are pinned by name, so the header of the next quantiser op went there -- and was pinned by name in turn.  The chain ends with a third,
-quant/include_ops/ (quant_op_headers()): EVERY later quantiser op drops its header there, and no test pins that directory's listing (tests
-assert membership and that no name is declared twice).  The library is rebuilt for, and bound from, all three.
-
-The operator has a second flat directory as well, include_ops/ (operator_op_headers()): the number of headers in include/ is pinned, so
-the header of the Qwen3 q / k norm went there, and every later operator op drops its header there too.  libqqq_amd.so is rebuilt for, and
-bound from, both.
+is rebuilt for, and bound from, what its lister returns, so a new op adds qqq_amd_<feature>.h to its library's directory, includes it from
+the translation unit, and nothing else: nothing here, and no test pins a directory's listing (tests/test_abi_cpu.py states the header
+properties over whatever the listers return).
 
 The .so files are git-ignored but travel to the GPU box with the repo snapshot.
 """
@@ -27,7 +21,7 @@ import shutil
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(_HERE, "csrc", "qqq_w4a8.hip")  # the one translation unit of the operator; it includes csrc/*.hip.h, csrc/qqq_plan.h and every header operator_headers() and operator_op_headers() list
+SRC = os.path.join(_HERE, "csrc", "qqq_w4a8.hip")  # the one translation unit of the operator; it includes csrc/*.hip.h, csrc/qqq_plan.h and every header operator_headers() lists
 DEV_SRC = os.path.join(_HERE, "csrc", "qqq_dev.hip")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB = os.environ.get("QQQ_AMD_LIB") or os.path.join(_HERE, "libqqq_amd.so")  # override: tuning builds only
@@ -56,26 +50,22 @@ def operator_headers() -> list:
     return [h for h in headers() if h != header("qqq_amd_dev.h")]
 
 
-OPS_INCLUDE = os.path.join(os.path.dirname(_HERE), "include_ops")  # flat, and open: the operator's headers from the Qwen3 q / k norm on
+def _sources(unit: str) -> list:
+    """every .hip and .h file beside a translation unit: what it includes is not tracked file by file"""
+    csrc = os.path.dirname(unit)
+    return [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
 
 
-def operator_op_headers() -> list:
-    """the operator library's headers outside include/, whose listing is pinned by count: one new file under include_ops/ is all a later
-    operator op adds here"""
-    return sorted(os.path.join(OPS_INCLUDE, f) for f in os.listdir(OPS_INCLUDE) if f.endswith(".h"))
-
-
-def _stale(lib: str, extra) -> bool:
+def _stale(lib: str, deps) -> bool:
+    """missing, or older than any dep"""
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    csrc = os.path.dirname(SRC)
-    deps = list(extra) + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
     return any(os.path.getmtime(p) > t for p in deps)
 
 
 def needs_build() -> bool:
-    return _stale(LIB, operator_headers() + operator_op_headers())
+    return _stale(LIB, operator_headers() + _sources(SRC))
 
 
 def _compile(src: str, out: str, verbose: bool, flags=()) -> str:
@@ -98,7 +88,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 QUANT_DIR = os.path.join(_HERE, "quant")
-QUANT_SRC = os.path.join(QUANT_DIR, "csrc", "qqq_quant.hip")  # the one translation unit of the quantiser; it includes quant/csrc/*.hip.h and every header quant_headers(), quant_ext_headers() and quant_op_headers() list
+QUANT_SRC = os.path.join(QUANT_DIR, "csrc", "qqq_quant.hip")  # the one translation unit of the quantiser; it includes quant/csrc/*.hip.h and every header quant_headers() lists
 QUANT_INCLUDE = os.path.join(QUANT_DIR, "include")  # outside include/: headers() does not see it
 QUANT_HEADER = os.path.join(QUANT_INCLUDE, "qqq_amd_quant.h")  # the ABI version is read from it
 QUANT_LIB = os.path.join(_HERE, "libqqq_amd_quant.so")
@@ -112,33 +102,15 @@ def quant_headers() -> list:
     return sorted(os.path.join(QUANT_INCLUDE, f) for f in os.listdir(QUANT_INCLUDE) if f.endswith(".h"))
 
 
-QUANT_EXT_INCLUDE = os.path.join(QUANT_DIR, "include_ext")  # flat, like the two others
-
-
-def quant_ext_headers() -> list:
-    """the quantiser library's headers outside the pinned quant/include/: one new file under quant/include_ext/ is all a new quantiser op adds here"""
-    return sorted(os.path.join(QUANT_EXT_INCLUDE, f) for f in os.listdir(QUANT_EXT_INCLUDE) if f.endswith(".h"))
-
-
-QUANT_OPS_INCLUDE = os.path.join(QUANT_DIR, "include_ops")  # flat, and open: the headers of every quantiser op from the smoothing op on
-
-
-def quant_op_headers() -> list:
-    """the quantiser library's headers outside the two pinned directories: one new file under quant/include_ops/ is all a new quantiser op adds here"""
-    return sorted(os.path.join(QUANT_OPS_INCLUDE, f) for f in os.listdir(QUANT_OPS_INCLUDE) if f.endswith(".h"))
-
-
 def build_quant(force: bool = False, verbose: bool = False) -> str:
     """the GPTQ quantiser's library (qqq_amd/quant): an offline tool with a library of its own, libqqq_amd.so stays as it is"""
-    csrc = os.path.dirname(QUANT_SRC)
-    deps = quant_headers() + quant_ext_headers() + quant_op_headers() + [header("qqq_amd.h")] + [os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))]
-    if not force and os.path.exists(QUANT_LIB) and os.path.getmtime(QUANT_LIB) >= max(map(os.path.getmtime, deps)):
+    if not force and not _stale(QUANT_LIB, quant_headers() + [header("qqq_amd.h")] + _sources(QUANT_SRC)):
         return QUANT_LIB
     return _compile(QUANT_SRC, QUANT_LIB, verbose, QUANT_FLAGS)
 
 
 def build_dev(force: bool = False, verbose: bool = False) -> str:
-    if not force and not _stale(DEV_LIB, [header("qqq_amd.h"), header("qqq_amd_dev.h")]):
+    if not force and not _stale(DEV_LIB, [header("qqq_amd.h"), header("qqq_amd_dev.h")] + _sources(DEV_SRC)):
         return DEV_LIB
     return _compile(DEV_SRC, DEV_LIB, verbose)
 
@@ -164,7 +136,7 @@ def build_torch_ext(force: bool = False, verbose: bool = False) -> str:
     default_lib = os.path.join(_HERE, "libqqq_amd.so")
     if not os.path.exists(default_lib):
         raise RuntimeError("build the operator library first (qqq_amd.build.build())")
-    if not force and os.path.exists(out) and os.path.getmtime(out) >= max(map(os.path.getmtime, (TORCH_SRC, header("qqq_amd.h"), header("qqq_amd_score.h")))):
+    if not force and not _stale(out, [TORCH_SRC, header("qqq_amd.h"), header("qqq_amd_score.h")]):
         return out
     tdir = os.path.dirname(torch.__file__)
     cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1",

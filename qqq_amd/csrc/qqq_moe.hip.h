@@ -1,5 +1,5 @@
 // qqq_moe.hip.h -- mixture-of-experts layers: the router (softmax, top-k, stable counting sort by expert), the grouped W4A8 GEMM over
-// routed rows, and the weighted combine (include_ops/qqq_amd_moe.h states the arithmetic).
+// routed rows, and the weighted combine (include/qqq_amd_moe.h states the arithmetic).
 // Part of the single translation unit qqq_w4a8.hip (see its header comment for the design).
 #ifndef QQQ_AMD_QQQ_MOE_HIP_H_
 #define QQQ_AMD_QQQ_MOE_HIP_H_

@@ -1,5 +1,5 @@
 // qqq_qknorm.hip.h -- the per-head q / k RMSNorm of a Qwen3 attention block, fused into the rotary embedding and KV-cache write
-// (include_ops/qqq_amd_qknorm.h).  Part of the single translation unit qqq_w4a8.hip.
+// (include/qqq_amd_qknorm.h).  Part of the single translation unit qqq_w4a8.hip.
 //
 // One kernel template serves the four entry points: PAGED picks the block pool (a slot per token, token-major q_out) over the static cache
 // (the token's position, q_out in SDPA layout), KV8 the int8 rows with their scales over fp16 rows.  The four kernels without the norm
@@ -17,7 +17,7 @@
 // short dependent chain per lane, latency- not issue-bound, and sixteen f64 multiply-adds and three adds a lane are far below what the
 // loads cost.  f64 makes the order of the sum almost irrelevant to the result and cheap to restate; it is still fixed (see the header).
 //
-// Arithmetic (include_ops/qqq_amd_qknorm.h): ss in f64 in the stated order; var = float(ss / d); rs = 1 / sqrt(var + eps), both correctly
+// Arithmetic (include/qqq_amd_qknorm.h): ss in f64 in the stated order; var = float(ss / d); rs = 1 / sqrt(var + eps), both correctly
 // rounded in f32; n = fp16(x * rs); y = fp16(w * n).  A square of an fp16 number is exact in f64, so contracting it into the add changes
 // nothing; no other rounded product feeds an add here, and contraction is switched off all the same.  The square root is sqrtf, which
 // the compiler expands to a correctly rounded sequence (__fsqrt_rn is the bare approximate instruction in this toolchain).

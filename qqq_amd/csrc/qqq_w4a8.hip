@@ -79,7 +79,7 @@
 #include "qqq_paged.hip.h"
 #include "../../include/qqq_amd_paged.h"
 #include "qqq_qknorm.hip.h"
-#include "../../include_ops/qqq_amd_qknorm.h"
+#include "../../include/qqq_amd_qknorm.h"
 #include "qqq_prefill.hip.h"
 #include "../../include/qqq_amd_prefill.h"
 #include "qqq_sample.hip.h"
@@ -107,7 +107,7 @@
 #include "qqq_lora.hip.h"
 #include "../../include/qqq_amd_lora.h"
 #include "qqq_moe.hip.h"
-#include "../../include_ops/qqq_amd_moe.h"
+#include "../../include/qqq_amd_moe.h"
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -864,7 +864,7 @@ extern "C" int qqq_rope_qkv_paged_kv8(const void* q, int ld_q, const void* k, in
                         k_scale, v_scale, m, h, kvh, d, num_blocks, block_size, dev, stream);
 }
 
-// ---- Qwen3's per-head q / k RMSNorm in front of the rotation (include_ops/qqq_amd_qknorm.h; kernel in qqq_qknorm.hip.h): the four RoPE /
+// ---- Qwen3's per-head q / k RMSNorm in front of the rotation (include/qqq_amd_qknorm.h; kernel in qqq_qknorm.hip.h): the four RoPE /
 // cache-write launches above with one kernel template of their own.  One body for the four; `name` is the entry point's.  The static
 // cache comes as (b, s, cap) with slots = nullptr, the pool as (m, num_blocks, block_size) with b = m, s = 1.
 static int rope_qkv_norm(const char* name, bool paged, bool kv8, const void* q, int ld_q, const void* k, int ld_k, const void* v, int ld_v,
@@ -2009,7 +2009,7 @@ extern "C" int qqq_lora_add(void* y, int ldy, const void* xq, const void* s1, co
   return QQQ_OK;
 }
 
-// ---- mixture-of-experts layers (include_ops/qqq_amd_moe.h; kernels in qqq_moe.hip.h): route = selection + sort, two launches; the
+// ---- mixture-of-experts layers (include/qqq_amd_moe.h; kernels in qqq_moe.hip.h): route = selection + sort, two launches; the
 // grouped GEMM, one launch over (column strip, expert); the combine, one launch.  No workspace anywhere.
 extern "C" int qqq_moe_route(const void* logits, int ld, void* ids, void* w, void* offsets, void* order, int T, int E, int top_k, int renorm,
                              int dev, void* stream) {

@@ -875,7 +875,7 @@ def rope_qkv_paged_kv8(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, cos: t
     return _rope_qkv_paged_impl(*ts)
 
 
-# ---- Qwen3's per-head q / k RMSNorm fused into the four RoPE / cache-write ops above (include_ops/qqq_amd_qknorm.h): still one launch each.
+# ---- Qwen3's per-head q / k RMSNorm fused into the four RoPE / cache-write ops above (include/qqq_amd_qknorm.h): still one launch each.
 
 def _qknorm_check(name, q, k, v, cos, sin, idx, q_weight, k_weight, eps, d):
     if any(t.dtype != torch.float16 for t in (q, k, v, cos, sin, q_weight, k_weight)) or any(t.dtype != torch.int64 for t in idx):
@@ -948,7 +948,7 @@ def rope_qkv_norm(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, q_weight: t
                   cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor) -> torch.Tensor:
     """rope_qkv with Qwen3's per-head RMSNorm of q and k in front of the rotation, one launch: every q / k head row x becomes
     fp16(w * fp16(x * rsqrt(mean(x^2) + eps))) -- transformers' Qwen3RMSNorm on fp16, the mean in f64 in the order
-    include_ops/qqq_amd_qknorm.h states -- and is then rotated and stored exactly as rope_qkv does; v is untouched.
+    include/qqq_amd_qknorm.h states -- and is then rotated and stored exactly as rope_qkv does; v is untouched.
 
     q_weight, k_weight   fp16 [head_dim]: q_norm.weight and k_norm.weight;  eps  rms_norm_eps;  head_dim 64 or 128
     Everything else, the return value and the out-of-range rule are rope_qkv's."""
@@ -2729,7 +2729,7 @@ def lora_add(y: torch.Tensor, xq: torch.Tensor, s1: torch.Tensor, A: torch.Tenso
     return y
 
 
-# ---- mixture-of-experts layers (include_ops/qqq_amd_moe.h): the router's top-k and sort by expert, the grouped W4A8 GEMM over routed
+# ---- mixture-of-experts layers (include/qqq_amd_moe.h): the router's top-k and sort by expert, the grouped W4A8 GEMM over routed
 # rows, the weighted combine.  Nothing is read on the host and every launch size depends on the shapes alone.
 
 def _moe_check(op, named):
@@ -2745,7 +2745,7 @@ def moe_route(logits: torch.Tensor, top_k: int, renorm: bool = True):
     f32 softmax over the row, the top_k largest probabilities in descending order (ties to the lower expert), divided by their sum with
     `renorm`; then the pairs p = t * top_k + j sorted by expert, stably: order[offsets[e] : offsets[e + 1]] are expert e's pairs,
     ascending.  A row of NaN or inf logits still gives distinct ids inside [0, E).  Two launches, whatever the routing; the exact
-    arithmetic is stated in include_ops/qqq_amd_moe.h."""
+    arithmetic is stated in include/qqq_amd_moe.h."""
     _moe_check("moe_route", (("logits", logits, torch.float16),))
     if logits.dim() != 2 or (logits.shape[0] > 1 and logits.stride(1) != 1):
         raise RuntimeError(f"moe_route: logits must be fp16 [T, E] with unit column stride, not {tuple(logits.shape)}")
@@ -2775,7 +2775,7 @@ def moe_gemm(xq: torch.Tensor, s1: torch.Tensor, B: torch.Tensor, s2: torch.Tens
                  QuantLinear buffers stacked
     ids, offsets, order   moe_route's
     Row p is bit for bit QuantLinear.forward_int8 of its activation row against expert ids[p]'s weights.  K % 128 == 0, N % 64 == 0,
-    any number of rows per expert.  include_ops/qqq_amd_moe.h states the arithmetic."""
+    any number of rows per expert.  include/qqq_amd_moe.h states the arithmetic."""
     _moe_check("moe_gemm", (("xq", xq, torch.int8), ("s1", s1, torch.float32), ("B", B, torch.int32), ("s2", s2, torch.float32),
                             ("s3", s3, torch.float16), ("ids", ids, torch.int32), ("offsets", offsets, torch.int32),
                             ("order", order, torch.int32)))
@@ -2802,7 +2802,7 @@ def moe_gemm(xq: torch.Tensor, s1: torch.Tensor, B: torch.Tensor, s2: torch.Tens
 def moe_combine(y: torch.Tensor, w: torch.Tensor, top_k: int) -> torch.Tensor:
     """out[t, h] = fp16(sum_j w[t, j] * float(y[t * top_k + j, h])) -> fp16 [T, H]: the experts' outputs of a token, weighted and summed in
     f32 in slot order (separate multiplies and adds onto 0.0f), one rounding, one launch.  y fp16 [T * top_k, H], H % 8 == 0; w f32
-    [T, top_k].  include_ops/qqq_amd_moe.h states the arithmetic."""
+    [T, top_k].  include/qqq_amd_moe.h states the arithmetic."""
     _moe_check("moe_combine", (("y", y, torch.float16), ("w", w, torch.float32)))
     k = int(top_k)
     if y.dim() != 2 or w.dim() != 2 or w.shape[1] != k or y.shape[0] != w.shape[0] * k or not y.is_contiguous() or not w.is_contiguous():

@@ -1,6 +1,6 @@
 """qqq_amd.quant -- the GPTQ weight quantiser on the device: makes the (fake-quantised weight, scales) pair QuantLinear.pack takes, and
 whole QQQ W4A8 checkpoints from fp16 ones, rotated first where asked.  A sub-package with a HIP library of its own
-(libqqq_amd_quant.so, the headers of include/, include_ext/ and include_ops/ here): an offline tool, nothing of it is loaded by serving.
+(libqqq_amd_quant.so, the headers of include/ here): an offline tool, nothing of it is loaded by serving.
 
     ops.weight_scales, ops.gptq_block   the two HIP ops: a row's 4-bit scale (optionally the reference's shrink search) and the column
                                         sweep of one 128-column GPTQ block in one launch

@@ -1,4 +1,4 @@
-// qqq_factor.hip.h -- the kernels of qqq_upper_factor (qqq_amd/quant/include_ops/qqq_amd_factor.h): U upper triangular with positive
+// qqq_factor.hip.h -- the kernels of qqq_upper_factor (qqq_amd/quant/include/qqq_amd_factor.h): U upper triangular with positive
 // diagonal and U^T U = H^-1, by the direct route  H = R R^T (R upper: a Cholesky factorisation taken from the bottom-right corner
 // upwards),  U = R^-1.  Part of the single translation unit qqq_quant.hip (floating-point contraction off).
 //

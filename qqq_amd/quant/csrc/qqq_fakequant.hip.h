@@ -1,5 +1,5 @@
 // qqq_fakequant.hip.h -- the symmetric fake-quantisation of the rows of a column-scaled fp16 matrix, the inner step of the smoothing
-// search (qqq_amd/quant/include_ops/qqq_amd_fakequant.h states the bits).  Part of the single translation unit qqq_quant.hip
+// search (qqq_amd/quant/include/qqq_amd_fakequant.h states the bits).  Part of the single translation unit qqq_quant.hip
 // (contraction off, correctly rounded divide, subnormals kept).
 //
 //   The matrix is a list of UNITS of 8 consecutive columns: one 16-byte load, one 16-byte store, and one 16-byte load of the eight

@@ -1,5 +1,5 @@
 // qqq_hadamard_k.hip.h -- the Hadamard transform of matrix rows for blocks of n = K * 2^p columns: the Sylvester stages inside every
-// sub-block of m = 2^p entries, then the K x K table that mixes the K sub-blocks (qqq_amd/quant/include_ext/qqq_amd_rotate_k.h states the
+// sub-block of m = 2^p entries, then the K x K table that mixes the K sub-blocks (qqq_amd/quant/include/qqq_amd_rotate_k.h states the
 // bits).  Part of the single translation unit qqq_quant.hip, after qqq_hadamard.hip.h, whose loads, stores, register butterflies, LDS
 // slots, sign flip and divide it uses as they are.
 //

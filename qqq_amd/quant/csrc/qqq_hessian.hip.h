@@ -1,4 +1,4 @@
-// qqq_hessian.hip.h -- the kernel of qqq_hessian_update (qqq_amd/quant/include_ops/qqq_amd_hessian.h): GPTQ's running Hessian
+// qqq_hessian.hip.h -- the kernel of qqq_hessian_update (qqq_amd/quant/include/qqq_amd_hessian.h): GPTQ's running Hessian
 //   H <- f32(f32(alpha H) + f32(beta S)),  S = X^T X,  X fp16 [tokens, n]
 // as a symmetric rank-k update on the fp16 matrix path.  Part of the single translation unit qqq_quant.hip (floating-point contraction
 // off: the epilogue's two products and its sum are three roundings).

@@ -1,10 +1,10 @@
 // qqq_quant.hip -- the one translation unit of libqqq_amd_quant.so: the C-ABI entry points of the GPTQ quantiser
 // (qqq_amd/quant/include/qqq_amd_quant.h) over the kernels of qqq_gptq.hip.h, of its act-order / static-groups ops
 // (qqq_amd/quant/include/qqq_amd_gptq_order.h) over those of qqq_gptq_order.hip.h, and of the rotation ops
-// (qqq_amd/quant/include/qqq_amd_rotate.h, qqq_amd/quant/include_ext/qqq_amd_rotate_k.h) over the kernels of qqq_hadamard.hip.h and qqq_hadamard_k.hip.h,
-// of the smoothing search's fake-quantisation op (qqq_amd/quant/include_ops/qqq_amd_fakequant.h) over those of qqq_fakequant.hip.h,
-// of the Cholesky factor op (qqq_amd/quant/include_ops/qqq_amd_factor.h) over those of qqq_factor.hip.h,
-// and of the Hessian accumulation op (qqq_amd/quant/include_ops/qqq_amd_hessian.h) over the kernel of qqq_hessian.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
+// (qqq_amd/quant/include/qqq_amd_rotate.h, qqq_amd/quant/include/qqq_amd_rotate_k.h) over the kernels of qqq_hadamard.hip.h and qqq_hadamard_k.hip.h,
+// of the smoothing search's fake-quantisation op (qqq_amd/quant/include/qqq_amd_fakequant.h) over those of qqq_fakequant.hip.h,
+// of the Cholesky factor op (qqq_amd/quant/include/qqq_amd_factor.h) over those of qqq_factor.hip.h,
+// and of the Hessian accumulation op (qqq_amd/quant/include/qqq_amd_hessian.h) over the kernel of qqq_hessian.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
 // (qqq_amd/build.py, build_quant): the entry points promise bits.
 #include <hip/hip_runtime.h>
 
@@ -16,10 +16,10 @@
 #include "../include/qqq_amd_gptq_order.h"
 #include "../include/qqq_amd_quant.h"
 #include "../include/qqq_amd_rotate.h"
-#include "../include_ext/qqq_amd_rotate_k.h"
-#include "../include_ops/qqq_amd_factor.h"
-#include "../include_ops/qqq_amd_fakequant.h"
-#include "../include_ops/qqq_amd_hessian.h"
+#include "../include/qqq_amd_rotate_k.h"
+#include "../include/qqq_amd_factor.h"
+#include "../include/qqq_amd_fakequant.h"
+#include "../include/qqq_amd_hessian.h"
 #include "qqq_factor.hip.h"
 #include "qqq_fakequant.hip.h"
 #include "qqq_gptq.hip.h"

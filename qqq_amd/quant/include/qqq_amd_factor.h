@@ -1,5 +1,5 @@
 /*
- * qqq_amd_factor.h -- C-ABI of the Cholesky factor op of the quantiser's library (libqqq_amd_quant.so; in quant/include_ops/ beside
+ * qqq_amd_factor.h -- C-ABI of the Cholesky factor op of the quantiser's library (libqqq_amd_quant.so; beside
  * qqq_amd_fakequant.h.  The prototypes and the ABI version of qqq_amd_quant.h stay as they are).  One device op: what GPTQ's
  * three-step chain  L = cholesky(H); Hi = cholesky_inverse(L); U = cholesky(Hi, upper)  computes, by the direct route.
  *

@@ -1,7 +1,6 @@
 /*
- * qqq_amd_fakequant.h -- C-ABI of the fake-quantisation op of the quantiser's library (libqqq_amd_quant.so; in quant/include_ops/, the
- * third flat header directory of the quantiser: the contents of quant/include/ and quant/include_ext/ are pinned by name, so this and
- * every later quantiser op's header go here.  The prototypes and the ABI version of qqq_amd_quant.h stay as they are).  One device op:
+ * qqq_amd_fakequant.h -- C-ABI of the fake-quantisation op of the quantiser's library (libqqq_amd_quant.so; beside qqq_amd_quant.h, whose
+ * prototypes and ABI version stay as they are).  One device op:
  * what the reference's smoothing search (QQQ/smooth/migration, MigratorBase.quantize) spends about fourteen elementwise and reduction
  * launches on per operand and candidate.  Everything else of smoothing is plain torch in qqq_amd/quant/smooth.py.
  *

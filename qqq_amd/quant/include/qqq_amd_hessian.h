@@ -1,5 +1,5 @@
 /*
- * qqq_amd_hessian.h -- C-ABI of the Hessian accumulation op of the quantiser's library (libqqq_amd_quant.so; in quant/include_ops/ beside
+ * qqq_amd_hessian.h -- C-ABI of the Hessian accumulation op of the quantiser's library (libqqq_amd_quant.so; beside
  * qqq_amd_fakequant.h and qqq_amd_factor.h.  The prototypes and the ABI version of qqq_amd_quant.h stay as they are).  One device op:
  * what GPTQ's add_batch does to its running Hessian per calibration batch, as one symmetric rank-k launch on the fp16 matrix path.
  *

@@ -1,7 +1,6 @@
 /*
- * qqq_amd_rotate_k.h -- C-ABI of the rotation op for hidden sizes K * 2^p of the quantiser's library (libqqq_amd_quant.so; in
- * quant/include_ext/, beside quant/include/ with qqq_amd_quant.h, qqq_amd_gptq_order.h and qqq_amd_rotate.h, whose prototypes and ABI
- * version stay as they are: that directory's contents are pinned by name).  For a size that is
+ * qqq_amd_rotate_k.h -- C-ABI of the rotation op for hidden sizes K * 2^p of the quantiser's library (libqqq_amd_quant.so; beside
+ * qqq_amd_quant.h, qqq_amd_gptq_order.h and qqq_amd_rotate.h, whose prototypes and ABI version stay as they are).  For a size that is
  * no power of two the reference's matmul_hadU multiplies by hadK (x) H_m: a K x K Hadamard matrix that mixes K sub-blocks, each turned
  * by the Sylvester matrix of m = 2^p.  This op does both in one launch; the K x K matrix is an ARGUMENT (the library ships none).
  *

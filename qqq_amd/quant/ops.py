@@ -1,6 +1,5 @@
 """Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h, qqq_amd_gptq_order.h,
-qqq_amd_rotate.h, in qqq_amd/quant/include_ext/ qqq_amd_rotate_k.h and in qqq_amd/quant/include_ops/ qqq_amd_fakequant.h,
-qqq_amd_factor.h and qqq_amd_hessian.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing
+qqq_amd_rotate.h, qqq_amd_rotate_k.h, qqq_amd_fakequant.h, qqq_amd_factor.h and qqq_amd_hessian.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing
 on the host; upper_factor enqueues a chain of launches, and reads one status word where its caller asks for the check."""
 from __future__ import annotations
 

@@ -1,4 +1,4 @@
-"""Reference restatement in numpy of the q / k norm fused into the RoPE / cache-write ops (include_ops/qqq_amd_qknorm.h), written from the
+"""Reference restatement in numpy of the q / k norm fused into the RoPE / cache-write ops (include/qqq_amd_qknorm.h), written from the
 header's text: the norm with its f64 sum in the stated lane order, then the rotation of include/qqq_amd_attn.h, then act_ref.quant_rows
 for the int8 forms.  Rows are head rows: fp16 [rows, d], d in {64, 128}.
 

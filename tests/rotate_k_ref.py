@@ -1,5 +1,5 @@
 """CPU restatement of the rotation op for blocks of n = K * 2^p columns and of the Q stage that uses it, in numpy f64
-(qqq_amd/quant/include_ext/qqq_amd_rotate_k.h, qqq_amd/quant/rotation.py mode="hadamard_k"): the Sylvester stages of every sub-block in the
+(qqq_amd/quant/include/qqq_amd_rotate_k.h, qqq_amd/quant/rotation.py mode="hadamard_k"): the Sylvester stages of every sub-block in the
 stated order, the table's signed adds with k' ascending, one divide, the two-step rounding.  The tests hold the HIP op to it bit for bit,
 and hold it to the fixture recorded from the reference's own rotation (tests/golden/rotate_k_small.npz, gen_rotate_k_golden.py)."""
 import numpy as np

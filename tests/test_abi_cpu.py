@@ -123,13 +123,36 @@ def test_unknown_parameter_type_raises_with_header_function_and_parameter(tmp_pa
         _abi.bind(Lib, str(p))
 
 
-# ---- the two libraries as bound from the headers
+# ---- the three libraries as bound from the headers: every property below is stated once, over every header of both directories
 
-def _headers():
-    return sorted(f for f in os.listdir(os.path.join(ROOT, "include")) if f.endswith(".h"))
+INCLUDE = os.path.join(ROOT, "include")                          # the operator's (libqqq_amd.so) and, in qqq_amd_dev.h, the dev companion's
+QUANT_INCLUDE = os.path.join(ROOT, "qqq_amd", "quant", "include")  # the quantiser's (libqqq_amd_quant.so)
+# the headers this was written over, by name: each must stay listed.  Whatever else is in a directory is listed, bound, watched and checked
+# like them -- no count and no complete list is asserted, so a new op adds its header without touching a test
+TODAY = {
+    "operator": {"qqq_amd.h", "qqq_amd_act.h", "qqq_amd_attn.h", "qqq_amd_beam.h", "qqq_amd_decode.h", "qqq_amd_guided.h", "qqq_amd_kv8.h",
+                 "qqq_amd_logprobs.h", "qqq_amd_lora.h", "qqq_amd_moe.h", "qqq_amd_paged.h", "qqq_amd_penalty.h", "qqq_amd_prefill.h",
+                 "qqq_amd_qknorm.h", "qqq_amd_sample.h", "qqq_amd_score.h", "qqq_amd_shared.h", "qqq_amd_spec.h", "qqq_amd_step.h",
+                 "qqq_amd_stop.h", "qqq_amd_verify.h"},
+    "dev": {"qqq_amd_dev.h"},
+    "quant": {"qqq_amd_factor.h", "qqq_amd_fakequant.h", "qqq_amd_gptq_order.h", "qqq_amd_hessian.h", "qqq_amd_quant.h", "qqq_amd_rotate.h",
+              "qqq_amd_rotate_k.h"},
+}
 
 
-OPERATOR_HEADERS = [h for h in _headers() if h != "qqq_amd_dev.h"]
+def _names(library):
+    """the header names of one library, from a listing of its directory made here (not by qqq_amd/build.py)"""
+    if library == "quant":
+        return sorted(f for f in os.listdir(QUANT_INCLUDE) if f.endswith(".h"))
+    return sorted(f for f in os.listdir(INCLUDE) if f.endswith(".h") and (f == "qqq_amd_dev.h") == (library == "dev"))
+
+
+def _path(library, header):
+    return os.path.join(QUANT_INCLUDE if library == "quant" else INCLUDE, header)
+
+
+def _every(*libraries):
+    return pytest.mark.parametrize("library, header", [pytest.param(lib, h, id=h) for lib in libraries for h in _names(lib)])
 
 
 @pytest.fixture(scope="module")
@@ -141,22 +164,43 @@ def D():
     return _dev.lib()
 
 
+@pytest.fixture(scope="module")
+def libs(L, D):
+    from qqq_amd.quant import _lib as qlib
+
+    return {"operator": L, "dev": D, "quant": qlib.lib()}  # (build.build() has built the quantiser's too)
+
+
+def _walk(inc):
+    """every header under `inc`, subdirectories included: one that a lister -- which lists the directory alone -- would miss fails the comparison"""
+    return sorted(os.path.join(top, f) for top, _, fs in os.walk(inc) for f in fs if f.endswith(".h"))
+
+
 def test_headers_are_found_by_listing_include():
+    """each lister is its directory's listing, and every header of TODAY is in it"""
     from qqq_amd import build
 
-    inc = os.path.join(ROOT, "include")
-    assert len(_headers()) == 20 and len(OPERATOR_HEADERS) == 19 and "qqq_amd.h" in OPERATOR_HEADERS
-    assert build.headers() == [os.path.join(inc, h) for h in _headers()]
-    assert build.operator_headers() == [os.path.join(inc, h) for h in OPERATOR_HEADERS]
+    assert build.INCLUDE == INCLUDE and build.headers() == _walk(INCLUDE)
+    assert build.operator_headers() == [h for h in _walk(INCLUDE) if h != _path("dev", "qqq_amd_dev.h")]
+    for library in ("operator", "dev"):
+        assert TODAY[library] <= set(_names(library)), (library, TODAY[library] - set(_names(library)))
+    assert build.header("qqq_amd.h") == _path("operator", "qqq_amd.h")
+
+
+def test_quant_headers_are_found_by_listing_the_quant_include_directory():
+    from qqq_amd import build
+
+    assert build.QUANT_INCLUDE == QUANT_INCLUDE and build.quant_headers() == _walk(QUANT_INCLUDE)
+    assert TODAY["quant"] <= set(_names("quant")), TODAY["quant"] - set(_names("quant"))
+    assert build.QUANT_HEADER == _path("quant", "qqq_amd_quant.h")
 
 
 def test_the_include_directories_are_flat():
     """headers() and quant_headers() list one directory each: a header in a subdirectory would go unbound and unwatched"""
     from qqq_amd import build
 
-    dirs = (os.path.join(ROOT, "include"), os.path.join(ROOT, "qqq_amd", "quant", "include"))
-    assert dirs == (build.INCLUDE, build.QUANT_INCLUDE)
-    for inc in dirs:
+    assert (INCLUDE, QUANT_INCLUDE) == (build.INCLUDE, build.QUANT_INCLUDE)
+    for inc in (INCLUDE, QUANT_INCLUDE):
         assert [d for d in os.listdir(inc) if os.path.isdir(os.path.join(inc, d))] == [], inc
 
 
@@ -173,12 +217,12 @@ def test_no_function_is_declared_in_two_headers_of_one_library(lister):
     assert seen
 
 
-@pytest.mark.parametrize("header", _headers())
-def test_every_declared_function_is_bound_as_declared(L, D, header):
+@_every("operator", "dev", "quant")
+def test_every_declared_function_is_bound_as_declared(libs, library, header):
     from qqq_amd import _abi
 
-    lib = D if header == "qqq_amd_dev.h" else L
-    protos = _abi.prototypes(os.path.join(ROOT, "include", header))
+    lib = libs[library]
+    protos = _abi.prototypes(_path(library, header))
     assert protos and all(n.startswith("qqq_") for n in protos)
     for name, (ret, params) in protos.items():
         fn = getattr(lib, name)
@@ -215,29 +259,46 @@ def test_tune_struct_and_abi_version_are_the_header_s():
     assert _lib.ABI_VERSION == 4
 
 
-def test_the_compiler_checks_every_definition_against_its_prototype():
-    """the two translation units include every header they define, so a definition that disagrees with its prototype does not compile
-    (extern "C": a second declaration with other parameters is an error)"""
+@_every("operator", "dev", "quant")
+def test_the_compiler_checks_every_definition_against_its_prototype(library, header):
+    """the translation units include every header they define, so a definition that disagrees with its prototype does not compile
+    (extern "C": a second declaration with other parameters is an error) -- and a header that no unit includes cannot sit in a directory"""
     from qqq_amd import build
 
-    unit = open(build.SRC).read()
-    # qqq_amd.h comes in with the unit's first include, the kernels' common header; the feature headers are included by the unit itself
-    assert '#include "qqq_common.hip.h"' in unit
-    unit += open(os.path.join(os.path.dirname(build.SRC), "qqq_common.hip.h")).read()
-    for h in OPERATOR_HEADERS:
-        assert f'#include "../../include/{h}"' in unit, h
-    assert '#include "../../include/qqq_amd_dev.h"' in open(build.DEV_SRC).read()
+    src, rel = {"operator": (build.SRC, "../../include/"), "dev": (build.DEV_SRC, "../../include/"), "quant": (build.QUANT_SRC, "../include/")}[library]
+    unit = open(src).read()
+    if library == "operator":  # qqq_amd.h comes in with the unit's first include, the kernels' common header; the feature headers are included by the unit itself
+        assert '#include "qqq_common.hip.h"' in unit
+        unit += open(os.path.join(os.path.dirname(src), "qqq_common.hip.h")).read()
+    assert f'#include "{rel}{header}"' in unit
 
 
-@pytest.mark.parametrize("header", OPERATOR_HEADERS)
-def test_a_newer_header_rebuilds_the_operator_library(monkeypatch, L, header):
+def _a_newer_header_rebuilds(monkeypatch, library, header):
+    """the library's build step returns early when the library is the newest file and compiles, with the library's flags, when this one
+    header is newer (nothing is compiled here)"""
     from qqq_amd import build
 
-    newer = os.path.join(ROOT, "include", header)
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 1.0)
-    assert not build.needs_build()
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.LIB else 3.0 if p == newer else 1.0)
-    assert build.needs_build()
+    step, src, lib, flags = {"operator": (build.build, build.SRC, build.LIB, ()), "dev": (build.build_dev, build.DEV_SRC, build.DEV_LIB, ()),
+                             "quant": (build.build_quant, build.QUANT_SRC, build.QUANT_LIB, build.QUANT_FLAGS)}[library]
+    newer = _path(library, header)
+    compiled = []
+    monkeypatch.setattr(build, "_compile", lambda src, out, verbose, flags=(): compiled.append((src, out, tuple(flags))) or out)
+    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == lib else 1.0)
+    assert step() == lib and not compiled
+    assert library != "operator" or not build.needs_build()
+    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == lib else 3.0 if p == newer else 1.0)
+    assert library != "operator" or build.needs_build()
+    assert step() == lib and [c for c in compiled if c[1] == lib] == [(src, lib, flags)]  # (qqq_amd.h is the quantiser's too: build() then compiles both)
+
+
+@_every("operator")
+def test_a_newer_header_rebuilds_the_operator_library(monkeypatch, libs, library, header):
+    _a_newer_header_rebuilds(monkeypatch, library, header)
+
+
+@_every("dev", "quant")
+def test_a_newer_header_rebuilds_the_dev_or_quantiser_library(monkeypatch, libs, library, header):
+    _a_newer_header_rebuilds(monkeypatch, library, header)
 
 
 def test_exports_every_declared_symbol(L):

@@ -9,8 +9,8 @@ def test_factor_header_binds_and_sizes_the_workspace():
     from qqq_amd.quant import _lib as qlib
 
     L = qlib.lib()
-    header = os.path.join(build.QUANT_OPS_INCLUDE, "qqq_amd_factor.h")
-    assert header in build.quant_op_headers() and set(_abi.prototypes(header)) == {"qqq_upper_factor_work", "qqq_upper_factor"}
+    header = os.path.join(build.QUANT_INCLUDE, "qqq_amd_factor.h")
+    assert header in build.quant_headers() and set(_abi.prototypes(header)) == {"qqq_upper_factor_work", "qqq_upper_factor"}
     assert len(L.qqq_upper_factor.argtypes) == 9 and L.qqq_quant_abi_version() == 1
     nbytes = ctypes.c_longlong(0)
     for n in (64, 192, 11008, 32768):

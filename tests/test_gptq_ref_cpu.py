@@ -125,33 +125,6 @@ def test_library_loads_and_binds_from_its_header_beside_the_operator():
     assert os.path.basename(build.QUANT_LIB) == "libqqq_amd_quant.so" and build.LIB != build.QUANT_LIB
 
 
-def _quant_headers():
-    inc = os.path.join(ROOT, "qqq_amd", "quant", "include")
-    return sorted(f for f in os.listdir(inc) if f.endswith(".h"))
-
-
-def test_quant_headers_are_found_by_listing_the_quant_include_directory():
-    from qqq_amd import build
-
-    assert _quant_headers() == ["qqq_amd_gptq_order.h", "qqq_amd_quant.h", "qqq_amd_rotate.h"]
-    assert build.quant_headers() == [os.path.join(ROOT, "qqq_amd", "quant", "include", h) for h in _quant_headers()]
-
-
-@pytest.mark.parametrize("header", _quant_headers())
-def test_a_newer_header_rebuilds_the_quantiser_library(monkeypatch, header):
-    """build_quant returns early when the library is the newest file and compiles when this one header is newer (nothing is compiled here)"""
-    from qqq_amd import build
-
-    build.build_quant()  # the library exists
-    newer = os.path.join(ROOT, "qqq_amd", "quant", "include", header)
-    compiled = []
-    monkeypatch.setattr(build, "_compile", lambda src, out, verbose, flags=(): compiled.append((src, out, tuple(flags))) or out)
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.QUANT_LIB else 1.0)
-    assert build.build_quant() == build.QUANT_LIB and not compiled
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.QUANT_LIB else 3.0 if p == newer else 1.0)
-    assert build.build_quant() == build.QUANT_LIB and compiled == [(build.QUANT_SRC, build.QUANT_LIB, build.QUANT_FLAGS)]
-
-
 def _refused(fn, *args):
     from qqq_amd.quant import _lib as qlib
 

