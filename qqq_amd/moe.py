@@ -6,7 +6,8 @@ run on the device in a fixed number of launches, so the block sits inside a capt
                           F.linear(y, gate.weight) -> moe_route -> moe_gemm(a_div = top_k) -> silu_mul_quant -> moe_gemm(a_div = 1) -> moe_combine
 
 State-dict keys under a layer's `mlp.`: gate.weight, experts.gate_up_proj.{B, s_channel, s_group}, experts.down_proj.{B, s_channel, s_group}.
-The quantiser for expert weights, shared experts, LoRA on experts and expert parallelism are not here.
+The weights come from qqq_amd.quant.quantize_model (per-expert Hessians over routed calibration rows) or from QuantLinears packed
+elsewhere, through load_expert.  Shared experts, LoRA on experts and expert parallelism are not here.
 """
 from __future__ import annotations
 

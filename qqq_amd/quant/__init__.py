@@ -29,15 +29,21 @@ whole QQQ W4A8 checkpoints from fp16 ones, rotated first where asked.  A sub-pac
     ops.hessian_update                  the HIP op of the Hessian: H <- alpha H + beta X^T X of fp16 inputs as one symmetric rank-k
                                         launch on the fp16 matrix path (Hessian(accumulate="fused"), quantize_model(hessian="fused"))
 
-Out of scope: token-wise clipping after smoothing, Hadamard tables of other orders (pass one as table=), a head_dim that is no power of two, act-order with moving (non-static) groups, asymmetric modes, other bit
+    ops.hessian_update_grouped          the HIP op of a mixture-of-experts layer's Hessians: every expert's H over the rows routed to it,
+    ExpertHessians,                     one launch over (tile, expert) that gathers through moe_route's offsets / order on the device;
+    gptq_quantize_experts               the per-expert running Hessians over it, and GPTQ of stacked expert weights (an expert without
+                                        calibration rows: round-to-nearest); quantize_model takes qwen3_moe / mixtral configs
+
+Out of scope: rotation and smoothing of mixture-of-experts models, shared experts, token-wise clipping after smoothing, Hadamard tables of other orders (pass one as table=), a head_dim that is no power of two, act-order with moving (non-static) groups, asymmetric modes, other bit
 widths and group sizes."""
 from . import ops
-from .gptq import BlockTrace, GPTQResult, Hessian, gptq_quantize, gptq_quantize_ordered, round_to_nearest
+from .gptq import (BlockTrace, ExpertHessians, GPTQResult, Hessian, gptq_quantize, gptq_quantize_experts, gptq_quantize_ordered,
+                   round_to_nearest)
 from .model import FloatDecoderLayer, quantize_model
 from .ops import gptq_block_cols, group_scales
 from .ops import check_table, hadamard_rows_k
 from .ops import fake_quant_rows
-from .ops import hessian_update
+from .ops import hessian_update, hessian_update_grouped
 from .smooth import apply_smooth, migration_scale, smooth_model, smooth_scales
 from .rotation import (fuse_layer_norms, hadamard_factor, hadamard_matrix, hadamard_matrix_k, hadamard_signs, hadamard_table,
                        random_orthogonal, rotate_model, rotate_state_dict)
@@ -46,4 +52,4 @@ __all__ = ["ops", "Hessian", "gptq_quantize", "gptq_quantize_ordered", "group_sc
            "BlockTrace", "FloatDecoderLayer", "quantize_model",
            "fuse_layer_norms", "hadamard_signs", "hadamard_matrix", "random_orthogonal", "rotate_state_dict", "rotate_model",
            "hadamard_rows_k", "check_table", "hadamard_table", "hadamard_factor", "hadamard_matrix_k",
-           "fake_quant_rows", "hessian_update", "migration_scale", "smooth_scales", "apply_smooth", "smooth_model"]
+           "fake_quant_rows", "hessian_update", "hessian_update_grouped", "ExpertHessians", "gptq_quantize_experts", "migration_scale", "smooth_scales", "apply_smooth", "smooth_model"]

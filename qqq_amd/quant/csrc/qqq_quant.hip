@@ -4,7 +4,8 @@
 // (qqq_amd/quant/include/qqq_amd_rotate.h, qqq_amd/quant/include/qqq_amd_rotate_k.h) over the kernels of qqq_hadamard.hip.h and qqq_hadamard_k.hip.h,
 // of the smoothing search's fake-quantisation op (qqq_amd/quant/include/qqq_amd_fakequant.h) over those of qqq_fakequant.hip.h,
 // of the Cholesky factor op (qqq_amd/quant/include/qqq_amd_factor.h) over those of qqq_factor.hip.h,
-// and of the Hessian accumulation op (qqq_amd/quant/include/qqq_amd_hessian.h) over the kernel of qqq_hessian.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
+// and of the Hessian accumulation ops (qqq_amd/quant/include/qqq_amd_hessian.h, qqq_amd/quant/include/qqq_amd_hessian_grouped.h) over the
+// kernels of qqq_hessian.hip.h and qqq_hessian_grouped.hip.h.  Built for gfx950 with -ffp-contract=off and no fast-math
 // (qqq_amd/build.py, build_quant): the entry points promise bits.
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,7 @@
 #include "../include/qqq_amd_factor.h"
 #include "../include/qqq_amd_fakequant.h"
 #include "../include/qqq_amd_hessian.h"
+#include "../include/qqq_amd_hessian_grouped.h"
 #include "qqq_factor.hip.h"
 #include "qqq_fakequant.hip.h"
 #include "qqq_gptq.hip.h"
@@ -27,6 +29,7 @@
 #include "qqq_hadamard.hip.h"
 #include "qqq_hadamard_k.hip.h"
 #include "qqq_hessian.hip.h"  // (behind qqq_factor.hip.h: it walks the tile triangle with fac_tri)
+#include "qqq_hessian_grouped.hip.h"  // (behind qqq_hessian.hip.h: the tile, the operand read and the LDS layout are the dense kernel's)
 
 static thread_local char g_err[512] = "";
 
@@ -618,5 +621,66 @@ extern "C" int qqq_hessian_update(void* H, int ldh, const void* X, int ldx, int 
   hipLaunchKernelGGL(qqq_hessian_kernel, dim3(static_cast<unsigned>(a.ntiles)), dim3(HES_NT), 0, static_cast<hipStream_t>(stream), a);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail_hip(e, "qqq_hessian_kernel launch");
+  return QQQ_OK;
+}
+
+extern "C" int qqq_hessian_update_grouped(void* H, size_t lde, int ldh, const void* X, int ldx, const void* offsets, const void* order,
+                                          const void* alpha, const void* beta, int P, int R, int E, int n, int a_div, int dev, void* stream) {
+  g_err[0] = 0;
+  if (n < 64 || n > 32768 || n % 64 != 0) {
+    snprintf(g_err, sizeof(g_err), "qqq_hessian_update_grouped: n=%d is not a multiple of 64 in 64 ... 32768", n);
+    return QQQ_ERR_ARG;
+  }
+  if (E < 1 || E > 256) {
+    snprintf(g_err, sizeof(g_err), "qqq_hessian_update_grouped: E=%d is not in 1 ... 256", E);
+    return QQQ_ERR_ARG;
+  }
+  if (P < 0 || P > 2097152 || a_div < 1 || R < 0 || static_cast<long long>(R) * a_div < P) {
+    snprintf(g_err, sizeof(g_err), "qqq_hessian_update_grouped: bad routing shape P=%d R=%d a_div=%d (need 0 <= P <= 2097152, a_div >= 1, R >= ceil(P / a_div))",
+             P, R, a_div);
+    return QQQ_ERR_ARG;
+  }
+  if (ldh < n || ldx < n || ldh % 4 != 0 || ldx % 8 != 0 || lde < static_cast<size_t>(n) * ldh || lde % 4 != 0 || lde > (size_t{1} << 40)) {
+    snprintf(g_err, sizeof(g_err),
+             "qqq_hessian_update_grouped: bad strides lde=%zu ldh=%d ldx=%d (need ldh and ldx >= n=%d, ldh a multiple of 4, ldx of 8, lde >= n * ldh "
+             "and a multiple of 4)",
+             lde, ldh, ldx, n);
+    return QQQ_ERR_ARG;
+  }
+  if (!H || !X || !offsets || !order || !alpha || !beta || misaligned(H, 16) || misaligned(X, 16) || misaligned(offsets, 4) || misaligned(order, 4) ||
+      misaligned(alpha, 4) || misaligned(beta, 4)) {
+    snprintf(g_err, sizeof(g_err),
+             "qqq_hessian_update_grouped: bad argument (every pointer must be non-NULL, H and X 16-byte aligned, offsets, order, alpha and beta 4-byte)");
+    return QQQ_ERR_ARG;
+  }
+  const uintptr_t h0 = reinterpret_cast<uintptr_t>(H), x0 = reinterpret_cast<uintptr_t>(X);
+  const uintptr_t hspan = (static_cast<uintptr_t>(E - 1) * lde + static_cast<uintptr_t>(n - 1) * ldh + n) * 4;
+  const uintptr_t xspan = R > 0 ? (static_cast<uintptr_t>(R - 1) * ldx + n) * 2 : 0;
+  if (h0 < x0 + xspan && x0 < h0 + hspan) {
+    snprintf(g_err, sizeof(g_err), "qqq_hessian_update_grouped: H and X overlap (the two must be disjoint)");
+    return QQQ_ERR_ARG;
+  }
+  if (P == 0) return QQQ_OK;  // no pair, no expert with a row: nothing to do
+  qqq_hessian_grouped_args a;
+  a.H = static_cast<float*>(H);
+  a.X = static_cast<const _Float16*>(X);
+  a.offsets = static_cast<const int*>(offsets);
+  a.order = static_cast<const int*>(order);
+  a.alpha = static_cast<const float*>(alpha);
+  a.beta = static_cast<const float*>(beta);
+  a.lde = static_cast<long long>(lde);
+  a.ldh = ldh;
+  a.ldx = ldx;
+  a.P = P;
+  a.R = R;
+  a.n = n;
+  a.a_div = a_div;
+  const int nb = (n + HES_TILE - 1) / HES_TILE;
+  a.ntiles = nb * (nb + 1) / 2;
+  a.work = E * a.ntiles;  // the launch follows (E, n) alone: a captured call replays with another routing
+  DeviceGuard guard(dev);
+  hipLaunchKernelGGL(qqq_hessian_grouped_kernel, dim3(static_cast<unsigned>(a.work)), dim3(HES_NT), 0, static_cast<hipStream_t>(stream), a);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_hessian_grouped_kernel launch");
   return QQQ_OK;
 }

@@ -8,7 +8,8 @@ factorisation and one triangular inverse in hand-written kernels, about half the
 
 Only what QuantLinear.pack can hold: symmetric 4-bit, per-channel (group_size -1) or groups of 128.  gptq_quantize is the plain flow;
 gptq_quantize_ordered adds the reference's act-order (columns swept by falling diag(H)) and static groups (every group's scale found
-before the sweep), which together still give contiguous groups: an ordinary QQQ checkpoint."""
+before the sweep), which together still give contiguous groups: an ordinary QQQ checkpoint.  ExpertHessians and gptq_quantize_experts are
+the two for the experts of a mixture-of-experts layer: one Hessian per expert over the rows routed to it (ops.hessian_update_grouped)."""
 from __future__ import annotations
 
 import math
@@ -55,6 +56,51 @@ class Hessian:
         self.nsamples += b
         x = math.sqrt(2 / self.nsamples) * x.float()
         self.H += x.t().matmul(x)
+
+
+class ExpertHessians:
+    """The running Hessians of the E experts of one mixture-of-experts linear, each over the rows routed to it: `H` f32
+    [E, columns, columns] and `count` int64 [E] (rows seen so far), both on the device.  A ROW counts as a sample -- GPTQ's result does
+    not depend on the scale of H, its damping being relative -- so that with c rows of a batch for an expert
+        H_e <- H_e count / (count + c) + (2 / (count + c)) X_e^T X_e,   count += c.
+    accumulate="torch": that statement as a loop over the experts of the reference's f32 steps on gathered rows; it reads `offsets` on
+    the host (the baseline and the default).  accumulate="fused": ops.hessian_update_grouped -- the factors made on the device in f64
+    and rounded to f32, one launch for all experts, nothing read on the host; fp16 inputs on the GPU only."""
+
+    def __init__(self, num_experts: int, columns: int, device, accumulate: str = "torch"):
+        if accumulate not in ACCUMULATORS:
+            raise RuntimeError(f"ExpertHessians: accumulate must be one of {ACCUMULATORS}, got {accumulate!r}")
+        self.num_experts, self.columns, self.accumulate = num_experts, columns, accumulate
+        self.H = torch.zeros((num_experts, columns, columns), dtype=torch.float32, device=device)
+        self.count = torch.zeros((num_experts,), dtype=torch.int64, device=device)
+
+    @torch.no_grad()
+    def add_batch(self, x: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor, a_div: int) -> None:
+        """`x` [R, columns]; `offsets` int32 [E + 1], `order` int32 [P] as ops.moe_route returns them; position p of order[] is row
+        order[p] // a_div of x (a_div = top_k for a row per token, 1 for a row per pair)"""
+        if x.dim() != 2 or x.shape[-1] != self.columns:
+            raise RuntimeError(f"ExpertHessians.add_batch: the input is {tuple(x.shape)}, [rows, {self.columns}] expected")
+        if offsets.numel() != self.num_experts + 1:
+            raise RuntimeError(f"ExpertHessians.add_batch: offsets holds {offsets.numel()} entries, {self.num_experts + 1} expected")
+        if self.accumulate == "fused":
+            if x.dtype != torch.float16 or not x.is_cuda:
+                raise RuntimeError(f"ExpertHessians.add_batch: accumulate='fused' takes float16 inputs on the GPU, got {x.dtype} on {x.device} "
+                                   "(there is no fallback)")
+            c = (offsets[1:] - offsets[:-1]).to(torch.int64)
+            den = (self.count + c).clamp_(min=1).double()
+            ops.hessian_update_grouped(self.H, x, offsets, order, (self.count.double() / den).float(), (2 / den).float(), a_div)
+            self.count += c
+            return
+        offs, seen = offsets.tolist(), self.count.tolist()
+        for e in range(self.num_experts):
+            c = offs[e + 1] - offs[e]
+            if c == 0:
+                continue
+            rows = x[order[offs[e]:offs[e + 1]].long() // a_div]
+            self.H[e] *= seen[e] / (seen[e] + c)
+            xf = math.sqrt(2 / (seen[e] + c)) * rows.float()
+            self.H[e] += xf.t().matmul(xf)
+        self.count += (offsets[1:] - offsets[:-1]).to(torch.int64)
 
 
 class BlockTrace(NamedTuple):
@@ -338,6 +384,36 @@ def round_to_nearest(W: torch.Tensor, scales: torch.Tensor, grouped: bool) -> GP
     weight = _quantise(W.float(), s, grouped).to(W.dtype)
     s_extra = _s_extra(weight) if grouped else None
     return GPTQResult(weight, scales, s_extra, 0.0)
+
+
+@torch.no_grad()
+def gptq_quantize_experts(W: torch.Tensor, H: torch.Tensor, count: torch.Tensor, group_size: int = -1, mse: bool = False,
+                          percdamp: float = 0.01, act_order: bool = False, static_groups: bool = False, factor: str = "torch",
+                          fallback: Optional[list] = None) -> List[GPTQResult]:
+    """GPTQ of the E stacked weights `W` [E, N, K] of one expert linear under ExpertHessians' `H` [E, K, K] and `count` [E]: per expert
+    gptq_quantize, or gptq_quantize_ordered where act_order / static_groups are set.  An expert that saw no calibration row
+    (count == 0) is quantised under H = I: round-to-nearest under the same scales, where its all-zero Hessian would have GPTQ's
+    dead-column rule zero the whole expert.  `count` is read once (one sync).  `fallback`: a list that receives those experts' indices."""
+    name = "gptq_quantize_experts"
+    if W.dim() != 3 or H.dim() != 3 or H.shape[0] != W.shape[0] or count.numel() != W.shape[0]:
+        raise RuntimeError(f"{name}: W must be [E, N, K], H [E, K, K] and count [E], got {tuple(W.shape)}, {tuple(H.shape)}, {tuple(count.shape)}")
+    seen = count.tolist()
+    eye = None
+    out = []
+    for e in range(W.shape[0]):
+        He = H[e]
+        if seen[e] == 0:
+            if eye is None:
+                eye = torch.eye(W.shape[2], dtype=torch.float32, device=W.device)
+            He = eye
+            if fallback is not None:
+                fallback.append(e)
+        if act_order or static_groups:
+            out.append(gptq_quantize_ordered(W[e], He, group_size, mse=mse, percdamp=percdamp, act_order=act_order,
+                                             static_groups=static_groups, factor=factor))
+        else:
+            out.append(gptq_quantize(W[e], He, group_size, mse=mse, percdamp=percdamp, factor=factor))
+    return out
 
 
 class _NoSection:

@@ -1,7 +1,8 @@
 """GPTQ over a whole Llama / Qwen2 checkpoint: the reference's layer-wise flow (QQQ/gptq/models/llama.py, gptq_llama_func) over a small fp16
 float decoder layer written here -- transformers is not imported.  The inputs of layer 0 are the embedded calibration tokens; every layer
 accumulates the Hessians of its linears' inputs with its FLOAT weights (all seven in one pass, as the reference), is quantised, and runs
-once more with the quantised weights to feed the next layer."""
+once more with the quantised weights to feed the next layer.  A sparse (mixture-of-experts) layer of Qwen3-MoE or Mixtral keeps one
+Hessian per expert and input, over the rows the router sends there (ExpertHessians), and quantises every expert under its own."""
 from __future__ import annotations
 
 import copy
@@ -12,7 +13,9 @@ import torch.nn.functional as F
 
 from ..attention import _config_rope, rope_inv_freq, rope_tables
 from ..model import QuantLlamaForCausalLM
-from .gptq import Hessian, gptq_quantize, gptq_quantize_ordered
+from .. import ops as _serve_ops
+from ..qlinear import QuantLinear
+from .gptq import ExpertHessians, Hessian, gptq_quantize, gptq_quantize_experts, gptq_quantize_ordered
 from .rotation import rotate_model
 
 ATTN = ("q_proj", "k_proj", "v_proj", "o_proj")
@@ -35,7 +38,10 @@ def _rotate_half(x):
 class FloatDecoderLayer:
     """transformers' Llama / Qwen2 decoder layer in fp16 from plain tensors: RMSNorm, RoPE (rope_tables), causal SDPA, SiLU MLP.
     `weights`: {"self_attn.q_proj.weight": ..., "mlp.down_proj.weight": ..., "input_layernorm.weight": ..., optional "...bias"} on one
-    device.  forward(x [b, s, hidden], taps=None): `taps` maps "qkv" / "o" / "gate_up" / "down" to a callable that sees that input."""
+    device.  forward(x [b, s, hidden], taps=None): `taps` maps "qkv" / "o" / "gate_up" / "down" to a callable that sees that input.
+    With "mlp.gate.weight" among the weights the MLP is the sparse block of Qwen3-MoE / Mixtral over "mlp.experts.E.{gate,up,down}_proj":
+    routed by ops.moe_route as inference routes, the experts a torch loop over gathered rows; its "gate_up" and "down" taps are called
+    with (rows, offsets, order): the flat normed rows [tokens, hidden], then the SiLU-mul rows [tokens * top_k, intermediate] in pair order."""
 
     def __init__(self, config, weights: dict):
         self.w = weights
@@ -46,6 +52,11 @@ class FloatDecoderLayer:
         theta, rope = _config_rope(config)
         self.inv_freq, self.attention_scaling = rope_inv_freq(self.head_dim, theta, rope)
         self._tables = None
+        self.sparse = "mlp.gate.weight" in weights
+        if self.sparse:
+            self.num_experts = weights["mlp.gate.weight"].shape[0]
+            self.top_k = config.num_experts_per_tok
+            self.renorm = getattr(config, "model_type", "") == "mixtral" or bool(getattr(config, "norm_topk_prob", False))
 
     def _linear(self, name, x):
         return F.linear(x, self.w[name + ".weight"], self.w.get(name + ".bias"))
@@ -79,12 +90,51 @@ class FloatDecoderLayer:
             taps["o"](a)
         x = x + self._linear("self_attn.o_proj", a)
         h = _rms_norm(x, self.w["post_attention_layernorm.weight"], self.eps)
+        if self.sparse:
+            return x + self._sparse_mlp(h, taps)
         if "gate_up" in taps:
             taps["gate_up"](h)
         m = F.silu(self._linear("mlp.gate_proj", h)) * self._linear("mlp.up_proj", h)
         if "down" in taps:
             taps["down"](m)
         return x + self._linear("mlp.down_proj", m)
+
+
+    def _sparse_mlp(self, h, taps):
+        k = self.top_k
+        flat = h.reshape(-1, h.shape[-1])
+        _, weights, offsets, order = _serve_ops.moe_route(F.linear(flat, self.w["mlp.gate.weight"]), k, self.renorm)
+        if "gate_up" in taps:
+            taps["gate_up"](flat, offsets, order)
+        offs = offsets.tolist()  # the one host read of the routing
+        pairs = [order[offs[e]:offs[e + 1]].long() for e in range(self.num_experts)]
+        m = torch.empty((order.numel(), self.w["mlp.experts.0.down_proj.weight"].shape[1]), dtype=h.dtype, device=h.device)
+        for e, p in enumerate(pairs):
+            if p.numel():
+                rows = flat[p // k]
+                m[p] = F.silu(self._linear(f"mlp.experts.{e}.gate_proj", rows)) * self._linear(f"mlp.experts.{e}.up_proj", rows)
+        if "down" in taps:
+            taps["down"](m, offsets, order)
+        d = torch.empty((order.numel(), h.shape[-1]), dtype=h.dtype, device=h.device)
+        for e, p in enumerate(pairs):
+            if p.numel():
+                d[p] = self._linear(f"mlp.experts.{e}.down_proj", m[p])
+        return _serve_ops.moe_combine(d, weights, k).reshape(h.shape)
+
+
+_MIXTRAL_KEYS = ((".block_sparse_moe.gate.", ".mlp.gate."), (".w1.", ".gate_proj."), (".w3.", ".up_proj."), (".w2.", ".down_proj."),
+                 (".block_sparse_moe.experts.", ".mlp.experts."))
+
+
+def _qwen3_moe_keys(state_dict):
+    """Mixtral's names of the sparse block mapped onto Qwen3-MoE's, which the packed model and everything below use"""
+    out = {}
+    for key, v in state_dict.items():
+        if ".block_sparse_moe." in key:
+            for old, new in _MIXTRAL_KEYS:
+                key = key.replace(old, new)
+        out[key] = v
+    return out
 
 
 def _run(layer, inps, seq_batch, taps=None):
@@ -112,8 +162,16 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
     `factor`: "torch" or "fused", handed to every linear's gptq_quantize / gptq_quantize_ordered (the factor of the inverse Hessian from
     torch's Cholesky chain, or from ops.upper_factor).
     `hessian`: "torch" or "fused", handed to the four Hessians of every layer as their `accumulate` (the reference's f32 steps, or
-    ops.hessian_update on the fp16 taps)."""
+    ops.hessian_update on the fp16 taps; for a sparse layer's experts, ExpertHessians' per-expert loop or ops.hessian_update_grouped).
+    A `qwen3_moe` or `mixtral` config: Mixtral's state-dict names (block_sparse_moe.gate, experts.E.w1 / w3 / w2) are mapped onto
+    Qwen3-MoE's on entry; every expert linear is quantised under its own Hessian over the rows routed to it (an expert that saw none:
+    round-to-nearest, gptq_quantize_experts) and loaded with load_expert; the router is copied.  `results` also receives, under
+    "model.layers.N.mlp.experts", {"gate_up": count, "down": count, "fallback": [experts]} -- the rows every expert saw.  `rotation` and
+    `smooth` with a sparse model raise NotImplementedError: neither folds into routed experts yet."""
     dev = torch.device(device if device is not None else "cuda:0")
+    state_dict = _qwen3_moe_keys(state_dict)
+    if (rotation is not None or smooth is not None) and any(k.endswith(".mlp.gate.weight") for k in state_dict):
+        raise NotImplementedError("quantize_model: rotation and smooth are not supported for mixture-of-experts models (sparse layers)")
     if rotation is not None:
         if isinstance(rotation, str):
             kw = dict(mode=rotation)
@@ -153,11 +211,39 @@ def quantize_model(state_dict: dict, config, calib_ids: torch.Tensor, group_size
         prefix = f"model.layers.{i}."
         w = {k[len(prefix):]: v.to(dev).half() for k, v in state_dict.items() if k.startswith(prefix)}
         layer = FloatDecoderLayer(config, w)
-        hidden, inter = w["mlp.gate_proj.weight"].shape[1], w["mlp.down_proj.weight"].shape[1]
-        hs = {"qkv": Hessian(hidden, dev, hessian), "o": Hessian(w["self_attn.o_proj.weight"].shape[1], dev, hessian),
-              "gate_up": Hessian(hidden, dev, hessian), "down": Hessian(inter, dev, hessian)}
-        _run(layer, inps, seq_batch, {k: h.add_batch for k, h in hs.items()})
-        for mod_name, names in (("self_attn", ATTN), ("mlp", MLP)):
+        hidden = w["self_attn.q_proj.weight"].shape[1]
+        hs = {"qkv": Hessian(hidden, dev, hessian), "o": Hessian(w["self_attn.o_proj.weight"].shape[1], dev, hessian)}
+        taps = {k: h.add_batch for k, h in hs.items()}
+        if layer.sparse:
+            E, top_k, inter = layer.num_experts, layer.top_k, w["mlp.experts.0.down_proj.weight"].shape[1]
+            xh = {"gate_up": ExpertHessians(E, hidden, dev, hessian), "down": ExpertHessians(E, inter, dev, hessian)}
+            taps["gate_up"] = lambda x, offsets, order: xh["gate_up"].add_batch(x, offsets, order, top_k)
+            taps["down"] = lambda x, offsets, order: xh["down"].add_batch(x, offsets, order, 1)
+        else:
+            hs.update(gate_up=Hessian(hidden, dev, hessian), down=Hessian(w["mlp.down_proj.weight"].shape[1], dev, hessian))
+            taps = {k: h.add_batch for k, h in hs.items()}
+        _run(layer, inps, seq_batch, taps)
+        if layer.sparse:
+            fallback, packed = [], {}
+            for name in MLP:
+                W = torch.stack([w[f"mlp.experts.{e}.{name}.weight"] for e in range(E)])
+                eh = xh[HESSIAN_OF[name]]
+                gs = -1 if group_size == W.shape[2] else group_size  # (one group over all of K is QuantLinear's per-channel format)
+                found = []
+                for e, res in enumerate(gptq_quantize_experts(W, eh.H, eh.count, gs, mse=mse, percdamp=percdamp, act_order=act_order,
+                                                              static_groups=static_groups, factor=factor, fallback=found)):
+                    packed[e, name] = res.pack_into(QuantLinear(4, gs, W.shape[2], W.shape[1], False).to(dev))
+                    w[f"mlp.experts.{e}.{name}.weight"] = res.weight
+                    if results is not None:
+                        results[f"{prefix}mlp.experts.{e}.{name}"] = res
+                fallback = sorted(set(fallback) | set(found))
+            for e in range(E):
+                qlayer.mlp.experts.load_expert(e, *(packed[e, name] for name in MLP))
+            qlayer.mlp.gate.weight.data.copy_(w["mlp.gate.weight"])
+            if results is not None:
+                results[prefix + "mlp.experts"] = {"gate_up": xh["gate_up"].count, "down": xh["down"].count, "fallback": fallback}
+            del xh, packed
+        for mod_name, names in (("self_attn", ATTN), ("mlp", () if layer.sparse else MLP)):
             for name in names:
                 key = f"{mod_name}.{name}"
                 W = w[key + ".weight"]

@@ -1,5 +1,5 @@
 """Operator layer of the GPTQ quantiser over libqqq_amd_quant.so (qqq_amd/quant/include/qqq_amd_quant.h, qqq_amd_gptq_order.h,
-qqq_amd_rotate.h, qqq_amd_rotate_k.h, qqq_amd_fakequant.h, qqq_amd_factor.h and qqq_amd_hessian.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing
+qqq_amd_rotate.h, qqq_amd_rotate_k.h, qqq_amd_fakequant.h, qqq_amd_factor.h, qqq_amd_hessian.h and qqq_amd_hessian_grouped.h state the exact semantics).  Every op enqueues one launch on the current stream of its tensors' device and reads nothing
 on the host; upper_factor enqueues a chain of launches, and reads one status word where its caller asks for the check."""
 from __future__ import annotations
 
@@ -367,5 +367,58 @@ def hessian_update(H: torch.Tensor, x: torch.Tensor, alpha: float, beta: float) 
             x = x.clone()
     err = _lib.lib().qqq_hessian_update(_ptr(H), ldh, _ptr(x), x.stride(0) if x.shape[0] > 1 else n, x.shape[0], n, float(alpha), float(beta),
                                         H.device.index or 0, _stream_for(H))
+    _raise_lib(name, err)
+    return H
+
+
+def _routing_vector(name, what, t, dtype, count=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.dim() != 1 or (count is not None and t.numel() != count) or not t.is_contiguous():
+        got = f"{_dt(t.dtype)} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise RuntimeError(f"{name}: {what} must be contiguous {_dt(dtype)} [{'P' if count is None else count}], got {got}")
+
+
+def hessian_update_grouped(H: torch.Tensor, x: torch.Tensor, offsets: torch.Tensor, order: torch.Tensor, alpha: torch.Tensor,
+                           beta: torch.Tensor, a_div: int) -> torch.Tensor:
+    """hessian_update for all experts of a mixture-of-experts layer in one launch (qqq_amd_hessian_grouped.h): for every expert e with
+    rows, H[e] <- f32(f32(alpha[e] H[e]) + f32(beta[e] x_e^T x_e)) in place, x_e the rows x[order[p] // a_div] of the positions
+    offsets[e] <= p < offsets[e + 1], summed in that order -- bit for bit hessian_update(H[e], x_e, alpha[e], beta[e]).  `H` f32
+    [E, n, n], E <= 256, n a multiple of 64 in 64 ... 32768; a view with its own expert and row strides (multiples of 4, 16-byte
+    aligned) is fine.  `x` fp16 [R, n] on H's GPU, R * a_div >= P; a view with its own row stride (a multiple of 8, 16-byte aligned) is
+    read in place, any other layout is made contiguous once; never written.  `offsets` int32 [E + 1] and `order` int32 [P] as
+    ops.moe_route returns them; `alpha`, `beta` f32 [E] ON THE DEVICE; `a_div` top_k where x holds a row per token, 1 where it holds a
+    row per pair.  Nothing is read on the host; an expert without rows keeps its matrix untouched; alpha[e] == 0 does not read H[e].
+    Returns H."""
+    name = "hessian_update_grouped"
+    if not isinstance(H, torch.Tensor) or H.dim() != 3 or H.dtype != torch.float32:
+        got = f"{_dt(H.dtype)} {tuple(H.shape)}" if isinstance(H, torch.Tensor) else type(H).__name__
+        raise RuntimeError(f"{name}: H must be a float32 [E, n, n] tensor, got {got}")
+    E, n = H.shape[0], H.shape[1]
+    if E < 1 or E > 256:
+        raise RuntimeError(f"{name}: H holds E = {E} matrices, 1 ... 256 expected")
+    ldh = _factor_matrix(name, "H[e]", H[0])
+    lde = H.stride(0) if E > 1 else n * ldh
+    if lde < n * ldh or lde % 4:
+        raise RuntimeError(f"{name}: H must have an expert stride >= n * its row stride that is a multiple of 4, got strides {tuple(H.stride())}")
+    if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.dtype != torch.float16:
+        got = f"{_dt(x.dtype)} {tuple(x.shape)}" if isinstance(x, torch.Tensor) else type(x).__name__
+        raise RuntimeError(f"{name}: x must be a float16 matrix, got {got}")
+    _routing_vector(name, "offsets", offsets, torch.int32, E + 1)
+    _routing_vector(name, "order", order, torch.int32)
+    _routing_vector(name, "alpha", alpha, torch.float32, E)
+    _routing_vector(name, "beta", beta, torch.float32, E)
+    P, R = order.numel(), x.shape[0]
+    if not isinstance(a_div, int) or a_div < 1:
+        raise RuntimeError(f"{name}: a_div must be an integer >= 1, got {a_div!r}")
+    if x.shape[1] != n or R * a_div < P:
+        raise RuntimeError(f"{name}: x has the shape {tuple(x.shape)}, (at least ceil({P} / {a_div}) rows, {n}) expected")
+    _same_gpu(name, (H, x, offsets, order, alpha, beta))
+    if P == 0:  # no pair: no expert has a row
+        return H
+    if x.stride(1) != 1 or x.stride(0) < n or x.stride(0) % 8 or x.stride(0) >= 2**31 or x.data_ptr() % 16:
+        x = x.contiguous()
+        if x.data_ptr() % 16:  # (a contiguous tensor that starts off a 16-byte boundary is returned as it is)
+            x = x.clone()
+    err = _lib.lib().qqq_hessian_update_grouped(_ptr(H), lde, ldh, _ptr(x), x.stride(0) if R > 1 else n, _ptr(offsets), _ptr(order),
+                                                _ptr(alpha), _ptr(beta), P, R, E, n, a_div, H.device.index or 0, _stream_for(H))
     _raise_lib(name, err)
     return H

@@ -4,7 +4,7 @@ torch calls (fused=False: a handful of launches per weight column, what the refe
 shapes, per-channel and g128.  Wall time per call with a synchronise on both sides, and the split of the GPU time into the scale search,
 the sweep, the trailing GEMM and the Cholesky chain from events around those sections.
 
-    python tools/bench_gptq.py [--rounds 5] [--out profiles/gptq_bench.json] [--small] [--act-order] [--factor torch,fused] [--hessian torch,fused]
+    python tools/bench_gptq.py [--rounds 5] [--out profiles/gptq_bench.json] [--small] [--act-order] [--factor torch,fused] [--hessian torch,fused [--experts]]
 
 --act-order times gptq_quantize_ordered (act-order, and static groups when grouped) instead: fused (ops.gptq_block_cols) against its own
 fused=False, and against plain gptq_quantize fused, with the split also showing the one-launch group scales and the permutation gathers;
@@ -16,6 +16,11 @@ profiles/gptq_factor_bench.json.
 alternating in one process -- at K = 4096 and 11008 with 2048 and 8 x 2048 fp16 tokens per call, 16 calls per Hessian, GPU time between
 events; and quantize_model over ONE Llama-2-7B-shaped layer (the reference's 128 calibration sequences of 2048 tokens) under both, with the share of its
 time the four Hessians take.  The default --out is then profiles/hessian_bench.json.
+--hessian torch,fused --experts times ExpertHessians.add_batch under each accumulator instead -- the per-expert loop of f32 steps, which
+reads the routing on the host, and ops.hessian_update_grouped -- and, third, E calls of ops.hessian_update on rows gathered BEFORE the
+clock starts (what the gather and the one launch buy over the dense op), alternating in one process: Qwen3-30B-A3B's layer (128 experts,
+top-8; n = 2048 with a row per token, n = 768 with a row per pair) and Mixtral's (8 experts, top-2, n = 4096) at 2048 and 16384 tokens
+per call under random router logits, 4 calls per timing, GPU time between events.  The default --out is then profiles/moe_hessian_bench.json.
 
 Writes the JSON and prints one line per point.  Nothing asserts a time.
 """
@@ -70,11 +75,14 @@ def main():
     ap.add_argument("--act-order", action="store_true", help="time gptq_quantize_ordered (act-order + static groups) instead")
     ap.add_argument("--factor", default=None, help="torch,fused: time gptq_quantize under both factors of the inverse Hessian instead")
     ap.add_argument("--hessian", default=None, help="torch,fused: time Hessian.add_batch under both accumulators, and its share of a layer, instead")
+    ap.add_argument("--experts", action="store_true", help="with --hessian: time ExpertHessians.add_batch (mixture-of-experts layers) instead")
     args = ap.parse_args()
     if args.hessian is not None:
         if sorted(args.hessian.split(",")) != ["fused", "torch"] or args.act_order or args.factor:
             sys.exit("bench_gptq.py: --hessian takes torch,fused (both, so that they share a run), without --act-order / --factor")
-        return hessian_main(args)
+        return experts_main(args) if args.experts else hessian_main(args)
+    if args.experts:
+        sys.exit("bench_gptq.py: --experts goes with --hessian torch,fused")
     factors = args.factor.split(",") if args.factor else []
     if factors and (args.act_order or sorted(factors) != ["fused", "torch"]):
         sys.exit("bench_gptq.py: --factor takes torch,fused (both, so that they share a run), without --act-order")
@@ -278,6 +286,72 @@ def hessian_main(args):
     os.makedirs(os.path.dirname(out), exist_ok=True)
     with open(out, "w") as f:
         json.dump({"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "points": points, "layer": layer}, f, indent=1)
+        f.write("\n")
+
+
+def experts_main(args):
+    import torch
+
+    if not torch.cuda.is_available():
+        sys.exit("bench_gptq.py needs a GPU")
+    from qqq_amd import ops as serve_ops
+    from qqq_amd.quant import ExpertHessians, ops
+
+    out = args.out or os.path.join(ROOT, "profiles", "moe_hessian_bench.json")
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(0)
+    kinds, calls, points = ("torch", "fused", "dense_calls"), 4, []
+    shapes = [("small", 8, 2, 256, 2, 512)] if args.small else [
+        (name, E, k, n, a_div, tokens) for name, E, k, n, a_div in (("Qwen3-30B-A3B gate|up", 128, 8, 2048, 8), ("Qwen3-30B-A3B down", 128, 8, 768, 1),
+                                                                   ("Mixtral gate|up", 8, 2, 4096, 2)) for tokens in (2048, 16384)]
+    for name, E, k, n, a_div, tokens in shapes:
+        logits = torch.randn((tokens, E), generator=g, device=dev).half()
+        _, _, offsets, order = serve_ops.moe_route(logits, k, True)
+        x = (torch.randn((tokens * k // a_div, n), generator=g, device=dev) * (0.2 + 2 * torch.rand(n, generator=g, device=dev))).half()
+        offs = offsets.tolist()
+        rows = [x[order[offs[e]:offs[e + 1]].long() // a_div].contiguous() for e in range(E)]  # the dense calls' inputs: gathered off the clock
+        ms, hs = {kind: [] for kind in kinds}, {}
+        for rnd in range(args.rounds + 1):  # (round 0 warms up)
+            for kind in kinds:  # alternating: all see the same minutes of the machine
+                h = ExpertHessians(E, n, dev, "torch" if kind == "torch" else "fused")
+                seen = [0] * E
+                torch.cuda.synchronize()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                for _ in range(calls):
+                    if kind != "dense_calls":
+                        h.add_batch(x, offsets, order, a_div)
+                        continue
+                    for e, r in enumerate(rows):
+                        if r.shape[0]:
+                            ops.hessian_update(h.H[e], r, seen[e] / (seen[e] + r.shape[0]), 2 / (seen[e] + r.shape[0]))
+                            seen[e] += r.shape[0]
+                b.record()
+                torch.cuda.synchronize()
+                if rnd:
+                    ms[kind].append(a.elapsed_time(b))
+                hs[kind] = h.H
+                del h
+        counts = [offs[e + 1] - offs[e] for e in range(E)]
+        point = {"shape": name, "E": E, "top_k": k, "n": n, "a_div": a_div, "tokens_per_call": tokens, "calls": calls,
+                 "rows_per_expert_min_max": [min(counts), max(counts)]}
+        for kind in kinds:
+            point[kind + "_ms"] = [round(t, 3) for t in ms[kind]]
+            point[kind + "_ms_median"] = round(_median(ms[kind]), 3)
+        spread = max(max(ms[kind]) - min(ms[kind]) for kind in kinds)
+        point["spread_ms"] = round(spread, 3)
+        point["speedup"] = round(point["torch_ms_median"] / point["fused_ms_median"], 2)
+        point["fused_wins_by_more_than_the_spread"] = bool(min(ms["torch"]) - max(ms["fused"]) > spread)
+        point["over_dense_calls"] = round(point["fused_ms_median"] / point["dense_calls_ms_median"], 3)
+        point["fused_beats_dense_calls_by_more_than_the_spread"] = bool(min(ms["dense_calls"]) - max(ms["fused"]) > spread)
+        point["same_bits_as_dense_calls"] = bool(torch.equal(hs["fused"], hs["dense_calls"]))
+        point["relative_difference"] = float((hs["fused"].double() - hs["torch"].double()).norm() / hs["torch"].double().norm())
+        print(json.dumps(point))
+        points.append(point)
+        del x, rows, hs
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump({"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "points": points}, f, indent=1)
         f.write("\n")
 
 

@@ -7,7 +7,8 @@ reference's examples/quant_model.py; --rotation is its rotation stage, --smooth 
                                    [--rotation {none,hadamard,hadamard_k,random}] [--rotation-seed 0] [--act-order] [--static-groups]
                                    [--smooth {os+,awq,sq}] [--save-scales PATH]
 
---config   a transformers config.json of a Llama or Qwen2 model (read as plain JSON; transformers is not needed)
+--config   a transformers config.json of a Llama, Qwen2, Qwen3, Qwen3-MoE or Mixtral model (read as plain JSON; transformers is not
+           needed); with a mixture-of-experts model every expert is quantised under its own Hessian, and --rotation / --smooth are refused
 --weights  the fp16 state dict with Hugging Face parameter names: a torch.save file, or .safetensors where the safetensors package can
            be imported
 --tokens   a .npy of calibration token ids of any integer dtype and shape, read in order and cut into windows of --seqlen (there is no
@@ -112,7 +113,7 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     torch.save({k: v.cpu() for k, v in lm.state_dict().items()}, os.path.join(args.out, "model.pt"))
     quant_config = {"group_size": args.group_size, "wbits": 4}
-    summary = {"group_size": args.group_size, "nsamples": nsamples, "seqlen": args.seqlen, "linears": len(results) - (rotation is not None) - (args.smooth is not None),
+    summary = {"group_size": args.group_size, "nsamples": nsamples, "seqlen": args.seqlen, "linears": sum(hasattr(v, "codes") for v in results.values()),  # (the GPTQResults: not the rotation, the scale list, an expert block's counts)
                "seconds": round(dt, 2)}
     if args.act_order or args.static_groups:
         quant_config.update(act_order=args.act_order, static_groups=args.static_groups)
