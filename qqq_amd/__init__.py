@@ -106,6 +106,11 @@ from .ops import (  # noqa: F401
     decode_attention_paged_shared,
     decode_attention_paged_shared_kv8,
     decode_attention_shared_plan,
+    decode_attention_paged_window,
+    decode_attention_paged_window_kv8,
+    decode_attention_window_plan,
+    prefill_attention_paged_window,
+    prefill_attention_paged_window_kv8,
 )
 from .qlinear import QuantLinear, fuse_quant_linears  # noqa: F401
 from .blocks import QuantLlamaMLP, QuantRMSNorm  # noqa: F401
@@ -131,4 +136,6 @@ __all__ = ["qqq_gemm", "qqq_gemm_bias", "qqq_gemm_ex", "qqq_gemm_w8", "expand_in
            "topk_logprobs", "topk_logprobs_step", "TokenLogprobs", "ban_tokens", "stop_check",
            "beam_step", "copy_blocks", "BeamHypothesis", "fsm_mask", "fsm_advance", "TokenFSM", "GuidedDecodeLoop",
            "lora_add", "LoraBank", "LoraStep", "rope_qkv_norm", "rope_qkv_norm_kv8", "rope_qkv_norm_paged", "rope_qkv_norm_paged_kv8",
-           "moe_route", "moe_gemm", "moe_combine", "QuantMoeExperts", "QuantSparseMoeBlock"]
+           "moe_route", "moe_gemm", "moe_combine", "QuantMoeExperts", "QuantSparseMoeBlock",
+           "decode_attention_paged_window", "decode_attention_paged_window_kv8", "decode_attention_window_plan",
+           "prefill_attention_paged_window", "prefill_attention_paged_window_kv8"]

@@ -148,13 +148,23 @@ class QuantLlamaAttention(nn.Module):
     Llama: qkv_bias = o_bias = config.attention_bias;  Qwen2: qkv_bias=True, o_bias=False.
     Qwen3: qk_norm=True -- the module owns q_norm.weight and k_norm.weight (fp16 [head_dim], transformers' names), a per-head RMSNorm with
     eps = rms_norm_eps between the q / k projections and RoPE, and every RoPE / cache-write launch is its rope_qkv_norm* counterpart
-    (the norm runs inside that launch).  Without qk_norm nothing of this is registered, allocated or run."""
+    (the norm runs inside that launch).  Without qk_norm nothing of this is registered, allocated or run.
+
+    sliding_window=W (Mistral, Mixtral, the window layers of Qwen2 / Qwen3): a query at position i attends keys i - W < j <= i.  Such a
+    layer runs over a PagedKVCache only: one-token steps take decode_attention_paged_window(_kv8), every other step
+    prefill_attention_paged_window(_kv8), whatever fuse_decode() / fuse_prefill() say -- there is no torch path -- and the RoPE / cache
+    write, o_proj and LoRA are the unwindowed layer's.  Over a KVCache, and for fuse_verify() / fuse_shared(), it raises
+    NotImplementedError: those kernels have no windowed twin."""
 
     def __init__(self, hidden: int, num_heads: int, num_kv_heads: int, group_size: int, head_dim: Optional[int] = None,
                  qkv_bias: bool = False, o_bias: bool = False, rope_theta: float = 10000.0, rope_scaling: Optional[dict] = None,
-                 layer_idx: int = 0, qk_norm: bool = False, rms_norm_eps: float = 1e-6):
+                 layer_idx: int = 0, qk_norm: bool = False, rms_norm_eps: float = 1e-6, sliding_window: Optional[int] = None):
         super().__init__()
         head_dim = head_dim or hidden // num_heads
+        if sliding_window is not None and int(sliding_window) < 1:
+            raise ValueError(f"sliding_window {sliding_window} must be at least 1 (None: full attention)")
+        # a query at position i attends the keys i - sliding_window < j <= i (transformers' sliding_window_overlay); None: keys 0 ... i
+        self.sliding_window = None if sliding_window is None else int(sliding_window)
         if qk_norm and head_dim not in (64, 128):
             raise ValueError(f"qk_norm needs head_dim 64 or 128, not {head_dim}")
         if num_heads % num_kv_heads:
@@ -249,6 +259,7 @@ class QuantLlamaAttention(nn.Module):
         chunk's queries in the padding of its operands, every token's row bit for bit the decode step's for that token.  Every other step
         goes where it goes without the flag (decode steps to the decode kernel, ragged or wider chunks to fuse_prefill()'s path or
         SDPA).  state_dict(): unchanged.  Returns self."""
+        self._no_window("fuse_verify()")
         self._verify = True
         return self
 
@@ -267,6 +278,7 @@ class QuantLlamaAttention(nn.Module):
         splits inside a family's shared keys are read once per pack of rows, every row bit for bit the plain decode step's.  Every other
         step goes where it goes without the flag; without it a step with families runs the plain paged decode op over the aliased
         tables.  state_dict(): unchanged.  Returns self."""
+        self._no_window("fuse_shared()")
         self._shared = True
         return self
 
@@ -278,6 +290,10 @@ class QuantLlamaAttention(nn.Module):
     @property
     def shared_fused(self) -> bool:
         return self._shared
+
+    def _no_window(self, what: str) -> None:
+        if self.sliding_window is not None:
+            raise NotImplementedError(f"{what}: no windowed kernel for a sliding-window layer (sliding_window={self.sliding_window})")
 
     def _verify_tokens(self, step: PagedStep) -> int:
         """T if fuse_verify() is set and `step` is a chunk the verify kernel takes (from the step's host lists alone), else 0."""
@@ -355,6 +371,11 @@ class QuantLlamaAttention(nn.Module):
                 q, k, v, self.q_norm.weight, self.k_norm.weight, self.q_norm.eps, cos, sin, step.pos, step.slots, *pools)
         else:
             q_out = (ops.rope_qkv_paged_kv8 if cache.quantized else ops.rope_qkv_paged)(q, k, v, cos, sin, step.pos, step.slots, *pools)
+        if self.sliding_window is not None:  # a window layer: the windowed decode / prefill kernels, whatever the fuse_*() flags say
+            table = (step.block_table, step.last_pos) if step.decode else (step.block_table, step.cu_tokens, step.start_pos)
+            name = ("decode" if step.decode else "prefill") + "_attention_paged_window" + ("_kv8" if cache.quantized else "")
+            aq, a1 = getattr(ops, name)(q_out, *pools, *table, self.scaling, self.sliding_window, max_len=step.max_len)
+            return forward_int8_lora(self.o_proj, aq, a1, o_lora)
         if step.decode and self._shared and step.family is not None:  # fuse_shared(): siblings read their common keys once per pack
             shared = ops.decode_attention_paged_shared_kv8 if cache.quantized else ops.decode_attention_paged_shared
             pack = min(int(step.family_max), 64 // (self.num_heads // self.num_key_value_heads))
@@ -385,6 +406,7 @@ class QuantLlamaAttention(nn.Module):
     def forward_int8(self, xq: torch.Tensor, s1: torch.Tensor, cache: KVCache, start: int) -> torch.Tensor:
         if isinstance(cache, PagedKVCache):  # `start` is the PagedStep of this forward pass
             return self._forward_paged(xq, s1, cache, start)
+        self._no_window("a static KVCache (use a PagedKVCache)")
         m = xq.shape[0]
         b = cache.batch
         if xq.dim() != 2 or m % b:
@@ -433,6 +455,26 @@ def _config_rope(config):
     return float(getattr(config, "rope_theta", 10000.0)), getattr(config, "rope_scaling", None)
 
 
+def _config_window(config, layer_idx: int) -> Optional[int]:
+    """The sliding window of layer `layer_idx` of a transformers config, or None for full attention: Mistral / Mixtral window every layer
+    (config.sliding_window, null: none); Qwen2 / Qwen3 / Qwen3-MoE the layers whose `layer_types` entry is "sliding_attention", derived as
+    their config classes derive it where the config carries none (use_sliding_window and layer_idx >= max_window_layers)."""
+    kind, window = getattr(config, "model_type", ""), getattr(config, "sliding_window", None)
+    if window is None:
+        return None
+    if kind in ("mistral", "mixtral"):
+        return int(window)
+    if kind not in ("qwen2", "qwen3", "qwen3_moe"):
+        return None
+    types = getattr(config, "layer_types", None)
+    if types:
+        if types[layer_idx] not in ("full_attention", "sliding_attention"):
+            raise NotImplementedError(f"layer_types[{layer_idx}] = {types[layer_idx]!r}: only full_attention and sliding_attention are supported")
+        return int(window) if types[layer_idx] == "sliding_attention" else None
+    sliding = getattr(config, "use_sliding_window", False) and layer_idx >= getattr(config, "max_window_layers", 0)
+    return int(window) if sliding else None
+
+
 class QuantLlamaDecoderLayer(nn.Module):
     """Quantized{Llama,Qwen2}DecoderLayer: transformers' layer output
         h = hidden + self_attn(input_layernorm(hidden));  out = h + mlp(post_attention_layernorm(h))
@@ -442,14 +484,16 @@ class QuantLlamaDecoderLayer(nn.Module):
 
     def __init__(self, hidden: int, num_heads: int, num_kv_heads: int, intermediate: int, group_size: int, head_dim: Optional[int] = None,
                  qkv_bias: bool = False, o_bias: bool = False, rms_norm_eps: float = 1e-6, rope_theta: float = 10000.0,
-                 rope_scaling: Optional[dict] = None, layer_idx: int = 0, qk_norm: bool = False, moe: Optional[dict] = None):
-        """`moe` (None: the dense MLP): dict(num_experts, top_k, moe_intermediate, norm_topk_prob) -- the layer's MLP is then a
+                 rope_scaling: Optional[dict] = None, layer_idx: int = 0, qk_norm: bool = False, moe: Optional[dict] = None,
+                 sliding_window: Optional[int] = None):
+        """`sliding_window` (None: full attention): QuantLlamaAttention's.
+        `moe` (None: the dense MLP): dict(num_experts, top_k, moe_intermediate, norm_topk_prob) -- the layer's MLP is then a
         QuantSparseMoeBlock (qqq_amd/moe.py), routed on the fp16 output of post_attention_layernorm; `intermediate` is not used."""
         super().__init__()
         self.hidden_size = hidden
         self.self_attn = QuantLlamaAttention(hidden, num_heads, num_kv_heads, group_size, head_dim=head_dim, qkv_bias=qkv_bias,
                                              o_bias=o_bias, rope_theta=rope_theta, rope_scaling=rope_scaling, layer_idx=layer_idx,
-                                             qk_norm=qk_norm, rms_norm_eps=rms_norm_eps)
+                                             qk_norm=qk_norm, rms_norm_eps=rms_norm_eps, sliding_window=sliding_window)
         if moe is None:
             self.mlp = QuantLlamaMLP(hidden, intermediate, group_size)
         else:
@@ -461,7 +505,7 @@ class QuantLlamaDecoderLayer(nn.Module):
         self.post_attention_layernorm = QuantRMSNorm(hidden, eps=rms_norm_eps)
 
     @classmethod
-    def from_config(cls, config, group_size: int, layer_idx: int = 0):
+    def from_config(cls, config, group_size: int, layer_idx: int = 0, sliding_window: bool = False):
         """The layer of a transformers LlamaConfig, Qwen2Config or Qwen3Config (duck-typed, 4.x or 5.x attribute style).  Qwen2: q/k/v
         with bias, o without; Llama and Qwen3: all four follow `attention_bias`; Qwen3: q_norm / k_norm (qk_norm=True), head_dim from the
         config.  Sliding-window Qwen2 / Qwen3 (`use_sliding_window`, or a `layer_types` entry other than "full_attention") and rope types
@@ -469,7 +513,13 @@ class QuantLlamaDecoderLayer(nn.Module):
         Qwen3MoeConfig (`qwen3_moe`): Qwen3's attention; layer i is sparse -- num_experts, num_experts_per_tok, moe_intermediate_size,
         norm_topk_prob -- unless it is in `mlp_only_layers` or (i + 1) % decoder_sparse_step != 0, and then takes the dense MLP of
         intermediate_size.  MixtralConfig (`mixtral`): Llama's attention, every layer sparse with num_local_experts experts of
-        intermediate_size, always renormalised; a non-null `sliding_window` raises NotImplementedError."""
+        intermediate_size, always renormalised; a non-null `sliding_window` raises NotImplementedError.
+
+        sliding_window=True opts in to the windowed kernels, and none of the sliding-window refusals above is then raised: `mistral` and
+        `mixtral` take config.sliding_window on every layer (null: none); Qwen2 / Qwen3 / `qwen3_moe` take it on the layers that
+        transformers' own derivation of `layer_types` marks "sliding_attention" (an explicit `layer_types`, else use_sliding_window and
+        layer_idx >= max_window_layers).  Without the keyword every config behaves as before -- a `mistral` config builds as Llama
+        and its window is IGNORED."""
         if getattr(config, "hidden_act", "silu") != "silu":
             raise NotImplementedError(f"hidden_act {config.hidden_act!r}: only SiLU MLPs are supported")
         qwen2 = getattr(config, "model_type", "") == "qwen2"
@@ -481,14 +531,16 @@ class QuantLlamaDecoderLayer(nn.Module):
                 moe = dict(num_experts=config.num_experts, top_k=config.num_experts_per_tok, moe_intermediate=config.moe_intermediate_size,
                            norm_topk_prob=bool(getattr(config, "norm_topk_prob", False)))
         elif getattr(config, "model_type", "") == "mixtral":
-            if getattr(config, "sliding_window", None) is not None:
-                raise NotImplementedError("sliding-window attention is not supported")
+            if getattr(config, "sliding_window", None) is not None and not sliding_window:
+                raise NotImplementedError("sliding-window attention is not supported without from_config(..., sliding_window=True)")
             moe = dict(num_experts=config.num_local_experts, top_k=config.num_experts_per_tok, moe_intermediate=config.intermediate_size,
                        norm_topk_prob=True)
-        if (qwen2 or qwen3) and getattr(config, "use_sliding_window", False):
-            raise NotImplementedError("sliding-window attention is not supported")
-        if qwen3 and any(t != "full_attention" for t in (getattr(config, "layer_types", None) or ())):
-            raise NotImplementedError("layer_types other than 'full_attention' (sliding-window layers) are not supported")
+        if (qwen2 or qwen3) and getattr(config, "use_sliding_window", False) and not sliding_window:
+            raise NotImplementedError("sliding-window attention is not supported without from_config(..., sliding_window=True)")
+        if qwen3 and any(t != "full_attention" for t in (getattr(config, "layer_types", None) or ())) and not sliding_window:
+            raise NotImplementedError("layer_types other than 'full_attention' (sliding-window layers) are not supported without "
+                                      "from_config(..., sliding_window=True)")
+        window = _config_window(config, layer_idx) if sliding_window else None
         theta, rope = _config_rope(config)
         heads = config.num_attention_heads
         kv = getattr(config, "num_key_value_heads", None) or heads
@@ -496,7 +548,7 @@ class QuantLlamaDecoderLayer(nn.Module):
         return cls(config.hidden_size, heads, kv, config.intermediate_size, group_size,
                    head_dim=getattr(config, "head_dim", None) or config.hidden_size // heads,
                    qkv_bias=True if qwen2 else bias, o_bias=False if qwen2 else bias, rms_norm_eps=config.rms_norm_eps,
-                   rope_theta=theta, rope_scaling=rope, layer_idx=layer_idx, qk_norm=qwen3, moe=moe)
+                   rope_theta=theta, rope_scaling=rope, layer_idx=layer_idx, qk_norm=qwen3, moe=moe, sliding_window=window)
 
     def fuse_decode(self):
         """self_attn.fuse_decode(): one-token steps take the split-K decode attention kernel.  Returns self."""

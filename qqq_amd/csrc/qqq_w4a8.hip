@@ -44,6 +44,7 @@
 //   qqq_guided.hip.h   guided decoding over a token automaton in device memory: the mask in front of a sampler, the advance behind a loop's step
 //   qqq_lora.hip.h     the batched LoRA op: fp16 low-rank adapters added to a GEMM's output, every token's adapter read from device memory
 //   qqq_moe.hip.h      mixture-of-experts layers: the router's top-k and stable sort by expert, the grouped GEMM over routed rows, the combine
+//   qqq_window.hip.h   sliding-window attention: the paged split-K decode and prefill kernels with every row's splits / tiles placed at its window
 //   each family's header ends with its launch table: the list of instantiations next to the template it instantiates
 //   qqq_plan.h         the dispatch planner (make_plan, the cost models, the M split): pure host C++, no HIP; its rates are GENERATED into
 //   qqq_rates.h        by tools/fit_rates.py and held against the committed measurements by tools/cost_model_report.py
@@ -108,6 +109,9 @@
 #include "../../include/qqq_amd_lora.h"
 #include "qqq_moe.hip.h"
 #include "../../include/qqq_amd_moe.h"
+#include "../../include/qqq_amd_window.h"
+#include "qqq_window.hip.h"
+
 #include "qqq_plan.h"
 
 // ------------------------------------------------------------------------------------------
@@ -974,16 +978,84 @@ extern "C" int qqq_rope_qkv_norm_paged_kv8(const void* q, int ld_q, const void* 
                        pos, slots, q_out, k_pool, v_pool, k_scale, v_scale, m, 1, h, kvh, d, 0, num_blocks, block_size, dev, stream);
 }
 
+// ---- sliding-window attention (include/qqq_amd_window.h; kernels in qqq_window.hip.h).  The windowed entries run the bodies of their
+// unwindowed twins -- one copy of the argument checks -- with `window` set; WINDOW_NONE is the unwindowed call.
+static constexpr int WINDOW_NONE = 0;
+
+static int window_error(const char* name) {
+  snprintf(g_err, sizeof(g_err), "%s: window must be at least 1", name);
+  return QQQ_ERR_ARG;
+}
+
+// the keys a windowed decode call plans its splits over: a row's splits start at lo rounded down to DEC_ROUND, so they span at most
+// window - 1 + DEC_ROUND keys, and never more than max_len
+static int window_span(int max_len, int window) {
+  const long long need = ((long long)window + 2 * DEC_ROUND - 2) / DEC_ROUND * DEC_ROUND;
+  return need < max_len ? (int)need : max_len;
+}
+
+extern "C" size_t qqq_decode_attn_window_workspace_bytes(int b, int h, int kvh, int d, int max_len, int window) {
+  if (window < 1 || max_len < 1) return 0;
+  return qqq_decode_attn_workspace_bytes(b, h, kvh, d, window_span(max_len, window));
+}
+
+template <int VPT>
+static void window_combine(int b, hipStream_t st, const float* wo, const float* wml, const long long* pos, long long limit, int window,
+                           _Float16* o16, int8_t* xq, float* s1, int h, int d, int chunk, int splits) {
+  hipLaunchKernelGGL((qqq_window_decode_combine_kernel<VPT, DEC_COMBINE_NT>), dim3(b), dim3(DEC_COMBINE_NT), 0, st, wo, wml, pos, limit,
+                     window, o16, xq, s1, h, d, chunk, splits);
+}
+
+static int decode_attn_window_launch(bool kv8, dim3 grid, dim3 block, hipStream_t st, const _Float16* qp, const void* k_pool,
+                                     const void* v_pool, const void* k_scale, const void* v_scale, const int* tp, int table_stride,
+                                     const long long* pp, long long limit, int window, float scale_log2, float* wo, float* wml, void* o_fp16,
+                                     void* xq, void* s1, int b, int h, int kvh, int d, int num_blocks, int lbs, int chunk, int splits) {
+  if (kv8) {
+    const int8_t *kp = static_cast<const int8_t*>(k_pool), *vp = static_cast<const int8_t*>(v_pool);
+    const float *ksp = static_cast<const float*>(k_scale), *vsp = static_cast<const float*>(v_scale);
+    if (d == 64)
+      hipLaunchKernelGGL((qqq_window_kv8_decode_split_kernel<64>), grid, block, 0, st, qp, kp, vp, ksp, vsp, tp, table_stride, pp, limit,
+                         window, scale_log2, wo, wml, h, kvh, num_blocks, lbs, chunk, splits);
+    else
+      hipLaunchKernelGGL((qqq_window_kv8_decode_split_kernel<128>), grid, block, 0, st, qp, kp, vp, ksp, vsp, tp, table_stride, pp, limit,
+                         window, scale_log2, wo, wml, h, kvh, num_blocks, lbs, chunk, splits);
+  } else {
+    const _Float16 *kp = static_cast<const _Float16*>(k_pool), *vp = static_cast<const _Float16*>(v_pool);
+    if (d == 64)
+      hipLaunchKernelGGL((qqq_window_decode_split_kernel<64>), grid, block, 0, st, qp, kp, vp, tp, table_stride, pp, limit, window,
+                         scale_log2, wo, wml, h, kvh, num_blocks, lbs, chunk, splits);
+    else
+      hipLaunchKernelGGL((qqq_window_decode_split_kernel<128>), grid, block, 0, st, qp, kp, vp, tp, table_stride, pp, limit, window,
+                         scale_log2, wo, wml, h, kvh, num_blocks, lbs, chunk, splits);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, kv8 ? "qqq_window_kv8_decode_split_kernel launch" : "qqq_window_decode_split_kernel launch");
+  _Float16* o16 = static_cast<_Float16*>(o_fp16);
+  int8_t* xqp = static_cast<int8_t*>(xq);
+  float* s1p = static_cast<float*>(s1);
+  const int nvec = h * d / 8;
+  if (nvec <= DEC_COMBINE_NT)
+    window_combine<1>(b, st, wo, wml, pp, limit, window, o16, xqp, s1p, h, d, chunk, splits);
+  else if (nvec <= 2 * DEC_COMBINE_NT)
+    window_combine<2>(b, st, wo, wml, pp, limit, window, o16, xqp, s1p, h, d, chunk, splits);
+  else
+    window_combine<4>(b, st, wo, wml, pp, limit, window, o16, xqp, s1p, h, d, chunk, splits);
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail_hip(e, "qqq_window_decode_combine_kernel launch");
+  return QQQ_OK;
+}
+
 static int decode_attn_paged(const char* name, bool kv8, const void* q, const void* k_pool, const void* v_pool, const void* k_scale,
                              const void* v_scale, const void* block_table, int table_stride, const void* pos, float scale, void* o_fp16,
                              void* xq, void* s1, void* workspace, size_t workspace_bytes, int b, int h, int kvh, int d, int num_blocks,
-                             int block_size, int max_len, int dev, void* stream) {
+                             int block_size, int max_len, int dev, void* stream, int window = WINDOW_NONE) {
   g_err[0] = 0;
   if (b < 0 || h < 0 || kvh < 0 || d < 0 || num_blocks < 0 || block_size < 0 || table_stride < 0 || max_len < 0) {
     snprintf(g_err, sizeof(g_err), "%s: negative size (b=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_stride=%d max_len=%d)", name,
              b, h, kvh, d, num_blocks, block_size, table_stride, max_len);
     return QQQ_ERR_ARG;
   }
+  if (window != WINDOW_NONE && window < 1) return window_error(name);
   if (b == 0) return QQQ_OK;
   const int lbs = paged_log2_block(block_size);
   if (decode_shape_error(b, h, kvh, d, max_len) || lbs < 0 || num_blocks < 1 || (long long)num_blocks * block_size > 0x7fffffffLL ||
@@ -1006,7 +1078,8 @@ static int decode_attn_paged(const char* name, bool kv8, const void* q, const vo
              "given or both NULL; q, pools, o_fp16, workspace 16-byte, pos / xq 8-byte, block_table, s1 and the scales 4-byte aligned)", name);
     return QQQ_ERR_ARG;
   }
-  const size_t need = qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len);
+  const int span = window == WINDOW_NONE ? max_len : window_span(max_len, window);  // the keys the splits are planned over
+  const size_t need = qqq_decode_attn_workspace_bytes(b, h, kvh, d, span);
   if (workspace_bytes < need) {
     snprintf(g_err, sizeof(g_err), "%s: workspace of %zu bytes, need %zu", name, workspace_bytes, need);
     return QQQ_ERR_ARG;
@@ -1014,7 +1087,7 @@ static int decode_attn_paged(const char* name, bool kv8, const void* q, const vo
   DeviceGuard guard(dev);
   hipStream_t st = static_cast<hipStream_t>(stream);
   int splits, chunk;
-  decode_split_plan(dev, b, kvh, max_len, &splits, &chunk);
+  decode_split_plan(dev, b, kvh, span, &splits, &chunk);
   float* wo = static_cast<float*>(workspace);
   float* wml = wo + (size_t)b * h * splits * d;
   const long long* pp = static_cast<const long long*>(pos);
@@ -1023,6 +1096,10 @@ static int decode_attn_paged(const char* name, bool kv8, const void* q, const vo
   const _Float16* qp = static_cast<const _Float16*>(q);
   const int* tp = static_cast<const int*>(block_table);
   const dim3 grid(splits, kvh, b), block(DEC_WAVES * 64);
+  if (window != WINDOW_NONE)  // the windowed pair of launches (qqq_window.hip.h): every row places the splits at its own window
+    return decode_attn_window_launch(kv8, grid, block, st, qp, k_pool, v_pool, k_scale, v_scale, tp, table_stride, pp, limit,
+                                     window < max_len ? window : max_len, scale_log2, wo, wml, o_fp16, xq, s1, b, h, kvh, d, num_blocks, lbs,
+                                     chunk, splits);
   if (kv8) {
     const int8_t *kp = static_cast<const int8_t*>(k_pool), *vp = static_cast<const int8_t*>(v_pool);
     const float *ksp = static_cast<const float*>(k_scale), *vsp = static_cast<const float*>(v_scale);
@@ -1059,6 +1136,25 @@ extern "C" int qqq_decode_attn_paged_kv8(const void* q, const void* k_pool, cons
                                          int block_size, int max_len, int dev, void* stream) {
   return decode_attn_paged("qqq_decode_attn_paged_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, pos, scale,
                            o_fp16, xq, s1, workspace, workspace_bytes, b, h, kvh, d, num_blocks, block_size, max_len, dev, stream);
+}
+
+extern "C" int qqq_decode_attn_paged_window(const void* q, const void* k_pool, const void* v_pool, const void* block_table, int table_stride,
+                                            const void* pos, float scale, void* o_fp16, void* xq, void* s1, void* workspace,
+                                            size_t workspace_bytes, int b, int h, int kvh, int d, int num_blocks, int block_size,
+                                            int max_len, int window, int dev, void* stream) {
+  return decode_attn_paged("qqq_decode_attn_paged_window", false, q, k_pool, v_pool, nullptr, nullptr, block_table, table_stride, pos, scale,
+                           o_fp16, xq, s1, workspace, workspace_bytes, b, h, kvh, d, num_blocks, block_size, max_len, dev, stream,
+                           window < 1 ? -1 : window);
+}
+
+extern "C" int qqq_decode_attn_paged_window_kv8(const void* q, const void* k_pool, const void* v_pool, const void* k_scale,
+                                                const void* v_scale, const void* block_table, int table_stride, const void* pos,
+                                                float scale, void* o_fp16, void* xq, void* s1, void* workspace, size_t workspace_bytes,
+                                                int b, int h, int kvh, int d, int num_blocks, int block_size, int max_len, int window,
+                                                int dev, void* stream) {
+  return decode_attn_paged("qqq_decode_attn_paged_window_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, pos,
+                           scale, o_fp16, xq, s1, workspace, workspace_bytes, b, h, kvh, d, num_blocks, block_size, max_len, dev, stream,
+                           window < 1 ? -1 : window);
 }
 
 // ---- the verify chunk's attention (include/qqq_amd_verify.h; kernels in qqq_verify.hip.h): decode_attn_paged's two launches for t tokens
@@ -1330,13 +1426,15 @@ static void prefill_quant(int m, hipStream_t st, const _Float16* o16, const int*
 static int prefill_attn_paged(const char* name, bool kv8, const void* q, const void* k_pool, const void* v_pool, const void* k_scale,
                               const void* v_scale, const void* block_table, int table_stride, const void* cu_tokens, const void* start_pos,
                               float scale, void* o_fp16, void* xq, void* s1, void* workspace, size_t workspace_bytes, int m, int b, int h,
-                              int kvh, int d, int num_blocks, int block_size, int max_len, int dev, void* stream) {
+                              int kvh, int d, int num_blocks, int block_size, int max_len, int dev, void* stream,
+                              int window = WINDOW_NONE) {
   g_err[0] = 0;
   if (m < 0 || b < 0 || h < 0 || kvh < 0 || d < 0 || num_blocks < 0 || block_size < 0 || table_stride < 0 || max_len < 0) {
     snprintf(g_err, sizeof(g_err), "%s: negative size (m=%d b=%d h=%d kvh=%d d=%d num_blocks=%d block_size=%d table_stride=%d max_len=%d)",
              name, m, b, h, kvh, d, num_blocks, block_size, table_stride, max_len);
     return QQQ_ERR_ARG;
   }
+  if (window != WINDOW_NONE && window < 1) return window_error(name);
   if (m == 0 || b == 0) return QQQ_OK;
   const int lbs = paged_log2_block(block_size);
   if (prefill_shape_error(h, kvh, d) || b > 65535 || lbs < 0 || num_blocks < 1 || (long long)num_blocks * block_size > 0x7fffffffLL ||
@@ -1379,7 +1477,18 @@ static int prefill_attn_paged(const char* name, bool kv8, const void* q, const v
   const int* cup = static_cast<const int*>(cu_tokens);
   const long long* spp = static_cast<const long long*>(start_pos);
   _Float16* o16 = static_cast<_Float16*>(o_fp16 ? o_fp16 : workspace);
-  if (kv8) {
+  if (window != WINDOW_NONE) {  // the windowed attention launch (qqq_window.hip.h): the same grid, tiles walked from the window's first
+    const int wn = window < max_len ? window : max_len;
+#define QQQ_WINDOW_PREFILL(D, KV8)                                                                                                       \
+  hipLaunchKernelGGL((qqq_window_prefill_attn_kernel<D, KV8>), grid, block, 0, st, qp, k_pool, v_pool, ksp, vsp, tp, table_stride, cup, spp, \
+                     limit, wn, scale_log2, o16, m, b, h, kvh, num_blocks, lbs, nslots)
+    if (kv8) {
+      if (d == 64) QQQ_WINDOW_PREFILL(64, true); else QQQ_WINDOW_PREFILL(128, true);
+    } else {
+      if (d == 64) QQQ_WINDOW_PREFILL(64, false); else QQQ_WINDOW_PREFILL(128, false);
+    }
+#undef QQQ_WINDOW_PREFILL
+  } else if (kv8) {
     if (d == 64)
       hipLaunchKernelGGL((qqq_prefill_attn_kernel<64, true>), grid, block, 0, st, qp, k_pool, v_pool, ksp, vsp, tp, table_stride, cup, spp,
                          limit, scale_log2, o16, m, b, h, kvh, num_blocks, lbs, nslots);
@@ -1395,7 +1504,7 @@ static int prefill_attn_paged(const char* name, bool kv8, const void* q, const v
                          limit, scale_log2, o16, m, b, h, kvh, num_blocks, lbs, nslots);
   }
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail_hip(e, "qqq_prefill_attn_kernel launch");
+  if (e != hipSuccess) return fail_hip(e, window != WINDOW_NONE ? "qqq_window_prefill_attn_kernel launch" : "qqq_prefill_attn_kernel launch");
   if (!xq) return QQQ_OK;
   int8_t* xqp = static_cast<int8_t*>(xq);
   float* s1p = static_cast<float*>(s1);
@@ -1427,6 +1536,25 @@ extern "C" int qqq_prefill_attn_paged_kv8(const void* q, const void* k_pool, con
   return prefill_attn_paged("qqq_prefill_attn_paged_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride, cu_tokens,
                             start_pos, scale, o_fp16, xq, s1, workspace, workspace_bytes, m, b, h, kvh, d, num_blocks, block_size, max_len,
                             dev, stream);
+}
+
+extern "C" int qqq_prefill_attn_paged_window(const void* q, const void* k_pool, const void* v_pool, const void* block_table,
+                                             int table_stride, const void* cu_tokens, const void* start_pos, float scale, void* o_fp16,
+                                             void* xq, void* s1, void* workspace, size_t workspace_bytes, int m, int b, int h, int kvh, int d,
+                                             int num_blocks, int block_size, int max_len, int window, int dev, void* stream) {
+  return prefill_attn_paged("qqq_prefill_attn_paged_window", false, q, k_pool, v_pool, nullptr, nullptr, block_table, table_stride,
+                            cu_tokens, start_pos, scale, o_fp16, xq, s1, workspace, workspace_bytes, m, b, h, kvh, d, num_blocks, block_size,
+                            max_len, dev, stream, window < 1 ? -1 : window);
+}
+
+extern "C" int qqq_prefill_attn_paged_window_kv8(const void* q, const void* k_pool, const void* v_pool, const void* k_scale,
+                                                 const void* v_scale, const void* block_table, int table_stride, const void* cu_tokens,
+                                                 const void* start_pos, float scale, void* o_fp16, void* xq, void* s1, void* workspace,
+                                                 size_t workspace_bytes, int m, int b, int h, int kvh, int d, int num_blocks,
+                                                 int block_size, int max_len, int window, int dev, void* stream) {
+  return prefill_attn_paged("qqq_prefill_attn_paged_window_kv8", true, q, k_pool, v_pool, k_scale, v_scale, block_table, table_stride,
+                            cu_tokens, start_pos, scale, o_fp16, xq, s1, workspace, workspace_bytes, m, b, h, kvh, d, num_blocks, block_size,
+                            max_len, dev, stream, window < 1 ? -1 : window);
 }
 
 // ---- the fused token sampler (include/qqq_amd_sample.h; kernel in qqq_sample.hip.h): one launch, one workgroup per row, no workspace.

@@ -50,10 +50,12 @@ class QuantLlamaModel(nn.Module):
         self.norm = QuantRMSNorm(hidden, eps=rms_norm_eps)
 
     @classmethod
-    def from_config(cls, config, group_size: int):
+    def from_config(cls, config, group_size: int, sliding_window: bool = False):
         """The model of a transformers LlamaConfig or Qwen2Config (duck-typed, as QuantLlamaDecoderLayer.from_config, whose refusals
-        propagate)."""
-        layers = [QuantLlamaDecoderLayer.from_config(config, group_size, layer_idx=i) for i in range(config.num_hidden_layers)]
+        propagate).  sliding_window=True: the window layers of a Mistral, Mixtral, Qwen2 or Qwen3 config run the windowed attention
+        kernels (QuantLlamaDecoderLayer.from_config); without it a config's window is refused or, for `mistral`, ignored, as before."""
+        layers = [QuantLlamaDecoderLayer.from_config(config, group_size, layer_idx=i, sliding_window=sliding_window)
+                  for i in range(config.num_hidden_layers)]
         heads = config.num_attention_heads
         return cls(config.vocab_size, config.num_hidden_layers, config.hidden_size, heads, getattr(config, "num_key_value_heads", None) or heads,
                    config.intermediate_size, group_size, rms_norm_eps=config.rms_norm_eps, padding_idx=getattr(config, "pad_token_id", None),
@@ -145,12 +147,22 @@ class QuantLlamaForCausalLM(nn.Module):
         self.vocab_size = model.vocab_size
         self.lm_head = nn.Linear(model.hidden_size, model.vocab_size, bias=False, dtype=torch.float16)
         self.lm_head.weight.requires_grad_(False)
+        self.release_blocks = True  # generate()'s host path: give back blocks behind the window of an all-window model (release_window())
         if tie_word_embeddings:
             self.lm_head.weight = self.model.embed_tokens.weight
 
     @classmethod
-    def from_config(cls, config, group_size: int):
-        return cls(QuantLlamaModel.from_config(config, group_size), tie_word_embeddings=bool(getattr(config, "tie_word_embeddings", False)))
+    def from_config(cls, config, group_size: int, sliding_window: bool = False):
+        """QuantLlamaModel.from_config's arguments; `sliding_window` opts in to the windowed attention kernels."""
+        return cls(QuantLlamaModel.from_config(config, group_size, sliding_window=sliding_window),
+                   tie_word_embeddings=bool(getattr(config, "tie_word_embeddings", False)))
+
+    def release_window(self) -> Optional[int]:
+        """The largest sliding window of the layers if EVERY layer is windowed (Mistral, Mixtral), else None: keys more than that far
+        behind a sequence's end are read by no layer, so the host generate path gives their blocks back (PagedKVCache.release_before).
+        A model with any full-attention layer releases nothing."""
+        windows = [layer.self_attn.sliding_window for layer in self.model.layers]
+        return max(windows) if windows and all(w is not None for w in windows) else None
 
     def fuse_decode(self):
         self.model.fuse_decode()
@@ -212,6 +224,10 @@ class QuantLlamaForCausalLM(nn.Module):
         running sequences may still take, so the pool never runs out mid-sequence; when it cannot hold all prompts at once the rest wait,
         in order, for blocks to come free.  Newly admitted prompts are prefilled in one packed step of their own and the running rows
         decode in another: a sequence's tokens do not depend on what else was in the batch.  The random draws do: one torch.rand per pass.
+        A model whose every layer has a sliding window (release_window(): Mistral, Mixtral built with sliding_window=True) gives the
+        blocks wholly behind the window back after every pass (PagedKVCache.release_before(seq, length - window)); the tokens are the
+        same with `self.release_blocks = False`.  Admission still counts a prompt's whole budget.  The device loops reserve their
+        whole budget up front and release nothing.
 
         device_loop=True hands the prompts to a DecodeLoop (qqq_amd/serve.py) of min(len(prompts), 64) rows, sized for the longest budget
         rounded up to a block: the decode steps replay from one captured graph and the host syncs once per several tokens.  Greedy tokens
@@ -316,6 +332,11 @@ class QuantLlamaForCausalLM(nn.Module):
         waiting, running = deque(range(len(prompts))), []  # prompts that wait; siblings that run (i * n + j)
         cur = None  # int64 [len(running)] on the device: the running sequences' last tokens
         workspace = torch.zeros(len(out) * self.lm_head.weight.shape[0], dtype=torch.int32, device=dev) if req.penalised else None
+        window = self.release_window() if self.release_blocks else None  # every layer windowed: blocks behind the window go back
+
+        def release(seqs):
+            for i in seqs if window is not None else ():
+                cache.release_before(sid(i), cache.length(sid(i)) - window)
 
         def settle(seqs, toks, fork=False):
             """record a pass's tokens; -> (the sequences that go on, their tokens of the pass).  After a prefill pass with n > 1 (`fork`)
@@ -341,6 +362,7 @@ class QuantLlamaForCausalLM(nn.Module):
                     logits = self(cur, cache, req.with_adapters(step, [i // n for i in running], step.counts))
                     toks = req.sample(logits, running, workspace)
                     running, cur = settle(running, toks)
+                    release(running)
                 new = []
                 owed = sum(need[i // n] - len(cache.blocks(sid(i))) for i in running)  # what the running sequences may still take
                 while waiting and fam_need[waiting[0]] <= cache.free_blocks - owed:
@@ -359,6 +381,7 @@ class QuantLlamaForCausalLM(nn.Module):
                 logits = self(ids, cache, req.with_adapters(step, new, step.counts))
                 toks = req.sample(logits, born, workspace)
                 alive, first = settle(born, toks, fork=n > 1)
+                release(alive)
                 cur = first if not running else torch.cat([cur, first])
                 running = running + alive
         except BaseException:  # leave the caller's pool as it was found

@@ -1076,9 +1076,17 @@ def _decode_attention_paged_shapes(name, q_out, k_pool, block_table, pos, max_le
     return b, q_out.shape[1], kvh, d, nb, bs, width, max_len
 
 
-def _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, k_scale=None, v_scale=None):
+def _window_name(name, kv8, window):
+    """the op's name in messages; a windowed call (window is not None) checks its window here"""
+    if window is not None and int(window) < 1:
+        raise RuntimeError(f"{name}_window{'_kv8' if kv8 else ''}: window must be at least 1, not {window}")
+    return name + ("_window" if window is not None else "") + ("_kv8" if kv8 else "")
+
+
+def _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, k_scale=None, v_scale=None,
+                                 window=None):
     kv8 = k_scale is not None
-    name = "decode_attention_paged_kv8" if kv8 else "decode_attention_paged"
+    name = _window_name("decode_attention_paged", kv8, window)
     ts = (q_out, k_pool, v_pool, block_table, pos) + ((k_scale, v_scale) if kv8 else ())
     _same_gpu(name, ts)
     if q_out.dtype != torch.float16 or pos.dtype != torch.int64 or block_table.dtype != torch.int32:
@@ -1092,15 +1100,19 @@ def _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale,
     if b == 0:
         return xq, s1, o16
     L = _lib.lib()
-    nbytes = L.qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len)
+    if window is None:
+        nbytes, win, fn = L.qqq_decode_attn_workspace_bytes(b, h, kvh, d, max_len), (), "qqq_decode_attn_paged"
+    else:  # the windowed entries (include/qqq_amd_window.h): a workspace that follows the window, `window` behind max_len
+        win, fn = (min(int(window), 2 ** 31 - 1),), "qqq_decode_attn_paged_window"
+        nbytes = L.qqq_decode_attn_window_workspace_bytes(b, h, kvh, d, max_len, *win)
     ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)  # torch's allocator: also under stream / graph capture
     q2, pos, table = q_out.contiguous(), pos.contiguous(), block_table.contiguous()
     tail = (_ptr(table), width, _ptr(pos), float(scale), _ptr(o16), _ptr(xq), _ptr(s1), _ptr(ws), ws.numel(), b, h, kvh, d, nb, bs, max_len,
-            dev.index or 0, _stream_for(q_out))
+            *win, dev.index or 0, _stream_for(q_out))
     if kv8:
-        err = L.qqq_decode_attn_paged_kv8(_ptr(q2), _ptr(k_pool), _ptr(v_pool), _ptr(k_scale), _ptr(v_scale), *tail)
+        err = getattr(L, fn + "_kv8")(_ptr(q2), _ptr(k_pool), _ptr(v_pool), _ptr(k_scale), _ptr(v_scale), *tail)
     else:
-        err = L.qqq_decode_attn_paged(_ptr(q2), _ptr(k_pool), _ptr(v_pool), *tail)
+        err = getattr(L, fn)(_ptr(q2), _ptr(k_pool), _ptr(v_pool), *tail)
     _raise_lib(name, err)
     return xq, s1, o16
 
@@ -1163,6 +1175,68 @@ def decode_attention_paged_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool
     else:
         out = _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, k_scale, v_scale)
     return out if return_fp16 else out[:2]
+
+
+# ---- sliding-window attention (include/qqq_amd_window.h): the paged decode and prefill ops with a band mask -- a query at position i
+# attends the `window` keys max(0, i - window + 1) ... i -- and a split of the work that follows the window, not the context.
+
+@torch.library.custom_op("qqq_amd::decode_attn_paged_window", mutates_args=())
+def _decode_attn_paged_window_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                                 pos: torch.Tensor, scale: float, window: int, max_len: Optional[int],
+                                 return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, window=window)
+
+
+@_decode_attn_paged_window_op.register_fake
+def _(q_out, k_pool, v_pool, block_table, pos, scale, window, max_len, return_fp16):
+    return _decode_paged_fake(_window_name("decode_attention_paged", False, window), q_out, k_pool, block_table, pos, max_len, return_fp16)
+
+
+def decode_attention_paged_window(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                                  pos: torch.Tensor, scale: float, window: int, max_len: Optional[int] = None, return_fp16: bool = False):
+    """decode_attention_paged of a sliding-window layer: row bi attends keys max(0, pos[bi] - window + 1) ... pos[bi], the `window` last
+    ones.  Every other argument, the outputs and the arithmetic are decode_attention_paged's; with window >= max_len so are the bits.
+
+    The keys are split over min(max_len, window rounded up) keys, each row's splits placed at its own window: the grid, the workspace
+    and the time follow the window, not the context.  Only the table entries of the blocks that hold a row's window are read, and no
+    key in front of it: blocks wholly behind a window may have gone back to the pool (PagedKVCache.release_before).  The launch sizes
+    depend on the shapes, max_len and window alone, so a captured graph replays at other positions."""
+    if _compiling(q_out, k_pool, v_pool, block_table, pos):
+        out = _decode_attn_paged_window_op(q_out, k_pool, v_pool, block_table, pos, scale, window, max_len, return_fp16)
+    else:
+        out = _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, window=window)
+    return out if return_fp16 else out[:2]
+
+
+@torch.library.custom_op("qqq_amd::decode_attn_paged_window_kv8", mutates_args=())
+def _decode_attn_paged_window_kv8_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor,
+                                     v_scale: torch.Tensor, block_table: torch.Tensor, pos: torch.Tensor, scale: float, window: int,
+                                     max_len: Optional[int], return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, k_scale, v_scale, window)
+
+
+@_decode_attn_paged_window_kv8_op.register_fake
+def _(q_out, k_pool, v_pool, k_scale, v_scale, block_table, pos, scale, window, max_len, return_fp16):
+    return _decode_paged_fake(_window_name("decode_attention_paged", True, window), q_out, k_pool, block_table, pos, max_len, return_fp16)
+
+
+def decode_attention_paged_window_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor,
+                                      v_scale: torch.Tensor, block_table: torch.Tensor, pos: torch.Tensor, scale: float, window: int,
+                                      max_len: Optional[int] = None, return_fp16: bool = False):
+    """decode_attention_paged_window over an int8 pool with decode_attention_paged_kv8's arithmetic."""
+    if _compiling(q_out, k_pool, v_pool, k_scale, v_scale, block_table, pos):
+        out = _decode_attn_paged_window_kv8_op(q_out, k_pool, v_pool, k_scale, v_scale, block_table, pos, scale, window, max_len, return_fp16)
+    else:
+        out = _decode_attention_paged_impl(q_out, k_pool, v_pool, block_table, pos, scale, max_len, return_fp16, k_scale, v_scale, window)
+    return out if return_fp16 else out[:2]
+
+
+def decode_attention_window_plan(b: int, h: int, kvh: int, max_len: int, window: int):
+    """(splits, chunk) of a decode_attention_paged_window call on the current device: a row at position p, lo = max(0, p - window + 1),
+    base = lo rounded down to 128, has split s cover keys base + s * chunk ... base + (s + 1) * chunk - 1 of lo ... p.  It is the
+    unwindowed plan (decode_attention_shared_plan with pack 1) over the span the workspace is sized for."""
+    span = min(int(max_len), (int(window) + 254) // 128 * 128)
+    return decode_attention_shared_plan(b, h, kvh, span, 1)
 
 
 # ---- the decode attention of sibling rows over a shared prefix (include/qqq_amd_shared.h): the n completions of one prompt read the
@@ -1311,9 +1385,9 @@ def _prefill_attention_paged_shapes(name, q_out, k_pool, block_table, cu_tokens,
 
 
 def _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16, k_scale=None,
-                                  v_scale=None):
+                                  v_scale=None, window=None):
     kv8 = k_scale is not None
-    name = "prefill_attention_paged_kv8" if kv8 else "prefill_attention_paged"
+    name = _window_name("prefill_attention_paged", kv8, window)
     ts = (q_out, k_pool, v_pool, block_table, cu_tokens, start_pos) + ((k_scale, v_scale) if kv8 else ())
     _same_gpu(name, ts)
     if q_out.dtype != torch.float16 or start_pos.dtype != torch.int64 or block_table.dtype != torch.int32 or cu_tokens.dtype != torch.int32:
@@ -1330,12 +1404,13 @@ def _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens,
     nbytes = 0 if return_fp16 else L.qqq_prefill_attn_workspace_bytes(m, h, d)
     ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)  # torch's allocator: also under stream / graph capture
     q2, table, cu, sp = q_out.contiguous(), block_table.contiguous(), cu_tokens.contiguous(), start_pos.contiguous()
+    win, fn = ((), "qqq_prefill_attn_paged") if window is None else ((min(int(window), 2 ** 31 - 1),), "qqq_prefill_attn_paged_window")
     tail = (_ptr(table), width, _ptr(cu), _ptr(sp), float(scale), _ptr(o16), _ptr(xq), _ptr(s1), _ptr(ws), ws.numel(), m, b, h, kvh, d, nb,
-            bs, max_len, dev.index or 0, _stream_for(q_out))
+            bs, max_len, *win, dev.index or 0, _stream_for(q_out))
     if kv8:
-        err = L.qqq_prefill_attn_paged_kv8(_ptr(q2), _ptr(k_pool), _ptr(v_pool), _ptr(k_scale), _ptr(v_scale), *tail)
+        err = getattr(L, fn + "_kv8")(_ptr(q2), _ptr(k_pool), _ptr(v_pool), _ptr(k_scale), _ptr(v_scale), *tail)
     else:
-        err = L.qqq_prefill_attn_paged(_ptr(q2), _ptr(k_pool), _ptr(v_pool), *tail)
+        err = getattr(L, fn)(_ptr(q2), _ptr(k_pool), _ptr(v_pool), *tail)
     _raise_lib(name, err)
     return xq, s1, o16
 
@@ -1404,6 +1479,62 @@ def prefill_attention_paged_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_poo
     else:
         out = _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16, k_scale,
                                             v_scale)
+    return out if return_fp16 else out[:2]
+
+
+@torch.library.custom_op("qqq_amd::prefill_attn_paged_window", mutates_args=())
+def _prefill_attn_paged_window_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                                  cu_tokens: torch.Tensor, start_pos: torch.Tensor, scale: float, window: int, max_len: Optional[int],
+                                  return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16, window=window)
+
+
+@_prefill_attn_paged_window_op.register_fake
+def _(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, window, max_len, return_fp16):
+    return _prefill_paged_fake(_window_name("prefill_attention_paged", False, window), q_out, k_pool, block_table, cu_tokens, start_pos,
+                               max_len, return_fp16)
+
+
+def prefill_attention_paged_window(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, block_table: torch.Tensor,
+                                   cu_tokens: torch.Tensor, start_pos: torch.Tensor, scale: float, window: int,
+                                   max_len: Optional[int] = None, return_fp16: bool = False):
+    """prefill_attention_paged of a sliding-window layer (sliding-window attention, include/qqq_amd_window.h): a token at position p
+    attends keys max(0, p - window + 1) ... p.  Every other argument, the outputs and the arithmetic are prefill_attention_paged's;
+    with window >= max_len so are the bits.  A query tile walks its keys from the window of its first token: what lies in front is
+    neither loaded nor are its table entries read."""
+    if _compiling(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos):
+        out = _prefill_attn_paged_window_op(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, window, max_len, return_fp16)
+    else:
+        out = _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16,
+                                            window=window)
+    return out if return_fp16 else out[:2]
+
+
+@torch.library.custom_op("qqq_amd::prefill_attn_paged_window_kv8", mutates_args=())
+def _prefill_attn_paged_window_kv8_op(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor,
+                                      v_scale: torch.Tensor, block_table: torch.Tensor, cu_tokens: torch.Tensor, start_pos: torch.Tensor,
+                                      scale: float, window: int, max_len: Optional[int],
+                                      return_fp16: bool) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    return _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16, k_scale,
+                                         v_scale, window)
+
+
+@_prefill_attn_paged_window_kv8_op.register_fake
+def _(q_out, k_pool, v_pool, k_scale, v_scale, block_table, cu_tokens, start_pos, scale, window, max_len, return_fp16):
+    return _prefill_paged_fake(_window_name("prefill_attention_paged", True, window), q_out, k_pool, block_table, cu_tokens, start_pos,
+                               max_len, return_fp16)
+
+
+def prefill_attention_paged_window_kv8(q_out: torch.Tensor, k_pool: torch.Tensor, v_pool: torch.Tensor, k_scale: torch.Tensor,
+                                       v_scale: torch.Tensor, block_table: torch.Tensor, cu_tokens: torch.Tensor, start_pos: torch.Tensor,
+                                       scale: float, window: int, max_len: Optional[int] = None, return_fp16: bool = False):
+    """prefill_attention_paged_window over an int8 pool with prefill_attention_paged_kv8's arithmetic."""
+    if _compiling(q_out, k_pool, v_pool, k_scale, v_scale, block_table, cu_tokens, start_pos):
+        out = _prefill_attn_paged_window_kv8_op(q_out, k_pool, v_pool, k_scale, v_scale, block_table, cu_tokens, start_pos, scale, window,
+                                                max_len, return_fp16)
+    else:
+        out = _prefill_attention_paged_impl(q_out, k_pool, v_pool, block_table, cu_tokens, start_pos, scale, max_len, return_fp16, k_scale,
+                                            v_scale, window)
     return out if return_fp16 else out[:2]
 
 

@@ -4,7 +4,7 @@ prefill_attention_paged and their _kv8 forms).
 
     PagedKVCache   k[layer], v[layer] of shape [num_blocks, num_kv_heads, block_size, head_dim] (fp16 or int8; an int8 pool with
                    k_scale[layer], v_scale[layer] [num_blocks, num_kv_heads, block_size]); add / fork / reorder / free / reserve / step /
-                   advance / gather
+                   advance / release_before / gather
     PagedStep      what one forward pass over a packed batch of sequences needs, built once on the host and shared by all layers
 
 Sequences arrive and finish at different times, have different lengths, and a finished sequence's blocks serve the next one.  The allocator
@@ -52,6 +52,9 @@ class PagedStep:
     shared: Optional[torch.Tensor] = None
     family_max: Optional[int] = None
     lora: Optional[object] = None
+
+
+RELEASED = -1  # an entry of a sequence's block list whose block release_before() gave back
 
 
 class _Family:
@@ -143,7 +146,8 @@ class PagedKVCache:
             raise RuntimeError("PagedKVCache.fork: the pool is exhausted (1 block needed, 0 free)")
         mine = self._blocks[src][:full]
         for blk in mine:
-            self._refs[blk] += 1
+            if blk != RELEASED:
+                self._refs[blk] += 1
         if n % bs:
             old, new = self._blocks[src][full], self._take()
             pools = self.k + self.v + ((self.k_scale + self.v_scale) if self.quantized else [])
@@ -203,7 +207,8 @@ class PagedKVCache:
         refs = {}
         for i in unchosen:
             for blk in self._blocks[seq_ids[i]]:
-                refs[blk] = refs.get(blk, self._refs[blk]) - 1
+                if blk != RELEASED:
+                    refs[blk] = refs.get(blk, self._refs[blk]) - 1
         released = sum(1 for r in refs.values() if r == 0)
         fresh = sum(len(t) - 1 for j, t in takers.items() if self._len[seq_ids[j]] % bs)
         if fresh > len(self._free) + released:
@@ -220,7 +225,8 @@ class PagedKVCache:
                 else:
                     mine = blocks[:full]
                     for blk in mine:
-                        self._refs[blk] += 1
+                        if blk != RELEASED:
+                            self._refs[blk] += 1
                     if part:
                         mine.append(self._take())
                         src.append(blocks[full])
@@ -257,15 +263,35 @@ class PagedKVCache:
         """The leading keys, a multiple of block_size, that the sequence has in common with its family (0 without a fork)."""
         return self._shared[seq_id]
 
+    def release_before(self, seq_id, first_key: int) -> int:
+        """Give back every block of the sequence that lies wholly below key `first_key` -- the blocks behind the sliding window of a
+        model whose every layer is windowed, which no kernel reads again (include/qqq_amd_window.h) -- and return how many this call
+        released.  A block that fork() or reorder() shared goes back to the free list only with its last owner.  The sequence's
+        length, its positions and its later blocks are unchanged; a released entry of its block list is RELEASED (-1), step() writes
+        it into the block table as 0, gather() of a range that holds one raises, and fork() / reorder() hand the holes on."""
+        if seq_id not in self._blocks:
+            raise KeyError(f"PagedKVCache.release_before: no sequence {seq_id!r}")
+        mine, gone = self._blocks[seq_id], 0
+        for i in range(min(max(int(first_key), 0) // self.block_size, len(mine))):
+            if mine[i] != RELEASED:
+                self._drop(mine[i])
+                mine[i], gone = RELEASED, gone + 1
+        return gone
+
+    def _drop(self, blk: int) -> None:
+        """one owner less; the last one sends the block to the free list"""
+        self._refs[blk] -= 1
+        if self._refs[blk] == 0:
+            self._free.append(blk)
+
     def free(self, seq_id) -> None:
         """Drop a sequence; its blocks go back to the free list (the last one it took is the first to go out again), a shared block only
         with its last owner."""
         if seq_id not in self._blocks:
             raise KeyError(f"PagedKVCache.free: no sequence {seq_id!r}")
         for blk in self._blocks.pop(seq_id):
-            self._refs[blk] -= 1
-            if self._refs[blk] == 0:
-                self._free.append(blk)
+            if blk != RELEASED:
+                self._drop(blk)
         del self._len[seq_id], self._root[seq_id], self._shared[seq_id]
 
     def length(self, seq_id) -> int:
@@ -325,7 +351,7 @@ class PagedKVCache:
                 slots.append(mine[p // bs] * bs + p % bs)
             self._len[sid] = start + c
         width = max(len(self._blocks[sid]) for sid in seq_ids)
-        table = [self._blocks[sid] + [0] * (width - len(self._blocks[sid])) for sid in seq_ids]
+        table = [[max(blk, 0) for blk in self._blocks[sid]] + [0] * (width - len(self._blocks[sid])) for sid in seq_ids]  # RELEASED: 0
         last = [self._len[sid] - 1 for sid in seq_ids]
         dev = self.device
         cu = [0]
@@ -364,6 +390,8 @@ class PagedKVCache:
         if n < 0 or n > self._len[seq_id]:
             raise ValueError(f"PagedKVCache.gather: length {n} outside the sequence's {self._len[seq_id]} keys")
         nblk = -(-n // self.block_size)
+        if RELEASED in self._blocks[seq_id][:nblk]:
+            raise ValueError("PagedKVCache.gather: the range holds blocks that release_before() gave back")
         idx = torch.tensor(self._blocks[seq_id][:nblk], dtype=torch.int64, device=self.k[layer].device)
         out = []
         for pool, scales in ((self.k[layer], self.k_scale[layer] if self.quantized else None),

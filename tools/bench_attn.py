@@ -46,6 +46,10 @@ KV cache.  Both paths start from the fp16 output of input_layernorm and end with
                 where the medians differ by more than the baseline's spread over the rounds.  The split plan of the call and the number of
                 jointly taken splits are written too.
 
+    window      (--points window [--kv8] [--block-size N]: this mode alone) sliding-window attention against the unwindowed paged ops on the
+                same pools, ops alone: decode_attention_paged_window and prefill_attention_paged_window (a 512-token chunk) with Mistral-7B /
+                Mixtral heads (32 / 8, d 128) and W = 4096 at contexts 4096, 16384 and 65536, batches 1 and 8.  Five alternations of the four
+                ops per point; a windowed op "loses" a point when its median is above the plain op's by more than the plain op's spread.
     qknorm      (--points qknorm [--block-size N]: this mode alone) the RoPE / cache-write launch of a Qwen3 layer alone, three ways over
                 the same fused q|k|v buffer, positions, slots and pool: rope_qkv_norm_paged(_kv8) (`fused`: the per-head q / k RMSNorm
                 inside the launch), the torch composition (`composed`: Qwen3RMSNorm's lines on the q and k views, then
@@ -64,6 +68,7 @@ where point i starts in a kernel trace.
     python tools/bench_attn.py --points verify [--kv8] [--block-size N] [--out profiles/verify_attn_bench.json]   -> the verify points alone
     python tools/bench_attn.py --points shared [--kv8] [--block-size N] [--out profiles/shared_attn_bench.json]   -> the shared points alone
     python tools/bench_attn.py --points qknorm [--block-size N] [--out profiles/qknorm_bench.json]   -> the q / k norm points alone
+    python tools/bench_attn.py --points window [--kv8] [--block-size N] [--out profiles/window_attn_bench.json]   -> the window points alone
     python tools/bench_attn.py --summarize TRACE_DIR [--bench FILE]     -> from a rocprofv3 --kernel-trace run of the above: the
                                                                           qqq_rope_qkv_kernel times and HBM fractions, and per decode point
                                                                           (labelled from the run's JSON output FILE) the median times of
@@ -105,6 +110,8 @@ VERIFY_POOL_BYTES = 8 << 30  # K and V pools of a point together
 SHARED_ROUNDS, SHARED_COLD_CALLS = 5, 9  # --points shared: alternations of the two ops at a point; cold calls per alternation
 SHARED_FAMILIES, SHARED_PREFIXES, SHARED_TAIL = (2, 4, 8, 16), (1024, 4096, 16384), 64
 SHARED_FLUSH_BYTES = 1 << 30  # four times the 256 MB Infinity Cache
+# --points window: Mistral-7B / Mixtral heads, their window, contexts at and beyond it; alternations of the four ops at a point
+WINDOW_HEADS, WINDOW, WINDOW_CONTEXTS, WINDOW_BATCHES, WINDOW_CHUNK, WINDOW_ROUNDS = (32, 8), 4096, (4096, 16384, 65536), (1, 8), 512, 5
 QKNORM_SHAPES = {"qwen3_8b": (32, 8), "qwen3_32b": (64, 8)}  # --points qknorm: (heads, KV heads) of 128
 QKNORM_TOKENS, QKNORM_ROUNDS, QKNORM_EPS = (1, 16, 2048), 5, 1e-6
 PREFILL_KERNELS = ("qqq_prefill_attn_kernel", "qqq_prefill_quant_kernel", "qqq_paged_rope_qkv_kernel", "qqq_paged_kv8_rope_qkv_kernel",
@@ -690,6 +697,73 @@ def run_qknorm(block_size=128):
     return out
 
 
+def run_window(kv8=False, block_size=128):
+    """--points window: see the module docstring; --kv8 adds the int8 pool's points behind the fp16 pool's"""
+    out = _run_window(False, block_size)
+    if kv8:
+        more = _run_window(True, block_size)
+        out["pool"] = "fp16, then int8"
+        out["points"] += more["points"]
+    return out
+
+
+def _run_window(kv8, block_size):
+    import statistics
+
+    import torch
+
+    from bench_llama import time_fn
+    from qqq_amd import ops
+
+    dev = torch.device("cuda:0")
+    h, kvh = WINDOW_HEADS
+    out = {"tool": "tools/bench_attn.py --points window", "device": torch.cuda.get_device_name(0), "head_dim": D, "block_size": block_size,
+           "heads": h, "kv_heads": kvh, "window": WINDOW, "pool": "int8" if kv8 else "fp16", "rounds": WINDOW_ROUNDS,
+           "unit": "us per call of the attention op alone, hipGraph replay (median of a round's replays); per op the rounds, their median, "
+                   "min and max.  decode: b rows at position context - 1; prefill: one chunk of WINDOW_CHUNK tokens that ends there",
+           "points": []}
+    g = torch.Generator(device=dev).manual_seed(7)
+    sfx = "_kv8" if kv8 else ""
+    for ctx in WINDOW_CONTEXTS:
+        for b in WINDOW_BATCHES:
+            per = -(-ctx // block_size)
+            nb = b * per
+            if kv8:
+                pools = tuple(torch.randint(-127, 128, (nb, kvh, block_size, D), generator=g, device=dev, dtype=torch.int8) for _ in range(2))
+                pools += tuple(torch.rand((nb, kvh, block_size), generator=g, device=dev) * 0.02 + 0.005 for _ in range(2))
+            else:
+                pools = tuple(torch.randn((nb, kvh, block_size, D), generator=g, device=dev).half() for _ in range(2))
+            table = torch.randperm(nb, generator=torch.Generator().manual_seed(ctx + b)).to(dev).reshape(b, per).to(torch.int32)
+            last = torch.full((b,), ctx - 1, dtype=torch.int64, device=dev)
+            q1 = torch.randn((b, h, D), generator=g, device=dev).half()
+            t = min(WINDOW_CHUNK, ctx)
+            qc = torch.randn((b * t, h, D), generator=g, device=dev).half()
+            cu, start = torch.arange(b + 1, dtype=torch.int32, device=dev) * t, last - (t - 1)
+            fns = {"decode": lambda: getattr(ops, "decode_attention_paged" + sfx)(q1, *pools, table, last, D ** -0.5, max_len=ctx),
+                   "decode_window": lambda: getattr(ops, "decode_attention_paged_window" + sfx)(q1, *pools, table, last, D ** -0.5, WINDOW,
+                                                                                                 max_len=ctx),
+                   "prefill": lambda: getattr(ops, "prefill_attention_paged" + sfx)(qc, *pools, table, cu, start, D ** -0.5, max_len=ctx),
+                   "prefill_window": lambda: getattr(ops, "prefill_attention_paged_window" + sfx)(qc, *pools, table, cu, start, D ** -0.5,
+                                                                                                   WINDOW, max_len=ctx)}
+            runs = {name: [] for name in fns}
+            for _ in range(WINDOW_ROUNDS):
+                for name, fn in fns.items():
+                    runs[name].append(round(time_fn(fn), 2))
+            pt = {"pool": "int8" if kv8 else "fp16", "batch": b, "context": ctx, "chunk_tokens": t}
+            for name, v in runs.items():
+                pt[name] = {"median_us": round(statistics.median(v), 2), "min_us": min(v), "max_us": max(v), "rounds_us": v}
+            for kind in ("decode", "prefill"):  # a windowed op loses a point when its median is above the plain op's by more than its spread
+                spread = round(pt[kind]["max_us"] - pt[kind]["min_us"], 2)
+                pt[kind + "_window_over_plain"] = round(pt[kind + "_window"]["median_us"] / pt[kind]["median_us"], 3)
+                pt[kind + "_window_loses"] = bool(pt[kind + "_window"]["median_us"] > pt[kind]["median_us"] + spread)
+            out["points"].append(pt)
+            print(json.dumps(pt), file=sys.stderr, flush=True)
+            del pools
+    out["losing_points"] = [(p["pool"], p["batch"], p["context"], kind) for p in out["points"] for kind in ("decode", "prefill")
+                            if p[kind + "_window_loses"]]
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points", default="decode,prefill")
@@ -710,6 +784,8 @@ def main():
         res = run_shared(kv8=a.kv8, block_size=a.block_size)
     elif a.points == "qknorm":
         res = run_qknorm(block_size=a.block_size)
+    elif a.points == "window":
+        res = run_window(kv8=a.kv8, block_size=a.block_size)
     elif a.paged and a.points == "prefill":
         res = run_paged_prefill([int(v) for v in a.group_sizes.split(",")], kv8=a.kv8, block_size=a.block_size)
     else:
